@@ -11,6 +11,11 @@ itself over the N ranks instead, and the weak line carries that measurement as i
 block.  Started WITHOUT torchrun, `--gpus N` launches its N ranks itself (a child
 `python -m torch.distributed.run`, before this process touches a GPU) and relays their line.
 
+A plain run sets up, warms up, times `--steps` steps and prints the headline.  `--full` adds everything else the line can
+carry: HIP-event kernel timing in the timed region and the serial pass behind the rooflines, the per-step median, the
+host-to-device and bound-output variants, the other callbacks, the CPU baseline and, with several ranks, the gather and
+strong-scaling blocks.  `--dump-outputs DIR` writes what the last timed step computed (see `dump_outputs`).
+
 Prints ONE JSON line on rank 0."""
 import argparse
 import ctypes
@@ -26,6 +31,7 @@ FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X FP64 matrix peak (AMD datasheet; BASELINE
 # guide lists no f64 MFMA figure; tools/mfma_f64_rate.py measures the issue rate on the box.
 HBM_PEAK_GBS = 8000.0
 WATCHDOG_S = int(os.environ.get("DTO_BENCH_WATCHDOG_S", "240"))  # limit for the multi-rank report blocks (gather, strong scaling)
+DUMP_MAX_ENTRIES = 1 << 22  # float64 entries written by --dump-outputs over all ranks: 32 MB
 
 
 def baseline_metric():
@@ -34,6 +40,25 @@ def baseline_metric():
         return json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
     except Exception:
         return "knot-points/sec for eval_constraint_jacobian, 256-state\u00d72000-knot bilinear"
+
+
+def dump_positions(length, cap):
+    """Positions of a value vector that --dump-outputs writes: all of them up to `cap`, above it a fixed sample -- the sorted
+    distinct positions among `cap` draws from a Philox stream (seed 0), the same for every run and build at the same length."""
+    import numpy as np
+    if length <= cap:
+        return None
+    return np.unique(np.random.Generator(np.random.Philox(0)).integers(0, length, size=cap))
+
+
+def dump_outputs(dirname, name, out, cap):
+    """DIR/<name>.npy: the float64 device vector `out` the timed callback wrote, whole or at `dump_positions`."""
+    import numpy as np
+    import torch
+    pos = dump_positions(out.numel(), cap)
+    vals = out if pos is None else out[torch.from_numpy(pos).to(out.device)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), vals.cpu().numpy())
 
 
 def spawn_ranks(n_ranks, argv):
@@ -390,6 +415,13 @@ def main():
     ap.add_argument("--m", type=int, default=4, help="number of drives")
     ap.add_argument("--knots", type=int, default=2000, help="knots per GPU")
     ap.add_argument("--callback", default="jacobian", choices=["jacobian", "hessian", "constraint"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beyond the headline: kernel timing and rooflines, per-step median, "
+                         "host-to-device and bound-output variants, other callbacks, CPU baseline, gather and strong scaling. "
+                         "The --no-* switches below thin out what --full adds")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the value vector of the last timed step to DIR/<callback name>[_rank<r>].npy (float64; above "
+                         f"{DUMP_MAX_ENTRIES} entries over all ranks a fixed, seeded sample of its positions)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-callbacks", action="store_true")
     ap.add_argument("--no-bound-output", action="store_true", help="skip the bound-output report block (profiling passes: every traced call is then a default call)")
@@ -404,13 +436,17 @@ def main():
     ap.add_argument("--gather", dest="gather", action="store_true", default=None,
                     help="configs[3] data path: after the compute-only timing, time K more steps in which every rank's slab is "
                          "written into the full value vector and all-gathered in place (RCCL over xGMI); reported next to `value`. "
-                         "On by default when there is more than one rank")
+                         "On by default under --full when there is more than one rank")
     ap.add_argument("--no-gather", dest="gather", action="store_false")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --knots per GPU (configs[3] at 8 GPUs: 16000 knots); strong: --knots in total, split over the GPUs "
-                         "(the metric's own 2000-knot problem at 1, 2, 4, 8 GPUs).  The weak line also carries the strong "
-                         "measurement as its `strong_scaling` block")
+                         "(the metric's own 2000-knot problem at 1, 2, 4, 8 GPUs).  Under --full the weak line also carries the "
+                         "strong measurement as its `strong_scaling` block")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.gather and not args.full:
+        ap.error("--gather is a report block of --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not under torchrun: start the ranks ourselves, BEFORE this process makes any GPU call, and relay their line
@@ -477,7 +513,8 @@ def main():
 
     if args.serial_kernels:
         ev.set_option("overlap_sweep", 0)
-    ev.profile_enable(not args.no_kernel_timing)  # warm-up runs with the timing events on too; they are recycled by profile_reset
+    # HIP-event kernel timing feeds the --full report only; the warm-up runs with the events on too, profile_reset recycles them
+    ev.profile_enable(args.full and not args.no_kernel_timing)
     for _ in range(args.warmup):
         step()
     fence()
@@ -492,6 +529,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        name = {"jacobian": "eval_constraint_jacobian", "hessian": "eval_hessian_lagrangian"}.get(args.callback, "eval_constraint")
+        dump_outputs(args.dump_outputs, name if world == 1 else f"{name}_rank{rank}", out, DUMP_MAX_ENTRIES // world)
+    smax, terms = ev.last_stats()
+    finite = bool(torch.isfinite(out).all().item())
 
     # the dominant kernel of the callback: the propagator chain's batched GEMM (Jacobian), the adjoint generator sweep (Hessian:
     # one persistent k_sweep_fused launch, 3.7 of 5.7 ms at 256 x 2000)
@@ -537,46 +579,45 @@ def main():
                         "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS}
         return ms_g, n_g, fl_g, ms_s, n_s, fl_s, var, asm
 
-    ms_gemm, n_gemm, fl_gemm, ms_sweep, n_sweep, fl_sweep, variants, assembly = collect()
-    # In the timed region the Jacobian's generator sweep shares the chip with the chain's products (option overlap_sweep, on
-    # by default): a kernel's HIP-event duration there includes what it waited for the other stream.  The roofline of the
-    # dominant kernel is therefore taken from a SERIAL pass -- the same K steps again with overlap_sweep = 0, one kernel at
-    # a time, which is also what `rocprofv3 -- python3 bench.py --serial-kernels` shows (profiles/) -- and the timed
-    # region's own figures are reported next to it.
     overlapped = None
-    if args.callback in ("jacobian", "hessian") and not args.serial_kernels and not args.no_kernel_timing:
-        overlapped = {"avg_launch_ms": ms_gemm / max(n_gemm, 1), "launches": n_gemm,
-                      "achieved": fl_gemm / (ms_gemm * 1e-3) / 1e12 if ms_gemm > 0 else 0.0,
-                      "sweep_ms_per_step": ms_sweep / args.steps,
-                      "note": ("the chain's launches of the timed region: the sweep runs next to them on a second stream" if args.callback == "jacobian"
-                               else "the adjoint sweep of the timed region: the forward sweep of the p column runs next to it on a second stream")}
-        ev.set_option("overlap_sweep", 0)
-        ev.profile_enable(True)
-        step()
-        fence()
-        ev.profile_reset()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        fence()
-        serial_elapsed = time.perf_counter() - t0
-        ev.profile_enable(False)
-        ev.set_option("overlap_sweep", 1)
+    if args.full:
         ms_gemm, n_gemm, fl_gemm, ms_sweep, n_sweep, fl_sweep, variants, assembly = collect()
-        overlapped["ms_per_step_serial_pass"] = serial_elapsed / args.steps * 1e3
-    smax, terms = ev.last_stats()
-    finite = bool(torch.isfinite(out).all().item())
-    if args.callback == "constraint" and n_gemm:
-        # the engine prices a one-launch sweep by its step BUDGET; the roofline takes the products of the Taylor terms actually run:
-        # 2 npad^2 (m + 1) flops per interval and term (terms - 1 products: term 0 is the state itself)
-        npad = -(-n // 64) * 64
-        fl_gemm = 2.0 * npad * npad * (m + 1) * n_int * max(terms - 1, 1) * n_gemm
+        # In the timed region the Jacobian's generator sweep shares the chip with the chain's products (option overlap_sweep, on
+        # by default): a kernel's HIP-event duration there includes what it waited for the other stream.  The roofline of the
+        # dominant kernel is therefore taken from a SERIAL pass -- the same K steps again with overlap_sweep = 0, one kernel at
+        # a time, which is also what `rocprofv3 -- python3 bench.py --serial-kernels` shows (profiles/) -- and the timed
+        # region's own figures are reported next to it.
+        if args.callback in ("jacobian", "hessian") and not args.serial_kernels and not args.no_kernel_timing:
+            overlapped = {"avg_launch_ms": ms_gemm / max(n_gemm, 1), "launches": n_gemm,
+                          "achieved": fl_gemm / (ms_gemm * 1e-3) / 1e12 if ms_gemm > 0 else 0.0,
+                          "sweep_ms_per_step": ms_sweep / args.steps,
+                          "note": ("the chain's launches of the timed region: the sweep runs next to them on a second stream" if args.callback == "jacobian"
+                                   else "the adjoint sweep of the timed region: the forward sweep of the p column runs next to it on a second stream")}
+            ev.set_option("overlap_sweep", 0)
+            ev.profile_enable(True)
+            step()
+            fence()
+            ev.profile_reset()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            fence()
+            serial_elapsed = time.perf_counter() - t0
+            ev.profile_enable(False)
+            ev.set_option("overlap_sweep", 1)
+            ms_gemm, n_gemm, fl_gemm, ms_sweep, n_sweep, fl_sweep, variants, assembly = collect()
+            overlapped["ms_per_step_serial_pass"] = serial_elapsed / args.steps * 1e3
+        if args.callback == "constraint" and n_gemm:
+            # the engine prices a one-launch sweep by its step BUDGET; the roofline takes the products of the Taylor terms actually run:
+            # 2 npad^2 (m + 1) flops per interval and term (terms - 1 products: term 0 is the state itself)
+            npad = -(-n // 64) * 64
+            fl_gemm = 2.0 * npad * npad * (m + 1) * n_int * max(terms - 1, 1) * n_gemm
 
     # The blocks below are reports next to `value` (gather, strong scaling).  With several ranks they run collectives that
     # have never executed on an 8-GPU node: should one of them hang, every rank leaves after WATCHDOG_S seconds and rank 0
     # still prints the headline measured above (marked as such) instead of losing the line.
     watchdog = None
-    if dist is not None and world > 1:
+    if args.full and dist is not None and world > 1:
         import threading
 
         def bail():
@@ -601,7 +642,7 @@ def main():
         watchdog.start()
 
     gather = None
-    want_gather = args.gather if args.gather is not None else world > 1
+    want_gather = args.full and (args.gather if args.gather is not None else world > 1)
     if want_gather and dist is not None and args.callback in ("jacobian", "hessian"):
         n_out = out.numel()
         del out  # its place is taken by the rank's slice of the full vector
@@ -613,7 +654,7 @@ def main():
 
     # the metric's own problem split over the ranks, next to the weak-scaling `value` (all ranks take part)
     strong_block = None
-    if dist is not None and not strong and args.callback == "jacobian":
+    if args.full and dist is not None and not strong and args.callback == "jacobian":
         try:
             strong_block = measure_strong(args, dto_amd, torch, dist, dev, rank, world, fence, n, m)
         except Exception as e:
@@ -624,7 +665,7 @@ def main():
 
     # per-step times, each step fenced on its own: the median next to the mean that `value` is (SURVEY.md §8d quotes a median)
     step_ms = []
-    if args.callback == "jacobian" and world == 1:
+    if args.full and args.callback == "jacobian" and world == 1:
         ostep = (lambda: ev.eval_jacobian_dev(Z.data_ptr(), out.data_ptr(), stream))
         for _ in range(args.steps):
             torch.cuda.synchronize(dev)
@@ -635,7 +676,7 @@ def main():
 
     # ... and the same with the host-to-device copy of Z inside each timed step (SURVEY.md section 8d's metric definition)
     h2d_ms = []
-    if args.callback == "jacobian" and world == 1:
+    if args.full and args.callback == "jacobian" and world == 1:
         Zh = torch.from_numpy(prob.trajectory.vec()).pin_memory()
         for _ in range(args.steps):
             torch.cuda.synchronize(dev)
@@ -649,7 +690,7 @@ def main():
     # device vector every iteration, can declare): the call-invariant half of the slab is then written once, not per call.
     # Reported next to `value`, never as `value` -- the headline keeps the reference's semantics (every entry written per call).
     bound_block = None
-    if args.callback in ("jacobian", "hessian") and world == 1 and not args.no_bound_output:
+    if args.full and args.callback in ("jacobian", "hessian") and world == 1 and not args.no_bound_output:
         vec = dto_amd.capi.VECTOR_JACOBIAN if args.callback == "jacobian" else dto_amd.capi.VECTOR_HESSIAN
         ev.bind_output_dev(vec, out.data_ptr())
         for _ in range(max(2, args.warmup)):
@@ -664,26 +705,8 @@ def main():
         bound_block = {"ms_per_step": tb / args.steps * 1e3, "knot_points_per_s": N_total * args.steps / tb,
                        "note": "dto_bind_output_dev: constants (structural zeros, identity blocks) written once; same buffer every call"}
 
-    traffic, traffic_src, traffic_call = None, None, None
-    try:  # HBM bytes per launch of the dominant kernel come from committed PMC passes (bench.py cannot run rocprofv3 on itself)
-        import glob
-        # the latest round's passes for THIS shape and callback (profiles/rNN*_traffic_<callback>_<n>x<knots>.json), else none
-        cands = sorted(glob.glob(os.path.join(ROOT, "profiles", f"r[0-9][0-9]*_traffic_{args.callback}_{n}x{Nk}.json")))
-        if cands:
-            tj = json.load(open(cands[-1]))
-            traffic, traffic_src = tj["avg_per_launch_bytes"], tj["source"]
-            traffic_call = tj.get("per_call_total_bytes")
-            pl = tj["per_launch_bytes"]
-            prods = [v["read"] + v["write"] for k, v in pl.items() if k.startswith("product")]
-            if "horner" in variants and prods:
-                variants["horner"]["traffic"] = sum(prods) / len(prods)
-            if "square" in variants and "square" in pl:
-                variants["square"]["traffic"] = pl["square"]["read"] + pl["square"]["write"]
-    except Exception:
-        pass
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        achieved = fl_gemm / (ms_gemm * 1e-3) / 1e12 if ms_gemm > 0 else 0.0
         line = {
             "metric": baseline_metric() if (args.callback, n, args.knots) == ("jacobian", 256, 2000)
             else f"knot-points/sec for eval_{args.callback}, {n}-state x {args.knots}-knot bilinear",
@@ -706,7 +729,27 @@ def main():
                        "max_squarings": smax, "sweep_terms": terms,
                        "inputs": "Z and the value slab resident in HBM; the 4.2 MB host-to-device copy of Z that SURVEY.md §8d's "
                                  "metric lists is NOT in `value` (host-pointer figures: DESIGN.md §5)"},
-            "roofline": {
+        }
+        if args.full:
+            traffic, traffic_src, traffic_call = None, None, None
+            try:  # HBM bytes per launch of the dominant kernel come from committed PMC passes (bench.py cannot run rocprofv3 on itself)
+                import glob
+                # the latest round's passes for THIS shape and callback (profiles/rNN*_traffic_<callback>_<n>x<knots>.json), else none
+                cands = sorted(glob.glob(os.path.join(ROOT, "profiles", f"r[0-9][0-9]*_traffic_{args.callback}_{n}x{Nk}.json")))
+                if cands:
+                    tj = json.load(open(cands[-1]))
+                    traffic, traffic_src = tj["avg_per_launch_bytes"], tj["source"]
+                    traffic_call = tj.get("per_call_total_bytes")
+                    pl = tj["per_launch_bytes"]
+                    prods = [v["read"] + v["write"] for k, v in pl.items() if k.startswith("product")]
+                    if "horner" in variants and prods:
+                        variants["horner"]["traffic"] = sum(prods) / len(prods)
+                    if "square" in variants and "square" in pl:
+                        variants["square"]["traffic"] = pl["square"]["read"] + pl["square"]["write"]
+            except Exception:
+                pass
+            achieved = fl_gemm / (ms_gemm * 1e-3) / 1e12 if ms_gemm > 0 else 0.0
+            line["roofline"] = {
                 "bound": "mfma", "kernel": {"hessian": ("k_sweep_s64" if n <= 64 else "k_sweep_fused / k_sweep_gs") +
                                                        " (adjoint generator sweep of the Hessian: exp(A')mu and its u-tangents, one persistent launch)",
                                             "constraint": ("k_sweep_s64" if 32 < n <= 64 else "k_sweep_gs / k_sweep") + " (generator sweep of the p column: exp(A)x)"}.get(
@@ -726,24 +769,23 @@ def main():
                                 "on the launch stream; same as rocprofv3 of `bench.py --serial-kernels`" if overlapped else
                                 "the timed region"),
                 "timed_region": overlapped,
-            },
+            }
             # the whole callback against the HBM roofline (BASELINE north_star asks for this fraction too): algorithmic
             # bytes = mandatory output write + read of Z + one read of the generators
-            "callback_hbm": (lambda nbytes: {"algorithmic_bytes": nbytes, "achieved": nbytes / (ms_per_step * 1e-3) / 1e9,
-                                             "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                             "frac": nbytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS})(
-                8.0 * (out.numel() + Z.numel() + (m + 1) * n * n + (ev.n_constraints if args.callback == "hessian" else 0))),
+            line["callback_hbm"] = (lambda nbytes: {"algorithmic_bytes": nbytes, "achieved": nbytes / (ms_per_step * 1e-3) / 1e9,
+                                                    "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                                    "frac": nbytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS})(
+                8.0 * (out.numel() + Z.numel() + (m + 1) * n * n + (ev.n_constraints if args.callback == "hessian" else 0)))
             # one timed region per sweep (its step kernels, termination tests and the gaps between them); flops = the
             # generator products of the Taylor terms actually used: 2 npad^2 (m+1) products per column, (1+m) column types
             # (Jacobian; the Hessian's two sweeps and the constraint's single column are priced by the engine's own count)
-            "secondary_kernel": (lambda fl: {"kernel": "k_sweep (generator sweep: exp(A)x and its u-tangents)",
-                                             "ms_per_step": ms_sweep / args.steps, "timed_regions": n_sweep,
-                                             "achieved_tflops": fl / (ms_sweep * 1e-3) / 1e12 if ms_sweep > 0 else 0.0})(
+            line["secondary_kernel"] = (lambda fl: {"kernel": "k_sweep (generator sweep: exp(A)x and its u-tangents)",
+                                                    "ms_per_step": ms_sweep / args.steps, "timed_regions": n_sweep,
+                                                    "achieved_tflops": fl / (ms_sweep * 1e-3) / 1e12 if ms_sweep > 0 else 0.0})(
                 (2.0 * (-(-n // 64) * 64) ** 2 * (-(-(Nk - 1) // 128) * 128) * (m + 1) * (m + 1) * terms * args.steps)
-                if args.callback == "jacobian" else fl_sweep),
-        }
-        if assembly:
-            line["assembly_hbm"] = assembly
+                if args.callback == "jacobian" else fl_sweep)
+            if assembly:
+                line["assembly_hbm"] = assembly
         if h2d_ms:
             hs = sorted(h2d_ms)
             med = hs[len(hs) // 2] if len(hs) % 2 else 0.5 * (hs[len(hs) // 2 - 1] + hs[len(hs) // 2])
@@ -761,13 +803,13 @@ def main():
             line["gather"] = gather
         if strong_block is not None:
             line["strong_scaling"] = strong_block
-        if world == 1 and args.callback == "jacobian" and not args.no_other_callbacks:
+        if args.full and world == 1 and args.callback == "jacobian" and not args.no_other_callbacks:
             # the other callbacks of the same problem, same protocol (3 untimed + 5 timed calls each): reported for
             # context (SURVEY.md §8d lists them next to the headline), never part of `value`
             line["other_callbacks"] = other_callbacks(dto_amd, torch, prob, ev, dev, Z, stream, N_total)
             if "host_pointer" in line["other_callbacks"]:
                 line["host_pointer"] = line["other_callbacks"].pop("host_pointer")
-        if world == 1 and not args.no_cpu_baseline and args.callback == "jacobian":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.callback == "jacobian":
             try:
                 line["cpu_baseline"] = cpu_baseline(prob, n, m, Nk, args.cpu_budget)
             except Exception as e:  # the baseline is a report, never a reason to lose the GPU number

@@ -1,6 +1,8 @@
-"""GPU: `bench.py` honours the driver's contract on a small shape -- one JSON line on stdout with the required keys, the
-roofline block (serial pass) and the CPU baseline block; and the two-rank one-device rehearsal of the multi-GPU path prints
+"""GPU: `bench.py` honours the driver's contract on a small shape -- one JSON line on stdout with the required keys; a plain
+run stops at the headline and `--dump-outputs` writes what its last timed step computed; under `--full` the line carries the
+roofline block (serial pass) and the CPU baseline block, and the two-rank one-device rehearsal of the multi-GPU path prints
 the gather block (sequential and overlapped forms)."""
+import importlib.util
 import json
 import os
 import socket
@@ -21,8 +23,47 @@ def _line(out):
     return json.loads(lines[0])
 
 
+def test_plain_line_is_lean_and_dumps_what_the_last_step_computed(tmp_path):
+    """Without --full the run times its --steps steps and prints the headline alone.  --dump-outputs writes the value vector of
+    the last timed step -- at 128 x 300 above the dump's cap, so the fixed sample of its positions: the same bits from run to
+    run, and the Jacobian the host-pointer entry point returns for the same seeded problem at those positions."""
+    import numpy as np
+    import dto_amd
+    from helpers import rel_err
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--n", "128", "--knots", "300",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _line(r.stdout)
+        for key in REQUIRED[:-1]:
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+        assert abs(d["value"] - 300 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"] and d["config"]["outputs_finite"] is True
+        extra = {"roofline", "callback_hbm", "secondary_kernel", "assembly_hbm", "ms_per_step_median", "value_incl_h2d_median",
+                 "bound_output", "other_callbacks", "host_pointer", "cpu_baseline"}
+        assert not extra & set(d), sorted(d)
+        assert os.listdir(out) == ["eval_constraint_jacobian.npy"]
+        dumps.append(np.load(out / "eval_constraint_jacobian.npy"))
+    assert dumps[0].dtype == np.float64 and dumps[0].nbytes <= 64 << 20 and np.array_equal(dumps[0], dumps[1])
+    prob = dto_amd.host.synthetic.make_scaled_problem(300, 128, 4, seed=42)
+    ev = dto_amd.Evaluator(prob, eval_hessian=False, device=0)
+    try:
+        jac = np.empty(ev.n_jacobian_entries)
+        ev.eval_constraint_jacobian(jac, prob.trajectory.vec())
+    finally:
+        ev.close()
+    pos = bench.dump_positions(jac.size, bench.DUMP_MAX_ENTRIES)
+    assert pos is not None and dumps[0].shape == pos.shape
+    assert rel_err(dumps[0], jac[pos]) <= 1e-12
+
+
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--n", "128", "--knots", "1200",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--n", "128", "--knots", "1200",
                         "--cpu-budget", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -59,7 +100,7 @@ def test_single_gpu_line():
 
 def test_64_states_report_the_one_launch_chain():
     """configs[1]'s shape: the propagator chain is k_chain64 (one launch per call), the sweep the generator-stationary form; the line says so."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--n", "64", "--knots", "1000",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--n", "64", "--knots", "1000",
                         "--no-cpu-baseline", "--no-other-callbacks"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -71,7 +112,7 @@ def test_64_states_report_the_one_launch_chain():
 
 @pytest.mark.parametrize("callback", ["hessian", "constraint"])
 def test_other_callbacks_have_a_roofline_line_of_their_own(callback):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--n", "256", "--knots", "300",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--n", "256", "--knots", "300",
                         "--callback", callback, "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -88,7 +129,7 @@ def test_four_rank_rehearsal_on_one_device():
     eight ranks) and tests/test_distributed_gloo.py (eight gloo processes)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--one-device",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--backend", "gloo", "--one-device",
                         "--n", "64", "--knots", "200", "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
@@ -108,7 +149,7 @@ def test_gpus_2_without_torchrun_starts_two_ranks_itself():
     on one device they pose as two hosts and use the socket transport), the strong-scaling block splits the same knots."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--one-device",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--one-device",
                         "--n", "64", "--knots", "600", "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
@@ -151,7 +192,7 @@ def test_a_hung_report_block_cannot_lose_the_headline():
     process exits NON-ZERO: a hung collective must never read as a clean run to whoever launched the bench."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", DTO_BENCH_WATCHDOG_S="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--one-device",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--one-device",
                         "--n", "64", "--knots", "600", "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode != 0, (r.stdout + r.stderr)[-3000:]

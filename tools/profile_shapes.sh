@@ -13,8 +13,8 @@ for spec in "64 1000 jacobian" "64 1000 hessian" "64 1000 constraint" "256 250 j
   set -- $spec
   n=$1; k=$2; cb=$3
   name=${n}x${k}_${cb}
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -- python3 $R/bench.py --states $n --knots $k --callback $cb \
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -- python3 $R/bench.py --full --states $n --knots $k --callback $cb \
       --steps 5 --warmup 2 --no-cpu-baseline --no-other-callbacks --no-bound-output --serial-kernels > $O/prof_$name.log 2>&1 || echo "rocprof $name failed"
-  (cd $R && timeout -k 10 300 python bench.py --states $n --knots $k --callback $cb --no-cpu-baseline --no-other-callbacks > $O/bench_$name.log 2>&1) || echo "bench $name failed"
+  (cd $R && timeout -k 10 300 python bench.py --full --states $n --knots $k --callback $cb --no-cpu-baseline --no-other-callbacks > $O/bench_$name.log 2>&1) || echo "bench $name failed"
   echo "$name: $(tail -1 $O/bench_$name.log | cut -c1-200)"
 done

@@ -8,7 +8,7 @@ import sys
 
 def main():
     tag, stats = sys.argv[1], sys.argv[2]
-    out = [f"# rocprofv3 summary {tag}", "", "command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-callbacks --serial-kernels`",
+    out = [f"# rocprofv3 summary {tag}", "", "command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-other-callbacks --serial-kernels`",
            "(2 warm-up + 5 timed + 5 individually timed eval_constraint_jacobian calls, 256-state x 2000-knot bilinear, 1x MI355X; --serial-kernels = "
            "option overlap_sweep 0, one kernel at a time; the 64x64 k_bgemm / k_add launches are create-time work)", "",
            "| kernel | calls | total ms | avg us | % |", "|---|---|---|---|---|"]

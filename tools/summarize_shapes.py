@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
 src = os.path.join(ROOT, "gpurun_out", f"shapes_{tag}")
 out = [f"# rocprofv3 summaries per shape, {tag}", "",
-       "command per row group: `rocprofv3 --kernel-trace --stats -- python3 bench.py --states N --knots K --callback C --steps 5 --warmup 2 "
+       "command per row group: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --states N --knots K --callback C --steps 5 --warmup 2 "
        "--no-cpu-baseline --no-other-callbacks --no-bound-output --serial-kernels` (7 calls + 5 individually fenced ones for the Jacobian; "
        "one kernel at a time), next to the line of the default run of the same shape (`bench_line`).", ""]
 for log in sorted(glob.glob(os.path.join(src, "bench_*.log"))):
