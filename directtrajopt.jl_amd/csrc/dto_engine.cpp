@@ -1523,7 +1523,10 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
             // (where the adjoint sweep has no single-workgroup form -- short shards -- both sweeps take the generator-stationary form,
             // one after the other; beside a fused adjoint sweep the forward column keeps its step launches, which fit into the CUs
             // that sweep leaves idle: measured 5.5 against 5.9 ms at 256 x 2000 with the forward column first and alone)
-            const bool side_by_side = fwd_needed && h->overlap_sweep && fused_sweep_applies(h, b, b.ad, ty1, plan, true);
+            // (option "deterministic": never side by side -- beside the adjoint sweep the forward column takes another form, step
+            // launches instead of the generator-stationary sweep at 128 / 256 states, another interval grouping at 33..64, so its
+            // summation order would follow overlap_sweep)
+            const bool side_by_side = fwd_needed && h->overlap_sweep && !h->deterministic && fused_sweep_applies(h, b, b.ad, ty1, plan, true);
             bool adjoint_enqueued = false;
             if (side_by_side) {
                 HIP_CHECK(hipEventRecord(h->ev_fork, st));  // dZ, dmu and the zeroed slab are ready here

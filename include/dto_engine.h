@@ -365,7 +365,9 @@ int dto_bind_output_dev(dto_handle* h, int32_t vector, double* dptr);
  *   order (column sums of the generator-subspace GEMMs per 64-row chunk, objective partial sums, listings of a term that
  *   repeats a knot layer by layer, contributions to global-variable entries in listing order; the sweeps' K order is a function
  *   of the block index).  What still depends on HOW a result is asked for is switched off by 1: the Jacobian's sweep keeps the
- *   interval grouping it has alone on the chip (else `overlap_sweep` changes the summation order at 256 states), and the
+ *   interval grouping it has alone on the chip (else `overlap_sweep` changes the summation order at 256 states), the Hessian's
+ *   forward p-column sweep runs after its adjoint sweep instead of beside it (else `overlap_sweep` switches that column between
+ *   step launches and the generator-stationary form at 128 / 256 states, and regroups its intervals at 33..64), and the
  *   host-pointer dto_eval_jacobian runs the propagator chain in the same chunks as dto_eval_jacobian_dev (else the early
  *   hand-over of -E_k caps the chunk, and the evaluation form is decided per chunk).  Cost at 256 x 2000: +0.1..0.4 ms per
  *   device-resident Jacobian, and the host-pointer Jacobian loses the overlap of its PCIe copy with the chain (23 -> 34 ms).

@@ -517,14 +517,39 @@ def _second_frechet_action(A, E1, E2, x):
     return (top_right(E1, E2) + top_right(E2, E1)) @ x
 
 
-def bilinear_block_hessian(integ, prob, zk, mu, skip_uu=False):
+def _second_frechet_action_cs(A, E1, E2, x, h=1e-20):
+    """d^2/(ds dt) exp(A + s E1 + t E2) x at 0 by the complex step on the first-order Frechet derivative:
+    Im[L(A + i h E1, E2)] x / h.  Valid because scipy's expm_frechet (scaling and squaring, Pade 13) is analytic in A: its
+    branch choice reads only ||A||_1, which a step of 1e-20 leaves unchanged; no subtraction, so no cancellation.  One
+    complex n x n Frechet derivative instead of the exponential of a 3n x 3n matrix: the (u, u) block stays affordable
+    at 1024 states."""
+    L = sla.expm_frechet(A + (1j * h) * E1, E2.astype(np.complex128), compute_expm=False)
+    return L.imag @ x / h
+
+
+# (u, u) terms of the bilinear Hessian: "block" (3n x 3n block-triangular exponential), "complex_step" (above) or "auto" --
+# the block form up to this many states (the oracle of every test at those sizes), the complex step above
+UU_BLOCK_MAX_STATES = 256
+
+
+def _uu_action(uu, n):
+    if uu == "auto":
+        uu = "block" if n <= UU_BLOCK_MAX_STATES else "complex_step"
+    if uu == "block":
+        return _second_frechet_action
+    if uu == "complex_step":
+        return _second_frechet_action_cs
+    raise ValueError(f"uu: {uu!r}")
+
+
+def bilinear_block_hessian(integ, prob, zk, mu, uu="auto"):
     """Dense z x z Hessian of mu' f wrt z_k for the bilinear defect (x_{k+1} rows/cols are 0).
 
     Exact second derivative of bilinear_integrator.jl:81 (reference: ForwardDiff.hessian,
-    :135-161).  skip_uu leaves the (u_i, u_j) block at zero: its second-order Frechet terms need the exponential of
-    a 3n x 3n matrix, which at n = 1024 takes minutes per pair (the large-state tests check that block against central
-    differences of the Jacobian instead, the reference's own method, evaluator.jl:779-790)."""
+    :135-161).  uu: how the second-order Frechet terms of the (u_i, u_j) block are formed (see _uu_action); the 3n x 3n
+    block exponential takes minutes per pair at n = 1024, the complex step about a second."""
     n, m, z = integ.x_dim, integ.u_dim, prob.z
+    second = _uu_action(uu, n)
     dt = zk[prob.dt_idx]
     x = zk[integ.x_off:integ.x_off + n]
     u = zk[integ.u_off:integ.u_off + m]
@@ -544,9 +569,9 @@ def bilinear_block_hessian(integ, prob, zk, mu, skip_uu=False):
         val = -(mu @ (integ.G[1 + j] @ Ex + Gu @ (Ls[j] @ x)))
         H[uj, prob.dt_idx] += val
         H[prob.dt_idx, uj] += val
-        for i in range(0 if skip_uu else j + 1):
+        for i in range(j + 1):
             ui = integ.u_off + i
-            val = -(mu @ _second_frechet_action(A, dt * integ.G[1 + i], dt * integ.G[1 + j], x))
+            val = -(mu @ second(A, dt * integ.G[1 + i], dt * integ.G[1 + j], x))
             H[ui, uj] += val
             if i != j:
                 H[uj, ui] += val
@@ -557,7 +582,7 @@ def bilinear_block_hessian(integ, prob, zk, mu, skip_uu=False):
     return H
 
 
-def integrator_hessian(integ, prob, Z, mu, skip_uu=False):
+def integrator_hessian(integ, prob, Z, mu, uu="auto"):
     """eval_hessian_of_lagrangian -- bilinear_integrator.jl:135-161, derivative_integrator.jl:90-116."""
     d, z = integ.x_dim, prob.z
     H = sp.lil_matrix((prob.n_vars, prob.n_vars))
@@ -569,7 +594,7 @@ def integrator_hessian(integ, prob, Z, mu, skip_uu=False):
             zz = np.concatenate([zk, _knot(Z, prob, k + 1)])
             blk = np.asarray(integ.hess(zz, k, muk), dtype=np.float64).reshape(2 * z, 2 * z)
         elif integ.kind == "bilinear":
-            blk[:z, :z] = bilinear_block_hessian(integ, prob, zk, muk, skip_uu)
+            blk[:z, :z] = bilinear_block_hessian(integ, prob, zk, muk, uu)
         else:
             for i in range(d):
                 blk[integ.xdot_off + i, prob.dt_idx] += -muk[i]
@@ -968,9 +993,9 @@ class OracleEvaluator:
                     out[idx] = vv
         return out
 
-    def eval_hessian_lagrangian(self, Z, sigma, mu, skip_uu=False):
+    def eval_hessian_lagrangian(self, Z, sigma, mu, uu="auto"):
         """_fill_hessian_values! -- evaluator.jl:560-647 (accumulation, upper triangle only).
-        skip_uu: see bilinear_block_hessian (large-state tests only)."""
+        uu: the form of the bilinear (u, u) terms, see bilinear_block_hessian."""
         out = np.zeros(len(self.hess_rows))
 
         def scatter(M, scale=1.0):
@@ -985,7 +1010,7 @@ class OracleEvaluator:
 
         for i, integ in enumerate(self.prob.integrators):
             o = self.integrator_offsets[i]
-            scatter(integrator_hessian(integ, self.prob, Z, mu[o:o + integ.x_dim * self.prob.K], skip_uu))
+            scatter(integrator_hessian(integ, self.prob, Z, mu[o:o + integ.x_dim * self.prob.K], uu))
         for i, con in enumerate(self.prob.constraints):
             o = self.constraint_offsets[i]
             scatter(constraint_hessian(con, self.prob, Z, mu[o:o + con.g_dim * len(con.times1)]))

@@ -150,6 +150,9 @@ def to_engine(prob: O.Problem, closure_derivatives="numeric", tdb_on_device=True
     return dto_amd.DirectTrajOptProblem(traj, obj, integ, constraints=cons)
 
 
+TOL, TOL_H = 1e-10, 1e-8  # values / Jacobian, Hessian
+
+
 def rel_err(a, b):
     """max |a-b| / max(1,|b|) elementwise (the tolerance form of SURVEY.md §8c)."""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
@@ -168,3 +171,164 @@ def run_all(ev, prob_o, Z, mu, sigma=1.0, hessian=True):
     if hessian:
         h = np.full(ev.shard.hess_len, np.nan); ev.eval_hessian_lagrangian(h, Z, sigma, mu); out["hess"] = h
     return out
+
+
+def check_callbacks(prob_o, Z=None, seed=0, hessian=True, tag="", closure_derivatives="numeric", tol_h=TOL_H, products=False):
+    """Every callback of a fresh engine handle against the oracle on prob_o: sparsity bit-exact, values at TOL / tol_h;
+    products: J w and J' w as well."""
+    ev_o = O.OracleEvaluator(prob_o)
+    ev = dto_amd.Evaluator(to_engine(prob_o, closure_derivatives), eval_hessian=hessian)
+    try:
+        assert ev.n_variables == prob_o.n_vars
+        assert ev.n_constraints == ev_o.n_constraints
+        assert ev.n_dynamics_constraints == ev_o.n_dynamics_constraints
+        jr, jc = ev.jacobian_structure()
+        r1, c1 = ev_o.jacobian_structure1()
+        assert np.array_equal(jr, r1) and np.array_equal(jc, c1), "Jacobian structure"
+        hr, hc = ev.hessian_lagrangian_structure()
+        r1, c1 = ev_o.hessian_structure1()
+        assert np.array_equal(hr, r1) and np.array_equal(hc, c1), "Hessian structure"
+        lo, hi = ev.constraint_bounds()
+        lo_o, hi_o = ev_o.row_bounds()
+        assert np.array_equal(lo, lo_o) and np.array_equal(hi, hi_o)
+        rng = np.random.default_rng(seed)
+        Z = prob_o.Z0.copy() if Z is None else Z
+        mu = rng.standard_normal(ev_o.n_constraints)
+        out = run_all(ev, prob_o, Z, mu, sigma=0.7, hessian=hessian)
+        errs = {
+            "f": rel_err(out["f"], ev_o.eval_objective(Z)),
+            "grad": rel_err(out["grad"], ev_o.eval_objective_gradient(Z)),
+            "cons": rel_err(out["cons"], ev_o.eval_constraint(Z)),
+            "jac": rel_err(out["jac"], ev_o.eval_constraint_jacobian(Z)),
+        }
+        if hessian:
+            errs["hess"] = rel_err(out["hess"], ev_o.eval_hessian_lagrangian(Z, 0.7, mu))
+        if products:
+            w = rng.standard_normal(prob_o.n_vars)
+            y = np.full(ev_o.n_constraints, np.nan); ev.eval_constraint_jacobian_product(y, Z, w)
+            errs["Jw"] = rel_err(y, ev_o.eval_constraint_jacobian_product(Z, w))
+            w = rng.standard_normal(ev_o.n_constraints)
+            y = np.full(prob_o.n_vars, np.nan); ev.eval_constraint_jacobian_transpose_product(y, Z, w)
+            errs["JTw"] = rel_err(y, ev_o.eval_constraint_jacobian_transpose_product(Z, w))
+        print(tag, errs, ev.last_stats())
+        for k, v in errs.items():
+            assert v <= (tol_h if k == "hess" else TOL), (tag, k, v)
+    finally:
+        ev.close()
+
+
+# ---- full-size outputs checked through sampled knots: knot k of a long horizon against the two-knot oracle problem (z_k, z_{k+1}) --
+# the bilinear and derivative integrators couple nothing else (SURVEY.md section 8e), so block k of the big problem IS block 0 of
+# that sub-problem
+
+
+def sub_problem(G, Zk2, n, m, z, dt_idx, extra_objectives=()):
+    """Oracle problem on the two knots (z_k, z_{k+1}) with the big problem's generators and objective terms."""
+    return O.Problem(N=2, z=z, dt_idx=dt_idx,
+                     integrators=[O.BilinearIntegrator(0, n, n, m, G), O.DerivativeIntegrator(n, m, n + m)],
+                     objectives=[O.QuadraticRegularizer(n, m, np.ones(m))] + list(extra_objectives),
+                     Z0=np.ascontiguousarray(Zk2).reshape(-1).copy())
+
+
+def dense(rows1, cols1, vals, shape):
+    M = np.zeros(shape)
+    M[rows1 - 1, cols1 - 1] = vals
+    return M
+
+
+def jac_column_block(get, k, z, D, K):
+    """Rows of column block k of the full-size Jacobian slab as a (cnt x z) array: per column and integrator the rows of
+    interval k-1, then of interval k.  `get(lo, hi)` returns a host copy of vals[lo:hi]."""
+    cnt = (1 if k >= 1 else 0) + (1 if k < K else 0)
+    start = 0 if k == 0 else z * D + (k - 1) * 2 * z * D
+    return get(start, start + z * cnt * D).reshape(z, cnt * D).T, cnt
+
+
+def check_jacobian_block(blk, cnt, k, sub_jac, n, m, z, K):
+    """blk: (cnt*D x z) of knot k; sub_jac: dense (D x 2z) Jacobian of interval k from the two-knot oracle problem (rows:
+    bilinear n, derivative m).  Own rows = its z_k half; previous interval's rows = the constant z_{k+1} half."""
+    has_prev = k >= 1
+    if k < K:
+        own_b = blk[(n if has_prev else 0):(n if has_prev else 0) + n]
+        own_d = blk[cnt * n + (m if has_prev else 0):cnt * n + (m if has_prev else 0) + m]
+        assert rel_err(own_b, sub_jac[:n, :z]) <= 1e-10, ("bilinear rows", k, rel_err(own_b, sub_jac[:n, :z]))
+        assert rel_err(own_d, sub_jac[n:, :z]) <= 1e-10, ("derivative rows", k)
+        assert np.all(own_b[:, n + m:n + 2 * m] == 0.0)  # du columns: structural zeros that are still stored
+    if has_prev:
+        prev_b, prev_d = blk[:n], blk[cnt * n:cnt * n + m]
+        ref_b = np.zeros((n, z)); ref_b[:, :n] = np.eye(n)
+        ref_d = np.zeros((m, z)); ref_d[:, n:n + m] = np.eye(m)
+        assert np.array_equal(prev_b, ref_b) and np.array_equal(prev_d, ref_d), ("z_{k+1} half", k)
+
+
+def hess_diag_block(get, k, z):
+    """Upper triangle (incl. diagonal) of diagonal block k and the off-diagonal block (k-1, k) of the full-size Hessian."""
+    tri = z * (z + 1) // 2
+    if k == 0:
+        return tri_from_cols(get(0, tri), z), None
+    start = tri + (k - 1) * (z * z + tri)
+    v = get(start, start + z * z + tri)
+    Hd, Ho = np.zeros((z, z)), np.zeros((z, z))
+    pos = 0
+    for b in range(z):
+        Ho[:, b] = v[pos:pos + z]
+        pos += z
+        Hd[:b + 1, b] = v[pos:pos + b + 1]
+        pos += b + 1
+    return Hd, Ho
+
+
+def tri_from_cols(v, z):
+    Hd = np.zeros((z, z))
+    pos = 0
+    for b in range(z):
+        Hd[:b + 1, b] = v[pos:pos + b + 1]
+        pos += b + 1
+    return Hd
+
+
+def sampled_checks(prob_e, ev, n, m, ks, jac_get=None, hess_get=None, cons=None, mu=None, sigma=1.0, extra_objectives=()):
+    """Compare column block / Hessian diagonal block of every sampled knot with the two-knot oracle problem."""
+    traj = prob_e.trajectory
+    N, z = traj.N, traj.dim
+    K, D = N - 1, n + m
+    dt_idx = traj.components[traj.timestep][0]
+    G = prob_e.integrators[0].G
+    X = traj.data
+    for k in ks:
+        if k < K:
+            sub = sub_problem(G, X[:, k:k + 2].T, n, m, z, dt_idx, extra_objectives)
+            ev_o = O.OracleEvaluator(sub)
+            r1, c1 = ev_o.jacobian_structure1()
+            sub_jac = dense(r1, c1, ev_o.eval_constraint_jacobian(sub.Z0), (D, 2 * z))
+        if jac_get is not None:
+            blk, cnt = jac_column_block(jac_get, k, z, D, K)
+            check_jacobian_block(blk, cnt, k, sub_jac if k < K else None, n, m, z, K)
+            if k < K and cons is not None:
+                # chain vs sweep: the dense -E_k of the propagator chain applied to x_k equals exp(A_k) x_k of the sweep
+                own = blk[(n if k >= 1 else 0):(n if k >= 1 else 0) + n]
+                delta = cons[k * n:(k + 1) * n]
+                assert rel_err(own[:, :n] @ X[:n, k], delta - X[:n, k + 1]) <= 1e-10, ("chain vs sweep", k)
+        if cons is not None and k < K:
+            ref = ev_o.eval_constraint(sub.Z0)
+            assert rel_err(cons[k * n:(k + 1) * n], ref[:n]) <= 1e-10, ("bilinear defect", k)
+            assert rel_err(cons[K * n + k * m:K * n + (k + 1) * m], ref[n:]) <= 1e-10, ("derivative defect", k)
+        if hess_get is not None:
+            Hd, Ho = hess_diag_block(hess_get, k, z)
+            if Ho is not None:
+                assert np.all(Ho == 0.0), ("off-diagonal block", k)  # these integrators never fill it (SURVEY.md section 8e)
+            if k < K:
+                mu_sub = np.concatenate([mu[k * n:(k + 1) * n], mu[K * n + k * m:K * n + (k + 1) * m]])
+                r1, c1 = ev_o.hessian_structure1()
+                Hs = dense(r1, c1, ev_o.eval_hessian_lagrangian(sub.Z0, sigma, mu_sub), (2 * z, 2 * z))
+                assert rel_err(Hd, Hs[:z, :z]) <= 1e-8, ("diagonal block", k, rel_err(Hd, Hs[:z, :z]))
+                assert np.all(Hd[:n, :n] == 0.0)  # (x_k, x_k): identically zero for a defect linear in x
+            else:
+                # last knot: only the objective term of that knot
+                sub = sub_problem(G, X[:, k - 1:k + 1].T, n, m, z, dt_idx, extra_objectives)
+                Hs = O.objective_full_hessian(sub, sub.Z0).toarray()[z:, z:]
+                assert rel_err(Hd, sigma * np.triu(Hs)) <= 1e-8, ("last knot", k)
+
+
+def host_getter(vals):
+    return lambda lo, hi: vals[lo:hi]

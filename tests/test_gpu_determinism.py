@@ -107,3 +107,35 @@ def test_deterministic_option_makes_the_bits_independent_of_how_they_are_asked_f
         assert np.array_equal(host, outs[0].cpu().numpy())
     finally:
         ev.close()
+
+
+@pytest.mark.parametrize("n,N", [(64, 1200), (256, 2000)])
+def test_deterministic_hessian_is_independent_of_overlap_sweep_and_entry_point(n, N):
+    """The Hessian's forward p-column sweep: beside the adjoint sweep (overlap_sweep = 1) it takes the step-per-launch form at 256
+    states and another interval grouping of the 64-state single-workgroup sweep, alone the generator-stationary form.  Under option
+    "deterministic" the bits may depend on neither the option nor the entry point."""
+    import torch
+    import dto_amd
+    p = dto_amd.host.synthetic.make_scaled_problem(N, n, 3, seed=11)
+    ev = dto_amd.Evaluator(p)
+    try:
+        ev.set_option("deterministic", 1)
+        Z = p.trajectory.vec()
+        mu = np.random.default_rng(4).standard_normal(ev.n_constraints)
+        dev = torch.device("cuda", 0)
+        dZ, dmu = torch.from_numpy(Z).to(dev), torch.from_numpy(mu).to(dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        outs = []
+        for overlap in (1, 0, 1):
+            ev.set_option("overlap_sweep", overlap)
+            o = torch.full((ev.shard.hess_len,), float("nan"), dtype=torch.float64, device=dev)
+            ev.eval_hessian_dev(dZ.data_ptr(), 0.9, dmu.data_ptr(), o.data_ptr(), st)
+            torch.cuda.synchronize()
+            outs.append(o)
+        assert bool(torch.isfinite(outs[0]).all())
+        assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+        host = np.full(ev.shard.hess_len, np.nan)
+        ev.eval_hessian_lagrangian(host, Z, 0.9, mu)   # overlap_sweep = 1 still set
+        assert np.array_equal(host, outs[0].cpu().numpy())
+    finally:
+        ev.close()

@@ -434,8 +434,9 @@ def test_sweep_on_the_second_stream_changes_no_bit():
         ev.close()
         assert bool(torch.isfinite(outs[0]).all())
         assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
-    # the Hessian's forward sweep next to its adjoint sweep (same option): accumulated with floating-point atomics, so equal
-    # to rounding rather than to the bit
+    # the Hessian's forward p-column sweep next to its adjoint sweep (same option): there it takes another interval grouping of the
+    # single-workgroup sweep than alone, so another summation order -- equal to rounding rather than to the bit (bit-equal under
+    # option "deterministic": test_gpu_determinism.py)
     p = O.make_scaled_problem(1200, 64, 3, seed=11)
     ev = dto_amd.Evaluator(to_engine(p))
     Z = torch.from_numpy(p.Z0).to(dev)
@@ -456,7 +457,8 @@ def test_host_pointer_calls_back_to_back_match_the_device_resident_ones():
     """The host-pointer Jacobian hands its -E_k blocks to a drainer thread chain chunk by chain chunk while the GPU still
     computes (dto_hostxfer.h), host threads scatter into the caller's vector.  Twelve calls in a row at changing points,
     Jacobian and Hessian alternating, each into a buffer full of NaN: every result must equal the device-resident entry
-    point's, bit for bit (Jacobian; same kernels) / to rounding (Hessian: floating-point atomics)."""
+    point's, bit for bit (Jacobian; same kernels) / to rounding (Hessian; its bit-equality across entry points is asserted
+    under option "deterministic" in test_gpu_determinism.py)."""
     import torch
     import dto_amd
     dev = torch.device("cuda", 0)

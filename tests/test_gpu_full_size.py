@@ -8,130 +8,18 @@ zeros, identity blocks, and the chain-vs-sweep cross check E_k x_k = exp(A_k) x_
 
   configs[1]  64-state, 4 drives, N = 1000          Jacobian + constraints + Hessian
   configs[2]  256-state, N = 2000, Hessian enabled  Hessian (the Jacobian's test is in test_gpu_golden_and_shards.py)
-  configs[3]  256-state, N = 16000 (one rank's view of the chunked chain: 3 chunks on one GPU), Jacobian + constraints
-  configs[4]  1024-state + NonlinearInequality + L1 slack: f / grad / cons / Jacobian / Hessian on 3 knots vs the oracle,
-              the (u,u) Hessian block vs central differences of the engine's own Jacobian at the reference's bar
-              (evaluator.jl:790), and a 1024 x 64-knot run checked by sampled sub-problems
+  configs[3]  256-state, N = 16000 (one rank's view of the chunked chain: 2 chunks on one GPU), Jacobian + constraints
+  configs[4]  1024-state + NonlinearInequality + L1 slack: f / grad / cons / Jacobian / Hessian on 3 knots vs the oracle (the
+              (u,u) block's second-order terms by the complex step), that block also vs central differences of the engine's
+              own Jacobian, and 1024 x 64-knot / 500-knot-share runs checked by sampled sub-problems
 Tolerances as everywhere: 1e-10 max(1,|ref|) values / Jacobian, 1e-8 Hessian."""
 import numpy as np
 import pytest
 
 import dto_oracle as O
-from helpers import rel_err, to_engine
+from helpers import dense, host_getter, rel_err, sampled_checks, sub_problem, to_engine
 
 pytestmark = pytest.mark.gpu
-
-
-def _sub_problem(G, Zk2, n, m, z, dt_idx, extra_objectives=()):
-    """Oracle problem on the two knots (z_k, z_{k+1}) with the big problem's generators and objective terms."""
-    return O.Problem(N=2, z=z, dt_idx=dt_idx,
-                     integrators=[O.BilinearIntegrator(0, n, n, m, G), O.DerivativeIntegrator(n, m, n + m)],
-                     objectives=[O.QuadraticRegularizer(n, m, np.ones(m))] + list(extra_objectives),
-                     Z0=np.ascontiguousarray(Zk2).reshape(-1).copy())
-
-
-def _dense(rows1, cols1, vals, shape):
-    M = np.zeros(shape)
-    M[rows1 - 1, cols1 - 1] = vals
-    return M
-
-
-def _jac_column_block(get, k, z, D, K):
-    """Rows of column block k of the full-size Jacobian slab as a (cnt x z) array: per column and integrator the rows of
-    interval k-1, then of interval k.  `get(lo, hi)` returns a host copy of vals[lo:hi]."""
-    cnt = (1 if k >= 1 else 0) + (1 if k < K else 0)
-    start = 0 if k == 0 else z * D + (k - 1) * 2 * z * D
-    return get(start, start + z * cnt * D).reshape(z, cnt * D).T, cnt
-
-
-def _check_jacobian_block(blk, cnt, k, sub_jac, n, m, z, K):
-    """blk: (cnt*D x z) of knot k; sub_jac: dense (D x 2z) Jacobian of interval k from the two-knot oracle problem (rows:
-    bilinear n, derivative m).  Own rows = its z_k half; previous interval's rows = the constant z_{k+1} half."""
-    has_prev = k >= 1
-    if k < K:
-        own_b = blk[(n if has_prev else 0):(n if has_prev else 0) + n]
-        own_d = blk[cnt * n + (m if has_prev else 0):cnt * n + (m if has_prev else 0) + m]
-        assert rel_err(own_b, sub_jac[:n, :z]) <= 1e-10, ("bilinear rows", k, rel_err(own_b, sub_jac[:n, :z]))
-        assert rel_err(own_d, sub_jac[n:, :z]) <= 1e-10, ("derivative rows", k)
-        assert np.all(own_b[:, n + m:n + 2 * m] == 0.0)  # du columns: structural zeros that are still stored
-    if has_prev:
-        prev_b, prev_d = blk[:n], blk[cnt * n:cnt * n + m]
-        ref_b = np.zeros((n, z)); ref_b[:, :n] = np.eye(n)
-        ref_d = np.zeros((m, z)); ref_d[:, n:n + m] = np.eye(m)
-        assert np.array_equal(prev_b, ref_b) and np.array_equal(prev_d, ref_d), ("z_{k+1} half", k)
-
-
-def _hess_diag_block(get, k, z):
-    """Upper triangle (incl. diagonal) of diagonal block k and the off-diagonal block (k-1, k) of the full-size Hessian."""
-    tri = z * (z + 1) // 2
-    if k == 0:
-        return _tri_from_cols(get(0, tri), z), None
-    start = tri + (k - 1) * (z * z + tri)
-    v = get(start, start + z * z + tri)
-    Hd, Ho = np.zeros((z, z)), np.zeros((z, z))
-    pos = 0
-    for b in range(z):
-        Ho[:, b] = v[pos:pos + z]
-        pos += z
-        Hd[:b + 1, b] = v[pos:pos + b + 1]
-        pos += b + 1
-    return Hd, Ho
-
-
-def _tri_from_cols(v, z):
-    Hd = np.zeros((z, z))
-    pos = 0
-    for b in range(z):
-        Hd[:b + 1, b] = v[pos:pos + b + 1]
-        pos += b + 1
-    return Hd
-
-
-def _sampled_checks(prob_e, ev, n, m, ks, jac_get=None, hess_get=None, cons=None, mu=None, sigma=1.0, extra_objectives=()):
-    """Compare column block / Hessian diagonal block of every sampled knot with the two-knot oracle problem."""
-    traj = prob_e.trajectory
-    N, z = traj.N, traj.dim
-    K, D = N - 1, n + m
-    dt_idx = traj.components[traj.timestep][0]
-    G = prob_e.integrators[0].G
-    X = traj.data
-    for k in ks:
-        if k < K:
-            sub = _sub_problem(G, X[:, k:k + 2].T, n, m, z, dt_idx, extra_objectives)
-            ev_o = O.OracleEvaluator(sub)
-            r1, c1 = ev_o.jacobian_structure1()
-            sub_jac = _dense(r1, c1, ev_o.eval_constraint_jacobian(sub.Z0), (D, 2 * z))
-        if jac_get is not None:
-            blk, cnt = _jac_column_block(jac_get, k, z, D, K)
-            _check_jacobian_block(blk, cnt, k, sub_jac if k < K else None, n, m, z, K)
-            if k < K and cons is not None:
-                # chain vs sweep: the dense -E_k of the propagator chain applied to x_k equals exp(A_k) x_k of the sweep
-                own = blk[(n if k >= 1 else 0):(n if k >= 1 else 0) + n]
-                delta = cons[k * n:(k + 1) * n]
-                assert rel_err(own[:, :n] @ X[:n, k], delta - X[:n, k + 1]) <= 1e-10, ("chain vs sweep", k)
-        if cons is not None and k < K:
-            ref = ev_o.eval_constraint(sub.Z0)
-            assert rel_err(cons[k * n:(k + 1) * n], ref[:n]) <= 1e-10, ("bilinear defect", k)
-            assert rel_err(cons[K * n + k * m:K * n + (k + 1) * m], ref[n:]) <= 1e-10, ("derivative defect", k)
-        if hess_get is not None:
-            Hd, Ho = _hess_diag_block(hess_get, k, z)
-            if Ho is not None:
-                assert np.all(Ho == 0.0), ("off-diagonal block", k)  # these integrators never fill it (SURVEY.md section 8e)
-            if k < K:
-                mu_sub = np.concatenate([mu[k * n:(k + 1) * n], mu[K * n + k * m:K * n + (k + 1) * m]])
-                r1, c1 = ev_o.hessian_structure1()
-                Hs = _dense(r1, c1, ev_o.eval_hessian_lagrangian(sub.Z0, sigma, mu_sub), (2 * z, 2 * z))
-                assert rel_err(Hd, Hs[:z, :z]) <= 1e-8, ("diagonal block", k, rel_err(Hd, Hs[:z, :z]))
-                assert np.all(Hd[:n, :n] == 0.0)  # (x_k, x_k): identically zero for a defect linear in x
-            else:
-                # last knot: only the objective term of that knot
-                sub = _sub_problem(G, X[:, k - 1:k + 1].T, n, m, z, dt_idx, extra_objectives)
-                Hs = O.objective_full_hessian(sub, sub.Z0).toarray()[z:, z:]
-                assert rel_err(Hd, sigma * np.triu(Hs)) <= 1e-8, ("last knot", k)
-
-
-def _host_getter(vals):
-    return lambda lo, hi: vals[lo:hi]
 
 
 def test_config1_64_states_1000_knots():
@@ -145,7 +33,7 @@ def test_config1_64_states_1000_knots():
     cons = np.empty(ev.n_constraints); ev.eval_constraint(cons, Z)
     hes = np.empty(ev.n_hessian_entries); ev.eval_hessian_lagrangian(hes, Z, 0.7, mu)
     assert np.isfinite(jac).all() and np.isfinite(cons).all() and np.isfinite(hes).all()
-    _sampled_checks(prob, ev, n, m, (0, 1, 2, 311, 500, 998, 999), _host_getter(jac), _host_getter(hes), cons, mu, 0.7)
+    sampled_checks(prob, ev, n, m, (0, 1, 2, 311, 500, 998, 999), host_getter(jac), host_getter(hes), cons, mu, 0.7)
     ev.close()
 
 
@@ -161,7 +49,7 @@ def test_config2_hessian_256_states_2000_knots():
     mu = np.random.default_rng(2).standard_normal(ev.n_constraints)
     hes = np.empty(ev.n_hessian_entries); ev.eval_hessian_lagrangian(hes, Z, 1.3, mu)
     assert np.isfinite(hes).all()
-    _sampled_checks(prob, ev, n, m, (0, 1, 777, 1998, 1999), None, _host_getter(hes), None, mu, 1.3)
+    sampled_checks(prob, ev, n, m, (0, 1, 777, 1998, 1999), None, host_getter(hes), None, mu, 1.3)
     # the whole vector: everything outside the diagonal blocks is zero
     z = n + 2 * m + 1
     tri = z * (z + 1) // 2
@@ -177,11 +65,18 @@ def test_config2_hessian_256_states_2000_knots():
 
 def test_config3_256_states_16000_knots_chunked_chain():
     """The 8-GPU configuration's total size on ONE device: 2.2e9 Jacobian values (17.6 GB) stay in HBM, the propagator
-    chain runs in three workspace chunks; sampled column blocks (first / last of each chunk among them) come back for the
-    comparison.  (The sharded form of this size is covered by the two-rank tests and the shard tests.)"""
+    chain runs in two workspace chunks of 8000 intervals; the column blocks on both sides of the chunk boundary, and the first and
+    last, come back for the comparison.  (The sharded form of this size is covered by the two-rank tests and the shard tests.)"""
     import torch
     import dto_amd
     n, m, N = 256, 4, 16000
+    K = N - 1
+    # the chunking of dto_engine.cpp: chunk_size() caps a chunk by the workspace budget of the 9 chain matrices (40e9 bytes), rounded
+    # down to a multiple of 8; run_chain() spreads the intervals evenly over ceil(K / cap) chunks, rounded up to a multiple of 8
+    cap = max(8, int(40e9 / (9.0 * 256 * 256 * 8)) // 8 * 8)
+    nchunk = -(-K // cap)
+    per = min(cap, (-(-K // nchunk) + 7) // 8 * 8)
+    assert (cap, nchunk, per) == (8472, 2, 8000)
     prob = dto_amd.host.synthetic.make_scaled_problem(N, n, m)
     ev = dto_amd.Evaluator(prob, eval_hessian=False)
     dev = torch.device("cuda", 0)
@@ -190,20 +85,22 @@ def test_config3_256_states_16000_knots_chunked_chain():
     st = torch.cuda.current_stream(dev).cuda_stream
     dj = torch.empty(ev.n_jacobian_entries, dtype=torch.float64, device=dev)
     dg = torch.empty(ev.n_constraints, dtype=torch.float64, device=dev)
+    # the engine's own count of chunks: at 256 states the generator-subspace launch (A^2..A^4) runs once per chain chunk
+    ev.profile_enable(True)
+    ev.profile_reset()
     ev.eval_jacobian_dev(dZ.data_ptr(), dj.data_ptr(), st)
+    torch.cuda.synchronize()
+    chunks = ev.profile_get("basis_multi")[1]
+    ev.profile_enable(False)
+    assert chunks == nchunk, (chunks, nchunk)
     ev.eval_constraint_dev(dZ.data_ptr(), dg.data_ptr(), st)
     torch.cuda.synchronize()
     assert ev.last_stats()[1] >= 1
     assert bool(torch.isfinite(dj).all()) and bool(torch.isfinite(dg).all())
     cons = dg.cpu().numpy()
     get = lambda lo, hi: dj[lo:hi].cpu().numpy()
-    K = N - 1
-    cap = int(36e9 / (9.0 * 256 * 256 * 8)) // 8 * 8  # the engine's chunk capacity at 256 states (dto_engine.cpp chunk_size)
-    nchunk = -(-K // cap)
-    per = min(cap, (-(-K // nchunk) + 7) // 8 * 8)
-    assert nchunk == 3
-    ks = (0, 1, per - 1, per, per + 1, 2 * per - 1, 2 * per, 9000, K - 1, K)
-    _sampled_checks(prob, ev, n, m, ks, get, None, cons)
+    ks = (0, 1, per - 1, per, per + 1, K - 1, K)
+    sampled_checks(prob, ev, n, m, ks, get, None, cons)
     del dj, dg
     ev.close()
 
@@ -234,20 +131,19 @@ def test_config4_workload_1024_states_three_knots_vs_oracle():
     e = rel_err(jac, ev_o.eval_constraint_jacobian(Z))
     assert e <= 1e-10, e
     hes = np.empty(ev.n_hessian_entries); ev.eval_hessian_lagrangian(hes, Z, 0.9, mu)
-    ref = ev_o.eval_hessian_lagrangian(Z, 0.9, mu, skip_uu=True)
-    # (u_i, u_j) entries of the two interval knots: second-order Frechet terms, checked by differences below
+    # the whole Hessian, (u_i, u_j) entries of both interval knots included: their second-order Frechet terms by the complex step
+    ref = ev_o.eval_hessian_lagrangian(Z, 0.9, mu, uu="complex_step")
     z = p.z
-    uu = np.zeros(len(hes), dtype=bool)
     hr, hc = r1 - 1, c1 - 1
+    uu = np.zeros(len(hes), dtype=bool)
     for k in range(N - 1):
-        inb = (hr >= k * z + n) & (hr < k * z + n + m) & (hc >= k * z + n) & (hc < k * z + n + m)
-        uu |= inb
-    assert uu.sum() == (N - 1) * m * (m + 1) // 2
-    e = rel_err(hes[~uu], ref[~uu])
-    assert e <= 1e-8, e
-    # (u,u): mu' d2(delta)/du_i du_j + constraint + sigma * objective, by central differences of the engine's Jacobian and
-    # gradient along u_i (the reference's own bar for Hessians is atol = 1e-2, evaluator.jl:790; differences of an
-    # analytic Jacobian with h = 1e-4 give ~1e-6 here)
+        uu |= (hr >= k * z + n) & (hr < k * z + n + m) & (hc >= k * z + n) & (hc < k * z + n + m)
+    assert uu.sum() == (N - 1) * m * (m + 1) // 2 and np.abs(ref[uu]).max() > 1e-3
+    e = rel_err(hes, ref)
+    assert e <= 1e-8, (e, rel_err(hes[uu], ref[uu]))
+    # (u,u) once more, independently of the oracle: mu' d2(delta)/du_i du_j + constraint + sigma * objective, by central
+    # differences of the engine's Jacobian and gradient along u_i (the reference's own bar for Hessians is atol = 1e-2,
+    # evaluator.jl:790; differences of an analytic Jacobian with h = 1e-4 give ~1e-6 here)
     jr, jc = ev.jacobian_structure()
     h = 1e-4
     for k in range(N - 1):
@@ -308,10 +204,10 @@ def test_config4_workload_1024_states_64_knots_sampled():
     G = prob.integrators[0].G
     lin = [O.LinearRegularizer(n + 2 * m, m, np.full(m, 1e-2))]
     for k in (0, 1, 40, K - 1):
-        sub = _sub_problem(G, X[:, k:k + 2].T, n, m, z, n + 3 * m, lin)
+        sub = sub_problem(G, X[:, k:k + 2].T, n, m, z, n + 3 * m, lin)
         ev_o = O.OracleEvaluator(sub)
         r1, c1 = ev_o.jacobian_structure1()
-        sub_jac = _dense(r1, c1, ev_o.eval_constraint_jacobian(sub.Z0), (D, 2 * z))
+        sub_jac = dense(r1, c1, ev_o.eval_constraint_jacobian(sub.Z0), (D, 2 * z))
         has_prev = k >= 1
         for j in list(range(0, n, 97)) + list(range(n, z)):
             c = k * z + j
@@ -331,7 +227,7 @@ def test_config4_per_rank_share_1024_states_500_knots_of_4000():
     handle owning knots 1501..2000 -- 500 knots, the per-GPU share -- with every output resident in HBM (8.5 GB of Jacobian
     values, 6.4 GB of Hessian values).  Sampled knots of the shard against two-knot oracle problems: bilinear and derivative
     defects, Jacobian column blocks cut by the GLOBAL column pointers minus the shard's offset, the constraint rows and their
-    Jacobian entries against the closed form, one Hessian diagonal block ((u, u) entries left to the three-knot test above)."""
+    Jacobian entries against the closed form, one whole Hessian diagonal block."""
     import torch
     import dto_amd
     n, m, N, world, rank = 1024, 4, 4000, 8, 3
@@ -379,10 +275,10 @@ def test_config4_per_rank_share_1024_states_500_knots_of_4000():
     G = prob.integrators[0].G
     lin = [O.LinearRegularizer(n + 2 * m, m, np.full(m, 1e-2))]
     for k in (k0, k0 + 251, k0 + n_knots - 1):
-        sub = _sub_problem(G, X[:, k:k + 2].T, n, m, z, n + 3 * m, lin)
+        sub = sub_problem(G, X[:, k:k + 2].T, n, m, z, n + 3 * m, lin)
         ev_o = O.OracleEvaluator(sub)
         r1, c1 = ev_o.jacobian_structure1()
-        sub_jac = _dense(r1, c1, ev_o.eval_constraint_jacobian(sub.Z0), (D, 2 * z))
+        sub_jac = dense(r1, c1, ev_o.eval_constraint_jacobian(sub.Z0), (D, 2 * z))
         for j in list(range(0, n, 131)) + list(range(n, z)):
             cj = col(k * z + j)
             own_b = cj[n:2 * n]                        # rows of interval k-1 come first (every sampled knot has one)
@@ -394,8 +290,8 @@ def test_config4_per_rank_share_1024_states_500_knots_of_4000():
         assert rel_err(cons[kl * n:(kl + 1) * n], ref[:n]) <= 1e-10
         assert rel_err(cons[n_int * n + kl * m:n_int * n + (kl + 1) * m], ref[n:]) <= 1e-10
     del dj
-    # Hessian of the shard: one diagonal block against the oracle (mu of the interval's rows; the norm constraint of knot k adds
-    # its own (u, u) block, which lies among the entries left out)
+    # Hessian of the shard: one whole diagonal block against the oracle (mu of the interval's rows; the (u, u) terms by the complex
+    # step) plus the closed-form (u, u) block of the norm constraint of knot k
     dh = torch.empty(sh.hess_len, dtype=torch.float64, device=dev)
     ev.eval_hessian_dev(dZ.data_ptr(), 0.8, dmu.data_ptr(), dh.data_ptr(), st)
     torch.cuda.synchronize()
@@ -410,13 +306,17 @@ def test_config4_per_rank_share_1024_states_500_knots_of_4000():
         pos += z
         Hd[:b + 1, b] = blkv[pos:pos + b + 1]
         pos += b + 1
-    sub = _sub_problem(G, X[:, k:k + 2].T, n, m, z, n + 3 * m, lin)
+    sub = sub_problem(G, X[:, k:k + 2].T, n, m, z, n + 3 * m, lin)
     ev_o = O.OracleEvaluator(sub)
     mu_sub = np.concatenate([mu[k * n:(k + 1) * n], mu[K * n + k * m:K * n + (k + 1) * m]])
     r1, c1 = ev_o.hessian_structure1()
-    Hs = _dense(r1, c1, ev_o.eval_hessian_lagrangian(sub.Z0, 0.8, mu_sub, skip_uu=True), (2 * z, 2 * z))[:z, :z]
-    keep = np.ones((z, z), dtype=bool)
-    keep[n:n + m, n:n + m] = False
-    assert rel_err(Hd[keep], Hs[keep]) <= 1e-8, rel_err(Hd[keep], Hs[keep])
+    Hs = dense(r1, c1, ev_o.eval_hessian_lagrangian(sub.Z0, 0.8, mu_sub, uu="complex_step"), (2 * z, 2 * z))[:z, :z]
+    # g(u) = ||u|| - 1 at knot k (0-based; the constraint lists knots 2..N-1, 1-based): its row follows the K * D dynamics rows
+    u = U[:, k]
+    r = np.linalg.norm(u)
+    mu_c = mu[K * D + k - 1]
+    Hs[n:n + m, n:n + m] += np.triu(mu_c * (np.eye(m) / r - np.outer(u, u) / r**3))
+    assert np.abs(Hs[n:n + m, n:n + m]).max() > 1e-3
+    assert rel_err(Hd, Hs) <= 1e-8, (rel_err(Hd, Hs), rel_err(Hd[n:n + m, n:n + m], Hs[n:n + m, n:n + m]))
     assert np.all(Hd[:n, :n] == 0.0)
     ev.close()

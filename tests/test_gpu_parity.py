@@ -6,48 +6,9 @@ import numpy as np
 import pytest
 
 import dto_oracle as O
-from helpers import rel_err, run_all, to_engine
+from helpers import TOL, check_callbacks as _check, rel_err, to_engine
 
 pytestmark = pytest.mark.gpu
-
-TOL, TOL_H = 1e-10, 1e-8
-
-
-def _check(prob_o, Z=None, seed=0, hessian=True, tag="", closure_derivatives="numeric", tol_h=TOL_H):
-    import dto_amd
-    ev_o = O.OracleEvaluator(prob_o)
-    ev = dto_amd.Evaluator(to_engine(prob_o, closure_derivatives), eval_hessian=hessian)
-    try:
-        assert ev.n_variables == prob_o.n_vars
-        assert ev.n_constraints == ev_o.n_constraints
-        assert ev.n_dynamics_constraints == ev_o.n_dynamics_constraints
-        jr, jc = ev.jacobian_structure()
-        r1, c1 = ev_o.jacobian_structure1()
-        assert np.array_equal(jr, r1) and np.array_equal(jc, c1), "Jacobian structure"
-        hr, hc = ev.hessian_lagrangian_structure()
-        r1, c1 = ev_o.hessian_structure1()
-        assert np.array_equal(hr, r1) and np.array_equal(hc, c1), "Hessian structure"
-        lo, hi = ev.constraint_bounds()
-        lo_o, hi_o = ev_o.row_bounds()
-        assert np.array_equal(lo, lo_o) and np.array_equal(hi, hi_o)
-        rng = np.random.default_rng(seed)
-        Z = prob_o.Z0.copy() if Z is None else Z
-        mu = rng.standard_normal(ev_o.n_constraints)
-        out = run_all(ev, prob_o, Z, mu, sigma=0.7, hessian=hessian)
-        errs = {
-            "f": rel_err(out["f"], ev_o.eval_objective(Z)),
-            "grad": rel_err(out["grad"], ev_o.eval_objective_gradient(Z)),
-            "cons": rel_err(out["cons"], ev_o.eval_constraint(Z)),
-            "jac": rel_err(out["jac"], ev_o.eval_constraint_jacobian(Z)),
-        }
-        if hessian:
-            errs["hess"] = rel_err(out["hess"], ev_o.eval_hessian_lagrangian(Z, 0.7, mu))
-        print(tag, errs, ev.last_stats())
-        for k, v in errs.items():
-            assert v <= (tol_h if k == "hess" else TOL), (tag, k, v)
-    finally:
-        ev.close()
-
 
 def test_readme_problem():
     _check(O.make_readme_problem(), tag="readme")
@@ -171,11 +132,12 @@ def test_large_state_shapes_against_the_oracle(n, m, N):
     _check(O.make_scaled_problem(N, n, m, seed=11), tag=f"large-state n={n}")
 
 
-@pytest.mark.parametrize("n,m", [(64, 4), (128, 2)])
+@pytest.mark.parametrize("n,m", [(64, 4), (128, 2), (384, 2), (320, 2)])
 def test_both_polynomial_forms_of_the_matrix_exponential(n, m):
     """Option "expm_form": the two-product degree-16 form (radius 0.78) and the three-product order-26 form (radius 2.82) of
     the propagator chain are each checked against the oracle on the same point (alpha ~ 4.5: 3 squarings against 1), and
-    against each other; n = 64 takes the plain power chain, n = 128 the generator-subspace powers."""
+    against each other; n = 64 takes the plain power chain, n = 128 the generator-subspace powers, 384 the ring core's squarings,
+    320 (npad % 128 != 0) every chain GEMM on 64 x 64 tiles."""
     import dto_amd
     p = O.make_scaled_problem(4, n, m, seed=3)
     Z = p.Z0.copy()
@@ -200,7 +162,7 @@ def test_both_polynomial_forms_of_the_matrix_exponential(n, m):
         ev.close()
 
 
-@pytest.mark.parametrize("n,m,scale", [(64, 3, 0.15), (128, 2, 0.5), (40, 4, 0.6)])
+@pytest.mark.parametrize("n,m,scale", [(64, 3, 0.15), (128, 2, 0.5), (40, 4, 0.6), (384, 2, 0.5), (320, 2, 0.15)])
 def test_no_squaring_inside_the_radius(n, m, scale):
     """Small steps (alpha below the radius of the polynomial form in use): the last polynomial product is exp(A_k) itself and
     stores into the Jacobian slab -- no squaring launch.  scale = 0.15 stays inside the degree-16 radius (two products),

@@ -426,3 +426,62 @@ def test_tdb_passes_the_reference_fd_bars():
     eps = 1e-6
     Jfd = np.stack([(ev.eval_constraint(Z + eps * e) - ev.eval_constraint(Z - eps * e)) / (2 * eps) for e in np.eye(p.n_vars)], axis=1)
     assert np.allclose(J, Jfd, atol=1e-3) and np.abs(J - Jfd).max() <= 1e-8
+
+
+def _frechet_case(n, norm1, skew, seed):
+    """A with ||A||_1 = norm1 and two directions of unit scale (skew-symmetric ones for skew generators)."""
+    rng = np.random.default_rng(seed)
+    A, E1, E2 = (rng.standard_normal((n, n)) for _ in range(3))
+    if skew:
+        A, E1, E2 = A - A.T, E1 - E1.T, E2 - E2.T
+    A *= norm1 / np.abs(A).sum(axis=0).max()
+    return A, E1 / np.sqrt(n), E2 / np.sqrt(n), rng.standard_normal(n)
+
+
+@pytest.mark.parametrize("skew", [False, True])
+@pytest.mark.parametrize("norm1", [0.1, 1.0, 5.4, 20.0])
+@pytest.mark.parametrize("n", [5, 40, 130])
+def test_second_frechet_complex_step_matches_the_block_exponential(n, norm1, skew):
+    """The oracle's (u, u) terms above 256 states: Im[L(A + i h E1, E2)] x / h against the top-right block of the 3n x 3n
+    block-triangular exponential, from inside the Pade-3 radius to past the scaling threshold of Pade 13 (5.37: squarings), and
+    symmetric in (E1, E2) although the complex step perturbs only one of them."""
+    A, E1, E2, x = _frechet_case(n, norm1, skew, seed=n + int(10 * norm1) + skew)
+    ref = O._second_frechet_action(A, E1, E2, x)
+    cs = O._second_frechet_action_cs(A, E1, E2, x)
+    cs_t = O._second_frechet_action_cs(A, E2, E1, x)
+    scale = np.abs(ref).max()
+    assert scale > 1e-3
+    assert np.abs(cs - ref).max() <= 1e-12 * scale, np.abs(cs - ref).max() / scale
+    assert np.abs(cs_t - cs).max() <= 1e-12 * scale
+    # the diagonal pair (E1 = E2) as the Hessian's (u_j, u_j) entries take it
+    ref = O._second_frechet_action(A, E1, E1, x)
+    assert np.abs(O._second_frechet_action_cs(A, E1, E1, x) - ref).max() <= 1e-12 * np.abs(ref).max()
+
+
+@pytest.mark.parametrize("n,m,skew", [(12, 3, False), (30, 2, True)])
+def test_bilinear_block_hessian_complex_step_equals_the_block_form(n, m, skew):
+    """A whole (u, u)-including Hessian block, and the evaluator's Hessian built on it, in both forms; "auto" is the block form up to
+    256 states and the complex step above."""
+    p = O.make_scaled_problem(3, n, m, seed=n, with_constraint=True, skew=skew)
+    zk = p.Z0[:p.z].copy()
+    zk[p.dt_idx] = 2.0   # ||dt G(u)||_1 = 23 and 11, past 5.4: the squaring branch
+    mu = np.random.default_rng(n).standard_normal(n)
+    Hb = O.bilinear_block_hessian(p.integrators[0], p, zk, mu, uu="block")
+    Hc = O.bilinear_block_hessian(p.integrators[0], p, zk, mu, uu="complex_step")
+    uu = slice(n, n + m)
+    assert np.abs(Hb[uu, uu]).max() > 1e-2
+    assert np.abs(Hc - Hb).max() <= 1e-12 * np.abs(Hb).max()
+    assert np.array_equal(Hc, Hc.T)
+    assert np.array_equal(O.bilinear_block_hessian(p.integrators[0], p, zk, mu), Hb)   # "auto" at n <= 256
+    ev = O.OracleEvaluator(p)
+    lam = np.random.default_rng(1).standard_normal(ev.n_constraints)
+    hb = ev.eval_hessian_lagrangian(p.Z0, 0.6, lam, uu="block")
+    hc = ev.eval_hessian_lagrangian(p.Z0, 0.6, lam, uu="complex_step")
+    assert np.abs(hc - hb).max() <= 1e-12 * max(1.0, np.abs(hb).max())
+    with pytest.raises(ValueError):
+        O.bilinear_block_hessian(p.integrators[0], p, zk, mu, uu="skip")
+
+
+def test_uu_auto_switches_to_the_complex_step_above_256_states():
+    assert O._uu_action("auto", O.UU_BLOCK_MAX_STATES) is O._second_frechet_action
+    assert O._uu_action("auto", O.UU_BLOCK_MAX_STATES + 1) is O._second_frechet_action_cs
