@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -271,6 +272,26 @@ struct dto_handle {
     std::vector<Slab> cons_segments;                                     // every rank's row segments of g ...
     std::vector<int> cons_segment_root;                                  // ... and the rank that owns each
     int64_t* d_ranges = nullptr;
+    // Hessian-vector products (dto_eval_hessian_product[_dev]): H is assembled once per point into a private slab, its entries
+    // that can be non-zero are gathered into a row-major copy of both triangles, and every product at that point is one launch
+    // (dto_hess_product.hip).  The point is (Z, sigma, mu) bit for bit plus `gen`, which every dto_set_external, dto_set_option and
+    // failed call bumps.
+    double* hp_slab = nullptr;       // [hess_len], allocated at the first product
+    bool hp_slab_primed = false;     // written in full once: later points clear only the variable runs (as a bound output)
+    bool hp_index = false;
+    KHessProduct hp{};
+    int64_t hp_nnz = 0;              // entries of the row-major copy (odd rows padded)
+    int64_t* d_hp_pos = nullptr;     // [hp_nnz] slab position of every entry, -1 for padding
+    double* d_hp_val = nullptr;
+    double* d_hp_Z = nullptr;        // the cached point
+    double* d_hp_mu = nullptr;
+    double* d_hp_v = nullptr;        // host-pointer form: v
+    int32_t* d_hp_eq = nullptr;
+    double hp_sigma = 0.0;
+    bool hp_valid = false;
+    uint64_t gen = 0, hp_gen = 0;
+    double hp_setup_ms = 0.0;        // host time of the index build ...
+    double hp_bytes = 0.0;           // ... and the device bytes of the private slab and the index
     std::vector<void*> owned;  // device allocations to free
 
     ~dto_handle();
@@ -340,7 +361,7 @@ struct ProfScope {
 };
 // (for the bandwidth-bound categories from CAT_ZERO on, `flops` carries the launch's algorithmic BYTES)
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11 };
 
 // ------------------------------------------------------------------------------------------
 // structure
@@ -1473,7 +1494,8 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
                              (size_t)h->info.hess_len * sizeof(double) >= ((size_t)256 << 20) &&
                              !h->integ_kind.empty() && h->integ_kind[0] == DTO_INTEGRATOR_BILINEAR;
     bool zero_joined = true;
-    if (h->bound[1] == dH && h->primed[1] && ensure_bind_runs(h, 1))   // bound output: structural zeros are in place
+    // bound output, or the private slab of the Hessian-vector products: structural zeros are in place
+    if (((h->bound[1] == dH && h->primed[1]) || (dH == h->hp_slab && h->hp_slab_primed)) && ensure_bind_runs(h, 1))
         launch_zero_runs(st, h->d_bind_start[1], h->d_bind_len[1], h->n_bind_runs[1], dH);
     else if (zero_beside) {
         // fill!(H, 0), evaluator.jl:571 -- on the second stream: the fill is HBM-bound, the sweeps that open the bilinear block
@@ -1836,6 +1858,7 @@ double* staging(dto_handle* h, size_t n) {
 
 void drop_caches(dto_handle* h) {
     for (auto& b : h->bil) { b.cache_kind = 0; b.p_terms = false; b.plan_q = 0; }
+    ++h->gen;  // (the Hessian-vector products' cached point as well)
 }
 void unprime(dto_handle* h) { h->primed[0] = h->primed[1] = false; }
 
@@ -1998,6 +2021,186 @@ void check_against_slab(dto_handle* h, const double* d_slab, const double* assem
 
 void upload_Z(dto_handle* h, const double* Z) {
     HIP_CHECK(hipMemcpyAsync(h->d_Z, Z, sizeof(double) * (size_t)h->n_vars, hipMemcpyHostToDevice, h->stream));
+}
+
+// ---- Hessian-vector products (dto_eval_hessian_product[_dev], dto_hess_product.hip)
+
+// Walks positions of the unsharded Hessian slab in slab order and names the (row, col) of each, 0-based: the closed forms
+// dto_hessian_structure emits (knot blocks column by column, then the CSC tail of the global-variable columns).
+struct HessCursor {
+    const dto_handle* h;
+    int64_t z, tri, blk;
+    int64_t kn = 0, b = 0, r = 0;  // knot block, column inside it, entry inside that column
+    int64_t j = 0, e = -1;         // e >= 0: entry e of the tail, in global column j
+    explicit HessCursor(const dto_handle* h_) : h(h_), z(h_->z), tri(h_->z * (int64_t)(h_->z + 1) / 2), blk(h_->z * (int64_t)h_->z + tri) {}
+    int64_t col_off(int64_t bb) const { return kn == 0 ? bb * (bb + 1) / 2 : bb * z + bb * (bb + 1) / 2; }
+    void tail_col() { while (j < h->gd && e >= h->tail_colptr[(size_t)j + 1]) ++j; }
+    void seek(int64_t pos) {
+        if (pos >= h->hess_block_nnz) {
+            e = pos - h->hess_block_nnz;
+            j = 0;
+            tail_col();
+            return;
+        }
+        e = -1;
+        kn = pos < tri ? 0 : 1 + (pos - tri) / blk;
+        const int64_t local = pos - hess_block_start(h, kn);
+        int64_t lo = 0, hi = z - 1;  // the last column whose entries start at or before `local`
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) / 2;
+            if (col_off(mid) <= local) lo = mid; else hi = mid - 1;
+        }
+        b = lo;
+        r = local - col_off(b);
+    }
+    void next() {
+        if (e >= 0) { ++e; tail_col(); return; }
+        if (++r < (kn == 0 ? b + 1 : z + b + 1)) return;
+        r = 0;
+        if (++b < z) return;
+        b = 0;
+        if (++kn < h->N) return;
+        e = 0;
+        j = 0;
+        tail_col();
+    }
+    void at(int64_t& row, int64_t& col) const {
+        if (e >= 0) { row = h->tail_rows[(size_t)e]; col = h->N * z + j; return; }
+        col = kn * z + b;
+        row = kn == 0 ? r : (r < z ? (kn - 1) * z + r : kn * z + (r - z));
+    }
+};
+
+// Once per handle, on the host: the row-major copy of both triangles.  Its entries are the slab positions that can be non-zero
+// (the Hessian hand-off plan: variable runs and constants, each position once); an off-diagonal position counts for (i, j) and
+// (j, i), as MOI defines the product.  Entries are emitted in slab order, which is column-major over the upper triangle, so every
+// row of the copy lists its columns in ascending order (a duplicate (i, j) in the tail stays a separate entry, summed in order).
+void build_hp_index(dto_handle* h) {
+    if (h->hp_index) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t nv = h->n_vars;
+    if (nv >= ((int64_t)1 << 31)) throw HipError{"Hessian-vector products: n_vars does not fit their 32-bit column indices"};
+    build_raw_plans(h);
+    const XferPlan& p = h->hess_plan;
+    std::vector<std::pair<int64_t, int64_t>> runs;
+    for (size_t i = 0; i < p.start.size(); ++i)
+        if (p.len[i] > 0) runs.emplace_back(p.start[i], p.len[i]);
+    for (int64_t q : p.one_pos) runs.emplace_back(q, 1);
+    std::sort(runs.begin(), runs.end());
+    auto walk = [&](auto&& emit) {
+        HessCursor cur(h);
+        int64_t done = 0;  // every position below this one was visited
+        for (auto& rl : runs) {
+            const int64_t a = std::max(rl.first, done), end = rl.first + rl.second;
+            if (a >= end) continue;
+            if (a < 0 || end > h->info.hess_len) throw HipError{"Hessian-vector products: hand-off plan outside the slab"};
+            cur.seek(a);
+            for (int64_t q = a; q < end; ++q, cur.next()) {
+                int64_t row, col;
+                cur.at(row, col);
+                if (row < 0 || row >= nv || col < 0 || col >= nv) throw HipError{"Hessian-vector products: entry outside the matrix"};
+                emit(row, col, q);
+            }
+            done = end;
+        }
+    };
+    std::vector<int32_t> len((size_t)nv, 0);
+    walk([&](int64_t row, int64_t col, int64_t) { ++len[(size_t)row]; if (row != col) ++len[(size_t)col]; });
+    std::vector<int64_t> start((size_t)nv);
+    int64_t nnz = 0;
+    for (int64_t r = 0; r < nv; ++r) {  // every row starts at an even entry (16-byte loads of value pairs)
+        start[(size_t)r] = nnz;
+        nnz += len[(size_t)r];
+        nnz += nnz & 1;
+    }
+    std::vector<int32_t> col((size_t)std::max<int64_t>(nnz, 2), 0);
+    std::vector<int64_t> pos(col.size(), -1);
+    std::vector<int64_t> fill(start);
+    walk([&](int64_t row, int64_t c, int64_t q) {
+        int64_t& a = fill[(size_t)row];
+        col[(size_t)a] = (int32_t)c;
+        pos[(size_t)a++] = q;
+        if (row != c) {
+            int64_t& t = fill[(size_t)c];
+            col[(size_t)t] = (int32_t)row;
+            pos[(size_t)t++] = q;
+        }
+    });
+    // classes of rows by length: 4, 16 or 64 lanes per row
+    static const int G[3] = {4, 16, 64};
+    auto cls = [](int32_t l) { return l <= 16 ? 0 : l <= 128 ? 1 : 2; };
+    std::vector<int32_t> rows;
+    rows.reserve((size_t)nv);
+    KHessProduct& k = h->hp;
+    k = KHessProduct{};
+    for (int c = 0; c < 3; ++c) {
+        const int64_t r0 = (int64_t)rows.size();
+        for (int64_t r = 0; r < nv; ++r)
+            if (cls(len[(size_t)r]) == c) rows.push_back((int32_t)r);
+        const int64_t nr = (int64_t)rows.size() - r0;
+        if (nr == 0) continue;
+        const int per = 256 / G[c];
+        k.row0[k.n_cls] = r0;
+        k.cls_g[k.n_cls] = G[c];
+        k.blk0[k.n_cls + 1] = k.blk0[k.n_cls] + (nr + per - 1) / per;
+        ++k.n_cls;
+        k.row0[k.n_cls] = (int64_t)rows.size();
+    }
+    k.start = own(h, dupload(start));
+    k.len = own(h, dupload(len));
+    k.col = own(h, dupload(col));
+    k.rows = own(h, dupload(rows));
+    h->d_hp_pos = own(h, dupload(pos));
+    h->d_hp_val = own(h, dalloc<double>(col.size()));
+    k.val = h->d_hp_val;
+    h->hp_nnz = (int64_t)col.size();
+    h->d_hp_Z = own(h, dalloc<double>((size_t)nv));
+    h->d_hp_mu = own(h, dalloc<double>((size_t)std::max<int64_t>(h->n_cons, 1)));
+    h->d_hp_eq = own(h, dalloc<int32_t>(1));
+    h->hp_index = true;
+    h->hp_bytes = 8.0 * (double)h->info.hess_len + (8.0 + 4.0 + 8.0) * (double)h->hp_nnz + (8.0 + 4.0 + 4.0) * (double)nv;
+    h->hp_setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// y = H(Z; sigma, mu) v.  At a new point: do_hessian into the private slab, one gather into the row-major copy; at the cached
+// point (Z, sigma, mu bit for bit, no dto_set_external / dto_set_option / failed call since): the product launch alone, after one
+// device-side compare with a 4-byte readback.
+void hess_product(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dv, double* dy, hipStream_t st) {
+    build_hp_index(h);
+    bool hit = h->hp_valid && h->hp_gen == h->gen && memcmp(&sigma, &h->hp_sigma, sizeof(double)) == 0;
+    if (hit) {
+        int32_t* flag = reinterpret_cast<int32_t*>(h->h_pinned + 26);
+        *flag = 1;
+        HIP_CHECK(hipMemcpyAsync(h->d_hp_eq, flag, sizeof(int32_t), hipMemcpyHostToDevice, st));
+        launch_bits_equal(st, dZ, h->d_hp_Z, h->n_vars, h->d_hp_eq);
+        launch_bits_equal(st, dmu, h->d_hp_mu, h->n_cons, h->d_hp_eq);
+        HIP_CHECK(hipMemcpyAsync(flag, h->d_hp_eq, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        hit = *flag != 0;
+    }
+    if (!hit) {
+        h->hp_valid = false;
+        if (!h->hp_slab) h->hp_slab = own(h, dalloc<double>((size_t)h->info.hess_len));
+        do_hessian(h, dZ, sigma, dmu, h->hp_slab, st);
+        h->hp_slab_primed = true;
+        {
+            ProfScope ps(h, st, CAT_HESS_PRODUCT, 24.0 * (double)h->hp_nnz);  // position, slab entry, value
+            launch_hess_gather(st, h->hp_slab, h->d_hp_pos, h->hp_nnz, h->d_hp_val);
+        }
+        HIP_CHECK(hipMemcpyAsync(h->d_hp_Z, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
+        if (h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->d_hp_mu, dmu, sizeof(double) * (size_t)h->n_cons, hipMemcpyDeviceToDevice, st));
+        h->hp_sigma = sigma;
+        h->hp_gen = h->gen;
+        h->hp_valid = true;
+    }
+    // bytes: values and columns of every entry, and per row its start, length, id, v and y (v read once: it stays in cache)
+    ProfScope ps(h, st, CAT_HESS_PRODUCT, 12.0 * (double)h->hp_nnz + 32.0 * (double)h->n_vars);
+    launch_hess_spmv(st, h->hp, dv, dy);
+}
+
+void hess_product_applies(const dto_handle* h) {
+    if (!h->eval_hessian) throw HipError{"handle was created with eval_hessian = 0"};
+    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{"Hessian-vector products need an unsharded handle"};
 }
 
 }  // namespace
@@ -2764,6 +2967,7 @@ int dto_set_external(dto_handle* h, int32_t n, const dto_external_values* v) {
     if (n != h->n_ext_int + h->n_ext_con + h->n_ext_obj || (n > 0 && !v))
         return fail(h, "dto_set_external: one entry per external term is required (integrators, constraints, objectives)");
     for (int i = 0; i < n && i < (int)h->ext.size(); ++i) h->ext[i].v = v[i];
+    ++h->gen;  // new blocks: the Hessian-vector products' cached point is stale
     return 0;
 }
 
@@ -2788,6 +2992,12 @@ int dto_eval_hessian_dev(dto_handle* h, const double* dZ, double sigma, const do
         if (!h->eval_hessian) throw HipError{"handle was created with eval_hessian = 0"};
         do_hessian(h, dZ, sigma, dmu, dvals, (hipStream_t)stream);
         if (h->bound[1] == dvals) h->primed[1] = true;
+    }, G_ASYNC, (hipStream_t)stream);
+}
+int dto_eval_hessian_product_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dv, double* dy, void* stream) {
+    return guarded(h, [&] {
+        hess_product_applies(h);
+        hess_product(h, dZ, sigma, dmu, dv, dy, (hipStream_t)stream);
     }, G_ASYNC, (hipStream_t)stream);
 }
 
@@ -2879,6 +3089,21 @@ int dto_eval_hessian(dto_handle* h, const double* Z, double sigma, const double*
         }
         do_hessian(h, h->d_Z, sigma, h->d_mu, o, h->stream);
         HIP_CHECK(hipMemcpyAsync(vals, o, sizeof(double) * (size_t)h->info.hess_len, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+
+// y = H(Z; sigma, mu) v -- MOI.eval_hessian_lagrangian_product
+int dto_eval_hessian_product(dto_handle* h, const double* Z, double sigma, const double* mu, const double* v, double* y) {
+    return guarded(h, [&] {
+        hess_product_applies(h);
+        upload_Z(h, Z);
+        if (h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->d_mu, mu, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        if (!h->d_hp_v) h->d_hp_v = own(h, dalloc<double>((size_t)h->n_vars));
+        HIP_CHECK(hipMemcpyAsync(h->d_hp_v, v, sizeof(double) * (size_t)h->n_vars, hipMemcpyHostToDevice, h->stream));
+        double* o = staging(h, (size_t)h->n_vars);
+        hess_product(h, h->d_Z, sigma, h->d_mu, h->d_hp_v, o, h->stream);
+        HIP_CHECK(hipMemcpyAsync(y, o, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToHost, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
     }, G_BLOCKING);
 }
@@ -3105,6 +3330,7 @@ int dto_bind_output_dev(dto_handle* h, int32_t vector, double* dptr) {
 // ---- measurement
 int dto_set_option(dto_handle* h, const char* name, int64_t value) {
     if (!h || !name) return 1;
+    ++h->gen;  // any option may change what the Hessian-vector products' cached point holds
     if (std::string(name) == "reuse_forward_sweep") {
         h->reuse = value != 0;
         drop_caches(h);
@@ -3196,6 +3422,15 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "assembly")) cat = CAT_ASSEMBLY;
         else if (!strcmp(name, "expmv")) cat = CAT_SWEEP;
         else if (!strcmp(name, "expmv_adjoint")) cat = CAT_SWEEP_ADJOINT;
+        else if (!strcmp(name, "hess_product")) cat = CAT_HESS_PRODUCT;
+        else if (!strcmp(name, "hess_product_setup")) {
+            // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
+            // slab and the index
+            if (ms) *ms = h->hp_setup_ms;
+            if (launches) *launches = 0;
+            if (flops) *flops = h->hp_bytes;
+            return;
+        }
         else if (strcmp(name, "all")) throw HipError{"dto_profile_get: unknown name"};
         double tot = 0, fl = 0;
         int64_t n = 0;

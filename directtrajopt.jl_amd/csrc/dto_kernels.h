@@ -429,6 +429,24 @@ void launch_add(hipStream_t st, double* dst, const double* src, int64_t n);  // 
 // *flag = 0 if a and b differ in any bit (flag preset to 1 by the caller)
 void launch_bits_equal(hipStream_t st, const double* a, const double* b, int64_t n, int32_t* flag);
 
+// Hessian-vector products (dto_hess_product.hip): y = H v from a row-major copy of both triangles of the Hessian slab.
+// Rows are sorted into up to three classes of 4 / 16 / 64 lanes per row; class c owns rows[row0[c] .. row0[c+1]) and the
+// blocks [blk0[c], blk0[c+1]) of the launch (256 threads each).  Every row starts at an even entry (an odd-length row is
+// followed by one padding entry, which the kernel never adds).
+struct KHessProduct {
+    const int64_t* start;   // [n_vars] first entry of each row (even)
+    const int32_t* len;     // [n_vars] entries of each row
+    const int32_t* col;     // [nnz, even]
+    const double* val;      // [nnz]
+    const int32_t* rows;    // [n_vars] row ids, class by class
+    int64_t row0[4], blk0[4];
+    int32_t cls_g[3];
+    int32_t n_cls;
+};
+// val[i] = slab[pos[i]] (pos -1: padding, written as 0)
+void launch_hess_gather(hipStream_t st, const double* slab, const int64_t* pos, int64_t n, double* val);
+void launch_hess_spmv(hipStream_t st, const KHessProduct& p, const double* v, double* y);
+
 // Powers of A_k from the generator subspace: A_k = dt*sum_j ubar_j G_j lives in an (m+1)-dimensional
 // matrix space, so A_k^r = sum over multisets alpha of size r of (dt^r prod ubar_alpha) * S_alpha with
 // S_alpha = sum of the distinct orderings of the product G_alpha1 ... G_alphar, shared by all knots.

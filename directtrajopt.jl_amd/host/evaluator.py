@@ -340,6 +340,16 @@ class Evaluator:
         self._stage_external(Z, con_need=2, obj_need=2 if sigma != 0.0 else -1, mu=mu)
         self._check(self._lib.dto_eval_hessian(self._h, _dp(Z), float(sigma), _dp(mu), _out(H, self.shard.hess_len, "H")))
 
+    def eval_hessian_lagrangian_product(self, y, Z, v, sigma, mu):  # MOI.eval_hessian_lagrangian_product (y = H v)
+        """y = H(Z; sigma, mu) v with H symmetric (its upper triangle is what eval_hessian_lagrangian returns).  Products at the
+        same (Z, sigma, mu) reuse the Hessian the first one assembled on the device -- unless external blocks are staged again,
+        which closure-based problems do on every call."""
+        Z = self._Z(Z)
+        mu = _in(mu, self.n_constraints, "mu")
+        v = _in(v, self.n_variables, "v")
+        self._stage_external(Z, con_need=2, obj_need=2 if sigma != 0.0 else -1, mu=mu)
+        self._check(self._lib.dto_eval_hessian_product(self._h, _dp(Z), float(sigma), _dp(mu), _dp(v), _out(y, self.n_variables, "y")))
+
     def eval_constraint_jacobian_product(self, y, Z, w):  # evaluator.jl:406 (y = J w)
         Z = self._Z(Z)
         w = _in(w, self.n_variables, "w")
@@ -386,6 +396,10 @@ class Evaluator:
     def eval_hessian_dev(self, dZ, sigma, dmu, dvals, stream=0, Z_host=None, mu_host=None):
         self._stage_external(Z_host, con_need=2, obj_need=2 if sigma != 0.0 else -1, mu=mu_host)
         self._check(self._lib.dto_eval_hessian_dev(self._h, dZ, float(sigma), dmu, dvals, stream))
+
+    def eval_hessian_product_dev(self, dZ, sigma, dmu, dv, dy, stream=0, Z_host=None, mu_host=None):
+        self._stage_external(Z_host, con_need=2, obj_need=2 if sigma != 0.0 else -1, mu=mu_host)
+        self._check(self._lib.dto_eval_hessian_product_dev(self._h, dZ, float(sigma), dmu, dv, dy, stream))
 
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DTO_ABI_VERSION 7
+#define DTO_ABI_VERSION 8
 
 /* integrator kinds (src/integrators/) */
 #define DTO_INTEGRATOR_BILINEAR 1   /* bilinear_integrator.jl:61-85   */
@@ -254,6 +254,15 @@ int dto_eval_hessian(dto_handle* h, const double* Z, double sigma, const double*
 /* y = J w  /  y = J' w without materialising J on the host (evaluator.jl:406-456) */
 int dto_eval_jacobian_product(dto_handle* h, const double* Z, const double* w, double* y);
 int dto_eval_jacobian_transpose_product(dto_handle* h, const double* Z, const double* w, double* y);
+/* y = H(Z; sigma, mu) v, H the symmetric matrix whose upper triangle is dto_hessian_structure / dto_eval_hessian
+   (off-diagonal entries count for (i,j) and (j,i), as MOI defines it); MOI.eval_hessian_lagrangian_product.
+   y [n_vars] is written in full (0 where H has no entry); H is exactly what dto_eval_hessian returns at that point.
+   Unsharded handles created with eval_hessian = 1 only (an error with text otherwise).  The engine assembles H once per
+   point into a private device slab and keeps a compact row-major copy of both triangles; a product at the same
+   (Z, sigma, mu) -- bit for bit, with no dto_set_external, dto_set_option or failed call since -- is one launch.  The copy
+   costs the handle a second Hessian slab plus 20 bytes per stored entry (about 2 x 1 % of the slab). */
+int dto_eval_hessian_product(dto_handle* h, const double* Z, double sigma, const double* mu,
+                             const double* v, double* y);
 
 /* device-pointer callbacks (asynchronous on `stream`; outputs stay in HBM) */
 int dto_eval_objective_dev(dto_handle* h, const double* dZ, double* df, void* stream);
@@ -262,6 +271,9 @@ int dto_eval_constraint_dev(dto_handle* h, const double* dZ, double* dg, void* s
 int dto_eval_jacobian_dev(dto_handle* h, const double* dZ, double* dvals, void* stream);
 int dto_eval_hessian_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu,
                          double* dvals, void* stream);
+/* the same product on device pointers; waits on one 4-byte readback when the handle holds a cached point */
+int dto_eval_hessian_product_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu,
+                                 const double* dv, double* dy, void* stream);
 
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
@@ -384,9 +396,12 @@ int dto_profile_reset(dto_handle* h);
  * (generator-subspace GEMM), "expmv" (forward generator sweeps and the pairing products), "expmv_adjoint" (the Hessian's adjoint
  * sweep: its dominant kernel), "all"; "basis_multi" / "basis_k" (the two generator-subspace launches apart: A^2..A^4, and the
  * factor K), and the bandwidth-bound assembly kernels "zero_fill" (the Jacobian's / Hessian's fill!(., 0)), "build_A" (A_k from the
- * generators), "assembly" (the writers of the bilinear Jacobian's tangent columns).
- * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the three assembly names the
- * third output is the launches' algorithmic BYTES (what they must read and write), not FLOPs. */
+ * generators), "assembly" (the writers of the bilinear Jacobian's tangent columns), "hess_product" (the Hessian-vector products'
+ * gather into their compact copy and the product launches; the Hessian they assemble counts under its own names).
+ * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names the
+ * third output is the launches' algorithmic BYTES (what they must read and write), not FLOPs.
+ * "hess_product_setup" returns the host milliseconds of the products' index build (once per handle), 0 launches, and the device
+ * bytes of their private slab and index. */
 int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launches, double* flops);
 /* diagnostics of the last Jacobian call: max squarings used, Taylor terms used by the tangent sweep */
 int dto_last_stats(const dto_handle* h, int32_t* max_squarings, int32_t* expmv_terms);

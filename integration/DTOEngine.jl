@@ -1,4 +1,4 @@
-# DTOEngine.jl -- the reference-side binding of libdto_engine.so (include/dto_engine.h, ABI version 6).
+# DTOEngine.jl -- the reference-side binding of libdto_engine.so (include/dto_engine.h, ABI version 8).
 #
 # Drop this file into DirectTrajOpt.jl (e.g. src/solvers/DTOEngine.jl, `include`d from src/solvers/_solvers.jl) and
 # replace the evaluator at the two swap points:
@@ -38,7 +38,7 @@ using ..Constraints: AbstractNonlinearConstraint, NonlinearKnotPointConstraint, 
 using ..CommonInterface: evaluate!, eval_jacobian, eval_hessian_of_lagrangian
 
 const lib = get(ENV, "DTO_ENGINE_LIB", "libdto_engine.so")
-const DTO_ABI_VERSION = Int32(7)
+const DTO_ABI_VERSION = Int32(8)
 
 const DTO_INTEGRATOR_BILINEAR = Int32(1)
 const DTO_INTEGRATOR_DERIVATIVE = Int32(2)
@@ -539,7 +539,7 @@ end
 
 # ---- MOI surface (evaluator.jl:291-456) -----------------------------------------------------------------------------
 MOI.initialize(::GPUEvaluator, features) = nothing
-MOI.features_available(ev::GPUEvaluator) = ev.eval_hessian ? [:Grad, :Jac, :Hess] : [:Grad, :Jac]
+MOI.features_available(ev::GPUEvaluator) = ev.eval_hessian ? [:Grad, :Jac, :Hess, :HessVec] : [:Grad, :Jac]
 MOI.jacobian_structure(ev::GPUEvaluator) = ev.jacobian_structure
 MOI.hessian_lagrangian_structure(ev::GPUEvaluator) = ev.hessian_structure
 
@@ -571,6 +571,16 @@ end
 function MOI.eval_hessian_lagrangian(ev::GPUEvaluator, H::AbstractVector{Float64}, Z::AbstractVector{Float64}, σ::Float64, μ::AbstractVector{Float64})
     stage_external!(ev, Z; con_need = 2, obj_need = σ != 0 ? 2 : -1, μ = μ)
     GC.@preserve H Z μ check(ev, @ccall lib.dto_eval_hessian(ev.handle::Ptr{Cvoid}, Z::Ptr{Float64}, σ::Float64, μ::Ptr{Float64}, H::Ptr{Float64})::Cint)
+    return nothing
+end
+
+# h = H(Z; σ, μ) v (:HessVec): the engine assembles H once per point on the device and multiplies from a compact copy; products
+# at the same (Z, σ, μ) cost one launch -- closure-based terms stage their blocks anew on every call, which starts a new point
+function MOI.eval_hessian_lagrangian_product(ev::GPUEvaluator, h::AbstractVector{Float64}, Z::AbstractVector{Float64}, v::AbstractVector{Float64},
+                                             σ::Float64, μ::AbstractVector{Float64})
+    stage_external!(ev, Z; con_need = 2, obj_need = σ != 0 ? 2 : -1, μ = μ)
+    GC.@preserve h Z v μ check(ev, @ccall lib.dto_eval_hessian_product(ev.handle::Ptr{Cvoid}, Z::Ptr{Float64}, σ::Float64, μ::Ptr{Float64},
+                                                                         v::Ptr{Float64}, h::Ptr{Float64})::Cint)
     return nothing
 end
 
@@ -619,6 +629,13 @@ function eval_hessian_lagrangian_dev!(ev::GPUEvaluator, dH::Ptr{Float64}, dZ::Pt
                                       Z_host = nothing, μ_host = nothing)
     Z_host === nothing || stage_external!(ev, Z_host; con_need = 2, obj_need = σ != 0 ? 2 : -1, μ = μ_host)
     check(ev, @ccall lib.dto_eval_hessian_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dH::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
+function eval_hessian_lagrangian_product_dev!(ev::GPUEvaluator, dh::Ptr{Float64}, dZ::Ptr{Float64}, dv::Ptr{Float64}, σ::Float64,
+                                              dμ::Ptr{Float64}, stream::Ptr{Cvoid}; Z_host = nothing, μ_host = nothing)
+    Z_host === nothing || stage_external!(ev, Z_host; con_need = 2, obj_need = σ != 0 ? 2 : -1, μ = μ_host)
+    check(ev, @ccall lib.dto_eval_hessian_product_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dv::Ptr{Float64},
+                                                      dh::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 end
 
 "Declare a device value vector (DTO_VECTOR_JACOBIAN / DTO_VECTOR_HESSIAN) that the `*_dev!` calls are handed every iteration: its call-invariant entries are then written once (include/dto_engine.h, bound outputs).  `C_NULL` unbinds."
