@@ -247,6 +247,7 @@ struct dto_handle {
     int32_t* d_eq = nullptr;
     bool profiling = false;
     std::vector<ProfRec> prof;
+    int64_t sweep_forms[5] = {0, 0, 0, 0, 0};  // run_sweep calls by the form they took (SWEEP_GS ..), counted while profiling
     std::vector<hipEvent_t> ev_pool;  // recycled timing events (creating them inside the timed region costs host time)
     int last_smax = 0, last_terms = 0;
     int expm_form = 0;  // option "expm_form": 0 = by cost, 2 / 3 = forced
@@ -362,6 +363,11 @@ struct ProfScope {
 // (for the bandwidth-bound categories from CAT_ZERO on, `flops` carries the launch's algorithmic BYTES)
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
        CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11 };
+// the form a generator sweep took (dto_profile_get "sweep_gs" .. "sweep_step"): one count per run_sweep call, not per launch
+enum { SWEEP_GS = 0, SWEEP_FUSED = 1, SWEEP_S64 = 2, SWEEP_CLUSTER = 3, SWEEP_STEP = 4 };
+inline void count_sweep_form(dto_handle* h, int form) {
+    if (h->profiling) ++h->sweep_forms[form];
+}
 
 // ------------------------------------------------------------------------------------------
 // structure
@@ -671,6 +677,7 @@ int run_sweep(dto_handle* h, BilHost& b, SweepBuf& w, const SweepTypes& ty, cons
             HIP_CHECK(launch_sweep_gs(st, h->P, b.k, w, ty, gp, b.gs_xn[wi], b.gs_arrive[wi], dZ, dmu, src_kind, transposed, plan.d_ub, tc,
                                       store, 1.1e-16));
         }
+        count_sweep_form(h, SWEEP_GS);
         if (!want_steps) return plan.d_ub;
         return fused_sweep_steps(h, w, plan.d_ub, st);
     }
@@ -686,6 +693,7 @@ int run_sweep(dto_handle* h, BilHost& b, SweepBuf& w, const SweepTypes& ty, cons
             HIP_CHECK(launch_sweep_fused(st, h->P, b.k, w, ty, fp, dZ, dmu, src_kind, transposed, plan.q, plan.d_ub, tc, store, 1.1e-16,
                                          plan_dev));
         }
+        count_sweep_form(h, fp.S64 ? SWEEP_S64 : SWEEP_FUSED);
         if (!want_steps) return plan.d_ub;
         return fused_sweep_steps(h, w, plan.d_ub, st);
     }
@@ -715,10 +723,12 @@ int run_sweep(dto_handle* h, BilHost& b, SweepBuf& w, const SweepTypes& ty, cons
             HIP_CHECK(launch_sweep_cluster(st, h->P, b.k, w, ty, cp, b.xch[wi], b.xch_arrive[wi], dZ, dmu, src_kind, transposed, plan.q,
                                            plan.d_ub, tc, store, 1.1e-16));
         }
+        count_sweep_form(h, SWEEP_CLUSTER);
         if (!want_steps) return plan.d_ub;
         return fused_sweep_steps(h, w, plan.d_ub, st);
     }
     w.nblk = w.TN;
+    count_sweep_form(h, SWEEP_STEP);
     const size_t tstride = (size_t)ty.T * w.Kpad * w.npad;
     SweepBuf ws = w;
     if (store) ws.Z[0] = w.Zt;
@@ -3403,6 +3413,7 @@ int dto_profile_reset(dto_handle* h) {
     if (!h) return 1;
     for (auto& r : h->prof) { h->ev_pool.push_back(r.a); h->ev_pool.push_back(r.b); }
     h->prof.clear();
+    for (auto& c : h->sweep_forms) c = 0;
     return 0;
 }
 int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launches, double* flops) {
@@ -3429,6 +3440,17 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (ms) *ms = h->hp_setup_ms;
             if (launches) *launches = 0;
             if (flops) *flops = h->hp_bytes;
+            return;
+        }
+        else if (!strncmp(name, "sweep_", 6)) {
+            // generator sweeps by the form they took (run_sweep): a count, no timing, no flops; they feed no other name
+            static const char* const forms[5] = {"sweep_gs", "sweep_fused", "sweep_s64", "sweep_cluster", "sweep_step"};
+            int f = 0;
+            while (f < 5 && strcmp(name, forms[f])) ++f;
+            if (f == 5) throw HipError{"dto_profile_get: unknown name"};
+            if (ms) *ms = 0.0;
+            if (launches) *launches = h->sweep_forms[f];
+            if (flops) *flops = 0.0;
             return;
         }
         else if (strcmp(name, "all")) throw HipError{"dto_profile_get: unknown name"};

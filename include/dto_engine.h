@@ -401,7 +401,10 @@ int dto_profile_reset(dto_handle* h);
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names the
  * third output is the launches' algorithmic BYTES (what they must read and write), not FLOPs.
  * "hess_product_setup" returns the host milliseconds of the products' index build (once per handle), 0 launches, and the device
- * bytes of their private slab and index. */
+ * bytes of their private slab and index.
+ * "sweep_gs" / "sweep_fused" / "sweep_s64" / "sweep_cluster" / "sweep_step": generator sweeps by the form they ran in
+ * (generator-stationary, fused, the 64-state fused form, row-split cluster, one launch per Taylor step), one count per sweep
+ * while profiling is on -- 0 ms, the count, 0 flops; they feed no other name ("all", "expmv", ...). */
 int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launches, double* flops);
 /* diagnostics of the last Jacobian call: max squarings used, Taylor terms used by the tangent sweep */
 int dto_last_stats(const dto_handle* h, int32_t* max_squarings, int32_t* expmv_terms);

@@ -332,3 +332,18 @@ def sampled_checks(prob_e, ev, n, m, ks, jac_get=None, hess_get=None, cons=None,
 
 def host_getter(vals):
     return lambda lo, hi: vals[lo:hi]
+
+
+# ---- the form a generator sweep ran in (dto_profile_get "sweep_gs" .. "sweep_step": one count per sweep while profiling is on)
+SWEEP_FORMS = ("gs", "fused", "s64", "cluster", "step")
+
+
+def sweep_forms(ev):
+    """Generator sweeps since the last profile_reset, by the form they took."""
+    return {f: ev.profile_get("sweep_" + f)[1] for f in SWEEP_FORMS}
+
+
+def assert_sweep_form(counts, form, zero=None, what=""):
+    """`form` ran; none of the forms in `zero` (default: every other form) did."""
+    zero = [f for f in SWEEP_FORMS if f != form] if zero is None else zero
+    assert counts[form] >= 1 and all(counts[f] == 0 for f in zero), (what, form, counts)

@@ -230,3 +230,14 @@ def test_cpu_baseline_worker_uses_the_bench_problem():
     b = dto_amd.host.synthetic.scaled_problem_arrays(9, 5, 2, 42)
     for p, q in zip(a, b):
         assert np.array_equal(p, q)
+
+
+def test_sweep_form_counters_are_documented_and_built_in(engine_lib):
+    """dto_profile_get's per-form sweep counts: every name is documented with dto_profile_get and compiled into the library (a
+    structure-only handle refuses every measurement, so what they count is checked by the GPU tests)."""
+    src = open(os.path.join(ROOT, "include", "dto_engine.h")).read()
+    doc = src[src.index("int dto_profile_reset"):src.index("int dto_profile_get")]
+    lib = open(dto_amd.capi.library_path(), "rb").read()
+    for f in ("gs", "fused", "s64", "cluster", "step"):
+        assert f'"sweep_{f}"' in doc, f
+        assert b"sweep_" + f.encode() + b"\0" in lib, f

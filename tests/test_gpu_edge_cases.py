@@ -334,11 +334,12 @@ def test_reuse_forward_sweep_where_the_sweep_is_one_launch(n, N):
     finds the p terms of its point stored sweeps all columns again (cheaper than the frozen step-per-launch form) and leaves the
     stored terms to the Hessian.  Compared with a handle that has the option off, every ordering, the point changing in between."""
     import dto_amd
-    from helpers import rel_err
+    from helpers import rel_err, sweep_forms
     p = dto_amd.host.synthetic.make_scaled_problem(N, n, 2, seed=5)
     ref = dto_amd.Evaluator(p)
     ev = dto_amd.Evaluator(p)
     ev.set_option("reuse_forward_sweep", 1)
+    ev.profile_enable(True)
     rng = np.random.default_rng(1)
     Z1 = p.trajectory.vec()
     Z2 = Z1 + 0.02 * rng.standard_normal(Z1.size)
@@ -355,10 +356,17 @@ def test_reuse_forward_sweep_where_the_sweep_is_one_launch(n, N):
 
     try:
         want = {id(Z): {w: one(ref, w, Z) for w in ("g", "J", "H")} for Z in (Z1, Z2)}
+        one_launch = 0
         for order in (("g", "J", "H"), ("J", "g", "H"), ("H", "J", "g"), ("g", "H", "J", "H")):
             for Z in (Z1, Z2, Z1):
                 for what in order:
+                    ev.profile_reset()
                     assert rel_err(one(ev, what, Z), want[id(Z)][what]) <= 1e-12, (order, what)
+                    if what == "J":   # all columns again in one launch (or nothing left to sweep), never the frozen step form
+                        f = sweep_forms(ev)
+                        assert f["step"] == 0, (order, f)
+                        one_launch += f["fused"] + f["s64"] + f["cluster"] + f["gs"]
+        assert one_launch >= 1
     finally:
         ref.close(); ev.close()
 

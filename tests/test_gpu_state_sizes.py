@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import dto_oracle as O
-from helpers import check_callbacks, host_getter, sampled_checks, to_engine
+from helpers import assert_sweep_form, check_callbacks, host_getter, sampled_checks, sweep_forms, to_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -31,12 +31,16 @@ def _path_counts(prob_o, Z, hessian=True):
         ev.profile_reset()
         j = np.empty(ev.n_jacobian_entries); ev.eval_constraint_jacobian(j, Z)
         out = {"jac": {k: _launches(ev, k) for k in ("basis_multi", "bgemm_square", "bgemm_plain", "chain64", "expmv")},
-               "jac_stats": ev.last_stats()}
+               "jac_stats": ev.last_stats(), "forms": {"J": sweep_forms(ev)}}
+        ev.profile_reset()
+        g = np.empty(ev.n_constraints); ev.eval_constraint(g, Z)
+        out["forms"]["g"] = sweep_forms(ev)
         if hessian:
             ev.profile_reset()
             mu = np.random.default_rng(0).standard_normal(ev.n_constraints)
             h = np.empty(ev.n_hessian_entries); ev.eval_hessian_lagrangian(h, Z, 0.7, mu)
             out["hess"] = {k: _launches(ev, k) for k in ("expmv", "expmv_adjoint")}
+            out["forms"]["H"] = sweep_forms(ev)
         return out
     finally:
         ev.close()
@@ -47,6 +51,8 @@ def _assert_large_state_chain(counts):
     alpha past the radius of either polynomial form at these sizes), no one-launch 64-state chain."""
     c = counts["jac"]
     assert c["basis_multi"] >= 1 and c["chain64"] == 0, counts
+    for what, f in counts["forms"].items():   # every sweep one launch per Taylor step: the one-launch forms refuse these sizes
+        assert_sweep_form(f, "step", what=what)
     assert c["bgemm_square"] >= 1 and counts["jac_stats"][0] >= 1, counts
 
 
@@ -88,6 +94,7 @@ def test_longer_horizons_sampled(n, m, N, ks):
         jac = np.full(ev.n_jacobian_entries, np.nan); ev.eval_constraint_jacobian(jac, Z)
         squares, chunks = _launches(ev, "bgemm_square"), _launches(ev, "basis_multi")
         squarings = ev.last_stats()[0]
+        assert_sweep_form(sweep_forms(ev), "step", what="Jacobian")
         ev.profile_enable(False)
         assert chunks == 1 and squares >= 1 and squarings >= 1, (chunks, squares, squarings)
         cons = np.full(ev.n_constraints, np.nan); ev.eval_constraint(cons, Z)

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import dto_oracle as O
-from helpers import rel_err, run_all, to_engine
+from helpers import assert_sweep_form, rel_err, run_all, sweep_forms, to_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +18,20 @@ def _all(p, Z, options=(), hessian=True, **kw):
         for k, v in options:
             ev.set_option(k, v)
         mu = np.random.default_rng(7).standard_normal(ev.n_constraints)
-        return run_all(ev, p, Z, mu, sigma=0.7, hessian=hessian), mu
+        out = run_all(ev, p, Z, mu, sigma=0.7, hessian=hessian)
+        # the form every sweep of each callback took (a second call each, profiled)
+        ev.profile_enable(True)
+        out["forms"] = {}
+        for what in ("g", "J", "H") if hessian else ("g", "J"):
+            ev.profile_reset()
+            if what == "g":
+                ev.eval_constraint(np.empty(ev.n_constraints), Z)
+            elif what == "J":
+                ev.eval_constraint_jacobian(np.empty(ev.shard.jac_len), Z)
+            else:
+                ev.eval_hessian_lagrangian(np.empty(ev.shard.hess_len), Z, 0.7, mu)
+            out["forms"][what] = sweep_forms(ev)
+        return out, mu
     finally:
         ev.close()
 
@@ -43,6 +56,9 @@ def test_forms_against_the_oracle_and_the_general_forms(n, m, N):
     assert rel_err(out["jac"], ref["jac"]) <= 1e-10
     assert rel_err(out["hess"], ref["hess"]) <= 1e-8
     gen, _ = _all(p, Z, options=(("chain_form", 1), ("sweep_form", 1)))
+    for what in ("g", "J", "H"):
+        assert_sweep_form(out["forms"][what], "s64", what=what)
+        assert_sweep_form(gen["forms"][what], "step", what=what)
     assert rel_err(out["jac"], gen["jac"]) <= 1e-11 and rel_err(out["cons"], gen["cons"]) <= 1e-11
     assert rel_err(out["hess"], gen["hess"]) <= 1e-9
 
