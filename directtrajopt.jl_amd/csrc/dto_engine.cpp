@@ -61,6 +61,14 @@ T* dupload(const std::vector<T>& v) {
     return p;
 }
 
+// Grow-only device workspace of a sweep form whose workgroups hand data to each other (ensure_sweep_work replaces both parts)
+struct SweepWork {
+    double* slab = nullptr;
+    unsigned* arrive = nullptr;
+    size_t cap = 0;     // doubles in slab
+    int counters = 0;   // interval groups (generator-stationary) or clusters (row-split) the counters serve
+};
+
 struct BilHost {
     KBil k;
     SweepBuf fw{}, ad{};
@@ -85,17 +93,11 @@ struct BilHost {
     bool p_terms = false;
     int p_steps = 0;
     int p_nblk = 0;           // intervals per entry of fw.nterms_p (the convergence blocks of the sweep that stored the p terms)
-    // row-split cluster sweeps (dto_sweep_fused.hip): exchange slabs and arrival counters, one set per sweep buffer (the
-    // Hessian's forward and adjoint sweeps may run side by side), grow-only
-    double* xch[2] = {nullptr, nullptr};
-    unsigned* xch_arrive[2] = {nullptr, nullptr};
-    size_t xch_cap[2] = {0, 0};
-    int xch_clusters[2] = {0, 0};
-    // generator-stationary sweeps (dto_sweep_gs.hip): partial-norm slabs and arrival counters per sweep buffer, grow-only
-    double* gs_xn[2] = {nullptr, nullptr};
-    unsigned* gs_arrive[2] = {nullptr, nullptr};
-    size_t gs_xn_cap[2] = {0, 0};
-    int gs_groups[2] = {0, 0};
+    // row-split cluster sweeps (dto_sweep_fused.hip): exchange slabs and arrival counters, one set per sweep buffer ([0] fw,
+    // [1] ad: the Hessian's forward and adjoint sweeps may run side by side)
+    SweepWork cluster_work[2];
+    // generator-stationary sweeps (dto_sweep_gs.hip): partial-norm slabs and arrival counters per sweep buffer
+    SweepWork gs_work[2];
     bool small = false;       // n <= 32: fused one-workgroup-per-interval path (dto_small.hip)
     double* d_Gs = nullptr;   // compact generators for that path
     bool use_basis = false;   // A^2..A^4 from the generator subspace instead of three batched GEMMs
@@ -580,9 +582,7 @@ void enqueue_bounds(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st)
     HIP_CHECK(hipMemcpyAsync(h->h_pinned, h->d_bounds, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
 }
 Bounds get_bounds(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st) {
-    HIP_CHECK(hipMemsetAsync(h->d_bounds, 0, 2 * sizeof(double), st));
-    launch_norm_bounds(st, h->P, b.k, dZ, b.d_g1, b.d_n2, reinterpret_cast<unsigned long long*>(h->d_bounds));
-    HIP_CHECK(hipMemcpyAsync(h->h_pinned, h->d_bounds, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    enqueue_bounds(h, b, dZ, st);
     HIP_CHECK(hipStreamSynchronize(st));
     Bounds r{h->h_pinned[0], h->h_pinned[1]};
     return r;
@@ -595,6 +595,15 @@ struct SweepPlan {
 void read_hump(dto_handle* h, BilHost& b);
 SweepPlan plan_hump(const BilHost& b, double beta_fallback);
 
+// Step budget of one round of radius br: the Taylor terms of exp(br) down to 1e-19 (8 to 200 of them), and six more
+int taylor_budget(double br) {
+    int t = 8;
+    double term = 1.0;
+    for (int i = 1; i <= t; ++i) term *= br / i;
+    while (term > 1e-19 && t < 200) { ++t; term *= br / t; }
+    return t + 6;
+}
+
 SweepPlan plan_sweep(double beta) {
     SweepPlan p{1, 12};
     if (!(beta == beta) || beta > 1e6) {  // non-finite iterate: bounded work, NaN/Inf propagates to the output
@@ -603,12 +612,7 @@ SweepPlan plan_sweep(double beta) {
     }
     static const double theta_v = tune_double("DTO_THETA_V", 9.0);  // worst-case cancellation budget e^9 ~ 1e4 on the Taylor sums (tolerance 1e-10)
     p.q = std::max(1, (int)std::ceil(beta / theta_v));
-    const double br = beta / p.q;
-    int t = 8;
-    double term = 1.0;
-    for (int i = 1; i <= t; ++i) term *= br / i;
-    while (term > 1e-19 && t < 200) { ++t; term *= br / t; }
-    p.d_ub = t + 6;
+    p.d_ub = taylor_budget(beta / p.q);
     return p;
 }
 
@@ -619,19 +623,76 @@ int fused_sweep_steps(dto_handle* h, const SweepBuf& w, int d_ub, hipStream_t st
     HIP_CHECK(hipStreamSynchronize(st));
     return std::max(1, std::min(hs[1] - 1, d_ub));
 }
-bool fused_sweep_applies(const dto_handle* h, const BilHost& b, const SweepBuf& w, const SweepTypes& ty, const SweepPlan& plan, bool store);
-bool cluster_sweep_applies(const dto_handle* h, const BilHost& b, const SweepBuf& w, const SweepTypes& ty, const SweepPlan& plan, bool store,
-                           ClusterSweepPlan& cp);
-bool gs_sweep_applies(const dto_handle* h, const BilHost& b, const SweepBuf& w, const SweepTypes& ty, const SweepPlan& plan, bool store,
-                      bool shared_chip, GsSweepPlan& gp);
 bool ensure_bind_runs(dto_handle* h, int which);
 
+// The form a generator sweep takes and that form's launch plan.  choose_sweep is the one place that decides it: run_sweep executes
+// a choice, and a caller whose streams or bookkeeping depend on the form asks first and hands the same choice on.
+struct SweepChoice {
+    int form = SWEEP_STEP;
+    GsSweepPlan gs;            // form == SWEEP_GS
+    FusedSweepPlan fused;      // form == SWEEP_FUSED, SWEEP_S64
+    ClusterSweepPlan cluster;  // form == SWEEP_CLUSTER
+    bool store = false, shared_chip = false;  // as asked (SweepArgs::as_chosen takes them from here)
+    bool one_workgroup() const { return form == SWEEP_FUSED || form == SWEEP_S64; }  // the single-workgroup forms (these read plan_dev)
+    SweepChoice& is(int f) { form = f; return *this; }
+};
+
+// store: every Taylor term is kept in w.Zt; shared_chip: another stream's kernels run beside the sweep (the propagator chain, the
+// Hessian's adjoint sweep); step_only: the caller has initialised the sweep itself (the products' extra start vector).
+// In order: generator-stationary, fused (64 states: its generator-stationary instance), row-split cluster, one launch per Taylor step.
+SweepChoice choose_sweep(const dto_handle* h, const BilHost& b, const SweepBuf& w, const SweepTypes& ty, const SweepPlan& plan,
+                         bool store, bool shared_chip, bool step_only = false) {
+    SweepChoice c{};
+    c.store = store;
+    c.shared_chip = shared_chip;
+    // no one-launch form: by option, with frozen p terms, where the term store cannot hold the step budget, and for a stored
+    // single column under reuse_forward_sweep (a frozen sweep reads nterms_p in blocks of TN intervals)
+    if (step_only || h->sweep_form == 1 || w.frozen) return c;
+    if (store && (!(w.Zt && plan.d_ub + 1 <= w.dcap) || (ty.T == 1 && h->reuse))) return c;
+    // the fused planner's answer for a sweep that has the chip to itself: asked by the generator-stationary and the fused form
+    const bool fused_alone = sweep_fused_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, c.fused);
+    // Generator-stationary form (dto_sweep_gs.hip): clusters of npad / 32 workgroups with the generators resident in their registers.
+    // It needs the whole chip to itself (one 512-register workgroup per CU, all cluster members resident): not beside the chain
+    // (`shared_chip`), not with sub-stepping.  It is taken where the single-workgroup form cannot fill the chip: single-column sweeps
+    // (eval_constraint, the Hessian's forward column) and sweeps the fused planner refuses (short shards); measured
+    // (tools/sweep_gs_probe, 256 states): p column of 2000 knots 0.77 ms against 1.38 ms for the split-K step launches, Jacobian
+    // sweep of 250 knots 0.80 against 1.15 ms for the row-split cluster form.
+    static const int gs_on = tune_int("DTO_SWEEP_GS", 1);  // A/B runs (TUNING builds): 0 = never, 2 = wherever it can run
+    if (gs_on && plan.q == 1 && h->n_cu >= 64 && !(shared_chip && gs_on != 2) &&
+        (size_t)ty.T * w.Kpad * w.npad * 8 < (1ull << 31) &&   // 32-bit buffer offsets into a term slab
+        sweep_gs_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, c.gs) && (gs_on == 2 || ty.T == 1 || !fused_alone))
+        return c.is(SWEEP_GS);
+    // Fused form (dto_sweep_fused.hip): the whole series in one persistent launch, a workgroup per few intervals; single-column
+    // sweeps only in the 64-state generator-stationary instance.  Beside another stream's kernels the planner is asked again for
+    // the shape it takes there (a refusal would fall through to the cluster form; see sweep_with in do_jacobian).
+    if (fused_alone && (ty.T != 1 || c.fused.S64) &&
+        (!shared_chip || sweep_fused_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, c.fused, shared_chip)))
+        return c.is(c.fused.S64 ? SWEEP_S64 : SWEEP_FUSED);
+    // Row-split cluster form: where the single-workgroup form has too few interval groups for the chip -- short shards of 128-
+    // and 256-state problems (the 250-knot share of the 2000-knot metric on 8 GPUs).  Measured per Jacobian / Hessian,
+    // cluster against step per launch (tools/cluster_time.py): 256 x 250 2.12 / 2.02 against 2.22 / 2.04 ms, 128 x 250 0.74 /
+    // 1.02 against 0.93 / 1.18 ms.  NOT used where it measured slower: single-column sweeps (eval_constraint 0.94 against
+    // 0.62 ms at 250 knots, 1.52 against 1.45 at 2000: the rendezvous + slice exchange costs ~10 us per Taylor step, as much
+    // as the step's MFMA work there) and 512 / 1024 states (23.6 against 18.7 ms, 57 against 47 ms per Jacobian: the step
+    // launches tile the 2500 columns 32 wide, a cluster member is held to 16 by its LDS).
+    static const int cluster_on = tune_int("DTO_SWEEP_CLUSTER", 1);  // A/B runs (TUNING builds): 0 = never
+    static const int cluster_big = tune_int("DTO_SWEEP_CLUSTER_BIG", 0);  // 512 and 1024 states as well
+    static const int cluster_t1 = tune_int("DTO_SWEEP_CLUSTER_T1", 0);    // single-column sweeps too
+    if (cluster_on && (ty.T != 1 || cluster_t1) && (w.npad <= 256 || cluster_big) &&
+        sweep_cluster_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, c.cluster))
+        return c.is(SWEEP_CLUSTER);
+    return c;   // one launch per Taylor step: what remains, and the form for frozen p terms and the products' extra start vector
+}
+
 // Does this sweep run in the 64-state generator-stationary form, which can read its step budget from device memory?  (No term
-// store, no reuse: the host then needs nothing of the plan.)
-bool s64_plans_itself(const dto_handle* h, const BilHost& b, const SweepBuf& w, const SweepTypes& ty) {
+// store, no reuse: the host then needs nothing of the plan.)  `alone`: the choice of such a sweep with the chip to itself.
+const SweepPlan PLAN_ON_DEVICE{1, 200};  // what the host passes where launch_plan_dev's {q, d_ub, tc} are read instead
+bool s64_plans_itself(const dto_handle* h, const BilHost& b, const SweepBuf& w, const SweepTypes& ty, SweepChoice* alone = nullptr) {
     static const int on = tune_int("DTO_PLAN_DEV", 1);  // A/B runs (TUNING builds)
-    FusedSweepPlan fp;
-    return on && !h->reuse && h->sweep_form != 1 && !w.frozen && b.k.npad == 64 && sweep_fused_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, fp) && fp.S64;
+    if (!on || h->reuse) return false;
+    const SweepChoice c = choose_sweep(h, b, w, ty, PLAN_ON_DEVICE, /*store=*/false, /*shared_chip=*/false);
+    if (alone) *alone = c;
+    return c.form == SWEEP_S64;
 }
 
 // 33..64 states: the propagator chain as one launch (dto_chain64.hip)
@@ -640,12 +701,35 @@ bool chain64_applies(const dto_handle* h, const BilHost& b) {
     return b.k.npad == 64 && chain64_on && h->chain_form != 1 && h->P.n_int <= b.chain_cap;
 }
 
-// Returns the number of Taylor steps enqueued in the last round.  store = true keeps every term in w.Zt
-// (term t of all types at Zt + t*T*Kpad*npad) instead of ping-ponging two buffers.
+SweepWork& ensure_sweep_work(dto_handle* h, SweepWork& k, size_t doubles, int counters, size_t counters_alloc) {
+    if (doubles > k.cap || counters > k.counters)
+        k = SweepWork{own(h, dalloc<double>(doubles)), own(h, dalloc<unsigned>(counters_alloc)), doubles, counters};
+    return k;
+}
+
+// What run_sweep takes besides the buffers, the plan and the stream, set by name: SweepArgs().keep_terms(keep) ...
+struct SweepArgs {
+    int src_kind = 0, transposed = 0;  // forward sweep from the states x_k; adjoint(): transposed, from the multipliers mu_k
+    bool store = false;        // keep every term in w.Zt (term t of all types at Zt + t*T*Kpad*npad) instead of ping-ponging two buffers
+    bool want_steps = false;   // one-launch forms: wait for the sweep and return the steps it took instead of the budget
+    bool shared_chip = false, step_only = false;   // see choose_sweep
+    int prof_cat = CAT_SWEEP;
+    const int32_t* plan_dev = nullptr;    // {q, d_ub, tc} in device memory (launch_plan_dev): the single-workgroup forms only
+    const SweepChoice* choice = nullptr;  // choose_sweep's answer from a caller that asked first; else run_sweep asks
+    SweepArgs& adjoint(int cat) { src_kind = transposed = 1; prof_cat = cat; return *this; }
+    SweepArgs& keep_terms(bool v) { store = v; return *this; }
+    SweepArgs& wait_for_steps(bool v) { want_steps = v; return *this; }
+    SweepArgs& beside_others(bool v) { shared_chip = v; return *this; }
+    SweepArgs& initialised() { step_only = true; return *this; }
+    SweepArgs& planned_on_device(const int32_t* p) { plan_dev = p; return *this; }
+    SweepArgs& as_chosen(const SweepChoice& c) { choice = &c; store = c.store; shared_chip = c.shared_chip; return *this; }
+};
+
+// Returns the number of Taylor steps enqueued in the last round.
 int run_sweep(dto_handle* h, BilHost& b, SweepBuf& w, const SweepTypes& ty, const double* dZ, const double* dmu,
-              int src_kind, int transposed, const SweepPlan& plan, hipStream_t st, bool store = false,
-              bool skip_init = false, bool want_steps = false, bool shared_chip = false, int prof_cat = CAT_SWEEP,
-              const int32_t* plan_dev = nullptr) {
+              const SweepPlan& plan, hipStream_t st, const SweepArgs& a = SweepArgs{}) {
+    const SweepChoice c = a.choice ? *a.choice : choose_sweep(h, b, w, ty, plan, a.store, a.shared_chip, a.step_only);
+    if (a.plan_dev && !c.one_workgroup()) throw HipError{"run_sweep: a device-side plan without the form that reads it"};
     const double flops_step = [&] {
         double segs = 0;
         for (int t = w.frozen ? w.first_type : 0; t < ty.T; ++t) segs += b.k.m + 1;  // an extra term rides in the segment of its generator
@@ -657,88 +741,44 @@ int run_sweep(dto_handle* h, BilHost& b, SweepBuf& w, const SweepTypes& ty, cons
     static const int tc_env = tune_int("DTO_SWEEP_TC", -1);
     int tc = tc_env >= 0 ? tc_env : (plan.tc >= 0 ? plan.tc : plan.d_ub / 2 - 1);
     if (tc < 2) tc = 0;
-    // Generator-stationary form (dto_sweep_gs.hip, round 4): clusters of npad / 32 workgroups with the generators resident in
-    // their registers; serves what the single-workgroup form cannot fill the chip with -- single-column sweeps (eval_constraint,
-    // the Hessian's forward column), short shards -- see gs_sweep_applies.
-    GsSweepPlan gp;
-    if (!skip_init && gs_sweep_applies(h, b, w, ty, plan, store, shared_chip, gp)) {
+    count_sweep_form(h, c.form);
+    if (c.form != SWEEP_STEP) {
+        // the one-launch forms: the whole series, termination tests included, in one persistent launch
         const int wi = &w == &b.ad ? 1 : 0;
-        const size_t need = sweep_gs_norm_doubles(gp);
-        if (need > b.gs_xn_cap[wi] || gp.n_groups > b.gs_groups[wi]) {
-            b.gs_xn[wi] = own(h, dalloc<double>(need));
-            b.gs_arrive[wi] = own(h, dalloc<unsigned>((size_t)(gp.n_groups + 3) / 4 * 4));
-            b.gs_xn_cap[wi] = need;
-            b.gs_groups[wi] = gp.n_groups;
-        }
-        w.nblk = gp.ipw;
-        HIP_CHECK(hipMemsetAsync(w.stats, 0, 4 * sizeof(int32_t), st));
-        {
-            ProfScope ps(h, st, prof_cat, flops_step * plan.d_ub);
-            HIP_CHECK(launch_sweep_gs(st, h->P, b.k, w, ty, gp, b.gs_xn[wi], b.gs_arrive[wi], dZ, dmu, src_kind, transposed, plan.d_ub, tc,
-                                      store, 1.1e-16));
-        }
-        count_sweep_form(h, SWEEP_GS);
-        if (!want_steps) return plan.d_ub;
-        return fused_sweep_steps(h, w, plan.d_ub, st);
-    }
-    // Fused form (dto_sweep_fused.hip): the whole series in one persistent launch, a workgroup per few intervals.  The
-    // step-per-launch form below remains for sweeps over frozen p terms and for the products' extra start vector.
-    FusedSweepPlan fp;
-    if (!skip_init && fused_sweep_applies(h, b, w, ty, plan, store) && sweep_fused_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, fp, shared_chip)) {
-        w.nblk = fp.ipw;
+        w.nblk = c.form == SWEEP_GS ? c.gs.ipw : c.form == SWEEP_CLUSTER ? c.cluster.ipw : c.fused.ipw;
+        SweepWork* k = nullptr;
+        if (c.form == SWEEP_GS)   // (the launch zeroes its counters four at a time)
+            k = &ensure_sweep_work(h, b.gs_work[wi], sweep_gs_norm_doubles(c.gs), c.gs.n_groups, (size_t)(c.gs.n_groups + 3) / 4 * 4);
+        if (c.form == SWEEP_CLUSTER)
+            k = &ensure_sweep_work(h, b.cluster_work[wi], sweep_cluster_workspace_doubles(w.npad, c.cluster), c.cluster.n_clusters,
+                                   (size_t)c.cluster.n_clusters);
         HIP_CHECK(hipMemsetAsync(w.stats, 0, 4 * sizeof(int32_t), st));
         {
             // flops of the step budget (an upper bound: workgroups leave when their columns have converged)
-            ProfScope ps(h, st, prof_cat, flops_step * plan.d_ub * plan.q);
-            HIP_CHECK(launch_sweep_fused(st, h->P, b.k, w, ty, fp, dZ, dmu, src_kind, transposed, plan.q, plan.d_ub, tc, store, 1.1e-16,
-                                         plan_dev));
+            ProfScope ps(h, st, a.prof_cat, flops_step * plan.d_ub * plan.q);
+            if (c.form == SWEEP_GS)   // (q == 1)
+                HIP_CHECK(launch_sweep_gs(st, h->P, b.k, w, ty, c.gs, k->slab, k->arrive, dZ, dmu, a.src_kind, a.transposed, plan.d_ub, tc,
+                                          a.store, 1.1e-16));
+            else if (c.form == SWEEP_CLUSTER)
+                HIP_CHECK(launch_sweep_cluster(st, h->P, b.k, w, ty, c.cluster, k->slab, k->arrive, dZ, dmu, a.src_kind, a.transposed, plan.q,
+                                               plan.d_ub, tc, a.store, 1.1e-16));
+            else
+                HIP_CHECK(launch_sweep_fused(st, h->P, b.k, w, ty, c.fused, dZ, dmu, a.src_kind, a.transposed, plan.q, plan.d_ub, tc, a.store,
+                                             1.1e-16, a.plan_dev));
         }
-        count_sweep_form(h, fp.S64 ? SWEEP_S64 : SWEEP_FUSED);
-        if (!want_steps) return plan.d_ub;
-        return fused_sweep_steps(h, w, plan.d_ub, st);
-    }
-    if (plan_dev) throw HipError{"run_sweep: a device-side plan without the form that reads it"};
-    // Row-split cluster form: where the single-workgroup form has too few interval groups for the chip -- short shards of 128-
-    // and 256-state problems (the 250-knot share of the 2000-knot metric on 8 GPUs).  Measured per Jacobian / Hessian,
-    // cluster against step per launch (tools/cluster_time.py): 256 x 250 2.12 / 2.02 against 2.22 / 2.04 ms, 128 x 250 0.74 /
-    // 1.02 against 0.93 / 1.18 ms.  NOT used where it measured slower: single-column sweeps (eval_constraint 0.94 against
-    // 0.62 ms at 250 knots, 1.52 against 1.45 at 2000: the rendezvous + slice exchange costs ~10 us per Taylor step, as much
-    // as the step's MFMA work there) and 512 / 1024 states (23.6 against 18.7 ms, 57 against 47 ms per Jacobian: the step
-    // launches tile the 2500 columns 32 wide, a cluster member is held to 16 by its LDS).  Not with frozen p terms or the
-    // products' extra start vector.
-    ClusterSweepPlan cp;
-    if (!skip_init && cluster_sweep_applies(h, b, w, ty, plan, store, cp)) {
-        const int wi = &w == &b.ad ? 1 : 0;
-        const size_t need = sweep_cluster_workspace_doubles(w.npad, cp);
-        if (need > b.xch_cap[wi] || cp.n_clusters > b.xch_clusters[wi]) {
-            b.xch[wi] = own(h, dalloc<double>(need));
-            b.xch_arrive[wi] = own(h, dalloc<unsigned>((size_t)cp.n_clusters));
-            b.xch_cap[wi] = need;
-            b.xch_clusters[wi] = cp.n_clusters;
-        }
-        w.nblk = cp.ipw;
-        HIP_CHECK(hipMemsetAsync(w.stats, 0, 4 * sizeof(int32_t), st));
-        {
-            ProfScope ps(h, st, prof_cat, flops_step * plan.d_ub * plan.q);
-            HIP_CHECK(launch_sweep_cluster(st, h->P, b.k, w, ty, cp, b.xch[wi], b.xch_arrive[wi], dZ, dmu, src_kind, transposed, plan.q,
-                                           plan.d_ub, tc, store, 1.1e-16));
-        }
-        count_sweep_form(h, SWEEP_CLUSTER);
-        if (!want_steps) return plan.d_ub;
-        return fused_sweep_steps(h, w, plan.d_ub, st);
+        return a.want_steps ? fused_sweep_steps(h, w, plan.d_ub, st) : plan.d_ub;
     }
     w.nblk = w.TN;
-    count_sweep_form(h, SWEEP_STEP);
     const size_t tstride = (size_t)ty.T * w.Kpad * w.npad;
     SweepBuf ws = w;
-    if (store) ws.Z[0] = w.Zt;
+    if (a.store) ws.Z[0] = w.Zt;
     if (w.frozen) launch_sweep_init_tangents(st, ws, ty.T);  // scale factors and type-0 sums are those of the earlier callback
-    else if (!skip_init) launch_sweep_init(st, h->P, b.k, ws, ty, dZ, dmu, src_kind, plan.q);
+    else if (!a.step_only) launch_sweep_init(st, h->P, b.k, ws, ty, dZ, dmu, a.src_kind, plan.q);
     int launched = 0;
     // one timed region per sweep (steps, termination tests and the gaps between them): an event pair per step costs
     // 0.2 ms per Jacobian call at 256x2000.  Its flop count covers every enqueued step, including the few that find their
     // column blocks already converged (bench.py prices the sweep by the terms actually used, dto_last_stats).
-    ProfScope ps(h, st, prof_cat, 0.0);
+    ProfScope ps(h, st, a.prof_cat, 0.0);
     for (int round = 0; round < plan.q; ++round) {
         if (round > 0) launch_sweep_restart(st, w, ty.T);
         int buf = 0;
@@ -752,14 +792,14 @@ int run_sweep(dto_handle* h, BilHost& b, SweepBuf& w, const SweepTypes& ty, cons
                 HIP_CHECK(hipMemsetAsync(w.termnorm, 0, sizeof(unsigned long long) * (size_t)3 * w.T_alloc * w.Kpad, st));
             {
                 ps.r.flops += flops_step;
-                if (store) {
+                if (a.store) {
                     ws.Z[0] = w.Zt + (size_t)t * tstride;
                     ws.Z[1] = w.Zt + (size_t)(t + 1) * tstride;
                     // one stored type: split K over the generators, the next terms' slots are the scratch
                     const bool split = ty.T == 1 && (int64_t)(t + b.k.m + 4) <= (int64_t)w.dcap * (1 + b.k.m);
-                    launch_sweep_step(st, b.k, ws, ty, transposed, t, 0, split ? 1 : 0);
+                    launch_sweep_step(st, b.k, ws, ty, a.transposed, t, 0, split ? 1 : 0);
                 } else {
-                    launch_sweep_step(st, b.k, w, ty, transposed, t, buf);
+                    launch_sweep_step(st, b.k, w, ty, a.transposed, t, buf);
                 }
             }
             if (t >= tc) launch_sweep_check(st, w, ty.T, t, 1.1e-16);
@@ -1063,48 +1103,6 @@ double run_chain(dto_handle* h, BilHost& b, const double* dZ, double* vals, doub
     return d2max;
 }
 
-bool fused_sweep_applies(const dto_handle* h, const BilHost& b, const SweepBuf& w, const SweepTypes& ty, const SweepPlan& plan, bool store) {
-    FusedSweepPlan fp;
-    if (h->sweep_form == 1 || w.frozen || (store && !(w.Zt && plan.d_ub + 1 <= w.dcap))) return false;
-    if (!sweep_fused_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, fp)) return false;
-    // single-column sweeps (eval_constraint, the Hessian's forward column): only the 64-state generator-stationary form
-    if (ty.T == 1) return fp.S64 && !(store && h->reuse);   // (a frozen sweep reads nterms_p in blocks of TN intervals)
-    return true;
-}
-
-bool cluster_sweep_applies(const dto_handle* h, const BilHost& b, const SweepBuf& w, const SweepTypes& ty, const SweepPlan& plan, bool store,
-                           ClusterSweepPlan& cp) {
-    static const int on = tune_int("DTO_SWEEP_CLUSTER", 1);  // A/B runs (TUNING builds): 0 = never
-    static const int big = tune_int("DTO_SWEEP_CLUSTER_BIG", 0);  // 512 and 1024 states as well
-    static const int t1 = tune_int("DTO_SWEEP_CLUSTER_T1", 0);    // single-column sweeps too
-    if (!on || h->sweep_form == 1 || w.frozen) return false;
-    if (ty.T == 1 && !t1) return false;
-    if (store && !(w.Zt && plan.d_ub + 1 <= w.dcap)) return false;
-    if (store && ty.T == 1 && h->reuse) return false;
-    if (w.npad > 256 && !big) return false;
-    return sweep_cluster_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, cp);
-}
-
-// The generator-stationary form needs the whole chip to itself (one 512-register workgroup per CU, all cluster members resident):
-// not beside the chain (`shared_chip`), not with sub-stepping, frozen p terms or the products' extra start vector.  It is taken
-// where the single-workgroup form cannot fill the chip: single-column sweeps and sweeps the fused planner refuses (short shards);
-// measured (tools/sweep_gs_probe, 256 states): p column of 2000 knots 0.77 ms against 1.38 ms for the split-K step launches,
-// Jacobian sweep of 250 knots 0.80 against 1.15 ms for the row-split cluster form.
-bool gs_sweep_applies(const dto_handle* h, const BilHost& b, const SweepBuf& w, const SweepTypes& ty, const SweepPlan& plan, bool store,
-                      bool shared_chip, GsSweepPlan& gp) {
-    static const int on = tune_int("DTO_SWEEP_GS", 1);  // A/B runs (TUNING builds): 0 = never, 2 = wherever it can run
-    if (!on || h->sweep_form == 1 || w.frozen || plan.q != 1 || h->n_cu < 64) return false;
-    if (shared_chip && on != 2) return false;
-    if (store && !(w.Zt && plan.d_ub + 1 <= w.dcap)) return false;
-    if (store && ty.T == 1 && h->reuse) return false;   // (a frozen sweep reads nterms_p in blocks of TN intervals)
-    if ((size_t)ty.T * w.Kpad * w.npad * 8 >= (1ull << 31)) return false;   // 32-bit buffer offsets into a term slab
-    if (!sweep_gs_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, gp)) return false;
-    if (on == 2) return true;
-    if (ty.T == 1) return true;
-    FusedSweepPlan fp;
-    return !sweep_fused_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, fp);
-}
-
 // max_k ||A_k^2||_1^(1/2), exact, for callbacks that do not run the propagator chain: A_k and A_k^2 only
 // (one streaming pass + one small GEMM per chunk).  Sharper than the generator-norm bound, so the sweep
 // usually needs a single round (q = 1).
@@ -1180,17 +1178,13 @@ SweepPlan plan_hump(const BilHost& b, double beta_fallback) {
 // host round trips: 0.2 of the callback's 1.1 ms) was bought only to learn what this already shows.
 // The step budget the cheap generator-norm bound alone gives, where that is a single round (q = 1): no exact norm needed.
 bool cheap_plan(const Bounds& bd, bool loose, SweepPlan& out) {
-    if (plan_sweep(bd.beta).q == 1) { out = plan_sweep(bd.beta); return true; }  // the cheap bound already gives one round
+    out = plan_sweep(bd.beta);
+    if (out.q == 1) return true;  // the cheap bound already gives one round
     if (loose && bd.beta == bd.beta && bd.beta < 40.0) {
         double lh = 0.0;
         for (int k = 1; k < 200; ++k) lh = std::max(lh, k * std::log(bd.beta) - std::lgamma(k + 1.0));
-        if (lh <= 9.0) {
-            SweepPlan p{1, 12};
-            int t = 8;
-            double term = 1.0;
-            for (int i = 1; i <= t; ++i) term *= bd.beta / i;
-            while (term > 1e-19 && t < 200) { ++t; term *= bd.beta / t; }
-            p.d_ub = t + 6;
+        if (lh <= 9.0) {   // (the literal e^9, where plan_sweep and plan_hump read DTO_THETA_V: they differ in TUNING builds that set it)
+            SweepPlan p{1, taylor_budget(bd.beta)};
             // the terms of the series grow up to index ~beta and fall from there: the test (two successive terms below 1.1e-16 of the
             // sum, Al-Mohy & Higham's own criterion, which they apply from the first term on) starts a few terms past the peak
             // of the BOUND -- a function of Z alone, like d_ub / 2 - 1, but not inflated by the bound's slack in the tail
@@ -1315,12 +1309,13 @@ void do_constraint(dto_handle* h, const double* dZ, double* dg, hipStream_t st) 
             continue;
         }
         if (h->P.n_int > 0) {
-            if (!(same && b.cache_kind >= 1) && s64_plans_itself(h, b, b.fw, make_types(0, false))) {
+            SweepChoice alone;
+            if (!(same && b.cache_kind >= 1) && s64_plans_itself(h, b, b.fw, make_types(0, false), &alone)) {
                 // 33..64 states: the one-launch sweep takes its step budget from the norm bound ON THE DEVICE (k_plan_dev: the
                 // formulas of cheap_plan / plan_sweep) -- the call no longer waits 40 us for eight bytes
                 enqueue_bounds(h, b, dZ, st);
                 launch_plan_dev(st, reinterpret_cast<const unsigned long long*>(h->d_bounds), h->d_plan);
-                run_sweep(h, b, b.fw, make_types(0, false), dZ, nullptr, 0, 0, SweepPlan{1, 200}, st, false, false, false, false, CAT_SWEEP, h->d_plan);
+                run_sweep(h, b, b.fw, make_types(0, false), dZ, nullptr, PLAN_ON_DEVICE, st, SweepArgs().as_chosen(alone).planned_on_device(h->d_plan));
                 b.cache_kind = 0;
                 remember_p_terms(h, b, false, 0, st);
             } else if (!(same && b.cache_kind >= 1)) {  // else exp(A)x of this very point is still in b.fw.S
@@ -1330,7 +1325,7 @@ void do_constraint(dto_handle* h, const double* dZ, double* dg, hipStream_t st) 
                 // with reuse on, the terms of the p column are kept: a Jacobian at this point then sweeps its tangent
                 // columns alone and a Hessian needs no forward sweep at all
                 const bool keep_p = h->reuse && b.pairing && plan.q == 1 && plan.d_ub + 1 <= b.fw.dcap;
-                const int steps = run_sweep(h, b, b.fw, ty, dZ, nullptr, 0, 0, plan, st, keep_p);
+                const int steps = run_sweep(h, b, b.fw, ty, dZ, nullptr, plan, st, SweepArgs().keep_terms(keep_p));
                 b.cache_kind = h->reuse ? 1 : 0;
                 remember_p_terms(h, b, keep_p, steps, st);
             }
@@ -1391,17 +1386,17 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                 // ... but where the whole sweep runs as ONE persistent launch beside the chain, sweeping all columns again is
                 // cheaper than the step-per-launch form the frozen variant needs (256 x 2000: 10.9 against 12.0 ms per Jacobian);
                 // the stored p terms stay valid for a Hessian at this point either way (a sweep without store leaves them alone)
-                ClusterSweepPlan cp_unused;
-                GsSweepPlan gp_unused;
-                const bool one_launch = fused_sweep_applies(h, b, b.fw, ty, plan, false) || cluster_sweep_applies(h, b, b.fw, ty, plan, false, cp_unused) ||
-                                        gs_sweep_applies(h, b, b.fw, ty, plan, false, overlap && !h->deterministic, gp_unused);
+                // (asked for the sweep without store beside the chain: what sweep_fused_plan accepts for a sweep alone it accepts there too
+                // -- it only tries the eight-wavefront search first, the 64-state instance changes its interval count, not its answer)
+                const bool beside_chain = overlap && !h->deterministic;
+                const bool one_launch = choose_sweep(h, b, b.fw, ty, plan, /*store=*/false, beside_chain).form != SWEEP_STEP;
                 if (have_p && !one_launch) {
                     // sweep the tangent columns alone, their inhomogeneous terms read the stored p terms
                     SweepBuf wf = b.fw;
                     wf.frozen = b.fw.Zt;
                     wf.frozen_total = b.p_steps + 1;
                     wf.first_type = 1;
-                    run_sweep(h, b, wf, ty, dZ, nullptr, 0, 0, plan, ss, false);
+                    run_sweep(h, b, wf, ty, dZ, nullptr, plan, ss);
                     launch_apply_Gu(ss, b.k, b.fw, 0, b.fw.S, b.fw.GY);
                     b.cache_kind = 2;
                     return;
@@ -1413,11 +1408,11 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                 // overlap_sweep; next to the chain the 256-state sweep otherwise groups its intervals by twelve instead of nine)
                 // (a short shard's sweep in the generator-stationary form wants the chip to itself for a fraction of a millisecond: it
                 // follows the chain on the call's stream instead of sharing the chip with it)
-                GsSweepPlan gp_j;
-                const bool gs_alone = gs_sweep_applies(h, b, b.fw, ty, plan, keep, false, gp_j);
+                SweepChoice choice = choose_sweep(h, b, b.fw, ty, plan, keep, /*shared_chip=*/false);
+                const bool gs_alone = choice.form == SWEEP_GS;
                 hipStream_t sw = gs_alone ? st : ss;
-                const int steps = run_sweep(h, b, b.fw, ty, dZ, nullptr, 0, 0, plan, sw, keep, false, false,
-                                            /*shared_chip=*/overlap && !h->deterministic && !gs_alone, CAT_SWEEP, plan_dev);
+                if (beside_chain && !gs_alone) choice = choose_sweep(h, b, b.fw, ty, plan, keep, /*shared_chip=*/true);
+                const int steps = run_sweep(h, b, b.fw, ty, dZ, nullptr, plan, sw, SweepArgs().as_chosen(choice).planned_on_device(plan_dev));
                 launch_apply_Gu(sw, b.k, b.fw, 0, b.fw.S, b.fw.GY);
                 b.cache_kind = h->reuse ? (keep ? 3 : 2) : 0;
                 b.cache_steps = steps;
@@ -1435,7 +1430,7 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                 launch_plan_dev(st, reinterpret_cast<const unsigned long long*>(h->d_bounds), h->d_plan);
                 HIP_CHECK(hipEventRecord(h->ev_fork, st));   // the plan is ready here
                 if (overlap) HIP_CHECK(hipStreamWaitEvent(ss, h->ev_fork, 0));
-                sweep_with(SweepPlan{1, 200}, h->d_plan);
+                sweep_with(PLAN_ON_DEVICE, h->d_plan);
                 swept = true;
                 if (lone && !keep_constants) {
                     // the fill behind the sweep on ITS stream: only the tangent-column writers after the join need it, and the chain
@@ -1558,14 +1553,16 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
             // (option "deterministic": never side by side -- beside the adjoint sweep the forward column takes another form, step
             // launches instead of the generator-stationary sweep at 128 / 256 states, another interval grouping at 33..64, so its
             // summation order would follow overlap_sweep)
-            const bool side_by_side = fwd_needed && h->overlap_sweep && !h->deterministic && fused_sweep_applies(h, b, b.ad, ty1, plan, true);
+            // the adjoint sweep's form, chosen as for a sweep alone on the chip either way: the eight-wavefront shape it would take as
+            // a neighbour, leaving more CUs to the forward sweep's launches, measured 5.9 against 5.7 ms
+            const SweepChoice adjoint = choose_sweep(h, b, b.ad, ty1, plan, /*store=*/pair, /*shared_chip=*/false);
+            SweepArgs aa = SweepArgs().adjoint(CAT_SWEEP_ADJOINT).as_chosen(adjoint);
+            const bool side_by_side = fwd_needed && h->overlap_sweep && !h->deterministic && adjoint.one_workgroup();
             bool adjoint_enqueued = false;
             if (side_by_side) {
                 HIP_CHECK(hipEventRecord(h->ev_fork, st));  // dZ, dmu and the zeroed slab are ready here
                 HIP_CHECK(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-                // (the adjoint sweep in the eight-wavefront shape it takes next to the chain, leaving more CUs to the forward
-                // sweep's launches: 5.9 against 5.7 ms, gpurun_out/r03t)
-                run_sweep(h, b, b.ad, ty1, dZ, dmu, 1, 1, plan, st, true, false, /*want_steps=*/false, false, CAT_SWEEP_ADJOINT);
+                run_sweep(h, b, b.ad, ty1, dZ, dmu, plan, st, aa);   // enqueue only: the steps it took are read below
                 adjoint_enqueued = true;
             }
             hipStream_t sf = side_by_side ? h->stream2 : st;
@@ -1579,7 +1576,7 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
                     steps_f = b.p_steps;      // eval_constraint (or an earlier Hessian) stored the p terms of this point
                 } else {
                     Tf = 1;
-                    steps_f = run_sweep(h, b, b.fw, make_types(0, false), dZ, nullptr, 0, 0, plan, sf, true, false, false, /*shared_chip=*/side_by_side);
+                    steps_f = run_sweep(h, b, b.fw, make_types(0, false), dZ, nullptr, plan, sf, SweepArgs().keep_terms(true).beside_others(side_by_side));
                     b.cache_kind = h->reuse ? 1 : 0;  // the p sums are valid, the tangent sums are not
                     b.cache_steps = steps_f;
                     remember_p_terms(h, b, true, steps_f, sf);
@@ -1590,7 +1587,7 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
                     HIP_CHECK(hipStreamWaitEvent(st, h->ev_join, 0));
                 }
             } else {
-                steps_f = run_sweep(h, b, b.fw, make_types(m, true), dZ, nullptr, 0, 0, plan, st, false);
+                steps_f = run_sweep(h, b, b.fw, make_types(m, true), dZ, nullptr, plan, st);
                 launch_apply_Gu(st, b.k, b.fw, 0, b.fw.S, b.fw.GY);
                 b.cache_kind = 0;
                 b.p_terms = false;  // this sweep re-initialised the scale factors for its own q
@@ -1599,7 +1596,7 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
                 launch_apply_generators(st, b.k, b.ad, 1, b.ad.Z[0], b.ad.W);
             }
             const int steps_a = adjoint_enqueued ? fused_sweep_steps(h, b.ad, plan.d_ub, st)
-                                                 : run_sweep(h, b, b.ad, ty1, dZ, dmu, 1, 1, plan, st, pair, false, /*want_steps=*/pair, false, CAT_SWEEP_ADJOINT);
+                                                 : run_sweep(h, b, b.ad, ty1, dZ, dmu, plan, st, aa.wait_for_steps(pair));
             if (h->profiling && pair)
                 // the fused launch was priced by its step budget; now that the terms it ran are known, price it by those: 2 npad^2
                 // (m+1) generator products per column and term, (1+m) column types (the flops bench.py's roofline uses)
@@ -3135,13 +3132,13 @@ static void jac_product_matrix_free(dto_handle* h, const double* dZ, const doubl
             SweepBuf ws = b.fw;
             launch_sweep_init(st, h->P, b.k, ws, ty, dZ, nullptr, 0, plan.q);
             launch_sweep_set_type(st, h->P, b.k, ws, ty.T, tw, dw);
-            run_sweep(h, b, b.fw, ty, dZ, nullptr, 0, 0, plan, st, false, /*skip_init=*/true);
+            run_sweep(h, b, b.fw, ty, dZ, nullptr, plan, st, SweepArgs().initialised());   // (above, with w_x as the start of its extra column)
             launch_apply_Gu(st, b.k, b.fw, 0, b.fw.S, b.fw.GY);
             launch_jv_bilinear(st, h->P, b.k, b.fw, tw, dw, dy);
         } else {
-            run_sweep(h, b, b.fw, ty, dZ, nullptr, 0, 0, plan, st);
+            run_sweep(h, b, b.fw, ty, dZ, nullptr, plan, st);
             launch_apply_Gu(st, b.k, b.fw, 0, b.fw.S, b.fw.GY);
-            run_sweep(h, b, b.ad, make_types(0, false), dZ, dw, 1, 1, plan, st);
+            run_sweep(h, b, b.ad, make_types(0, false), dZ, dw, plan, st, SweepArgs().adjoint(CAT_SWEEP));
             launch_jtv_bilinear(st, h->P, b.k, b.fw, b.ad, dw, dy);
         }
     }

@@ -1,6 +1,6 @@
 """GPU: the form every generator sweep takes, and every instance of the two forms that hand data between workgroups.
 
-`run_sweep` (csrc/dto_engine.cpp) runs a sweep in one of five forms and counts the one it took (dto_profile_get "sweep_gs",
+`run_sweep` (csrc/dto_engine.cpp) runs a sweep in the form `choose_sweep` picked, one of five, and counts it (dto_profile_get "sweep_gs",
 "sweep_fused", "sweep_s64", "sweep_cluster", "sweep_step"): generator-stationary (k_sweep_gs, csrc/dto_sweep_gs.hip), fused
 (k_sweep_fused), the 64-state fused form (k_sweep_s64), row-split cluster (k_sweep_cluster) and one launch per Taylor step
 (k_sweep).  Every case below asserts, per callback, the form through those counters (the other forms 0), compares eval_constraint,
