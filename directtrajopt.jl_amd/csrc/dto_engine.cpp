@@ -108,6 +108,13 @@ struct BilHost {
     double* EP = nullptr;
     double* Upair = nullptr;
     double* d_Btab = nullptr;
+    // DTO_FLAG_BLOCK_GENERATORS: G_j = I_r (x) B_j found at create (kb x kb blocks, kr of them; (n, 1) without); `kron`: the
+    // structured path (dto_kron.hip) serves the integrator -- none of the workspaces above exist then
+    int kb = 0, kr = 1;
+    bool kron = false;
+    KKron kk{};
+    double* d_kron_scratch = nullptr;
+    size_t kron_stride = 0;
 };
 
 struct ConHost {
@@ -374,6 +381,30 @@ inline void count_sweep_form(dto_handle* h, int form) {
 // ------------------------------------------------------------------------------------------
 // structure
 // ------------------------------------------------------------------------------------------
+
+// Largest r dividing n with G_j == I_r (x) B_j for all m1 generators (n x n column-major, compared with ==): off-diagonal blocks
+// exactly zero, every diagonal block equal to the first.  1 if there is none.
+int find_replicas(const double* G, int n, int m1) {
+    for (int r = n; r >= 2; --r) {
+        if (n % r) continue;
+        const int b = n / r;
+        bool ok = true;
+        for (int j = 0; j < m1 && ok; ++j) {
+            const double* M = G + (size_t)j * n * n;
+            for (int c = 0; c < n && ok; ++c) {
+                const int bc = c / b;
+                const double* col = M + (size_t)c * n;
+                const double* first = M + (size_t)(c - bc * b) * n;
+                for (int q = 0; q < n; ++q) {
+                    const int bq = q / b;
+                    if (bq != bc ? !(col[q] == 0.0) : !(col[q] == first[q - bq * b])) { ok = false; break; }
+                }
+            }
+        }
+        if (ok) return r;
+    }
+    return 1;
+}
 
 // number of integrator rows touching a column of knot kn (0-based): D per adjacent interval
 inline int col_cnt(const dto_handle* h, int64_t kn) { return kn >= h->N ? 0 : (kn >= 1 ? 1 : 0) + (kn < h->K ? 1 : 0); }
@@ -1277,6 +1308,16 @@ void for_layers(dto_handle* h, size_t i, F&& f, bool first_only = false) {
     }
 }
 
+// structured bilinear integrator (dto_kron.hip): need 0 defect, 1 Jacobian block, 2 Hessian block of the owned intervals
+void kron_eval(dto_handle* h, BilHost& b, const double* dZ, const double* dmu, int need, double* dg, double* dvals, double* dH, hipStream_t st) {
+    HIP_CHECK(hipMemsetAsync(b.kk.stats, 0, 2 * sizeof(int32_t), st));
+    const int cp = (b.kk.rw + 15) / 16 * 16, m = b.k.m;
+    const int cols = need == 0 ? cp : (need == 1 ? (1 + m) * cp + b.kk.bp : (2 + 2 * m + m * (m + 1) / 2) * cp);
+    // priced at sixteen terms of 2 bp^2 per column and (on average two) sources
+    ProfScope ps(h, st, need == 2 ? CAT_SWEEP_ADJOINT : CAT_SWEEP, 2.0 * b.kk.bp * b.kk.bp * cols * 2.0 * 16.0 * (double)h->P.n_int);
+    HIP_CHECK(launch_kron(st, h->P, b.k, b.kk, dZ, dmu, need, dg, dvals, dH, b.d_kron_scratch, b.kron_stride));
+}
+
 void do_objective(dto_handle* h, const double* dZ, double* df, hipStream_t st) {
     HIP_CHECK(hipMemsetAsync(df, 0, sizeof(double), st));
     for (auto& o : h->obj) launch_objective(st, h->P, o, dZ, h->d_partial, df);
@@ -1304,6 +1345,7 @@ void remember_p_terms(dto_handle* h, BilHost& b, bool stored, int steps, hipStre
 void do_constraint(dto_handle* h, const double* dZ, double* dg, hipStream_t st) {
     const bool same = same_point(h, dZ, st);
     for (auto& b : h->bil) {
+        if (b.kron) { kron_eval(h, b, dZ, nullptr, 0, dg, nullptr, nullptr, st); continue; }
         if (b.small) {
             HIP_CHECK(launch_small(st, h->P, b.k, b.d_Gs, make_types(0, false), make_types(0, false), dZ, nullptr, dg, nullptr, nullptr, 1));
             continue;
@@ -1347,7 +1389,7 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
     // fill!(∂, 0), evaluator.jl:497 -- the -E_k block of a lone bilinear integrator is skipped: the chain
     // overwrites all of it
     // (enqueued inside the chain, where it fills the GPU while the host waits for the scaling decision)
-    const bool lone = h->bil.size() == 1 && h->P.n_int > 0 && !h->bil[0].small;
+    const bool lone = h->bil.size() == 1 && h->P.n_int > 0 && !h->bil[0].small && !h->bil[0].kron;
     // bound and primed output (dto_bind_output_dev): constants are in place, clear only the runs kernels accumulate into
     const bool keep_constants = h->bound[0] == dvals && h->primed[0] && ensure_bind_runs(h, 0);
     if (keep_constants) launch_zero_runs(st, h->d_bind_start[0], h->d_bind_len[0], h->n_bind_runs[0], dvals);
@@ -1358,6 +1400,7 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
     h->last_terms = 0;
     const bool same = same_point(h, dZ, st);
     for (auto& b : h->bil) {
+        if (b.kron) { kron_eval(h, b, dZ, nullptr, 1, nullptr, dvals, nullptr, st); continue; }
         if (b.small) {
             HIP_CHECK(launch_small(st, h->P, b.k, b.d_Gs, make_types(b.k.m, false), make_types(0, false), dZ, nullptr, nullptr, dvals, nullptr, 2));
             continue;
@@ -1527,6 +1570,11 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
         if (h->integ_kind[i] == DTO_INTEGRATOR_BILINEAR) {
             BilHost& b = h->bil[h->integ_index[i]];
             if (h->P.n_int <= 0) continue;
+            if (b.kron) {
+                need_zero();
+                kron_eval(h, b, dZ, dmu, 2, nullptr, nullptr, dH, st);
+                continue;
+            }
             if (b.small) {
                 need_zero();
                 HIP_CHECK(launch_small(st, h->P, b.k, b.d_Gs, make_types(b.k.m, true), make_types(b.k.m, false), dZ, dmu, nullptr, nullptr, dH, 4));
@@ -1670,7 +1718,7 @@ void build_jac_plan(dto_handle* h) {
     auto one = [&](int64_t at, double v) { p.one_pos.push_back(at); p.one_val.push_back(v); };
     // the -E_k block of a lone general-path bilinear integrator is written by the propagator chain alone (do_jacobian): final
     // with its chain chunk
-    const bool lone = h->bil.size() == 1 && P.n_int > 0 && !h->bil[0].small;
+    const bool lone = h->bil.size() == 1 && P.n_int > 0 && !h->bil[0].small && !h->bil[0].kron;
     for (int64_t kn = P.kn_lo; kn < P.kn_lo + P.n_knots; ++kn) {
         const int has_prev = kn >= 1, has_own = kn < h->K;
         const int cnt = has_prev + has_own;
@@ -1683,12 +1731,16 @@ void build_jac_plan(dto_handle* h) {
                 const int64_t prev_at = base + (int64_t)pre * cnt, own_at = prev_at + (has_prev ? d : 0);
                 const int kind = h->integ_kind[i];
                 if (kind == DTO_INTEGRATOR_BILINEAR) {
-                    const KBil& b = h->bil[h->integ_index[i]].k;
+                    const BilHost& bh = h->bil[h->integ_index[i]];
+                    const KBil& b = bh.k;
                     const bool xcol = j >= b.x_off && j < b.x_off + b.n;
                     // z_{k+1} half: identity on the state columns, zeros elsewhere -- constant
                     if (has_prev && xcol) one(prev_at + (j - b.x_off), 1.0);
                     // own rows: -E_k (x), the tangents (u) and -G(u) E_k x (dt) change; every other column is a structural zero
-                    if (has_own && (xcol || (j >= b.u_off && j < b.u_off + b.m) || j == h->dt_idx))
+                    // (structured path: of an x column only the rows of its own diagonal block change, the share (r-1)/r of the
+                    // x-block is a constant zero -- never shipped, never cleared again in a bound output)
+                    if (has_own && bh.kron && xcol) var(own_at + (int64_t)((j - b.x_off) / bh.kb) * bh.kb, bh.kb);
+                    else if (has_own && (xcol || (j >= b.u_off && j < b.u_off + b.m) || j == h->dt_idx))
                         var(own_at, d, lone && xcol && j != h->dt_idx && kn - P.kn_lo < P.n_int ? kn - P.kn_lo : -1);
                 } else if (kind == DTO_INTEGRATOR_DERIVATIVE) {
                     const KDer& dd = h->der[h->integ_index[i]];
@@ -2300,7 +2352,38 @@ int dto_create(const dto_problem_desc* d, dto_handle** out) {
                         }
                         b.g1[j] = std::max(b.g1[j], cs);
                     }
-                if (!sonly) {
+                b.kb = n; b.kr = 1;
+                if (d->flags & DTO_FLAG_BLOCK_GENERATORS) {
+                    b.kr = find_replicas(s.G, n, m1);
+                    b.kb = n / b.kr;
+                    KKron& kk = b.kk;
+                    kk.b = b.kb; kk.r = b.kr;
+                    // blocks below 16 rows are grouped while the group fits one MFMA row tile (I_g (x) B is a replicated block too)
+                    int grp = 1;
+                    if (b.kb < 16)
+                        for (int c = 1; c <= b.kr; ++c)
+                            if (b.kr % c == 0 && c * b.kb <= 16) grp = c;
+                    kk.bw = grp * b.kb; kk.rw = b.kr / grp; kk.bp = (kk.bw + 15) / 16 * 16;
+                    // the structured kernel gives every Hessian entry of the block one writer: state, controls and timestep apart
+                    const bool apart = (s.u_dim == 0 || s.u_off + s.u_dim <= s.x_off || s.u_off >= s.x_off + n) &&
+                                       (d->dt_idx < s.x_off || d->dt_idx >= s.x_off + n) &&
+                                       (s.u_dim == 0 || d->dt_idx < s.u_off || d->dt_idx >= s.u_off + s.u_dim);
+                    b.kron = b.kr >= 2 && b.kb <= 64 && n > 32 && apart && kron_supported(kk, s.u_dim, d->eval_hessian != 0);
+                }
+                if (!sonly && b.kron) {
+                    const int bp = b.kk.bp, bw = b.kk.bw;
+                    std::vector<double> Bm((size_t)m1 * bp * bp, 0.0), BmT((size_t)m1 * bp * bp, 0.0);
+                    for (int j = 0; j < m1; ++j)
+                        for (int c = 0; c < bw; ++c)
+                            for (int r = 0; r < bw; ++r) {
+                                const double v = s.G[(size_t)j * n * n + (size_t)c * n + r];
+                                Bm[(size_t)j * bp * bp + (size_t)c * bp + r] = v;
+                                BmT[(size_t)j * bp * bp + (size_t)r * bp + c] = v;
+                            }
+                    b.kk.Bm = own(h, dupload(Bm));
+                    b.kk.BmT = own(h, dupload(BmT));
+                    HIP_CHECK(kron_prepare());
+                } else if (!sonly) {
                     b.k.G = own(h, dupload(G));
                     b.k.GT = own(h, dupload(GT));
                     const bool small_on = (d->flags & DTO_FLAG_GENERAL_PATH_ONLY) == 0;
@@ -2737,6 +2820,15 @@ int dto_create(const dto_problem_desc* d, dto_handle** out) {
                 if (d->eval_hessian && 1 + m + m * (m + 1) / 2 > MAX_TYPES) throw HipError{"bilinear integrator: too many drives for second-order sweep"};
                 continue;  // the fused kernel needs no workspace
             }
+            if (b.kron) {
+                // one term slab per owned interval; the statistics words sit where the sweeps' do (deferred error convention)
+                b.kron_stride = (std::max(kron_scratch_doubles(b.kk, m, 1), d->eval_hessian ? kron_scratch_doubles(b.kk, m, 2) : (size_t)0) + 1) & ~(size_t)1;
+                b.d_kron_scratch = own(h, dalloc<double>(b.kron_stride * (size_t)std::max<int64_t>(h->P.n_int, 1)));
+                b.kk.stats = own(h, dalloc<int32_t>(2));
+                HIP_CHECK(hipMemset(b.kk.stats, 0, 2 * sizeof(int32_t)));
+                b.fw.stats = b.kk.stats;
+                continue;
+            }
             const int T_fw = std::max(2 + m, d->eval_hessian ? 1 + m + m * (m + 1) / 2 : 1 + m);  // +1: exp(A)w_x column of J w
             if (T_fw > MAX_TYPES) throw HipError{"bilinear integrator: too many drives for the second-order sweep"};
             alloc_sweep(h, b, b.fw, T_fw, d->eval_hessian != 0);  // W: G_l x for the Hessian's scalar blocks
@@ -2848,6 +2940,21 @@ int dto_interval_costs(const dto_handle* h, const double* Z, int64_t first, int6
     if (!h || !Z || !cost || first < 0 || count < 0 || first + count > h->K) return 1;
     for (int64_t i = 0; i < count; ++i) cost[i] = 0.0;
     for (const BilHost& b : h->bil) {
+        if (b.kron) {
+            // structured path: one sweep of (1 + m) r + b columns against bp x bp blocks, about two sources per column and term; the
+            // norm bound of a block is that of the whole generator (||I (x) B||_1 = ||B||_1)
+            const double bp = b.kk.bp, cols = (1.0 + b.k.m) * ((b.kk.rw + 15) / 16 * 16) + bp;
+            for (int64_t i = 0; i < count; ++i) {
+                const double* zk = Z + (first + i) * h->z;
+                double b1 = b.g1[0];
+                for (int j = 0; j < b.k.m; ++j) b1 += std::fabs(zk[b.k.u_off + j]) * b.g1[j + 1];
+                b1 *= std::fabs(zk[h->dt_idx]);
+                if (!(b1 == b1) || b1 > 1e6) b1 = 1e6;
+                const SweepPlan sp = plan_sweep(b1);
+                cost[i] += 2.0 * bp * bp * cols * 2.0 * (double)sp.d_ub * sp.q;
+            }
+            continue;
+        }
         const int m1 = b.k.m + 1;
         const double np = b.k.npad, gemm = 2.0 * np * np * np;
         // multisets of sizes 2..4 (and 0..4 for the factor K) over m + 1 generators: the generator-subspace GEMMs
@@ -2879,6 +2986,19 @@ int dto_interval_costs(const dto_handle* h, const double* Z, int64_t first, int6
     }
     // every other term kind costs O(z) per knot: a constant that keeps intervals without a bilinear integrator from counting as free
     for (int64_t i = 0; i < count; ++i) cost[i] += 64.0 * h->z;
+    return 0;
+}
+
+int dto_integrator_blocks(const dto_handle* h, int32_t integrator, int32_t* block_dim, int32_t* reps, int32_t* active) {
+    if (!h || integrator < 0 || integrator >= (int32_t)h->integ_kind.size()) return 1;
+    int bd = h->integ_dim[integrator], r = 1, on = 0;
+    if (h->integ_kind[integrator] == DTO_INTEGRATOR_BILINEAR) {
+        const BilHost& b = h->bil[h->integ_index[integrator]];
+        if (b.kr >= 2) { bd = b.kb; r = b.kr; on = b.kron ? 1 : 0; }
+    }
+    if (block_dim) *block_dim = bd;
+    if (reps) *reps = r;
+    if (active) *active = on;
     return 0;
 }
 
@@ -3149,7 +3269,7 @@ static void jac_product_matrix_free(dto_handle* h, const double* dZ, const doubl
 static void jac_product(dto_handle* h, const double* Z, const double* w, double* y, int transpose) {
     if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{"Jacobian-vector products need an unsharded handle"};
     bool mfree = h->eval_hessian != 0 || transpose == 0;  // the adjoint sweep buffers exist only with eval_hessian
-    for (auto& b : h->bil) mfree = mfree && !b.small && (transpose == 0 || b.ad.S != nullptr) && b.k.m + 2 <= MAX_TYPES;
+    for (auto& b : h->bil) mfree = mfree && !b.kron && !b.small && (transpose == 0 || b.ad.S != nullptr) && b.k.m + 2 <= MAX_TYPES;
     for (auto& c : h->con) mfree = mfree && !c.external;  // external blocks are placed into the value slab
     mfree = mfree && h->ext_int.empty() && h->tdb.empty();
     static const bool mfree_on = tune_int("DTO_JV_MATRIX_FREE", 1) != 0;

@@ -359,6 +359,22 @@ size_t tdb_scratch_doubles(const KTdb& T, int need);
 hipError_t launch_tdb(hipStream_t st, const KProb& P, const KTdb& T, const double* dZ, const double* dmu, int need, int64_t i_lo,
                       int64_t count, double* vals, double* jac, double* hess, double* scratch, size_t scratch_stride);
 
+// BilinearIntegrator with replicated-block generators G_j = I_r (x) B_j (dto_kron.hip): one workgroup per interval sweeps b-row
+// column groups against the b x b blocks and writes defect, Jacobian block or Hessian block of mu_k' f straight to their positions
+struct KKron {
+    int32_t b, r;        // finest structure found (what dto_integrator_blocks reports)
+    int32_t bw, rw, bp;  // working block (a few finest blocks grouped while they fit 16 rows), its replicas, bw padded to 16
+    const double* Bm;    // (m+1) working blocks, bp x bp column-major, zero-padded
+    const double* BmT;   // their transposes
+    int32_t* stats;      // [0] += workgroups whose sweep exhausted its budget, [1] = max terms used (the caller zeroes them)
+};
+hipError_t kron_prepare();
+bool kron_supported(const KKron& K, int m, bool hessian);
+size_t kron_scratch_doubles(const KKron& K, int m, int need);
+// need: 0 defect into g, 1 Jacobian block into vals (and the identity of the z_{k+1} half), 2 Hessian block added into H
+hipError_t launch_kron(hipStream_t st, const KProb& P, const KBil& B, const KKron& K, const double* dZ, const double* dmu, int need,
+                       double* g, double* vals, double* H, double* scratch, size_t stride);
+
 // host-evaluated knot terms (DTO_CONSTRAINT_EXTERNAL / DTO_OBJECTIVE_EXTERNAL_KNOT): scatter of caller-supplied blocks
 void launch_ext_cons(hipStream_t st, const KCon& C, const double* vals, double* g);
 void launch_ext_jac(hipStream_t st, const KCon& C, const double* blocks, double* vals);

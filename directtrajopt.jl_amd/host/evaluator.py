@@ -67,7 +67,8 @@ class Evaluator:
     # options applied to every new handle (dto_set_option name -> value); the repository's tests switch "host_xfer_check" on here
     default_options = {}
 
-    def __init__(self, prob, eval_hessian=True, device=0, k_lo=0, k_hi=0, verbose=False, general_path_only=False):
+    def __init__(self, prob, eval_hessian=True, device=0, k_lo=0, k_hi=0, verbose=False, general_path_only=False,
+                 block_generators=False):
         self._lib = load_library()
         self._h = capi.H()
         traj = prob.trajectory
@@ -197,7 +198,8 @@ class Evaluator:
         Z0 = np.ascontiguousarray(traj.vec(), dtype=np.float64)
         desc = capi.ProblemDesc(capi.DTO_ABI_VERSION, device, traj.N, traj.dim, traj.global_dim,
                                 traj.components[traj.timestep][0], int(eval_hessian), len(prob.integrators),
-                                len(terms), len(nl), capi.FLAG_GENERAL_PATH_ONLY if general_path_only else 0, integ, objs, cons,
+                                len(terms), len(nl), (capi.FLAG_GENERAL_PATH_ONLY if general_path_only else 0) |
+                                (capi.FLAG_BLOCK_GENERATORS if block_generators else 0), integ, objs, cons,
                                 _dp(Z0), k_lo, k_hi)
         if self._lib.dto_create(C.byref(desc), C.byref(self._h)) != 0:
             raise EngineError(self._lib.dto_last_error(None).decode())
@@ -232,6 +234,13 @@ class Evaluator:
     @property
     def handle(self):
         return self._h
+
+    def integrator_blocks(self, i):
+        """(block_dim, reps, active) of integrator i (0-based): the finest replicated-block structure G_j = I_reps (x) B_j found
+        at create with ``block_generators=True`` and whether the structured path serves it; (x_dim, 1, 0) otherwise."""
+        b, r, a = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self._lib.dto_integrator_blocks(self._h, int(i), C.byref(b), C.byref(r), C.byref(a)))
+        return b.value, r.value, a.value
 
     # ---- MOI surface (host vectors)
     def initialize(self, features=None):  # MOI.initialize, evaluator.jl:291

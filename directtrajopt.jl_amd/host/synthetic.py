@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .problem import (BilinearIntegrator, DerivativeIntegrator, DirectTrajOptProblem, LinearRegularizer,
+from .problem import (BilinearIntegrator, DerivativeIntegrator, DirectTrajOptProblem, KnotPointObjective, LinearRegularizer,
                       NonlinearKnotPointConstraint, QuadraticRegularizer)
 from .trajectory import NamedTrajectory
 
@@ -45,4 +45,52 @@ def make_l1_slack_problem(N, n, m=4, seed=42):
     integrators = [BilinearIntegrator(G, "x", "u", traj), DerivativeIntegrator("u", "du", traj)]
     J = QuadraticRegularizer("u", traj, 1.0) + LinearRegularizer("s_du", traj, 1e-2)
     con = NonlinearKnotPointConstraint("norm", "u", traj, c=1.0, equality=False, times=range(2, N))
+    return DirectTrajOptProblem(traj, J, integrators, constraints=[con])
+
+
+def unitary_fidelity_factor(goal_iso_cols, levels):
+    """A (2 x 2 levels^2) with ||A v||^2 = |tr(U_goal' U)|^2 / levels^2 for v the stacked iso columns [Re u_c; Im u_c]."""
+    g = np.asarray(goal_iso_cols, dtype=np.float64).reshape(levels, 2 * levels)
+    gr, gi = g[:, :levels], g[:, levels:]
+    return np.vstack([np.concatenate([gr, gi], axis=1).reshape(-1), np.concatenate([-gi, gr], axis=1).reshape(-1)]) / levels
+
+
+def unitary_problem(levels, drives, N, seed=42, dt=0.1, dt_large=None, dt_small=None, a_bound=1.0):
+    """A Piccolo-shaped unitary gate-synthesis problem.  Components: U (2 levels^2: the operator in isomorphic coordinates,
+    column after column), a (drives), da, dda, dt.  Dynamics G(a) = kron(I_levels, iso(-i H(a))), H(a) = H_0 + sum_j a_j H_j with
+    random Hermitian drift and drives -- what ``Evaluator(..., block_generators=True)`` recognises as ``levels`` replicas of a
+    2 levels x 2 levels block -- and two DerivativeIntegrators (a, da), (da, dda); QuadraticRegularizers on a, da, dda; a
+    terminal unitary-infidelity objective; the knot constraint ||a||^2 - a_bound <= 0 at the interior knots.
+    ``dt_large`` / ``dt_small`` replace the timestep of knot 2 / knot 3 (a step whose exponential needs scaling, one that needs
+    nothing beyond a few terms)."""
+    rng = np.random.Generator(np.random.Philox(seed))
+    b, n = 2 * levels, 2 * levels * levels
+
+    def iso_minus_i(H):  # iso(-i H) = [[Im H, Re H], [-Re H, Im H]]
+        return np.block([[H.imag, H.real], [-H.real, H.imag]])
+
+    blocks = []
+    for _ in range(drives + 1):
+        M = rng.standard_normal((levels, levels)) + 1j * rng.standard_normal((levels, levels))
+        H = (M + M.conj().T) / (2.0 * np.sqrt(levels))
+        blocks.append(iso_minus_i(H))
+    G = np.stack([np.kron(np.eye(levels), B) for B in blocks])
+    U = rng.standard_normal((n, N)) / np.sqrt(levels)
+    a = 0.1 * rng.standard_normal((drives, N))
+    da = rng.standard_normal((drives, N))
+    dda = rng.standard_normal((drives, N))
+    dts = np.full((1, N), float(dt))
+    if dt_large is not None and N >= 3:
+        dts[0, 1] = dt_large
+    if dt_small is not None and N >= 4:
+        dts[0, 2] = dt_small
+    traj = NamedTrajectory({"U": U, "a": a, "da": da, "dda": dda, "dt": dts}, timestep="dt")
+    integrators = [BilinearIntegrator(G, "U", "a", traj), DerivativeIntegrator("a", "da", traj),
+                   DerivativeIntegrator("da", "dda", traj)]
+    goal = np.linalg.qr(rng.standard_normal((levels, levels)) + 1j * rng.standard_normal((levels, levels)))[0]
+    goal_iso = np.concatenate([goal.real, goal.imag], axis=0).T  # row c: [Re u_c; Im u_c]
+    A = unitary_fidelity_factor(goal_iso, levels)
+    J = (QuadraticRegularizer("a", traj, 1e-2) + QuadraticRegularizer("da", traj, 1e-2) + QuadraticRegularizer("dda", traj, 1e-2)
+         + KnotPointObjective("lowrank_infidelity", "U", traj, times=[N], Qs=[100.0], A=A))
+    con = NonlinearKnotPointConstraint("sqnorm", "a", traj, c=a_bound, equality=False, times=range(2, N))
     return DirectTrajOptProblem(traj, J, integrators, constraints=[con])

@@ -152,6 +152,16 @@ typedef struct dto_constraint_desc {
 #define DTO_FLAG_GENERAL_PATH_ONLY 1 /* bilinear integrators with <= 32 states also take the batched-GEMM path instead of
                                         the fused one-workgroup-per-interval kernel (tests run both and compare) */
 
+#define DTO_FLAG_BLOCK_GENERATORS 2   /* look for replicated blocks in the generators of every DTO_INTEGRATOR_BILINEAR at create:
+                                        the largest r dividing x_dim with G_j == I_r (x) B_j for all m+1 generators (exact
+                                        comparison with ==).  Such an integrator -- an operator state in isomorphic coordinates,
+                                        x = vec(X), X of b x r, b = x_dim / r -- is served by the structured path when r >= 2,
+                                        b <= 64 and x_dim > 32: b x b work per interval instead of x_dim x x_dim, same value
+                                        layout, same structure (dto_integrator_blocks tells).  The options that concern the dense
+                                        chain and its sweeps (chain_form, chain_chunk, expm_form, sweep_form, reuse_forward_sweep,
+                                        overlap_sweep) are accepted and have no effect on a structured integrator; its J w and
+                                        J' w products go through the value slab */
+
 typedef struct dto_problem_desc {
     int32_t abi_version;    /* DTO_ABI_VERSION */
     int32_t device;         /* HIP device ordinal */
@@ -203,6 +213,10 @@ int dto_features_available(const dto_handle* h, int32_t* grad, int32_t* jac, int
 int dto_get_shard_info(const dto_handle* h, dto_shard_info* out);
 /* local constraint buffer = concatenation of global row segments [start1 (1-based), len] */
 int dto_shard_rows(const dto_handle* h, int64_t* start1, int64_t* len);
+
+/* finest replicated-block structure found in integrator i (0-based) and whether the structured path serves it;
+   (x_dim, 1, 0) when the flag is clear, the kind is not bilinear, or no structure exists */
+int dto_integrator_blocks(const dto_handle* h, int32_t integrator, int32_t* block_dim, int32_t* reps, int32_t* active);
 
 /* Cost model of one eval_constraint_jacobian for intervals first .. first+count-1 (0-based, GLOBAL numbering; Z is the whole NLP
  * vector, host memory): flops from the growth bound of every interval's A_k = dt_k G(u_k) -- squarings of the propagator chain,

@@ -40,6 +40,7 @@ using ..CommonInterface: evaluate!, eval_jacobian, eval_hessian_of_lagrangian
 const lib = get(ENV, "DTO_ENGINE_LIB", "libdto_engine.so")
 const DTO_ABI_VERSION = Int32(8)
 
+const DTO_FLAG_BLOCK_GENERATORS = Int32(2)
 const DTO_INTEGRATOR_BILINEAR = Int32(1)
 const DTO_INTEGRATOR_DERIVATIVE = Int32(2)
 const DTO_INTEGRATOR_EXTERNAL = Int32(3)
@@ -241,7 +242,8 @@ end
 
 first0(traj, name) = Int32(first(traj.components[name]) - 1)   # 0-based offset of a component inside a knot
 
-function GPUEvaluator(prob::DirectTrajOptProblem; eval_hessian::Bool = true, device::Integer = 0, k_lo::Integer = 0, k_hi::Integer = 0)
+function GPUEvaluator(prob::DirectTrajOptProblem; eval_hessian::Bool = true, device::Integer = 0, k_lo::Integer = 0, k_hi::Integer = 0,
+                      block_generators::Bool = false)
     traj = prob.trajectory
     traj.timestep isa Symbol || error("DTOEngine: the engine needs a timestep component (bilinear_integrator.jl:123)")
     keep = Any[]   # everything the descriptors point at, alive until dto_create returns
@@ -365,7 +367,7 @@ function GPUEvaluator(prob::DirectTrajOptProblem; eval_hessian::Bool = true, dev
     GC.@preserve keep idescs odescs cdescs Z0 begin
         desc = Ref(ProblemDesc(DTO_ABI_VERSION, Int32(device), Int64(traj.N), Int32(traj.dim), Int32(traj.global_dim),
                                first0(traj, traj.timestep), Int32(eval_hessian), Int32(length(idescs)), Int32(length(odescs)),
-                               Int32(length(cdescs)), Int32(0), pointer(idescs), pointer(odescs), pointer(cdescs),
+                               Int32(length(cdescs)), block_generators ? DTO_FLAG_BLOCK_GENERATORS : Int32(0), pointer(idescs), pointer(odescs), pointer(cdescs),
                                pointer(Z0), Int64(k_lo), Int64(k_hi)))
         rc = @ccall lib.dto_create(desc::Ptr{ProblemDesc}, h::Ptr{Ptr{Cvoid}})::Cint
         rc == 0 || error(unsafe_string(@ccall lib.dto_last_error(C_NULL::Ptr{Cvoid})::Cstring))
@@ -674,6 +676,18 @@ gather_constraint_dev!(ev::GPUEvaluator, dg_local::Ptr{Float64}, dg_full::Ptr{Fl
     check(ev, @ccall lib.dto_gather_constraint_dev(ev.handle::Ptr{Cvoid}, dg_local::Ptr{Float64}, dg_full::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 allreduce_objective_dev!(ev::GPUEvaluator, df::Ptr{Float64}, stream::Ptr{Cvoid}) =
     check(ev, @ccall lib.dto_allreduce_objective_dev(ev.handle::Ptr{Cvoid}, df::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+
+"""
+`(block_dim, reps, active)` of integrator `i` (1-based): the finest replicated-block structure `G_j = I_reps ⊗ B_j` the engine found
+in the generators it extracted from the closure (`GPUEvaluator(prob; block_generators = true)`: the `I(levels) ⊗ G̃(a)` of a unitary
+in isomorphic coordinates) and whether the structured path serves it; `(x_dim, 1, false)` otherwise.
+"""
+function integrator_blocks(ev::GPUEvaluator, i::Integer)
+    b, r, a = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    i0 = Int32(i - 1)
+    check(ev, @ccall lib.dto_integrator_blocks(ev.handle::Ptr{Cvoid}, i0::Int32, b::Ptr{Int32}, r::Ptr{Int32}, a::Ptr{Int32})::Cint)
+    return Int(b[]), Int(r[]), a[] != 0
+end
 
 """
 Flop model of one `eval_constraint_jacobian` per interval (`dto_interval_costs`): squarings of the propagator chain and Taylor

@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Replicated-block generators (Evaluator(..., block_generators=True)) against the dense path on the same unitary problem,
+timed with HIP events (a tools/ probe; GPU).
+
+Per shape, in ONE process: a flagged and an unflagged handle on ``synthetic.unitary_problem(levels, drives=4, N)``; device-resident
+inputs and outputs; eval_constraint, eval_constraint_jacobian and eval_hessian_lagrangian, each after a warm-up of at least 30 ms of
+GPU work (the chip ramps for about that long); the median of ``--reps`` single-call timings.  The unflagged handle runs the dense
+path untouched: it is the yardstick.  For the structured handle the line also gives the kernel time, the priced FP64 rate of the
+sweep launches (dto_profile_get "expmv" / "expmv_adjoint") and the rate at which the value slab is produced (slab bytes / call time).
+One JSON line per shape.
+
+    python tools/kron_time.py                          # levels 8 x 1000 knots (n = 128), 16 x 500 (n = 512)
+    python tools/kron_time.py --shapes 32x40 --dense 0 # n = 2048 (b = 64): the structured handle alone
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+import dto_amd  # noqa: E402
+
+
+def one_call_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def timed(fn, reps):
+    spent = 0.0
+    while spent < 30.0:          # warm-up: at least 30 ms of GPU work
+        spent += one_call_ms(fn)
+    return statistics.median(one_call_ms(fn) for _ in range(reps))
+
+
+def measure_handle(prob, flagged, reps, sigma=0.7):
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ev = dto_amd.Evaluator(prob, eval_hessian=True, block_generators=flagged)
+    try:
+        g = torch.Generator(device="cpu").manual_seed(1)
+        Z = torch.from_numpy(prob.trajectory.vec()).to(dev)
+        mu = torch.randn(ev.n_constraints, generator=g, dtype=torch.float64).to(dev)
+        out = {"blocks": ev.integrator_blocks(0)}
+        con = torch.empty(ev.n_constraints, dtype=torch.float64, device=dev)
+        out["constraint_ms"] = round(timed(lambda: ev.eval_constraint_dev(Z.data_ptr(), con.data_ptr(), st), reps), 4)
+        J = torch.empty(ev.n_jacobian_entries, dtype=torch.float64, device=dev)
+        jac = lambda: ev.eval_jacobian_dev(Z.data_ptr(), J.data_ptr(), st)
+        out["jacobian_ms"] = round(timed(jac, reps), 4)
+        out["jacobian_slab_GB"] = round(8e-9 * ev.n_jacobian_entries, 3)
+        out["jacobian_slab_TBps"] = round(8e-9 * ev.n_jacobian_entries / out["jacobian_ms"], 3)
+        if flagged:
+            ev.profile_enable(True); ev.profile_reset(); jac(); torch.cuda.synchronize()
+            ms, _, fl = ev.profile_get("expmv")
+            zms, _, zb = ev.profile_get("zero_fill")
+            out.update({"jacobian_kernel_ms": round(ms, 4), "jacobian_kernel_TFLOPs": round(fl / ms * 1e-9, 3) if ms > 0 else None,
+                        "jacobian_zero_fill_ms": round(zms, 4), "jacobian_zero_fill_TBps": round(zb / zms * 1e-9, 3) if zms > 0 else None})
+            ev.profile_enable(False)
+        del J
+        H = torch.empty(ev.n_hessian_entries, dtype=torch.float64, device=dev)
+        hes = lambda: ev.eval_hessian_dev(Z.data_ptr(), sigma, mu.data_ptr(), H.data_ptr(), st)
+        out["hessian_ms"] = round(timed(hes, reps), 4)
+        out["hessian_slab_GB"] = round(8e-9 * ev.n_hessian_entries, 3)
+        if flagged:
+            ev.profile_enable(True); ev.profile_reset(); hes(); torch.cuda.synchronize()
+            ms, _, fl = ev.profile_get("expmv_adjoint")
+            zms, _, zb = ev.profile_get("zero_fill")
+            out.update({"hessian_kernel_ms": round(ms, 4), "hessian_kernel_TFLOPs": round(fl / ms * 1e-9, 3) if ms > 0 else None,
+                        "hessian_zero_fill_ms": round(zms, 4), "hessian_zero_fill_TBps": round(zb / zms * 1e-9, 3) if zms > 0 else None})
+            ev.profile_enable(False)
+        return out
+    finally:
+        ev.close()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--shapes", default="8x1000,16x500", help="comma-separated levels x knots")
+    ap.add_argument("--drives", type=int, default=4)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--dense", type=int, default=1, help="0: time the structured handle alone")
+    ap.add_argument("--sigma", type=float, default=0.7, help="objective weight of the Hessian (0: the constraint side alone -- the\n"
+                    "terminal infidelity's n x n block is assembled by one launch of its own, the same on both handles)")
+    a = ap.parse_args()
+    for s in a.shapes.split(","):
+        levels, N = (int(x) for x in s.lower().split("x"))
+        prob = dto_amd.host.synthetic.unitary_problem(levels, a.drives, N, seed=42)
+        out = {"levels": levels, "n": 2 * levels * levels, "knots": N, "drives": a.drives, "sigma": a.sigma}
+        out["structured"] = measure_handle(prob, True, a.reps, a.sigma)
+        if a.dense:
+            out["dense"] = measure_handle(prob, False, a.reps, a.sigma)
+            out["speedup"] = {k: round(out["dense"][k + "_ms"] / out["structured"][k + "_ms"], 2) for k in ("constraint", "jacobian", "hessian")}
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
