@@ -6,7 +6,7 @@ error behaviour) on top of it through ``ctypes``:
 
     NamedTrajectory, BilinearIntegrator, DerivativeIntegrator, QuadraticRegularizer,
     LinearRegularizer, MinimumTimeObjective, NullObjective, CompositeObjective (``+`` / ``*``),
-    NonlinearKnotPointConstraint (built-in g kinds), DirectTrajOptProblem, Evaluator (MOI surface)
+    NonlinearKnotPointConstraint (built-in g kinds), fidelity_constraint, DirectTrajOptProblem, Evaluator (MOI surface)
 
 There is no CPU fallback: constructing an ``Evaluator`` without the HIP library or without a GPU
 raises.  The directory name carries a dot, so import it through ``dto_amd`` (repo root shim).
@@ -30,6 +30,7 @@ from .host.problem import (  # noqa: F401
     ModulatedGenerators,
     ket_fidelity_factor,
     NonlinearKnotPointConstraint,
+    fidelity_constraint,
     DirectTrajOptProblem,
 )
 from .host.evaluator import Evaluator, EngineError, load_library, library_path  # noqa: F401

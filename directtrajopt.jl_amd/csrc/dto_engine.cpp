@@ -130,6 +130,7 @@ struct ConHost {
     int ext_slot = -1;
     std::vector<double> jac0;     // external: Jacobian blocks at Z0 (pattern)
     std::vector<double> hess0;    // global: Hessian of sum(g) at Z0 (pattern)
+    std::vector<double> M;        // QUADFORM_MINUS_C: the symmetric n_comps x n_comps matrix, column-major
     KExtTerm xk{};                // external: placement of the Hessian blocks
 };
 
@@ -410,6 +411,15 @@ int find_replicas(const double* G, int n, int m1) {
 inline int col_cnt(const dto_handle* h, int64_t kn) { return kn >= h->N ? 0 : (kn >= 1 ? 1 : 0) + (kn < h->K ? 1 : 0); }
 
 double con_jac_value(const ConHost& c, const double* zk, int comp_i) {
+    if (c.k.kind == DTO_CONSTRAINT_QUADFORM_MINUS_C) {  // 2 (M v)_c, summed over j ascending with an unfused multiply-add: the
+        const size_t n = c.comps.size();                // arithmetic of the device's row walk (dto_quadform.hip, qf_row)
+        double y = 0.0;
+        {
+#pragma clang fp contract(off)
+            for (size_t j = 0; j < n; ++j) y = y + c.M[(size_t)comp_i + n * j] * zk[c.comps[j]];
+        }
+        return 2.0 * y;
+    }
     double s = 0.0;
     for (int q : c.comps) s += zk[q] * zk[q];
     const double v = zk[c.comps[comp_i]];
@@ -2454,7 +2464,7 @@ int dto_create(const dto_problem_desc* d, dto_handle** out) {
         for (int i = 0; i < d->n_constraints; ++i) {
             const dto_constraint_desc& s = d->constraints[i];
             if (s.kind != DTO_CONSTRAINT_NORM_MINUS_C && s.kind != DTO_CONSTRAINT_SQNORM_MINUS_C && s.kind != DTO_CONSTRAINT_EXTERNAL &&
-                s.kind != DTO_CONSTRAINT_EXTERNAL_GLOBAL)
+                s.kind != DTO_CONSTRAINT_EXTERNAL_GLOBAL && s.kind != DTO_CONSTRAINT_QUADFORM_MINUS_C)
                 throw HipError{"unknown constraint kind"};
             if (s.kind == DTO_CONSTRAINT_EXTERNAL_GLOBAL) {
                 // NonlinearGlobalConstraint: one listing at the pseudo-knot N whose "components" are global_data entries
@@ -2493,6 +2503,18 @@ int dto_create(const dto_problem_desc* d, dto_handle** out) {
             c.comps.assign(s.comps, s.comps + s.n_comps);
             for (int q : c.comps)
                 if (q < 0 || q >= d->z) throw HipError{"constraint: component out of range"};
+            if (s.kind == DTO_CONSTRAINT_QUADFORM_MINUS_C) {
+                if (!s.hess0) throw HipError{"quadratic-form constraint: the matrix M (hess0, n_comps x n_comps) is required"};
+                const size_t n = (size_t)s.n_comps;
+                std::vector<int32_t> sc = c.comps;
+                std::sort(sc.begin(), sc.end());
+                if (std::adjacent_find(sc.begin(), sc.end()) != sc.end())
+                    throw HipError{"quadratic-form constraint: a component is listed twice in comps"};
+                c.M.assign(s.hess0, s.hess0 + n * n);
+                for (size_t a = 0; a < n; ++a)
+                    for (size_t b2 = a + 1; b2 < n; ++b2)
+                        if (!(c.M[a + n * b2] == c.M[b2 + n * a])) throw HipError{"quadratic-form constraint: M is not symmetric"};
+            }
             c.n_times_total = s.n_times;
             for (int64_t t = 0; t < s.n_times; ++t) {
                 if (s.times[t] < 1 || s.times[t] > d->N) throw HipError{"constraint: time out of range"};
@@ -2637,6 +2659,7 @@ int dto_create(const dto_problem_desc* d, dto_handle** out) {
                 c.k.tidx = own(h, dupload(tidx));
                 c.k.hess_on = own(h, dupload(hess_on));
                 c.k.jpos = own(h, dupload(jpos));
+                if (!c.M.empty()) c.k.M = own(h, dupload(c.M));
                 if (c.external) {  // Hessian blocks: knot constraints place knot entries, the global one tail entries
                     c.xk.nc = c.global ? 0 : (int32_t)c.comps.size();
                     c.xk.ng = c.global ? (int32_t)c.comps.size() : 0;

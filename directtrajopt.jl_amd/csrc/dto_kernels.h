@@ -328,11 +328,17 @@ struct KCon {  // NonlinearKnotPointConstraint with a built-in g
                              // ForwardDiff.hessian! into the block view overwrites (knot_point_constraint.jl:285-291)
     int32_t g_dim, external; // outputs per listed time (1 for the built-in kinds); external: values come from the host
     int32_t repeats, comp_repeats;  // the owned `times` name a knot twice / `comps` name a component twice (J' w then adds in listing order)
+    const double* M;         // device, QUADFORM_MINUS_C (kind 5): the symmetric n_comps x n_comps matrix, column-major
 };
 void launch_cons_knot(hipStream_t st, const KProb& P, const KCon& C, const double* dZ, double* g);
 void launch_jv_knot(hipStream_t st, const KProb& P, const KCon& C, const double* dZ, const double* w, double* y, int transpose);
 void launch_jac_knot(hipStream_t st, const KProb& P, const KCon& C, const double* dZ, double* vals);
 void launch_hess_knot(hipStream_t st, const KProb& P, const KCon& C, const double* dZ, const double* dmu, double* H);
+// kind 5, g(v) = v' M v - c (dto_quadform.hip): the four launchers above hand such a constraint to these
+void launch_qf_cons(hipStream_t st, const KProb& P, const KCon& C, const double* dZ, double* g);
+void launch_qf_jac(hipStream_t st, const KProb& P, const KCon& C, const double* dZ, double* vals);
+void launch_qf_jv(hipStream_t st, const KProb& P, const KCon& C, const double* dZ, const double* w, double* y, int transpose);
+void launch_qf_hess(hipStream_t st, const KProb& P, const KCon& C, const double* dmu, double* H);
 
 // host-evaluated integrator (DTO_INTEGRATOR_EXTERNAL): placement of the caller's per-interval blocks
 struct KExtInt {

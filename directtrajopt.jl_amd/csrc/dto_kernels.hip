@@ -1856,6 +1856,7 @@ __global__ void k_cons_knot(KProb P, KCon C, const double* __restrict__ Z, doubl
     g[C.lrow[i]] = (C.kind == 1 ? sqrt(s) : s) - C.c;
 }
 void launch_cons_knot(hipStream_t st, const KProb& P, const KCon& C, const double* dZ, double* g) {
+    if (C.kind == 5) return launch_qf_cons(st, P, C, dZ, g);
     if (C.n_times <= 0) return;
     hipLaunchKernelGGL(k_cons_knot, dim3((unsigned)((C.n_times + 255) / 256)), dim3(256), 0, st, P, C, dZ, g);
 }
@@ -1942,6 +1943,7 @@ __global__ void k_jac_knot(KProb P, KCon C, const double* __restrict__ Z, double
     vals[p] = C.kind == 1 ? v / sqrt(knot_norm2(P, C, zk)) : 2.0 * v;
 }
 void launch_jac_knot(hipStream_t st, const KProb& P, const KCon& C, const double* dZ, double* vals) {
+    if (C.kind == 5) return launch_qf_jac(st, P, C, dZ, vals);
     const int64_t n = C.n_times * C.n_comps;
     if (n <= 0) return;
     hipLaunchKernelGGL(k_jac_knot, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, C, dZ, vals);
@@ -2093,6 +2095,7 @@ __global__ void k_jtv_knot(KProb P, KCon C, const double* __restrict__ Z, const 
     }
 }
 void launch_jv_knot(hipStream_t st, const KProb& P, const KCon& C, const double* dZ, const double* w, double* y, int transpose) {
+    if (C.kind == 5) return launch_qf_jv(st, P, C, dZ, w, y, transpose);
     const int64_t n = C.n_times * C.n_comps;
     if (n <= 0) return;
     if (!transpose) {
@@ -2183,18 +2186,8 @@ __global__ void k_gradient(KProb P, KObj O, const double* __restrict__ Z, double
     const double* zk = Z + kn * P.z;
     double* gk = grad + kn * P.z - P.grad_lo;
     const double dt = zk[P.dt_idx];
-    if (O.kind == 6) {  // grad l = -2 sign(1 - F) A'(A v); same per-listing overwrite as kind 4
-        if (!O.last[i]) return;
-        const double sgn = sign0(1.0 - lowrank_F(O, zk));
-        for (int c = 0; c < O.n_comps; ++c) {
-            double g = 0.0;
-            for (int r = 0; r < O.comp_dim; ++r) {
-                double y = 0.0;
-                for (int c2 = 0; c2 < O.n_comps; ++c2) y += O.R[r + (int64_t)O.comp_dim * c2] * zk[O.comps[c2]];
-                g += O.R[r + (int64_t)O.comp_dim * c] * y;
-            }
-            atomicAdd(&gk[O.comps[c]], O.weight * O.Qs[i] * (-2.0 * sgn) * g);
-        }
+    if (O.kind == 6) {  // served by k_gradient_lowrank (launch_gradient)
+        return;
     } else if (O.kind == 4) {  // gradient! writes 2 Q_i (v - p_i) per listed time, later entries overwrite (knot_point_objectives.jl:184-207)
         if (!O.last[i]) return;
         for (int c = 0; c < O.n_comps; ++c) {
@@ -2220,8 +2213,32 @@ __global__ void k_gradient(KProb P, KObj O, const double* __restrict__ Z, double
         atomicAdd(&gk[P.dt_idx], O.weight * s);
     }
 }
+// kind 6, grad l = -2 sign(1 - F) A'(A v), same per-listing overwrite as kind 4: one thread per (listing, component) -- a
+// workgroup serves one listing, so F and A v (each thread sums them itself, in lowrank_F's serial order) come from uniform loads
+__global__ void __launch_bounds__(256) k_gradient_lowrank(KProb P, KObj O, const double* __restrict__ Z, double* __restrict__ grad,
+                                                          int tiles) {
+    const int64_t i = blockIdx.x / (unsigned)tiles;
+    const int c = (int)(blockIdx.x % (unsigned)tiles) * 256 + (int)threadIdx.x;
+    if (c >= O.n_comps || !O.last[i]) return;
+    const int64_t kn = O.times[i];
+    const double* zk = Z + kn * P.z;
+    double* gk = grad + kn * P.z - P.grad_lo;
+    const double sgn = sign0(1.0 - lowrank_F(O, zk));
+    double g = 0.0;
+    for (int r = 0; r < O.comp_dim; ++r) {
+        double y = 0.0;
+        for (int c2 = 0; c2 < O.n_comps; ++c2) y += O.R[r + (int64_t)O.comp_dim * c2] * zk[O.comps[c2]];
+        g += O.R[r + (int64_t)O.comp_dim * c] * y;
+    }
+    atomicAdd(&gk[O.comps[c]], O.weight * O.Qs[i] * (-2.0 * sgn) * g);
+}
 void launch_gradient(hipStream_t st, const KProb& P, const KObj& O, const double* dZ, double* grad) {
     if (O.n_times <= 0) return;
+    if (O.kind == 6) {
+        const int tiles = (O.n_comps + 255) / 256;
+        hipLaunchKernelGGL(k_gradient_lowrank, dim3((unsigned)(O.n_times * tiles)), dim3(256), 0, st, P, O, dZ, grad, tiles);
+        return;
+    }
     hipLaunchKernelGGL(k_gradient, dim3((unsigned)((O.n_times + 255) / 256)), dim3(256), 0, st, P, O, dZ, grad);
 }
 
@@ -2245,18 +2262,8 @@ __global__ void k_hess_objective(KProb P, KObj O, const double* __restrict__ Z, 
     const double* zk = Z + kn * P.z;
     const double dt = zk[P.dt_idx];
     const double sw = sigma * O.weight;
-    if (O.kind == 6) {  // A' G A with G = -2 sign(1 - F) I (knot_hvp.jl:58-66), row <= col entries
-        if (!O.last[i]) return;
-        const double sgn = sign0(1.0 - lowrank_F(O, zk));
-        if (sgn == 0.0) return;
-        for (int a = 0; a < O.n_comps; ++a)
-            for (int b = 0; b < O.n_comps; ++b) {
-                const int ca = O.comps[a], cb = O.comps[b];
-                if (ca > cb) continue;
-                double h = 0.0;
-                for (int r = 0; r < O.comp_dim; ++r) h += O.R[r + (int64_t)O.comp_dim * a] * O.R[r + (int64_t)O.comp_dim * b];
-                if (h != 0.0) atomicAdd(&H[hess_pos(P, kn, ca, cb)], sw * O.Qs[i] * (-2.0 * sgn) * h);
-            }
+    if (O.kind == 6) {  // served by k_hess_lowrank (launch_hess_objective)
+        return;
     } else if (O.kind == 4) {  // triu of the per-knot Hessian 2 Q_i I (knot_point_objectives.jl:224-243)
         if (!O.last[i]) return;
         for (int c = 0; c < O.n_comps; ++c) {
@@ -2285,8 +2292,31 @@ __global__ void k_hess_objective(KProb P, KObj O, const double* __restrict__ Z, 
         }
     }
 }
+// kind 6, A' G A with G = -2 sign(1 - F) I (knot_hvp.jl:58-66), row <= col entries: one thread per (listing, a, b), adjacent
+// lanes on adjacent a (adjacent slab entries where the components ascend); a workgroup serves one listing, F as above
+__global__ void __launch_bounds__(256) k_hess_lowrank(KProb P, KObj O, const double* __restrict__ Z, double sigma, double* __restrict__ H,
+                                                      int tiles) {
+    const int64_t i = blockIdx.x / (unsigned)tiles;
+    const int64_t ab = (int64_t)(blockIdx.x % (unsigned)tiles) * 256 + threadIdx.x;
+    if (ab >= (int64_t)O.n_comps * O.n_comps || !O.last[i]) return;
+    const int a = (int)(ab % O.n_comps), b = (int)(ab / O.n_comps);
+    const int ca = O.comps[a], cb = O.comps[b];
+    if (ca > cb) return;
+    const int64_t kn = O.times[i];
+    const double sw = sigma * O.weight;
+    const double sgn = sign0(1.0 - lowrank_F(O, Z + kn * P.z));
+    if (sgn == 0.0) return;
+    double h = 0.0;
+    for (int r = 0; r < O.comp_dim; ++r) h += O.R[r + (int64_t)O.comp_dim * a] * O.R[r + (int64_t)O.comp_dim * b];
+    if (h != 0.0) atomicAdd(&H[hess_pos(P, kn, ca, cb)], sw * O.Qs[i] * (-2.0 * sgn) * h);
+}
 void launch_hess_objective(hipStream_t st, const KProb& P, const KObj& O, const double* dZ, double sigma, double* H) {
     if (O.n_times <= 0 || O.kind == 3) return;
+    if (O.kind == 6) {
+        const int tiles = (int)(((int64_t)O.n_comps * O.n_comps + 255) / 256);
+        hipLaunchKernelGGL(k_hess_lowrank, dim3((unsigned)(O.n_times * tiles)), dim3(256), 0, st, P, O, dZ, sigma, H, tiles);
+        return;
+    }
     hipLaunchKernelGGL(k_hess_objective, dim3((unsigned)((O.n_times + 255) / 256)), dim3(256), 0, st, P, O, dZ, sigma, H);
 }
 
@@ -2333,6 +2363,7 @@ __global__ void k_hess_knot(KProb P, KCon C, const double* __restrict__ Z, const
     if (v != 0.0) atomicAdd(&H[hess_pos(P, kn, ca, cb)], v);
 }
 void launch_hess_knot(hipStream_t st, const KProb& P, const KCon& C, const double* dZ, const double* dmu, double* H) {
+    if (C.kind == 5) return launch_qf_hess(st, P, C, dmu, H);
     const int64_t n = C.n_times * C.n_comps * C.n_comps;
     if (n <= 0) return;
     hipLaunchKernelGGL(k_hess_knot, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, C, dZ, dmu, H);

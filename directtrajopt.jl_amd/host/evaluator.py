@@ -192,8 +192,13 @@ class Evaluator:
                                               comps.ctypes.data_as(capi.c_int32_p), 0.0, _ip(t), t.size, _dp(jac0), None)
                 self._ext_con.append(c)
                 continue
+            M = None
+            if c.kind == "quadform":  # the matrix rides in hess0, column-major
+                M = np.ascontiguousarray(c.M.T, dtype=np.float64)
+                keep.append(M)
             cons[i] = capi.ConstraintDesc(NonlinearKnotPointConstraint.KINDS[c.kind], int(c.equality), comps.size, 1,
-                                          comps.ctypes.data_as(capi.c_int32_p), c.c, _ip(t), t.size, None, None)
+                                          comps.ctypes.data_as(capi.c_int32_p), c.c, _ip(t), t.size, None,
+                                          None if M is None else _dp(M))
 
         Z0 = np.ascontiguousarray(traj.vec(), dtype=np.float64)
         desc = capi.ProblemDesc(capi.DTO_ABI_VERSION, device, traj.N, traj.dim, traj.global_dim,

@@ -409,15 +409,17 @@ class NonlinearKnotPointConstraint:
     src/constraints/nonlinear/knot_point_constraint.jl:27-107.
 
     ``g`` is either a kind built into the engine -- ``"norm"`` (g(v) = [||v|| - c], the shape of
-    test/test_snippets.jl:39-45) or ``"sqnorm"`` (g(v) = [||v||^2 - c]) -- or a callable ``g(v, p) -> array``
+    test/test_snippets.jl:39-45), ``"sqnorm"`` (g(v) = [||v||^2 - c]) or ``"quadform"`` (g(v) = [v' M v - c] with the constant
+    symmetric matrix ``M``: expectation values, weighted populations, fidelity bounds, see ``fidelity_constraint``) -- or a
+    callable ``g(v, p) -> array``
     (the reference's closure form; g_dim is taken from one evaluation at the trajectory, as the reference does,
     knot_point_constraint.jl:84-90).  A callable is evaluated on the host together with its Jacobian and the
     Hessian of mu_i' g (``jac(v, p)``, ``hess(v, p, mu_i)`` if given, else differentiated numerically) and the
     engine merges the blocks."""
 
-    KINDS = {"norm": 1, "sqnorm": 2}
+    KINDS = {"norm": 1, "sqnorm": 2, "quadform": 5}
 
-    def __init__(self, g, names, traj, c=0.0, equality=True, times=None, params=None, jac=None, hess=None):
+    def __init__(self, g, names, traj, c=0.0, equality=True, times=None, params=None, jac=None, hess=None, M=None):
         names = [names] if isinstance(names, str) else list(names)
         self.external = callable(g)
         if not self.external and g not in self.KINDS:
@@ -426,6 +428,12 @@ class NonlinearKnotPointConstraint:
         self.times = _times(range(1, traj.N + 1) if times is None else times, traj.N)
         self.comps = np.concatenate([np.asarray(traj.components[n]) for n in names]).astype(np.int32)
         self.g_dim, self.var_dim = 1, self.comps.size
+        if g == "quadform":
+            if M is None:
+                raise ValueError("the quadratic form needs its matrix M")
+            self.M = np.array(M, dtype=np.float64)
+            if self.M.shape != (self.comps.size, self.comps.size) or not np.array_equal(self.M, self.M.T):
+                raise ValueError("M must be a symmetric (n_comps, n_comps) matrix")
         if self.external:
             self.g, self.jac, self.hess = g, jac, hess
             self.params = [None] * self.times.size if params is None else list(params)
@@ -454,6 +462,18 @@ class NonlinearKnotPointConstraint:
                                       None if self.hess is None else (lambda x: self.hess(x, p, m)))
                 second[i] = Hm.T
         return vals, first, second
+
+
+def fidelity_constraint(A, names, traj, fidelity, times=None):
+    """The final-fidelity bound ||A v||^2 >= fidelity of the minimum-time stage as a built-in quadratic form:
+    NonlinearKnotPointConstraint(x -> [F_min - F(x)], names, traj; times=[N], equality=false) with F(v) = ||A v||^2, i.e.
+    M = -A'A, c = -fidelity.  ``A`` is the (rank, n_comps) factor of the coherent fidelities (``ket_fidelity_factor``,
+    ``synthetic.unitary_fidelity_factor``); ``times`` defaults to the last knot."""
+    A = np.asarray(A, dtype=np.float64)
+    M = -(A.T @ A)
+    M = 0.5 * (M + M.T)  # exactly symmetric whatever the product's summation order
+    return NonlinearKnotPointConstraint("quadform", names, traj, c=-float(fidelity), M=M, equality=False,
+                                        times=[traj.N] if times is None else times)
 
 
 class DirectTrajOptProblem:

@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from .problem import (BilinearIntegrator, DerivativeIntegrator, DirectTrajOptProblem, KnotPointObjective, LinearRegularizer,
-                      NonlinearKnotPointConstraint, QuadraticRegularizer)
+                      MinimumTimeObjective, NonlinearKnotPointConstraint, QuadraticRegularizer, fidelity_constraint)
 from .trajectory import NamedTrajectory
 
 
@@ -94,3 +94,24 @@ def unitary_problem(levels, drives, N, seed=42, dt=0.1, dt_large=None, dt_small=
          + KnotPointObjective("lowrank_infidelity", "U", traj, times=[N], Qs=[100.0], A=A))
     con = NonlinearKnotPointConstraint("sqnorm", "a", traj, c=a_bound, equality=False, times=range(2, N))
     return DirectTrajOptProblem(traj, J, integrators, constraints=[con])
+
+
+def unitary_minimum_time_problem(levels, drives, N, fidelity=0.99, seed=42, D=1.0, closure=False, **kw):
+    """The second stage of gate synthesis on ``unitary_problem``'s trajectory, generators and goal (same random stream):
+    MinimumTimeObjective(D) plus the three regularizers, the bound ||a||^2 <= a_bound at the interior knots and the
+    final-fidelity bound F(U_N) >= fidelity at the last knot, F(v) = ||A v||^2 the unitary fidelity -- the built-in quadratic
+    form M = -A'A, c = -fidelity (``fidelity_constraint``).  ``closure=True`` states the same bound as a host closure with
+    analytic derivatives (DTO_CONSTRAINT_EXTERNAL: the route such a bound had to take before the built-in kind)."""
+    base = unitary_problem(levels, drives, N, seed=seed, **kw)
+    traj = base.trajectory
+    terms = [(o, w) for o, w in zip(base.objective.objectives, base.objective.weights) if isinstance(o, QuadraticRegularizer)]
+    infid = [o for o in base.objective.objectives if isinstance(o, KnotPointObjective)][0]
+    J = MinimumTimeObjective(traj, D=D)
+    for o, w in terms:
+        J = J + w * o
+    bound = fidelity_constraint(infid.A, "U", traj, fidelity)
+    if closure:
+        M, c = bound.M, bound.c
+        bound = NonlinearKnotPointConstraint(lambda v, p: np.array([v @ (M @ v) - c]), "U", traj, equality=False, times=[N],
+                                             jac=lambda v, p: (2.0 * (M @ v))[None, :], hess=lambda v, p, mu: 2.0 * mu[0] * M)
+    return DirectTrajOptProblem(traj, J, base.integrators, constraints=list(base.constraints) + [bound])

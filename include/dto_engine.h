@@ -85,6 +85,13 @@ extern "C" {
 /* built-in g kinds for NonlinearKnotPointConstraint (knot_point_constraint.jl:27-107) */
 #define DTO_CONSTRAINT_NORM_MINUS_C 1   /* g(v) = [ ||v||_2   - c ] */
 #define DTO_CONSTRAINT_SQNORM_MINUS_C 2 /* g(v) = [ ||v||_2^2 - c ] */
+#define DTO_CONSTRAINT_QUADFORM_MINUS_C 5 /* g(v) = [ v' M v - c ], M symmetric n_comps x n_comps, passed in `hess0` (column-major,
+                                           copied at create; M[a,b] == M[b,a] exactly, no component listed twice in `comps`).
+                                           Expectation values, weighted populations, subspace fidelities; a final-fidelity
+                                           bound ||A v||^2 >= F_min is M = -A'A, c = -F_min, equality = 0.  Evaluated on the
+                                           device like the two kinds above (csrc/dto_quadform.hip): Jacobian entries 2 (M v)_c
+                                           with the pattern of the numeric Jacobian at Z0, Hessian block 2 mu_i M (exact zeros of
+                                           M are not added) */
 #define DTO_CONSTRAINT_EXTERNAL_GLOBAL 4 /* NonlinearGlobalConstraint g(global_data[comps]) with g_dim outputs
                                            (global_constraint.jl:20-160): host closure; `comps` index global_data,
                                            `times` is unused; patterns = non-zeros of `jac0` (g_dim x n_comps) and
@@ -145,7 +152,8 @@ typedef struct dto_constraint_desc {
     int64_t n_times;
     const double* jac0;     /* EXTERNAL only: Jacobian blocks at Z0, [n_times] blocks g_dim x n_comps column-major;
                                entries that are exactly 0.0 are outside the pattern (evaluator.jl:136) */
-    const double* hess0;    /* EXTERNAL_GLOBAL only: Hessian of sum(g) at Z0, n_comps x n_comps column-major */
+    const double* hess0;    /* EXTERNAL_GLOBAL: Hessian of sum(g) at Z0, n_comps x n_comps column-major;
+                               QUADFORM_MINUS_C: the matrix M, n_comps x n_comps column-major */
 } dto_constraint_desc;
 
 /* dto_problem_desc.flags */

@@ -52,6 +52,7 @@ const DTO_OBJECTIVE_EXTERNAL_KNOT = Int32(5)
 const DTO_OBJECTIVE_EXTERNAL_GLOBAL = Int32(7)
 const DTO_CONSTRAINT_EXTERNAL = Int32(3)
 const DTO_CONSTRAINT_EXTERNAL_GLOBAL = Int32(4)
+const DTO_CONSTRAINT_QUADFORM_MINUS_C = Int32(5)
 const DTO_COMM_ID_BYTES = Int32(128)
 const DTO_VECTOR_JACOBIAN = Int32(1)
 const DTO_VECTOR_HESSIAN = Int32(2)
@@ -187,6 +188,35 @@ const DEVICE_FAMILIES = IdDict{Any,ModulatedGenerators}()
 device_family!(B, fam::ModulatedGenerators) = (DEVICE_FAMILIES[B] = fam; B)
 
 # ---- the evaluator --------------------------------------------------------------------------------------------------
+"""
+    QuadraticFormKnotConstraint(M, c, names, traj; times=[traj.N], equality=false)
+
+g(v) = [v' M v - c] on v = z_t[names] with a constant symmetric `M`: the built-in device form (DTO_CONSTRAINT_QUADFORM_MINUS_C) of
+`NonlinearKnotPointConstraint(v -> [v' * M * v - c], names, traj; times, equality)`, which as a closure is evaluated on the host
+and uploaded before every callback.  `fidelity_constraint(A, names, traj, F_min)` is the final-fidelity bound of the
+minimum-time stage, `NonlinearKnotPointConstraint(x -> [F_min - F(x)], names, traj; times=[N], equality=false)` with F(v) = ||A v||^2.
+"""
+struct QuadraticFormKnotConstraint <: AbstractNonlinearConstraint
+    M::Matrix{Float64}
+    c::Float64
+    var_names::Vector{Symbol}
+    times::Vector{Int}
+    equality::Bool
+    g_dim::Int
+    dim::Int
+    function QuadraticFormKnotConstraint(M::AbstractMatrix, c::Real, names, traj::NamedTrajectory; times=[traj.N], equality::Bool=false)
+        names = names isa Symbol ? [names] : collect(Symbol, names)
+        n = sum(length(traj.components[nm]) for nm in names)
+        size(M) == (n, n) && M == M' || error("QuadraticFormKnotConstraint: M must be a symmetric $n x $n matrix")
+        new(Matrix{Float64}(M), Float64(c), names, collect(Int, times), equality, 1, length(times))
+    end
+end
+
+function fidelity_constraint(A::AbstractMatrix, names, traj::NamedTrajectory, fidelity::Real; times=[traj.N])
+    M = -Matrix{Float64}(A' * A)
+    QuadraticFormKnotConstraint((M + M') / 2, -fidelity, names, traj; times=times, equality=false)
+end
+
 mutable struct GPUEvaluator <: MOI.AbstractNLPEvaluator
     handle::Ptr{Cvoid}
     trajectory::NamedTrajectory
@@ -345,6 +375,16 @@ function GPUEvaluator(prob::DirectTrajOptProblem; eval_hessian::Bool = true, dev
                                          pointer(gcomps), 0.0, Ptr{Int64}(C_NULL), 0, pointer(jac0), pointer(hess0)))
             push!(ext_constraints, (con, row))
             ext_gcomps[con] = gcomps1
+            row += con.dim
+            continue
+        end
+        if con isa QuadraticFormKnotConstraint   # built into the engine: nothing to evaluate or upload per callback
+            comps = Int32.(vcat([collect(traj.components[n]) for n in con.var_names]...) .- 1)
+            times = Vector{Int64}(con.times)
+            M = vec(con.M)   # column-major n_comps x n_comps, rides in hess0
+            push!(keep, comps, times, M)
+            push!(cdescs, ConstraintDesc(DTO_CONSTRAINT_QUADFORM_MINUS_C, Int32(con.equality), Int32(length(comps)), Int32(1),
+                                         pointer(comps), con.c, pointer(times), length(times), null, pointer(M)))
             row += con.dim
             continue
         end

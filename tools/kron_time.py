@@ -11,12 +11,17 @@ One JSON line per shape.
 
     python tools/kron_time.py                          # levels 8 x 1000 knots (n = 128), 16 x 500 (n = 512)
     python tools/kron_time.py --shapes 32x40 --dense 0 # n = 2048 (b = 64): the structured handle alone
+    python tools/kron_time.py --objective-block 1      # also the Hessian at sigma = 0 and the difference: the objective's share
+    python tools/kron_time.py --minimum-time 1         # synthetic.unitary_minimum_time_problem instead: the built-in quadratic-form
+                                                       # fidelity bound (device-resident and through host pointers) against the same
+                                                       # bound as a host-merged closure (host pointers: its blocks come from the host)
 """
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -41,7 +46,33 @@ def timed(fn, reps):
     return statistics.median(one_call_ms(fn) for _ in range(reps))
 
 
-def measure_handle(prob, flagged, reps, sigma=0.7):
+def host_timed(fn, reps):
+    """Median wall-clock milliseconds of a blocking host-pointer callback (host evaluation of closures and copies included)."""
+    fn(); fn()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        out.append(1e3 * (time.perf_counter() - t0))
+    return statistics.median(out)
+
+
+def measure_host(prob, flagged, reps, sigma=0.7):
+    """eval_constraint, Jacobian and Hessian through host pointers (what a closure-based term forces)."""
+    import numpy as np
+    ev = dto_amd.Evaluator(prob, eval_hessian=True, block_generators=flagged)
+    try:
+        Z = prob.trajectory.vec()
+        mu = np.random.default_rng(1).standard_normal(ev.n_constraints)
+        g, J, H = np.empty(ev.n_constraints), np.empty(ev.n_jacobian_entries), np.empty(ev.n_hessian_entries)
+        return {"constraint_ms": round(host_timed(lambda: ev.eval_constraint(g, Z), reps), 4),
+                "jacobian_ms": round(host_timed(lambda: ev.eval_constraint_jacobian(J, Z), reps), 4),
+                "hessian_ms": round(host_timed(lambda: ev.eval_hessian_lagrangian(H, Z, sigma, mu), reps), 4)}
+    finally:
+        ev.close()
+
+
+def measure_handle(prob, flagged, reps, sigma=0.7, objective_block=False):
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev).cuda_stream
     ev = dto_amd.Evaluator(prob, eval_hessian=True, block_generators=flagged)
@@ -69,6 +100,10 @@ def measure_handle(prob, flagged, reps, sigma=0.7):
         hes = lambda: ev.eval_hessian_dev(Z.data_ptr(), sigma, mu.data_ptr(), H.data_ptr(), st)
         out["hessian_ms"] = round(timed(hes, reps), 4)
         out["hessian_slab_GB"] = round(8e-9 * ev.n_hessian_entries, 3)
+        if objective_block:  # the objective's share of the call: the same Hessian without it
+            hes0 = lambda: ev.eval_hessian_dev(Z.data_ptr(), 0.0, mu.data_ptr(), H.data_ptr(), st)
+            out["hessian_sigma0_ms"] = round(timed(hes0, reps), 4)
+            out["objective_block_ms"] = round(out["hessian_ms"] - out["hessian_sigma0_ms"], 4)
         if flagged:
             ev.profile_enable(True); ev.profile_reset(); hes(); torch.cuda.synchronize()
             ms, _, fl = ev.profile_get("expmv_adjoint")
@@ -89,14 +124,27 @@ def main():
     ap.add_argument("--dense", type=int, default=1, help="0: time the structured handle alone")
     ap.add_argument("--sigma", type=float, default=0.7, help="objective weight of the Hessian (0: the constraint side alone -- the\n"
                     "terminal infidelity's n x n block is assembled by one launch of its own, the same on both handles)")
+    ap.add_argument("--objective-block", type=int, default=0, help="1: also time the Hessian at sigma = 0 and report the difference")
+    ap.add_argument("--minimum-time", type=int, default=0, help="1: time synthetic.unitary_minimum_time_problem, built-in bound against\n"
+                    "host-merged closure")
     a = ap.parse_args()
     for s in a.shapes.split(","):
         levels, N = (int(x) for x in s.lower().split("x"))
-        prob = dto_amd.host.synthetic.unitary_problem(levels, a.drives, N, seed=42)
         out = {"levels": levels, "n": 2 * levels * levels, "knots": N, "drives": a.drives, "sigma": a.sigma}
-        out["structured"] = measure_handle(prob, True, a.reps, a.sigma)
+        if a.minimum_time:
+            built_in = dto_amd.host.synthetic.unitary_minimum_time_problem(levels, a.drives, N, seed=42)
+            closure = dto_amd.host.synthetic.unitary_minimum_time_problem(levels, a.drives, N, seed=42, closure=True)
+            out["problem"] = "unitary_minimum_time_problem"
+            for name, flagged in (("structured", True), ("dense", False)) if a.dense else (("structured", True),):
+                out[name] = {"built_in_dev": measure_handle(built_in, flagged, a.reps, a.sigma),
+                             "built_in_host": measure_host(built_in, flagged, a.reps, a.sigma),
+                             "closure_host": measure_host(closure, flagged, a.reps, a.sigma)}
+            print(json.dumps(out), flush=True)
+            continue
+        prob = dto_amd.host.synthetic.unitary_problem(levels, a.drives, N, seed=42)
+        out["structured"] = measure_handle(prob, True, a.reps, a.sigma, a.objective_block)
         if a.dense:
-            out["dense"] = measure_handle(prob, False, a.reps, a.sigma)
+            out["dense"] = measure_handle(prob, False, a.reps, a.sigma, a.objective_block)
             out["speedup"] = {k: round(out["dense"][k + "_ms"] / out["structured"][k + "_ms"], 2) for k in ("constraint", "jacobian", "hessian")}
         print(json.dumps(out), flush=True)
 
