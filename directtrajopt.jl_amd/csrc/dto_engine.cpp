@@ -115,6 +115,14 @@ struct BilHost {
     KKron kk{};
     double* d_kron_scratch = nullptr;
     size_t kron_stride = 0;
+    // DTO_FLAG_SHARED_GENERATORS: the group of integrators with these generators and controls (indices into dto_handle::bil; the
+    // leader is the first member in list order; -1 / 1 without a partner).  `share_active`: the group shares the leader's
+    // propagator chain -- a follower runs none, its -E_k blocks are copies of the leader's (dto_share.hip).  `share_followers`
+    // (leader of an active group only): the other members in list order.  `list_pos`: position in the integrator list.
+    int share_leader = -1, share_size = 1, list_pos = 0;
+    bool share_active = false;
+    std::vector<int> share_followers;
+    bool follows() const { return share_active && share_followers.empty(); }
 };
 
 struct ConHost {
@@ -372,7 +380,7 @@ struct ProfScope {
 };
 // (for the bandwidth-bound categories from CAT_ZERO on, `flops` carries the launch's algorithmic BYTES)
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12 };
 // the form a generator sweep took (dto_profile_get "sweep_gs" .. "sweep_step"): one count per run_sweep call, not per launch
 enum { SWEEP_GS = 0, SWEEP_FUSED = 1, SWEEP_S64 = 2, SWEEP_CLUSTER = 3, SWEEP_STEP = 4 };
 inline void count_sweep_form(dto_handle* h, int form) {
@@ -405,6 +413,51 @@ int find_replicas(const double* G, int n, int m1) {
         if (ok) return r;
     }
     return 1;
+}
+
+// Does the fused one-workgroup-per-interval path (dto_small.hip) serve a bilinear integrator of n states and m drives?  n <= 16 with
+// one wavefront, 17..32 with four, while the interval's matrices, generators and sweep columns fit the CU's LDS.  The one place
+// that decides it: dto_create and the grouping below ask here.
+bool small_path_serves(int flags, int eval_hessian, int n, int m) {
+    const int Tf = eval_hessian ? 1 + m + m * (m + 1) / 2 : 1 + m;
+    return (flags & DTO_FLAG_GENERAL_PATH_ONLY) == 0 && n <= 32 && Tf <= MAX_TYPES && small_lds_bytes(n, m, Tf, 1 + m) <= 150 * 1024;
+}
+
+// DTO_FLAG_SHARED_GENERATORS: partition the bilinear integrators into groups with equal x_dim, control component and generators
+// (compared with ==, as find_replicas does).  Host arithmetic on the descriptor: also on structure-only handles.
+void find_share_groups(dto_handle* h, const dto_problem_desc* d) {
+    for (int i = 0; i < d->n_integrators; ++i)
+        if (h->integ_kind[i] == DTO_INTEGRATOR_BILINEAR) h->bil[h->integ_index[i]].list_pos = i;
+    if (!(d->flags & DTO_FLAG_SHARED_GENERATORS)) return;
+    // the path an integrator takes follows from x_dim, m and the flags -- equal for the members of a group -- except the structured
+    // path, which also asks where state, controls and timestep lie: an integrator it serves is grouped with its like only
+    for (int i = 0; i < d->n_integrators; ++i) {
+        if (h->integ_kind[i] != DTO_INTEGRATOR_BILINEAR) continue;
+        const int bi = h->integ_index[i];
+        if (h->bil[bi].share_leader >= 0) continue;  // a member of an earlier group
+        const dto_integrator_desc& a = d->integrators[i];
+        const size_t len = (size_t)(a.u_dim + 1) * a.x_dim * a.x_dim;
+        std::vector<int> members{bi};
+        for (int j = i + 1; j < d->n_integrators; ++j) {
+            if (h->integ_kind[j] != DTO_INTEGRATOR_BILINEAR) continue;
+            const int bj = h->integ_index[j];
+            const dto_integrator_desc& c = d->integrators[j];
+            if (h->bil[bj].share_leader >= 0 || c.x_dim != a.x_dim || c.u_dim != a.u_dim || (a.u_dim > 0 && c.u_off != a.u_off) ||
+                h->bil[bj].kron != h->bil[bi].kron)
+                continue;
+            bool eq = true;
+            for (size_t e = 0; e < len && eq; ++e) eq = a.G[e] == c.G[e];
+            if (eq) members.push_back(bj);
+        }
+        if (members.size() < 2) continue;
+        const bool active = !h->bil[bi].kron && !small_path_serves(d->flags, d->eval_hessian, a.x_dim, a.u_dim) && members.size() - 1 <= (size_t)SHARE_MAX_FOLLOWERS;
+        for (int mb : members) {
+            h->bil[mb].share_leader = bi;
+            h->bil[mb].share_size = (int)members.size();
+            h->bil[mb].share_active = active;
+        }
+        if (active) h->bil[bi].share_followers.assign(members.begin() + 1, members.end());
+    }
 }
 
 // number of integrator rows touching a column of knot kn (0-based): D per adjacent interval
@@ -1395,6 +1448,18 @@ void do_constraint(dto_handle* h, const double* dZ, double* dg, hipStream_t st) 
     }
 }
 
+// DTO_FLAG_SHARED_GENERATORS: -E_k of intervals int0 .. int0 + nb - 1, final in the leader's positions behind what `st` holds, to
+// the positions of the group's other members
+void share_blocks(dto_handle* h, BilHost* const* members, int n_members, int64_t int0, int nb, double* dvals, hipStream_t st) {
+    KShare sh{};
+    sh.n = members[0]->k.n;
+    sh.nf = n_members - 1;
+    for (int i = 0; i < n_members; ++i) { sh.x_off[i] = members[i]->k.x_off; sh.pre[i] = members[i]->k.pre; }
+    // priced by the bytes it writes: one block per follower and interval (it reads one more block per interval)
+    ProfScope ps(h, st, CAT_SHARE, 8.0 * sh.n * (double)sh.n * nb * sh.nf);
+    launch_share_E(st, h->P, sh, int0, nb, dvals);
+}
+
 void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st) {
     // fill!(∂, 0), evaluator.jl:497 -- the -E_k block of a lone bilinear integrator is skipped: the chain
     // overwrites all of it
@@ -1416,7 +1481,16 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
             continue;
         }
         Bounds bd{0, 0};
-        if (h->P.n_int > 0) {
+        // DTO_FLAG_SHARED_GENERATORS: the leader of an active group runs the one chain; its followers' sweeps are enqueued where
+        // its own is -- planned from the leader's bounds and the leader's chain readback, which are functions of the generators, u
+        // and dt alone -- and k_share_E copies every finished chunk of -E_k blocks to the followers' positions on the chain's
+        // stream.  A follower has been swept and filled by the time the loop reaches it (the leader comes first in list order,
+        // and the join below covers the whole group): it only writes its tangent columns.
+        // (with the flag clear: the integrator alone, nothing allocated, no hook installed)
+        BilHost* members[1 + SHARE_MAX_FOLLOWERS] = {&b};
+        int n_members = 1;
+        for (int f : b.share_followers) members[n_members++] = &h->bil[f];
+        if (h->P.n_int > 0 && !b.follows()) {
             // generator-norm bounds: enqueued here, read inside the chain's own readback point (no stream sync of their
             // own); the squaring cap they used to provide is the constant 60, a NaN iterate gets one squaring
             enqueue_bounds(h, b, dZ, st);
@@ -1432,50 +1506,54 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                 HIP_CHECK(hipEventRecord(h->ev_fork, st));  // dZ (and the zero-filled slab) are ready here
                 HIP_CHECK(hipStreamWaitEvent(ss, h->ev_fork, 0));
             }
-            auto sweep_with = [&](SweepPlan plan, const int32_t* plan_dev = nullptr) {
-                SweepTypes ty = make_types(b.k.m, false);
+            auto sweep_one = [&](BilHost& mb, SweepPlan plan, const int32_t* plan_dev) {
+                SweepTypes ty = make_types(mb.k.m, false);
                 // the p column of this very point is stored (eval_constraint or a Hessian came first)
-                const bool have_p = same && b.p_terms && plan.q == 1;
+                const bool have_p = same && mb.p_terms && plan.q == 1;
                 // ... but where the whole sweep runs as ONE persistent launch beside the chain, sweeping all columns again is
                 // cheaper than the step-per-launch form the frozen variant needs (256 x 2000: 10.9 against 12.0 ms per Jacobian);
                 // the stored p terms stay valid for a Hessian at this point either way (a sweep without store leaves them alone)
                 // (asked for the sweep without store beside the chain: what sweep_fused_plan accepts for a sweep alone it accepts there too
                 // -- it only tries the eight-wavefront search first, the 64-state instance changes its interval count, not its answer)
                 const bool beside_chain = overlap && !h->deterministic;
-                const bool one_launch = choose_sweep(h, b, b.fw, ty, plan, /*store=*/false, beside_chain).form != SWEEP_STEP;
+                const bool one_launch = choose_sweep(h, mb, mb.fw, ty, plan, /*store=*/false, beside_chain).form != SWEEP_STEP;
                 if (have_p && !one_launch) {
                     // sweep the tangent columns alone, their inhomogeneous terms read the stored p terms
-                    SweepBuf wf = b.fw;
-                    wf.frozen = b.fw.Zt;
-                    wf.frozen_total = b.p_steps + 1;
+                    SweepBuf wf = mb.fw;
+                    wf.frozen = mb.fw.Zt;
+                    wf.frozen_total = mb.p_steps + 1;
                     wf.first_type = 1;
-                    run_sweep(h, b, wf, ty, dZ, nullptr, plan, ss);
-                    launch_apply_Gu(ss, b.k, b.fw, 0, b.fw.S, b.fw.GY);
-                    b.cache_kind = 2;
+                    run_sweep(h, mb, wf, ty, dZ, nullptr, plan, ss);
+                    launch_apply_Gu(ss, mb.k, mb.fw, 0, mb.fw.S, mb.fw.GY);
+                    mb.cache_kind = 2;
                     return;
                 }
                 // with reuse on and a Hessian to follow, keep every Taylor term so that the Hessian can skip its forward sweep
                 // (not when the p terms are there already: they are all the Hessian's pairing takes from the forward sweep)
-                const bool keep = h->reuse && b.pairing && plan.q == 1 && plan.d_ub + 1 <= b.fw.dcap && !have_p;
+                const bool keep = h->reuse && mb.pairing && plan.q == 1 && plan.d_ub + 1 <= mb.fw.dcap && !have_p;
                 // (option "deterministic": the sweep keeps the shape it has when it runs alone, so the bits do not depend on
                 // overlap_sweep; next to the chain the 256-state sweep otherwise groups its intervals by twelve instead of nine)
                 // (a short shard's sweep in the generator-stationary form wants the chip to itself for a fraction of a millisecond: it
                 // follows the chain on the call's stream instead of sharing the chip with it)
-                SweepChoice choice = choose_sweep(h, b, b.fw, ty, plan, keep, /*shared_chip=*/false);
+                SweepChoice choice = choose_sweep(h, mb, mb.fw, ty, plan, keep, /*shared_chip=*/false);
                 const bool gs_alone = choice.form == SWEEP_GS;
                 hipStream_t sw = gs_alone ? st : ss;
-                if (beside_chain && !gs_alone) choice = choose_sweep(h, b, b.fw, ty, plan, keep, /*shared_chip=*/true);
-                const int steps = run_sweep(h, b, b.fw, ty, dZ, nullptr, plan, sw, SweepArgs().as_chosen(choice).planned_on_device(plan_dev));
-                launch_apply_Gu(sw, b.k, b.fw, 0, b.fw.S, b.fw.GY);
-                b.cache_kind = h->reuse ? (keep ? 3 : 2) : 0;
-                b.cache_steps = steps;
-                if (keep || plan.q > 1) b.p_terms = false;  // the store now holds every column type / the scale factors changed
+                if (beside_chain && !gs_alone) choice = choose_sweep(h, mb, mb.fw, ty, plan, keep, /*shared_chip=*/true);
+                const int steps = run_sweep(h, mb, mb.fw, ty, dZ, nullptr, plan, sw, SweepArgs().as_chosen(choice).planned_on_device(plan_dev));
+                launch_apply_Gu(sw, mb.k, mb.fw, 0, mb.fw.S, mb.fw.GY);
+                mb.cache_kind = h->reuse ? (keep ? 3 : 2) : 0;
+                mb.cache_steps = steps;
+                if (keep || plan.q > 1) mb.p_terms = false;  // the store now holds every column type / the scale factors changed
+            };
+            auto sweep_with = [&](SweepPlan plan, const int32_t* plan_dev = nullptr) {
+                for (int i = 0; i < n_members; ++i) sweep_one(*members[i], plan, plan_dev);
             };
             // One-launch chain (33..64 states): the chain's exact norms arrive only when ALL of it is done, so a sweep planned from
             // them would run behind it.  Where the cheap bound already gives a single round, the sweep is planned from that bound
             // (as eval_constraint and the Hessian do) and enqueued FIRST, on the second stream: its workgroups and the chain's
             // share the CUs (64 x 1000: 0.42 -> 0.3x ms per Jacobian).
-            bool swept = same && b.cache_kind >= 2;  // the tangent sums of this very point are still in b.fw
+            bool swept = same;  // the tangent sums of this very point are still in b.fw (of every member)
+            for (int i = 0; i < n_members; ++i) swept = swept && members[i]->cache_kind >= 2;
             bool zeroed = false;
             static const int early_on = tune_int("DTO_SWEEP_EARLY", 1);  // A/B runs (TUNING builds)
             if (!swept && early_on && chain64_applies(h, b) && s64_plans_itself(h, b, b.fw, make_types(b.k.m, false))) {
@@ -1509,13 +1587,30 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                 }
             }
             const bool nothing_waits = swept && chain64_applies(h, b);
+            // the copy follows each chunk of the chain (run_chain's hook for a finished chunk; the host-pointer Jacobian's own hook,
+            // which ships a lone integrator's blocks early, comes after it)
+            struct ChunkHook {
+                dto_handle* h;
+                bool installed = false;
+                std::function<void(int64_t, int)> outer;
+                ~ChunkHook() { if (installed) h->on_chain_chunk = std::move(outer); }
+            } chunk_hook{h};
+            if (n_members > 1) {
+                chunk_hook.outer = std::move(h->on_chain_chunk);
+                chunk_hook.installed = true;
+                h->on_chain_chunk = [&](int64_t c0, int nb) {
+                    share_blocks(h, members, n_members, h->P.kn_lo + c0, nb, dvals, st);
+                    if (chunk_hook.outer) chunk_hook.outer(c0, nb);
+                };
+            }
             run_chain(h, b, dZ, dvals, INFINITY, st, [&](double d2) {
                 bd = Bounds{h->h_pinned[0], h->h_pinned[1]};  // copied before the chain's readback event
                 // ||A^t|| <= ||A^2||^floor(t/2) ||A||^(t mod 2): the exact d2 of the chain is the sharper
                 // (and still rigorous) growth rate for the sweep's step budget
                 if (swept) return;
                 const SweepPlan from_chain = plan_hump(b, d2 == d2 ? std::min(bd.beta, d2) : d2);
-                if (h->reuse) { b.plan_q = from_chain.q; b.plan_dub = from_chain.d_ub; }  // a Hessian at this very point need not buy the norms again
+                if (h->reuse)   // a Hessian at this very point need not buy the norms again
+                    for (int i = 0; i < n_members; ++i) { members[i]->plan_q = from_chain.q; members[i]->plan_dub = from_chain.d_ub; }
                 sweep_with(from_chain);
             }, [&] {
                 if (lone && !keep_constants && !zeroed) {
@@ -2396,11 +2491,8 @@ int dto_create(const dto_problem_desc* d, dto_handle** out) {
                 } else if (!sonly) {
                     b.k.G = own(h, dupload(G));
                     b.k.GT = own(h, dupload(GT));
-                    const bool small_on = (d->flags & DTO_FLAG_GENERAL_PATH_ONLY) == 0;
-                    // fused one-workgroup-per-interval path: n <= 16 with one wavefront, 17..32 with four, while the
-                    // interval's matrices, generators and sweep columns fit the CU's LDS
                     const int mm_ = s.u_dim, Tf = d->eval_hessian ? 1 + mm_ + mm_ * (mm_ + 1) / 2 : 1 + mm_;
-                    if (small_on && n <= 32 && Tf <= MAX_TYPES && small_lds_bytes(n, mm_, Tf, 1 + mm_) <= 150 * 1024) {
+                    if (small_path_serves(d->flags, d->eval_hessian, n, mm_)) {
                         b.small = true;
                         // worst-case dynamic LDS of this handle's fused kernel, opted into on THIS device
                         HIP_CHECK(small_prepare(small_lds_bytes(n, mm_, Tf, 1 + mm_)));
@@ -2458,6 +2550,7 @@ int dto_create(const dto_problem_desc* d, dto_handle** out) {
         h->D = pre;
         h->n_dyn = row;
         h->n_ext_int = (int)h->ext_int.size();
+        find_share_groups(h, d);
         if (h->integ_kind.size() > 8) throw HipError{"at most 8 integrators"};
 
         // nonlinear knot constraints: rows follow the dynamics (evaluator.jl:219-223)
@@ -3004,6 +3097,7 @@ int dto_interval_costs(const dto_handle* h, const double* Z, int64_t first, int6
             const double products = std::min(2.0 + sq2, 3.0 + sq3);
             const SweepPlan sp = plan_sweep(alpha);
             const double sweep = 2.0 * np * np * m1 * m1 * (double)sp.d_ub * sp.q;
+            if (b.follows()) { cost[i] += sweep; continue; }  // its propagators are copies of the leader's: no chain of its own
             cost[i] += b.small ? 2.0 * b.k.n * (double)b.k.n * b.k.n * (6.0 + sq2) : gemm * products + basis + sweep;
         }
     }
@@ -3021,6 +3115,19 @@ int dto_integrator_blocks(const dto_handle* h, int32_t integrator, int32_t* bloc
     }
     if (block_dim) *block_dim = bd;
     if (reps) *reps = r;
+    if (active) *active = on;
+    return 0;
+}
+
+int dto_integrator_share(const dto_handle* h, int32_t integrator, int32_t* leader, int32_t* group_size, int32_t* active) {
+    if (!h || integrator < 0 || integrator >= (int32_t)h->integ_kind.size()) return 1;
+    int lead = integrator, size = 1, on = 0;
+    if (h->integ_kind[integrator] == DTO_INTEGRATOR_BILINEAR) {
+        const BilHost& b = h->bil[h->integ_index[integrator]];
+        if (b.share_leader >= 0) { lead = h->bil[b.share_leader].list_pos; size = b.share_size; on = b.share_active ? 1 : 0; }
+    }
+    if (leader) *leader = lead;
+    if (group_size) *group_size = size;
     if (active) *active = on;
     return 0;
 }
@@ -3574,6 +3681,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "expmv")) cat = CAT_SWEEP;
         else if (!strcmp(name, "expmv_adjoint")) cat = CAT_SWEEP_ADJOINT;
         else if (!strcmp(name, "hess_product")) cat = CAT_HESS_PRODUCT;
+        else if (!strcmp(name, "share")) cat = CAT_SHARE;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -3603,7 +3711,8 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));
-            tot += t; fl += r.flops; ++n;
+            tot += t; ++n;
+            if (cat == CAT_SHARE || r.cat != CAT_SHARE) fl += r.flops;  // (priced in bytes: not part of the sum of "all")
         }
         if (ms) *ms = tot;
         if (launches) *launches = n;

@@ -424,6 +424,16 @@ void launch_hess_derivative(hipStream_t st, const KProb& P, const KDer& Dv, cons
 void launch_hess_bilinear(hipStream_t st, const KProb& P, const KBil& B, const SweepBuf& fw, const SweepBuf& ad,
                           const double* dmu, double* H, int with_uu);
 
+// DTO_FLAG_SHARED_GENERATORS (dto_share.hip): the -E_k blocks of intervals int0 .. int0 + nb - 1 (global, 0-based), n x n each, are
+// copied from the leader's positions in the Jacobian slab ([0]) to the followers' ([1 .. nf]); x_off / pre as in KBil
+constexpr int SHARE_MAX_FOLLOWERS = 15;
+struct KShare {
+    int32_t n, nf;
+    int32_t x_off[1 + SHARE_MAX_FOLLOWERS];
+    int32_t pre[1 + SHARE_MAX_FOLLOWERS];
+};
+void launch_share_E(hipStream_t st, const KProb& P, const KShare& S, int64_t int0, int nb, double* vals);
+
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);
 

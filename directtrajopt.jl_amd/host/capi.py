@@ -11,6 +11,7 @@ c_int32_p = C.POINTER(C.c_int32)
 DTO_ABI_VERSION = 8
 FLAG_GENERAL_PATH_ONLY = 1
 FLAG_BLOCK_GENERATORS = 2
+FLAG_SHARED_GENERATORS = 4
 INTEGRATOR_BILINEAR, INTEGRATOR_DERIVATIVE, INTEGRATOR_EXTERNAL, INTEGRATOR_TIME_DEPENDENT_BILINEAR = 1, 2, 3, 4
 OBJECTIVE_QUADRATIC, OBJECTIVE_LINEAR, OBJECTIVE_MINTIME, OBJECTIVE_KNOT_SQDIST, OBJECTIVE_EXTERNAL_KNOT, OBJECTIVE_KNOT_LOWRANK, OBJECTIVE_EXTERNAL_GLOBAL = 1, 2, 3, 4, 5, 6, 7
 CONSTRAINT_NORM, CONSTRAINT_SQNORM, CONSTRAINT_EXTERNAL, CONSTRAINT_EXTERNAL_GLOBAL, CONSTRAINT_QUADFORM = 1, 2, 3, 4, 5
@@ -81,6 +82,7 @@ SYMBOLS = {
     "dto_get_shard_info": (C.c_int, [H, C.POINTER(ShardInfo)]),
     "dto_shard_rows": (C.c_int, [H, c_int64_p, c_int64_p]),
     "dto_integrator_blocks": (C.c_int, [H, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
+    "dto_integrator_share": (C.c_int, [H, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
     "dto_interval_costs": (C.c_int, [H, c_double_p, C.c_int64, C.c_int64, c_double_p]),
     "dto_jacobian_structure": (C.c_int, [H, C.c_int64, C.c_int64, c_int64_p, c_int64_p]),
     "dto_hessian_structure": (C.c_int, [H, C.c_int64, C.c_int64, c_int64_p, c_int64_p]),

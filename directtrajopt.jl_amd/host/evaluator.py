@@ -68,7 +68,7 @@ class Evaluator:
     default_options = {}
 
     def __init__(self, prob, eval_hessian=True, device=0, k_lo=0, k_hi=0, verbose=False, general_path_only=False,
-                 block_generators=False):
+                 block_generators=False, shared_generators=False):
         self._lib = load_library()
         self._h = capi.H()
         traj = prob.trajectory
@@ -204,7 +204,8 @@ class Evaluator:
         desc = capi.ProblemDesc(capi.DTO_ABI_VERSION, device, traj.N, traj.dim, traj.global_dim,
                                 traj.components[traj.timestep][0], int(eval_hessian), len(prob.integrators),
                                 len(terms), len(nl), (capi.FLAG_GENERAL_PATH_ONLY if general_path_only else 0) |
-                                (capi.FLAG_BLOCK_GENERATORS if block_generators else 0), integ, objs, cons,
+                                (capi.FLAG_BLOCK_GENERATORS if block_generators else 0) |
+                                (capi.FLAG_SHARED_GENERATORS if shared_generators else 0), integ, objs, cons,
                                 _dp(Z0), k_lo, k_hi)
         if self._lib.dto_create(C.byref(desc), C.byref(self._h)) != 0:
             raise EngineError(self._lib.dto_last_error(None).decode())
@@ -246,6 +247,14 @@ class Evaluator:
         b, r, a = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._lib.dto_integrator_blocks(self._h, int(i), C.byref(b), C.byref(r), C.byref(a)))
         return b.value, r.value, a.value
+
+    def integrator_share(self, i):
+        """(leader, group_size, active) of integrator i (0-based): the group of bilinear integrators with the same generators and
+        controls found at create with ``shared_generators=True``, its first member in list order, and whether the group shares
+        one propagator chain in eval_constraint_jacobian; (i, 1, 0) otherwise."""
+        l, n, a = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self._lib.dto_integrator_share(self._h, int(i), C.byref(l), C.byref(n), C.byref(a)))
+        return l.value, n.value, a.value
 
     # ---- MOI surface (host vectors)
     def initialize(self, features=None):  # MOI.initialize, evaluator.jl:291

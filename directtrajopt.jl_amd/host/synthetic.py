@@ -115,3 +115,44 @@ def unitary_minimum_time_problem(levels, drives, N, fidelity=0.99, seed=42, D=1.
         bound = NonlinearKnotPointConstraint(lambda v, p: np.array([v @ (M @ v) - c]), "U", traj, equality=False, times=[N],
                                              jac=lambda v, p: (2.0 * (M @ v))[None, :], hess=lambda v, p, mu: 2.0 * mu[0] * M)
     return DirectTrajOptProblem(traj, J, base.integrators, constraints=list(base.constraints) + [bound])
+
+
+def multi_ket_problem(n, kets, drives, N, seed=42, dt=0.1, u_bound=None, extra_ket=False, derivative_between=False, scale=None):
+    """A multi-state transfer problem: ``kets`` states driven by ONE system.  Components psi1..psiP (n each), u (drives), du, dt;
+    one skew-symmetric drift and ``drives`` skew-symmetric drive generators (a real isomorphic Schroedinger generator, scaled so
+    that ||dt G(u)|| stays of order one at any n) shared by P BilinearIntegrators -- what ``Evaluator(..., shared_generators=True)``
+    groups -- plus DerivativeIntegrator(u, du); QuadraticRegularizers on u and du and a terminal ||psi_i - goal_i||^2 per ket.
+    ``u_bound``: the knot constraint ||u||^2 - u_bound <= 0 at the interior knots (its entries interleave with the integrators'
+    in the u columns).  ``scale``: the generators' entries are N(0, scale^2) before antisymmetrisation (default 1 / sqrt(n); 1.0
+    gives the norms of ``make_scaled_problem``, whose propagators need several squarings).  ``extra_ket``: one more ket "phi" with generators of its own.  ``derivative_between``: the derivative
+    integrator sits between the first ket's integrator and the others in the list instead of at its end."""
+    rng = np.random.Generator(np.random.Philox(seed))
+    def generators():
+        M = rng.standard_normal((drives + 1, n, n))
+        return (M - M.transpose(0, 2, 1)) * ((1.0 / np.sqrt(n) if scale is None else float(scale)) / np.sqrt(2.0))
+    G = generators()
+    u = 0.1 * rng.standard_normal((drives, N))   # (drawn before the kets: generators and controls do not depend on their number)
+    du = rng.standard_normal((drives, N))
+    comps = {}
+    for i in range(kets):
+        v = rng.standard_normal((n, N))
+        comps[f"psi{i + 1}"] = v / np.linalg.norm(v, axis=0)
+    if extra_ket:
+        v = rng.standard_normal((n, N))
+        comps["phi"] = v / np.linalg.norm(v, axis=0)
+    comps["u"], comps["du"] = u, du
+    comps["dt"] = np.full((1, N), float(dt))
+    traj = NamedTrajectory(comps, timestep="dt")
+    kets_int = [BilinearIntegrator(G, f"psi{i + 1}", "u", traj) for i in range(kets)]
+    if extra_ket:
+        kets_int.append(BilinearIntegrator(generators(), "phi", "u", traj))
+    der = DerivativeIntegrator("u", "du", traj)
+    integrators = kets_int[:1] + [der] + kets_int[1:] if derivative_between else kets_int + [der]
+    J = QuadraticRegularizer("u", traj, 1e-2) + QuadraticRegularizer("du", traj, 1e-2)
+    for name in [k for k in comps if k.startswith("psi") or k == "phi"]:
+        goal = rng.standard_normal(n)
+        J = J + KnotPointObjective("sqdist", name, traj, times=[N], Qs=[10.0], params=(goal / np.linalg.norm(goal))[None, :])
+    cons = []
+    if u_bound is not None:
+        cons.append(NonlinearKnotPointConstraint("sqnorm", "u", traj, c=float(u_bound), equality=False, times=range(2, N)))
+    return DirectTrajOptProblem(traj, J, integrators, constraints=cons)

@@ -170,6 +170,19 @@ typedef struct dto_constraint_desc {
                                         overlap_sweep) are accepted and have no effect on a structured integrator; its J w and
                                         J' w products go through the value slab */
 
+#define DTO_FLAG_SHARED_GENERATORS 4  /* look for DTO_INTEGRATOR_BILINEAR integrators that are driven by the same system: equal x_dim, the same
+                                        control component (u_off, u_dim) and all m+1 generators equal entry by entry (==, no tolerance) --
+                                        the kets of a multi-state transfer or ensemble problem, each with its own
+                                        BilinearIntegrator(G, :psi_i, :u).  Their propagators exp(dt_k G(u_k)) are the same matrices: the
+                                        first member in list order (the LEADER) runs the propagator chain of eval_constraint_jacobian, the
+                                        others (FOLLOWERS) receive copies of its -E_k blocks (csrc/dto_share.hip) and run only their own
+                                        tangent sweep, planned from the leader's norms.  A group is ACTIVE (shares) when it has two members
+                                        or more and its members take the dense chain (33 states and up, or DTO_FLAG_GENERAL_PATH_ONLY);
+                                        integrators on the small path or the structured path are reported as grouped but keep their
+                                        evaluation.  Same structure, same value layout, the followers' blocks bit-identical to the leader's
+                                        (dto_integrator_share tells).  eval_constraint, the Hessian and the matrix-free J w / J' w form
+                                        no propagator and are not changed */
+
 typedef struct dto_problem_desc {
     int32_t abi_version;    /* DTO_ABI_VERSION */
     int32_t device;         /* HIP device ordinal */
@@ -225,6 +238,11 @@ int dto_shard_rows(const dto_handle* h, int64_t* start1, int64_t* len);
 /* finest replicated-block structure found in integrator i (0-based) and whether the structured path serves it;
    (x_dim, 1, 0) when the flag is clear, the kind is not bilinear, or no structure exists */
 int dto_integrator_blocks(const dto_handle* h, int32_t integrator, int32_t* block_dim, int32_t* reps, int32_t* active);
+
+/* the group of integrator i (0-based) under DTO_FLAG_SHARED_GENERATORS: its leader (0-based position in the integrator list), the
+   number of members, and whether the group shares one propagator chain; (i, 1, 0) when the flag is clear, the kind is not
+   bilinear, or the integrator has no partner */
+int dto_integrator_share(const dto_handle* h, int32_t integrator, int32_t* leader, int32_t* group_size, int32_t* active);
 
 /* Cost model of one eval_constraint_jacobian for intervals first .. first+count-1 (0-based, GLOBAL numbering; Z is the whole NLP
  * vector, host memory): flops from the growth bound of every interval's A_k = dt_k G(u_k) -- squarings of the propagator chain,
@@ -419,8 +437,10 @@ int dto_profile_reset(dto_handle* h);
  * sweep: its dominant kernel), "all"; "basis_multi" / "basis_k" (the two generator-subspace launches apart: A^2..A^4, and the
  * factor K), and the bandwidth-bound assembly kernels "zero_fill" (the Jacobian's / Hessian's fill!(., 0)), "build_A" (A_k from the
  * generators), "assembly" (the writers of the bilinear Jacobian's tangent columns), "hess_product" (the Hessian-vector products'
- * gather into their compact copy and the product launches; the Hessian they assemble counts under its own names).
- * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names the
+ * gather into their compact copy and the product launches; the Hessian they assemble counts under its own names), "share" (the
+ * copies of the leader's -E_k blocks to the followers of a DTO_FLAG_SHARED_GENERATORS group; its bytes are the bytes WRITTEN, one
+ * block per follower and interval -- each launch reads a further block per interval -- and stay out of the third output of "all").
+ * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the
  * third output is the launches' algorithmic BYTES (what they must read and write), not FLOPs.
  * "hess_product_setup" returns the host milliseconds of the products' index build (once per handle), 0 launches, and the device
  * bytes of their private slab and index.

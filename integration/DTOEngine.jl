@@ -41,6 +41,7 @@ const lib = get(ENV, "DTO_ENGINE_LIB", "libdto_engine.so")
 const DTO_ABI_VERSION = Int32(8)
 
 const DTO_FLAG_BLOCK_GENERATORS = Int32(2)
+const DTO_FLAG_SHARED_GENERATORS = Int32(4)
 const DTO_INTEGRATOR_BILINEAR = Int32(1)
 const DTO_INTEGRATOR_DERIVATIVE = Int32(2)
 const DTO_INTEGRATOR_EXTERNAL = Int32(3)
@@ -273,7 +274,7 @@ end
 first0(traj, name) = Int32(first(traj.components[name]) - 1)   # 0-based offset of a component inside a knot
 
 function GPUEvaluator(prob::DirectTrajOptProblem; eval_hessian::Bool = true, device::Integer = 0, k_lo::Integer = 0, k_hi::Integer = 0,
-                      block_generators::Bool = false)
+                      block_generators::Bool = false, shared_generators::Bool = false)
     traj = prob.trajectory
     traj.timestep isa Symbol || error("DTOEngine: the engine needs a timestep component (bilinear_integrator.jl:123)")
     keep = Any[]   # everything the descriptors point at, alive until dto_create returns
@@ -407,7 +408,7 @@ function GPUEvaluator(prob::DirectTrajOptProblem; eval_hessian::Bool = true, dev
     GC.@preserve keep idescs odescs cdescs Z0 begin
         desc = Ref(ProblemDesc(DTO_ABI_VERSION, Int32(device), Int64(traj.N), Int32(traj.dim), Int32(traj.global_dim),
                                first0(traj, traj.timestep), Int32(eval_hessian), Int32(length(idescs)), Int32(length(odescs)),
-                               Int32(length(cdescs)), block_generators ? DTO_FLAG_BLOCK_GENERATORS : Int32(0), pointer(idescs), pointer(odescs), pointer(cdescs),
+                               Int32(length(cdescs)), (block_generators ? DTO_FLAG_BLOCK_GENERATORS : Int32(0)) | (shared_generators ? DTO_FLAG_SHARED_GENERATORS : Int32(0)), pointer(idescs), pointer(odescs), pointer(cdescs),
                                pointer(Z0), Int64(k_lo), Int64(k_hi)))
         rc = @ccall lib.dto_create(desc::Ptr{ProblemDesc}, h::Ptr{Ptr{Cvoid}})::Cint
         rc == 0 || error(unsafe_string(@ccall lib.dto_last_error(C_NULL::Ptr{Cvoid})::Cstring))
@@ -727,6 +728,19 @@ function integrator_blocks(ev::GPUEvaluator, i::Integer)
     i0 = Int32(i - 1)
     check(ev, @ccall lib.dto_integrator_blocks(ev.handle::Ptr{Cvoid}, i0::Int32, b::Ptr{Int32}, r::Ptr{Int32}, a::Ptr{Int32})::Cint)
     return Int(b[]), Int(r[]), a[] != 0
+end
+
+"""
+`(leader, group_size, active)` of integrator `i` (1-based): the group of `BilinearIntegrator`s whose extracted generators and control
+component are equal (`GPUEvaluator(prob; shared_generators = true)`: the kets `ψ̃1 … ψ̃P` of a multi-state problem, all built from
+one closure `G`), its first member in list order, and whether the group shares one propagator chain in
+`eval_constraint_jacobian`; `(i, 1, false)` otherwise.
+"""
+function integrator_share(ev::GPUEvaluator, i::Integer)
+    l, n, a = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    i0 = Int32(i - 1)
+    check(ev, @ccall lib.dto_integrator_share(ev.handle::Ptr{Cvoid}, i0::Int32, l::Ptr{Int32}, n::Ptr{Int32}, a::Ptr{Int32})::Cint)
+    return Int(l[]) + 1, Int(n[]), a[] != 0
 end
 
 """
