@@ -159,12 +159,17 @@ struct ExtSlot {
     double* d[3] = {nullptr, nullptr, nullptr};
 };
 
-// DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR: evaluated by dto_tdb.hip into per-interval blocks, placed like an external integrator
+// DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR: evaluated by dto_tdb.hip (1..64 states) or dto_tdb_mfma.hip (65..256 states) into
+// per-interval blocks, placed like an external integrator
 struct TdbHost {
     KTdb k{};
     KExtInt place{};
     double *d_vals = nullptr, *d_jac = nullptr, *d_hess = nullptr, *d_scratch = nullptr;
     size_t stride = 0;
+    // 65..256 states: zero-padded generators and their transposes, and the scratch slots (= workgroups) of the persistent grid
+    bool mfma = false;
+    double *d_Bp = nullptr, *d_BpT = nullptr;
+    int resident = 0;
 };
 
 struct ProfRec {
@@ -380,7 +385,7 @@ struct ProfScope {
 };
 // (for the bandwidth-bound categories from CAT_ZERO on, `flops` carries the launch's algorithmic BYTES)
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13 };
 // the form a generator sweep took (dto_profile_get "sweep_gs" .. "sweep_step"): one count per run_sweep call, not per launch
 enum { SWEEP_GS = 0, SWEEP_FUSED = 1, SWEEP_S64 = 2, SWEEP_CLUSTER = 3, SWEEP_STEP = 4 };
 inline void count_sweep_form(dto_handle* h, int form) {
@@ -1350,6 +1355,12 @@ void tdb_eval(dto_handle* h, TdbHost& t, const double* dZ, const double* dmu, in
     const KProb& P = h->P;
     const int64_t lo = need == 0 ? P.kn_lo : std::max<int64_t>(0, P.kn_lo - 1);
     const int64_t hi = need == 0 ? P.kn_lo + P.n_int : std::min<int64_t>(P.K, P.kn_lo + P.n_knots);
+    if (t.mfma) {
+        ProfScope ps(h, st, CAT_TDB_MFMA, tdb_mfma_flops(t.k, need) * (double)std::max<int64_t>(hi - lo, 0));
+        HIP_CHECK(launch_tdb_mfma(st, P, t.k, t.d_Bp, t.d_BpT, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch,
+                                  t.stride, t.resident));
+        return;
+    }
     HIP_CHECK(launch_tdb(st, P, t.k, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch, t.stride));
 }
 
@@ -2516,7 +2527,10 @@ int dto_create(const dto_problem_desc* d, dto_handle** out) {
                 TdbHost t;
                 t.k.n = s.x_dim; t.k.m = s.u_dim; t.k.x_off = s.x_off; t.k.u_off = s.u_off; t.k.t_off = s.t_off;
                 t.k.order = s.spline_order; t.k.substeps = s.substeps; t.k.nmod = s.n_mod; t.k.row_off = row;
-                if (!tdb_supported(t.k)) throw HipError{"time-dependent bilinear integrator: outside the device kernel's range (1..64 states, substeps >= 1, coefficient table)"};
+                // 1..64 states: k_tdb; 65..256 states: k_tdb_mfma; the refusal names the limit that was hit
+                if (const char* why = tdb_mfma_refusal(t.k)) throw HipError{why};
+                t.mfma = tdb_mfma_supported(t.k);
+                if (!t.mfma && !tdb_supported(t.k)) throw HipError{"time-dependent bilinear integrator: outside the device kernels' range (1..256 states, substeps >= 1, coefficient table)"};
                 for (int c = 0; c < s.n_mod; ++c)
                     if (s.mod_kind[c] != 1 && s.mod_kind[c] != 2) throw HipError{"time-dependent bilinear integrator: mod_kind is 1 (cos) or 2 (sin)"};
                 t.place.d = s.x_dim; t.place.pre = pre; t.place.row_off = row;
@@ -2527,6 +2541,24 @@ int dto_create(const dto_problem_desc* d, dto_handle** out) {
                         t.k.H = own(h, dupload(std::vector<double>(s.H, s.H + (size_t)s.n_mod * m1 * nn)));
                         t.k.mod_kind = own(h, dupload(std::vector<int32_t>(s.mod_kind, s.mod_kind + s.n_mod)));
                         t.k.mod_omega = own(h, dupload(std::vector<double>(s.mod_omega, s.mod_omega + s.n_mod)));
+                    }
+                    if (t.mfma) {
+                        // B_q, q = j (1 + n_mod) + c (c = 0: G_j, c >= 1: H_{c-1, j}), zero-padded, and their transposes
+                        const size_t n_ = (size_t)s.x_dim, np_ = (size_t)tdb_mfma_npad(s.x_dim), nm1 = (size_t)s.n_mod + 1;
+                        std::vector<double> Bp(m1 * nm1 * np_ * np_, 0.0), BpT(Bp.size(), 0.0);
+                        for (size_t j = 0; j < m1; ++j)
+                            for (size_t c = 0; c < nm1; ++c) {
+                                const double* src = c == 0 ? s.G + j * nn : s.H + ((c - 1) * m1 + j) * nn;
+                                double* dst = Bp.data() + (j * nm1 + c) * np_ * np_;
+                                double* dstT = BpT.data() + (j * nm1 + c) * np_ * np_;
+                                for (size_t col = 0; col < n_; ++col)
+                                    for (size_t r = 0; r < n_; ++r) {
+                                        dst[col * np_ + r] = src[col * n_ + r];
+                                        dstT[r * np_ + col] = src[col * n_ + r];
+                                    }
+                            }
+                        t.d_Bp = own(h, dupload(Bp));
+                        t.d_BpT = own(h, dupload(BpT));
                     }
                 }
                 h->integ_index.push_back((int)h->tdb.size());
@@ -2926,6 +2958,15 @@ int dto_create(const dto_problem_desc* d, dto_handle** out) {
             t.d_vals = own(h, dalloc<double>(K * n));
             t.d_jac = own(h, dalloc<double>(K * n * 2 * z));
             if (d->eval_hessian) t.d_hess = own(h, dalloc<double>(K * 4 * z * z));
+            if (t.mfma) {
+                // sized by the persistent grid (two workgroups per compute unit), not by the number of intervals
+                int cus = 0;
+                HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+                t.resident = (int)std::min<int64_t>(P.n_knots + 1, 2 * (int64_t)std::max(cus, 1));
+                t.stride = (std::max(tdb_mfma_scratch_doubles(t.k, 1), d->eval_hessian ? tdb_mfma_scratch_doubles(t.k, 2) : (size_t)0) + 1) & ~(size_t)1;
+                t.d_scratch = own(h, dalloc<double>(t.stride * (size_t)t.resident));
+                continue;
+            }
             t.stride = (std::max(tdb_scratch_doubles(t.k, 1), d->eval_hessian ? tdb_scratch_doubles(t.k, 2) : (size_t)0) + 1) & ~(size_t)1;
             t.d_scratch = own(h, dalloc<double>(t.stride * (size_t)(P.n_knots + 1)));
         }
@@ -3101,6 +3142,13 @@ int dto_interval_costs(const dto_handle* h, const double* Z, int64_t first, int6
             cost[i] += b.small ? 2.0 * b.k.n * (double)b.k.n * b.k.n * (6.0 + sq2) : gemm * products + basis + sweep;
         }
     }
+    // time-dependent bilinear integrators of 65..256 states: the flops of one Jacobian call of k_tdb_mfma (fixed steps: the same
+    // for every interval)
+    for (const TdbHost& t : h->tdb)
+        if (t.mfma) {
+            const double c = tdb_mfma_flops(t.k, 1);
+            for (int64_t i = 0; i < count; ++i) cost[i] += c;
+        }
     // every other term kind costs O(z) per knot: a constant that keeps intervals without a bilinear integrator from counting as free
     for (int64_t i = 0; i < count; ++i) cost[i] += 64.0 * h->z;
     return 0;
@@ -3682,6 +3730,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "expmv_adjoint")) cat = CAT_SWEEP_ADJOINT;
         else if (!strcmp(name, "hess_product")) cat = CAT_HESS_PRODUCT;
         else if (!strcmp(name, "share")) cat = CAT_SHARE;
+        else if (!strcmp(name, "tdb_mfma")) cat = CAT_TDB_MFMA;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index

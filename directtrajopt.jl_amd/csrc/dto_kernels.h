@@ -364,6 +364,19 @@ size_t tdb_scratch_doubles(const KTdb& T, int need);
 // blocks of intervals i_lo .. i_lo + count - 1 (global, 0-based) into vals [K][n], jac [K][2z][n], hess [K][2z][2z]
 hipError_t launch_tdb(hipStream_t st, const KProb& P, const KTdb& T, const double* dZ, const double* dmu, int need, int64_t i_lo,
                       int64_t count, double* vals, double* jac, double* hess, double* scratch, size_t scratch_stride);
+// The same integrator at 65..256 states (dto_tdb_mfma.hip): FP64 MFMA products against M0 = sum_q c_q B_q, the derivative jets
+// applied as scalar combinations of B_q y; a persistent grid of `resident` workgroups, one scratch slot of `scratch_stride` doubles
+// each.  Bp / BpT: the Q = (m+1)(1+nmod) matrices G_j, H_cj (q = j (1 + nmod) + c) and their transposes, zero-padded to
+// tdb_mfma_npad(n) rows and columns, column-major.  tdb_mfma_refusal: nullptr, or which limit of the device kernels (either of
+// them: 1..256 states, substeps, coefficient table) a description exceeds.  tdb_mfma_flops: flops of one interval as executed.
+int tdb_mfma_npad(int n);
+const char* tdb_mfma_refusal(const KTdb& T);
+bool tdb_mfma_supported(const KTdb& T);
+size_t tdb_mfma_scratch_doubles(const KTdb& T, int need);
+double tdb_mfma_flops(const KTdb& T, int need);
+hipError_t launch_tdb_mfma(hipStream_t st, const KProb& P, const KTdb& T, const double* Bp, const double* BpT, const double* dZ,
+                           const double* dmu, int need, int64_t i_lo, int64_t count, double* vals, double* jac, double* hess,
+                           double* scratch, size_t scratch_stride, int resident);
 
 // BilinearIntegrator with replicated-block generators G_j = I_r (x) B_j (dto_kron.hip): one workgroup per interval sweeps b-row
 // column groups against the b x b blocks and writes defect, Jacobian block or Hessian block of mu_k' f straight to their positions

@@ -1,0 +1,418 @@
+// dto_tdb_mfma.hip -- device propagator of the TimeDependentBilinearIntegrator for 65..256 states, on v_mfma_f64_16x16x4_f64.
+//
+// Same mathematics, ABI family and output blocks as k_tdb (dto_tdb.hip, which keeps 1..64 states): classical RK4 with `substeps`
+// fixed steps on tau in [0, 1] applied to the state together with its variational equations, parameters
+// theta = [u_k (m), t_k, dt_k, u_{k+1} (m, order 1)], the (x, theta) block of the Hessian of mu' f by the discrete adjoint.  What
+// differs is the organisation, because at these sizes k_tdb's per-interval slab of materialised jets (1 + p + p (p+1) / 2 matrices
+// of n x n) does not fit and its scalar matrix-vector loops do not scale:
+//
+//   * NO MATERIALISED JETS.  Every jet of M = dt G(u(tau), t) is a scalar combination of the Q = (m+1)(1+nmod) shared matrices B_q
+//     (G_j, H_cj; the engine keeps zero-padded copies B_q and B_q' of np x np, np = n rounded up to 32).  Only
+//     M0 = sum_q c_q B_q is formed as a matrix, once per stage time (three per sub-step, the last is the next one's first).  A
+//     derivative jet is applied as M_b y = sum_q c_bq (B_q y): U_q = B_q y is computed once per stage for the stage's few vectors
+//     (x alone in a Jacobian call; x and x_b in a Hessian call; kbar_0 in the adjoint) and combined with scalars in the epilogue of
+//     the M0 product.
+//   * ONE WORKGROUP-LEVEL GEMM.  All M0 / B_q products with 32 columns or more go through gemm_accumulate_s (dto_gemm.hip.h:
+//     LDS-staged K panels, 2 x 2 wavefronts) on TM x 64 tiles, TM x 32 for a last half tile; TM = 64 where np is a multiple of 64,
+//     else 32.  Columns of one call, each of np rows (column-major, leading dimension np):
+//         defect    x | zeros to 32
+//         Jacobian  x, x_b (p) | zeros to 32 | Phi (np columns, starts as the identity)       -- the Phi block carries the flops
+//         Hessian   x, x_b (p), x_ab (p (p+1) / 2) | zeros to a multiple of 32                 -- no Phi, no Phi_b
+//     The single-vector U_q of Jacobian calls and of the adjoint is a vector pass (one thread per (q, row), B_q read once).
+//   * PERSISTENT GRID.  `resident` workgroups walk the intervals (interval i of the launch goes to workgroup i mod resident); the
+//     scratch is one slot per workgroup, so it is sized by the grid and not by the number of intervals.
+//
+// Numerical rules: what a workgroup computes is a function of its interval's data alone (not of the grid, the shard or the slot);
+// every sum has a fixed order; there is no floating-point atomic.  Output entries that share a position (a component that serves
+// twice, e.g. the timestep listed as the time variable) are added by one thread in a fixed order.  Padded rows and columns are
+// computed (they are zeros) and never written to vals / jac / hess.
+#include <algorithm>
+
+#include "dto_gemm.hip.h"
+#include "dto_kernels.h"
+
+namespace dto {
+
+namespace {
+
+constexpr int TDBM_MAX_COEFS = 6144;  // (1 + p + p (p+1)/2) * Q, as in dto_tdb.hip
+constexpr int TDBM_VEC = 32;          // column tile of the vector block
+constexpr int TDBM_MAX_PAIRS = 160;   // p (p+1) / 2 <= 136 at 7 drives, order 1
+
+inline __host__ __device__ int pad32(int v) { return (v + 31) / 32 * 32; }
+
+// scratch of one resident workgroup (doubles): four column sets, M0, the U_q vectors, ubar of the adjoint, the coefficient table
+struct TdbmLayout {
+    int np, p, P2, Q, C, Cv, Ctot, ucols;
+    size_t oY, oACC, oTA, oTB, oM0, oU, oUB, oCoef, total;
+};
+inline __host__ __device__ TdbmLayout tdbm_layout(const KTdb& T, int need) {
+    TdbmLayout L;
+    L.np = pad32(T.n);
+    L.p = T.m + 2 + (T.order ? T.m : 0);
+    L.P2 = L.p * (L.p + 1) / 2;
+    L.Q = (T.m + 1) * (1 + T.nmod);
+    L.C = need == 0 ? 1 : (need == 1 ? 1 + L.p : 1 + L.p + L.P2);   // meaningful columns of the vector block
+    L.Cv = pad32(L.C);
+    L.Ctot = L.Cv + (need == 1 ? L.np : 0);
+    L.ucols = need == 2 ? TDBM_VEC : 1;
+    const size_t cols = (size_t)L.np * L.Ctot;
+    L.oY = 0; L.oACC = cols; L.oTA = 2 * cols; L.oTB = 3 * cols;
+    L.oM0 = 4 * cols;
+    L.oU = L.oM0 + (size_t)L.np * L.np;
+    L.oUB = L.oU + (size_t)L.Q * L.ucols * L.np;
+    L.oCoef = L.oUB + (size_t)L.np * TDBM_VEC;
+    L.total = L.oCoef + (size_t)(1 + L.p + L.P2) * L.Q;
+    L.total = (L.total + 1) & ~(size_t)1;
+    return L;
+}
+
+struct TdbmArgs {
+    KProb P;
+    KTdb T;
+    const double* Bp;    // [Q][np][np] zero-padded B_q, column-major; q = j (1 + nmod) + c, c = 0: G_j, c >= 1: H_{c-1, j}
+    const double* BpT;   // their transposes
+    const double* Z;
+    const double* mu;
+    int need;
+    int64_t i_lo, count;
+    double* vals;        // [K][n]
+    double* jac;         // [K][2z][n]
+    double* hess;        // [K][2z][2z]
+    double* scratch;
+    int64_t scratch_stride;
+};
+
+// Scalar coefficient of B_q in one jet of M(tau) = dt sum_j a_j(tau) (G_j + sum_c phi_c(t) H_cj), t = t_k + tau dt -- the table of
+// k_tdb's form_jets.  which: 0 value; 1 + b first derivative; 1 + p + pair(a, b) second derivative (a <= b, row-major triangle).
+__device__ double tdbm_coef(const KTdb& T, const double* zk, const double* zk1, double tk, double dt, double tau, int p, int which, int q) {
+    const int m = T.m, nmod = T.nmod;
+    const int j = q / (1 + nmod), c = q - j * (1 + nmod);
+    int b1 = -1, b2 = -1;
+    if (which >= 1 && which <= p) b1 = which - 1;
+    else if (which > p) {
+        int rem = which - 1 - p, aa = 0;
+        while (rem >= p - aa) { rem -= p - aa; ++aa; }
+        b1 = aa; b2 = aa + rem;
+    }
+    // a_j and its derivative slots: wk = d a_j / d u_kj, wk1 = d a_j / d u_{k+1,j}
+    double aj = 1.0, wk = 0.0, wk1 = 0.0;
+    if (j >= 1) {
+        const double uk = zk[T.u_off + j - 1];
+        if (T.order) { const double uk1 = zk1[T.u_off + j - 1]; aj = (1.0 - tau) * uk + tau * uk1; wk = 1.0 - tau; wk1 = tau; }
+        else { aj = uk; wk = 1.0; }
+    }
+    double ph = 1.0, ph1 = 0.0, ph2 = 0.0;
+    if (c >= 1) {
+        const double om = T.mod_omega[c - 1], arg = om * (tk + tau * dt);
+        const double cs = cos(arg), sn = sin(arg);
+        if (T.mod_kind[c - 1] == 1) { ph = cs; ph1 = -om * sn; ph2 = -om * om * cs; }
+        else { ph = sn; ph1 = om * cs; ph2 = -om * om * sn; }
+    }
+    // parameter classes: 0 = u_k (drive jj), 1 = t, 2 = dt, 3 = u_{k+1} (drive jj)
+    auto cls = [&](int b, int& jj) { if (b < m) { jj = b + 1; return 0; } if (b == m) { jj = -1; return 1; }
+                                     if (b == m + 1) { jj = -1; return 2; } jj = b - m - 1; return 3; };
+    if (which == 0) return dt * aj * ph;
+    if (b2 < 0) {
+        int jj; const int k1 = cls(b1, jj);
+        if (k1 == 0) return jj == j ? dt * wk * ph : 0.0;
+        if (k1 == 3) return jj == j ? dt * wk1 * ph : 0.0;
+        if (k1 == 1) return dt * aj * ph1;
+        return aj * ph + dt * aj * tau * ph1;
+    }
+    int j1, j2; const int k1 = cls(b1, j1), k2 = cls(b2, j2);
+    const bool u1 = k1 == 0 || k1 == 3, u2 = k2 == 0 || k2 == 3;
+    if (u1 && u2) return 0.0;
+    if (u1 || u2) {
+        const int ju = u1 ? j1 : j2, ku = u1 ? k1 : k2, ko = u1 ? k2 : k1;
+        const double w = ku == 0 ? wk : wk1;
+        if (ju != j) return 0.0;
+        return ko == 1 ? dt * w * ph1 : w * (ph + dt * tau * ph1);
+    }
+    if (k1 == 1 && k2 == 1) return dt * aj * ph2;
+    if (k1 == 2 && k2 == 2) return 2.0 * aj * tau * ph1 + dt * aj * tau * tau * ph2;
+    return aj * ph1 + dt * aj * tau * ph2;   // (t, dt)
+}
+
+// One TM x TN tile of A (np x np, column-major) times columns c0 .. of B; epi(row, col, value) for every element of the tile.
+// All threads of the workgroup call it (the core ends with a barrier).
+template <class S, class Epi>
+__device__ __forceinline__ void mm_tile(const double* __restrict__ A, const double* __restrict__ B, int np, int r0, int c0,
+                                        double* smem, Epi&& epi) {
+    GemmAccS<S> acc;
+    acc.zero();
+    gemm_accumulate_s<S>(acc, A + r0, np, B + (size_t)c0 * np, np, np, nullptr, smem);
+    const GemmCoordS<S> co;
+#pragma unroll
+    for (int ti = 0; ti < S::MT; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < S::NT; ++tj)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) epi(r0 + co.row_base + 16 * ti, c0 + co.col_base + 16 * tj + 4 * r, acc.v[ti][tj][r]);
+}
+
+// A (np x np) times `ncols` (a multiple of 32) columns of B: 64-column tiles, a 32-column one for the rest
+template <int TM, class Epi>
+__device__ __forceinline__ void mm_cols(const double* __restrict__ A, const double* __restrict__ B, int np, int ncols, double* smem,
+                                        Epi&& epi) {
+    for (int r0 = 0; r0 < np; r0 += TM) {
+        int c0 = 0;
+        for (; c0 + 64 <= ncols; c0 += 64) mm_tile<GemmShape<TM, 64, 2, 2>>(A, B, np, r0, c0, smem, epi);
+        if (c0 < ncols) mm_tile<GemmShape<TM, 32, 2, 2>>(A, B, np, r0, c0, smem, epi);
+    }
+}
+
+template <int TM>
+__global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
+    const int n = a.T.n, m = a.T.m, z = a.P.z, need = a.need;
+    const TdbmLayout L = tdbm_layout(a.T, need);
+    const int np = L.np, p = L.p, P2 = L.P2, Q = L.Q, C = L.C, Ctot = L.Ctot, ucols = L.ucols;
+    const int tid = threadIdx.x;
+    const size_t nn = (size_t)np * np;
+    __shared__ __attribute__((aligned(16))) double smem[GemmShape<TM, 64, 2, 2>::SMEM_DOUBLES];
+    __shared__ double vsh[256];                                // the vector of a vector pass
+    __shared__ unsigned char pair_a[TDBM_MAX_PAIRS], pair_b[TDBM_MAX_PAIRS];
+    for (int e = tid; e < P2; e += 256) {
+        int rem = e, aa = 0;
+        while (rem >= p - aa) { rem -= p - aa; ++aa; }
+        pair_a[e] = (unsigned char)aa; pair_b[e] = (unsigned char)(aa + rem);
+    }
+    double* S = a.scratch + (int64_t)blockIdx.x * a.scratch_stride;
+    double* Y = S + L.oY;
+    double* ACC = S + L.oACC;
+    double* TA = S + L.oTA;
+    double* TB = S + L.oTB;
+    double* M0 = S + L.oM0;
+    double* U = S + L.oU;       // [Q][ucols][np]
+    double* UB = S + L.oUB;     // [32][np]
+    double* coefs = S + L.oCoef;  // [jets][Q]
+    __syncthreads();
+
+    for (int64_t it = blockIdx.x; it < a.count; it += gridDim.x) {
+        const int64_t kn = a.i_lo + it;
+        const double* zk = a.Z + kn * z;
+        const double* zk1 = zk + z;
+        const double tk = zk[a.T.t_off], dt = zk[a.P.dt_idx];
+
+        // coefficients of `njet` jets at tau, then M0 = sum_q c_q B_q (or B_q' for the adjoint) in the fixed order q = 0, 1, ...
+        auto form_m0 = [&](double tau, int njet, const double* __restrict__ B) {
+            for (int e = tid; e < njet * Q; e += 256) coefs[e] = tdbm_coef(a.T, zk, zk1, tk, dt, tau, p, e / Q, e % Q);
+            __syncthreads();
+            for (size_t e = 2 * (size_t)tid; e < nn; e += 512) {
+                d2 acc = d2{0.0, 0.0};
+                for (int q = 0; q < Q; ++q) {
+                    const double cf = coefs[q];
+                    const d2 b = *reinterpret_cast<const d2*>(B + q * nn + e);
+                    acc.x += cf * b.x; acc.y += cf * b.y;
+                }
+                *reinterpret_cast<d2*>(M0 + e) = acc;
+            }
+            __syncthreads();
+        };
+        // U[q][0][:] = B_q v for one vector v (np rows): thread per (q, row), four partial sums over k mod 4 joined in a fixed order
+        auto vec_pass = [&](const double* __restrict__ B, const double* __restrict__ v) {
+            for (int r = tid; r < np; r += 256) vsh[r] = v[r];
+            __syncthreads();
+            for (int e = tid; e < Q * np; e += 256) {
+                const int q = e / np, r = e - q * np;
+                const double* col = B + q * nn + r;
+                double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+                for (int k = 0; k < np; k += 4) {
+                    s0 += col[(size_t)k * np] * vsh[k];
+                    s1 += col[(size_t)(k + 1) * np] * vsh[k + 1];
+                    s2 += col[(size_t)(k + 2) * np] * vsh[k + 2];
+                    s3 += col[(size_t)(k + 3) * np] * vsh[k + 3];
+                }
+                U[(size_t)q * ucols * np + r] = (s0 + s1) + (s2 + s3);
+            }
+            __syncthreads();
+        };
+
+        // initial values: x = x_k, Phi = I, everything else (padding included) 0
+        for (size_t e = tid; e < (size_t)np * Ctot; e += 256) {
+            const int c = (int)(e / np), r = (int)(e - (size_t)c * np);
+            double v = 0.0;
+            if (c == 0) v = r < n ? zk[a.T.x_off + r] : 0.0;
+            else if (c >= L.Cv) v = (c - L.Cv == r && r < n) ? 1.0 : 0.0;
+            Y[e] = v;
+        }
+        __syncthreads();
+
+        const double h = 1.0 / a.T.substeps;
+        const int njet_fwd = need == 0 ? 1 : (need == 1 ? 1 + p : 1 + p + P2);
+        for (int step = 0; step < a.T.substeps; ++step) {
+            for (int stage = 0; stage < 4; ++stage) {
+                const double tau = (step + (stage == 0 ? 0.0 : (stage == 3 ? 1.0 : 0.5))) * h;
+                const double* IN = stage == 0 ? Y : (stage == 2 ? TB : TA);
+                double* OUT = stage == 0 ? TA : (stage == 1 ? TB : (stage == 2 ? TA : Y));
+                if (stage != 2) form_m0(tau, njet_fwd, a.Bp);   // stages 1 and 2 share their time
+                // U_q = B_q y for the vectors whose jets enter this call: x (Jacobian), x and x_b (Hessian)
+                if (need == 1) vec_pass(a.Bp, IN);
+                else if (need == 2) {
+                    for (int q = 0; q < Q; ++q)
+                        mm_cols<TM>(a.Bp + q * nn, IN, np, TDBM_VEC, smem,
+                                    [&](int row, int col, double v) { U[((size_t)q * TDBM_VEC + col) * np + row] = v; });
+                    __syncthreads();
+                }
+                const double w_acc = (stage == 0 || stage == 3) ? h / 6.0 : h / 3.0;
+                const double w_tmp = stage == 2 ? h : 0.5 * h;
+                // K = M0 IN (+ the jets' terms), then the RK4 update of this stage
+                mm_cols<TM>(M0, IN, np, Ctot, smem, [&](int row, int col, double K) {
+                    if (need >= 1 && col >= 1 && col <= p) {
+                        const double* cf = coefs + (size_t)col * Q;   // jet 1 + b, b = col - 1
+                        double s = 0.0;
+                        for (int q = 0; q < Q; ++q) s += cf[q] * U[(size_t)q * ucols * np + row];
+                        K += s;
+                    } else if (need == 2 && col > p && col < C) {
+                        const int e = col - 1 - p, aa = pair_a[e], bb = pair_b[e];
+                        const double *ca = coefs + (size_t)(1 + aa) * Q, *cb = coefs + (size_t)(1 + bb) * Q, *cab = coefs + (size_t)(1 + p + e) * Q;
+                        double s = 0.0;
+                        for (int q = 0; q < Q; ++q) {
+                            const double* uq = U + (size_t)q * TDBM_VEC * np + row;
+                            s += ca[q] * uq[(size_t)(1 + bb) * np] + cb[q] * uq[(size_t)(1 + aa) * np] + cab[q] * uq[0];
+                        }
+                        K += s;
+                    }
+                    const size_t e = (size_t)col * np + row;
+                    const double y0 = Y[e];
+                    if (stage == 0) { ACC[e] = y0 + w_acc * K; OUT[e] = y0 + w_tmp * K; }
+                    else if (stage < 3) { ACC[e] += w_acc * K; OUT[e] = y0 + w_tmp * K; }
+                    else OUT[e] = ACC[e] + w_acc * K;
+                });
+                __syncthreads();
+            }
+        }
+
+        // ---- outputs (blocks of a generic integrator, laid out as k_tdb writes them)
+        for (int r = tid; r < n; r += 256) a.vals[kn * n + r] = zk1[a.T.x_off + r] - Y[r];
+        auto zz_of = [&](int b) { return b < m ? a.T.u_off + b : (b == m ? a.T.t_off : (b == m + 1 ? a.P.dt_idx : z + a.T.u_off + (b - m - 2))); };
+        if (need == 1) {
+            double* J = a.jac + kn * (int64_t)n * 2 * z;
+            for (int64_t e = tid; e < (int64_t)n * 2 * z; e += 256) J[e] = 0.0;
+            __syncthreads();
+            const double* PHI = Y + (size_t)L.Cv * np;
+            for (int e = tid; e < n * n; e += 256) {
+                const int i = e / n, r = e - i * n;
+                J[(int64_t)(a.T.x_off + i) * n + r] = -PHI[(size_t)i * np + r];
+            }
+            for (int r = tid; r < n; r += 256) J[(int64_t)(z + a.T.x_off + r) * n + r] = 1.0;
+            __syncthreads();
+            // parameter columns ADD (a component may serve twice); row r belongs to one thread, b in order
+            for (int r = tid; r < n; r += 256)
+                for (int b = 0; b < p; ++b) J[(int64_t)zz_of(b) * n + r] -= Y[(size_t)(1 + b) * np + r];
+        } else if (need == 2) {
+            // discrete adjoint lambda = Phi' mu and its parameter sensitivities lambda_b, backward through the steps (k_tdb's
+            // recursion).  Columns 0 .. p of W: lambda, lambda_b; Y keeps x_ab for the (theta, theta) block.
+            const double* muk = a.mu + a.T.row_off + kn * n;
+            double* W = TA;
+            double* WN = TB;
+            double* KB = ACC;
+            const int CA = 1 + p, nv = np * TDBM_VEC;
+            for (int e = tid; e < nv; e += 256) { W[e] = e < n ? muk[e] : 0.0; UB[e] = 0.0; }
+            __syncthreads();
+            for (int step = a.T.substeps - 1; step >= 0; --step) {
+                for (int e = tid; e < nv; e += 256) WN[e] = W[e];
+                for (int stage = 3; stage >= 0; --stage) {
+                    const double tau = (step + (stage == 0 ? 0.0 : (stage == 3 ? 1.0 : 0.5))) * h;
+                    if (stage != 1) form_m0(tau, CA, a.BpT);   // stages 2 and 1 share their time
+                    const double cw = (stage == 3 || stage == 0) ? h / 6.0 : h / 3.0;
+                    const double cu = stage == 3 ? 0.0 : (stage == 2 ? h : 0.5 * h);
+                    for (int e = tid; e < nv; e += 256) KB[e] = cw * W[e] + (cu != 0.0 ? cu * UB[e] : 0.0);
+                    __syncthreads();
+                    vec_pass(a.BpT, KB);   // U_q = B_q' kbar_0 (ucols = 32 in a Hessian call: column 0 of each q)
+                    // ubar_c = M0' kbar_c (+ M_b' kbar_0 for the sensitivity columns)
+                    mm_cols<TM>(M0, KB, np, TDBM_VEC, smem, [&](int row, int col, double u) {
+                        if (col >= 1 && col <= p) {
+                            const double* cf = coefs + (size_t)col * Q;
+                            double s = 0.0;
+                            for (int q = 0; q < Q; ++q) s += cf[q] * U[(size_t)q * ucols * np + row];
+                            u += s;
+                        }
+                        const size_t e = (size_t)col * np + row;
+                        UB[e] = u;
+                        WN[e] += u;
+                    });
+                    __syncthreads();
+                }
+                for (int e = tid; e < nv; e += 256) W[e] = WN[e];
+                __syncthreads();
+            }
+
+            const int ld = 2 * z;
+            double* Hb = a.hess + kn * (int64_t)4 * z * z;
+            for (int64_t e = tid; e < (int64_t)4 * z * z; e += 256) Hb[e] = 0.0;
+            __syncthreads();
+            // (x_i, theta_b) = -d lambda_i / d theta_b: thread i owns row x_i in the first pass and column x_i in the second, b in order
+            for (int i = tid; i < n; i += 256)
+                for (int b = 0; b < p; ++b) Hb[(a.T.x_off + i) + (int64_t)ld * zz_of(b)] -= W[(size_t)(1 + b) * np + i];
+            __syncthreads();
+            for (int i = tid; i < n; i += 256)
+                for (int b = 0; b < p; ++b) Hb[zz_of(b) + (int64_t)ld * (a.T.x_off + i)] -= W[(size_t)(1 + b) * np + i];
+            __syncthreads();
+            // (theta_a, theta_b) = -mu' x_ab: the dot products in parallel (into UB), then one thread adds them in order
+            for (int e = tid; e < P2; e += 256) {
+                double s = 0.0;
+                const double* xab = Y + (size_t)(1 + p + e) * np;
+                for (int r = 0; r < n; ++r) s += muk[r] * xab[r];
+                UB[e] = s;
+            }
+            __syncthreads();
+            if (tid == 0)
+                for (int e = 0; e < P2; ++e) {
+                    const int ra = zz_of(pair_a[e]), rb = zz_of(pair_b[e]);
+                    Hb[ra + (int64_t)ld * rb] -= UB[e];
+                    if (pair_a[e] != pair_b[e]) Hb[rb + (int64_t)ld * ra] -= UB[e];
+                }
+        }
+        __syncthreads();   // the slot is reused by this workgroup's next interval
+    }
+}
+
+}  // namespace
+
+int tdb_mfma_npad(int n) { return pad32(n); }
+
+const char* tdb_mfma_refusal(const KTdb& T) {
+    const int p = T.m + 2 + (T.order ? T.m : 0);
+    const long nM = 1 + p + (long)p * (p + 1) / 2;
+    if (T.n < 1 || T.n > 256) return "time-dependent bilinear integrator: the device kernels take 1..256 states";
+    if (T.substeps < 1) return "time-dependent bilinear integrator: substeps must be >= 1";
+    if (T.nmod < 0) return "time-dependent bilinear integrator: n_mod must be >= 0";
+    if (nM * (T.m + 1) * (1 + T.nmod) > TDBM_MAX_COEFS)
+        return "time-dependent bilinear integrator: coefficient table (1 + p + p (p+1) / 2) (m+1) (1 + n_mod) exceeds 6144 entries";
+    return nullptr;
+}
+
+bool tdb_mfma_supported(const KTdb& T) { return T.n > 64 && tdb_mfma_refusal(T) == nullptr; }
+
+size_t tdb_mfma_scratch_doubles(const KTdb& T, int need) { return tdbm_layout(T, need).total; }
+
+// MFMA and vector-pass flops of one interval as executed (padding included): per stage the M0 product over all columns and the
+// U_q products; per stage time the formation of M0
+double tdb_mfma_flops(const KTdb& T, int need) {
+    const TdbmLayout L = tdbm_layout(T, need);
+    const double np2 = (double)L.np * L.np, S = T.substeps;
+    const double form = 2.0 * L.Q * np2;
+    double fwd = 4.0 * 2.0 * np2 * L.Ctot + 3.0 * form;
+    if (need == 1) fwd += 4.0 * 2.0 * L.Q * np2;
+    if (need == 2) fwd += 4.0 * 2.0 * L.Q * np2 * TDBM_VEC;
+    double bwd = 0.0;
+    if (need == 2) bwd = 4.0 * (2.0 * np2 * TDBM_VEC + 2.0 * L.Q * np2) + 3.0 * form;
+    return S * (fwd + bwd);
+}
+
+hipError_t launch_tdb_mfma(hipStream_t st, const KProb& P, const KTdb& T, const double* Bp, const double* BpT, const double* dZ,
+                           const double* dmu, int need, int64_t i_lo, int64_t count, double* vals, double* jac, double* hess,
+                           double* scratch, size_t scratch_stride, int resident) {
+    if (count <= 0) return hipSuccess;
+    if (resident < 1 || tdbm_layout(T, need).total > scratch_stride) return hipErrorInvalidValue;
+    TdbmArgs a{};
+    a.P = P; a.T = T; a.Bp = Bp; a.BpT = BpT; a.Z = dZ; a.mu = dmu; a.need = need; a.i_lo = i_lo; a.count = count;
+    a.vals = vals; a.jac = jac; a.hess = hess; a.scratch = scratch; a.scratch_stride = (int64_t)scratch_stride;
+    const unsigned grid = (unsigned)std::min<int64_t>(count, resident);
+    if (pad32(T.n) % 64 == 0) hipLaunchKernelGGL(k_tdb_mfma<64>, dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_tdb_mfma<32>, dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace dto

@@ -1,24 +1,138 @@
 #!/usr/bin/env python3
-"""Timing of the device TimeDependentBilinearIntegrator (a tools/ probe): Jacobian / Hessian per call, n states x N knots."""
-import sys, os, time
+"""The device TimeDependentBilinearIntegrator at 65..256 states (csrc/dto_tdb_mfma.hip), timed with HIP events (a tools/ probe; GPU).
+
+Per shape, in ONE process: a problem with random generators of unit-order norm (`drives` drives, two carrier terms, 16 sub-steps),
+both spline orders; device-resident inputs and outputs; eval_constraint, eval_constraint_jacobian and eval_hessian_lagrangian, each
+after a warm-up of at least 30 ms of GPU work; the median of ``--reps`` single-call timings.  Beside the call time the line gives
+the new kernel's time alone and its FP64 rate from the flop count as executed (dto_profile_get "tdb_mfma").  ``--host 72x20``
+adds the host-evaluated path (on_device=False: Python RK4, numeric derivatives, merged by the engine) against the device path on
+the same problem, through host pointers, one call each.  One JSON line per shape and order.
+
+    python tools/tdb_time.py                                  # 72 x 500, 128 x 500, 256 x 250 and the host path at 72 x 20
+    python tools/tdb_time.py --shapes 128x500 --orders 1 --host ""
+    python tools/tdb_time.py --small 1                        # the scalar kernel's sizes (4 .. 64 states, csrc/dto_tdb.hip) through
+                                                              # host pointers, as this probe reported them before
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
-import numpy as np
-import dto_amd, dto_oracle as O
-from helpers import to_engine
-for n, N, sub in ((4, 1000, 16), (16, 500, 16), (32, 500, 16), (64, 200, 16)):
-    po = O.make_tdb_problem(N=N, n=n, m=2, order=1, seed=3, substeps=sub)
-    ev = dto_amd.Evaluator(to_engine(po))
-    Z = po.Z0
-    mu = np.ones(ev.n_constraints)
-    j = np.empty(ev.shard.jac_len); h = np.empty(ev.shard.hess_len)
-    out = []
-    for name, fn in (("jac", lambda: ev.eval_constraint_jacobian(j, Z)), ("hess", lambda: ev.eval_hessian_lagrangian(h, Z, 1.0, mu))):
-        fn(); fn()
-        t0 = time.perf_counter()
-        for _ in range(5):
-            fn()
-        out.append(f"{name} {(time.perf_counter() - t0) / 5 * 1e3:.2f} ms")
-    print(f"tdb {n} states x {N} knots, {sub} sub-steps (host pointers): " + ", ".join(out), flush=True)
-    ev.close()
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import dto_amd  # noqa: E402
+
+
+def problem(n, N, drives, order, substeps, on_device=True, seed=42):
+    rng = np.random.default_rng(seed)
+    traj = dto_amd.NamedTrajectory({"x": rng.standard_normal((n, N)), "u": 0.4 * rng.standard_normal((drives, N)),
+                                    "t": np.cumsum(np.full(N, 0.3))[None, :], "dt": 0.25 + 0.1 * rng.random((1, N))}, timestep="dt")
+    s = 1.0 / np.sqrt(n / 4.0)
+    G = s * rng.standard_normal((drives + 1, n, n))
+    mods = [("cos", 1.7, 0.5 * s * rng.standard_normal((drives + 1, n, n))), ("sin", 0.6, 0.5 * s * rng.standard_normal((drives + 1, n, n)))]
+    tdb = dto_amd.TimeDependentBilinearIntegrator(dto_amd.ModulatedGenerators(G, mods), "x", "u", "t", traj, spline_order=order,
+                                                  substeps=substeps, on_device=on_device)
+    return dto_amd.DirectTrajOptProblem(traj, dto_amd.QuadraticRegularizer("u", traj, 1.0), [tdb])
+
+
+def one_call_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def timed(fn, reps):
+    spent = 0.0
+    while spent < 30.0:          # warm-up: at least 30 ms of GPU work
+        spent += one_call_ms(fn)
+    return statistics.median(one_call_ms(fn) for _ in range(reps))
+
+
+def measure_device(prob, reps, sigma=0.7):
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ev = dto_amd.Evaluator(prob, eval_hessian=True)
+    try:
+        Z = torch.from_numpy(prob.trajectory.vec()).to(dev)
+        mu = torch.randn(ev.n_constraints, generator=torch.Generator(device="cpu").manual_seed(1), dtype=torch.float64).to(dev)
+        con = torch.empty(ev.n_constraints, dtype=torch.float64, device=dev)
+        J = torch.empty(ev.n_jacobian_entries, dtype=torch.float64, device=dev)
+        H = torch.empty(ev.n_hessian_entries, dtype=torch.float64, device=dev)
+        calls = {"constraint": lambda: ev.eval_constraint_dev(Z.data_ptr(), con.data_ptr(), st),
+                 "jacobian": lambda: ev.eval_jacobian_dev(Z.data_ptr(), J.data_ptr(), st),
+                 "hessian": lambda: ev.eval_hessian_dev(Z.data_ptr(), sigma, mu.data_ptr(), H.data_ptr(), st)}
+        out = {}
+        for name, fn in calls.items():
+            out[name + "_ms"] = round(timed(fn, reps), 4)
+            ev.profile_enable(True); ev.profile_reset(); fn(); torch.cuda.synchronize()
+            ms, launches, fl = ev.profile_get("tdb_mfma")
+            ev.profile_enable(False)
+            out[name + "_kernel_ms"] = round(ms, 4)
+            out[name + "_kernel_launches"] = launches
+            out[name + "_kernel_TFLOPs"] = round(fl / ms * 1e-9, 3) if ms > 0 else None
+        return out
+    finally:
+        ev.close()
+
+
+def measure_host_pointers(prob, reps):
+    """One blocking call each through host pointers (wall clock): what the host-evaluated path can be compared on."""
+    ev = dto_amd.Evaluator(prob, eval_hessian=True)
+    try:
+        Z = prob.trajectory.vec()
+        mu = np.random.default_rng(1).standard_normal(ev.n_constraints)
+        g, J, H = np.empty(ev.n_constraints), np.empty(ev.n_jacobian_entries), np.empty(ev.n_hessian_entries)
+        out = {}
+        for name, fn in (("constraint", lambda: ev.eval_constraint(g, Z)), ("jacobian", lambda: ev.eval_constraint_jacobian(J, Z)),
+                         ("hessian", lambda: ev.eval_hessian_lagrangian(H, Z, 0.7, mu))):
+            ts = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                fn()
+                ts.append(1e3 * (time.perf_counter() - t0))
+            out[name + "_ms"] = round(statistics.median(ts), 3)
+        return out
+    finally:
+        ev.close()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--shapes", default="72x500,128x500,256x250", help="comma-separated states x knots")
+    ap.add_argument("--orders", default="0,1")
+    ap.add_argument("--drives", type=int, default=4)
+    ap.add_argument("--substeps", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--host", default="72x20", help="states x knots of the host-evaluated comparison (empty: none)")
+    ap.add_argument("--small", type=int, default=0, help="1: 4 .. 64 states (k_tdb), 2 drives, order 1, host pointers; nothing else")
+    a = ap.parse_args()
+    if a.small:
+        for n, N in ((4, 1000), (16, 500), (32, 500), (64, 200)):
+            out = {"n": n, "knots": N, "drives": 2, "substeps": a.substeps, "order": 1, "through": "host pointers, wall clock"}
+            out.update(measure_host_pointers(problem(n, N, 2, 1, a.substeps), 5))
+            print(json.dumps(out), flush=True)
+        return
+    for s in [x for x in a.shapes.split(",") if x]:
+        n, N = (int(x) for x in s.lower().split("x"))
+        for order in (int(x) for x in a.orders.split(",")):
+            out = {"n": n, "knots": N, "drives": a.drives, "substeps": a.substeps, "order": order}
+            out.update(measure_device(problem(n, N, a.drives, order, a.substeps), a.reps))
+            print(json.dumps(out), flush=True)
+    if a.host:
+        n, N = (int(x) for x in a.host.lower().split("x"))
+        out = {"n": n, "knots": N, "drives": a.drives, "substeps": a.substeps, "order": 1, "through": "host pointers, wall clock"}
+        out["device"] = measure_host_pointers(problem(n, N, a.drives, 1, a.substeps), 3)
+        out["host_evaluated"] = measure_host_pointers(problem(n, N, a.drives, 1, a.substeps, on_device=False), 1)
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
