@@ -1,325 +1,20 @@
-// dto_engine.cpp -- host side of the C ABI declared in include/dto_engine.h.
+// dto_engine.cpp -- evaluation side of the C ABI declared in include/dto_engine.h.
 //
-// Owns the handle, builds the sparsity structure in the reference's exact order
-// (src/solvers/evaluator.jl:119-209, closed forms of SURVEY.md §3.6 + a per-column prefix sum for
-// the value-dependent constraint entries), and orchestrates the HIP kernels of dto_kernels.hip.
-// There is NO CPU fallback: every evaluation runs on the GPU or fails with an error code.
-#include "../../include/dto_engine.h"
+// Orchestrates the HIP kernels of dto_kernels.hip on a handle (dto_handle.h) that dto_create.cpp built: sweep planning, the
+// propagator chain, the callbacks, the transfer plans, the extern "C" entry points other than dto_create, the communicator and
+// profiling.  There is NO CPU fallback: every evaluation runs on the GPU or fails with an error code.
+#include "dto_handle.h"
 
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <limits>
 #include <map>
-#include <string>
-#include <vector>
-
-#include "dto_comm.h"
-#include "dto_hostxfer.h"
-#include "dto_kernels.h"
-
-#include <memory>
 
 using namespace dto;
 
-namespace {
-
-thread_local std::string g_create_error;
-
-struct HipError {
-    std::string msg;
-};
-
-#define HIP_CHECK(expr)                                                                          \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) {                                                                  \
-            char buf_[512];                                                                      \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                     __FILE__, __LINE__);                                                        \
-            throw HipError{buf_};                                                                \
-        }                                                                                        \
-    } while (0)
-
-template <class T>
-T* dalloc(size_t n) {
-    void* p = nullptr;
-    if (n == 0) n = 1;
-    HIP_CHECK(hipMalloc(&p, n * sizeof(T)));
-    return static_cast<T*>(p);
-}
-template <class T>
-T* dupload(const std::vector<T>& v) {
-    T* p = dalloc<T>(v.size());
-    if (!v.empty()) HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return p;
-}
-
-// Grow-only device workspace of a sweep form whose workgroups hand data to each other (ensure_sweep_work replaces both parts)
-struct SweepWork {
-    double* slab = nullptr;
-    unsigned* arrive = nullptr;
-    size_t cap = 0;     // doubles in slab
-    int counters = 0;   // interval groups (generator-stationary) or clusters (row-split) the counters serve
-};
-
-struct BilHost {
-    KBil k;
-    SweepBuf fw{}, ad{};
-    int T_alloc = 0;
-    std::vector<double> g1;   // ||G_j||_1
-    std::vector<double> n2;   // ||G_i G_j||_1, (m+1)^2
-    double* d_g1 = nullptr;
-    double* d_n2 = nullptr;
-    ChainWork chain{};
-    int chain_cap = 0;
-    unsigned long long* d_hump = nullptr;  // [8] k_hump output: log hump(q), last term index, q = 1..4 (max over intervals)
-    double hump_logH[4] = {0, 0, 0, 0};
-    int hump_kend[4] = {0, 0, 0, 0};
-    bool hump_valid = false;
-    // reuse_forward_sweep: what b.fw still holds for the cached Z -- 0 nothing, 1 the p sums (S type 0), 2 p and d^j sums
-    // and GY, 3 additionally every Taylor term in fw.Zt (cache_steps of them)
-    int cache_kind = 0, cache_steps = 0;
-    // option reuse_forward_sweep: the step budget the Jacobian's chain planned from its exact norms at the cached point (q = 0: none)
-    int plan_q = 0, plan_dub = 0;
-    // ... and whether the Taylor terms of the p column of that point sit in fw.Zt ([term][Kpad][npad], one type per term:
-    // eval_constraint and the Hessian's forward sweep store them), p_steps + 1 of them, valid counts per block in fw.nterms_p
-    bool p_terms = false;
-    int p_steps = 0;
-    int p_nblk = 0;           // intervals per entry of fw.nterms_p (the convergence blocks of the sweep that stored the p terms)
-    // row-split cluster sweeps (dto_sweep_fused.hip): exchange slabs and arrival counters, one set per sweep buffer ([0] fw,
-    // [1] ad: the Hessian's forward and adjoint sweeps may run side by side)
-    SweepWork cluster_work[2];
-    // generator-stationary sweeps (dto_sweep_gs.hip): partial-norm slabs and arrival counters per sweep buffer
-    SweepWork gs_work[2];
-    bool small = false;       // n <= 32: fused one-workgroup-per-interval path (dto_small.hip)
-    double* d_Gs = nullptr;   // compact generators for that path
-    bool use_basis = false;   // A^2..A^4 from the generator subspace instead of three batched GEMMs
-    BasisSet basis[3]{};      // degrees 2, 3, 4
-    BasisSet basis_all{};     // every multiset of degree 0..4: one GEMM gives the factor K of the two-product Taylor form
-    // Hessian pairing path: stored Taylor terms of both sweeps, E_j * forward terms, Beta-weighted adjoint sums
-    bool pairing = false;
-    double* EP = nullptr;
-    double* Upair = nullptr;
-    double* d_Btab = nullptr;
-    // DTO_FLAG_BLOCK_GENERATORS: G_j = I_r (x) B_j found at create (kb x kb blocks, kr of them; (n, 1) without); `kron`: the
-    // structured path (dto_kron.hip) serves the integrator -- none of the workspaces above exist then
-    int kb = 0, kr = 1;
-    bool kron = false;
-    KKron kk{};
-    double* d_kron_scratch = nullptr;
-    size_t kron_stride = 0;
-    // DTO_FLAG_SHARED_GENERATORS: the group of integrators with these generators and controls (indices into dto_handle::bil; the
-    // leader is the first member in list order; -1 / 1 without a partner).  `share_active`: the group shares the leader's
-    // propagator chain -- a follower runs none, its -E_k blocks are copies of the leader's (dto_share.hip).  `share_followers`
-    // (leader of an active group only): the other members in list order.  `list_pos`: position in the integrator list.
-    int share_leader = -1, share_size = 1, list_pos = 0;
-    bool share_active = false;
-    std::vector<int> share_followers;
-    bool follows() const { return share_active && share_followers.empty(); }
-};
-
-struct ConHost {
-    KCon k{};
-    int equality = 0;
-    int64_t n_times_total = 0;
-    int64_t row_off = 0;  // global 0-based first row
-    std::vector<int64_t> times0;  // all times (0-based knots), reference order
-    std::vector<int32_t> comps;
-    int g_dim = 1;
-    bool external = false;        // DTO_CONSTRAINT_EXTERNAL[_GLOBAL]: values/Jacobian/Hessian blocks come from dto_set_external
-    bool global = false;          // ..._GLOBAL: `comps` index global_data; the single listing sits at the pseudo-knot N
-    int ext_slot = -1;
-    std::vector<double> jac0;     // external: Jacobian blocks at Z0 (pattern)
-    std::vector<double> hess0;    // global: Hessian of sum(g) at Z0 (pattern)
-    std::vector<double> M;        // QUADFORM_MINUS_C: the symmetric n_comps x n_comps matrix, column-major
-    KExtTerm xk{};                // external: placement of the Hessian blocks
-};
-
-// DTO_OBJECTIVE_EXTERNAL_KNOT / _GLOBAL: placement data of a host-evaluated objective term
-struct ExtObjHost {
-    double weight = 1.0;
-    bool global = false;
-    std::vector<int32_t> comps, gcomps;
-    std::vector<int64_t> times0;  // listed knots, 0-based; {N} for a GlobalObjective (no knot part)
-    KExtTerm k{};
-    int ext_slot = -1;
-};
-
-// one host-evaluated term's values for the coming callbacks + grow-only device staging
-struct ExtSlot {
-    dto_external_values v{nullptr, nullptr, nullptr};
-    size_t len[3] = {0, 0, 0};   // doubles per array (all listed times)
-    double* d[3] = {nullptr, nullptr, nullptr};
-};
-
-// DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR: evaluated by dto_tdb.hip (1..64 states) or dto_tdb_mfma.hip (65..256 states) into
-// per-interval blocks, placed like an external integrator
-struct TdbHost {
-    KTdb k{};
-    KExtInt place{};
-    double *d_vals = nullptr, *d_jac = nullptr, *d_hess = nullptr, *d_scratch = nullptr;
-    size_t stride = 0;
-    // 65..256 states: zero-padded generators and their transposes, and the scratch slots (= workgroups) of the persistent grid
-    bool mfma = false;
-    double *d_Bp = nullptr, *d_BpT = nullptr;
-    int resident = 0;
-};
-
-struct ProfRec {
-    hipEvent_t a, b;
-    int cat;
-    double flops;
-};
-
-}  // namespace
-
-struct dto_handle {
-    std::string err;
-    int device = 0;
-    bool structure_only = false;  // created with device < 0: sizes, structure and shard queries only
-    int64_t N = 0, K = 0;
-    int z = 0, gd = 0, dt_idx = 0, D = 0;
-    int eval_hessian = 1;
-    int64_t n_vars = 0, n_cons = 0, n_dyn = 0, jac_nnz = 0, hess_nnz = 0;
-    int64_t k_lo = 1, k_hi = 1;
-    KProb P{};
-    std::vector<int64_t> colptr;            // host copy
-    std::vector<int64_t> con_cols, con_rows;  // constraint pattern entries sorted by (col,row), 0-based
-    std::vector<int64_t> con_colstart;      // index into con_* of each column with entries (map col -> range)
-    std::vector<BilHost> bil;
-    std::vector<KDer> der;
-    std::vector<int> integ_kind, integ_index;  // reference order -> (kind, index into bil/der)
-    std::vector<int> integ_dim;
-    std::vector<int64_t> integ_row_off;
-    std::vector<ConHost> con;
-    std::vector<KObj> obj;
-    struct ObjInfo {  // host copy of what a built-in objective term touches in the Hessian (the D2H plan needs it)
-        int kind, comp_off, comp_dim;
-        std::vector<int32_t> comps;
-        std::vector<int64_t> times;  // owned, 0-based
-        // The term's listings are stored in LAYERS: layer l holds the (l+1)-th listing of every knot, so that inside one layer
-        // no two listings name the same knot.  Gradient and Hessian kernels run layer by layer (one launch each; a single
-        // layer unless `times` repeats a knot): contributions to one entry are added in listing order, never concurrently.
-        std::vector<int64_t> layer_start;  // [n_layers + 1] offsets into the (layer-sorted) listing arrays
-    };
-    std::vector<ObjInfo> obj_info;
-    // host-pointer entry points: only the entries that can change cross PCIe (dto_hostxfer.h); built lazily at the first
-    // host-pointer Jacobian / Hessian call, option "host_xfer" = 0 keeps the plain whole-slab copy
-    std::unique_ptr<HostXfer> xfer;
-    XferPlan jac_plan, hess_plan;
-    int xfer_cap = 0;                                         // host-pointer Jacobian: chain chunk (intervals) for the early hand-over, 0 = off
-    std::function<void(int64_t, int)> on_chain_chunk;         // ... and its hook: (first local interval, count) of a finished chunk
-    bool plans_built = false;
-    bool raw_plans_built = false;
-    // dto_bind_output_dev: a device buffer the caller passes again and again (MadNLP's value vectors in GPU mode).  Once a call
-    // has written it in full ("primed"), later calls into the SAME pointer leave the call-invariant entries alone -- structural
-    // zeros, the identity z_{k+1} halves: half of a Jacobian slab, 99 % of a Hessian slab -- and clear only the runs a kernel
-    // accumulates into.  [0] Jacobian, [1] Hessian.
-    double* bound[2] = {nullptr, nullptr};
-    bool primed[2] = {false, false};
-    int64_t* d_bind_start[2] = {nullptr, nullptr};
-    int64_t* d_bind_len[2] = {nullptr, nullptr};
-    int64_t n_bind_runs[2] = {0, 0};
-    bool bind_ready[2] = {false, false};
-    int host_xfer = 1;
-    int xfer_check = 0;  // option "host_xfer_check": every host-pointer Jacobian / Hessian is compared with the whole device slab
-    std::vector<ExtObjHost> ext_obj;
-    std::vector<KExtInt> ext_int;  // DTO_INTEGRATOR_EXTERNAL, slot = index
-    std::vector<TdbHost> tdb;      // DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR
-    std::vector<ExtSlot> ext;      // external integrators, then constraints, then objectives, each in list order
-    int n_ext_int = 0, n_ext_con = 0, n_ext_obj = 0;
-    std::vector<int64_t> tail_colptr, tail_rows;  // Hessian entries in global-variable columns (CSC tail)
-    int64_t hess_block_nnz = 0;
-    std::vector<std::pair<int64_t, int64_t>> row_segments;  // (global start 0-based, len)
-    int64_t cons_len = 0;
-    dto_shard_info info{};
-
-    // device scratch
-    int64_t* d_colptr = nullptr;
-    double* d_Z = nullptr;
-    double* d_mu = nullptr;
-    double* d_out = nullptr;  // host-API staging for the largest output
-    size_t d_out_cap = 0;
-    double* d_partial = nullptr;
-    double* d_f = nullptr;
-    double* d_bounds = nullptr;  // [2] max beta, max b1 (as uint64 bit patterns)
-    int32_t* d_plan = nullptr;   // [4] {q, d_ub, tc} of a sweep planned on the device from d_bounds (launch_plan_dev)
-    double* d_jac_scratch = nullptr;     // value slab for the Jacobian-vector products (lazy)
-    double* d_w = nullptr;               // product input
-    int64_t* d_conbase = nullptr;        // [n_vars+1] first constraint-pattern entry of each column
-    int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
-    int64_t* d_crow_col = nullptr;
-    int64_t* d_crow_pos = nullptr;
-    int64_t* d_con_rows = nullptr;       // constraint-pattern rows, (col,row) order
-    double* h_pinned = nullptr;  // [32]: 0-1 bounds, 2-3 chain scalars, 6 sweep stats, 16-23 hump readback, 28 deferred squaring count
-    bool smax_pending = false;   // the one-launch chain's squaring count lands in h_pinned[28] behind ev_done (read by check_sweeps)
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;   // generator sweep runs here, concurrently with the propagator chain
-    hipStream_t stream_rb = nullptr; // the chain's 96-byte readback (evaluation form, squaring counts, hump bound) leaves on this one
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_stats = nullptr, ev_chain = nullptr, ev_rb = nullptr, ev_zero = nullptr;
-
-    bool reuse = false;          // option reuse_forward_sweep
-    double* d_Zcache = nullptr;  // the Z the cached sweeps belong to
-    int32_t* d_eq = nullptr;
-    bool profiling = false;
-    std::vector<ProfRec> prof;
-    int64_t sweep_forms[5] = {0, 0, 0, 0, 0};  // run_sweep calls by the form they took (SWEEP_GS ..), counted while profiling
-    std::vector<hipEvent_t> ev_pool;  // recycled timing events (creating them inside the timed region costs host time)
-    int last_smax = 0, last_terms = 0;
-    int expm_form = 0;  // option "expm_form": 0 = by cost, 2 / 3 = forced
-    int overlap_sweep = 1;  // option "overlap_sweep": the Jacobian's generator sweep on a second stream next to the chain's products
-    int sweep_form = 0;   // option "sweep_form": 0 = fused persistent sweep where it applies, 1 = step-per-launch form only
-    int chain_form = 0;   // option "chain_form": 0 = the one-launch chain of 33..64-state integrators where it applies, 1 = batched-GEMM launches only
-    int n_cu = 256;
-    int chain_chunk = 0;  // option "chain_chunk": upper bound on the intervals per chain chunk (0: workspace capacity)
-    int deterministic = 0;  // option "deterministic": results independent of overlap_sweep and of the entry-point family
-    // deferred errors of the `*_dev` entry points (dto_engine.h, error convention): the sweep statistics of the last
-    // asynchronous call are copied to pinned memory behind its kernels and looked at by the next call through the ABI
-    hipEvent_t ev_done = nullptr;
-    bool stats_pending = false;
-    int32_t* h_stats = nullptr;  // pinned [2 * bilinear integrators][2]
-    int last_form = 0;
-    // multi-GPU (dto_comm.h): the knot ranges of the communicator's ranks (dto_comm_create exchanges them over RCCL,
-    // dto_comm_set_ranges takes them from a caller with a transport of its own), the gather plans that follow from them,
-    // and the communicator itself
-    std::unique_ptr<Comm> comm;
-    int comm_rank = -1;
-    std::vector<std::pair<int64_t, int64_t>> rank_ranges;               // (k_lo, k_hi) per rank, 1-based inclusive
-    GatherPlan gather_plan[4];                                           // DTO_VECTOR_* - 1
-    std::vector<Slab> cons_segments;                                     // every rank's row segments of g ...
-    std::vector<int> cons_segment_root;                                  // ... and the rank that owns each
-    int64_t* d_ranges = nullptr;
-    // Hessian-vector products (dto_eval_hessian_product[_dev]): H is assembled once per point into a private slab, its entries
-    // that can be non-zero are gathered into a row-major copy of both triangles, and every product at that point is one launch
-    // (dto_hess_product.hip).  The point is (Z, sigma, mu) bit for bit plus `gen`, which every dto_set_external, dto_set_option and
-    // failed call bumps.
-    double* hp_slab = nullptr;       // [hess_len], allocated at the first product
-    bool hp_slab_primed = false;     // written in full once: later points clear only the variable runs (as a bound output)
-    bool hp_index = false;
-    KHessProduct hp{};
-    int64_t hp_nnz = 0;              // entries of the row-major copy (odd rows padded)
-    int64_t* d_hp_pos = nullptr;     // [hp_nnz] slab position of every entry, -1 for padding
-    double* d_hp_val = nullptr;
-    double* d_hp_Z = nullptr;        // the cached point
-    double* d_hp_mu = nullptr;
-    double* d_hp_v = nullptr;        // host-pointer form: v
-    int32_t* d_hp_eq = nullptr;
-    double hp_sigma = 0.0;
-    bool hp_valid = false;
-    uint64_t gen = 0, hp_gen = 0;
-    double hp_setup_ms = 0.0;        // host time of the index build ...
-    double hp_bytes = 0.0;           // ... and the device bytes of the private slab and the index
-    std::vector<void*> owned;  // device allocations to free
-
-    ~dto_handle();
-};
+thread_local std::string dto::g_create_error;
 
 dto_handle::~dto_handle() {
     if (structure_only) return;
@@ -346,19 +41,6 @@ dto_handle::~dto_handle() {
 }
 
 namespace {
-
-template <class T>
-T* own(dto_handle* h, T* p) {
-    h->owned.push_back(p);
-    return p;
-}
-
-int fail(dto_handle* h, const std::string& m) {
-    if (h) h->err = m; else g_create_error = m;
-    return 1;
-}
-
-inline int pad64(int n) { return ((n + 63) / 64) * 64; }
 
 struct ProfScope {
     dto_handle* h;
@@ -396,183 +78,16 @@ inline void count_sweep_form(dto_handle* h, int form) {
 // structure
 // ------------------------------------------------------------------------------------------
 
-// Largest r dividing n with G_j == I_r (x) B_j for all m1 generators (n x n column-major, compared with ==): off-diagonal blocks
-// exactly zero, every diagonal block equal to the first.  1 if there is none.
-int find_replicas(const double* G, int n, int m1) {
-    for (int r = n; r >= 2; --r) {
-        if (n % r) continue;
-        const int b = n / r;
-        bool ok = true;
-        for (int j = 0; j < m1 && ok; ++j) {
-            const double* M = G + (size_t)j * n * n;
-            for (int c = 0; c < n && ok; ++c) {
-                const int bc = c / b;
-                const double* col = M + (size_t)c * n;
-                const double* first = M + (size_t)(c - bc * b) * n;
-                for (int q = 0; q < n; ++q) {
-                    const int bq = q / b;
-                    if (bq != bc ? !(col[q] == 0.0) : !(col[q] == first[q - bq * b])) { ok = false; break; }
-                }
-            }
-        }
-        if (ok) return r;
-    }
-    return 1;
-}
-
-// Does the fused one-workgroup-per-interval path (dto_small.hip) serve a bilinear integrator of n states and m drives?  n <= 16 with
-// one wavefront, 17..32 with four, while the interval's matrices, generators and sweep columns fit the CU's LDS.  The one place
-// that decides it: dto_create and the grouping below ask here.
-bool small_path_serves(int flags, int eval_hessian, int n, int m) {
-    const int Tf = eval_hessian ? 1 + m + m * (m + 1) / 2 : 1 + m;
-    return (flags & DTO_FLAG_GENERAL_PATH_ONLY) == 0 && n <= 32 && Tf <= MAX_TYPES && small_lds_bytes(n, m, Tf, 1 + m) <= 150 * 1024;
-}
-
-// DTO_FLAG_SHARED_GENERATORS: partition the bilinear integrators into groups with equal x_dim, control component and generators
-// (compared with ==, as find_replicas does).  Host arithmetic on the descriptor: also on structure-only handles.
-void find_share_groups(dto_handle* h, const dto_problem_desc* d) {
-    for (int i = 0; i < d->n_integrators; ++i)
-        if (h->integ_kind[i] == DTO_INTEGRATOR_BILINEAR) h->bil[h->integ_index[i]].list_pos = i;
-    if (!(d->flags & DTO_FLAG_SHARED_GENERATORS)) return;
-    // the path an integrator takes follows from x_dim, m and the flags -- equal for the members of a group -- except the structured
-    // path, which also asks where state, controls and timestep lie: an integrator it serves is grouped with its like only
-    for (int i = 0; i < d->n_integrators; ++i) {
-        if (h->integ_kind[i] != DTO_INTEGRATOR_BILINEAR) continue;
-        const int bi = h->integ_index[i];
-        if (h->bil[bi].share_leader >= 0) continue;  // a member of an earlier group
-        const dto_integrator_desc& a = d->integrators[i];
-        const size_t len = (size_t)(a.u_dim + 1) * a.x_dim * a.x_dim;
-        std::vector<int> members{bi};
-        for (int j = i + 1; j < d->n_integrators; ++j) {
-            if (h->integ_kind[j] != DTO_INTEGRATOR_BILINEAR) continue;
-            const int bj = h->integ_index[j];
-            const dto_integrator_desc& c = d->integrators[j];
-            if (h->bil[bj].share_leader >= 0 || c.x_dim != a.x_dim || c.u_dim != a.u_dim || (a.u_dim > 0 && c.u_off != a.u_off) ||
-                h->bil[bj].kron != h->bil[bi].kron)
-                continue;
-            bool eq = true;
-            for (size_t e = 0; e < len && eq; ++e) eq = a.G[e] == c.G[e];
-            if (eq) members.push_back(bj);
-        }
-        if (members.size() < 2) continue;
-        const bool active = !h->bil[bi].kron && !small_path_serves(d->flags, d->eval_hessian, a.x_dim, a.u_dim) && members.size() - 1 <= (size_t)SHARE_MAX_FOLLOWERS;
-        for (int mb : members) {
-            h->bil[mb].share_leader = bi;
-            h->bil[mb].share_size = (int)members.size();
-            h->bil[mb].share_active = active;
-        }
-        if (active) h->bil[bi].share_followers.assign(members.begin() + 1, members.end());
-    }
-}
-
-// number of integrator rows touching a column of knot kn (0-based): D per adjacent interval
-inline int col_cnt(const dto_handle* h, int64_t kn) { return kn >= h->N ? 0 : (kn >= 1 ? 1 : 0) + (kn < h->K ? 1 : 0); }
-
-double con_jac_value(const ConHost& c, const double* zk, int comp_i) {
-    if (c.k.kind == DTO_CONSTRAINT_QUADFORM_MINUS_C) {  // 2 (M v)_c, summed over j ascending with an unfused multiply-add: the
-        const size_t n = c.comps.size();                // arithmetic of the device's row walk (dto_quadform.hip, qf_row)
-        double y = 0.0;
-        {
-#pragma clang fp contract(off)
-            for (size_t j = 0; j < n; ++j) y = y + c.M[(size_t)comp_i + n * j] * zk[c.comps[j]];
-        }
-        return 2.0 * y;
-    }
-    double s = 0.0;
-    for (int q : c.comps) s += zk[q] * zk[q];
-    const double v = zk[c.comps[comp_i]];
-    return c.k.kind == DTO_CONSTRAINT_NORM_MINUS_C ? v / std::sqrt(s) : 2.0 * v;
-}
-
-void build_structure(dto_handle* h, const double* Z0) {
-    const int64_t nv = h->n_vars;
-    // constraint pattern = numeric Jacobian at Z0, exact zeros not stored (evaluator.jl:136)
-    std::vector<std::pair<int64_t, int64_t>> ent;
-    for (auto& c : h->con) {
-        for (int64_t i = 0; i < c.n_times_total; ++i) {
-            const int64_t kn = c.times0[i];
-            const double* zk = Z0 + kn * h->z;
-            for (size_t q = 0; q < c.comps.size(); ++q) {
-                if (c.external) {
-                    for (int r = 0; r < c.g_dim; ++r)
-                        if (c.jac0[((size_t)i * c.comps.size() + q) * c.g_dim + r] != 0.0)
-                            ent.emplace_back(kn * h->z + c.comps[q], c.row_off + i * c.g_dim + r);
-                    continue;
-                }
-                const double v = con_jac_value(c, zk, (int)q);
-                if (v != 0.0) ent.emplace_back(kn * h->z + c.comps[q], c.row_off + i);
-            }
-        }
-    }
-    std::sort(ent.begin(), ent.end());
-    ent.erase(std::unique(ent.begin(), ent.end()), ent.end());
-    h->con_cols.resize(ent.size());
-    h->con_rows.resize(ent.size());
-    std::vector<int32_t> extra(nv, 0);
-    for (size_t i = 0; i < ent.size(); ++i) {
-        h->con_cols[i] = ent[i].first;
-        h->con_rows[i] = ent[i].second;
-        extra[ent[i].first]++;
-    }
-    h->colptr.assign(nv + 1, 0);
-    for (int64_t kn = 0; kn < h->N; ++kn) {
-        const int64_t per = (int64_t)h->D * col_cnt(h, kn);
-        for (int j = 0; j < h->z; ++j) {
-            const int64_t c = kn * h->z + j;
-            h->colptr[c + 1] = h->colptr[c] + per + extra[c];
-        }
-    }
-    for (int64_t c = h->N * h->z; c < nv; ++c) h->colptr[c + 1] = h->colptr[c] + extra[c];  // global columns: only NonlinearGlobalConstraint rows
-    h->jac_nnz = h->colptr[nv];
-    const int64_t z = h->z;
-    h->hess_block_nnz = h->N * (z * (z + 1) / 2) + h->K * z * z;  // evaluator.jl:201-202 on the block pattern
-    // tail: entries whose column is a global variable (global columns follow every knot column in the CSC order).
-    // GlobalObjective / GlobalKnotPointObjective mark their whole index block (global_objectives.jl:89-101, 277-300),
-    // NonlinearGlobalConstraint contributes the non-zeros of its Hessian at mu = ones (evaluator.jl:166)
-    std::vector<std::vector<int64_t>> rows(h->gd);
-    const int64_t g0 = h->N * z;
-    for (auto& e : h->ext_obj) {
-        if (!e.global) continue;
-        for (int gb : e.gcomps) {
-            for (int64_t t : e.times0)
-                if (t < h->N)
-                    for (int ca : e.comps) rows[gb].push_back(t * z + ca);
-            for (int ga : e.gcomps)
-                if (ga <= gb) rows[gb].push_back(g0 + ga);
-        }
-    }
-    for (auto& c : h->con) {
-        if (!c.global) continue;
-        const size_t ng = c.comps.size();
-        for (size_t b = 0; b < ng; ++b)
-            for (size_t a = 0; a < ng; ++a)
-                if (c.comps[a] <= c.comps[b] && c.hess0[a + ng * b] != 0.0) rows[c.comps[b]].push_back(g0 + c.comps[a]);
-    }
-    h->tail_colptr.assign(h->gd + 1, 0);
-    h->tail_rows.clear();
-    for (int j = 0; j < h->gd; ++j) {
-        std::sort(rows[j].begin(), rows[j].end());
-        rows[j].erase(std::unique(rows[j].begin(), rows[j].end()), rows[j].end());
-        h->tail_rows.insert(h->tail_rows.end(), rows[j].begin(), rows[j].end());
-        h->tail_colptr[j + 1] = (int64_t)h->tail_rows.size();
-    }
-    h->hess_nnz = h->hess_block_nnz + (int64_t)h->tail_rows.size();
-}
-
-// first constraint-pattern entry of column c
-inline size_t con_lower(const dto_handle* h, int64_t c) {
-    return std::lower_bound(h->con_cols.begin(), h->con_cols.end(), c) - h->con_cols.begin();
-}
-
 int64_t hess_block_start(const dto_handle* h, int64_t kn) {
     const int64_t z = h->z, tri = z * (z + 1) / 2;
     return kn == 0 ? 0 : tri + (kn - 1) * (z * z + tri);
 }
 
+}  // namespace
+
+namespace dto {
+
 // value slabs of the handle that owns knots k_lo..k_hi (1-based, inclusive): positions inside the global vectors
-struct ShardExtents {
-    int64_t grad_lo, grad_len, jac_lo, jac_len, hess_lo, hess_len;
-};
 ShardExtents shard_extents(const dto_handle* h, int64_t k_lo, int64_t k_hi) {
     const int64_t kn_lo = k_lo - 1, n_knots = k_hi - k_lo + 1;
     const int64_t c_lo = kn_lo * h->z, c_hi = (kn_lo + n_knots) * h->z;
@@ -610,38 +125,13 @@ std::vector<std::pair<int64_t, int64_t>> shard_row_segments(const dto_handle* h,
     return seg;
 }
 
+}  // namespace dto
+
+namespace {
+
 // ------------------------------------------------------------------------------------------
 // sweeps and chain
 // ------------------------------------------------------------------------------------------
-
-void alloc_sweep(dto_handle* h, BilHost& b, SweepBuf& w, int T, bool with_W) {
-    const int npad = b.k.npad;
-    w.npad = npad;
-    w.T_alloc = T;
-    w.TN = (npad % 128 == 0) ? 128 : 64;
-    w.nblk = w.TN;
-    int64_t nint = std::max<int64_t>(h->P.n_int, 1);
-    w.Kpad = (int)(((nint + w.TN - 1) / w.TN) * w.TN);
-    const size_t typesz = (size_t)w.Kpad * npad;
-    w.Z[0] = own(h, dalloc<double>(typesz * T));
-    w.Z[1] = own(h, dalloc<double>(typesz * T));
-    w.S = own(h, dalloc<double>(typesz * T));
-    w.GY = own(h, dalloc<double>(typesz));
-    w.W = with_W ? own(h, dalloc<double>(typesz * (b.k.m + 1))) : nullptr;
-    w.scaleA = own(h, dalloc<double>((size_t)(b.k.m + 1) * w.Kpad));
-    w.scaleU = own(h, dalloc<double>((size_t)(b.k.m + 1) * w.Kpad));
-    w.scaleE = own(h, dalloc<double>((size_t)2 * w.Kpad));
-    w.termnorm = own(h, dalloc<unsigned long long>((size_t)3 * T * w.Kpad));
-    w.sumnorm = own(h, dalloc<unsigned long long>((size_t)T * w.Kpad));
-    w.active = own(h, dalloc<int32_t>(w.Kpad / w.TN));
-    w.stats = own(h, dalloc<int32_t>(4));
-    HIP_CHECK(hipMemset(w.stats, 0, 4 * sizeof(int32_t)));
-    // padding columns/rows must be finite zeros from the start
-    HIP_CHECK(hipMemset(w.Z[0], 0, typesz * T * sizeof(double)));
-    HIP_CHECK(hipMemset(w.Z[1], 0, typesz * T * sizeof(double)));
-    HIP_CHECK(hipMemset(w.S, 0, typesz * T * sizeof(double)));
-    HIP_CHECK(hipMemset(w.GY, 0, typesz * sizeof(double)));
-}
 
 SweepTypes make_types(int m, bool second_order) {
     SweepTypes ty{};
@@ -921,111 +411,6 @@ int run_sweep(dto_handle* h, BilHost& b, SweepBuf& w, const SweepTypes& ty, cons
         }
     }
     return launched;
-}
-
-// multisets of size r over {0..m} as sorted tuples, lexicographic
-void enum_multisets(int m1, int r, std::vector<int>& cur, int start, std::vector<std::vector<int>>& out) {
-    if ((int)cur.size() == r) { out.push_back(cur); return; }
-    for (int i = start; i < m1; ++i) {
-        cur.push_back(i);
-        enum_multisets(m1, r, cur, i, out);
-        cur.pop_back();
-    }
-}
-
-// S_alpha = sum over distinct first letters i of alpha of G_i * S_(alpha minus i): built once at create with
-// the engine's own batched GEMM (one product per (alpha, i)).
-void build_basis(dto_handle* h, BilHost& b, int cap) {
-    const int m1 = b.k.m + 1, npad = b.k.npad;
-    const size_t nn = (size_t)npad * npad;
-    std::vector<std::vector<std::vector<int>>> sets(5);
-    std::vector<std::map<std::vector<int>, int>> index(5);
-    for (int r = 1; r <= 4; ++r) {
-        std::vector<int> cur;
-        enum_multisets(m1, r, cur, 0, sets[r]);
-        for (size_t a = 0; a < sets[r].size(); ++a) index[r][sets[r][a]] = (int)a;
-    }
-    double* tmp = own(h, dalloc<double>(nn));
-    std::vector<double*> S(5, nullptr);
-    S[1] = const_cast<double*>(b.k.G);
-    for (int r = 2; r <= 4; ++r) {
-        const int cnt = (int)sets[r].size(), cntpad = ((cnt + 15) / 16) * 16;
-        S[r] = own(h, dalloc<double>(nn * cntpad));
-        HIP_CHECK(hipMemsetAsync(S[r], 0, nn * cntpad * sizeof(double), h->stream));
-        std::vector<int32_t> idx;
-        for (int a = 0; a < cnt; ++a) {
-            const std::vector<int>& al = sets[r][a];
-            for (int v : al) idx.push_back(v);
-            int last = -1;
-            for (size_t p = 0; p < al.size(); ++p) {
-                const int i = al[p];
-                if (i == last) continue;  // distinct first letters only
-                last = i;
-                std::vector<int> rest = al;
-                rest.erase(rest.begin() + p);
-                const double* prev = S[r - 1] + (size_t)index[r - 1][rest] * nn;
-                launch_bgemm_plain(h->stream, npad, 1, b.k.G + (size_t)i * nn, prev, tmp);
-                launch_add(h->stream, S[r] + (size_t)a * nn, tmp, (int64_t)nn);
-            }
-        }
-        BasisSet& bs = b.basis[r - 2];
-        bs.r = r; bs.cnt = cnt; bs.cntpad = cntpad; bs.S = S[r];
-        bs.idx = own(h, dupload(idx));
-        const int cappad = ((cap + 127) / 128) * 128;
-        bs.coef = own(h, dalloc<double>((size_t)cappad * cntpad));
-    }
-    {
-        // concatenation [I | G_0..G_m | S2 | S3 | S4] for the factor K
-        int cnt = 1 + m1;
-        for (int r = 2; r <= 4; ++r) cnt += (int)sets[r].size();
-        const int cntpad = ((cnt + 15) / 16) * 16;
-        double* Sall = own(h, dalloc<double>(nn * cntpad));
-        HIP_CHECK(hipMemsetAsync(Sall, 0, nn * cntpad * sizeof(double), h->stream));
-        std::vector<double> eye(nn, 0.0);
-        for (int i = 0; i < b.k.n; ++i) eye[(size_t)i * npad + i] = 1.0;  // identity on the un-padded block only
-        HIP_CHECK(hipMemcpyAsync(Sall, eye.data(), nn * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-        std::vector<int32_t> idx;
-        size_t col = 1;
-        for (int q = 0; q < 4; ++q) idx.push_back(-1);
-        for (int r = 1; r <= 4; ++r) {
-            HIP_CHECK(hipMemcpyAsync(Sall + col * nn, S[r], nn * sets[r].size() * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            col += sets[r].size();
-            for (auto& al : sets[r]) {
-                for (int q = 0; q < 4; ++q) idx.push_back(q < r ? al[q] : -1);
-            }
-        }
-        BasisSet& bs = b.basis_all;
-        bs.r = 4; bs.cnt = cnt; bs.cntpad = cntpad; bs.S = Sall;
-        bs.idx = own(h, dupload(idx));
-        const int cappad = ((cap + 127) / 128) * 128;
-        bs.coef = own(h, dalloc<double>((size_t)cappad * cntpad));
-    }
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    b.use_basis = true;
-}
-
-void alloc_chain(dto_handle* h, BilHost& b, int cap) {
-    const size_t nn = (size_t)b.k.npad * b.k.npad;
-    for (int i = 0; i < 9; ++i) b.chain.W[i] = own(h, dalloc<double>(nn * cap));
-    b.chain.norms = own(h, dalloc<double>((size_t)cap * 4));
-    b.chain.colsum = own(h, dalloc<double>((size_t)3 * cap * b.k.npad * (b.k.npad / 64)));  // [set][interval][column][64-row chunk]
-    if (!b.d_hump) b.d_hump = own(h, dalloc<unsigned long long>(8));
-    b.chain.coef = own(h, dalloc<double>((size_t)cap * COEF_STRIDE));
-    b.chain.s = own(h, dalloc<int32_t>(cap));
-    b.chain.s3 = own(h, dalloc<int32_t>(cap));
-    b.chain.smax = own(h, dalloc<int32_t>(8));
-    HIP_CHECK(hipMemset(b.chain.smax, 0, 8 * sizeof(int32_t)));
-    b.chain.d2max = reinterpret_cast<unsigned long long*>(b.chain.smax + 2);
-    b.chain_cap = cap;
-}
-
-int chunk_size(const dto_handle* h, int npad) {
-    // workspace budget for the 9 chain matrices (option "chain_chunk" lowers the chunk per call)
-    const double budget = 40e9;   // (1024 states x 500 knots, the configs[4] share, in ONE chunk: 37.7 GB)
-    int c = (int)(budget / (9.0 * npad * (double)npad * 8.0));
-    c = std::max(8, (c / 8) * 8);
-    return (int)std::min<int64_t>(c, std::max<int64_t>(h->P.n_int, 1));
 }
 
 // exp(dt G(u_k)) for every owned interval; -E_k goes straight into the Jacobian slab.
@@ -2389,683 +1774,6 @@ extern "C" {
 const char* dto_last_error(const dto_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 void dto_destroy(dto_handle* h) { delete h; }
-
-int dto_create(const dto_problem_desc* d, dto_handle** out) {
-    if (!d || !out) return fail(nullptr, "dto_create: null argument");
-    *out = nullptr;
-    if (d->abi_version != DTO_ABI_VERSION) return fail(nullptr, "dto_create: ABI version mismatch");
-    if (d->N < 2) return fail(nullptr, "dto_create: need at least 2 knots");
-    if (d->z < 1 || d->gd < 0) return fail(nullptr, "dto_create: bad dimensions");
-    if (d->dt_idx < 0 || d->dt_idx >= d->z)
-        return fail(nullptr, "dto_create: the timestep must be a trajectory component (bilinear_integrator.jl:123)");
-    if (!d->Z0) return fail(nullptr, "dto_create: Z0 is required (constraint patterns are taken at Z0)");
-    const bool sonly = d->device < 0;  // structure-only handle: no GPU is touched, evaluations fail
-    if (!sonly) {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-            return fail(nullptr, "dto_create: no HIP device available (the engine has no CPU fallback)");
-        if (d->device >= ndev) return fail(nullptr, "dto_create: bad device ordinal");
-    }
-
-    dto_handle* h = new dto_handle();
-    try {
-        h->device = d->device;
-        h->structure_only = sonly;
-        if (!sonly) {
-            HIP_CHECK(hipSetDevice(h->device));
-            HIP_CHECK(hipStreamCreate(&h->stream));
-            HIP_CHECK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-            HIP_CHECK(hipStreamCreateWithFlags(&h->stream_rb, hipStreamNonBlocking));
-            HIP_CHECK(hipEventCreateWithFlags(&h->ev_rb, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&h->ev_zero, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&h->ev_stats, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&h->ev_chain, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
-            HIP_CHECK(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
-            HIP_CHECK(sweep_fused_prepare());
-            HIP_CHECK(sweep_cluster_prepare());
-            HIP_CHECK(sweep_gs_prepare());
-            HIP_CHECK(chain64_prepare());
-        }
-        h->N = d->N; h->K = d->N - 1; h->z = d->z; h->gd = d->gd; h->dt_idx = d->dt_idx;
-        h->eval_hessian = d->eval_hessian;
-        h->n_vars = (int64_t)d->z * d->N + d->gd;
-        h->k_lo = d->k_lo > 0 ? d->k_lo : 1;
-        h->k_hi = d->k_hi > 0 ? d->k_hi : d->N;
-        if (h->k_lo > h->k_hi || h->k_hi > h->N) throw HipError{"dto_create: bad knot shard"};
-
-        // integrators: rows stacked in list order (evaluator.jl:211-217)
-        int pre = 0;
-        int64_t row = 0;
-        for (int i = 0; i < d->n_integrators; ++i) {
-            const dto_integrator_desc& s = d->integrators[i];
-            if (s.x_dim < 1 || (s.kind != DTO_INTEGRATOR_EXTERNAL && (s.x_off < 0 || s.x_off + s.x_dim > d->z)))
-                throw HipError{"integrator: bad state range"};
-            h->integ_kind.push_back(s.kind);
-            h->integ_dim.push_back(s.x_dim);
-            h->integ_row_off.push_back(row);
-            if (s.kind == DTO_INTEGRATOR_BILINEAR) {
-                if (s.u_dim < 0 || s.u_dim > MAX_DRIVES) throw HipError{"bilinear integrator: supports 0..7 drives"};
-                if (s.u_dim > 0 && (s.u_off < 0 || s.u_off + s.u_dim > d->z)) throw HipError{"bilinear integrator: bad control range"};
-                if (!s.G) throw HipError{"bilinear integrator: G is null"};
-                BilHost b;
-                b.k.n = s.x_dim; b.k.m = s.u_dim; b.k.npad = pad64(s.x_dim);
-                b.k.x_off = s.x_off; b.k.u_off = s.u_off; b.k.pre = pre; b.k.row_off = row;
-                const int n = s.x_dim, np = b.k.npad, m1 = s.u_dim + 1;
-                // (+ 16 zero columns: the fused sweep streams the generators a few k-steps ahead, past the last one)
-                std::vector<double> G((size_t)m1 * np * np + 16 * (size_t)np, 0.0), GT((size_t)m1 * np * np + 16 * (size_t)np, 0.0);
-                b.g1.assign(m1, 0.0);
-                for (int j = 0; j < m1; ++j)
-                    for (int c = 0; c < n; ++c) {
-                        double cs = 0.0;
-                        for (int r = 0; r < n; ++r) {
-                            const double v = s.G[(size_t)j * n * n + (size_t)c * n + r];
-                            G[(size_t)j * np * np + (size_t)c * np + r] = v;
-                            GT[(size_t)j * np * np + (size_t)r * np + c] = v;
-                            cs += std::fabs(v);
-                        }
-                        b.g1[j] = std::max(b.g1[j], cs);
-                    }
-                b.kb = n; b.kr = 1;
-                if (d->flags & DTO_FLAG_BLOCK_GENERATORS) {
-                    b.kr = find_replicas(s.G, n, m1);
-                    b.kb = n / b.kr;
-                    KKron& kk = b.kk;
-                    kk.b = b.kb; kk.r = b.kr;
-                    // blocks below 16 rows are grouped while the group fits one MFMA row tile (I_g (x) B is a replicated block too)
-                    int grp = 1;
-                    if (b.kb < 16)
-                        for (int c = 1; c <= b.kr; ++c)
-                            if (b.kr % c == 0 && c * b.kb <= 16) grp = c;
-                    kk.bw = grp * b.kb; kk.rw = b.kr / grp; kk.bp = (kk.bw + 15) / 16 * 16;
-                    // the structured kernel gives every Hessian entry of the block one writer: state, controls and timestep apart
-                    const bool apart = (s.u_dim == 0 || s.u_off + s.u_dim <= s.x_off || s.u_off >= s.x_off + n) &&
-                                       (d->dt_idx < s.x_off || d->dt_idx >= s.x_off + n) &&
-                                       (s.u_dim == 0 || d->dt_idx < s.u_off || d->dt_idx >= s.u_off + s.u_dim);
-                    b.kron = b.kr >= 2 && b.kb <= 64 && n > 32 && apart && kron_supported(kk, s.u_dim, d->eval_hessian != 0);
-                }
-                if (!sonly && b.kron) {
-                    const int bp = b.kk.bp, bw = b.kk.bw;
-                    std::vector<double> Bm((size_t)m1 * bp * bp, 0.0), BmT((size_t)m1 * bp * bp, 0.0);
-                    for (int j = 0; j < m1; ++j)
-                        for (int c = 0; c < bw; ++c)
-                            for (int r = 0; r < bw; ++r) {
-                                const double v = s.G[(size_t)j * n * n + (size_t)c * n + r];
-                                Bm[(size_t)j * bp * bp + (size_t)c * bp + r] = v;
-                                BmT[(size_t)j * bp * bp + (size_t)r * bp + c] = v;
-                            }
-                    b.kk.Bm = own(h, dupload(Bm));
-                    b.kk.BmT = own(h, dupload(BmT));
-                    HIP_CHECK(kron_prepare());
-                } else if (!sonly) {
-                    b.k.G = own(h, dupload(G));
-                    b.k.GT = own(h, dupload(GT));
-                    const int mm_ = s.u_dim, Tf = d->eval_hessian ? 1 + mm_ + mm_ * (mm_ + 1) / 2 : 1 + mm_;
-                    if (small_path_serves(d->flags, d->eval_hessian, n, mm_)) {
-                        b.small = true;
-                        // worst-case dynamic LDS of this handle's fused kernel, opted into on THIS device
-                        HIP_CHECK(small_prepare(small_lds_bytes(n, mm_, Tf, 1 + mm_)));
-                        b.d_Gs = own(h, dupload(std::vector<double>(s.G, s.G + (size_t)m1 * n * n)));
-                    }
-                }
-                h->integ_index.push_back((int)h->bil.size());
-                h->bil.push_back(std::move(b));
-            } else if (s.kind == DTO_INTEGRATOR_DERIVATIVE) {
-                if (s.u_off < 0 || s.u_off + s.x_dim > d->z) throw HipError{"derivative integrator: bad derivative range"};
-                KDer k{};
-                k.d = s.x_dim; k.x_off = s.x_off; k.xdot_off = s.u_off; k.pre = pre; k.row_off = row;
-                h->integ_index.push_back((int)h->der.size());
-                h->der.push_back(k);
-            } else if (s.kind == DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) {
-                if (s.u_dim < 0 || s.u_dim > MAX_DRIVES) throw HipError{"time-dependent bilinear integrator: supports 0..7 drives"};
-                if (s.u_dim > 0 && (s.u_off < 0 || s.u_off + s.u_dim > d->z)) throw HipError{"time-dependent bilinear integrator: bad control range"};
-                if (s.t_off < 0 || s.t_off >= d->z) throw HipError{"time-dependent bilinear integrator: bad time component"};
-                if (s.spline_order != 0 && s.spline_order != 1) throw HipError{"Unsupported spline order (0 or 1)"};
-                if (!s.G || (s.n_mod > 0 && (!s.H || !s.mod_kind || !s.mod_omega))) throw HipError{"time-dependent bilinear integrator: G / H / modulation arrays are null"};
-                TdbHost t;
-                t.k.n = s.x_dim; t.k.m = s.u_dim; t.k.x_off = s.x_off; t.k.u_off = s.u_off; t.k.t_off = s.t_off;
-                t.k.order = s.spline_order; t.k.substeps = s.substeps; t.k.nmod = s.n_mod; t.k.row_off = row;
-                // 1..64 states: k_tdb; 65..256 states: k_tdb_mfma; the refusal names the limit that was hit
-                if (const char* why = tdb_mfma_refusal(t.k)) throw HipError{why};
-                t.mfma = tdb_mfma_supported(t.k);
-                if (!t.mfma && !tdb_supported(t.k)) throw HipError{"time-dependent bilinear integrator: outside the device kernels' range (1..256 states, substeps >= 1, coefficient table)"};
-                for (int c = 0; c < s.n_mod; ++c)
-                    if (s.mod_kind[c] != 1 && s.mod_kind[c] != 2) throw HipError{"time-dependent bilinear integrator: mod_kind is 1 (cos) or 2 (sin)"};
-                t.place.d = s.x_dim; t.place.pre = pre; t.place.row_off = row;
-                if (!sonly) {
-                    const size_t nn = (size_t)s.x_dim * s.x_dim, m1 = (size_t)s.u_dim + 1;
-                    t.k.G = own(h, dupload(std::vector<double>(s.G, s.G + m1 * nn)));
-                    if (s.n_mod > 0) {
-                        t.k.H = own(h, dupload(std::vector<double>(s.H, s.H + (size_t)s.n_mod * m1 * nn)));
-                        t.k.mod_kind = own(h, dupload(std::vector<int32_t>(s.mod_kind, s.mod_kind + s.n_mod)));
-                        t.k.mod_omega = own(h, dupload(std::vector<double>(s.mod_omega, s.mod_omega + s.n_mod)));
-                    }
-                    if (t.mfma) {
-                        // B_q, q = j (1 + n_mod) + c (c = 0: G_j, c >= 1: H_{c-1, j}), zero-padded, and their transposes
-                        const size_t n_ = (size_t)s.x_dim, np_ = (size_t)tdb_mfma_npad(s.x_dim), nm1 = (size_t)s.n_mod + 1;
-                        std::vector<double> Bp(m1 * nm1 * np_ * np_, 0.0), BpT(Bp.size(), 0.0);
-                        for (size_t j = 0; j < m1; ++j)
-                            for (size_t c = 0; c < nm1; ++c) {
-                                const double* src = c == 0 ? s.G + j * nn : s.H + ((c - 1) * m1 + j) * nn;
-                                double* dst = Bp.data() + (j * nm1 + c) * np_ * np_;
-                                double* dstT = BpT.data() + (j * nm1 + c) * np_ * np_;
-                                for (size_t col = 0; col < n_; ++col)
-                                    for (size_t r = 0; r < n_; ++r) {
-                                        dst[col * np_ + r] = src[col * n_ + r];
-                                        dstT[r * np_ + col] = src[col * n_ + r];
-                                    }
-                            }
-                        t.d_Bp = own(h, dupload(Bp));
-                        t.d_BpT = own(h, dupload(BpT));
-                    }
-                }
-                h->integ_index.push_back((int)h->tdb.size());
-                h->tdb.push_back(t);
-            } else if (s.kind == DTO_INTEGRATOR_EXTERNAL) {
-                KExtInt e{};
-                e.d = s.x_dim; e.pre = pre; e.row_off = row;
-                h->integ_index.push_back((int)h->ext_int.size());
-                h->ext_int.push_back(e);
-                ExtSlot sl;
-                sl.len[0] = (size_t)s.x_dim * h->K;
-                sl.len[1] = (size_t)s.x_dim * 2 * d->z * h->K;
-                sl.len[2] = (size_t)4 * d->z * d->z * h->K;
-                h->ext.push_back(sl);
-            } else {
-                throw HipError{"unknown integrator kind"};
-            }
-            pre += s.x_dim;
-            row += (int64_t)s.x_dim * h->K;
-        }
-        h->D = pre;
-        h->n_dyn = row;
-        h->n_ext_int = (int)h->ext_int.size();
-        find_share_groups(h, d);
-        if (h->integ_kind.size() > 8) throw HipError{"at most 8 integrators"};
-
-        // nonlinear knot constraints: rows follow the dynamics (evaluator.jl:219-223)
-        for (int i = 0; i < d->n_constraints; ++i) {
-            const dto_constraint_desc& s = d->constraints[i];
-            if (s.kind != DTO_CONSTRAINT_NORM_MINUS_C && s.kind != DTO_CONSTRAINT_SQNORM_MINUS_C && s.kind != DTO_CONSTRAINT_EXTERNAL &&
-                s.kind != DTO_CONSTRAINT_EXTERNAL_GLOBAL && s.kind != DTO_CONSTRAINT_QUADFORM_MINUS_C)
-                throw HipError{"unknown constraint kind"};
-            if (s.kind == DTO_CONSTRAINT_EXTERNAL_GLOBAL) {
-                // NonlinearGlobalConstraint: one listing at the pseudo-knot N whose "components" are global_data entries
-                if (s.n_comps < 1 || !s.comps || s.g_dim < 1 || !s.jac0 || !s.hess0)
-                    throw HipError{"global constraint: comps, g_dim, jac0 and hess0 are required"};
-                ConHost c;
-                c.k.kind = s.kind; c.k.n_comps = s.n_comps; c.equality = s.equality;
-                c.external = true; c.global = true; c.g_dim = s.g_dim;
-                c.k.g_dim = c.g_dim; c.k.external = 1;
-                c.comps.assign(s.comps, s.comps + s.n_comps);
-                for (int q : c.comps)
-                    if (q < 0 || q >= d->gd) throw HipError{"global constraint: global component out of range"};
-                c.jac0.assign(s.jac0, s.jac0 + (size_t)s.g_dim * s.n_comps);
-                c.hess0.assign(s.hess0, s.hess0 + (size_t)s.n_comps * s.n_comps);
-                c.n_times_total = 1;
-                c.times0.push_back(d->N);
-                c.row_off = row;
-                row += c.g_dim;
-                h->con.push_back(std::move(c));
-                continue;
-            }
-            if (s.n_comps < 1 || !s.comps || (!s.times && s.n_times > 0)) throw HipError{"constraint: bad description"};
-            ConHost c;
-            c.k.kind = s.kind; c.k.n_comps = s.n_comps; c.k.c = s.c;
-            c.equality = s.equality;
-            if (s.kind == DTO_CONSTRAINT_EXTERNAL) {
-                if (s.g_dim < 1) throw HipError{"external constraint: g_dim must be >= 1"};
-                if (!s.jac0) throw HipError{"external constraint: jac0 (Jacobian blocks at Z0) is required for the sparsity pattern"};
-                c.external = true;
-                c.g_dim = s.g_dim;
-                c.jac0.assign(s.jac0, s.jac0 + (size_t)s.g_dim * s.n_comps * s.n_times);
-            } else if (s.g_dim > 1) {
-                throw HipError{"constraint: the built-in kinds have g_dim = 1"};
-            }
-            c.k.g_dim = c.g_dim; c.k.external = c.external ? 1 : 0;
-            c.comps.assign(s.comps, s.comps + s.n_comps);
-            for (int q : c.comps)
-                if (q < 0 || q >= d->z) throw HipError{"constraint: component out of range"};
-            if (s.kind == DTO_CONSTRAINT_QUADFORM_MINUS_C) {
-                if (!s.hess0) throw HipError{"quadratic-form constraint: the matrix M (hess0, n_comps x n_comps) is required"};
-                const size_t n = (size_t)s.n_comps;
-                std::vector<int32_t> sc = c.comps;
-                std::sort(sc.begin(), sc.end());
-                if (std::adjacent_find(sc.begin(), sc.end()) != sc.end())
-                    throw HipError{"quadratic-form constraint: a component is listed twice in comps"};
-                c.M.assign(s.hess0, s.hess0 + n * n);
-                for (size_t a = 0; a < n; ++a)
-                    for (size_t b2 = a + 1; b2 < n; ++b2)
-                        if (!(c.M[a + n * b2] == c.M[b2 + n * a])) throw HipError{"quadratic-form constraint: M is not symmetric"};
-            }
-            c.n_times_total = s.n_times;
-            for (int64_t t = 0; t < s.n_times; ++t) {
-                if (s.times[t] < 1 || s.times[t] > d->N) throw HipError{"constraint: time out of range"};
-                c.times0.push_back(s.times[t] - 1);
-            }
-            c.row_off = row;
-            row += s.n_times * c.g_dim;
-            h->con.push_back(std::move(c));
-        }
-        h->n_cons = row;
-        for (auto& c : h->con)
-            if (c.external) {
-                c.ext_slot = (int)h->ext.size();  // after the external integrators
-                ExtSlot e;
-                e.len[0] = (size_t)c.g_dim * c.n_times_total;
-                e.len[1] = (size_t)c.g_dim * c.comps.size() * c.n_times_total;
-                e.len[2] = c.comps.size() * c.comps.size() * (size_t)c.n_times_total;
-                h->ext.push_back(e);
-            }
-        h->n_ext_con = (int)h->ext.size() - h->n_ext_int;
-        // host-evaluated objective terms: their slots follow, and the Global* ones shape the Hessian structure
-        for (int i = 0; i < d->n_objectives; ++i) {
-            const dto_objective_desc& s = d->objectives[i];
-            if (s.kind != DTO_OBJECTIVE_EXTERNAL_KNOT && s.kind != DTO_OBJECTIVE_EXTERNAL_GLOBAL) continue;
-            ExtObjHost e;
-            e.weight = s.weight;
-            e.global = s.kind == DTO_OBJECTIVE_EXTERNAL_GLOBAL;
-            if (s.n_comps > 0) {
-                if (!s.comps) throw HipError{"external objective: comps is null"};
-                e.comps.assign(s.comps, s.comps + s.n_comps);
-            }
-            for (int q : e.comps)
-                if (q < 0 || q >= d->z) throw HipError{"external objective: component out of range"};
-            if (e.global) {
-                if (s.n_gcomps < 1 || !s.gcomps) throw HipError{"global objective: gcomps are required"};
-                e.gcomps.assign(s.gcomps, s.gcomps + s.n_gcomps);
-                for (int q : e.gcomps)
-                    if (q < 0 || q >= d->gd) throw HipError{"global objective: global component out of range"};
-            } else if (e.comps.empty() || !s.times) {
-                throw HipError{"external knot objective: comps and times are required"};
-            }
-            if (s.n_times > 0 && !s.times) throw HipError{"external objective: times is null"};
-            for (int64_t t = 0; t < s.n_times; ++t) {
-                if (s.times[t] < 1 || s.times[t] > d->N) throw HipError{"objective: time out of range"};
-                e.times0.push_back(s.times[t] - 1);
-            }
-            if (e.times0.empty()) {  // GlobalObjective: the global variables alone
-                if (!e.comps.empty()) throw HipError{"global objective: knot components without times"};
-                e.times0.push_back(d->N);
-            }
-            const size_t nb = e.comps.size() + e.gcomps.size(), nl = e.times0.size();
-            e.ext_slot = (int)h->ext.size();
-            ExtSlot sl;
-            sl.len[0] = nl; sl.len[1] = nb * nl; sl.len[2] = nb * nb * nl;
-            h->ext.push_back(sl);
-            h->ext_obj.push_back(std::move(e));
-        }
-        h->n_ext_obj = (int)h->ext_obj.size();
-
-        // shard
-        KProb& P = h->P;
-        P.N = h->N; P.K = h->K; P.z = h->z; P.dt_idx = h->dt_idx; P.D = h->D;
-        P.kn_lo = h->k_lo - 1;
-        P.n_knots = h->k_hi - h->k_lo + 1;
-        P.n_int = std::max<int64_t>(0, std::min<int64_t>(h->k_hi, h->K) - h->k_lo + 1);
-
-        build_structure(h, d->Z0);
-        if (!sonly) {
-            h->d_colptr = own(h, dupload(h->colptr));
-            P.colptr = h->d_colptr;
-        }
-        const ShardExtents ext = shard_extents(h, h->k_lo, h->k_hi);
-        P.jac_lo = ext.jac_lo;
-        P.hess_lo = ext.hess_lo;
-        P.grad_lo = ext.grad_lo;
-        dto_shard_info& I = h->info;
-        I.k_lo = h->k_lo; I.k_hi = h->k_hi;
-        I.n_vars = h->n_vars; I.n_cons = h->n_cons; I.jac_nnz = h->jac_nnz; I.hess_nnz = h->hess_nnz;
-        I.grad_lo = ext.grad_lo; I.grad_len = ext.grad_len;
-        I.jac_lo = ext.jac_lo; I.jac_len = ext.jac_len;      // global columns ride with the last knot
-        I.hess_lo = ext.hess_lo; I.hess_len = ext.hess_len;
-        P.tail_lo = h->k_hi == h->N ? h->hess_block_nnz - P.hess_lo : -1;
-        if (!sonly) {
-            P.tail_colptr = own(h, dupload(h->tail_colptr));
-            P.tail_rows = own(h, dupload(h->tail_rows));
-        }
-
-        // local constraint rows: integrators first, then constraints
-        int64_t lrow = 0;
-        for (size_t i = 0; i < h->integ_kind.size(); ++i) {
-            const int dd = h->integ_dim[i];
-            if (h->integ_kind[i] == DTO_INTEGRATOR_BILINEAR) h->bil[h->integ_index[i]].k.lrow_off = lrow;
-            else if (h->integ_kind[i] == DTO_INTEGRATOR_DERIVATIVE) h->der[h->integ_index[i]].lrow_off = lrow;
-            else if (h->integ_kind[i] == DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) h->tdb[h->integ_index[i]].place.lrow_off = lrow;
-            else h->ext_int[h->integ_index[i]].lrow_off = lrow;
-            lrow += P.n_int * dd;
-        }
-        for (auto& c : h->con) {
-            std::vector<int64_t> times, lrows, tidx, jpos;
-            std::vector<int32_t> hess_on;
-            for (int64_t i = 0; i < c.n_times_total; ++i) {
-                const int64_t kn = c.times0[i];
-                if (kn >= h->N ? h->k_hi != h->N : (kn < P.kn_lo || kn >= P.kn_lo + P.n_knots)) continue;  // pseudo-knot N: last rank
-                times.push_back(kn);
-                lrows.push_back(lrow);
-                lrow += c.g_dim;
-                tidx.push_back(i);
-                {
-                    int32_t last = 1;
-                    for (int64_t i2 = i + 1; i2 < c.n_times_total; ++i2)
-                        if (c.times0[i2] == kn) { last = 0; break; }
-                    hess_on.push_back(last);
-                }
-                for (size_t q = 0; q < c.comps.size(); ++q) {
-                    const int64_t col = kn * h->z + c.comps[q];
-                    const size_t lo = con_lower(h, col);
-                    for (int r = 0; r < c.g_dim; ++r) {
-                        int64_t pos = -1;
-                        for (size_t e = lo; e < h->con_cols.size() && h->con_cols[e] == col; ++e)
-                            if (h->con_rows[e] == c.row_off + i * c.g_dim + r) {
-                                pos = h->colptr[col] + (int64_t)h->D * col_cnt(h, kn) + (int64_t)(e - lo) - P.jac_lo;
-                                break;
-                            }
-                        jpos.push_back(pos);
-                    }
-                }
-            }
-            c.k.n_times = (int64_t)times.size();
-            c.k.mu_off = c.row_off;
-            {
-                std::vector<int64_t> st = times;
-                std::sort(st.begin(), st.end());
-                c.k.repeats = std::adjacent_find(st.begin(), st.end()) != st.end() ? 1 : 0;
-                std::vector<int32_t> sc = c.comps;
-                std::sort(sc.begin(), sc.end());
-                c.k.comp_repeats = std::adjacent_find(sc.begin(), sc.end()) != sc.end() ? 1 : 0;
-            }
-            if (!sonly) {
-                c.k.comps = own(h, dupload(c.comps));
-                c.k.times = own(h, dupload(times));
-                c.k.lrow = own(h, dupload(lrows));
-                c.k.tidx = own(h, dupload(tidx));
-                c.k.hess_on = own(h, dupload(hess_on));
-                c.k.jpos = own(h, dupload(jpos));
-                if (!c.M.empty()) c.k.M = own(h, dupload(c.M));
-                if (c.external) {  // Hessian blocks: knot constraints place knot entries, the global one tail entries
-                    c.xk.nc = c.global ? 0 : (int32_t)c.comps.size();
-                    c.xk.ng = c.global ? (int32_t)c.comps.size() : 0;
-                    c.xk.comps = c.k.comps; c.xk.gcomps = c.k.comps;
-                    c.xk.times = c.k.times; c.xk.tidx = c.k.tidx;
-                    c.xk.knot_on = c.k.hess_on; c.xk.count = c.k.hess_on;
-                    c.xk.glob_on = h->k_hi == h->N ? 1 : 0;
-                    c.xk.n_list = c.k.n_times;
-                }
-            }
-        }
-        h->row_segments = shard_row_segments(h, h->k_lo, h->k_hi);  // the local buffer is their concatenation, in this order
-        h->cons_len = lrow;
-        I.cons_len = lrow;
-        I.n_row_segments = (int32_t)h->row_segments.size();
-
-        // objectives
-        for (int i = 0; i < d->n_objectives && !sonly; ++i) {
-            const dto_objective_desc& s = d->objectives[i];
-            KObj o{};
-            o.kind = s.kind; o.weight = s.weight; o.D = s.D;
-            std::vector<int64_t> times;
-            std::vector<int64_t> layer_start;
-            // stable order of the listings by layer (occurrence index of their knot); returns the permutation
-            auto layer_order = [&](const std::vector<int64_t>& t) {
-                std::map<int64_t, int> seen;
-                std::vector<int> layer(t.size());
-                int nl = 0;
-                for (size_t q = 0; q < t.size(); ++q) { layer[q] = seen[t[q]]++; nl = std::max(nl, layer[q] + 1); }
-                std::vector<size_t> perm(t.size());
-                for (size_t q = 0; q < perm.size(); ++q) perm[q] = q;
-                std::stable_sort(perm.begin(), perm.end(), [&](size_t a, size_t b2) { return layer[a] < layer[b2]; });
-                layer_start.assign((size_t)nl + 1, 0);
-                for (size_t q = 0; q < t.size(); ++q) layer_start[(size_t)layer[q] + 1]++;
-                for (int l = 0; l < nl; ++l) layer_start[(size_t)l + 1] += layer_start[(size_t)l];
-                if (t.empty()) layer_start.assign(1, 0);
-                return perm;
-            };
-            auto permute = [&](auto& v, const std::vector<size_t>& perm, size_t width) {
-                if (v.empty()) return;
-                auto src = v;
-                for (size_t q = 0; q < perm.size(); ++q)
-                    for (size_t c = 0; c < width; ++c) v[q * width + c] = src[perm[q] * width + c];
-            };
-            if (s.kind == DTO_OBJECTIVE_MINIMUM_TIME) {
-                for (int64_t kn = P.kn_lo; kn < P.kn_lo + P.n_knots; ++kn)
-                    if (kn < h->K) times.push_back(kn);
-                (void)layer_order(times);
-            } else if (s.kind == DTO_OBJECTIVE_QUADRATIC_REGULARIZER || s.kind == DTO_OBJECTIVE_LINEAR_REGULARIZER) {
-                if (s.comp_dim < 1 || s.comp_off < 0 || s.comp_off + s.comp_dim > d->z || !s.R)
-                    throw HipError{"objective: bad component range"};
-                o.comp_off = s.comp_off; o.comp_dim = s.comp_dim;
-                o.R = own(h, dupload(std::vector<double>(s.R, s.R + s.comp_dim)));
-                if (s.baseline && s.kind == DTO_OBJECTIVE_QUADRATIC_REGULARIZER) {
-                    o.has_baseline = 1;
-                    o.baseline = own(h, dupload(std::vector<double>(s.baseline, s.baseline + (size_t)s.comp_dim * d->N)));
-                }
-                if (s.times) {
-                    for (int64_t t = 0; t < s.n_times; ++t) {
-                        if (s.times[t] < 1 || s.times[t] > d->N) throw HipError{"objective: time out of range"};
-                        const int64_t kn = s.times[t] - 1;
-                        if (kn >= P.kn_lo && kn < P.kn_lo + P.n_knots) times.push_back(kn);
-                    }
-                } else {
-                    for (int64_t kn = P.kn_lo; kn < P.kn_lo + P.n_knots; ++kn) times.push_back(kn);
-                }
-                permute(times, layer_order(times), 1);
-            } else if (s.kind == DTO_OBJECTIVE_KNOT_SQDIST || s.kind == DTO_OBJECTIVE_KNOT_LOWRANK_INFIDELITY) {
-                if (s.n_comps < 1 || !s.comps || !s.times) throw HipError{"knot objective: comps and times are required"};
-                if (s.kind == DTO_OBJECTIVE_KNOT_LOWRANK_INFIDELITY) {
-                    if (s.comp_dim < 1 || !s.R) throw HipError{"low-rank infidelity: the factor A (R) and its row count (comp_dim) are required"};
-                    o.comp_dim = s.comp_dim;
-                    o.R = own(h, dupload(std::vector<double>(s.R, s.R + (size_t)s.comp_dim * s.n_comps)));
-                }
-                std::vector<int32_t> comps(s.comps, s.comps + s.n_comps);
-                for (int q : comps)
-                    if (q < 0 || q >= d->z) throw HipError{"knot objective: component out of range"};
-                std::vector<double> params, Qs;
-                std::vector<int32_t> last;
-                for (int64_t t = 0; t < s.n_times; ++t) {
-                    if (s.times[t] < 1 || s.times[t] > d->N) throw HipError{"objective: time out of range"};
-                    const int64_t kn = s.times[t] - 1;
-                    if (kn < P.kn_lo || kn >= P.kn_lo + P.n_knots) continue;
-                    times.push_back(kn);
-                    Qs.push_back(s.Qs ? s.Qs[t] : 1.0);
-                    if (s.params) params.insert(params.end(), s.params + (size_t)t * s.n_comps, s.params + (size_t)(t + 1) * s.n_comps);
-                    int32_t is_last = 1;
-                    for (int64_t t2 = t + 1; t2 < s.n_times; ++t2)
-                        if (s.times[t2] == s.times[t]) { is_last = 0; break; }
-                    last.push_back(is_last);
-                }
-                {
-                    const std::vector<size_t> perm = layer_order(times);
-                    permute(times, perm, 1);
-                    permute(Qs, perm, 1);
-                    permute(last, perm, 1);
-                    permute(params, perm, (size_t)s.n_comps);
-                }
-                o.n_comps = s.n_comps;
-                o.comps = own(h, dupload(comps));
-                o.Qs = own(h, dupload(Qs));
-                o.last = own(h, dupload(last));
-                o.params = s.params ? own(h, dupload(params)) : nullptr;
-            } else if (s.kind == DTO_OBJECTIVE_EXTERNAL_KNOT || s.kind == DTO_OBJECTIVE_EXTERNAL_GLOBAL) {
-                continue;  // placed by the external-term kernels (set up below)
-            } else {
-                throw HipError{"unknown objective kind"};
-            }
-            o.n_times = (int64_t)times.size();
-            o.times = own(h, dupload(times));
-            h->obj.push_back(o);
-            dto_handle::ObjInfo oi;
-            oi.layer_start = layer_start;
-            oi.kind = s.kind; oi.comp_off = s.comp_off; oi.comp_dim = s.comp_dim; oi.times = times;
-            if (s.comps && s.n_comps > 0) oi.comps.assign(s.comps, s.comps + s.n_comps);
-            h->obj_info.push_back(std::move(oi));
-        }
-
-        // host-evaluated objective terms: which listings this handle places (knot part: the knot's owner; entries in
-        // global-variable columns and listings without a knot part: the rank that owns the last knot)
-        const bool last_rank = h->k_hi == h->N;
-        for (auto& e : h->ext_obj) {
-            std::vector<int64_t> times, tix;
-            std::vector<int32_t> knot_on, count;
-            for (size_t i = 0; i < e.times0.size(); ++i) {
-                const int64_t kn = e.times0[i];
-                const bool pseudo = kn >= h->N;
-                const bool own = pseudo ? last_rank : (kn >= P.kn_lo && kn < P.kn_lo + P.n_knots);
-                if (!own && !(e.global && last_rank)) continue;
-                int32_t on = own && !pseudo;
-                if (on && !e.global)  // KnotPointObjective's gradient!/hessian! overwrite per listing: the last one wins
-                    for (size_t i2 = i + 1; i2 < e.times0.size(); ++i2)
-                        if (e.times0[i2] == kn) { on = 0; break; }
-                times.push_back(kn);
-                tix.push_back((int64_t)i);
-                knot_on.push_back(on);
-                count.push_back(own ? 1 : 0);
-            }
-            e.k.nc = (int32_t)e.comps.size(); e.k.ng = (int32_t)e.gcomps.size();
-            e.k.n_list = (int64_t)times.size();
-            e.k.glob_on = last_rank ? 1 : 0;
-            if (!sonly) {
-                e.k.comps = own(h, dupload(e.comps));
-                e.k.gcomps = own(h, dupload(e.gcomps));
-                e.k.times = own(h, dupload(times));
-                e.k.tidx = own(h, dupload(tix));
-                e.k.knot_on = own(h, dupload(knot_on));
-                e.k.count = own(h, dupload(count));
-            }
-        }
-
-        if (sonly) {
-            *out = h;
-            return 0;
-        }
-        // scratch
-        h->d_Z = own(h, dalloc<double>(h->n_vars));
-        h->d_mu = own(h, dalloc<double>(std::max<int64_t>(h->n_cons, 1)));
-        h->d_partial = own(h, dalloc<double>(256));
-        h->d_f = own(h, dalloc<double>(1));
-        h->d_bounds = own(h, dalloc<double>(2));
-        h->d_plan = own(h, dalloc<int32_t>(4));
-        HIP_CHECK(hipHostMalloc((void**)&h->h_pinned, 32 * sizeof(double)));
-        HIP_CHECK(hipHostMalloc((void**)&h->h_stats, sizeof(int32_t) * 4 * std::max<size_t>(h->bil.size(), 1)));
-        memset(h->h_stats, 0, sizeof(int32_t) * 4 * std::max<size_t>(h->bil.size(), 1));
-
-        // device buffers of the time-dependent bilinear integrators: blocks indexed by the global interval (like the
-        // host-evaluated integrators' arrays), one scratch slab per interval this handle evaluates
-        for (auto& t : h->tdb) {
-            const size_t n = t.k.n, z = h->z, K = (size_t)h->K;
-            t.d_vals = own(h, dalloc<double>(K * n));
-            t.d_jac = own(h, dalloc<double>(K * n * 2 * z));
-            if (d->eval_hessian) t.d_hess = own(h, dalloc<double>(K * 4 * z * z));
-            if (t.mfma) {
-                // sized by the persistent grid (two workgroups per compute unit), not by the number of intervals
-                int cus = 0;
-                HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-                t.resident = (int)std::min<int64_t>(P.n_knots + 1, 2 * (int64_t)std::max(cus, 1));
-                t.stride = (std::max(tdb_mfma_scratch_doubles(t.k, 1), d->eval_hessian ? tdb_mfma_scratch_doubles(t.k, 2) : (size_t)0) + 1) & ~(size_t)1;
-                t.d_scratch = own(h, dalloc<double>(t.stride * (size_t)t.resident));
-                continue;
-            }
-            t.stride = (std::max(tdb_scratch_doubles(t.k, 1), d->eval_hessian ? tdb_scratch_doubles(t.k, 2) : (size_t)0) + 1) & ~(size_t)1;
-            t.d_scratch = own(h, dalloc<double>(t.stride * (size_t)(P.n_knots + 1)));
-        }
-        // per-bilinear workspaces + generator product norms (for the step-budget bounds)
-        for (auto& b : h->bil) {
-            const int m = b.k.m;
-            if (b.small) {
-                if (d->eval_hessian && 1 + m + m * (m + 1) / 2 > MAX_TYPES) throw HipError{"bilinear integrator: too many drives for second-order sweep"};
-                continue;  // the fused kernel needs no workspace
-            }
-            if (b.kron) {
-                // one term slab per owned interval; the statistics words sit where the sweeps' do (deferred error convention)
-                b.kron_stride = (std::max(kron_scratch_doubles(b.kk, m, 1), d->eval_hessian ? kron_scratch_doubles(b.kk, m, 2) : (size_t)0) + 1) & ~(size_t)1;
-                b.d_kron_scratch = own(h, dalloc<double>(b.kron_stride * (size_t)std::max<int64_t>(h->P.n_int, 1)));
-                b.kk.stats = own(h, dalloc<int32_t>(2));
-                HIP_CHECK(hipMemset(b.kk.stats, 0, 2 * sizeof(int32_t)));
-                b.fw.stats = b.kk.stats;
-                continue;
-            }
-            const int T_fw = std::max(2 + m, d->eval_hessian ? 1 + m + m * (m + 1) / 2 : 1 + m);  // +1: exp(A)w_x column of J w
-            if (T_fw > MAX_TYPES) throw HipError{"bilinear integrator: too many drives for the second-order sweep"};
-            alloc_sweep(h, b, b.fw, T_fw, d->eval_hessian != 0);  // W: G_l x for the Hessian's scalar blocks
-            if (d->eval_hessian) {
-                alloc_sweep(h, b, b.ad, 1 + m, true);
-                // pairing path: term stores for both sweeps + E_j*terms + Beta-weighted sums (skipped when they
-                // would take more than 40 % of the free HBM: the second-order sweep is then used)
-                // (80 terms: the step budget from the cheap norm bound of the 256 x 2000 benchmark is 66 -- with 64 the Hessian
-                // bought the exact norms, a store-less basis GEMM and two round trips, only to fit its budget into the store)
-                const int dcap = PAIR_DCAP, T1 = 1 + m;
-                const double bytes = (double)dcap * T1 * b.fw.Kpad * b.k.npad * 8.0;
-                static const bool pair_on = tune_int("DTO_HESS_PAIRING", 1) != 0;
-                size_t free_b = 0, total_b = 0;
-                HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-                if (pair_on && m >= 1 && bytes * (3.0 + 1.0 * m / T1) < 0.4 * (double)free_b) {
-                    const size_t store = (size_t)dcap * T1 * b.fw.Kpad * b.k.npad;
-                    for (SweepBuf* w : {&b.fw, &b.ad}) {
-                        w->Zt = own(h, dalloc<double>(store));
-                        w->dcap = dcap;
-                        // one entry per convergence block; the fused sweep's blocks are as small as one interval
-                        w->nterms = own(h, dalloc<int32_t>(w->Kpad));
-                        HIP_CHECK(hipMemset(w->nterms, 0, sizeof(int32_t) * w->Kpad));
-                        w->nterms_p = own(h, dalloc<int32_t>(w->Kpad));
-                        HIP_CHECK(hipMemset(w->nterms_p, 0, sizeof(int32_t) * w->Kpad));
-                    }
-                    b.EP = own(h, dalloc<double>((size_t)m * dcap * b.fw.Kpad * b.k.npad));  // G_j' U_a
-                    b.Upair = own(h, dalloc<double>(store));
-                    std::vector<double> bt(PAIR_DCAP * PAIR_DCAP);
-                    for (int a = 0; a < PAIR_DCAP; ++a)
-                        for (int c = 0; c < PAIR_DCAP; ++c)
-                            bt[a * PAIR_DCAP + c] = std::exp(std::lgamma(a + 1.0) + std::lgamma(c + 1.0) - std::lgamma(a + c + 2.0));
-                    b.d_Btab = own(h, dupload(bt));
-                    b.pairing = true;
-                }
-            }
-            const int npad = b.k.npad;
-            alloc_chain(h, b, std::max(chunk_size(h, npad), (m + 1) * (m + 1)));
-            // N2[i][j] = ||G_i G_j||_1 with the engine's own batched GEMM + norm kernels
-            const int m1 = m + 1, nb = m1 * m1;
-            const size_t nn = (size_t)npad * npad;
-            for (int i = 0; i < m1; ++i)
-                for (int j = 0; j < m1; ++j) {
-                    HIP_CHECK(hipMemcpyAsync(b.chain.W[0] + (size_t)(i * m1 + j) * nn, b.k.G + (size_t)i * nn, nn * 8, hipMemcpyDeviceToDevice, h->stream));
-                    HIP_CHECK(hipMemcpyAsync(b.chain.W[2] + (size_t)(i * m1 + j) * nn, b.k.G + (size_t)j * nn, nn * 8, hipMemcpyDeviceToDevice, h->stream));
-                }
-            launch_bgemm_plain(h->stream, npad, nb, b.chain.W[0], b.chain.W[2], b.chain.W[1]);
-            launch_norm1(h->stream, npad, nb, b.chain);
-            std::vector<double> norms((size_t)nb * 4);
-            HIP_CHECK(hipMemcpyAsync(norms.data(), b.chain.norms, norms.size() * 8, hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(hipStreamSynchronize(h->stream));
-            b.n2.resize(nb);
-            for (int i = 0; i < nb; ++i) b.n2[i] = norms[(size_t)i * 4 + 1];
-            b.d_g1 = own(h, dupload(b.g1));
-            b.d_n2 = own(h, dupload(b.n2));
-            // generator-subspace powers pay off while the number of symmetrised products stays well
-            // below the 3n columns the three GEMMs would process (DTO_BASIS_POWERS=0/1 overrides)
-            {
-                long cnt = 0;
-                long c2 = (long)m1 * (m1 + 1) / 2, c3 = c2 * (m1 + 2) / 3, c4 = c3 * (m1 + 3) / 4;
-                cnt = c2 + c3 + c4;
-                // (npad is a multiple of 64: npad^2 is a multiple of the kernel's 128-row tiles and every wave's 64 rows of
-                // vec(A^r) stay inside one matrix column, which is all k_basis_gemm's fused column sums need)
-                bool want = cnt * 2 <= 3L * npad;
-                { const int f = tune_int("DTO_BASIS_POWERS", -1); if (f >= 0) want = f != 0; }
-                if (want) build_basis(h, b, b.chain_cap);
-            }
-        }
-        HIP_CHECK(hipDeviceSynchronize());
-    } catch (const HipError& e) {
-        g_create_error = e.msg;
-        delete h;
-        return 1;
-    } catch (const std::exception& e) {
-        g_create_error = e.what();
-        delete h;
-        return 1;
-    }
-    *out = h;
-    return 0;
-}
 
 int dto_num_vars(const dto_handle* h, int64_t* out) { if (!h || !out) return 1; *out = h->n_vars; return 0; }
 int dto_num_cons(const dto_handle* h, int64_t* out) { if (!h || !out) return 1; *out = h->n_cons; return 0; }

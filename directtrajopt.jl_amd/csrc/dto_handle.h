@@ -1,0 +1,347 @@
+// dto_handle.h -- what the engine's translation units share: the handle behind the C ABI (dto_engine.h), the host-side records it
+// is made of, and the few helpers both creation (dto_create.cpp) and evaluation (dto_engine.cpp) call.  Private: not installed,
+// not included from include/dto_engine.h.
+#pragma once
+
+#include "../../include/dto_engine.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <functional>
+#include <memory>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "dto_comm.h"
+#include "dto_hostxfer.h"
+#include "dto_kernels.h"
+
+namespace dto {
+
+extern thread_local std::string g_create_error;  // dto_last_error(nullptr): why the last dto_create of this thread failed
+
+struct HipError {
+    std::string msg;
+};
+
+#define HIP_CHECK(expr)                                                                          \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess) {                                                                  \
+            char buf_[512];                                                                      \
+            snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                     __FILE__, __LINE__);                                                        \
+            throw HipError{buf_};                                                                \
+        }                                                                                        \
+    } while (0)
+
+template <class T>
+T* dalloc(size_t n) {
+    void* p = nullptr;
+    if (n == 0) n = 1;
+    HIP_CHECK(hipMalloc(&p, n * sizeof(T)));
+    return static_cast<T*>(p);
+}
+template <class T>
+T* dupload(const std::vector<T>& v) {
+    T* p = dalloc<T>(v.size());
+    if (!v.empty()) HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return p;
+}
+
+// Grow-only device workspace of a sweep form whose workgroups hand data to each other (ensure_sweep_work replaces both parts)
+struct SweepWork {
+    double* slab = nullptr;
+    unsigned* arrive = nullptr;
+    size_t cap = 0;     // doubles in slab
+    int counters = 0;   // interval groups (generator-stationary) or clusters (row-split) the counters serve
+};
+
+struct BilHost {
+    KBil k;
+    SweepBuf fw{}, ad{};
+    int T_alloc = 0;
+    std::vector<double> g1;   // ||G_j||_1
+    std::vector<double> n2;   // ||G_i G_j||_1, (m+1)^2
+    double* d_g1 = nullptr;
+    double* d_n2 = nullptr;
+    ChainWork chain{};
+    int chain_cap = 0;
+    unsigned long long* d_hump = nullptr;  // [8] k_hump output: log hump(q), last term index, q = 1..4 (max over intervals)
+    double hump_logH[4] = {0, 0, 0, 0};
+    int hump_kend[4] = {0, 0, 0, 0};
+    bool hump_valid = false;
+    // reuse_forward_sweep: what b.fw still holds for the cached Z -- 0 nothing, 1 the p sums (S type 0), 2 p and d^j sums
+    // and GY, 3 additionally every Taylor term in fw.Zt (cache_steps of them)
+    int cache_kind = 0, cache_steps = 0;
+    // option reuse_forward_sweep: the step budget the Jacobian's chain planned from its exact norms at the cached point (q = 0: none)
+    int plan_q = 0, plan_dub = 0;
+    // ... and whether the Taylor terms of the p column of that point sit in fw.Zt ([term][Kpad][npad], one type per term:
+    // eval_constraint and the Hessian's forward sweep store them), p_steps + 1 of them, valid counts per block in fw.nterms_p
+    bool p_terms = false;
+    int p_steps = 0;
+    int p_nblk = 0;           // intervals per entry of fw.nterms_p (the convergence blocks of the sweep that stored the p terms)
+    // row-split cluster sweeps (dto_sweep_fused.hip): exchange slabs and arrival counters, one set per sweep buffer ([0] fw,
+    // [1] ad: the Hessian's forward and adjoint sweeps may run side by side)
+    SweepWork cluster_work[2];
+    // generator-stationary sweeps (dto_sweep_gs.hip): partial-norm slabs and arrival counters per sweep buffer
+    SweepWork gs_work[2];
+    bool small = false;       // n <= 32: fused one-workgroup-per-interval path (dto_small.hip)
+    double* d_Gs = nullptr;   // compact generators for that path
+    bool use_basis = false;   // A^2..A^4 from the generator subspace instead of three batched GEMMs
+    BasisSet basis[3]{};      // degrees 2, 3, 4
+    BasisSet basis_all{};     // every multiset of degree 0..4: one GEMM gives the factor K of the two-product Taylor form
+    // Hessian pairing path: stored Taylor terms of both sweeps, E_j * forward terms, Beta-weighted adjoint sums
+    bool pairing = false;
+    double* EP = nullptr;
+    double* Upair = nullptr;
+    double* d_Btab = nullptr;
+    // DTO_FLAG_BLOCK_GENERATORS: G_j = I_r (x) B_j found at create (kb x kb blocks, kr of them; (n, 1) without); `kron`: the
+    // structured path (dto_kron.hip) serves the integrator -- none of the workspaces above exist then
+    int kb = 0, kr = 1;
+    bool kron = false;
+    KKron kk{};
+    double* d_kron_scratch = nullptr;
+    size_t kron_stride = 0;
+    // DTO_FLAG_SHARED_GENERATORS: the group of integrators with these generators and controls (indices into dto_handle::bil; the
+    // leader is the first member in list order; -1 / 1 without a partner).  `share_active`: the group shares the leader's
+    // propagator chain -- a follower runs none, its -E_k blocks are copies of the leader's (dto_share.hip).  `share_followers`
+    // (leader of an active group only): the other members in list order.  `list_pos`: position in the integrator list.
+    int share_leader = -1, share_size = 1, list_pos = 0;
+    bool share_active = false;
+    std::vector<int> share_followers;
+    bool follows() const { return share_active && share_followers.empty(); }
+};
+
+struct ConHost {
+    KCon k{};
+    int equality = 0;
+    int64_t n_times_total = 0;
+    int64_t row_off = 0;  // global 0-based first row
+    std::vector<int64_t> times0;  // all times (0-based knots), reference order
+    std::vector<int32_t> comps;
+    int g_dim = 1;
+    bool external = false;        // DTO_CONSTRAINT_EXTERNAL[_GLOBAL]: values/Jacobian/Hessian blocks come from dto_set_external
+    bool global = false;          // ..._GLOBAL: `comps` index global_data; the single listing sits at the pseudo-knot N
+    int ext_slot = -1;
+    std::vector<double> jac0;     // external: Jacobian blocks at Z0 (pattern)
+    std::vector<double> hess0;    // global: Hessian of sum(g) at Z0 (pattern)
+    std::vector<double> M;        // QUADFORM_MINUS_C: the symmetric n_comps x n_comps matrix, column-major
+    KExtTerm xk{};                // external: placement of the Hessian blocks
+};
+
+// DTO_OBJECTIVE_EXTERNAL_KNOT / _GLOBAL: placement data of a host-evaluated objective term
+struct ExtObjHost {
+    double weight = 1.0;
+    bool global = false;
+    std::vector<int32_t> comps, gcomps;
+    std::vector<int64_t> times0;  // listed knots, 0-based; {N} for a GlobalObjective (no knot part)
+    KExtTerm k{};
+    int ext_slot = -1;
+};
+
+// one host-evaluated term's values for the coming callbacks + grow-only device staging
+struct ExtSlot {
+    dto_external_values v{nullptr, nullptr, nullptr};
+    size_t len[3] = {0, 0, 0};   // doubles per array (all listed times)
+    double* d[3] = {nullptr, nullptr, nullptr};
+};
+
+// DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR: evaluated by dto_tdb.hip (1..64 states) or dto_tdb_mfma.hip (65..256 states) into
+// per-interval blocks, placed like an external integrator
+struct TdbHost {
+    KTdb k{};
+    KExtInt place{};
+    double *d_vals = nullptr, *d_jac = nullptr, *d_hess = nullptr, *d_scratch = nullptr;
+    size_t stride = 0;
+    // 65..256 states: zero-padded generators and their transposes, and the scratch slots (= workgroups) of the persistent grid
+    bool mfma = false;
+    double *d_Bp = nullptr, *d_BpT = nullptr;
+    int resident = 0;
+};
+
+struct ProfRec {
+    hipEvent_t a, b;
+    int cat;
+    double flops;
+};
+}  // namespace dto
+
+struct dto_handle {
+    std::string err;
+    int device = 0;
+    bool structure_only = false;  // created with device < 0: sizes, structure and shard queries only
+    int64_t N = 0, K = 0;
+    int z = 0, gd = 0, dt_idx = 0, D = 0;
+    int eval_hessian = 1;
+    int64_t n_vars = 0, n_cons = 0, n_dyn = 0, jac_nnz = 0, hess_nnz = 0;
+    int64_t k_lo = 1, k_hi = 1;
+    dto::KProb P{};
+    std::vector<int64_t> colptr;            // host copy
+    std::vector<int64_t> con_cols, con_rows;  // constraint pattern entries sorted by (col,row), 0-based
+    std::vector<int64_t> con_colstart;      // index into con_* of each column with entries (map col -> range)
+    std::vector<dto::BilHost> bil;
+    std::vector<dto::KDer> der;
+    std::vector<int> integ_kind, integ_index;  // reference order -> (kind, index into bil/der)
+    std::vector<int> integ_dim;
+    std::vector<int64_t> integ_row_off;
+    std::vector<dto::ConHost> con;
+    std::vector<dto::KObj> obj;
+    struct ObjInfo {  // host copy of what a built-in objective term touches in the Hessian (the D2H plan needs it)
+        int kind, comp_off, comp_dim;
+        std::vector<int32_t> comps;
+        std::vector<int64_t> times;  // owned, 0-based
+        // The term's listings are stored in LAYERS: layer l holds the (l+1)-th listing of every knot, so that inside one layer
+        // no two listings name the same knot.  Gradient and Hessian kernels run layer by layer (one launch each; a single
+        // layer unless `times` repeats a knot): contributions to one entry are added in listing order, never concurrently.
+        std::vector<int64_t> layer_start;  // [n_layers + 1] offsets into the (layer-sorted) listing arrays
+    };
+    std::vector<ObjInfo> obj_info;
+    // host-pointer entry points: only the entries that can change cross PCIe (dto_hostxfer.h); built lazily at the first
+    // host-pointer Jacobian / Hessian call, option "host_xfer" = 0 keeps the plain whole-slab copy
+    std::unique_ptr<dto::HostXfer> xfer;
+    dto::XferPlan jac_plan, hess_plan;
+    int xfer_cap = 0;                                         // host-pointer Jacobian: chain chunk (intervals) for the early hand-over, 0 = off
+    std::function<void(int64_t, int)> on_chain_chunk;         // ... and its hook: (first local interval, count) of a finished chunk
+    bool plans_built = false;
+    bool raw_plans_built = false;
+    // dto_bind_output_dev: a device buffer the caller passes again and again (MadNLP's value vectors in GPU mode).  Once a call
+    // has written it in full ("primed"), later calls into the SAME pointer leave the call-invariant entries alone -- structural
+    // zeros, the identity z_{k+1} halves: half of a Jacobian slab, 99 % of a Hessian slab -- and clear only the runs a kernel
+    // accumulates into.  [0] Jacobian, [1] Hessian.
+    double* bound[2] = {nullptr, nullptr};
+    bool primed[2] = {false, false};
+    int64_t* d_bind_start[2] = {nullptr, nullptr};
+    int64_t* d_bind_len[2] = {nullptr, nullptr};
+    int64_t n_bind_runs[2] = {0, 0};
+    bool bind_ready[2] = {false, false};
+    int host_xfer = 1;
+    int xfer_check = 0;  // option "host_xfer_check": every host-pointer Jacobian / Hessian is compared with the whole device slab
+    std::vector<dto::ExtObjHost> ext_obj;
+    std::vector<dto::KExtInt> ext_int;  // DTO_INTEGRATOR_EXTERNAL, slot = index
+    std::vector<dto::TdbHost> tdb;      // DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR
+    std::vector<dto::ExtSlot> ext;      // external integrators, then constraints, then objectives, each in list order
+    int n_ext_int = 0, n_ext_con = 0, n_ext_obj = 0;
+    std::vector<int64_t> tail_colptr, tail_rows;  // Hessian entries in global-variable columns (CSC tail)
+    int64_t hess_block_nnz = 0;
+    std::vector<std::pair<int64_t, int64_t>> row_segments;  // (global start 0-based, len)
+    int64_t cons_len = 0;
+    dto_shard_info info{};
+
+    // device scratch
+    int64_t* d_colptr = nullptr;
+    double* d_Z = nullptr;
+    double* d_mu = nullptr;
+    double* d_out = nullptr;  // host-API staging for the largest output
+    size_t d_out_cap = 0;
+    double* d_partial = nullptr;
+    double* d_f = nullptr;
+    double* d_bounds = nullptr;  // [2] max beta, max b1 (as uint64 bit patterns)
+    int32_t* d_plan = nullptr;   // [4] {q, d_ub, tc} of a sweep planned on the device from d_bounds (launch_plan_dev)
+    double* d_jac_scratch = nullptr;     // value slab for the Jacobian-vector products (lazy)
+    double* d_w = nullptr;               // product input
+    int64_t* d_conbase = nullptr;        // [n_vars+1] first constraint-pattern entry of each column
+    int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
+    int64_t* d_crow_col = nullptr;
+    int64_t* d_crow_pos = nullptr;
+    int64_t* d_con_rows = nullptr;       // constraint-pattern rows, (col,row) order
+    double* h_pinned = nullptr;  // [32]: 0-1 bounds, 2-3 chain scalars, 6 sweep stats, 16-23 hump readback, 28 deferred squaring count
+    bool smax_pending = false;   // the one-launch chain's squaring count lands in h_pinned[28] behind ev_done (read by check_sweeps)
+    hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;   // generator sweep runs here, concurrently with the propagator chain
+    hipStream_t stream_rb = nullptr; // the chain's 96-byte readback (evaluation form, squaring counts, hump bound) leaves on this one
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_stats = nullptr, ev_chain = nullptr, ev_rb = nullptr, ev_zero = nullptr;
+
+    bool reuse = false;          // option reuse_forward_sweep
+    double* d_Zcache = nullptr;  // the Z the cached sweeps belong to
+    int32_t* d_eq = nullptr;
+    bool profiling = false;
+    std::vector<dto::ProfRec> prof;
+    int64_t sweep_forms[5] = {0, 0, 0, 0, 0};  // run_sweep calls by the form they took (SWEEP_GS ..), counted while profiling
+    std::vector<hipEvent_t> ev_pool;  // recycled timing events (creating them inside the timed region costs host time)
+    int last_smax = 0, last_terms = 0;
+    int expm_form = 0;  // option "expm_form": 0 = by cost, 2 / 3 = forced
+    int overlap_sweep = 1;  // option "overlap_sweep": the Jacobian's generator sweep on a second stream next to the chain's products
+    int sweep_form = 0;   // option "sweep_form": 0 = fused persistent sweep where it applies, 1 = step-per-launch form only
+    int chain_form = 0;   // option "chain_form": 0 = the one-launch chain of 33..64-state integrators where it applies, 1 = batched-GEMM launches only
+    int n_cu = 256;
+    int chain_chunk = 0;  // option "chain_chunk": upper bound on the intervals per chain chunk (0: workspace capacity)
+    int deterministic = 0;  // option "deterministic": results independent of overlap_sweep and of the entry-point family
+    // deferred errors of the `*_dev` entry points (dto_engine.h, error convention): the sweep statistics of the last
+    // asynchronous call are copied to pinned memory behind its kernels and looked at by the next call through the ABI
+    hipEvent_t ev_done = nullptr;
+    bool stats_pending = false;
+    int32_t* h_stats = nullptr;  // pinned [2 * bilinear integrators][2]
+    int last_form = 0;
+    // multi-GPU (dto_comm.h): the knot ranges of the communicator's ranks (dto_comm_create exchanges them over RCCL,
+    // dto_comm_set_ranges takes them from a caller with a transport of its own), the gather plans that follow from them,
+    // and the communicator itself
+    std::unique_ptr<dto::Comm> comm;
+    int comm_rank = -1;
+    std::vector<std::pair<int64_t, int64_t>> rank_ranges;               // (k_lo, k_hi) per rank, 1-based inclusive
+    dto::GatherPlan gather_plan[4];                                           // DTO_VECTOR_* - 1
+    std::vector<dto::Slab> cons_segments;                                     // every rank's row segments of g ...
+    std::vector<int> cons_segment_root;                                  // ... and the rank that owns each
+    int64_t* d_ranges = nullptr;
+    // Hessian-vector products (dto_eval_hessian_product[_dev]): H is assembled once per point into a private slab, its entries
+    // that can be non-zero are gathered into a row-major copy of both triangles, and every product at that point is one launch
+    // (dto_hess_product.hip).  The point is (Z, sigma, mu) bit for bit plus `gen`, which every dto_set_external, dto_set_option and
+    // failed call bumps.
+    double* hp_slab = nullptr;       // [hess_len], allocated at the first product
+    bool hp_slab_primed = false;     // written in full once: later points clear only the variable runs (as a bound output)
+    bool hp_index = false;
+    dto::KHessProduct hp{};
+    int64_t hp_nnz = 0;              // entries of the row-major copy (odd rows padded)
+    int64_t* d_hp_pos = nullptr;     // [hp_nnz] slab position of every entry, -1 for padding
+    double* d_hp_val = nullptr;
+    double* d_hp_Z = nullptr;        // the cached point
+    double* d_hp_mu = nullptr;
+    double* d_hp_v = nullptr;        // host-pointer form: v
+    int32_t* d_hp_eq = nullptr;
+    double hp_sigma = 0.0;
+    bool hp_valid = false;
+    uint64_t gen = 0, hp_gen = 0;
+    double hp_setup_ms = 0.0;        // host time of the index build ...
+    double hp_bytes = 0.0;           // ... and the device bytes of the private slab and the index
+    std::vector<void*> owned;  // device allocations to free
+
+    ~dto_handle();
+};
+
+namespace dto {
+
+template <class T>
+T* own(dto_handle* h, T* p) {
+    h->owned.push_back(p);
+    return p;
+}
+
+inline int fail(dto_handle* h, const std::string& m) {
+    if (h) h->err = m; else g_create_error = m;
+    return 1;
+}
+
+inline int pad64(int n) { return ((n + 63) / 64) * 64; }
+
+// number of integrator rows touching a column of knot kn (0-based): D per adjacent interval
+inline int col_cnt(const dto_handle* h, int64_t kn) { return kn >= h->N ? 0 : (kn >= 1 ? 1 : 0) + (kn < h->K ? 1 : 0); }
+
+// first constraint-pattern entry of column c
+inline size_t con_lower(const dto_handle* h, int64_t c) {
+    return std::lower_bound(h->con_cols.begin(), h->con_cols.end(), c) - h->con_cols.begin();
+}
+
+// value slabs of the handle that owns knots k_lo..k_hi (1-based, inclusive): positions inside the global vectors
+struct ShardExtents {
+    int64_t grad_lo, grad_len, jac_lo, jac_len, hess_lo, hess_len;
+};
+ShardExtents shard_extents(const dto_handle* h, int64_t k_lo, int64_t k_hi);
+
+// rows of g that handle owns, as (global 0-based start, length) segments in the order of its local buffer: per integrator the
+// rows of the owned intervals, then per constraint the listed times at owned knots (runs of consecutive listings merged)
+std::vector<std::pair<int64_t, int64_t>> shard_row_segments(const dto_handle* h, int64_t k_lo, int64_t k_hi);
+
+}  // namespace dto

@@ -71,8 +71,9 @@ def test_config3_256_states_16000_knots_chunked_chain():
     import dto_amd
     n, m, N = 256, 4, 16000
     K = N - 1
-    # the chunking of dto_engine.cpp: chunk_size() caps a chunk by the workspace budget of the 9 chain matrices (40e9 bytes), rounded
-    # down to a multiple of 8; run_chain() spreads the intervals evenly over ceil(K / cap) chunks, rounded up to a multiple of 8
+    # the chunking of the engine: chunk_size() (dto_create.cpp) caps a chunk by the workspace budget of the 9 chain matrices (40e9 bytes),
+    # rounded down to a multiple of 8; run_chain() (dto_engine.cpp) spreads the intervals evenly over ceil(K / cap) chunks, rounded up
+    # to a multiple of 8
     cap = max(8, int(40e9 / (9.0 * 256 * 256 * 8)) // 8 * 8)
     nchunk = -(-K // cap)
     per = min(cap, (-(-K // nchunk) + 7) // 8 * 8)
