@@ -456,7 +456,8 @@ void upload_generators(dto_handle* h, const dto_problem_desc* d, const dto_integ
         const int Tf = d->eval_hessian ? 1 + m + m * (m + 1) / 2 : 1 + m;
         b.small = true;
         // worst-case dynamic LDS of this handle's fused kernel, opted into on THIS device
-        HIP_CHECK(small_prepare(small_lds_bytes(n, m, Tf, 1 + m)));
+        // (the J w mode sweeps one forward column more than a Jacobian-only handle's other calls)
+        HIP_CHECK(small_prepare(std::max(small_lds_bytes(n, m, Tf, 1 + m), small_lds_bytes(n, m, 2 + m, 1))));
         b.d_Gs = own(h, dupload(std::vector<double>(s.G, s.G + (size_t)m1 * n * n)));
     }
 }
@@ -962,7 +963,9 @@ void alloc_tdb(dto_handle* h) {
 
 // structured path: one term slab per owned interval; the statistics words sit where the sweeps' do (deferred error convention)
 void alloc_kron(dto_handle* h, BilHost& b) {
-    b.kron_stride = scratch_stride(kron_scratch_doubles(b.kk, b.k.m, 1), kron_scratch_doubles(b.kk, b.k.m, 2), h->eval_hessian != 0);
+    // (the product modes' r-column pw / pa group takes more room than the Jacobian's b-column e group when r pads wider than b)
+    b.kron_stride = scratch_stride(std::max(kron_scratch_doubles(b.kk, b.k.m, 1), kron_scratch_doubles(b.kk, b.k.m, 3)),
+                                   kron_scratch_doubles(b.kk, b.k.m, 2), h->eval_hessian != 0);
     b.d_kron_scratch = own(h, dalloc<double>(b.kron_stride * (size_t)std::max<int64_t>(h->P.n_int, 1)));
     b.kk.stats = own(h, dalloc<int32_t>(2));
     HIP_CHECK(hipMemset(b.kk.stats, 0, 2 * sizeof(int32_t)));

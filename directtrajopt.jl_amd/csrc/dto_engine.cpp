@@ -66,8 +66,11 @@ struct ProfScope {
     }
 };
 // (for the bandwidth-bound categories from CAT_ZERO on, `flops` carries the launch's algorithmic BYTES)
+// CAT_JAC_PRODUCT ("jac_product"): the J w / J' w launches of the structured and small paths, priced in FLOPS as kron_eval prices a
+// sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
+// the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14 };
 // the form a generator sweep took (dto_profile_get "sweep_gs" .. "sweep_step"): one count per run_sweep call, not per launch
 enum { SWEEP_GS = 0, SWEEP_FUSED = 1, SWEEP_S64 = 2, SWEEP_CLUSTER = 3, SWEEP_STEP = 4 };
 inline void count_sweep_form(dto_handle* h, int form) {
@@ -775,6 +778,21 @@ void kron_eval(dto_handle* h, BilHost& b, const double* dZ, const double* dmu, i
     // priced at sixteen terms of 2 bp^2 per column and (on average two) sources
     ProfScope ps(h, st, need == 2 ? CAT_SWEEP_ADJOINT : CAT_SWEEP, 2.0 * b.kk.bp * b.kk.bp * cols * 2.0 * 16.0 * (double)h->P.n_int);
     HIP_CHECK(launch_kron(st, h->P, b.k, b.kk, dZ, dmu, need, dg, dvals, dH, b.d_kron_scratch, b.kron_stride));
+}
+
+// ... and its product modes: the integrator's rows of J w (transpose = 0) or its part of J' w into the zero-filled dy; no value slab
+void kron_product(dto_handle* h, BilHost& b, const double* dZ, const double* dw, double* dy, int transpose, hipStream_t st) {
+    HIP_CHECK(hipMemsetAsync(b.kk.stats, 0, 2 * sizeof(int32_t), st));
+    const int cp = (b.kk.rw + 15) / 16 * 16;
+    ProfScope ps(h, st, CAT_JAC_PRODUCT, 2.0 * b.kk.bp * b.kk.bp * ((b.k.m + 2) * cp) * 2.0 * 16.0 * (double)h->P.n_int);
+    HIP_CHECK(launch_kron(st, h->P, b.k, b.kk, dZ, dw, transpose ? 4 : 3, dy, nullptr, nullptr, b.d_kron_scratch, b.kron_stride));
+}
+// the same two products on the small path (dto_small.hip): exp(A) w_x as one more forward column, exp(A)' w_k as an adjoint column
+void small_product(dto_handle* h, BilHost& b, const double* dZ, const double* dw, double* dy, int transpose, hipStream_t st) {
+    SweepTypes ty = make_types(b.k.m, false);
+    if (!transpose) ty.t[ty.T++] = TypeDesc{0, {0, 0}, {0, 0}, {0, 0}};
+    ProfScope ps(h, st, CAT_JAC_PRODUCT, 2.0 * b.k.n * b.k.n * (b.k.m + 2) * 2.0 * 16.0 * (double)h->P.n_int);
+    HIP_CHECK(launch_small(st, h->P, b.k, b.d_Gs, ty, make_types(0, false), dZ, dw, dy, nullptr, nullptr, transpose ? 16 : 8));
 }
 
 void do_objective(dto_handle* h, const double* dZ, double* df, hipStream_t st) {
@@ -2121,12 +2139,14 @@ int dto_eval_hessian_product(dto_handle* h, const double* Z, double sigma, const
     }, G_BLOCKING);
 }
 
-// Matrix-free products for handles whose bilinear integrators all take the general path: exp(A)w_x rides the
-// forward sweep as an extra column type (J w), exp(A')w_k is an adjoint sweep (J' w); no value slab is formed.
+// Matrix-free products: no value slab is formed.  Per bilinear integrator: structured -> k_kron's product modes, small -> k_small's,
+// general -> exp(A)w_x rides the forward sweep as an extra column type (J w), exp(A')w_k is an adjoint sweep (J' w).
 static void jac_product_matrix_free(dto_handle* h, const double* dZ, const double* dw, double* dy, int transpose, hipStream_t st) {
     const int64_t n_out = transpose ? h->n_vars : h->n_cons;
     HIP_CHECK(hipMemsetAsync(dy, 0, sizeof(double) * (size_t)n_out, st));  // fill!(y, 0), evaluator.jl:416,442
     for (auto& b : h->bil) {
+        if (b.kron) { kron_product(h, b, dZ, dw, dy, transpose, st); continue; }
+        if (b.small) { small_product(h, b, dZ, dw, dy, transpose, st); continue; }
         if (h->P.n_int <= 0) continue;
         b.cache_kind = 0;  // the product sweeps use b.fw with their own column types
         b.p_terms = false;
@@ -2152,29 +2172,28 @@ static void jac_product_matrix_free(dto_handle* h, const double* dZ, const doubl
     for (auto& c : h->con) launch_jv_knot(st, h->P, c.k, dZ, dw, dy, transpose);
 }
 
-static void jac_product(dto_handle* h, const double* Z, const double* w, double* y, int transpose) {
-    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{"Jacobian-vector products need an unsharded handle"};
-    bool mfree = h->eval_hessian != 0 || transpose == 0;  // the adjoint sweep buffers exist only with eval_hessian
-    for (auto& b : h->bil) mfree = mfree && !b.kron && !b.small && (transpose == 0 || b.ad.S != nullptr) && b.k.m + 2 <= MAX_TYPES;
-    for (auto& c : h->con) mfree = mfree && !c.external;  // external blocks are placed into the value slab
-    mfree = mfree && h->ext_int.empty() && h->tdb.empty();
-    static const bool mfree_on = tune_int("DTO_JV_MATRIX_FREE", 1) != 0;
-    if (mfree && mfree_on) {
-        const int64_t n_in = transpose ? h->n_cons : h->n_vars, n_out = transpose ? h->n_vars : h->n_cons;
-        if (!h->d_w) h->d_w = own(h, dalloc<double>((size_t)std::max(h->n_vars, h->n_cons)));
-        upload_Z(h, Z);
-        HIP_CHECK(hipMemcpyAsync(h->d_w, w, sizeof(double) * (size_t)n_in, hipMemcpyHostToDevice, h->stream));
-        double* o = staging(h, (size_t)n_out);
-        jac_product_matrix_free(h, h->d_Z, h->d_w, o, transpose, h->stream);
-        HIP_CHECK(hipMemcpyAsync(y, o, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-        return;
+// Which route a product takes.  The slab route keeps: time-dependent and external integrators, external constraints (their blocks
+// are placed into the value slab), m + 2 > MAX_TYPES, and a transpose product without adjoint buffers on the general path (they
+// exist only with eval_hessian; structured and small integrators need none).
+static bool jac_product_is_matrix_free(const dto_handle* h, int transpose) {
+    bool mfree = h->ext_int.empty() && h->tdb.empty();
+    for (auto& b : h->bil) {
+        mfree = mfree && b.k.m + 2 <= MAX_TYPES;
+        if (!b.kron && !b.small) mfree = mfree && (transpose == 0 || (h->eval_hessian != 0 && b.ad.S != nullptr));
     }
+    for (auto& c : h->con) mfree = mfree && !c.external;
+    static const bool mfree_on = tune_int("DTO_JV_MATRIX_FREE", 1) != 0;
+    return mfree && mfree_on;
+}
+
+// The device routine both entry-point families run: everything on `st`, dZ / dw / dy device pointers.
+static void jac_product(dto_handle* h, const double* dZ, const double* dw, double* dy, int transpose, hipStream_t st) {
+    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{"Jacobian-vector products need an unsharded handle"};
+    if (jac_product_is_matrix_free(h, transpose)) return jac_product_matrix_free(h, dZ, dw, dy, transpose, st);
     if (h->integ_kind.size() > 8) throw HipError{"Jacobian-vector products support at most 8 integrators"};
-    const int64_t n_in = transpose ? h->n_cons : h->n_vars, n_out = transpose ? h->n_vars : h->n_cons;
+    const int64_t n_out = transpose ? h->n_vars : h->n_cons;
     if (!h->d_jac_scratch) {
         h->d_jac_scratch = own(h, dalloc<double>((size_t)h->info.jac_len));
-        h->d_w = own(h, dalloc<double>((size_t)std::max(h->n_vars, h->n_cons)));
         std::vector<int64_t> base((size_t)h->n_vars + 1, 0);
         for (size_t e = 0; e < h->con_cols.size(); ++e) base[(size_t)h->con_cols[e] + 1]++;
         for (int64_t c = 0; c < h->n_vars; ++c) base[(size_t)c + 1] += base[(size_t)c];
@@ -2201,25 +2220,38 @@ static void jac_product(dto_handle* h, const double* Z, const double* w, double*
     KIntegTable T{};
     T.n = (int)h->integ_kind.size();
     for (int i = 0; i < T.n; ++i) { T.d[i] = h->integ_dim[i]; T.off[i] = h->integ_row_off[i]; }
+    do_jacobian(h, dZ, h->d_jac_scratch, st);   // (external blocks are staged as for dto_eval_jacobian_dev)
+    HIP_CHECK(hipMemsetAsync(dy, 0, sizeof(double) * (size_t)n_out, st));  // fill!(y, 0), evaluator.jl:416,442
+    if (T.n > 0 || !h->con.empty()) {
+        if (transpose) launch_jac_spmv(st, h->P, T, h->d_conbase, h->d_con_rows, h->d_jac_scratch, dw, dy, 1, h->gd);
+        else launch_jac_rowgather(st, h->P, T, h->n_cons - h->n_dyn, h->d_crow_ptr, h->d_crow_col, h->d_crow_pos, h->n_dyn, h->d_jac_scratch, dw, dy);
+    }
+}
+// host-pointer form: upload, the device routine, download
+static void jac_product_host(dto_handle* h, const double* Z, const double* w, double* y, int transpose) {
+    const int64_t n_in = transpose ? h->n_cons : h->n_vars, n_out = transpose ? h->n_vars : h->n_cons;
+    if (!h->d_w) h->d_w = own(h, dalloc<double>((size_t)std::max(h->n_vars, h->n_cons)));
     upload_Z(h, Z);
     HIP_CHECK(hipMemcpyAsync(h->d_w, w, sizeof(double) * (size_t)n_in, hipMemcpyHostToDevice, h->stream));
-    do_jacobian(h, h->d_Z, h->d_jac_scratch, h->stream);
     double* o = staging(h, (size_t)n_out);
-    HIP_CHECK(hipMemsetAsync(o, 0, sizeof(double) * (size_t)n_out, h->stream));  // fill!(y, 0), evaluator.jl:416,442
-    if (T.n > 0 || !h->con.empty()) {
-        if (transpose) launch_jac_spmv(h->stream, h->P, T, h->d_conbase, h->d_con_rows, h->d_jac_scratch, h->d_w, o, 1, h->gd);
-        else launch_jac_rowgather(h->stream, h->P, T, h->n_cons - h->n_dyn, h->d_crow_ptr, h->d_crow_col, h->d_crow_pos, h->n_dyn, h->d_jac_scratch, h->d_w, o);
-    }
+    jac_product(h, h->d_Z, h->d_w, o, transpose, h->stream);
     HIP_CHECK(hipMemcpyAsync(y, o, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));
 }
 // y = J(Z) w  -- MOI.eval_constraint_jacobian_product (evaluator.jl:406-430)
 int dto_eval_jacobian_product(dto_handle* h, const double* Z, const double* w, double* y) {
-    return guarded(h, [&] { jac_product(h, Z, w, y, 0); }, G_BLOCKING);
+    return guarded(h, [&] { jac_product_host(h, Z, w, y, 0); }, G_BLOCKING);
 }
 // y = J(Z)' w -- MOI.eval_constraint_jacobian_transpose_product (evaluator.jl:432-456)
 int dto_eval_jacobian_transpose_product(dto_handle* h, const double* Z, const double* w, double* y) {
-    return guarded(h, [&] { jac_product(h, Z, w, y, 1); }, G_BLOCKING);
+    return guarded(h, [&] { jac_product_host(h, Z, w, y, 1); }, G_BLOCKING);
+}
+// ... and their device-pointer forms: enqueued on the caller's stream, errors deferred (dto_engine.h, error convention)
+int dto_eval_jacobian_product_dev(dto_handle* h, const double* dZ, const double* dw, double* dy, void* stream) {
+    return guarded(h, [&] { jac_product(h, dZ, dw, dy, 0, (hipStream_t)stream); }, G_ASYNC, (hipStream_t)stream);
+}
+int dto_eval_jacobian_transpose_product_dev(dto_handle* h, const double* dZ, const double* dw, double* dy, void* stream) {
+    return guarded(h, [&] { jac_product(h, dZ, dw, dy, 1, (hipStream_t)stream); }, G_ASYNC, (hipStream_t)stream);
 }
 
 // ---- multi-GPU: ranges, gather plans, collectives (dto_comm.h)
@@ -2439,6 +2471,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "hess_product")) cat = CAT_HESS_PRODUCT;
         else if (!strcmp(name, "share")) cat = CAT_SHARE;
         else if (!strcmp(name, "tdb_mfma")) cat = CAT_TDB_MFMA;
+        else if (!strcmp(name, "jac_product")) cat = CAT_JAC_PRODUCT;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index

@@ -390,7 +390,8 @@ struct KKron {
 hipError_t kron_prepare();
 bool kron_supported(const KKron& K, int m, bool hessian);
 size_t kron_scratch_doubles(const KKron& K, int m, int need);
-// need: 0 defect into g, 1 Jacobian block into vals (and the identity of the z_{k+1} half), 2 Hessian block added into H
+// need: 0 defect into g, 1 Jacobian block into vals (and the identity of the z_{k+1} half), 2 Hessian block added into H,
+// 3 the integrator's rows of J w into g (dmu = w), 4 its part of J' w added into g (dmu = w, g zero-filled by the caller)
 hipError_t launch_kron(hipStream_t st, const KProb& P, const KBil& B, const KKron& K, const double* dZ, const double* dmu, int need,
                        double* g, double* vals, double* H, double* scratch, size_t stride);
 

@@ -9,6 +9,8 @@
 //     h^ij (r columns, start 0)      h^ij_t = s_t (Gu h^ij_{t-1} + B_i d^j_{t-1} + B_j d^i_{t-1})   (Hessian calls)
 //     e    (b columns, start I_b)    e_t    = s_t Gu e_{t-1}                              sum = exp(A)       (Jacobian calls)
 //     pa, da^j                       the p / d^j recurrences with Gu', B_j' on M = reshape(mu_k, b, r)      (Hessian calls)
+//     pw   (r columns, start W)      the p recurrence on W = reshape(w_x(k), b, r)        sum = exp(A) W     (J w calls)
+// (J' w calls run p, d^j and pa with M = reshape(w rows of interval k, b, r): DESIGN 4.19.)
 //
 // (Gu = B_0 + sum_j u_j B_j, s_t = dt / (q t); q rounds restart the recurrences from the sums: the groups together are the columns
 // of the exponential of one block-triangular matrix.)  No n x n matrix is formed: the work per term is 2 b^2 per column and source,
@@ -36,7 +38,7 @@ struct KronArgs {
     KKron K;
     const double* Z;
     const double* mu;
-    int need;  // 0 defect, 1 Jacobian block, 2 Hessian block
+    int need;  // 0 defect, 1 Jacobian block, 2 Hessian block, 3 J w (mu = w, g = y), 4 J' w (mu = w, g = y)
     double* g;
     double* vals;
     double* H;
@@ -98,8 +100,10 @@ __global__ void __launch_bounds__(256) k_kron(KronArgs a) {
     const double* zk = a.Z + kn * z;
     const double dt = zk[a.P.dt_idx];
     const int P2 = m * (m + 1) / 2;
-    const int G = need == 0 ? 1 : (need == 1 ? m + 2 : 2 + 2 * m + P2);
-    const int g_e = m + 1, g_pa = 1 + m + P2;   // Jacobian calls: the e group; Hessian calls: the first adjoint group
+    const int G = need == 0 ? 1 : (need == 2 ? 2 + 2 * m + P2 : m + 2);
+    // Jacobian calls: the e group (J w: pw in its place); Hessian and J' w calls: the first adjoint group
+    const int g_e = m + 1, g_pa = need == 4 ? m + 1 : 1 + m + P2;
+    const bool adj = need == 2 || need == 4;
     const int ctot = (G - 1) * cp + (need == 1 ? BP : cp);
     double* T0 = a.scratch + kl * a.stride;
     double* T1 = T0 + (size_t)ctot * BP;
@@ -112,6 +116,7 @@ __global__ void __launch_bounds__(256) k_kron(KronArgs a) {
         if (need >= 1)
             for (int j = 1; j <= m; ++j) { grp[j].n_extra = 1; grp[j].gen[0] = j; grp[j].src[0] = 0; grp[j].mult[0] = 1.0; }
         if (need == 1) grp[g_e].cols = bw;
+        if (adj) grp[g_pa].tr = 1;
         if (need == 2) {
             int g = 1 + m;
             for (int i = 1; i <= m; ++i)
@@ -119,7 +124,6 @@ __global__ void __launch_bounds__(256) k_kron(KronArgs a) {
                     if (i == j) { grp[g].n_extra = 1; grp[g].gen[0] = i; grp[g].src[0] = i; grp[g].mult[0] = 2.0; }
                     else { grp[g].n_extra = 2; grp[g].gen[0] = i; grp[g].src[0] = j; grp[g].gen[1] = j; grp[g].src[1] = i; grp[g].mult[0] = grp[g].mult[1] = 1.0; }
                 }
-            grp[g_pa].tr = 1;
             for (int j = 1; j <= m; ++j) {
                 Group& d = grp[g_pa + j];
                 d.tr = 1; d.n_extra = 1; d.gen[0] = j; d.src[0] = g_pa; d.mult[0] = 1.0;
@@ -135,7 +139,8 @@ __global__ void __launch_bounds__(256) k_kron(KronArgs a) {
         sGuT[k + i * LD] = v;
     }
     // ---- start vectors: term 0 and sum
-    const double* muk = need == 2 ? a.mu + a.B.row_off + kn * n : nullptr;
+    const double* muk = adj ? a.mu + a.B.row_off + kn * n : nullptr;   // mu_k, or the rows of interval k of w (J' w)
+    const double* wxk = need == 3 ? a.mu + kn * z + a.B.x_off : nullptr; // w_x(k) (J w)
     for (int e = tid; e < ctot * BP; e += 256) {
         const int c = e / BP, i = e - c * BP;
         const int g = min(c / cp, G - 1), cw = c - g * cp;
@@ -143,7 +148,8 @@ __global__ void __launch_bounds__(256) k_kron(KronArgs a) {
         if (i < bw) {
             if (g == 0 && cw < rw) v = zk[a.B.x_off + cw * bw + i];
             else if (need == 1 && g == g_e && cw < bw) v = cw == i ? 1.0 : 0.0;
-            else if (need == 2 && g == g_pa && cw < rw) v = muk[cw * bw + i];
+            else if (adj && g == g_pa && cw < rw) v = muk[cw * bw + i];
+            else if (need == 3 && g == g_e && cw < rw) v = wxk[cw * bw + i];
         }
         T0[e] = v;
         S[e] = v;
@@ -317,6 +323,33 @@ __global__ void __launch_bounds__(256) k_kron(KronArgs a) {
         for (int e = tid; e < n; e += 256) a.vals[base + e] = -at_state(AUX, aux_gy * cp, e);
         return;
     }
+    if (need == 3) {
+        // rows of interval kn of J w: w_x(k+1) - exp(A) W - sum_j w_uj d^j - w_dt Gu exp(A) X, one writer per row
+        const double* wk = a.mu + kn * z;
+        const double wdt = wk[a.P.dt_idx];
+        for (int e = tid; e < n; e += 256) {
+            double v = wk[z + a.B.x_off + e] - at_state(S, grp[g_e].col0, e) - wdt * at_state(AUX, aux_gy * cp, e);
+            for (int j = 1; j <= m; ++j) v -= wk[a.B.u_off + j - 1] * at_state(S, grp[j].col0, e);
+            a.g[a.B.row_off + kn * n + e] = v;
+        }
+        return;
+    }
+    if (need == 4) {
+        // entries of knot kn of J' w (y is zero-filled, launches follow each other on the stream: one writer per entry and launch).
+        // The +w_{k-1} of the last knot, which owns no interval, is k_kron_jtv_tail's.
+        double* yk = a.g + kn * z;
+        for (int e = tid; e < n; e += 256)
+            yk[a.B.x_off + e] += (kn >= 1 ? a.mu[a.B.row_off + (kn - 1) * n + e] : 0.0) - at_state(S, grp[g_pa].col0, e);
+        for (int sc = wave; sc <= m; sc += 4) {   // u_j = -<W, d^j>, dt = -<W, Gu exp(A) X>: as the Hessian's scalar blocks
+            double s = 0.0;
+            if (sc < m) for (int e = lane; e < n; e += 64) s += muk[e] * at_state(S, grp[1 + sc].col0, e);
+            else for (int e = lane; e < n; e += 64) s += muk[e] * at_state(AUX, aux_gy * cp, e);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            if (lane == 0) yk[sc < m ? a.B.u_off + sc : a.P.dt_idx] -= s;
+        }
+        return;
+    }
     // Hessian of mu_k' delta_k (per replica, summed over the replicas in state order).  Every entry has one writer.
     auto hadd = [&](int c1, int c2, double v) { a.H[hess_pos(a.P, kn, c1 < c2 ? c1 : c2, c1 < c2 ? c2 : c1)] += v; };
     for (int e = tid; e < n; e += 256) {
@@ -354,13 +387,20 @@ __global__ void k_kron_identity(KProb P, KBil B, double* __restrict__ vals) {
     for (int r = threadIdx.x; r < B.n; r += blockDim.x) vals[jac_pos(P, P.colptr, kn, B.x_off + r, B.pre, B.n, 0, r)] = 1.0;
 }
 
+// J' w: +w_{k-1} into the state entries of the first owned knot past the owned intervals (the last knot of an unsharded handle)
+__global__ void k_kron_jtv_tail(KProb P, KBil B, const double* __restrict__ w, double* __restrict__ y) {
+    const int64_t kn = P.kn_lo + P.n_int;
+    if (kn < 1 || kn >= P.N || kn >= P.kn_lo + P.n_knots) return;
+    for (int r = threadIdx.x; r < B.n; r += blockDim.x) y[kn * P.z + B.x_off + r] += w[B.row_off + (kn - 1) * B.n + r];
+}
+
 }  // namespace
 
 hipError_t kron_prepare() {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kron<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * 80 * 8);
 }
 
-int kron_groups(int m, int need) { return need == 0 ? 1 : (need == 1 ? m + 2 : 2 + 2 * m + m * (m + 1) / 2); }
+int kron_groups(int m, int need) { return need == 0 ? 1 : (need == 2 ? 2 + 2 * m + m * (m + 1) / 2 : m + 2); }
 
 bool kron_supported(const KKron& K, int m, bool hessian) {
     return K.bw >= 1 && K.bp >= 16 && K.bp <= 64 && K.bp % 16 == 0 && K.bw <= K.bp && kron_groups(m, hessian ? 2 : 1) <= KRON_MAX_GROUPS;
@@ -376,6 +416,7 @@ size_t kron_scratch_doubles(const KKron& K, int m, int need) {
 hipError_t launch_kron(hipStream_t st, const KProb& P, const KBil& B, const KKron& K, const double* dZ, const double* dmu, int need,
                        double* g, double* vals, double* H, double* scratch, size_t stride) {
     if (need == 1 && P.n_knots > 0) hipLaunchKernelGGL(k_kron_identity, dim3((unsigned)P.n_knots), dim3(P.debug_bad_launch ? 4096 : 256), 0, st, P, B, vals);
+    if (need == 4 && P.n_knots > 0) hipLaunchKernelGGL(k_kron_jtv_tail, dim3(1), dim3(P.debug_bad_launch ? 4096 : 256), 0, st, P, B, dmu, g);
     if (P.n_int <= 0) return hipGetLastError();
     KronArgs a{};
     a.P = P; a.B = B; a.K = K; a.Z = dZ; a.mu = dmu; a.need = need; a.g = g; a.vals = vals; a.H = H;

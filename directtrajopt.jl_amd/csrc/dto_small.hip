@@ -60,16 +60,16 @@ struct SmallLds {
     double* pn;              // [MAX_TYPES] previous term norms
 };
 
-// Taylor recurrences for T column types starting from term0 (type 0 = v0, others 0); sums left in S.
+// Taylor recurrences for T column types starting from term0 (type 0 = v0, type t1 = v1 if given, others 0); sums left in S.
 //   transposed = 0: A v, G_g v      1: A' v, G_g' v
 template <int NT>
 __device__ void small_sweep(const SmallLds& L, const SweepTypes& ty, int n, int m, const double* ub, double dt,
-                            const double* v0, double* S, int transposed, double beta) {
+                            const double* v0, double* S, int transposed, double beta, const double* v1 = nullptr, int t1 = 0) {
     const int T = ty.T;
     const int q = beta == beta && beta < 1e6 ? max(1, (int)ceil(beta / 9.0)) : 1;
     const double dq = dt / q;
     for (int e = threadIdx.x; e < T * n; e += NT) {
-        const double v = e < n ? v0[e] : 0.0;
+        const double v = e < n ? v0[e] : (v1 && e / n == t1 ? v1[e - t1 * n] : 0.0);
         L.cur[e] = v;
         S[e] = v;
     }
@@ -134,7 +134,7 @@ struct SmallArgs {
     double* cons;
     double* jac;
     double* hess;
-    int mode;           // bit0 constraint values, bit1 Jacobian, bit2 Hessian
+    int mode;           // bit0 constraint values, bit1 Jacobian, bit2 Hessian, bit3 J w, bit4 J' w (both: mu = w, cons = y)
 };
 
 template <int NT>
@@ -199,7 +199,8 @@ __global__ void __launch_bounds__(NT) k_small(SmallArgs a) {
 
     const double* xk = zk + B.x_off;
     double* yv = L.S;  // forward sums: S[0] = exp(A) x, S[1+j] = dexp(A)[dt G_j] x, then h^{ij}
-    small_sweep<NT>(L, a.ty_fw, n, m, ub, dt, xk, L.S, 0, n1);
+    // J w: exp(A) w_x(k) rides the forward sweep as one more p column (the last type of ty_fw)
+    small_sweep<NT>(L, a.ty_fw, n, m, ub, dt, xk, L.S, 0, n1, (a.mode & 8) ? a.mu + kn * P.z + B.x_off : nullptr, Tfw - 1);
     __syncthreads();
     // GY = G(u) y
     double* GY = L.vec;
@@ -250,6 +251,36 @@ __global__ void __launch_bounds__(NT) k_small(SmallArgs a) {
             a.jac[jac_pos(P, P.colptr, kn, B.u_off + j, B.pre, n, 1, r)] = -L.S[(1 + j) * n + r];
         }
         for (int r = threadIdx.x; r < n; r += NT) a.jac[jac_pos(P, P.colptr, kn, P.dt_idx, B.pre, n, 1, r)] = -GY[r];
+    }
+
+    if (a.mode & 8) {
+        // rows of interval kn: w_x(k+1) - exp(A) w_x(k) - sum_j w_uj c_j - w_dt G(u) y, one writer per row
+        const double* wk = a.mu + kn * P.z;
+        for (int r = threadIdx.x; r < n; r += NT) {
+            double v = wk[P.z + B.x_off + r] - L.S[(1 + m) * n + r] - wk[P.dt_idx] * GY[r];
+            for (int j = 0; j < m; ++j) v -= wk[B.u_off + j] * L.S[(1 + j) * n + r];
+            a.cons[B.row_off + kn * n + r] = v;
+        }
+    }
+
+    if (a.mode & 16) {
+        // entries of knot kn (y zero-filled, one writer per entry and launch); exp(A)' w_k is an adjoint column.  The +w_{k-1} of the
+        // last knot, which owns no interval, is k_small_jtv_tail's.
+        const double* wk = a.mu + B.row_off + kn * n;
+        double* muv = L.vec + 3 * n;
+        for (int i = threadIdx.x; i < n; i += NT) muv[i] = wk[i];
+        __syncthreads();
+        small_sweep<NT>(L, a.ty_ad, n, m, ub, dt, muv, L.S2, 1, n1);
+        __syncthreads();
+        double* yk = a.cons + kn * P.z;
+        for (int r = threadIdx.x; r < n; r += NT)
+            yk[B.x_off + r] += (kn >= 1 ? a.mu[B.row_off + (kn - 1) * n + r] : 0.0) - L.S2[r];
+        for (int e = threadIdx.x; e <= m; e += NT) {   // one lane per entry, the state in order
+            const double* c = e < m ? L.S + (1 + e) * n : GY;
+            double s = 0.0;
+            for (int r = 0; r < n; ++r) s += muv[r] * c[r];
+            yk[e < m ? B.u_off + e : P.dt_idx] -= s;
+        }
     }
 
     if (a.mode & 4) {
@@ -325,6 +356,13 @@ __global__ void k_small_identity(KProb P, KBil B, double* __restrict__ jac) {
     if (kn >= 1) jac[jac_pos(P, P.colptr, kn, B.x_off + r, B.pre, B.n, 0, r)] = 1.0;
 }
 
+// J' w: +w_{k-1} into the state entries of the first owned knot past the owned intervals (the last knot of an unsharded handle)
+__global__ void k_small_jtv_tail(KProb P, KBil B, const double* __restrict__ w, double* __restrict__ y) {
+    const int64_t kn = P.kn_lo + P.n_int;
+    if (kn < 1 || kn >= P.N || kn >= P.kn_lo + P.n_knots) return;
+    for (int r = threadIdx.x; r < B.n; r += blockDim.x) y[kn * P.z + B.x_off + r] += w[B.row_off + (kn - 1) * B.n + r];
+}
+
 // Dynamic LDS beyond 64 KB has to be opted into per kernel and per DEVICE: called from dto_create (after
 // hipSetDevice) with the handle's worst-case request, so that no launch depends on what another handle did.
 hipError_t small_prepare(size_t bytes) {
@@ -339,6 +377,7 @@ hipError_t launch_small(hipStream_t st, const KProb& P, const KBil& B, const dou
         const int64_t nid = P.n_knots * B.n;
         if (nid > 0) hipLaunchKernelGGL(k_small_identity, dim3((unsigned)((nid + 255) / 256)), dim3(256), 0, st, P, B, jac);
     }
+    if ((mode & 16) && P.n_knots > 0) hipLaunchKernelGGL(k_small_jtv_tail, dim3(1), dim3(64), 0, st, P, B, dmu, cons);
     if (P.n_int <= 0) return hipGetLastError();
     SmallArgs a{};
     a.P = P; a.B = B; a.ty_fw = ty_fw; a.ty_ad = ty_ad; a.Gs = Gs; a.Z = dZ; a.mu = dmu;

@@ -103,6 +103,8 @@ SYMBOLS = {
     "dto_eval_jacobian_dev": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dto_eval_hessian_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dto_eval_hessian_product_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dto_eval_jacobian_product_dev": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dto_eval_jacobian_transpose_product_dev": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dto_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dto_comm_create": (C.c_int, [H, C.c_void_p, C.c_int32, C.c_int32]),
     "dto_comm_set_ranges": (C.c_int, [H, C.c_int32, C.c_int32, c_int64_p, c_int64_p]),

@@ -424,6 +424,14 @@ class Evaluator:
         self._stage_external(Z_host, con_need=2, obj_need=2 if sigma != 0.0 else -1, mu=mu_host)
         self._check(self._lib.dto_eval_hessian_product_dev(self._h, dZ, float(sigma), dmu, dv, dy, stream))
 
+    def eval_jacobian_product_dev(self, dZ, dw, dy, stream=0, Z_host=None):  # y = J w, dw [n_variables], dy [n_constraints]
+        self._stage_external(Z_host, con_need=1)
+        self._check(self._lib.dto_eval_jacobian_product_dev(self._h, dZ, dw, dy, stream))
+
+    def eval_jacobian_transpose_product_dev(self, dZ, dw, dy, stream=0, Z_host=None):  # y = J' w, dw [n_constraints], dy [n_variables]
+        self._stage_external(Z_host, con_need=1)
+        self._check(self._lib.dto_eval_jacobian_transpose_product_dev(self._h, dZ, dw, dy, stream))
+
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod
     def comm_unique_id():

@@ -294,7 +294,13 @@ int dto_eval_constraint(dto_handle* h, const double* Z, double* g);             
 int dto_eval_jacobian(dto_handle* h, const double* Z, double* vals);               /* evaluator.jl:368 */
 int dto_eval_hessian(dto_handle* h, const double* Z, double sigma, const double* mu,
                      double* vals);                                                /* evaluator.jl:389 */
-/* y = J w  /  y = J' w without materialising J on the host (evaluator.jl:406-456) */
+/* y = J w  /  y = J' w without materialising J on the host (evaluator.jl:406-456).  Unsharded handles only.  y is written in
+   full.  Handles made of bilinear integrators (structured, small or general), DerivativeIntegrators and built-in knot constraints
+   form no Jacobian at all: each integrator contracts its sweep with w and the handle never holds a jac_len-sized
+   allocation for the products.  Handles with a time-dependent or external integrator, an external constraint, more than
+   MAX_TYPES - 2 drives, or (J' w only) a general-path integrator created with eval_hessian = 0 evaluate the Jacobian into a
+   private device slab, allocated at the first product, and contract that.  The `_dev` forms below run the same device routine on
+   the caller's pointers and stream: both families return the same bits. */
 int dto_eval_jacobian_product(dto_handle* h, const double* Z, const double* w, double* y);
 int dto_eval_jacobian_transpose_product(dto_handle* h, const double* Z, const double* w, double* y);
 /* y = H(Z; sigma, mu) v, H the symmetric matrix whose upper triangle is dto_hessian_structure / dto_eval_hessian
@@ -317,6 +323,10 @@ int dto_eval_hessian_dev(dto_handle* h, const double* dZ, double sigma, const do
 /* the same product on device pointers; waits on one 4-byte readback when the handle holds a cached point */
 int dto_eval_hessian_product_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu,
                                  const double* dv, double* dy, void* stream);
+/* y = J w (dw [n_vars], dy [n_cons]) and y = J' w (dw [n_cons], dy [n_vars]) on device pointers: enqueued on `stream`, nothing
+   crosses the bus, errors are deferred as for every `_dev` call, one call in flight per handle */
+int dto_eval_jacobian_product_dev(dto_handle* h, const double* dZ, const double* dw, double* dy, void* stream);
+int dto_eval_jacobian_transpose_product_dev(dto_handle* h, const double* dZ, const double* dw, double* dy, void* stream);
 
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL

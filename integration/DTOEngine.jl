@@ -681,6 +681,17 @@ function eval_hessian_lagrangian_product_dev!(ev::GPUEvaluator, dh::Ptr{Float64}
                                                       dh::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 end
 
+# y = J(Z) w and y = J(Z)' w on device pointers (dw / dy: n_variables / n_constraints doubles, swapped for the transpose)
+function eval_constraint_jacobian_product_dev!(ev::GPUEvaluator, dy::Ptr{Float64}, dZ::Ptr{Float64}, dw::Ptr{Float64}, stream::Ptr{Cvoid}; Z_host = nothing)
+    Z_host === nothing || stage_external!(ev, Z_host; con_need = 1)
+    check(ev, @ccall lib.dto_eval_jacobian_product_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, dw::Ptr{Float64}, dy::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
+function eval_constraint_jacobian_transpose_product_dev!(ev::GPUEvaluator, dy::Ptr{Float64}, dZ::Ptr{Float64}, dw::Ptr{Float64}, stream::Ptr{Cvoid}; Z_host = nothing)
+    Z_host === nothing || stage_external!(ev, Z_host; con_need = 1)
+    check(ev, @ccall lib.dto_eval_jacobian_transpose_product_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, dw::Ptr{Float64}, dy::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
 "Declare a device value vector (DTO_VECTOR_JACOBIAN / DTO_VECTOR_HESSIAN) that the `*_dev!` calls are handed every iteration: its call-invariant entries are then written once (include/dto_engine.h, bound outputs).  `C_NULL` unbinds."
 bind_output_dev!(ev::GPUEvaluator, vector::Int32, dptr::Ptr{Float64}) =
     check(ev, @ccall lib.dto_bind_output_dev(ev.handle::Ptr{Cvoid}, vector::Int32, dptr::Ptr{Float64})::Cint)

@@ -15,6 +15,10 @@ One JSON line per shape.
     python tools/kron_time.py --minimum-time 1         # synthetic.unitary_minimum_time_problem instead: the built-in quadratic-form
                                                        # fidelity bound (device-resident and through host pointers) against the same
                                                        # bound as a host-merged closure (host pointers: its blocks come from the host)
+    python tools/kron_time.py --products 1             # also J w and J' w on both handles: through host pointers (wall clock, the
+                                                       # copies included) and, where the library has them, the device-pointer
+                                                       # entry points (HIP events), with the kernel time of "jac_product"
+    python tools/kron_time.py --products 1 --small 4x1000   # the same two products on a small-path handle (states x knots)
 """
 import argparse
 import json
@@ -68,6 +72,41 @@ def measure_host(prob, flagged, reps, sigma=0.7):
         return {"constraint_ms": round(host_timed(lambda: ev.eval_constraint(g, Z), reps), 4),
                 "jacobian_ms": round(host_timed(lambda: ev.eval_constraint_jacobian(J, Z), reps), 4),
                 "hessian_ms": round(host_timed(lambda: ev.eval_hessian_lagrangian(H, Z, sigma, mu), reps), 4)}
+    finally:
+        ev.close()
+
+
+def measure_products(prob, flagged, reps):
+    """J w and J' w: host-pointer calls (wall clock) and the device-pointer entry points (HIP events) where the library exports them."""
+    import numpy as np
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ev = dto_amd.Evaluator(prob, eval_hessian=True, block_generators=flagged)
+    try:
+        rng = np.random.default_rng(1)
+        Z = prob.trajectory.vec()
+        w, wt = rng.standard_normal(ev.n_variables), rng.standard_normal(ev.n_constraints)
+        y, t = np.empty(ev.n_constraints), np.empty(ev.n_variables)
+        out = {"Jw_host_ms": round(host_timed(lambda: ev.eval_constraint_jacobian_product(y, Z, w), reps), 4),
+               "JTw_host_ms": round(host_timed(lambda: ev.eval_constraint_jacobian_transpose_product(t, Z, wt), reps), 4)}
+        if not hasattr(ev._lib, "dto_eval_jacobian_product_dev"):
+            return out
+        dZ, dw, dwt = (torch.from_numpy(a).to(dev) for a in (Z, w, wt))
+        dy = torch.empty(ev.n_constraints, dtype=torch.float64, device=dev)
+        dt_ = torch.empty(ev.n_variables, dtype=torch.float64, device=dev)
+        jw = lambda: ev.eval_jacobian_product_dev(dZ.data_ptr(), dw.data_ptr(), dy.data_ptr(), st)
+        jtw = lambda: ev.eval_jacobian_transpose_product_dev(dZ.data_ptr(), dwt.data_ptr(), dt_.data_ptr(), st)
+        out["Jw_dev_ms"] = round(timed(jw, reps), 4)
+        out["JTw_dev_ms"] = round(timed(jtw, reps), 4)
+        for name, fn in (("Jw", jw), ("JTw", jtw)):
+            ev.profile_enable(True); ev.profile_reset(); fn(); torch.cuda.synchronize()
+            ms, n, fl = ev.profile_get("jac_product")
+            out[name + "_kernel_ms"] = round(ms, 4)
+            out[name + "_kernel_launches"] = n
+            out[name + "_kernel_TFLOPs"] = round(fl / ms * 1e-9, 3) if ms > 0 else None
+            out[name + "_zero_fill_launches"] = ev.profile_get("zero_fill")[1]
+            ev.profile_enable(False)
+        return out
     finally:
         ev.close()
 
@@ -127,7 +166,13 @@ def main():
     ap.add_argument("--objective-block", type=int, default=0, help="1: also time the Hessian at sigma = 0 and report the difference")
     ap.add_argument("--minimum-time", type=int, default=0, help="1: time synthetic.unitary_minimum_time_problem, built-in bound against\n"
                     "host-merged closure")
+    ap.add_argument("--products", type=int, default=0, help="1: also time J w and J' w (host pointers and device pointers)")
+    ap.add_argument("--small", default="", help="with --products 1: states x knots of one small-path problem timed first")
     a = ap.parse_args()
+    if a.products and a.small:
+        n, N = (int(x) for x in a.small.lower().split("x"))
+        prob = dto_amd.host.synthetic.make_scaled_problem(N, n, 4, seed=42)
+        print(json.dumps({"small_states": n, "knots": N, "products": measure_products(prob, False, a.reps)}), flush=True)
     for s in a.shapes.split(","):
         levels, N = (int(x) for x in s.lower().split("x"))
         out = {"levels": levels, "n": 2 * levels * levels, "knots": N, "drives": a.drives, "sigma": a.sigma}
@@ -143,6 +188,10 @@ def main():
             continue
         prob = dto_amd.host.synthetic.unitary_problem(levels, a.drives, N, seed=42)
         out["structured"] = measure_handle(prob, True, a.reps, a.sigma, a.objective_block)
+        if a.products:
+            out["structured"]["products"] = measure_products(prob, True, a.reps)
+            if a.dense:
+                out["dense_products"] = measure_products(prob, False, a.reps)
         if a.dense:
             out["dense"] = measure_handle(prob, False, a.reps, a.sigma, a.objective_block)
             out["speedup"] = {k: round(out["dense"][k + "_ms"] / out["structured"][k + "_ms"], 2) for k in ("constraint", "jacobian", "hessian")}
