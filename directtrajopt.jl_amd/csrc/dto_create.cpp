@@ -18,15 +18,16 @@ namespace {
 // structure
 // ------------------------------------------------------------------------------------------
 
-// Largest r dividing n with G_j == I_r (x) B_j for all m1 generators (n x n column-major, compared with ==): off-diagonal blocks
-// exactly zero, every diagonal block equal to the first.  1 if there is none.
-int find_replicas(const double* G, int n, int m1) {
+// Largest r dividing n with M == I_r (x) B for all m1 matrices of G and all mh of H (n x n column-major, compared with ==):
+// off-diagonal blocks exactly zero, every diagonal block equal to the first.  1 if there is none.  (H: the carrier matrices of a
+// time-dependent family; an all-zero matrix conforms to every r.)
+int find_replicas(const double* G, int n, int m1, const double* H = nullptr, int mh = 0) {
     for (int r = n; r >= 2; --r) {
         if (n % r) continue;
         const int b = n / r;
         bool ok = true;
-        for (int j = 0; j < m1 && ok; ++j) {
-            const double* M = G + (size_t)j * n * n;
+        for (int j = 0; j < m1 + mh && ok; ++j) {
+            const double* M = j < m1 ? G + (size_t)j * n * n : H + (size_t)(j - m1) * n * n;
             for (int c = 0; c < n && ok; ++c) {
                 const int bc = c / b;
                 const double* col = M + (size_t)c * n;
@@ -40,6 +41,17 @@ int find_replicas(const double* G, int n, int m1) {
         if (ok) return r;
     }
     return 1;
+}
+
+// the working block of a structured path: blocks below 16 rows are grouped while the group fits one MFMA row tile (I_g (x) B is a
+// replicated block too)
+void set_working_block(KKron& kk, int b, int r) {
+    kk.b = b; kk.r = r;
+    int grp = 1;
+    if (b < 16)
+        for (int c = 1; c <= r; ++c)
+            if (r % c == 0 && c * b <= 16) grp = c;
+    kk.bw = grp * b; kk.rw = r / grp; kk.bp = (kk.bw + 15) / 16 * 16;
 }
 
 // Does the fused one-workgroup-per-interval path (dto_small.hip) serve a bilinear integrator of n states and m drives?  n <= 16 with
@@ -419,13 +431,7 @@ void find_blocks(BilHost& b, const dto_problem_desc* d, const dto_integrator_des
     b.kr = find_replicas(s.G, n, s.u_dim + 1);
     b.kb = n / b.kr;
     KKron& kk = b.kk;
-    kk.b = b.kb; kk.r = b.kr;
-    // blocks below 16 rows are grouped while the group fits one MFMA row tile (I_g (x) B is a replicated block too)
-    int grp = 1;
-    if (b.kb < 16)
-        for (int c = 1; c <= b.kr; ++c)
-            if (b.kr % c == 0 && c * b.kb <= 16) grp = c;
-    kk.bw = grp * b.kb; kk.rw = b.kr / grp; kk.bp = (kk.bw + 15) / 16 * 16;
+    set_working_block(kk, b.kb, b.kr);
     // the structured kernel gives every Hessian entry of the block one writer: state, controls and timestep apart
     const bool apart = (s.u_dim == 0 || s.u_off + s.u_dim <= s.x_off || s.u_off >= s.x_off + n) &&
                        (d->dt_idx < s.x_off || d->dt_idx >= s.x_off + n) &&
@@ -492,11 +498,23 @@ void add_derivative(dto_handle* h, const dto_problem_desc* d, const dto_integrat
 
 void upload_time_dependent(dto_handle* h, const dto_integrator_desc& s, TdbHost& t) {
     const size_t n = s.x_dim, nn = n * n, m1 = (size_t)s.u_dim + 1;
-    t.k.G = own(h, dupload(std::vector<double>(s.G, s.G + m1 * nn)));
+    // (the structured kernel reads the blocks below, not the n x n matrices)
+    if (!t.kron) t.k.G = own(h, dupload(std::vector<double>(s.G, s.G + m1 * nn)));
     if (s.n_mod > 0) {
-        t.k.H = own(h, dupload(std::vector<double>(s.H, s.H + (size_t)s.n_mod * m1 * nn)));
+        if (!t.kron) t.k.H = own(h, dupload(std::vector<double>(s.H, s.H + (size_t)s.n_mod * m1 * nn)));
         t.k.mod_kind = own(h, dupload(std::vector<int32_t>(s.mod_kind, s.mod_kind + s.n_mod)));
         t.k.mod_omega = own(h, dupload(std::vector<double>(s.mod_omega, s.mod_omega + s.n_mod)));
+    }
+    if (t.kron) {
+        // the working blocks of B_q (the leading bw x bw block of each matrix), same order, and their transposes
+        const size_t bp = t.kk.bp, nm1 = (size_t)s.n_mod + 1;
+        std::vector<double> Bm(m1 * nm1 * bp * bp, 0.0), BmT(Bm.size(), 0.0);
+        for (size_t j = 0; j < m1; ++j)
+            for (size_t c = 0; c < nm1; ++c)
+                pad_with_transpose(c == 0 ? s.G + j * nn : s.H + ((c - 1) * m1 + j) * nn, 1, n, t.kk.bw, bp, Bm.data() + (j * nm1 + c) * bp * bp,
+                                   BmT.data() + (j * nm1 + c) * bp * bp);
+        t.kk.Bm = own(h, dupload(Bm));
+        t.kk.BmT = own(h, dupload(BmT));
     }
     if (t.mfma) {
         // B_q, q = j (1 + n_mod) + c (c = 0: G_j, c >= 1: H_{c-1, j}), zero-padded, and their transposes
@@ -511,6 +529,21 @@ void upload_time_dependent(dto_handle* h, const dto_integrator_desc& s, TdbHost&
     }
 }
 
+// DTO_FLAG_BLOCK_GENERATORS on a time-dependent family: the replicated blocks shared by every G_j and H_cj, and whether the
+// structured path (dto_tdb_kron.hip) serves the integrator
+void find_blocks_time_dependent(TdbHost& t, const dto_problem_desc* d, const dto_integrator_desc& s) {
+    const int n = s.x_dim, m1 = s.u_dim + 1;
+    t.kr = find_replicas(s.G, n, m1, s.H, s.n_mod > 0 ? s.n_mod * m1 : 0);
+    t.kb = n / t.kr;
+    set_working_block(t.kk, t.kb, t.kr);
+    // the structured kernel assigns its entries of the staged blocks: state, controls, time and timestep apart
+    auto in_x = [&](int q) { return q >= s.x_off && q < s.x_off + n; };
+    auto in_u = [&](int q) { return s.u_dim > 0 && q >= s.u_off && q < s.u_off + s.u_dim; };
+    const bool apart = (s.u_dim == 0 || s.u_off + s.u_dim <= s.x_off || s.u_off >= s.x_off + n) && !in_x(s.t_off) && !in_u(s.t_off) &&
+                       !in_x(d->dt_idx) && !in_u(d->dt_idx) && s.t_off != d->dt_idx;
+    t.kron = apart && tdb_kron_supported(t.k, t.kk);
+}
+
 void add_time_dependent(dto_handle* h, const dto_problem_desc* d, const dto_integrator_desc& s, int pre, int64_t row) {
     if (s.u_dim < 0 || s.u_dim > MAX_DRIVES) throw HipError{"time-dependent bilinear integrator: supports 0..7 drives"};
     if (s.u_dim > 0 && (s.u_off < 0 || s.u_off + s.u_dim > d->z)) throw HipError{"time-dependent bilinear integrator: bad control range"};
@@ -520,10 +553,17 @@ void add_time_dependent(dto_handle* h, const dto_problem_desc* d, const dto_inte
     TdbHost t;
     t.k.n = s.x_dim; t.k.m = s.u_dim; t.k.x_off = s.x_off; t.k.u_off = s.u_off; t.k.t_off = s.t_off;
     t.k.order = s.spline_order; t.k.substeps = s.substeps; t.k.nmod = s.n_mod; t.k.row_off = row;
-    // 1..64 states: k_tdb; 65..256 states: k_tdb_mfma; the refusal names the limit that was hit
-    if (const char* why = tdb_mfma_refusal(t.k)) throw HipError{why};
-    t.mfma = tdb_mfma_supported(t.k);
-    if (!t.mfma && !tdb_supported(t.k)) throw HipError{"time-dependent bilinear integrator: outside the device kernels' range (1..256 states, substeps >= 1, coefficient table)"};
+    t.kb = s.x_dim; t.kr = 1;
+    if (d->flags & DTO_FLAG_BLOCK_GENERATORS) find_blocks_time_dependent(t, d, s);
+    // 1..64 states: k_tdb; 65..256 states: k_tdb_mfma; replicated blocks, 33..512 states: k_tdb_kron; the refusal names the limit
+    // that was hit
+    if (!t.kron) {
+        if (t.kr >= 2 && t.kb <= 64 && s.x_dim > 512)
+            throw HipError{"time-dependent bilinear integrator: the structured path (replicated-block generators) takes up to 512 states"};
+        if (const char* why = tdb_mfma_refusal(t.k)) throw HipError{why};
+        t.mfma = tdb_mfma_supported(t.k);
+        if (!t.mfma && !tdb_supported(t.k)) throw HipError{"time-dependent bilinear integrator: outside the device kernels' range (1..256 states, substeps >= 1, coefficient table)"};
+    }
     for (int c = 0; c < s.n_mod; ++c)
         if (s.mod_kind[c] != 1 && s.mod_kind[c] != 2) throw HipError{"time-dependent bilinear integrator: mod_kind is 1 (cos) or 2 (sin)"};
     t.place.d = s.x_dim; t.place.pre = pre; t.place.row_off = row;
@@ -949,6 +989,15 @@ void alloc_tdb(dto_handle* h) {
         t.d_vals = own(h, dalloc<double>(K * n));
         t.d_jac = own(h, dalloc<double>(K * n * 2 * z));
         if (hess) t.d_hess = own(h, dalloc<double>(K * 4 * z * z));
+        if (t.kron) {
+            // the kernel assigns the entries it owns and nothing else: the constant zeros of the blocks are written here, once
+            HIP_CHECK(hipMemset(t.d_jac, 0, K * n * 2 * z * sizeof(double)));
+            if (hess) HIP_CHECK(hipMemset(t.d_hess, 0, K * 4 * z * z * sizeof(double)));
+            t.resident = (int)std::min<int64_t>(h->P.n_knots + 1, 2 * (int64_t)std::max(h->n_cu, 1));
+            t.stride = scratch_stride(tdb_kron_scratch_doubles(t.k, t.kk, 1), tdb_kron_scratch_doubles(t.k, t.kk, 2), hess);
+            t.d_scratch = own(h, dalloc<double>(t.stride * (size_t)t.resident));
+            continue;
+        }
         if (t.mfma) {
             // sized by the persistent grid (two workgroups per compute unit), not by the number of intervals
             t.resident = (int)std::min<int64_t>(h->P.n_knots + 1, 2 * (int64_t)std::max(h->n_cu, 1));

@@ -70,7 +70,7 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15 };
 // the form a generator sweep took (dto_profile_get "sweep_gs" .. "sweep_step"): one count per run_sweep call, not per launch
 enum { SWEEP_GS = 0, SWEEP_FUSED = 1, SWEEP_S64 = 2, SWEEP_CLUSTER = 3, SWEEP_STEP = 4 };
 inline void count_sweep_form(dto_handle* h, int form) {
@@ -743,6 +743,11 @@ void tdb_eval(dto_handle* h, TdbHost& t, const double* dZ, const double* dmu, in
     const KProb& P = h->P;
     const int64_t lo = need == 0 ? P.kn_lo : std::max<int64_t>(0, P.kn_lo - 1);
     const int64_t hi = need == 0 ? P.kn_lo + P.n_int : std::min<int64_t>(P.K, P.kn_lo + P.n_knots);
+    if (t.kron) {
+        ProfScope ps(h, st, CAT_TDB_KRON, tdb_kron_flops(t.k, t.kk, need) * (double)std::max<int64_t>(hi - lo, 0));
+        HIP_CHECK(launch_tdb_kron(st, P, t.k, t.kk, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch, t.stride, t.resident));
+        return;
+    }
     if (t.mfma) {
         ProfScope ps(h, st, CAT_TDB_MFMA, tdb_mfma_flops(t.k, need) * (double)std::max<int64_t>(hi - lo, 0));
         HIP_CHECK(launch_tdb_mfma(st, P, t.k, t.d_Bp, t.d_BpT, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch,
@@ -1871,8 +1876,8 @@ int dto_interval_costs(const dto_handle* h, const double* Z, int64_t first, int6
     // time-dependent bilinear integrators of 65..256 states: the flops of one Jacobian call of k_tdb_mfma (fixed steps: the same
     // for every interval)
     for (const TdbHost& t : h->tdb)
-        if (t.mfma) {
-            const double c = tdb_mfma_flops(t.k, 1);
+        if (t.kron || t.mfma) {   // (the structured path by its own flops)
+            const double c = t.kron ? tdb_kron_flops(t.k, t.kk, 1) : tdb_mfma_flops(t.k, 1);
             for (int64_t i = 0; i < count; ++i) cost[i] += c;
         }
     // every other term kind costs O(z) per knot: a constant that keeps intervals without a bilinear integrator from counting as free
@@ -1886,6 +1891,10 @@ int dto_integrator_blocks(const dto_handle* h, int32_t integrator, int32_t* bloc
     if (h->integ_kind[integrator] == DTO_INTEGRATOR_BILINEAR) {
         const BilHost& b = h->bil[h->integ_index[integrator]];
         if (b.kr >= 2) { bd = b.kb; r = b.kr; on = b.kron ? 1 : 0; }
+    }
+    if (h->integ_kind[integrator] == DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) {
+        const TdbHost& t = h->tdb[h->integ_index[integrator]];
+        if (t.kr >= 2) { bd = t.kb; r = t.kr; on = t.kron ? 1 : 0; }
     }
     if (block_dim) *block_dim = bd;
     if (reps) *reps = r;
@@ -2471,6 +2480,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "hess_product")) cat = CAT_HESS_PRODUCT;
         else if (!strcmp(name, "share")) cat = CAT_SHARE;
         else if (!strcmp(name, "tdb_mfma")) cat = CAT_TDB_MFMA;
+        else if (!strcmp(name, "tdb_kron")) cat = CAT_TDB_KRON;
         else if (!strcmp(name, "jac_product")) cat = CAT_JAC_PRODUCT;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private

@@ -150,8 +150,8 @@ struct ExtSlot {
     double* d[3] = {nullptr, nullptr, nullptr};
 };
 
-// DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR: evaluated by dto_tdb.hip (1..64 states) or dto_tdb_mfma.hip (65..256 states) into
-// per-interval blocks, placed like an external integrator
+// DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR: evaluated by dto_tdb.hip (1..64 states), dto_tdb_mfma.hip (65..256 states) or, with
+// replicated-block generators, dto_tdb_kron.hip (33..512 states) into per-interval blocks, placed like an external integrator
 struct TdbHost {
     KTdb k{};
     KExtInt place{};
@@ -161,6 +161,12 @@ struct TdbHost {
     bool mfma = false;
     double *d_Bp = nullptr, *d_BpT = nullptr;
     int resident = 0;
+    // DTO_FLAG_BLOCK_GENERATORS: every G_j and H_cj is I_r (x) B_q (kb x kb blocks, kr of them; (n, 1) without); `kron`: the
+    // structured path (dto_tdb_kron.hip) serves the integrator -- it shares `resident` and the blocks above, whose constant zeros
+    // are written once at allocation
+    int kb = 0, kr = 1;
+    bool kron = false;
+    KKron kk{};
 };
 
 struct ProfRec {

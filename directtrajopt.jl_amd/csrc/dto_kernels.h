@@ -383,7 +383,7 @@ hipError_t launch_tdb_mfma(hipStream_t st, const KProb& P, const KTdb& T, const 
 struct KKron {
     int32_t b, r;        // finest structure found (what dto_integrator_blocks reports)
     int32_t bw, rw, bp;  // working block (a few finest blocks grouped while they fit 16 rows), its replicas, bw padded to 16
-    const double* Bm;    // (m+1) working blocks, bp x bp column-major, zero-padded
+    const double* Bm;    // (m+1) working blocks (time-dependent family: Q of them), bp x bp column-major, zero-padded
     const double* BmT;   // their transposes
     int32_t* stats;      // [0] += workgroups whose sweep exhausted its budget, [1] = max terms used (the caller zeroes them)
 };
@@ -394,6 +394,18 @@ size_t kron_scratch_doubles(const KKron& K, int m, int need);
 // 3 the integrator's rows of J w into g (dmu = w), 4 its part of J' w added into g (dmu = w, g zero-filled by the caller)
 hipError_t launch_kron(hipStream_t st, const KProb& P, const KBil& B, const KKron& K, const double* dZ, const double* dmu, int need,
                        double* g, double* vals, double* H, double* scratch, size_t stride);
+
+// TimeDependentBilinearIntegrator whose G_j and H_cj are all I_r (x) B_q (dto_tdb_kron.hip): k_tdb_mfma's discrete map on b x b
+// blocks, into the same staged blocks.  K.Bm / K.BmT hold the Q = (m+1)(1+nmod) working blocks (q = j (1 + nmod) + c) and their
+// transposes; K.stats is unused.  `need` and the interval range as launch_tdb_mfma; the kernel assigns only the entries it owns
+// (the caller zero-fills jac and hess once).  tdb_kron_supported: every condition of the path that the description and the blocks
+// decide (32 < n <= 512, r >= 2, b <= 64, substeps, coefficient table).  tdb_kron_flops: flops of one interval as executed.
+bool tdb_kron_supported(const KTdb& T, const KKron& K);
+size_t tdb_kron_scratch_doubles(const KTdb& T, const KKron& K, int need);
+double tdb_kron_flops(const KTdb& T, const KKron& K, int need);
+hipError_t launch_tdb_kron(hipStream_t st, const KProb& P, const KTdb& T, const KKron& K, const double* dZ, const double* dmu, int need,
+                           int64_t i_lo, int64_t count, double* vals, double* jac, double* hess, double* scratch, size_t scratch_stride,
+                           int resident);
 
 // host-evaluated knot terms (DTO_CONSTRAINT_EXTERNAL / DTO_OBJECTIVE_EXTERNAL_KNOT): scatter of caller-supplied blocks
 void launch_ext_cons(hipStream_t st, const KCon& C, const double* vals, double* g);

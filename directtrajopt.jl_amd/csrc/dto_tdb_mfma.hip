@@ -30,12 +30,12 @@
 
 #include "dto_gemm.hip.h"
 #include "dto_kernels.h"
+#include "dto_tdb_coef.hip.h"
 
 namespace dto {
 
 namespace {
 
-constexpr int TDBM_MAX_COEFS = 6144;  // (1 + p + p (p+1)/2) * Q, as in dto_tdb.hip
 constexpr int TDBM_VEC = 32;          // column tile of the vector block
 constexpr int TDBM_MAX_PAIRS = 160;   // p (p+1) / 2 <= 136 at 7 drives, order 1
 
@@ -82,57 +82,6 @@ struct TdbmArgs {
     double* scratch;
     int64_t scratch_stride;
 };
-
-// Scalar coefficient of B_q in one jet of M(tau) = dt sum_j a_j(tau) (G_j + sum_c phi_c(t) H_cj), t = t_k + tau dt -- the table of
-// k_tdb's form_jets.  which: 0 value; 1 + b first derivative; 1 + p + pair(a, b) second derivative (a <= b, row-major triangle).
-__device__ double tdbm_coef(const KTdb& T, const double* zk, const double* zk1, double tk, double dt, double tau, int p, int which, int q) {
-    const int m = T.m, nmod = T.nmod;
-    const int j = q / (1 + nmod), c = q - j * (1 + nmod);
-    int b1 = -1, b2 = -1;
-    if (which >= 1 && which <= p) b1 = which - 1;
-    else if (which > p) {
-        int rem = which - 1 - p, aa = 0;
-        while (rem >= p - aa) { rem -= p - aa; ++aa; }
-        b1 = aa; b2 = aa + rem;
-    }
-    // a_j and its derivative slots: wk = d a_j / d u_kj, wk1 = d a_j / d u_{k+1,j}
-    double aj = 1.0, wk = 0.0, wk1 = 0.0;
-    if (j >= 1) {
-        const double uk = zk[T.u_off + j - 1];
-        if (T.order) { const double uk1 = zk1[T.u_off + j - 1]; aj = (1.0 - tau) * uk + tau * uk1; wk = 1.0 - tau; wk1 = tau; }
-        else { aj = uk; wk = 1.0; }
-    }
-    double ph = 1.0, ph1 = 0.0, ph2 = 0.0;
-    if (c >= 1) {
-        const double om = T.mod_omega[c - 1], arg = om * (tk + tau * dt);
-        const double cs = cos(arg), sn = sin(arg);
-        if (T.mod_kind[c - 1] == 1) { ph = cs; ph1 = -om * sn; ph2 = -om * om * cs; }
-        else { ph = sn; ph1 = om * cs; ph2 = -om * om * sn; }
-    }
-    // parameter classes: 0 = u_k (drive jj), 1 = t, 2 = dt, 3 = u_{k+1} (drive jj)
-    auto cls = [&](int b, int& jj) { if (b < m) { jj = b + 1; return 0; } if (b == m) { jj = -1; return 1; }
-                                     if (b == m + 1) { jj = -1; return 2; } jj = b - m - 1; return 3; };
-    if (which == 0) return dt * aj * ph;
-    if (b2 < 0) {
-        int jj; const int k1 = cls(b1, jj);
-        if (k1 == 0) return jj == j ? dt * wk * ph : 0.0;
-        if (k1 == 3) return jj == j ? dt * wk1 * ph : 0.0;
-        if (k1 == 1) return dt * aj * ph1;
-        return aj * ph + dt * aj * tau * ph1;
-    }
-    int j1, j2; const int k1 = cls(b1, j1), k2 = cls(b2, j2);
-    const bool u1 = k1 == 0 || k1 == 3, u2 = k2 == 0 || k2 == 3;
-    if (u1 && u2) return 0.0;
-    if (u1 || u2) {
-        const int ju = u1 ? j1 : j2, ku = u1 ? k1 : k2, ko = u1 ? k2 : k1;
-        const double w = ku == 0 ? wk : wk1;
-        if (ju != j) return 0.0;
-        return ko == 1 ? dt * w * ph1 : w * (ph + dt * tau * ph1);
-    }
-    if (k1 == 1 && k2 == 1) return dt * aj * ph2;
-    if (k1 == 2 && k2 == 2) return 2.0 * aj * tau * ph1 + dt * aj * tau * tau * ph2;
-    return aj * ph1 + dt * aj * tau * ph2;   // (t, dt)
-}
 
 // One TM x TN tile of A (np x np, column-major) times columns c0 .. of B; epi(row, col, value) for every element of the tile.
 // All threads of the workgroup call it (the core ends with a barrier).
@@ -378,7 +327,7 @@ const char* tdb_mfma_refusal(const KTdb& T) {
     if (T.n < 1 || T.n > 256) return "time-dependent bilinear integrator: the device kernels take 1..256 states";
     if (T.substeps < 1) return "time-dependent bilinear integrator: substeps must be >= 1";
     if (T.nmod < 0) return "time-dependent bilinear integrator: n_mod must be >= 0";
-    if (nM * (T.m + 1) * (1 + T.nmod) > TDBM_MAX_COEFS)
+    if (nM * (T.m + 1) * (1 + T.nmod) > TDB_MAX_COEFS)
         return "time-dependent bilinear integrator: coefficient table (1 + p + p (p+1) / 2) (m+1) (1 + n_mod) exceeds 6144 entries";
     return nullptr;
 }

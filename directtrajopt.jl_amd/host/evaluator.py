@@ -243,7 +243,8 @@ class Evaluator:
 
     def integrator_blocks(self, i):
         """(block_dim, reps, active) of integrator i (0-based): the finest replicated-block structure G_j = I_reps (x) B_j found
-        at create with ``block_generators=True`` and whether the structured path serves it; (x_dim, 1, 0) otherwise."""
+        at create with ``block_generators=True`` -- for a TimeDependentBilinearIntegrator the structure shared by every G_j and
+        carrier matrix H_cj -- and whether the structured path serves it; (x_dim, 1, 0) otherwise."""
         b, r, a = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._lib.dto_integrator_blocks(self._h, int(i), C.byref(b), C.byref(r), C.byref(a)))
         return b.value, r.value, a.value

@@ -10,7 +10,8 @@ from __future__ import annotations
 import numpy as np
 
 from .problem import (BilinearIntegrator, DerivativeIntegrator, DirectTrajOptProblem, KnotPointObjective, LinearRegularizer,
-                      MinimumTimeObjective, NonlinearKnotPointConstraint, QuadraticRegularizer, fidelity_constraint)
+                      MinimumTimeObjective, ModulatedGenerators, NonlinearKnotPointConstraint, QuadraticRegularizer,
+                      TimeDependentBilinearIntegrator, fidelity_constraint)
 from .trajectory import NamedTrajectory
 
 
@@ -94,6 +95,43 @@ def unitary_problem(levels, drives, N, seed=42, dt=0.1, dt_large=None, dt_small=
          + KnotPointObjective("lowrank_infidelity", "U", traj, times=[N], Qs=[100.0], A=A))
     con = NonlinearKnotPointConstraint("sqnorm", "a", traj, c=a_bound, equality=False, times=range(2, N))
     return DirectTrajOptProblem(traj, J, integrators, constraints=[con])
+
+
+def unitary_tdb_problem(levels, drives, N, n_mods=2, spline_order=1, substeps=16, seed=42, dt=0.1):
+    """``unitary_problem`` in the lab frame: its components plus a time component ``t`` (U, a, da, dda, t, dt), and the dynamics a
+    TimeDependentBilinearIntegrator on ``ModulatedGenerators`` with G_j = kron(I_levels, iso(-i H_j)) and ``n_mods`` carrier terms
+    (cos 1.7 t, sin 0.6 t) H_cj of the same shape, random Hermitian H -- what ``Evaluator(..., block_generators=True)`` recognises
+    as ``levels`` replicas of a 2 levels x 2 levels block on the time-dependent path.  The two DerivativeIntegrators (a, da),
+    (da, dda), QuadraticRegularizers on a, da, dda and the terminal unitary-infidelity objective are ``unitary_problem``'s."""
+    rng = np.random.Generator(np.random.Philox(seed))
+    n = 2 * levels * levels
+
+    def family(scale):  # (drives + 1) generators kron(I_levels, iso(-i H)), iso(-i H) = [[Im H, Re H], [-Re H, Im H]]
+        out = []
+        for _ in range(drives + 1):
+            M = rng.standard_normal((levels, levels)) + 1j * rng.standard_normal((levels, levels))
+            H = scale * (M + M.conj().T) / (2.0 * np.sqrt(levels))
+            out.append(np.kron(np.eye(levels), np.block([[H.imag, H.real], [-H.real, H.imag]])))
+        return np.stack(out)
+
+    G = family(1.0)
+    mods = [("cos", 1.7, family(0.5)), ("sin", 0.6, family(0.5))][:n_mods]
+    U = rng.standard_normal((n, N)) / np.sqrt(levels)
+    a = 0.1 * rng.standard_normal((drives, N))
+    da = rng.standard_normal((drives, N))
+    dda = rng.standard_normal((drives, N))
+    dts = np.full((1, N), float(dt))
+    t = np.concatenate([[0.0], np.cumsum(dts[0])[:-1]])[None, :]
+    traj = NamedTrajectory({"U": U, "a": a, "da": da, "dda": dda, "t": t, "dt": dts}, timestep="dt")
+    integrators = [TimeDependentBilinearIntegrator(ModulatedGenerators(G, mods), "U", "a", "t", traj, spline_order=spline_order,
+                                                   substeps=substeps),
+                   DerivativeIntegrator("a", "da", traj), DerivativeIntegrator("da", "dda", traj)]
+    goal = np.linalg.qr(rng.standard_normal((levels, levels)) + 1j * rng.standard_normal((levels, levels)))[0]
+    goal_iso = np.concatenate([goal.real, goal.imag], axis=0).T
+    A = unitary_fidelity_factor(goal_iso, levels)
+    J = (QuadraticRegularizer("a", traj, 1e-2) + QuadraticRegularizer("da", traj, 1e-2) + QuadraticRegularizer("dda", traj, 1e-2)
+         + KnotPointObjective("lowrank_infidelity", "U", traj, times=[N], Qs=[100.0], A=A))
+    return DirectTrajOptProblem(traj, J, integrators)
 
 
 def unitary_minimum_time_problem(levels, drives, N, fidelity=0.99, seed=42, D=1.0, closure=False, **kw):

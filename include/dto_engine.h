@@ -59,7 +59,9 @@ extern "C" {
                                        (1..64: a scalar kernel; 65..256: FP64 matrix-core products), substeps >= 1, and a
                                        coefficient table (1 + p + p (p+1) / 2) (m+1) (1 + n_mod) <= 6144 with
                                        p = m + 2 (+ m for spline_order 1); dto_create refuses anything else and names the
-                                       limit.  An arbitrary closure G(u, t) stays DTO_INTEGRATOR_EXTERNAL */
+                                       limit.  With DTO_FLAG_BLOCK_GENERATORS a family of replicated blocks (every G_j and
+                                       H_cj == I_r (x) B, r >= 2, blocks of at most 64 rows) runs on the blocks at 33..512
+                                       states.  An arbitrary closure G(u, t) stays DTO_INTEGRATOR_EXTERNAL */
 
 /* objective term kinds (src/objectives/) */
 #define DTO_OBJECTIVE_QUADRATIC_REGULARIZER 1 /* regularizers.jl:38-167   */
@@ -171,7 +173,12 @@ typedef struct dto_constraint_desc {
                                         layout, same structure (dto_integrator_blocks tells).  The options that concern the dense
                                         chain and its sweeps (chain_form, chain_chunk, expm_form, sweep_form, reuse_forward_sweep,
                                         overlap_sweep) are accepted and have no effect on a structured integrator; its J w and
-                                        J' w products go through the value slab */
+                                        J' w products go through the value slab.  The same search runs on every
+                                        DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR over all (m+1)(1+n_mod) matrices G_j and H_cj (an
+                                        all-zero matrix conforms): r >= 2, b <= 64, 32 < x_dim <= 512, state, controls, t and dt
+                                        disjoint components, and the kind's substeps and coefficient-table limits put it on the
+                                        structured time-dependent path (same discrete map on b x b); otherwise it is served as
+                                        with the flag clear */
 
 #define DTO_FLAG_SHARED_GENERATORS 4  /* look for DTO_INTEGRATOR_BILINEAR integrators that are driven by the same system: equal x_dim, the same
                                         control component (u_off, u_dim) and all m+1 generators equal entry by entry (==, no tolerance) --
@@ -239,7 +246,7 @@ int dto_get_shard_info(const dto_handle* h, dto_shard_info* out);
 int dto_shard_rows(const dto_handle* h, int64_t* start1, int64_t* len);
 
 /* finest replicated-block structure found in integrator i (0-based) and whether the structured path serves it;
-   (x_dim, 1, 0) when the flag is clear, the kind is not bilinear, or no structure exists */
+   (x_dim, 1, 0) when the flag is clear, the kind is neither bilinear nor time-dependent bilinear, or no structure exists */
 int dto_integrator_blocks(const dto_handle* h, int32_t integrator, int32_t* block_dim, int32_t* reps, int32_t* active);
 
 /* the group of integrator i (0-based) under DTO_FLAG_SHARED_GENERATORS: its leader (0-based position in the integrator list), the

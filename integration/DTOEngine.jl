@@ -732,7 +732,8 @@ allreduce_objective_dev!(ev::GPUEvaluator, df::Ptr{Float64}, stream::Ptr{Cvoid})
 """
 `(block_dim, reps, active)` of integrator `i` (1-based): the finest replicated-block structure `G_j = I_reps ⊗ B_j` the engine found
 in the generators it extracted from the closure (`GPUEvaluator(prob; block_generators = true)`: the `I(levels) ⊗ G̃(a)` of a unitary
-in isomorphic coordinates) and whether the structured path serves it; `(x_dim, 1, false)` otherwise.
+in isomorphic coordinates; for a device `TimeDependentBilinearIntegrator` the structure shared by every `G_j` and carrier matrix `H_cj`)
+and whether the structured path serves it; `(x_dim, 1, false)` otherwise.
 """
 function integrator_blocks(ev::GPUEvaluator, i::Integer)
     b, r, a = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)

@@ -12,6 +12,11 @@ the same problem, through host pointers, one call each.  One JSON line per shape
     python tools/tdb_time.py --shapes 128x500 --orders 1 --host ""
     python tools/tdb_time.py --small 1                        # the scalar kernel's sizes (4 .. 64 states, csrc/dto_tdb.hip) through
                                                               # host pointers, as this probe reported them before
+    python tools/tdb_time.py --block 1                        # replicated-block generators (csrc/dto_tdb_kron.hip): a unitary's
+                                                              # I_r (x) B family, flagged (block_generators=True) against unflagged
+                                                              # handles alternated in one process; order 1; 72 x 500, 128 x 500,
+                                                              # 162 x 250 both ways, 512 x 100 flagged only (the dense kernels stop
+                                                              # at 256 states)
 """
 import argparse
 import json
@@ -38,6 +43,66 @@ def problem(n, N, drives, order, substeps, on_device=True, seed=42):
     tdb = dto_amd.TimeDependentBilinearIntegrator(dto_amd.ModulatedGenerators(G, mods), "x", "u", "t", traj, spline_order=order,
                                                   substeps=substeps, on_device=on_device)
     return dto_amd.DirectTrajOptProblem(traj, dto_amd.QuadraticRegularizer("u", traj, 1.0), [tdb])
+
+
+def block_problem(levels, N, drives, order, substeps, seed=42):
+    """States 2 levels^2: generators kron(I_levels, B) with random 2 levels x 2 levels blocks of `problem`'s scale, two carriers."""
+    rng = np.random.default_rng(seed)
+    b, n = 2 * levels, 2 * levels * levels
+    traj = dto_amd.NamedTrajectory({"x": rng.standard_normal((n, N)), "u": 0.4 * rng.standard_normal((drives, N)),
+                                    "t": np.cumsum(np.full(N, 0.3))[None, :], "dt": 0.25 + 0.1 * rng.random((1, N))}, timestep="dt")
+    s = 1.0 / np.sqrt(b / 4.0)
+    rep = lambda B: np.stack([np.kron(np.eye(levels), Bj) for Bj in B])
+    G = rep(s * rng.standard_normal((drives + 1, b, b)))
+    mods = [("cos", 1.7, rep(0.5 * s * rng.standard_normal((drives + 1, b, b)))), ("sin", 0.6, rep(0.5 * s * rng.standard_normal((drives + 1, b, b))))]
+    tdb = dto_amd.TimeDependentBilinearIntegrator(dto_amd.ModulatedGenerators(G, mods), "x", "u", "t", traj, spline_order=order, substeps=substeps)
+    return dto_amd.DirectTrajOptProblem(traj, dto_amd.QuadraticRegularizer("u", traj, 1.0), [tdb])
+
+
+def measure_block(prob, reps, with_dense, sigma=0.7):
+    """Flagged and unflagged handles of one problem in one process, their timed calls alternated: per call a warm-up of at least
+    30 ms on each handle, then `reps` rounds of one call on each; medians.  Kernel time and rate from the profile names."""
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    evs = {"flagged": dto_amd.Evaluator(prob, eval_hessian=True, block_generators=True)}
+    if with_dense:
+        evs["unflagged"] = dto_amd.Evaluator(prob, eval_hessian=True)
+    try:
+        e0 = evs["flagged"]
+        Z = torch.from_numpy(prob.trajectory.vec()).to(dev)
+        mu = torch.randn(e0.n_constraints, generator=torch.Generator(device="cpu").manual_seed(1), dtype=torch.float64).to(dev)
+        con = torch.empty(e0.n_constraints, dtype=torch.float64, device=dev)
+        J = torch.empty(e0.n_jacobian_entries, dtype=torch.float64, device=dev)
+        H = torch.empty(e0.n_hessian_entries, dtype=torch.float64, device=dev)
+        out = {"blocks": e0.integrator_blocks(0)}
+
+        def calls(ev):
+            return {"constraint": lambda: ev.eval_constraint_dev(Z.data_ptr(), con.data_ptr(), st),
+                    "jacobian": lambda: ev.eval_jacobian_dev(Z.data_ptr(), J.data_ptr(), st),
+                    "hessian": lambda: ev.eval_hessian_dev(Z.data_ptr(), sigma, mu.data_ptr(), H.data_ptr(), st)}
+
+        fns = {k: calls(ev) for k, ev in evs.items()}
+        for name in ("constraint", "jacobian", "hessian"):
+            for k in evs:
+                spent = 0.0
+                while spent < 30.0:
+                    spent += one_call_ms(fns[k][name])
+            ts = {k: [] for k in evs}
+            for _ in range(reps):
+                for k in evs:
+                    ts[k].append(one_call_ms(fns[k][name]))
+            for k, ev in evs.items():
+                out[f"{k}_{name}_ms"] = round(statistics.median(ts[k]), 4)
+                prof = "tdb_kron" if k == "flagged" else "tdb_mfma"
+                ev.profile_enable(True); ev.profile_reset(); fns[k][name](); torch.cuda.synchronize()
+                ms, launches, fl = ev.profile_get(prof)
+                ev.profile_enable(False)
+                out[f"{k}_{name}_{prof}_ms"] = round(ms, 4)
+                out[f"{k}_{name}_{prof}_TFLOPs"] = round(fl / ms * 1e-9, 3) if ms > 0 else None
+        return out
+    finally:
+        for ev in evs.values():
+            ev.close()
 
 
 def one_call_ms(fn):
@@ -113,7 +178,17 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host", default="72x20", help="states x knots of the host-evaluated comparison (empty: none)")
     ap.add_argument("--small", type=int, default=0, help="1: 4 .. 64 states (k_tdb), 2 drives, order 1, host pointers; nothing else")
+    ap.add_argument("--block", type=int, default=0, help="1: replicated-block generators, flagged against unflagged handles; nothing else")
+    ap.add_argument("--block-shapes", default="6x500,8x500,9x250,16x100", help="with --block: comma-separated levels x knots (states = 2 levels^2)")
     a = ap.parse_args()
+    if a.block:
+        for s in [x for x in a.block_shapes.split(",") if x]:
+            levels, N = (int(x) for x in s.lower().split("x"))
+            n = 2 * levels * levels
+            out = {"n": n, "levels": levels, "knots": N, "drives": a.drives, "substeps": a.substeps, "order": 1}
+            out.update(measure_block(block_problem(levels, N, a.drives, 1, a.substeps), a.reps, with_dense=n <= 256))
+            print(json.dumps(out), flush=True)
+        return
     if a.small:
         for n, N in ((4, 1000), (16, 500), (32, 500), (64, 200)):
             out = {"n": n, "knots": N, "drives": 2, "substeps": a.substeps, "order": 1, "through": "host pointers, wall clock"}
