@@ -998,14 +998,19 @@ void alloc_tdb(dto_handle* h) {
             t.d_scratch = own(h, dalloc<double>(t.stride * (size_t)t.resident));
             continue;
         }
+        // the product modes (need 3, 4) share the scratch below with the value calls; their J' w stages n + p doubles per interval
+        const int p = t.k.m + 2 + (t.k.order ? t.k.m : 0);
+        t.d_jtv = own(h, dalloc<double>(std::max<size_t>(K, 1) * (n + (size_t)p)));
         if (t.mfma) {
             // sized by the persistent grid (two workgroups per compute unit), not by the number of intervals
             t.resident = (int)std::min<int64_t>(h->P.n_knots + 1, 2 * (int64_t)std::max(h->n_cu, 1));
-            t.stride = scratch_stride(tdb_mfma_scratch_doubles(t.k, 1), tdb_mfma_scratch_doubles(t.k, 2), hess);
+            t.stride = scratch_stride(std::max({tdb_mfma_scratch_doubles(t.k, 1), tdb_mfma_scratch_doubles(t.k, 3), tdb_mfma_scratch_doubles(t.k, 4)}),
+                                      tdb_mfma_scratch_doubles(t.k, 2), hess);
             t.d_scratch = own(h, dalloc<double>(t.stride * (size_t)t.resident));
             continue;
         }
-        t.stride = scratch_stride(tdb_scratch_doubles(t.k, 1), tdb_scratch_doubles(t.k, 2), hess);
+        t.stride = scratch_stride(std::max({tdb_scratch_doubles(t.k, 1), tdb_scratch_doubles(t.k, 3), tdb_scratch_doubles(t.k, 4)}),
+                                  tdb_scratch_doubles(t.k, 2), hess);
         t.d_scratch = own(h, dalloc<double>(t.stride * (size_t)(h->P.n_knots + 1)));
     }
 }

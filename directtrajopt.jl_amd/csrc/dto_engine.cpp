@@ -70,7 +70,7 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16 };
 // the form a generator sweep took (dto_profile_get "sweep_gs" .. "sweep_step"): one count per run_sweep call, not per launch
 enum { SWEEP_GS = 0, SWEEP_FUSED = 1, SWEEP_S64 = 2, SWEEP_CLUSTER = 3, SWEEP_STEP = 4 };
 inline void count_sweep_form(dto_handle* h, int form) {
@@ -755,6 +755,18 @@ void tdb_eval(dto_handle* h, TdbHost& t, const double* dZ, const double* dmu, in
         return;
     }
     HIP_CHECK(launch_tdb(st, P, t.k, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch, t.stride));
+}
+
+// Matrix-free products of a dense device time-dependent integrator (option "tdb_matrix_free_products"): its rows of J w, or its
+// part of J' w added into the zero-filled dy -- staged per interval, then placed by one thread per entry.  No block, no slab.
+void tdb_product(dto_handle* h, TdbHost& t, const double* dZ, const double* dw, double* dy, int transpose, hipStream_t st) {
+    const KProb& P = h->P;
+    const int need = transpose ? 4 : 3;
+    ProfScope ps(h, st, CAT_TDB_PRODUCT, (t.mfma ? tdb_mfma_flops(t.k, need) : tdb_product_flops(t.k, need)) * (double)std::max<int64_t>(P.K, 0));
+    double* out = transpose ? t.d_jtv : dy;
+    if (t.mfma) HIP_CHECK(launch_tdb_mfma_product(st, P, t.k, t.d_Bp, t.d_BpT, dZ, dw, need, out, t.d_scratch, t.stride, t.resident));
+    else HIP_CHECK(launch_tdb_product(st, P, t.k, dZ, dw, need, out, t.d_scratch, t.stride));
+    if (transpose) HIP_CHECK(launch_tdb_jtv_place(st, P, t.k, dw, t.d_jtv, dy));
 }
 
 // One launch per layer of an objective term's listings (a single layer unless its `times` repeats a knot): within a launch no
@@ -2177,15 +2189,19 @@ static void jac_product_matrix_free(dto_handle* h, const double* dZ, const doubl
             launch_jtv_bilinear(st, h->P, b.k, b.fw, b.ad, dw, dy);
         }
     }
+    for (auto& t : h->tdb) tdb_product(h, t, dZ, dw, dy, transpose, st);
     for (auto& d : h->der) launch_jv_derivative(st, h->P, d, dZ, dw, dy, transpose);
     for (auto& c : h->con) launch_jv_knot(st, h->P, c.k, dZ, dw, dy, transpose);
 }
 
-// Which route a product takes.  The slab route keeps: time-dependent and external integrators, external constraints (their blocks
-// are placed into the value slab), m + 2 > MAX_TYPES, and a transpose product without adjoint buffers on the general path (they
-// exist only with eval_hessian; structured and small integrators need none).
+// Which route a product takes.  The slab route keeps: external integrators, time-dependent integrators unless the option
+// "tdb_matrix_free_products" is 1 and every one of them is on a dense device path (k_tdb, k_tdb_mfma; the structured path of
+// dto_tdb_kron.hip has no product modes), external constraints (their blocks are placed into the value slab), m + 2 > MAX_TYPES, and
+// a transpose product without adjoint buffers on the general path (they exist only with eval_hessian; structured and small
+// integrators need none, nor do the time-dependent ones).
 static bool jac_product_is_matrix_free(const dto_handle* h, int transpose) {
-    bool mfree = h->ext_int.empty() && h->tdb.empty();
+    bool mfree = h->ext_int.empty() && (h->tdb.empty() || h->tdb_matrix_free_products != 0);
+    for (auto& t : h->tdb) mfree = mfree && !t.kron;
     for (auto& b : h->bil) {
         mfree = mfree && b.k.m + 2 <= MAX_TYPES;
         if (!b.kron && !b.small) mfree = mfree && (transpose == 0 || (h->eval_hessian != 0 && b.ad.S != nullptr));
@@ -2432,6 +2448,12 @@ int dto_set_option(dto_handle* h, const char* name, int64_t value) {
         drop_caches(h);
         return 0;
     }
+    if (std::string(name) == "tdb_matrix_free_products") {
+        if (value != 0 && value != 1)
+            return fail(h, "dto_set_option: tdb_matrix_free_products takes 0 (J w / J' w of time-dependent integrators through the value slab) or 1 (matrix-free)");
+        h->tdb_matrix_free_products = (int)value;
+        return 0;
+    }
     if (std::string(name) == "expm_form") {
         if (value != 0 && value != 2 && value != 3) return fail(h, "dto_set_option: expm_form takes 0 (by cost), 2 or 3");
         h->expm_form = (int)value;
@@ -2482,6 +2504,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "tdb_mfma")) cat = CAT_TDB_MFMA;
         else if (!strcmp(name, "tdb_kron")) cat = CAT_TDB_KRON;
         else if (!strcmp(name, "jac_product")) cat = CAT_JAC_PRODUCT;
+        else if (!strcmp(name, "tdb_product")) cat = CAT_TDB_PRODUCT;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index

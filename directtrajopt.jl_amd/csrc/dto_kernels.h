@@ -364,6 +364,14 @@ size_t tdb_scratch_doubles(const KTdb& T, int need);
 // blocks of intervals i_lo .. i_lo + count - 1 (global, 0-based) into vals [K][n], jac [K][2z][n], hess [K][2z][2z]
 hipError_t launch_tdb(hipStream_t st, const KProb& P, const KTdb& T, const double* dZ, const double* dmu, int need, int64_t i_lo,
                       int64_t count, double* vals, double* jac, double* hess, double* scratch, size_t scratch_stride);
+// Product modes of the same integrator, no block and no slab: need 3 assigns the integrator's rows of J w in `out` = y; need 4 stages
+// per interval [Phi_k' w_k (n), w_k' (dPhi_k / dtheta_b) x_k (p)] in `out` = [K][n + p], which launch_tdb_jtv_place (either
+// kernel's staging) then ADDS into y, every entry by one thread.  All K intervals (products need an unsharded handle).
+// tdb_scratch_doubles covers need 3 and 4; tdb_product_flops: flops of one interval as executed.
+double tdb_product_flops(const KTdb& T, int need);
+hipError_t launch_tdb_product(hipStream_t st, const KProb& P, const KTdb& T, const double* dZ, const double* dw, int need, double* out,
+                              double* scratch, size_t scratch_stride);
+hipError_t launch_tdb_jtv_place(hipStream_t st, const KProb& P, const KTdb& T, const double* dw, const double* stage, double* dy);
 // The same integrator at 65..256 states (dto_tdb_mfma.hip): FP64 MFMA products against M0 = sum_q c_q B_q, the derivative jets
 // applied as scalar combinations of B_q y; a persistent grid of `resident` workgroups, one scratch slot of `scratch_stride` doubles
 // each.  Bp / BpT: the Q = (m+1)(1+nmod) matrices G_j, H_cj (q = j (1 + nmod) + c) and their transposes, zero-padded to
@@ -377,6 +385,9 @@ double tdb_mfma_flops(const KTdb& T, int need);
 hipError_t launch_tdb_mfma(hipStream_t st, const KProb& P, const KTdb& T, const double* Bp, const double* BpT, const double* dZ,
                            const double* dmu, int need, int64_t i_lo, int64_t count, double* vals, double* jac, double* hess,
                            double* scratch, size_t scratch_stride, int resident);
+// ... and its product modes (need 3 / 4, `out` as launch_tdb_product's; tdb_mfma_scratch_doubles and tdb_mfma_flops cover them)
+hipError_t launch_tdb_mfma_product(hipStream_t st, const KProb& P, const KTdb& T, const double* Bp, const double* BpT, const double* dZ,
+                                   const double* dw, int need, double* out, double* scratch, size_t scratch_stride, int resident);
 
 // BilinearIntegrator with replicated-block generators G_j = I_r (x) B_j (dto_kron.hip): one workgroup per interval sweeps b-row
 // column groups against the b x b blocks and writes defect, Jacobian block or Hessian block of mu_k' f straight to their positions

@@ -33,13 +33,20 @@
 //
 // Bound: this is small-state work (quantum-control systems in a rotating frame have 4..32 states); the kernel keeps its
 // columns in an L2-resident scratch slab per workgroup and is latency-, not bandwidth- or MFMA-bound.
+//
+// Product modes (k_tdb_product; need 3: J w, need 4: J' w).  The discrete map is linear in the state, so a product needs no Phi:
+//     J w   rows of interval k:  w_x(k+1) - d(1),  d the scheme applied to d' = M d + M_w x, d(0) = w_x(k), beside x' = M x;
+//           M_w = sum_b w_theta_b M_b is ONE jet (directional coefficient row, dto_tdb_coef.hip.h).  Columns x, d; jets M, M_w.
+//     J' w  per interval: the forward columns x, x_b (jets M, M_b), the p dot products w_k' x_b(1), then the one-column adjoint
+//           lambda = Phi_k' w_k (the recursion above without its sensitivity columns; jet M only).  The n + p results are staged
+//           per interval and k_tdb_jtv_place adds them into y, one thread per entry of y in a fixed order.
+// No second-order jet, no n-column block, no staged Jacobian block, no value slab.
 #include "dto_kernels.h"
+#include "dto_tdb_coef.hip.h"
 
 namespace dto {
 
 namespace {
-
-constexpr int TDB_MAX_COEFS = 6144;  // (1 + p + p (p+1)/2) * (m+1) * (1 + nmod) must fit (checked by tdb_supported)
 
 __host__ __device__ inline bool tdb_uses_adjoint(int n) { return n >= 12; }
 
@@ -313,6 +320,169 @@ __global__ void __launch_bounds__(256) k_tdb(TdbArgs a) {
     theta_block();
 }
 
+// (1 + p) rows of first-order coefficients and the directional row: (2 + p) Q <= 2/3 (1 + p + p (p+1)/2) Q for p >= 2
+constexpr int TDB_PRODUCT_COEFS = TDB_MAX_COEFS * 2 / 3;
+
+struct TdbProductArgs {
+    KProb P;
+    KTdb T;
+    const double* Z;
+    const double* w;
+    int need;          // 3: J w, 4: J' w
+    double* out;       // need 3: y (the integrator's rows are assigned); need 4: staging [K][n + p]
+    double* scratch;
+    int64_t scratch_stride;
+};
+
+__global__ void __launch_bounds__(256) k_tdb_product(TdbProductArgs a) {
+    const int n = a.T.n, m = a.T.m, z = a.P.z, nmod = a.T.nmod, order = a.T.order;
+    const int p = m + 2 + (order ? m : 0);
+    const int need = a.need;
+    const int64_t kn = blockIdx.x;
+    const double* zk = a.Z + kn * z;
+    const double* zk1 = zk + z;
+    const double tk = zk[a.T.t_off], dt = zk[a.P.dt_idx];
+    const int tid = threadIdx.x;
+    // columns: x, d (J w) | x, x_b (J' w); jet c belongs to column c: M, then M_w | M_b
+    const int C = need == 3 ? 2 : 1 + p;
+    double* S = a.scratch + (int64_t)blockIdx.x * a.scratch_stride;
+    double* Y = S;
+    double* ACC = Y + (int64_t)C * n;
+    double* TA = ACC + (int64_t)C * n;
+    double* TB = TA + (int64_t)C * n;
+    double* MJ = TB + (int64_t)C * n;   // [C][n*n] column-major jets of M
+    const int nn = n * n;
+    const int Q = (m + 1) * (1 + nmod);
+    auto Bq = [&](int j, int c) { return c == 0 ? a.T.G + (int64_t)j * nn : a.T.H + ((int64_t)(c - 1) * (m + 1) + j) * nn; };
+    __shared__ double coefs[TDB_PRODUCT_COEFS];   // rows 0 .. p of tdbm_coef, row 1 + p: the directional row (J w)
+    __shared__ double w_theta[2 * MAX_DRIVES + 2];
+    if (need == 3 && tid < p) w_theta[tid] = a.w[kn * z + tdb_param_entry(a.T, z, a.P.dt_idx, tid)];
+
+    // `njet` jets at tau: the coefficient rows, then the matrices (jet s from row s; in a J w call jet 1 from the directional row)
+    auto form_jets = [&](double tau, int njet) {
+        const int rows = need == 3 ? 1 + p : njet;
+        for (int e = tid; e < rows * Q; e += 256) coefs[e] = tdbm_coef(a.T, zk, zk1, tk, dt, tau, p, e / Q, e % Q);
+        __syncthreads();
+        if (need == 3) {
+            for (int q = tid; q < Q; q += 256) coefs[(1 + p) * Q + q] = tdbm_dir_coef(coefs, Q, p, q, w_theta);
+            __syncthreads();
+        }
+        for (int e = tid; e < njet * nn; e += 256) {
+            const int s = e / nn, off = e - s * nn;
+            const double* cf = coefs + (need == 3 && s == 1 ? 1 + p : s) * Q;
+            double acc = 0.0;
+            for (int q = 0; q < Q; ++q)
+                if (cf[q] != 0.0) acc += cf[q] * Bq(q / (1 + nmod), q % (1 + nmod))[off];
+            MJ[e] = acc;
+        }
+        __syncthreads();
+    };
+
+    // initial values: x = x_k, d = w_x(k), x_b = 0
+    for (int e = tid; e < C * n; e += 256) {
+        const int c = e / n, r = e - c * n;
+        Y[e] = c == 0 ? zk[a.T.x_off + r] : (need == 3 ? a.w[kn * z + a.T.x_off + r] : 0.0);
+    }
+    __syncthreads();
+
+    const double h = 1.0 / a.T.substeps;
+    for (int step = 0; step < a.T.substeps; ++step) {
+        for (int stage = 0; stage < 4; ++stage) {
+            const double tau = (step + (stage == 0 ? 0.0 : (stage == 3 ? 1.0 : 0.5))) * h;
+            const double* IN = stage == 0 ? Y : (stage == 2 ? TB : TA);
+            if (stage != 2) form_jets(tau, C);   // stages 1 and 2 share their time
+            double* OUT = stage == 0 ? TA : (stage == 1 ? TB : (stage == 2 ? TA : Y));
+            const double w_acc = (stage == 0 || stage == 3) ? h / 6.0 : h / 3.0;
+            const double w_tmp = stage == 2 ? h : 0.5 * h;
+            for (int e = tid; e < C * n; e += 256) {
+                const int c = e / n, r = e - c * n;
+                auto mv = [&](const double* M, int col) {   // (M * IN[col])[r]
+                    double s = 0.0;
+                    const double* y = IN + (int64_t)col * n;
+                    for (int k = 0; k < n; ++k) s += M[r + k * n] * y[k];
+                    return s;
+                };
+                double K = mv(MJ, c);
+                if (c >= 1) K += mv(MJ + (int64_t)c * nn, 0);
+                const double y0 = Y[e];
+                if (stage == 0) { ACC[e] = y0 + w_acc * K; OUT[e] = y0 + w_tmp * K; }
+                else if (stage < 3) { ACC[e] += w_acc * K; OUT[e] = y0 + w_tmp * K; }
+                else OUT[e] = ACC[e] + w_acc * K;
+            }
+            __syncthreads();
+        }
+    }
+
+    if (need == 3) {
+        for (int r = tid; r < n; r += 256) a.out[a.T.row_off + kn * n + r] = a.w[(kn + 1) * z + a.T.x_off + r] - Y[n + r];
+        return;
+    }
+    const double* wk = a.w + a.T.row_off + kn * n;
+    double* out = a.out + kn * (int64_t)(n + p);
+    for (int b = tid; b < p; b += 256) {   // w_k' (dPhi_k / dtheta_b) x_k
+        double s = 0.0;
+        for (int r = 0; r < n; ++r) s += wk[r] * Y[(int64_t)(1 + b) * n + r];
+        out[n + b] = s;
+    }
+    // lambda = Phi_k' w_k: the discrete adjoint, one column, backward through the steps (k_tdb's recursion)
+    double* W = TA;
+    double* WN = TB;
+    double* KB = ACC;
+    double* UB = ACC + n;
+    for (int e = tid; e < n; e += 256) W[e] = wk[e];
+    __syncthreads();
+    for (int step = a.T.substeps - 1; step >= 0; --step) {
+        for (int e = tid; e < n; e += 256) WN[e] = W[e];
+        for (int stage = 3; stage >= 0; --stage) {
+            const double tau = (step + (stage == 0 ? 0.0 : (stage == 3 ? 1.0 : 0.5))) * h;
+            if (stage != 1) form_jets(tau, 1);   // stages 2 and 1 share their time (form_jets ends with a barrier)
+            const double cw = (stage == 3 || stage == 0) ? h / 6.0 : h / 3.0;
+            const double cu = stage == 3 ? 0.0 : (stage == 2 ? h : 0.5 * h);
+            for (int e = tid; e < n; e += 256) KB[e] = cw * W[e] + (cu != 0.0 ? cu * UB[e] : 0.0);
+            __syncthreads();
+            for (int r = tid; r < n; r += 256) {   // ubar = M' kbar: column r of M . kbar
+                double s = 0.0;
+                const double* mc = MJ + (int64_t)r * n;
+                for (int k = 0; k < n; ++k) s += mc[k] * KB[k];
+                UB[r] = s;
+                WN[r] += s;
+            }
+            __syncthreads();
+        }
+        for (int e = tid; e < n; e += 256) W[e] = WN[e];
+        __syncthreads();
+    }
+    for (int i = tid; i < n; i += 256) out[i] = W[i];
+}
+
+// J' w: the staged per-interval results into y.  One thread per entry of the knots' part of y adds what the interval on its left
+// (w_{k-1}, the u_{k+1} terms) and the interval on its right (-Phi_k' w_k, the u_k, t_k, dt_k terms) contribute, in that order
+__global__ void __launch_bounds__(256) k_tdb_jtv_place(KProb P, KTdb T, const double* __restrict__ w, const double* __restrict__ stage,
+                                                       double* __restrict__ y) {
+    const int z = P.z, n = T.n, m = T.m, p = m + 2 + (T.order ? m : 0);
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= P.N * z) return;
+    const int64_t kn = e / z;
+    const int c = (int)(e - kn * z), i = c - T.x_off;
+    const bool in_x = i >= 0 && i < n;
+    double acc = 0.0;
+    if (kn >= 1) {
+        if (in_x) acc += w[T.row_off + (kn - 1) * n + i];
+        if (T.order) {
+            const double* s = stage + (kn - 1) * (int64_t)(n + p) + n + m + 2;
+            for (int j = 0; j < m; ++j)
+                if (T.u_off + j == c) acc -= s[j];
+        }
+    }
+    if (kn < P.K) {
+        const double* s = stage + kn * (int64_t)(n + p);
+        if (in_x) acc -= s[i];
+        for (int b = 0; b < m + 2; ++b)
+            if (tdb_param_entry(T, z, P.dt_idx, b) == c) acc -= s[n + b];
+    }
+    y[e] += acc;
+}
+
 }  // namespace
 
 bool tdb_supported(const KTdb& T) {
@@ -324,6 +494,10 @@ bool tdb_supported(const KTdb& T) {
 size_t tdb_scratch_doubles(const KTdb& T, int need) {
     const int n = T.n, m = T.m, p = m + 2 + (T.order ? m : 0);
     const size_t P2 = (size_t)p * (p + 1) / 2;
+    if (need >= 3) {   // product modes: x, d | x, x_b, one jet per column
+        const size_t Cp = need == 3 ? 2 : 1 + p;
+        return 4 * Cp * n + Cp * (size_t)n * n;
+    }
     const size_t C = need == 0 ? 1 : (need == 1 ? 1 + n + p : (tdb_uses_adjoint(n) ? 1 + p + P2 : 1 + n + p + (size_t)n * p + P2));
     const size_t nM = need == 0 ? 1 : (need == 1 ? 1 + p : 1 + p + (size_t)p * (p + 1) / 2);
     return 4 * C * n + nM * (size_t)n * n;
@@ -336,6 +510,32 @@ hipError_t launch_tdb(hipStream_t st, const KProb& P, const KTdb& T, const doubl
     a.P = P; a.T = T; a.Z = dZ; a.mu = dmu; a.need = need; a.i_lo = i_lo;
     a.vals = vals; a.jac = jac; a.hess = hess; a.scratch = scratch; a.scratch_stride = (int64_t)scratch_stride;
     hipLaunchKernelGGL(k_tdb, dim3((unsigned)count), dim3(P.debug_bad_launch ? 4096 : 256), 0, st, a);
+    return hipGetLastError();
+}
+
+// flops of one interval of a product call as executed: per stage the M and jet products of every column, per stage time the jets
+double tdb_product_flops(const KTdb& T, int need) {
+    const double n2 = (double)T.n * T.n, S = T.substeps;
+    const int p = T.m + 2 + (T.order ? T.m : 0), C = need == 3 ? 2 : 1 + p, Q = (T.m + 1) * (1 + T.nmod);
+    double fl = 4.0 * 2.0 * n2 * (2 * C - 1) + 3.0 * 2.0 * Q * n2 * C;
+    if (need == 4) fl += 4.0 * 2.0 * n2 + 3.0 * 2.0 * Q * n2;
+    return S * fl;
+}
+
+hipError_t launch_tdb_product(hipStream_t st, const KProb& P, const KTdb& T, const double* dZ, const double* dw, int need, double* out,
+                              double* scratch, size_t scratch_stride) {
+    if (P.K <= 0) return hipSuccess;
+    if ((need != 3 && need != 4) || tdb_scratch_doubles(T, need) > scratch_stride) return hipErrorInvalidValue;
+    TdbProductArgs a{};
+    a.P = P; a.T = T; a.Z = dZ; a.w = dw; a.need = need; a.out = out; a.scratch = scratch; a.scratch_stride = (int64_t)scratch_stride;
+    hipLaunchKernelGGL(k_tdb_product, dim3((unsigned)P.K), dim3(P.debug_bad_launch ? 4096 : 256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tdb_jtv_place(hipStream_t st, const KProb& P, const KTdb& T, const double* dw, const double* stage, double* dy) {
+    const int64_t entries = P.N * P.z;
+    if (entries <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_tdb_jtv_place, dim3((unsigned)((entries + 255) / 256)), dim3(P.debug_bad_launch ? 4096 : 256), 0, st, P, T, dw, stage, dy);
     return hipGetLastError();
 }
 

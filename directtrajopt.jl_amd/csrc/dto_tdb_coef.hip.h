@@ -1,5 +1,5 @@
 // dto_tdb_coef.hip.h -- the scalar jet coefficients of the TimeDependentBilinearIntegrator's generator family, shared by the
-// kernels that apply jets as combinations of B_q y (dto_tdb_mfma.hip, dto_tdb_kron.hip).
+// kernels that apply jets as combinations of B_q y (dto_tdb_mfma.hip, dto_tdb_kron.hip) and by the product modes of dto_tdb.hip.
 #pragma once
 
 #include "dto_kernels.h"
@@ -57,6 +57,21 @@ __device__ inline double tdbm_coef(const KTdb& T, const double* zk, const double
     return aj * ph1 + dt * aj * tau * ph2;   // (t, dt)
 }
 
-constexpr int TDB_MAX_COEFS = 6144;  // entries of the table, (1 + p + p (p+1)/2) * Q, as in dto_tdb.hip
+constexpr int TDB_MAX_COEFS = 6144;  // entries of the table, (1 + p + p (p+1)/2) * Q (tdb_supported, tdb_mfma_refusal)
+
+// Entry of the stacked pair [z_k ; z_{k+1}] that parameter b of theta = [u_k (m), t_k, dt_k, u_{k+1} (m, order 1)] lives in: where a
+// J w mode reads its component of w (relative to knot k) and where a J' w mode lands its term.  Two parameters may name one entry
+// (the timestep listed as the time variable).
+__host__ __device__ inline int tdb_param_entry(const KTdb& T, int z, int dt_idx, int b) {
+    return b < T.m ? T.u_off + b : (b == T.m ? T.t_off : (b == T.m + 1 ? dt_idx : z + T.u_off + (b - T.m - 2)));
+}
+
+// Directional coefficient row of J w: M_w = sum_b w_theta_b M_b = sum_q c_wq B_q with c_wq = sum_b w_theta_b c_{1+b, q}, b ascending.
+// `table` holds rows 0 .. p of tdbm_coef at the stage time ([which][Q]); the product modes keep the result in row 1 + p.
+__device__ inline double tdbm_dir_coef(const double* table, int Q, int p, int q, const double* w_theta) {
+    double s = 0.0;
+    for (int b = 0; b < p; ++b) s += w_theta[b] * table[(size_t)(1 + b) * Q + q];
+    return s;
+}
 
 }  // namespace dto

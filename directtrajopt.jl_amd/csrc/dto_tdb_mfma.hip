@@ -26,6 +26,14 @@
 // every sum has a fixed order; there is no floating-point atomic.  Output entries that share a position (a component that serves
 // twice, e.g. the timestep listed as the time variable) are added by one thread in a fixed order.  Padded rows and columns are
 // computed (they are zeros) and never written to vals / jac / hess.
+//
+// Product modes (the PROD instantiation of the same kernel; need 3: J w, need 4: J' w; formulas in dto_tdb.hip).  The column block is
+// one 32-column tile and there is no Phi block:
+//         J w       x, d | zeros to 32          d' = M0 d + M_w x: the Jacobian call's epilogue with ONE jet, the directional row
+//         J' w      x, x_b (p) | zeros to 32    the Jacobian call's vector block; then p dot products with w_k
+// M0 is formed for the forward tile as in the value calls.  The adjoint of J' w is a single column, so it forms no M0 and runs no
+// GEMM: ubar = M0' kbar = sum_q c_q (B_q' kbar) from the vector pass that the Hessian's adjoint already has.  Results go to y (J w:
+// the integrator's rows, one writer per entry) or to the per-interval staging of n + p doubles that k_tdb_jtv_place adds into y.
 #include <algorithm>
 
 #include "dto_gemm.hip.h"
@@ -52,7 +60,8 @@ inline __host__ __device__ TdbmLayout tdbm_layout(const KTdb& T, int need) {
     L.p = T.m + 2 + (T.order ? T.m : 0);
     L.P2 = L.p * (L.p + 1) / 2;
     L.Q = (T.m + 1) * (1 + T.nmod);
-    L.C = need == 0 ? 1 : (need == 1 ? 1 + L.p : 1 + L.p + L.P2);   // meaningful columns of the vector block
+    // meaningful columns of the vector block (need 3: x, d; need 4: x, x_b)
+    L.C = need == 0 ? 1 : (need == 3 ? 2 : (need == 1 || need == 4 ? 1 + L.p : 1 + L.p + L.P2));
     L.Cv = pad32(L.C);
     L.Ctot = L.Cv + (need == 1 ? L.np : 0);
     L.ucols = need == 2 ? TDBM_VEC : 1;
@@ -81,6 +90,8 @@ struct TdbmArgs {
     double* hess;        // [K][2z][2z]
     double* scratch;
     int64_t scratch_stride;
+    const double* w;     // product modes: the vector
+    double* out;         // need 3: y (the integrator's rows are assigned); need 4: staging [K][n + p]
 };
 
 // One TM x TN tile of A (np x np, column-major) times columns c0 .. of B; epi(row, col, value) for every element of the tile.
@@ -111,7 +122,8 @@ __device__ __forceinline__ void mm_cols(const double* __restrict__ A, const doub
     }
 }
 
-template <int TM>
+// PROD: the instantiation that serves need 3 and 4 and nothing else (the value modes' code is unchanged by it)
+template <int TM, bool PROD>
 __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
     const int n = a.T.n, m = a.T.m, z = a.P.z, need = a.need;
     const TdbmLayout L = tdbm_layout(a.T, need);
@@ -121,7 +133,10 @@ __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
     __shared__ __attribute__((aligned(16))) double smem[GemmShape<TM, 64, 2, 2>::SMEM_DOUBLES];
     __shared__ double vsh[256];                                // the vector of a vector pass
     __shared__ unsigned char pair_a[TDBM_MAX_PAIRS], pair_b[TDBM_MAX_PAIRS];
-    for (int e = tid; e < P2; e += 256) {
+    __shared__ double w_theta[PROD ? 2 * MAX_DRIVES + 2 : 1];   // J w: the entries of w at the interval's parameters
+    // first-order jets that enter the epilogue of the forward tile, and the coefficient row of the first of them
+    const int pj = PROD && need == 3 ? 1 : p, row1 = PROD && need == 3 ? 1 + p : 1;
+    for (int e = tid; e < (PROD ? 0 : P2); e += 256) {
         int rem = e, aa = 0;
         while (rem >= p - aa) { rem -= p - aa; ++aa; }
         pair_a[e] = (unsigned char)aa; pair_b[e] = (unsigned char)(aa + rem);
@@ -147,6 +162,9 @@ __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
         auto form_m0 = [&](double tau, int njet, const double* __restrict__ B) {
             for (int e = tid; e < njet * Q; e += 256) coefs[e] = tdbm_coef(a.T, zk, zk1, tk, dt, tau, p, e / Q, e % Q);
             __syncthreads();
+            if (PROD && need == 3) {   // the directional row, behind rows 0 .. p (read by the epilogue, after the barriers below)
+                for (int q = tid; q < Q; q += 256) coefs[(size_t)(1 + p) * Q + q] = tdbm_dir_coef(coefs, Q, p, q, w_theta);
+            }
             for (size_t e = 2 * (size_t)tid; e < nn; e += 512) {
                 d2 acc = d2{0.0, 0.0};
                 for (int q = 0; q < Q; ++q) {
@@ -177,18 +195,20 @@ __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
             __syncthreads();
         };
 
-        // initial values: x = x_k, Phi = I, everything else (padding included) 0
+        if (PROD && need == 3 && tid < p) w_theta[tid] = a.w[kn * z + tdb_param_entry(a.T, z, a.P.dt_idx, tid)];
+        // initial values: x = x_k, Phi = I (d = w_x(k) in a J w call), everything else (padding included) 0
         for (size_t e = tid; e < (size_t)np * Ctot; e += 256) {
             const int c = (int)(e / np), r = (int)(e - (size_t)c * np);
             double v = 0.0;
             if (c == 0) v = r < n ? zk[a.T.x_off + r] : 0.0;
+            else if (PROD && need == 3 && c == 1) v = r < n ? a.w[kn * z + a.T.x_off + r] : 0.0;
             else if (c >= L.Cv) v = (c - L.Cv == r && r < n) ? 1.0 : 0.0;
             Y[e] = v;
         }
         __syncthreads();
 
         const double h = 1.0 / a.T.substeps;
-        const int njet_fwd = need == 0 ? 1 : (need == 1 ? 1 + p : 1 + p + P2);
+        const int njet_fwd = PROD ? 1 + p : (need == 0 ? 1 : (need == 1 ? 1 + p : 1 + p + P2));
         for (int step = 0; step < a.T.substeps; ++step) {
             for (int stage = 0; stage < 4; ++stage) {
                 const double tau = (step + (stage == 0 ? 0.0 : (stage == 3 ? 1.0 : 0.5))) * h;
@@ -196,8 +216,8 @@ __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
                 double* OUT = stage == 0 ? TA : (stage == 1 ? TB : (stage == 2 ? TA : Y));
                 if (stage != 2) form_m0(tau, njet_fwd, a.Bp);   // stages 1 and 2 share their time
                 // U_q = B_q y for the vectors whose jets enter this call: x (Jacobian), x and x_b (Hessian)
-                if (need == 1) vec_pass(a.Bp, IN);
-                else if (need == 2) {
+                if (PROD || need == 1) vec_pass(a.Bp, IN);
+                else if (!PROD && need == 2) {
                     for (int q = 0; q < Q; ++q)
                         mm_cols<TM>(a.Bp + q * nn, IN, np, TDBM_VEC, smem,
                                     [&](int row, int col, double v) { U[((size_t)q * TDBM_VEC + col) * np + row] = v; });
@@ -207,12 +227,12 @@ __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
                 const double w_tmp = stage == 2 ? h : 0.5 * h;
                 // K = M0 IN (+ the jets' terms), then the RK4 update of this stage
                 mm_cols<TM>(M0, IN, np, Ctot, smem, [&](int row, int col, double K) {
-                    if (need >= 1 && col >= 1 && col <= p) {
-                        const double* cf = coefs + (size_t)col * Q;   // jet 1 + b, b = col - 1
+                    if (need >= 1 && col >= 1 && col <= pj) {
+                        const double* cf = coefs + (size_t)(row1 + col - 1) * Q;   // jet 1 + b, b = col - 1 (J w: the directional row)
                         double s = 0.0;
                         for (int q = 0; q < Q; ++q) s += cf[q] * U[(size_t)q * ucols * np + row];
                         K += s;
-                    } else if (need == 2 && col > p && col < C) {
+                    } else if (!PROD && need == 2 && col > p && col < C) {
                         const int e = col - 1 - p, aa = pair_a[e], bb = pair_b[e];
                         const double *ca = coefs + (size_t)(1 + aa) * Q, *cb = coefs + (size_t)(1 + bb) * Q, *cab = coefs + (size_t)(1 + p + e) * Q;
                         double s = 0.0;
@@ -232,6 +252,51 @@ __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
             }
         }
 
+        if (PROD) {
+            if (need == 3) {
+                for (int r = tid; r < n; r += 256) a.out[a.T.row_off + kn * n + r] = a.w[(kn + 1) * z + a.T.x_off + r] - Y[np + r];
+            } else {
+                const double* wk = a.w + a.T.row_off + kn * n;
+                double* out = a.out + kn * (int64_t)(n + p);
+                for (int b = tid; b < p; b += 256) {   // w_k' (dPhi_k / dtheta_b) x_k
+                    double s = 0.0;
+                    const double* xb = Y + (size_t)(1 + b) * np;
+                    for (int r = 0; r < n; ++r) s += wk[r] * xb[r];
+                    out[n + b] = s;
+                }
+                // lambda = Phi_k' w_k: one adjoint column, backward through the steps; ubar = sum_q c_q (B_q' kbar), q in order
+                double* W = TA;
+                double* WN = TB;
+                double* KB = ACC;
+                for (int e = tid; e < np; e += 256) { W[e] = e < n ? wk[e] : 0.0; UB[e] = 0.0; }
+                __syncthreads();
+                for (int step = a.T.substeps - 1; step >= 0; --step) {
+                    for (int e = tid; e < np; e += 256) WN[e] = W[e];
+                    for (int stage = 3; stage >= 0; --stage) {
+                        const double tau = (step + (stage == 0 ? 0.0 : (stage == 3 ? 1.0 : 0.5))) * h;
+                        if (stage != 1)   // stages 2 and 1 share their time
+                            for (int q = tid; q < Q; q += 256) coefs[q] = tdbm_coef(a.T, zk, zk1, tk, dt, tau, p, 0, q);
+                        const double cw = (stage == 3 || stage == 0) ? h / 6.0 : h / 3.0;
+                        const double cu = stage == 3 ? 0.0 : (stage == 2 ? h : 0.5 * h);
+                        for (int e = tid; e < np; e += 256) KB[e] = cw * W[e] + (cu != 0.0 ? cu * UB[e] : 0.0);
+                        __syncthreads();
+                        vec_pass(a.BpT, KB);   // U_q = B_q' kbar
+                        for (int r = tid; r < np; r += 256) {
+                            double u = 0.0;
+                            for (int q = 0; q < Q; ++q) u += coefs[q] * U[(size_t)q * np + r];
+                            UB[r] = u;
+                            WN[r] += u;
+                        }
+                        __syncthreads();
+                    }
+                    for (int e = tid; e < np; e += 256) W[e] = WN[e];
+                    __syncthreads();
+                }
+                for (int i = tid; i < n; i += 256) out[i] = W[i];
+            }
+            __syncthreads();   // the slot is reused by this workgroup's next interval
+            continue;
+        }
         // ---- outputs (blocks of a generic integrator, laid out as k_tdb writes them)
         for (int r = tid; r < n; r += 256) a.vals[kn * n + r] = zk1[a.T.x_off + r] - Y[r];
         auto zz_of = [&](int b) { return b < m ? a.T.u_off + b : (b == m ? a.T.t_off : (b == m + 1 ? a.P.dt_idx : z + a.T.u_off + (b - m - 2))); };
@@ -343,10 +408,11 @@ double tdb_mfma_flops(const KTdb& T, int need) {
     const double np2 = (double)L.np * L.np, S = T.substeps;
     const double form = 2.0 * L.Q * np2;
     double fwd = 4.0 * 2.0 * np2 * L.Ctot + 3.0 * form;
-    if (need == 1) fwd += 4.0 * 2.0 * L.Q * np2;
+    if (need == 1 || need >= 3) fwd += 4.0 * 2.0 * L.Q * np2;
     if (need == 2) fwd += 4.0 * 2.0 * L.Q * np2 * TDBM_VEC;
     double bwd = 0.0;
     if (need == 2) bwd = 4.0 * (2.0 * np2 * TDBM_VEC + 2.0 * L.Q * np2) + 3.0 * form;
+    if (need == 4) bwd = 4.0 * 2.0 * L.Q * np2;   // the one-column adjoint: vector passes only
     return S * (fwd + bwd);
 }
 
@@ -359,8 +425,21 @@ hipError_t launch_tdb_mfma(hipStream_t st, const KProb& P, const KTdb& T, const 
     a.P = P; a.T = T; a.Bp = Bp; a.BpT = BpT; a.Z = dZ; a.mu = dmu; a.need = need; a.i_lo = i_lo; a.count = count;
     a.vals = vals; a.jac = jac; a.hess = hess; a.scratch = scratch; a.scratch_stride = (int64_t)scratch_stride;
     const unsigned grid = (unsigned)std::min<int64_t>(count, resident);
-    if (pad32(T.n) % 64 == 0) hipLaunchKernelGGL(k_tdb_mfma<64>, dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_tdb_mfma<32>, dim3(grid), dim3(256), 0, st, a);
+    if (pad32(T.n) % 64 == 0) hipLaunchKernelGGL((k_tdb_mfma<64, false>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_tdb_mfma<32, false>), dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tdb_mfma_product(hipStream_t st, const KProb& P, const KTdb& T, const double* Bp, const double* BpT, const double* dZ,
+                                   const double* dw, int need, double* out, double* scratch, size_t scratch_stride, int resident) {
+    if (P.K <= 0) return hipSuccess;
+    if ((need != 3 && need != 4) || resident < 1 || tdbm_layout(T, need).total > scratch_stride) return hipErrorInvalidValue;
+    TdbmArgs a{};
+    a.P = P; a.T = T; a.Bp = Bp; a.BpT = BpT; a.Z = dZ; a.need = need; a.i_lo = 0; a.count = P.K;
+    a.scratch = scratch; a.scratch_stride = (int64_t)scratch_stride; a.w = dw; a.out = out;
+    const unsigned grid = (unsigned)std::min<int64_t>(P.K, resident);
+    if (pad32(T.n) % 64 == 0) hipLaunchKernelGGL((k_tdb_mfma<64, true>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_tdb_mfma<32, true>), dim3(grid), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

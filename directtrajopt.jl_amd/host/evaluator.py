@@ -490,7 +490,9 @@ class Evaluator:
 
     def set_option(self, name, value):
         """dto_set_option: ``reuse_forward_sweep`` (solver loops evaluate g, J, H at the same point), ``expm_form``
-        (0 = by cost, 2 / 3 = two- / three-product form of the Jacobian's matrix exponential)."""
+        (0 = by cost, 2 / 3 = two- / three-product form of the Jacobian's matrix exponential), ``tdb_matrix_free_products`` (0 | 1,
+        default 0: 1 evaluates J w / J' w of dense device TimeDependentBilinearIntegrators without forming a Jacobian -- the scheme
+        applied to two vectors, or to 1 + p forward vectors and one adjoint vector); include/dto_engine.h lists every option."""
         self._check(self._lib.dto_set_option(self._h, name.encode(), int(value)))
 
     # ---- measurement

@@ -430,6 +430,13 @@ int dto_bind_output_dev(dto_handle* h, int32_t vector, double* dptr);
  *   "host_xfer_check" (default 0): every host-pointer dto_eval_jacobian / dto_eval_hessian also copies the whole device slab and
  *   compares it bit for bit with the vector it assembled from the variable runs and the constants; a difference (a kernel that
  *   wrote an entry the hand-off plan does not list) fails the call.  The repository's GPU tests run with it on.
+ *   "tdb_matrix_free_products" (default 0): 1 makes dto_eval_jacobian_product / _transpose_product (and their _dev forms) of a handle
+ *   whose TimeDependentBilinearIntegrators all run on a dense device path (1..256 states without DTO_FLAG_BLOCK_GENERATORS structure)
+ *   matrix-free: J w is the discrete scheme applied to two vectors, J' w to 1 + p forward vectors and one adjoint vector -- no
+ *   propagator block, no staged Jacobian block, no value slab; a product then costs about a constraint call, not a Jacobian call.
+ *   Such a handle may also hold bilinear and derivative integrators and built-in knot constraints; external integrators and
+ *   constraints, and integrators on the structured time-dependent path, keep the slab route whatever the option says.  0 leaves every
+ *   call as it was; values other than 0 and 1 are refused.  Results of the two routes agree to rounding (another summation order).
  *   "debug_bad_launch": TUNING builds only (libdto_engine_t.so) -- 1 gives the next callbacks' kernels an invalid launch
  *   configuration, which must come back as a non-zero return code with text (test of the error convention); the product
  *   library refuses the name. */
@@ -459,7 +466,9 @@ int dto_profile_reset(dto_handle* h);
  * generators), "assembly" (the writers of the bilinear Jacobian's tangent columns), "hess_product" (the Hessian-vector products'
  * gather into their compact copy and the product launches; the Hessian they assemble counts under its own names), "share" (the
  * copies of the leader's -E_k blocks to the followers of a DTO_FLAG_SHARED_GENERATORS group; its bytes are the bytes WRITTEN, one
- * block per follower and interval -- each launch reads a further block per interval -- and stay out of the third output of "all").
+ * block per follower and interval -- each launch reads a further block per interval -- and stay out of the third output of "all"),
+ * "tdb_product" (the matrix-free J w / J' w of time-dependent integrators, option "tdb_matrix_free_products": one record per
+ * integrator and product, flops as executed with padding; these launches do not count under "tdb_mfma").
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the
  * third output is the launches' algorithmic BYTES (what they must read and write), not FLOPs.
  * "hess_product_setup" returns the host milliseconds of the products' index build (once per handle), 0 launches, and the device

@@ -17,6 +17,12 @@ the same problem, through host pointers, one call each.  One JSON line per shape
                                                               # handles alternated in one process; order 1; 72 x 500, 128 x 500,
                                                               # 162 x 250 both ways, 512 x 100 flagged only (the dense kernels stop
                                                               # at 256 states)
+    python tools/tdb_time.py --products 1 --shapes 4x1000,64x1000,128x500,256x250 --orders 1 --host ""
+                                                              # adds the device-pointer J w / J' w with the handle option
+                                                              # "tdb_matrix_free_products" on (csrc/dto_tdb.hip and dto_tdb_mfma.hip,
+                                                              # product modes) next to eval_constraint and the Jacobian;
+                                                              # --products-route slab leaves the option alone (the slab route: what
+                                                              # a build without the option does, e.g. one named by DTO_ENGINE_LIB)
 """
 import argparse
 import json
@@ -121,11 +127,13 @@ def timed(fn, reps):
     return statistics.median(one_call_ms(fn) for _ in range(reps))
 
 
-def measure_device(prob, reps, sigma=0.7):
+def measure_device(prob, reps, sigma=0.7, products=False, route="matrix_free"):
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev).cuda_stream
     ev = dto_amd.Evaluator(prob, eval_hessian=True)
     try:
+        if products and route == "matrix_free":
+            ev.set_option("tdb_matrix_free_products", 1)
         Z = torch.from_numpy(prob.trajectory.vec()).to(dev)
         mu = torch.randn(ev.n_constraints, generator=torch.Generator(device="cpu").manual_seed(1), dtype=torch.float64).to(dev)
         con = torch.empty(ev.n_constraints, dtype=torch.float64, device=dev)
@@ -135,10 +143,19 @@ def measure_device(prob, reps, sigma=0.7):
                  "jacobian": lambda: ev.eval_jacobian_dev(Z.data_ptr(), J.data_ptr(), st),
                  "hessian": lambda: ev.eval_hessian_dev(Z.data_ptr(), sigma, mu.data_ptr(), H.data_ptr(), st)}
         out = {}
+        if products:
+            gen = torch.Generator(device="cpu").manual_seed(2)
+            w = torch.randn(ev.n_variables, generator=gen, dtype=torch.float64).to(dev)
+            y = torch.empty(ev.n_constraints, dtype=torch.float64, device=dev)
+            yt = torch.empty(ev.n_variables, dtype=torch.float64, device=dev)
+            del calls["hessian"]
+            calls["jw"] = lambda: ev.eval_jacobian_product_dev(Z.data_ptr(), w.data_ptr(), y.data_ptr(), st)
+            calls["jtw"] = lambda: ev.eval_jacobian_transpose_product_dev(Z.data_ptr(), mu.data_ptr(), yt.data_ptr(), st)
+            out["products_route"] = route
         for name, fn in calls.items():
             out[name + "_ms"] = round(timed(fn, reps), 4)
             ev.profile_enable(True); ev.profile_reset(); fn(); torch.cuda.synchronize()
-            ms, launches, fl = ev.profile_get("tdb_mfma")
+            ms, launches, fl = ev.profile_get("tdb_product" if products and route == "matrix_free" and name in ("jw", "jtw") else "tdb_mfma")
             ev.profile_enable(False)
             out[name + "_kernel_ms"] = round(ms, 4)
             out[name + "_kernel_launches"] = launches
@@ -180,6 +197,8 @@ def main():
     ap.add_argument("--small", type=int, default=0, help="1: 4 .. 64 states (k_tdb), 2 drives, order 1, host pointers; nothing else")
     ap.add_argument("--block", type=int, default=0, help="1: replicated-block generators, flagged against unflagged handles; nothing else")
     ap.add_argument("--block-shapes", default="6x500,8x500,9x250,16x100", help="with --block: comma-separated levels x knots (states = 2 levels^2)")
+    ap.add_argument("--products", type=int, default=0, help="1: time the device-pointer J w / J' w (option tdb_matrix_free_products on) instead of the Hessian")
+    ap.add_argument("--products-route", default="matrix_free", choices=["matrix_free", "slab"], help="with --products: slab leaves the option alone")
     a = ap.parse_args()
     if a.block:
         for s in [x for x in a.block_shapes.split(",") if x]:
@@ -199,7 +218,7 @@ def main():
         n, N = (int(x) for x in s.lower().split("x"))
         for order in (int(x) for x in a.orders.split(",")):
             out = {"n": n, "knots": N, "drives": a.drives, "substeps": a.substeps, "order": order}
-            out.update(measure_device(problem(n, N, a.drives, order, a.substeps), a.reps))
+            out.update(measure_device(problem(n, N, a.drives, order, a.substeps), a.reps, products=bool(a.products), route=a.products_route))
             print(json.dumps(out), flush=True)
     if a.host:
         n, N = (int(x) for x in a.host.lower().split("x"))
