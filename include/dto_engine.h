@@ -55,7 +55,7 @@ extern "C" {
                                        x_{k+1} - Phi_k x_k of  dx/dtau = dt_k G(u(tau), t_k + tau dt_k) x,  tau in [0,1], by
                                        classical RK4 with `substeps` fixed steps (the reference integrates adaptively with
                                        Tsit5), controls held (spline_order 0) or interpolated linearly to u_{k+1} (1), with the
-                                       exact first and second derivatives of that discrete map.  Device range: 1..256 states
+                                       exact first and second derivatives of that discrete map.  Device range: 0..7 drives, 1..256 states
                                        (1..64: a scalar kernel; 65..256: FP64 matrix-core products), substeps >= 1, and a
                                        coefficient table (1 + p + p (p+1) / 2) (m+1) (1 + n_mod) <= 6144 with
                                        p = m + 2 (+ m for spline_order 1); dto_create refuses anything else and names the

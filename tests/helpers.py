@@ -14,8 +14,9 @@ def to_engine(prob: O.Problem, closure_derivatives="numeric", tdb_on_device=True
     for it in prob.integrators:
         if isinstance(it, O.TimeDependentBilinearIntegrator):
             ranges[(it.x_off, it.x_dim)] = None
-            ranges[(it.u_off, it.u_dim)] = None
-            ranges[(it.t_off, 1)] = None
+            if it.u_dim:
+                ranges[(it.u_off, it.u_dim)] = None
+            ranges[(it.t_off, 1)] = None     # (t_off == dt_idx: the timestep's own component, named once)
             continue
         if it.kind == "external":
             continue
@@ -49,6 +50,9 @@ def to_engine(prob: O.Problem, closure_derivatives="numeric", tdb_on_device=True
             # the DEVICE integrator (csrc/dto_tdb.hip) for the same generator family; `tdb_on_device=False` routes the same
             # closure through the host-evaluated merge path instead
             fam = dto_amd.ModulatedGenerators(it.G, it.mods)
+            if it.u_dim == 0:
+                integ.append(_tdb_without_drives(fam, it, names, traj, tdb_on_device))
+                continue
             integ.append(dto_amd.TimeDependentBilinearIntegrator(fam, names[(it.x_off, it.x_dim)], names[(it.u_off, it.u_dim)],
                                                                  names[(it.t_off, 1)], traj, spline_order=it.spline_order,
                                                                  substeps=it.substeps, on_device=tdb_on_device))
@@ -148,6 +152,20 @@ def to_engine(prob: O.Problem, closure_derivatives="numeric", tdb_on_device=True
         k.dim = k.times.size
         cons.append(k)
     return dto_amd.DirectTrajOptProblem(traj, obj, integ, constraints=cons)
+
+
+def _tdb_without_drives(fam, it, names, traj, on_device):
+    """The host mirror's TimeDependentBilinearIntegrator for a family without drives (the engine's ABI takes 0..7): the mirror's
+    constructor wants a control component, a NamedTrajectory has none of dimension 0, so the description is filled in directly."""
+    if not on_device:
+        raise NotImplementedError
+    o = dto_amd.TimeDependentBilinearIntegrator.__new__(dto_amd.TimeDependentBilinearIntegrator)
+    o.family, o.G, o.spline_order, o.substeps = fam, fam, int(it.spline_order), int(it.substeps)
+    o.x_name, o.u_name, o.t_name = names[(it.x_off, it.x_dim)], None, names[(it.t_off, 1)]
+    o.x_off, o.u_off, o.t_off, o.x_dim, o.u_dim = it.x_off, 0, it.t_off, it.x_dim, 0
+    o.f = o.jac = o.hess = None
+    o.dim, o.var_dim = it.x_dim * (traj.N - 1), 2 * traj.dim
+    return o
 
 
 TOL, TOL_H = 1e-10, 1e-8  # SURVEY.md §8c: values / Jacobian, Hessian

@@ -69,7 +69,11 @@ def _evaluator(pe, option=1, **kw):
 
 def check_case(shape, **kw):
     """Parity of the host and the device forms at TOL, and the two forms bit-equal."""
-    c = case(shape)
+    check_built(case(shape), shape, **kw)
+
+
+def check_built(c, shape, **kw):
+    """check_case on a prepared case `c` (the keys of `case`); `shape` labels the output."""
     ev = _evaluator(c["pe"], **kw)
     try:
         yh, th = host_products(ev, c["Z"], c["w"], c["wt"])
