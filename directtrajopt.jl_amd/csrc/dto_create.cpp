@@ -5,6 +5,7 @@
 // of the stages and touches no GPU.  Device allocations, uploads and the kernel launches of creation (the generator product
 // norms, then the generator-subspace basis) keep one fixed order: the pairing store's decision reads the free device memory.
 #include "dto_handle.h"
+#include "dto_tdb_scheme.h"
 
 #include <cmath>
 #include <cstring>
@@ -999,7 +1000,7 @@ void alloc_tdb(dto_handle* h) {
             continue;
         }
         // the product modes (need 3, 4) share the scratch below with the value calls; their J' w stages n + p doubles per interval
-        const int p = t.k.m + 2 + (t.k.order ? t.k.m : 0);
+        const int p = tdb_num_params(t.k.m, t.k.order);
         t.d_jtv = own(h, dalloc<double>(std::max<size_t>(K, 1) * (n + (size_t)p)));
         if (t.mfma) {
             // sized by the persistent grid (two workgroups per compute unit), not by the number of intervals

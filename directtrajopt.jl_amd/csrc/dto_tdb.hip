@@ -103,55 +103,7 @@ __global__ void __launch_bounds__(256) k_tdb(TdbArgs a) {
     auto form_jets = [&](double tau, int njet) {
         for (int e = tid; e < njet * Q; e += 256) {
             const int which = e / Q, q = e - which * Q;
-            const int j = q / (1 + nmod), c = q - j * (1 + nmod);
-            // which: 0 value; 1 + b first derivative; 1 + p + pair(a, b) second derivative
-            int b1 = -1, b2 = -1;
-            if (which >= 1 && which <= p) b1 = which - 1;
-            else if (which > p) {
-                int rem = which - 1 - p, aa = 0;
-                while (rem >= p - aa) { rem -= p - aa; ++aa; }
-                b1 = aa; b2 = aa + rem;
-            }
-            // a_j and its derivative slots: wk = d a_j / d u_kj, wk1 = d a_j / d u_{k+1,j}
-            double aj = 1.0, wk = 0.0, wk1 = 0.0;
-            if (j >= 1) {
-                const double uk = zk[a.T.u_off + j - 1];
-                if (order) { const double uk1 = zk1[a.T.u_off + j - 1]; aj = (1.0 - tau) * uk + tau * uk1; wk = 1.0 - tau; wk1 = tau; }
-                else { aj = uk; wk = 1.0; }
-            }
-            double ph = 1.0, ph1 = 0.0, ph2 = 0.0;
-            if (c >= 1) {
-                const double om = a.T.mod_omega[c - 1], arg = om * (tk + tau * dt);
-                const double cs = cos(arg), sn = sin(arg);
-                if (a.T.mod_kind[c - 1] == 1) { ph = cs; ph1 = -om * sn; ph2 = -om * om * cs; }
-                else { ph = sn; ph1 = om * cs; ph2 = -om * om * sn; }
-            }
-            // s = dt * a_j * phi(t_k + tau dt) and its derivatives; parameter classes: 0 = u_k (drive jj), 1 = t, 2 = dt,
-            // 3 = u_{k+1} (drive jj)
-            auto cls = [&](int b, int& jj) { if (b < m) { jj = b + 1; return 0; } if (b == m) { jj = -1; return 1; }
-                                             if (b == m + 1) { jj = -1; return 2; } jj = b - m - 1; return 3; };
-            double coef;
-            if (which == 0) coef = dt * aj * ph;
-            else if (b2 < 0) {
-                int jj; const int k1 = cls(b1, jj);
-                if (k1 == 0) coef = jj == j ? dt * wk * ph : 0.0;
-                else if (k1 == 3) coef = jj == j ? dt * wk1 * ph : 0.0;
-                else if (k1 == 1) coef = dt * aj * ph1;
-                else coef = aj * ph + dt * aj * tau * ph1;
-            } else {
-                int j1, j2; const int k1 = cls(b1, j1), k2 = cls(b2, j2);
-                const bool u1 = k1 == 0 || k1 == 3, u2 = k2 == 0 || k2 == 3;
-                if (u1 && u2) coef = 0.0;
-                else if (u1 || u2) {
-                    const int ju = u1 ? j1 : j2, ku = u1 ? k1 : k2, ko = u1 ? k2 : k1;
-                    const double w = ku == 0 ? wk : wk1;
-                    if (ju != j) coef = 0.0;
-                    else coef = ko == 1 ? dt * w * ph1 : w * (ph + dt * tau * ph1);
-                } else if (k1 == 1 && k2 == 1) coef = dt * aj * ph2;
-                else if (k1 == 2 && k2 == 2) coef = 2.0 * aj * tau * ph1 + dt * aj * tau * tau * ph2;
-                else coef = aj * ph1 + dt * aj * tau * ph2;   // (t, dt)
-            }
-            coefs[e] = coef;
+            coefs[e] = tdbm_coef(a.T, zk, zk1, tk, dt, tau, p, which, q);
         }
         __syncthreads();
         for (int e = tid; e < njet * nn; e += 256) {
@@ -219,7 +171,7 @@ __global__ void __launch_bounds__(256) k_tdb(TdbArgs a) {
     // ---- outputs (blocks of a generic integrator: _integrators.jl:49-77)
     for (int r = tid; r < n; r += 256) a.vals[kn * n + r] = zk1[a.T.x_off + r] - Y[c_x * n + r];
     if (need < 1) return;
-    auto zz_of = [&](int b) { return b < m ? a.T.u_off + b : (b == m ? a.T.t_off : (b == m + 1 ? a.P.dt_idx : z + a.T.u_off + (b - m - 2))); };
+    auto zz_of = [&](int b) { return tdb_param_entry(a.T, z, a.P.dt_idx, b); };
     if (need == 1) {
         double* J = a.jac + kn * (int64_t)n * 2 * z;
         for (int e = tid; e < n * 2 * z; e += 256) J[e] = 0.0;
@@ -486,20 +438,18 @@ __global__ void __launch_bounds__(256) k_tdb_jtv_place(KProb P, KTdb T, const do
 }  // namespace
 
 bool tdb_supported(const KTdb& T) {
-    const int p = T.m + 2 + (T.order ? T.m : 0);
-    const long nM = 1 + p + (long)p * (p + 1) / 2;
-    return T.n >= 1 && T.n <= 64 && T.nmod >= 0 && T.substeps >= 1 && nM * (T.m + 1) * (1 + T.nmod) <= TDB_MAX_COEFS;
+    return T.n >= 1 && T.n <= 64 && T.nmod >= 0 && T.substeps >= 1 && tdb_table_fits(T.m, T.order, T.nmod);
 }
 
 size_t tdb_scratch_doubles(const KTdb& T, int need) {
-    const int n = T.n, m = T.m, p = m + 2 + (T.order ? m : 0);
-    const size_t P2 = (size_t)p * (p + 1) / 2;
+    const int n = T.n, p = tdb_num_params(T.m, T.order);
+    const size_t P2 = tdb_num_pairs(p);
     if (need >= 3) {   // product modes: x, d | x, x_b, one jet per column
         const size_t Cp = need == 3 ? 2 : 1 + p;
         return 4 * Cp * n + Cp * (size_t)n * n;
     }
     const size_t C = need == 0 ? 1 : (need == 1 ? 1 + n + p : (tdb_uses_adjoint(n) ? 1 + p + P2 : 1 + n + p + (size_t)n * p + P2));
-    const size_t nM = need == 0 ? 1 : (need == 1 ? 1 + p : 1 + p + (size_t)p * (p + 1) / 2);
+    const size_t nM = need == 0 ? 1 : (need == 1 ? 1 + p : 1 + p + P2);
     return 4 * C * n + nM * (size_t)n * n;
 }
 
@@ -516,7 +466,7 @@ hipError_t launch_tdb(hipStream_t st, const KProb& P, const KTdb& T, const doubl
 // flops of one interval of a product call as executed: per stage the M and jet products of every column, per stage time the jets
 double tdb_product_flops(const KTdb& T, int need) {
     const double n2 = (double)T.n * T.n, S = T.substeps;
-    const int p = T.m + 2 + (T.order ? T.m : 0), C = need == 3 ? 2 : 1 + p, Q = (T.m + 1) * (1 + T.nmod);
+    const int p = tdb_num_params(T.m, T.order), C = need == 3 ? 2 : 1 + p, Q = tdb_num_shared(T.m, T.nmod);
     double fl = 4.0 * 2.0 * n2 * (2 * C - 1) + 3.0 * 2.0 * Q * n2 * C;
     if (need == 4) fl += 4.0 * 2.0 * n2 + 3.0 * 2.0 * Q * n2;
     return S * fl;

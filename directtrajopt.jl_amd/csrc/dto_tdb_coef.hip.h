@@ -3,21 +3,18 @@
 #pragma once
 
 #include "dto_kernels.h"
+#include "dto_tdb_scheme.h"
 
 namespace dto {
 
-// Scalar coefficient of B_q in one jet of M(tau) = dt sum_j a_j(tau) (G_j + sum_c phi_c(t) H_cj), t = t_k + tau dt -- the table of
-// k_tdb's form_jets.  which: 0 value; 1 + b first derivative; 1 + p + pair(a, b) second derivative (a <= b, row-major triangle).
+// Scalar coefficient of B_q in one jet of M(tau) = dt sum_j a_j(tau) (G_j + sum_c phi_c(t) H_cj), t = t_k + tau dt -- the one table
+// of all three kernels.  which: 0 value; 1 + b first derivative; 1 + p + tdb_pair_rank(a, b) second derivative (a <= b).
 __device__ inline double tdbm_coef(const KTdb& T, const double* zk, const double* zk1, double tk, double dt, double tau, int p, int which, int q) {
     const int m = T.m, nmod = T.nmod;
     const int j = q / (1 + nmod), c = q - j * (1 + nmod);
     int b1 = -1, b2 = -1;
     if (which >= 1 && which <= p) b1 = which - 1;
-    else if (which > p) {
-        int rem = which - 1 - p, aa = 0;
-        while (rem >= p - aa) { rem -= p - aa; ++aa; }
-        b1 = aa; b2 = aa + rem;
-    }
+    else if (which > p) tdb_pair_unrank(which - 1 - p, p, &b1, &b2);
     // a_j and its derivative slots: wk = d a_j / d u_kj, wk1 = d a_j / d u_{k+1,j}
     double aj = 1.0, wk = 0.0, wk1 = 0.0;
     if (j >= 1) {
@@ -56,8 +53,6 @@ __device__ inline double tdbm_coef(const KTdb& T, const double* zk, const double
     if (k1 == 2 && k2 == 2) return 2.0 * aj * tau * ph1 + dt * aj * tau * tau * ph2;
     return aj * ph1 + dt * aj * tau * ph2;   // (t, dt)
 }
-
-constexpr int TDB_MAX_COEFS = 6144;  // entries of the table, (1 + p + p (p+1)/2) * Q (tdb_supported, tdb_mfma_refusal)
 
 // Entry of the stacked pair [z_k ; z_{k+1}] that parameter b of theta = [u_k (m), t_k, dt_k, u_{k+1} (m, order 1)] lives in: where a
 // J w mode reads its component of w (relative to knot k) and where a J' w mode lands its term.  Two parameters may name one entry

@@ -46,9 +46,9 @@ inline __host__ __device__ TdbkLayout tdbk_layout(const KTdb& T, const KKron& K,
     TdbkLayout L;
     L.bp = K.bp;
     L.cp = pad16(K.rw);
-    L.p = T.m + 2 + (T.order ? T.m : 0);
-    L.P2 = L.p * (L.p + 1) / 2;
-    L.Q = (T.m + 1) * (1 + T.nmod);
+    L.p = tdb_num_params(T.m, T.order);
+    L.P2 = tdb_num_pairs(L.p);
+    L.Q = tdb_num_shared(T.m, T.nmod);
     L.G = need == 0 ? 1 : (need == 1 ? 1 + L.p : 1 + L.p + L.P2);   // column groups of the forward pass
     L.ctot = L.G * L.cp + (need == 1 ? L.bp : 0);
     L.ucols = need == 0 ? 0 : (need == 1 ? L.cp : (1 + L.p) * L.cp);  // columns whose U_q enter this call's jets
@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(256) k_tdb_kron(TdbkArgs a) {
     constexpr int BP = 16 * MT;
     constexpr int LD = (MT & 1) ? BP : BP + 16;   // as k_kron: LD mod 32 == 16
     const TdbkLayout L = tdbk_layout(a.T, a.K, a.need);
-    const int n = a.T.n, m = a.T.m, z = a.P.z, need = a.need;
+    const int n = a.T.n, z = a.P.z, need = a.need;
     const int bw = a.K.bw, rw = a.K.rw, bf = a.K.b;
     const int cp = L.cp, p = L.p, P2 = L.P2, Q = L.Q, G = L.G, ctot = L.ctot, ucols = L.ucols;
     const int cpt = cp / 16;
@@ -115,9 +115,9 @@ __global__ void __launch_bounds__(256) k_tdb_kron(TdbkArgs a) {
     __shared__ double sM0[BP * LD];
     __shared__ unsigned char pair_a[TDBK_MAX_PAIRS], pair_b[TDBK_MAX_PAIRS];
     for (int e = tid; e < P2; e += 256) {
-        int rem = e, aa = 0;
-        while (rem >= p - aa) { rem -= p - aa; ++aa; }
-        pair_a[e] = (unsigned char)aa; pair_b[e] = (unsigned char)(aa + rem);
+        int aa, ab;
+        tdb_pair_unrank(e, p, &aa, &ab);
+        pair_a[e] = (unsigned char)aa; pair_b[e] = (unsigned char)ab;
     }
     double* S = a.scratch + (int64_t)blockIdx.x * a.scratch_stride;
     double* Y = S + L.oY;
@@ -235,7 +235,7 @@ __global__ void __launch_bounds__(256) k_tdb_kron(TdbkArgs a) {
 
         // ---- outputs: the owned entries of the staged blocks, each assigned by one thread
         for (int e = tid; e < n; e += 256) a.vals[kn * n + e] = zk1[a.T.x_off + e] - at_state(Y, 0, e);
-        auto zz_of = [&](int b) { return b < m ? a.T.u_off + b : (b == m ? a.T.t_off : (b == m + 1 ? a.P.dt_idx : z + a.T.u_off + (b - m - 2))); };
+        auto zz_of = [&](int b) { return tdb_param_entry(a.T, z, a.P.dt_idx, b); };
         if (need == 1) {
             double* J = a.jac + kn * (int64_t)n * 2 * z;
             // -(I_r (x) Phi~): the diagonal blocks of the finest size (what lies outside them is a constant zero)
@@ -331,11 +331,9 @@ __global__ void __launch_bounds__(256) k_tdb_kron(TdbkArgs a) {
 }  // namespace
 
 bool tdb_kron_supported(const KTdb& T, const KKron& K) {
-    const int p = T.m + 2 + (T.order ? T.m : 0);
-    const long nM = 1 + p + (long)p * (p + 1) / 2;
     return K.r >= 2 && K.b <= 64 && T.n > 32 && T.n <= 512 && K.bw >= 1 && K.bw <= K.bp && K.bp >= 16 && K.bp <= 64 && K.bp % 16 == 0 &&
-           K.rw >= 1 && K.bw * K.rw == T.n && T.substeps >= 1 && T.nmod >= 0 && nM * (T.m + 1) * (1 + T.nmod) <= TDB_MAX_COEFS &&
-           p * (p + 1) / 2 <= TDBK_MAX_PAIRS;
+           K.rw >= 1 && K.bw * K.rw == T.n && T.substeps >= 1 && T.nmod >= 0 && tdb_table_fits(T.m, T.order, T.nmod) &&
+           tdb_num_pairs(tdb_num_params(T.m, T.order)) <= TDBK_MAX_PAIRS;
 }
 
 size_t tdb_kron_scratch_doubles(const KTdb& T, const KKron& K, int need) { return tdbk_layout(T, K, need).total; }

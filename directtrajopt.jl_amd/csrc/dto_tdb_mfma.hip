@@ -57,9 +57,9 @@ struct TdbmLayout {
 inline __host__ __device__ TdbmLayout tdbm_layout(const KTdb& T, int need) {
     TdbmLayout L;
     L.np = pad32(T.n);
-    L.p = T.m + 2 + (T.order ? T.m : 0);
-    L.P2 = L.p * (L.p + 1) / 2;
-    L.Q = (T.m + 1) * (1 + T.nmod);
+    L.p = tdb_num_params(T.m, T.order);
+    L.P2 = tdb_num_pairs(L.p);
+    L.Q = tdb_num_shared(T.m, T.nmod);
     // meaningful columns of the vector block (need 3: x, d; need 4: x, x_b)
     L.C = need == 0 ? 1 : (need == 3 ? 2 : (need == 1 || need == 4 ? 1 + L.p : 1 + L.p + L.P2));
     L.Cv = pad32(L.C);
@@ -125,7 +125,7 @@ __device__ __forceinline__ void mm_cols(const double* __restrict__ A, const doub
 // PROD: the instantiation that serves need 3 and 4 and nothing else (the value modes' code is unchanged by it)
 template <int TM, bool PROD>
 __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
-    const int n = a.T.n, m = a.T.m, z = a.P.z, need = a.need;
+    const int n = a.T.n, z = a.P.z, need = a.need;
     const TdbmLayout L = tdbm_layout(a.T, need);
     const int np = L.np, p = L.p, P2 = L.P2, Q = L.Q, C = L.C, Ctot = L.Ctot, ucols = L.ucols;
     const int tid = threadIdx.x;
@@ -137,9 +137,9 @@ __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
     // first-order jets that enter the epilogue of the forward tile, and the coefficient row of the first of them
     const int pj = PROD && need == 3 ? 1 : p, row1 = PROD && need == 3 ? 1 + p : 1;
     for (int e = tid; e < (PROD ? 0 : P2); e += 256) {
-        int rem = e, aa = 0;
-        while (rem >= p - aa) { rem -= p - aa; ++aa; }
-        pair_a[e] = (unsigned char)aa; pair_b[e] = (unsigned char)(aa + rem);
+        int aa, bb;
+        tdb_pair_unrank(e, p, &aa, &bb);
+        pair_a[e] = (unsigned char)aa; pair_b[e] = (unsigned char)bb;
     }
     double* S = a.scratch + (int64_t)blockIdx.x * a.scratch_stride;
     double* Y = S + L.oY;
@@ -299,7 +299,7 @@ __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
         }
         // ---- outputs (blocks of a generic integrator, laid out as k_tdb writes them)
         for (int r = tid; r < n; r += 256) a.vals[kn * n + r] = zk1[a.T.x_off + r] - Y[r];
-        auto zz_of = [&](int b) { return b < m ? a.T.u_off + b : (b == m ? a.T.t_off : (b == m + 1 ? a.P.dt_idx : z + a.T.u_off + (b - m - 2))); };
+        auto zz_of = [&](int b) { return tdb_param_entry(a.T, z, a.P.dt_idx, b); };
         if (need == 1) {
             double* J = a.jac + kn * (int64_t)n * 2 * z;
             for (int64_t e = tid; e < (int64_t)n * 2 * z; e += 256) J[e] = 0.0;
@@ -387,12 +387,10 @@ __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
 int tdb_mfma_npad(int n) { return pad32(n); }
 
 const char* tdb_mfma_refusal(const KTdb& T) {
-    const int p = T.m + 2 + (T.order ? T.m : 0);
-    const long nM = 1 + p + (long)p * (p + 1) / 2;
     if (T.n < 1 || T.n > 256) return "time-dependent bilinear integrator: the device kernels take 1..256 states";
     if (T.substeps < 1) return "time-dependent bilinear integrator: substeps must be >= 1";
     if (T.nmod < 0) return "time-dependent bilinear integrator: n_mod must be >= 0";
-    if (nM * (T.m + 1) * (1 + T.nmod) > TDB_MAX_COEFS)
+    if (!tdb_table_fits(T.m, T.order, T.nmod))
         return "time-dependent bilinear integrator: coefficient table (1 + p + p (p+1) / 2) (m+1) (1 + n_mod) exceeds 6144 entries";
     return nullptr;
 }
