@@ -976,7 +976,7 @@ void alloc_scratch(dto_handle* h) {
     h->d_f = own(h, dalloc<double>(1));
     h->d_bounds = own(h, dalloc<double>(2));
     h->d_plan = own(h, dalloc<int32_t>(4));
-    HIP_CHECK(hipHostMalloc((void**)&h->h_pinned, 32 * sizeof(double)));
+    HIP_CHECK(hipHostMalloc((void**)&h->mailbox, sizeof(PinnedMailbox)));
     HIP_CHECK(hipHostMalloc((void**)&h->h_stats, sizeof(int32_t) * 4 * std::max<size_t>(h->bil.size(), 1)));
     memset(h->h_stats, 0, sizeof(int32_t) * 4 * std::max<size_t>(h->bil.size(), 1));
 }

@@ -7,8 +7,10 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <map>
 
@@ -26,7 +28,7 @@ dto_handle::~dto_handle() {
     }
     for (auto& e : ev_pool) (void)hipEventDestroy(e);
     for (void* p : owned) (void)hipFree(p);
-    if (h_pinned) (void)hipHostFree(h_pinned);
+    if (mailbox) (void)hipHostFree(mailbox);
     if (stream) (void)hipStreamDestroy(stream);
     if (stream2) (void)hipStreamDestroy(stream2);
     if (stream_rb) (void)hipStreamDestroy(stream_rb);
@@ -166,18 +168,18 @@ SweepTypes make_types(int m, bool second_order) {
 struct Bounds {
     double beta, b1;
 };
+Bounds read_bounds(const dto_handle* h) { return Bounds{h->mailbox->bounds[0], h->mailbox->bounds[1]}; }
 
-// enqueue only: the two doubles land in h_pinned[0..1] in stream order (read them after a later synchronisation point)
+// enqueue only: the two doubles land in mailbox->bounds in stream order (read them after a later synchronisation point)
 void enqueue_bounds(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st) {
     HIP_CHECK(hipMemsetAsync(h->d_bounds, 0, 2 * sizeof(double), st));
     launch_norm_bounds(st, h->P, b.k, dZ, b.d_g1, b.d_n2, reinterpret_cast<unsigned long long*>(h->d_bounds));
-    HIP_CHECK(hipMemcpyAsync(h->h_pinned, h->d_bounds, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(h->mailbox->bounds, h->d_bounds, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
 }
 Bounds get_bounds(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st) {
     enqueue_bounds(h, b, dZ, st);
     HIP_CHECK(hipStreamSynchronize(st));
-    Bounds r{h->h_pinned[0], h->h_pinned[1]};
-    return r;
+    return read_bounds(h);
 }
 
 struct SweepPlan {
@@ -210,7 +212,7 @@ SweepPlan plan_sweep(double beta) {
 
 // Taylor steps a fused sweep (already enqueued on st) actually took: waits for it.
 int fused_sweep_steps(dto_handle* h, const SweepBuf& w, int d_ub, hipStream_t st) {
-    int32_t* hs = reinterpret_cast<int32_t*>(h->h_pinned + 6);
+    int32_t* hs = h->mailbox->sweep_stats;
     HIP_CHECK(hipMemcpyAsync(hs, w.stats, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     return std::max(1, std::min(hs[1] - 1, d_ub));
@@ -401,7 +403,7 @@ int run_sweep(dto_handle* h, BilHost& b, SweepBuf& w, const SweepTypes& ty, cons
             // PREVIOUS checkpoint is read before enqueueing more, so the host never waits on the GPU's current
             // work (the decision lags by 4 steps, which then cost ~5 us each as inactive blocks exit at once).
             if (t >= 3 && (t % 4) == 3 && t + 1 < plan.d_ub) {
-                int32_t* hs = reinterpret_cast<int32_t*>(h->h_pinned + 6);
+                int32_t* hs = h->mailbox->sweep_stats;
                 if (pending) {
                     HIP_CHECK(hipEventSynchronize(h->ev_stats));
                     if (hs[slot ^ 1] == 0) break;
@@ -449,7 +451,7 @@ double run_chain(dto_handle* h, BilHost& b, const double* dZ, double* vals, doub
         if (nothing_waits) {
             // the caller has planned and enqueued its sweep already: nothing on the host depends on this launch, the call stays
             // enqueue-only; the squaring count (a diagnostic) is read with the sweep statistics at the next entry point
-            HIP_CHECK(hipMemcpyAsync(h->h_pinned + 28, w.smax, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(&h->mailbox->deferred_smax, w.smax, sizeof(int32_t), hipMemcpyDeviceToHost, st));
             h->smax_pending = true;
             h->last_form = 0;
             if (in_bubble) in_bubble();
@@ -458,20 +460,16 @@ double run_chain(dto_handle* h, BilHost& b, const double* dZ, double* vals, doub
             return 0.0;
         }
         launch_hump(st, h->P, b.k, dZ, b.d_g1, h->P.kn_lo, (int)nint, w.norms, b.d_hump);
-        int32_t* hs = reinterpret_cast<int32_t*>(h->h_pinned + 2);
-        HIP_CHECK(hipMemcpyAsync(hs, w.smax, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(h->h_pinned + 16, b.d_hump, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        const ChainReadback& rb = h->mailbox->chain;
+        HIP_CHECK(hipMemcpyAsync(&h->mailbox->chain, w.smax, sizeof(ChainReadback), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h->mailbox->hump, b.d_hump, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipEventRecord(h->ev_chain, st));
         if (in_bubble) in_bubble();
         HIP_CHECK(hipEventSynchronize(h->ev_chain));
         h->last_form = 0;   // per interval
-        h->last_smax = hs[0];
+        h->last_smax = rb.s_max2;
         read_hump(h, b);
-        {
-            double dv;
-            memcpy(&dv, hs + 2, sizeof(double));
-            d2max = dv;
-        }
+        d2max = rb.d2max;
         if (h->on_chain_chunk) h->on_chain_chunk(0, (int)nint);
         if (after_last_enqueue) after_last_enqueue(d2max);
         return d2max;
@@ -530,12 +528,12 @@ double run_chain(dto_handle* h, BilHost& b, const double* dZ, double* vals, doub
         launch_expm_coef(st, nb, w, want_form);
         // ... and it leaves on a stream of its own right behind k_expm_coef, so the host learns the form while the GPU is still
         // busy with K's GEMM (0.65 ms at 256 x 2000) and has the products enqueued before that GEMM ends: no bubble
-        int32_t* hs = reinterpret_cast<int32_t*>(h->h_pinned + 2);
+        const ChainReadback& rb = h->mailbox->chain;
         static const int rb_side = tune_int("DTO_RB_STREAM", 1);  // 0: the readback follows K's GEMM on the call's stream (round 2)
         hipEvent_t ev_s = h->ev_chain;
         auto readback = [&](hipStream_t rs) {
-            HIP_CHECK(hipMemcpyAsync(hs, w.smax, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, rs));
-            HIP_CHECK(hipMemcpyAsync(h->h_pinned + 16, b.d_hump, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, rs));
+            HIP_CHECK(hipMemcpyAsync(&h->mailbox->chain, w.smax, sizeof(ChainReadback), hipMemcpyDeviceToHost, rs));
+            HIP_CHECK(hipMemcpyAsync(h->mailbox->hump, b.d_hump, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, rs));
             HIP_CHECK(hipEventRecord(ev_s, rs));
         };
         if (rb_side) {
@@ -553,7 +551,7 @@ double run_chain(dto_handle* h, BilHost& b, const double* dZ, double* vals, doub
         if (!rb_side) readback(st);
         if (c0 == 0 && in_bubble) in_bubble();
         HIP_CHECK(hipEventSynchronize(ev_s));
-        const int form = hs[6];
+        const int form = rb.form;
         if (form != 2 && form != 3) throw HipError{"propagator chain: the evaluation form did not come back from the device"};
         h->last_form = form;
         // Y = A^4 K -> (Y + Pa, Y + Pb) in one launch
@@ -568,14 +566,11 @@ double run_chain(dto_handle* h, BilHost& b, const double* dZ, double* vals, doub
             { ProfScope ps(h, st, CAT_BGEMM_HORNER, gemm_flops * nb); launch_bgemm_poly(st, npad, nb, w, 4, 6, 7, COEF_L, 8, COEF_R, true); }
             { ProfScope ps(h, st, CAT_BGEMM_HORNER, gemm_flops * nb); launch_bgemm_poly(st, npad, nb, w, 7, 8, 5, COEF_PC, -1, 0, false, &slab); }
         }
-        const int s_max = form == 3 ? hs[4] : hs[0];
-        const int s_sum = form == 3 ? hs[5] : hs[1];
+        const int s_max = form == 3 ? rb.s_max3 : rb.s_max2;
+        const int s_sum = form == 3 ? rb.s_sum3 : rb.s_sum2;
         read_hump(h, b);  // accumulated over the chunks so far; final after the last one
-        {
-            double dv;
-            memcpy(&dv, hs + 2, sizeof(double));
-            d2max = (dv == dv) ? std::max(d2max, dv) : dv;
-        }
+        const double dv = rb.d2max;
+        d2max = (dv == dv) ? std::max(d2max, dv) : dv;
         const double sq_flops = s_max > 0 ? gemm_flops * (double)s_sum / s_max : 0.0;
         h->last_smax = std::max(h->last_smax, s_max);
         int src = 5;
@@ -624,12 +619,11 @@ double exact_d2(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st, boo
             launch_norm1_one(st, npad, nb, w, 1);
         }
         launch_hump(st, h->P, b.k, dZ, b.d_g1, int0, nb, w.norms, b.d_hump);
-        int32_t* hs = reinterpret_cast<int32_t*>(h->h_pinned + 2);
-        HIP_CHECK(hipMemcpyAsync(hs, w.smax, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(h->h_pinned + 16, b.d_hump, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        // (the first 16 bytes of the readback: the two-product counts, which nothing reads here, and d2max)
+        HIP_CHECK(hipMemcpyAsync(&h->mailbox->chain, w.smax, offsetof(ChainReadback, s_max3), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h->mailbox->hump, b.d_hump, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        double dv;
-        memcpy(&dv, hs + 2, sizeof(double));
+        const double dv = h->mailbox->chain.d2max;
         d2max = (dv == dv) ? std::max(d2max, dv) : dv;
     }
     read_hump(h, b);
@@ -639,7 +633,7 @@ double exact_d2(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st, boo
 // Plan from the a-priori hump bound of k_hump: the fewest rounds whose Taylor sums cannot lose more than theta_v
 // e-folds to cancellation; falls back to the growth-rate rule when no q <= 4 qualifies or the bound is not finite.
 void read_hump(dto_handle* h, BilHost& b) {
-    const unsigned long long* hp = reinterpret_cast<const unsigned long long*>(h->h_pinned + 16);
+    const unsigned long long* hp = h->mailbox->hump;
     b.hump_valid = true;
     for (int q = 0; q < 4; ++q) {
         double v;
@@ -701,6 +695,25 @@ SweepPlan plan_from(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st,
 // callbacks (device-pointer forms)
 // ------------------------------------------------------------------------------------------
 
+// Is every vector `now` bit-identical to its `cached` copy (both on the device)?  One round trip: the flag (a mailbox member) goes
+// up as 1, one compare launch per pair clears it on a difference, it comes back, the host waits for it.
+struct BitsPair {
+    const double *now, *cached;
+    int64_t n;
+};
+bool bits_equal(hipStream_t st, std::initializer_list<BitsPair> pairs, int32_t* d_flag, int32_t* flag) {
+    *flag = 1;
+    HIP_CHECK(hipMemcpyAsync(d_flag, flag, sizeof(int32_t), hipMemcpyHostToDevice, st));
+    for (const BitsPair& p : pairs) launch_bits_equal(st, p.now, p.cached, p.n, d_flag);
+    HIP_CHECK(hipMemcpyAsync(flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return *flag != 0;
+}
+
+void invalidate_sweep_caches(dto_handle* h) {
+    for (auto& b : h->bil) b.cache.invalidate();
+}
+
 // reuse_forward_sweep: is dZ bit-identical to the point the cached sweeps were computed at?  If not, dZ becomes the new
 // cache point and every integrator's cache is dropped.
 bool same_point(dto_handle* h, const double* dZ, hipStream_t st) {
@@ -708,19 +721,11 @@ bool same_point(dto_handle* h, const double* dZ, hipStream_t st) {
     if (!h->d_Zcache) {
         h->d_Zcache = own(h, dalloc<double>((size_t)h->n_vars));
         h->d_eq = own(h, dalloc<int32_t>(1));
-        HIP_CHECK(hipMemcpyAsync(h->d_Zcache, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
-        for (auto& b : h->bil) { b.cache_kind = 0; b.p_terms = false; b.plan_q = 0; }
-        return false;
+    } else if (bits_equal(st, {{dZ, h->d_Zcache, h->n_vars}}, h->d_eq, &h->mailbox->same_flag)) {
+        return true;
     }
-    int32_t* flag = reinterpret_cast<int32_t*>(h->h_pinned + 24);
-    *flag = 1;
-    HIP_CHECK(hipMemcpyAsync(h->d_eq, flag, sizeof(int32_t), hipMemcpyHostToDevice, st));
-    launch_bits_equal(st, dZ, h->d_Zcache, h->n_vars, h->d_eq);
-    HIP_CHECK(hipMemcpyAsync(flag, h->d_eq, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (*flag) return true;
     HIP_CHECK(hipMemcpyAsync(h->d_Zcache, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
-    for (auto& b : h->bil) { b.cache_kind = 0; b.p_terms = false; b.plan_q = 0; }
+    invalidate_sweep_caches(h);
     return false;
 }
 
@@ -827,13 +832,10 @@ void do_gradient(dto_handle* h, const double* dZ, double* dgrad, hipStream_t st)
         if (e.k.n_list > 0) launch_ext_gradient(st, h->P, e.k, e.weight, ext_upload(h, e.ext_slot, 1, st), dgrad);
 }
 
-// after a stored sweep of the p column alone: its terms stay valid for later callbacks at the same point
-void remember_p_terms(dto_handle* h, BilHost& b, bool stored, int steps, hipStream_t st) {
-    b.p_terms = stored && h->reuse;
-    b.p_steps = steps;
-    b.p_nblk = b.fw.nblk;
-    if (stored)
-        HIP_CHECK(hipMemcpyAsync(b.fw.nterms_p, b.fw.nterms, sizeof(int32_t) * b.fw.Kpad, hipMemcpyDeviceToDevice, st));
+// after a stored sweep of the p column alone: its terms stay valid for later callbacks at the same point, so their counts per block
+// move out of the way of the next sweep (b.cache's recorder of that sweep does the bookkeeping)
+void keep_p_column_counts(BilHost& b, hipStream_t st) {
+    HIP_CHECK(hipMemcpyAsync(b.fw.nterms_p, b.fw.nterms, sizeof(int32_t) * b.fw.Kpad, hipMemcpyDeviceToDevice, st));
 }
 
 void do_constraint(dto_handle* h, const double* dZ, double* dg, hipStream_t st) {
@@ -846,15 +848,15 @@ void do_constraint(dto_handle* h, const double* dZ, double* dg, hipStream_t st) 
         }
         if (h->P.n_int > 0) {
             SweepChoice alone;
-            if (!(same && b.cache_kind >= 1) && s64_plans_itself(h, b, b.fw, make_types(0, false), &alone)) {
+            const bool have_sums = b.cache.at(same).has_p_sums();
+            if (!have_sums && s64_plans_itself(h, b, b.fw, make_types(0, false), &alone)) {
                 // 33..64 states: the one-launch sweep takes its step budget from the norm bound ON THE DEVICE (k_plan_dev: the
                 // formulas of cheap_plan / plan_sweep) -- the call no longer waits 40 us for eight bytes
                 enqueue_bounds(h, b, dZ, st);
                 launch_plan_dev(st, reinterpret_cast<const unsigned long long*>(h->d_bounds), h->d_plan);
                 run_sweep(h, b, b.fw, make_types(0, false), dZ, nullptr, PLAN_ON_DEVICE, st, SweepArgs().as_chosen(alone).planned_on_device(h->d_plan));
-                b.cache_kind = 0;
-                remember_p_terms(h, b, false, 0, st);
-            } else if (!(same && b.cache_kind >= 1)) {  // else exp(A)x of this very point is still in b.fw.S
+                b.cache.constraint_swept_on_device_plan(b.fw.nblk);
+            } else if (!have_sums) {  // else exp(A)x of this very point is still in b.fw.S
                 SweepPlan plan = plan_from(h, b, dZ, st, /*loose=*/true);
                 if (plan.tc >= 0 && h->reuse && b.pairing && plan.d_ub + 1 > b.fw.dcap) plan = plan_from(h, b, dZ, st);  // the term store is what limits
                 SweepTypes ty = make_types(0, false);
@@ -862,8 +864,8 @@ void do_constraint(dto_handle* h, const double* dZ, double* dg, hipStream_t st) 
                 // columns alone and a Hessian needs no forward sweep at all
                 const bool keep_p = h->reuse && b.pairing && plan.q == 1 && plan.d_ub + 1 <= b.fw.dcap;
                 const int steps = run_sweep(h, b, b.fw, ty, dZ, nullptr, plan, st, SweepArgs().keep_terms(keep_p));
-                b.cache_kind = h->reuse ? 1 : 0;
-                remember_p_terms(h, b, keep_p, steps, st);
+                b.cache.constraint_swept(h->reuse, keep_p, steps, b.fw.nblk);
+                if (keep_p) keep_p_column_counts(b, st);
             }
             launch_cons_bilinear(st, h->P, b.k, b.fw, dZ, dg);
         }
@@ -939,8 +941,9 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
             }
             auto sweep_one = [&](BilHost& mb, SweepPlan plan, const int32_t* plan_dev) {
                 SweepTypes ty = make_types(mb.k.m, false);
+                const auto held = mb.cache.at(same);
                 // the p column of this very point is stored (eval_constraint or a Hessian came first)
-                const bool have_p = same && mb.p_terms && plan.q == 1;
+                const bool have_p = held.has_p_column() && plan.q == 1;
                 // ... but where the whole sweep runs as ONE persistent launch beside the chain, sweeping all columns again is
                 // cheaper than the step-per-launch form the frozen variant needs (256 x 2000: 10.9 against 12.0 ms per Jacobian);
                 // the stored p terms stay valid for a Hessian at this point either way (a sweep without store leaves them alone)
@@ -952,11 +955,11 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                     // sweep the tangent columns alone, their inhomogeneous terms read the stored p terms
                     SweepBuf wf = mb.fw;
                     wf.frozen = mb.fw.Zt;
-                    wf.frozen_total = mb.p_steps + 1;
+                    wf.frozen_total = held.p_column_steps() + 1;
                     wf.first_type = 1;
                     run_sweep(h, mb, wf, ty, dZ, nullptr, plan, ss);
                     launch_apply_Gu(ss, mb.k, mb.fw, 0, mb.fw.S, mb.fw.GY);
-                    mb.cache_kind = 2;
+                    mb.cache.jacobian_swept_frozen();
                     return;
                 }
                 // with reuse on and a Hessian to follow, keep every Taylor term so that the Hessian can skip its forward sweep
@@ -972,9 +975,7 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                 if (beside_chain && !gs_alone) choice = choose_sweep(h, mb, mb.fw, ty, plan, keep, /*shared_chip=*/true);
                 const int steps = run_sweep(h, mb, mb.fw, ty, dZ, nullptr, plan, sw, SweepArgs().as_chosen(choice).planned_on_device(plan_dev));
                 launch_apply_Gu(sw, mb.k, mb.fw, 0, mb.fw.S, mb.fw.GY);
-                mb.cache_kind = h->reuse ? (keep ? 3 : 2) : 0;
-                mb.cache_steps = steps;
-                if (keep || plan.q > 1) mb.p_terms = false;  // the store now holds every column type / the scale factors changed
+                mb.cache.jacobian_swept(h->reuse, keep, plan.q, steps);  // (keep: the store now holds every column type; q > 1: the scale factors changed)
             };
             auto sweep_with = [&](SweepPlan plan, const int32_t* plan_dev = nullptr) {
                 for (int i = 0; i < n_members; ++i) sweep_one(*members[i], plan, plan_dev);
@@ -983,9 +984,17 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
             // them would run behind it.  Where the cheap bound already gives a single round, the sweep is planned from that bound
             // (as eval_constraint and the Hessian do) and enqueued FIRST, on the second stream: its workgroups and the chain's
             // share the CUs (64 x 1000: 0.42 -> 0.3x ms per Jacobian).
-            bool swept = same;  // the tangent sums of this very point are still in b.fw (of every member)
-            for (int i = 0; i < n_members; ++i) swept = swept && members[i]->cache_kind >= 2;
+            bool swept = true;  // the tangent sums of this very point are still in b.fw (of every member; members[0] is always there)
+            for (int i = 0; i < n_members; ++i) swept = swept && members[i]->cache.at(same).has_tangent_sums();
+            // every entry but the -E_k blocks, which the chain overwrites: once per call, behind the early sweep on ITS stream or in
+            // the chain's bubble on the call's
             bool zeroed = false;
+            auto zero_around_blocks = [&](hipStream_t s) {
+                if (!lone || keep_constants || zeroed) return;
+                ProfScope ps(h, s, CAT_ZERO, 8.0 * ((double)h->info.jac_len - (double)h->P.n_int * b.k.n * b.k.n));
+                launch_jac_zero(s, h->P, b.k, dvals);
+                zeroed = true;
+            };
             static const int early_on = tune_int("DTO_SWEEP_EARLY", 1);  // A/B runs (TUNING builds)
             if (!swept && early_on && chain64_applies(h, b) && s64_plans_itself(h, b, b.fw, make_types(b.k.m, false))) {
                 // ... and planned on the device: the whole call is enqueue-only
@@ -994,27 +1003,18 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                 if (overlap) HIP_CHECK(hipStreamWaitEvent(ss, h->ev_fork, 0));
                 sweep_with(PLAN_ON_DEVICE, h->d_plan);
                 swept = true;
-                if (lone && !keep_constants) {
-                    // the fill behind the sweep on ITS stream: only the tangent-column writers after the join need it, and the chain
-                    // (which skips nothing the fill touches) starts 28 us earlier than with the fill in front of it
-                    ProfScope ps(h, ss, CAT_ZERO, 8.0 * ((double)h->info.jac_len - (double)h->P.n_int * b.k.n * b.k.n));
-                    launch_jac_zero(ss, h->P, b.k, dvals);
-                    zeroed = true;
-                }
+                // the fill behind the sweep on ITS stream: only the tangent-column writers after the join need it, and the chain
+                // (which skips nothing the fill touches) starts 28 us earlier than with the fill in front of it
+                zero_around_blocks(ss);
             }
             if (!swept && early_on && chain64_applies(h, b)) {   // (with or without overlap: the plan, hence the bits, must not depend on it)
                 HIP_CHECK(hipStreamSynchronize(st));
-                bd = Bounds{h->h_pinned[0], h->h_pinned[1]};
+                bd = read_bounds(h);
                 SweepPlan early;
                 if (cheap_plan(bd, /*loose=*/true, early)) {
                     sweep_with(early);
                     swept = true;
-                    if (lone && !keep_constants) {
-                        // (the fill no longer has a host wait to hide in: it goes behind the sweep, on the sweep's stream)
-                        ProfScope ps(h, ss, CAT_ZERO, 8.0 * ((double)h->info.jac_len - (double)h->P.n_int * b.k.n * b.k.n));
-                        launch_jac_zero(ss, h->P, b.k, dvals);
-                        zeroed = true;
-                    }
+                    zero_around_blocks(ss);  // (the fill no longer has a host wait to hide in: it goes behind the sweep, on the sweep's stream)
                 }
             }
             const bool nothing_waits = swept && chain64_applies(h, b);
@@ -1035,21 +1035,15 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                 };
             }
             run_chain(h, b, dZ, dvals, INFINITY, st, [&](double d2) {
-                bd = Bounds{h->h_pinned[0], h->h_pinned[1]};  // copied before the chain's readback event
+                bd = read_bounds(h);  // copied before the chain's readback event
                 // ||A^t|| <= ||A^2||^floor(t/2) ||A||^(t mod 2): the exact d2 of the chain is the sharper
                 // (and still rigorous) growth rate for the sweep's step budget
                 if (swept) return;
                 const SweepPlan from_chain = plan_hump(b, d2 == d2 ? std::min(bd.beta, d2) : d2);
                 if (h->reuse)   // a Hessian at this very point need not buy the norms again
-                    for (int i = 0; i < n_members; ++i) { members[i]->plan_q = from_chain.q; members[i]->plan_dub = from_chain.d_ub; }
+                    for (int i = 0; i < n_members; ++i) members[i]->cache.chain_planned(from_chain.q, from_chain.d_ub);
                 sweep_with(from_chain);
-            }, [&] {
-                if (lone && !keep_constants && !zeroed) {
-                    // every entry but the -E_k blocks, which the chain overwrites
-                    ProfScope ps(h, st, CAT_ZERO, 8.0 * ((double)h->info.jac_len - (double)h->P.n_int * b.k.n * b.k.n));
-                    launch_jac_zero(st, h->P, b.k, dvals);
-                }
-            }, nothing_waits);
+            }, [&] { zero_around_blocks(st); }, nothing_waits);
             if (overlap) {
                 HIP_CHECK(hipEventRecord(h->ev_join, ss));
                 HIP_CHECK(hipStreamWaitEvent(st, h->ev_join, 0));
@@ -1120,17 +1114,17 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
             // pairing loops run over the terms actually produced -- the exact norms cost a store-less basis GEMM and two round trips)
             // (reuse_forward_sweep, same point as the last Jacobian: the chain's exact norms have planned that call's sweep already --
             // at 1024 states the passes that establish q = 1 for a Hessian on its own are 4.9 of its 29.5 ms)
-            const bool planned = same && b.plan_q > 0;
-            SweepPlan plan = planned ? SweepPlan{b.plan_q, b.plan_dub} : plan_from(h, b, dZ, st, /*loose=*/b.pairing);
+            const auto held = b.cache.at(same);
+            SweepPlan plan = held.has_plan() ? SweepPlan{held.plan_rounds(), held.plan_budget()} : plan_from(h, b, dZ, st, /*loose=*/b.pairing);
             if (plan.tc >= 0 && plan.d_ub + 1 > b.fw.dcap) plan = plan_from(h, b, dZ, st);
             const bool pair = b.pairing && plan.q == 1 && plan.d_ub + 1 <= b.fw.dcap;
             const int m = b.k.m, T1 = 1 + m;
-            int steps_f, Tf = T1;  // Tf: types per stored forward term
+            int steps_f, Tf = T1, nblk_p = 0;  // Tf: types per stored forward term; nblk_p: intervals per entry of fw.nterms_p (Tf == 1)
             SweepTypes ty1 = make_types(m, false);
             // Pairing path with a forward sweep of its own: the adjoint sweep is one persistent launch that leaves CUs idle, the
             // forward sweep of the p column a host-driven sequence of small launches -- independent until the pairing kernels,
             // so the adjoint sweep is enqueued first and the forward sweep runs next to it on the second stream.
-            const bool fwd_needed = pair && !(same && (b.cache_kind == 3 || b.p_terms));
+            const bool fwd_needed = pair && !(held.has_all_terms() || held.has_p_column());
             // (where the adjoint sweep has no single-workgroup form -- short shards -- both sweeps take the generator-stationary form,
             // one after the other; beside a fused adjoint sweep the forward column keeps its step launches, which fit into the CUs
             // that sweep leaves idle: measured 5.5 against 5.9 ms at 256 x 2000 with the forward column first and alone)
@@ -1153,17 +1147,18 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
             if (pair) {
                 // Pairing path: every tangent comes from the ADJOINT sweep (the (x,u) block needs those anyway); of the forward
                 // sweep only the Taylor terms of the p column are used (k_hess_pair, k_hess_bilinear).
-                if (same && b.cache_kind == 3) {
-                    steps_f = b.cache_steps;  // the Jacobian of this very point stored every forward term
-                } else if (same && b.p_terms) {
+                if (held.has_all_terms()) {
+                    steps_f = held.all_terms_steps();  // the Jacobian of this very point stored every forward term
+                } else if (held.has_p_column()) {
                     Tf = 1;
-                    steps_f = b.p_steps;      // eval_constraint (or an earlier Hessian) stored the p terms of this point
+                    steps_f = held.p_column_steps();   // eval_constraint (or an earlier Hessian) stored the p terms of this point
+                    nblk_p = held.p_column_nblk();     // (a frozen Jacobian sweep in between re-used fw.nterms and fw.nblk)
                 } else {
                     Tf = 1;
                     steps_f = run_sweep(h, b, b.fw, make_types(0, false), dZ, nullptr, plan, sf, SweepArgs().keep_terms(true).beside_others(side_by_side));
-                    b.cache_kind = h->reuse ? 1 : 0;  // the p sums are valid, the tangent sums are not
-                    b.cache_steps = steps_f;
-                    remember_p_terms(h, b, true, steps_f, sf);
+                    nblk_p = b.fw.nblk;
+                    b.cache.hessian_swept_p_column(h->reuse, steps_f, nblk_p);  // the p sums are valid, the tangent sums are not
+                    keep_p_column_counts(b, sf);
                 }
                 launch_apply_generators(sf, b.k, b.fw, 0, b.fw.Zt, b.fw.W);  // V_l = G_l x (term 0 of the p column is x)
                 if (side_by_side) {
@@ -1173,8 +1168,7 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
             } else {
                 steps_f = run_sweep(h, b, b.fw, make_types(m, true), dZ, nullptr, plan, st);
                 launch_apply_Gu(st, b.k, b.fw, 0, b.fw.S, b.fw.GY);
-                b.cache_kind = 0;
-                b.p_terms = false;  // this sweep re-initialised the scale factors for its own q
+                b.cache.hessian_swept_second_order();  // this sweep re-initialised the scale factors for its own q
                 // W_j = G_j' mu from the adjoint sweep's term-0 buffer
                 launch_sweep_init(st, h->P, b.k, b.ad, make_types(0, false), dZ, dmu, 1, plan.q);
                 launch_apply_generators(st, b.k, b.ad, 1, b.ad.Z[0], b.ad.W);
@@ -1199,7 +1193,7 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
                 const int64_t typesz = (int64_t)b.fw.Kpad * b.k.npad;
                 const int64_t cols = (int64_t)na * b.fw.Kpad;  // one type of every stored term
                 SweepBuf plain = b.fw;
-                if (Tf == 1) { plain.nterms = b.fw.nterms_p; plain.nblk = b.p_nblk; }  // (a frozen Jacobian sweep in between re-used fw.nterms)
+                if (Tf == 1) { plain.nterms = b.fw.nterms_p; plain.nblk = nblk_p; }
                 launch_pair_combine(st, plain, Tf, 1, na, nf, b.ad.nterms, b.ad.nblk, b.d_Btab, b.Upair);
                 {
                     ProfScope ps(h, st, CAT_SWEEP, 2.0 * b.k.npad * (double)b.k.npad * cols * m);
@@ -1452,7 +1446,7 @@ double* staging(dto_handle* h, size_t n) {
 }
 
 void drop_caches(dto_handle* h) {
-    for (auto& b : h->bil) { b.cache_kind = 0; b.p_terms = false; b.plan_q = 0; }
+    invalidate_sweep_caches(h);
     ++h->gen;  // (the Hessian-vector products' cached point as well)
 }
 void unprime(dto_handle* h) { h->primed[0] = h->primed[1] = false; }
@@ -1482,7 +1476,7 @@ void check_sweeps(dto_handle* h, bool wait = true) {
     if (!wait && hipEventQuery(h->ev_done) != hipSuccess) { (void)hipGetLastError(); return; }
     h->stats_pending = false;
     HIP_CHECK(hipEventSynchronize(h->ev_done));
-    if (h->smax_pending) { h->last_smax = *reinterpret_cast<const int32_t*>(h->h_pinned + 28); h->smax_pending = false; }
+    if (h->smax_pending) { h->last_smax = h->mailbox->deferred_smax; h->smax_pending = false; }
     size_t i = 0;
     bool bad = false;
     for (auto& b : h->bil)
@@ -1763,16 +1757,7 @@ void build_hp_index(dto_handle* h) {
 void hess_product(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dv, double* dy, hipStream_t st) {
     build_hp_index(h);
     bool hit = h->hp_valid && h->hp_gen == h->gen && memcmp(&sigma, &h->hp_sigma, sizeof(double)) == 0;
-    if (hit) {
-        int32_t* flag = reinterpret_cast<int32_t*>(h->h_pinned + 26);
-        *flag = 1;
-        HIP_CHECK(hipMemcpyAsync(h->d_hp_eq, flag, sizeof(int32_t), hipMemcpyHostToDevice, st));
-        launch_bits_equal(st, dZ, h->d_hp_Z, h->n_vars, h->d_hp_eq);
-        launch_bits_equal(st, dmu, h->d_hp_mu, h->n_cons, h->d_hp_eq);
-        HIP_CHECK(hipMemcpyAsync(flag, h->d_hp_eq, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        hit = *flag != 0;
-    }
+    if (hit) hit = bits_equal(st, {{dZ, h->d_hp_Z, h->n_vars}, {dmu, h->d_hp_mu, h->n_cons}}, h->d_hp_eq, &h->mailbox->hp_flag);
     if (!hit) {
         h->hp_valid = false;
         if (!h->hp_slab) h->hp_slab = own(h, dalloc<double>((size_t)h->info.hess_len));
@@ -2169,8 +2154,7 @@ static void jac_product_matrix_free(dto_handle* h, const double* dZ, const doubl
         if (b.kron) { kron_product(h, b, dZ, dw, dy, transpose, st); continue; }
         if (b.small) { small_product(h, b, dZ, dw, dy, transpose, st); continue; }
         if (h->P.n_int <= 0) continue;
-        b.cache_kind = 0;  // the product sweeps use b.fw with their own column types
-        b.p_terms = false;
+        b.cache.products_swept();  // the product sweeps use b.fw with their own column types
         SweepPlan plan = plan_from(h, b, dZ, st);
         SweepTypes ty = make_types(b.k.m, false);
         if (!transpose) {

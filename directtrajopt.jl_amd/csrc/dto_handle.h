@@ -12,12 +12,14 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
 #include "dto_comm.h"
 #include "dto_hostxfer.h"
 #include "dto_kernels.h"
+#include "dto_sweep_cache.h"
 
 namespace dto {
 
@@ -74,16 +76,9 @@ struct BilHost {
     double hump_logH[4] = {0, 0, 0, 0};
     int hump_kend[4] = {0, 0, 0, 0};
     bool hump_valid = false;
-    // reuse_forward_sweep: what b.fw still holds for the cached Z -- 0 nothing, 1 the p sums (S type 0), 2 p and d^j sums
-    // and GY, 3 additionally every Taylor term in fw.Zt (cache_steps of them)
-    int cache_kind = 0, cache_steps = 0;
-    // option reuse_forward_sweep: the step budget the Jacobian's chain planned from its exact norms at the cached point (q = 0: none)
-    int plan_q = 0, plan_dub = 0;
-    // ... and whether the Taylor terms of the p column of that point sit in fw.Zt ([term][Kpad][npad], one type per term:
-    // eval_constraint and the Hessian's forward sweep store them), p_steps + 1 of them, valid counts per block in fw.nterms_p
-    bool p_terms = false;
-    int p_steps = 0;
-    int p_nblk = 0;           // intervals per entry of fw.nterms_p (the convergence blocks of the sweep that stored the p terms)
+    // option reuse_forward_sweep: what b.fw still holds for the cached Z, and the step budget the Jacobian's chain planned there
+    // (dto_sweep_cache.h: written by one recorder per producer, read through cache.at(same) only)
+    SweepCache cache;
     // row-split cluster sweeps (dto_sweep_fused.hip): exchange slabs and arrival counters, one set per sweep buffer ([0] fw,
     // [1] ad: the Hessian's forward and adjoint sweeps may run side by side)
     SweepWork cluster_work[2];
@@ -175,6 +170,29 @@ struct ProfRec {
     int cat;
     double flops;
 };
+
+// ChainWork::smax[0..7] as the host reads it back, member for member as launch_expm_params, launch_expm_coef, launch_norm1_one and
+// launch_chain64 write it
+struct ChainReadback {
+    int32_t s_max2, s_sum2;   // two-product form: largest squaring count and the sum of the counts over the chunk
+    double d2max;             // max_k ||A_k^2||_1^(1/2) (smax[2..3])
+    int32_t s_max3, s_sum3;   // three-product form
+    int32_t form;             // the evaluation form taken (2 or 3)
+    int32_t pad;
+};
+static_assert(sizeof(ChainReadback) == 32 && std::is_standard_layout<ChainReadback>::value, "ChainReadback mirrors eight int32 of ChainWork::smax");
+
+// The handle's pinned host memory: where the asynchronous device-to-host copies of the few scalars the host plans from land, one
+// typed member per destination (the copies leave on the call's stream, the sweep's and the readback stream: none overlaps another).
+struct PinnedMailbox {
+    double bounds[2];              // enqueue_bounds: max beta, max b1
+    ChainReadback chain;           // the chain's readback (32 bytes; exact_d2 copies the first 16)
+    int32_t sweep_stats[2];        // fused_sweep_steps: a sweep's two statistics; step-per-launch sweeps: their checkpoints, alternating
+    unsigned long long hump[8];    // k_hump's output (read_hump)
+    int32_t same_flag;             // same_point's bit compare
+    int32_t hp_flag;               // hess_product's bit compare
+    int32_t deferred_smax;         // the one-launch chain's squaring count of an enqueue-only call (smax_pending)
+};
 }  // namespace dto
 
 struct dto_handle {
@@ -255,8 +273,8 @@ struct dto_handle {
     int64_t* d_crow_col = nullptr;
     int64_t* d_crow_pos = nullptr;
     int64_t* d_con_rows = nullptr;       // constraint-pattern rows, (col,row) order
-    double* h_pinned = nullptr;  // [32]: 0-1 bounds, 2-3 chain scalars, 6 sweep stats, 16-23 hump readback, 28 deferred squaring count
-    bool smax_pending = false;   // the one-launch chain's squaring count lands in h_pinned[28] behind ev_done (read by check_sweeps)
+    dto::PinnedMailbox* mailbox = nullptr;  // pinned; every readback the host plans from lands in a member of its own
+    bool smax_pending = false;   // the one-launch chain's squaring count lands in mailbox->deferred_smax behind ev_done (read by check_sweeps)
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;   // generator sweep runs here, concurrently with the propagator chain
     hipStream_t stream_rb = nullptr; // the chain's 96-byte readback (evaluation form, squaring counts, hump bound) leaves on this one

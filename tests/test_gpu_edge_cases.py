@@ -371,6 +371,162 @@ def test_reuse_forward_sweep_where_the_sweep_is_one_launch(n, N):
         ref.close(); ev.close()
 
 
+# ---- reuse_forward_sweep must actually reuse: generator sweeps per call, by form, with the option on and off
+_REUSE_SEQUENCES = ("g g", "J J", "J g", "g H", "H H", "J H", "g J H", "g Jw g")
+# (states, knots, seed): the padded one-launch chain, the 64-state forms, the 128-state forms
+_REUSE_SHAPES = [(40, 6, 17), (64, 12, 5), (128, 8, 5)]
+# Sweeps per call as sweep_forms() counted them, recorded ONCE with this very test body on the commit before the cache became a
+# record (dto_sweep_cache.h), and to be reproduced exactly.  Per sequence the three visits Z1, Z2, Z1; per visit one entry per call:
+# the forms that ran joined by "+", "0" where the call ran no sweep.
+_REUSE_SWEEPS = {
+    (40, 6): {
+        0: {
+            'g g': ('s64 s64', 's64 s64', 's64 s64'),
+            'J J': ('s64 s64', 's64 s64', 's64 s64'),
+            'J g': ('s64 s64', 's64 s64', 's64 s64'),
+            'g H': ('s64 s64+s64', 's64 s64+s64', 's64 s64+s64'),
+            'H H': ('s64+s64 s64+s64', 's64+s64 s64+s64', 's64+s64 s64+s64'),
+            'J H': ('s64 s64+s64', 's64 s64+s64', 's64 s64+s64'),
+            'g J H': ('s64 s64 s64+s64', 's64 s64 s64+s64', 's64 s64 s64+s64'),
+            'g Jw g': ('s64 step s64', 's64 step s64', 's64 step s64'),
+        },
+        1: {
+            'g g': ('step 0', 'step 0', 'step 0'),
+            'J J': ('s64 0', 's64 0', 's64 0'),
+            'J g': ('s64 0', 's64 0', 's64 0'),
+            'g H': ('step s64', 'step s64', 'step s64'),
+            'H H': ('s64+step s64', 's64+step s64', 's64+step s64'),
+            'J H': ('s64 s64', 's64 s64', 's64 s64'),
+            'g J H': ('step s64 s64', 'step s64 s64', 'step s64 s64'),
+            'g Jw g': ('step step step', 'step step step', 'step step step'),
+        },
+    },
+    (64, 12): {
+        0: {
+            'g g': ('s64 s64', 's64 s64', 's64 s64'),
+            'J J': ('s64 s64', 's64 s64', 's64 s64'),
+            'J g': ('s64 s64', 's64 s64', 's64 s64'),
+            'g H': ('s64 s64+s64', 's64 s64+s64', 's64 s64+s64'),
+            'H H': ('s64+s64 s64+s64', 's64+s64 s64+s64', 's64+s64 s64+s64'),
+            'J H': ('s64 s64+s64', 's64 s64+s64', 's64 s64+s64'),
+            'g J H': ('s64 s64 s64+s64', 's64 s64 s64+s64', 's64 s64 s64+s64'),
+            'g Jw g': ('s64 step s64', 's64 step s64', 's64 step s64'),
+        },
+        1: {
+            'g g': ('step 0', 'step 0', 'step 0'),
+            'J J': ('s64 0', 's64 0', 's64 0'),
+            'J g': ('s64 0', 's64 0', 's64 0'),
+            'g H': ('step s64', 'step s64', 'step s64'),
+            'H H': ('s64+step s64', 's64+step s64', 's64+step s64'),
+            'J H': ('s64 s64', 's64 s64', 's64 s64'),
+            'g J H': ('step s64 s64', 'step s64 s64', 'step s64 s64'),
+            'g Jw g': ('step step step', 'step step step', 'step step step'),
+        },
+    },
+    (128, 8): {
+        0: {
+            'g g': ('gs gs', 'gs gs', 'gs gs'),
+            'J J': ('gs gs', 'gs gs', 'gs gs'),
+            'J g': ('gs gs', 'gs gs', 'gs gs'),
+            'g H': ('gs gs+gs', 'gs gs+gs', 'gs gs+gs'),
+            'H H': ('gs+gs gs+gs', 'gs+gs gs+gs', 'gs+gs gs+gs'),
+            'J H': ('gs gs+gs', 'gs gs+gs', 'gs gs+gs'),
+            'g J H': ('gs gs gs+gs', 'gs gs gs+gs', 'gs gs gs+gs'),
+            'g Jw g': ('gs step gs', 'gs step gs', 'gs step gs'),
+        },
+        1: {
+            'g g': ('step 0', 'step 0', 'step 0'),
+            'J J': ('gs 0', 'gs 0', 'gs 0'),
+            'J g': ('gs 0', 'gs 0', 'gs 0'),
+            'g H': ('step gs', 'step gs', 'step gs'),
+            'H H': ('gs+step gs', 'gs+step gs', 'gs+step gs'),
+            'J H': ('gs gs', 'gs gs', 'gs gs'),
+            'g J H': ('step gs gs', 'step gs gs', 'step gs gs'),
+            'g Jw g': ('step step step', 'step step step', 'step step step'),
+        },
+    },
+}
+
+
+def _sweeps_per_call(n, N, seed):
+    """Runs every sequence of _REUSE_SEQUENCES over Z1, Z2, Z1 on a handle with reuse_forward_sweep = 1 and on one with 0.
+    Returns ({reuse: {sequence: (visit, visit, visit)}}, the largest relative deviation of any output from the option-off handle)."""
+    import dto_amd
+    from helpers import SWEEP_FORMS, sweep_forms
+    p = dto_amd.host.synthetic.make_scaled_problem(N, n, 2, seed=seed)
+    handles = {0: dto_amd.Evaluator(p), 1: dto_amd.Evaluator(p)}
+    handles[1].set_option("reuse_forward_sweep", 1)
+    rng = np.random.default_rng(1)
+    Z1 = p.trajectory.vec()
+    Z2 = Z1 + 0.02 * rng.standard_normal(Z1.size)
+    Z3 = Z1 + 0.02 * rng.standard_normal(Z1.size)   # visited (unrecorded) before every sequence: it starts with nothing cached
+    mu = rng.standard_normal(handles[0].n_constraints)
+    w = rng.standard_normal(Z1.size)
+
+    def one(e, what, Z):
+        if what == "g":
+            out = np.empty(e.n_constraints); e.eval_constraint(out, Z)
+        elif what == "J":
+            out = np.empty(e.n_jacobian_entries); e.eval_constraint_jacobian(out, Z)
+        elif what == "Jw":
+            out = np.empty(e.n_constraints); e.eval_constraint_jacobian_product(out, Z, w)
+        else:
+            out = np.empty(e.n_hessian_entries); e.eval_hessian_lagrangian(out, Z, 0.9, mu)
+        return out
+
+    try:
+        want = {(what, id(Z)): one(handles[0], what, Z) for what in ("g", "J", "Jw", "H") for Z in (Z1, Z2)}
+        table, worst = {}, 0.0
+        for reuse, e in handles.items():
+            e.profile_enable(True)
+            table[reuse] = {}
+            for seq in _REUSE_SEQUENCES:
+                one(e, "g", Z3)
+                visits = []
+                for Z in (Z1, Z2, Z1):
+                    calls = []
+                    for what in seq.split():
+                        e.profile_reset()
+                        out = one(e, what, Z)
+                        f = sweep_forms(e)
+                        calls.append("+".join(form for form in SWEEP_FORMS for _ in range(f[form])) or "0")
+                        worst = max(worst, rel_err(out, want[(what, id(Z))]))
+                    visits.append(" ".join(calls))
+                table[reuse][seq] = tuple(visits)
+        return table, worst
+    finally:
+        for e in handles.values():
+            e.close()
+
+
+def _sweep_counts(visit):
+    return [0 if call == "0" else len(call.split("+")) for call in visit.split()]
+
+
+@pytest.mark.parametrize("n,N,seed", _REUSE_SHAPES)
+def test_reuse_forward_sweep_runs_no_sweep_it_has_cached(n, N, seed):
+    """The reuse tests above compare numbers, which stay right when the cache is lost and every call sweeps again; this one counts
+    the sweeps.  Every call of every sequence must run the sweeps, form by form, that the recorded table lists, and every output
+    must equal the option-off handle's to 1e-13.  The table itself obeys what follows from the driver wherever the plan is a
+    single round and the term store holds it (true of these three shapes with these seeds: none had to be changed):
+    option on -- a call whose sums are cached runs no sweep (the second g, the second J, g after J); H after g, J or H at the same
+    point runs one sweep (the adjoint one), a first H two; g after a J w product sweeps again; Z2 and the return to Z1 repeat the
+    first visit; option off -- every g and J runs one sweep, every H two."""
+    table, worst = _sweeps_per_call(n, N, seed)
+    print("sweeps per call", (n, N), table, "largest deviation from the option-off handle", worst)
+    recorded = _REUSE_SWEEPS[(n, N)]
+    on = {seq: [_sweep_counts(v) for v in visits] for seq, visits in recorded[1].items()}
+    for seq, first in (("g g", [1, 0]), ("J J", [1, 0]), ("J g", [1, 0]), ("g H", [1, 1]), ("H H", [2, 1]), ("J H", [1, 1]), ("g J H", [1, 1, 1])):
+        assert on[seq] == [first] * 3, (seq, on[seq])
+    assert all(v[0] == 1 and v[2] == 1 for v in on["g Jw g"]) and on["g Jw g"][1:] == on["g Jw g"][:2], on["g Jw g"]
+    for seq, visits in recorded[0].items():
+        per_call = [{"g": 1, "J": 1, "H": 2}.get(what) for what in seq.split()]
+        for v in visits:
+            assert all(a is None or a == c for a, c in zip(per_call, _sweep_counts(v))), (seq, visits)
+    assert table == recorded
+    assert worst <= 1e-13, worst
+
+
 def test_host_pointer_hand_off_ships_only_what_changes():
     """dto_hostxfer: the host-pointer Jacobian / Hessian copy the variable runs only and fill constants on the host.  The
     result must be bit-identical to the whole-slab copy (option host_xfer = 0), into buffers pre-filled with garbage, for
