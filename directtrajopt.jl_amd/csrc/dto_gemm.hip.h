@@ -1,15 +1,17 @@
-// dto_gemm.hip.h -- workgroup-level FP64 MFMA GEMM core for gfx950 (CDNA4).
-//
-// One 256-thread workgroup (4 wavefronts of 64, one per SIMD) computes a TM x TN tile of
-// C = A * B for COLUMN-MAJOR operands.  The wave grid is 2 x 2, each wave owns a
-// (TM/2) x (TN/2) sub-tile made of 16x16 `v_mfma_f64_16x16x4_f64` accumulators.
+// dto_gemm.hip.h -- workgroup-level FP64 MFMA GEMM cores for gfx950 (CDNA4): C = A * B for COLUMN-MAJOR operands, a TM x TN tile
+// per workgroup, WR x WC wavefronts of 64 (one or two per SIMD), each owning a (TM/WR) x (TN/WC) sub-tile made of 16x16
+// `v_mfma_f64_16x16x4_f64` accumulators.
+//   the 8-byte core (GemmShape, gemm_accumulate_s): the generator sweeps, the structured and time-dependent kernels, and the
+//       64x64-tile batched product k_bgemm of dto_kernels.hip;
+//   the paired-rows core (GemmShapeP, gemm_accumulate_p): the generator-subspace GEMMs; its accumulator and epilogue layout
+//       (GemmCoordP) is also that of the ring core (dto_gemm_ring.hip.h), which runs the 128x128-tile batched products.
 //
 // The product is issued TRANSPOSED (MFMA a-operand <- B fragment, b-operand <- A fragment) so
-// that the accumulator's lane index runs along C's rows: lane l, register r of accumulator
+// that the accumulator's lane index runs along C's rows: in the 8-byte core lane l, register r of accumulator
 // (ti,tj) holds C[row0 + 16*ti + (l&15)][col0 + 16*tj + (l>>4) + 4*r].  Sixteen consecutive lanes
 // therefore touch 128 contiguous bytes of a column-major C, which is what the epilogues store.
 //
-// LDS staging (double buffered, one barrier per 16-deep K panel):
+// LDS staging of the 8-byte core (double buffered, one barrier per 16-deep K panel):
 //   As[k][m]  : KB rows of TM doubles, row pitch TM+16  (2*(TM+16) mod 64 == 32 -> the two k's of a
 //               32-lane ds_read_b64 group land on disjoint bank halves: conflict-free)
 //   Bs[n][k]  : TN rows of KB doubles, row pitch KB+2   (36*c mod 64 distinct for c<16: conflict-free)
@@ -26,7 +28,6 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 template <int TM_, int TN_, int WR_ = 2, int WC_ = 2, int KB_ = 16>
 struct GemmShape {
     static constexpr int TM = TM_, TN = TN_, WR = WR_, WC = WC_, KB = KB_;
-    static constexpr bool PAIRED = false;
     static constexpr int THREADS = WR * WC * 64;
     static constexpr int LDA_S = TM + 16;  // (TM+16) mod 32 == 16 for TM multiple of 32
     static constexpr int LDB_S = KB + 2;
@@ -144,93 +145,31 @@ __device__ __forceinline__ void gemm_accumulate_s(GemmAccS<C>& acc, const double
 #pragma unroll
         for (int kk = 0; kk < C::KB; kk += 4) {
             // LLVM's MFMA/DS interleaving strategy for small GEMM loops: measured -2.5 % on the fused-polynomial GEMM and
-            // -2..5 % on the sweep step; the DMA-staged loop below is faster without it (+8 % with it)
+            // -2..5 % on the sweep step
             __builtin_amdgcn_iglp_opt(0);
             double af[C::MT], bf[C::NT];
 #pragma unroll
             for (int ti = 0; ti < C::MT; ++ti) af[ti] = as[(kk + lq) * C::LDA_S + 16 * ti];
 #pragma unroll
             for (int tj = 0; tj < C::NT; ++tj) bf[tj] = bs[16 * tj * C::LDB_S + kk + lq];
-#ifdef DTO_GEMM_SETPRIO
-            __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
             for (int ti = 0; ti < C::MT; ++ti)
 #pragma unroll
                 for (int tj = 0; tj < C::NT; ++tj)
                     acc.v[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[tj], af[ti], acc.v[ti][tj], 0, 0, 0);
-#ifdef DTO_GEMM_SETPRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
         }
         if (kb + 1 < nkb) store_panel(buf ^ 1);
         __syncthreads();
     }
 }
-// DMA-staged form (operands unscaled): the K panels go global -> LDS directly with `global_load_lds_dwordx4`
-// (1 KB per wave-instruction, no staging registers, no ds_write).  The LDS images are unpadded because a DMA
-// piece must be wave-contiguous; conflicts are avoided by the SOURCE permutation instead:
-//   As[k][m'] , m' = (m + 16 (k & 1)) mod TM   -- the two k's of a 32-lane ds_read_b64 group land 128 B apart
-//   Bs[kp][c][2]                                -- the two k's of a k-pair are adjacent: a group reads 256 contiguous B
-// Requires TM = TN = 128, KB = 16 (A: 16 pieces/panel, B: 16 pieces/panel, spread over the workgroup's waves).
+// an LDS / a global address for `global_load_lds_dwordx4` (LDS-DMA: 1 KB per wave-instruction, no staging registers, no ds_write)
 #define DTO_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define DTO_GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-template <class C>
-__device__ __forceinline__ void gemm_accumulate_dma(GemmAccS<C>& acc, const double* __restrict__ A, int lda,
-                                                    const double* __restrict__ B, int ldb, int Klen, double* smem) {
-    static_assert(C::TM == 128 && C::TN == 128 && C::KB == 16, "DMA staging is laid out for 128x128x16 panels");
-    constexpr int TM = 128, TN = 128, KB = 16, AS = KB * TM, BS = KB * TN;
-    constexpr int NW = C::THREADS / 64, PPW = 16 / NW;  // pieces per wave and operand
-    static_assert(2 * (AS + BS) <= C::SMEM_DOUBLES, "LDS budget");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / C::WC, wn = wave % C::WC;
-    const int lr = lane & 15, lq = lane >> 4;
-    double* As = smem;
-    double* Bs = smem + 2 * AS;
-    auto dma_panel = [&](int kb, int buf) {
-        const int k0 = kb * KB;
-#pragma unroll
-        for (int q = 0; q < PPW; ++q) {
-            const int k = wave + NW * q;
-            const int m = (2 * lane - 16 * (k & 1)) & (TM - 1);
-            __builtin_amdgcn_global_load_lds(DTO_GLB_PTR(A + (size_t)(k0 + k) * lda + m), DTO_LDS_PTR(As + buf * AS + k * TM), 16, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < PPW; ++q) {
-            const int piece = wave + NW * q;
-            const int g = piece * 64 + lane;
-            const int kp = g / TN, c = g % TN;
-            __builtin_amdgcn_global_load_lds(DTO_GLB_PTR(B + (size_t)c * ldb + k0 + 2 * kp), DTO_LDS_PTR(Bs + buf * BS + piece * 128), 16, 0, 0);
-        }
-    };
-    const int nkb = Klen / KB;
-    dma_panel(0, 0);
-    __syncthreads();  // its fence waits for the DMA (vmcnt(0)) before the barrier
-    for (int kb = 0; kb < nkb; ++kb) {
-        const int buf = kb & 1;
-        if (kb + 1 < nkb) dma_panel(kb + 1, buf ^ 1);
-        const double* as = As + buf * AS;
-        const double* bs = Bs + buf * BS;
-#pragma unroll
-        for (int kk = 0; kk < KB; kk += 4) {
-            const int k = kk + lq;
-            double af[C::MT], bf[C::NT];
-#pragma unroll
-            for (int ti = 0; ti < C::MT; ++ti) af[ti] = as[k * TM + ((wm * C::WTM + 16 * ti + lr + 16 * (k & 1)) & (TM - 1))];
-#pragma unroll
-            for (int tj = 0; tj < C::NT; ++tj) bf[tj] = bs[(k >> 1) * (TN * 2) + (wn * C::WTN + 16 * tj + lr) * 2 + (k & 1)];
-#pragma unroll
-            for (int ti = 0; ti < C::MT; ++ti)
-#pragma unroll
-                for (int tj = 0; tj < C::NT; ++tj)
-                    acc.v[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[tj], af[ti], acc.v[ti][tj], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-}
 
 // ------------------------------------------------------------------------------------------------------------------
-// "Paired rows" core (round 3): 16-byte LDS fragment reads and 16-byte epilogue accesses.
+// "Paired rows" core: 16-byte LDS fragment reads and 16-byte epilogue accesses.  It runs the generator-subspace GEMMs
+// (k_basis_gemm, k_basis_gemm_multi); the ring core keeps its accumulator layout, and with it the epilogue of the batched products.
+// (As a stand-alone batched kernel it beat the 8-byte core and lost to the ring core: DESIGN.md section 4.10.)
 //
 // Accumulator tile ti of a wave covers the rows 32 (ti/2) + 2 lr + (ti & 1) of the wave tile instead of 16 ti + lr, so the
 // two tiles 2p, 2p+1 of a lane hold two CONSECUTIVE rows: one ds_read_b128 feeds both A fragments, and an epilogue moves 16
@@ -239,16 +178,15 @@ __device__ __forceinline__ void gemm_accumulate_dma(GemmAccS<C>& acc, const doub
 // double step run in the order {0,2,4,6}, {1,3,5,7} -- lane group lq supplies k = 2 lq + s in step s, for both operands, and
 // a sum over k does not care.  LDS images (double buffered, one barrier per 16-deep panel):
 //   As[k][TM]      unpadded, pitch TM*8 = a multiple of 256 B: the b128 lane groups {0-3,12-15,20-27}, ... of two adjacent k
-//                  rows cover all 64 banks once; a K row is one wave-contiguous KB piece, so A can come by LDS-DMA
+//                  rows cover all 64 banks once; a K row is one wave-contiguous KB piece, so A comes by LDS-DMA
 //                  (`global_load_lds_dwordx4`, no staging registers) exactly as it lies in memory
 //   Bs[n][KB + 4]  pitch 160 B: conflict-free for the b128 reads (16-byte slot = 10 n + lq mod 16 is a bijection on every
 //                  lane group) and for the staging stores (8 consecutive lanes = 8 consecutive slots)
 // Measured (tools/bgemm_probe4, 2000 x 256^3, one box, steady state): 8-byte core 59.4-60.0 TFLOP/s, this core 60.5-61.1
-// with register staging and 62.2-62.5 with A by DMA; rocBLAS (torch.bmm) 52 / 61 (product / squaring) on another box.
+// with A staged through registers and 62.2-62.5 with A by DMA; rocBLAS (torch.bmm) 52 / 61 (product / squaring) on another box.
 template <int TM_, int TN_, int WR_ = 2, int WC_ = 2>
 struct GemmShapeP {
     static constexpr int TM = TM_, TN = TN_, WR = WR_, WC = WC_, KB = 16;
-    static constexpr bool PAIRED = true;
     static constexpr int THREADS = WR * WC * 64;
     static constexpr int LDB_S = KB + 4;
     static constexpr int AS_ELEMS = KB * TM;
@@ -256,39 +194,30 @@ struct GemmShapeP {
     static constexpr int SMEM_DOUBLES = 2 * (AS_ELEMS + BS_ELEMS);
     static constexpr int WTM = TM / WR, WTN = TN / WC;
     static constexpr int MT = WTM / 16, NT = WTN / 16;
-    static constexpr int A_LD = (TM * KB / 2) / THREADS, B_LD = (TN * KB / 2) / THREADS;
+    static constexpr int B_LD = (TN * KB / 2) / THREADS;
     static constexpr int A_PIECES = KB / (THREADS / 64);  // DMA pieces (K rows) per wave and panel
     static_assert(TM % 32 == 0 && WTM % 32 == 0 && WTN % 16 == 0, "wave tile: pairs of 16-row tiles");
     static_assert((TM * KB / 2) % THREADS == 0 && (TN * KB / 2) % THREADS == 0 && KB % (THREADS / 64) == 0, "panel loads must divide evenly");
     static_assert(TM == 128, "a DMA piece is one K row of 128 doubles");
 };
 
-template <class C, bool DMA_A>
+template <class C>
 __device__ __forceinline__ void gemm_accumulate_p(GemmAccS<C>& acc, const double* __restrict__ A, int lda,
-                                                  const double* __restrict__ B, int ldb, int Klen, double* smem,
-                                                  unsigned long long* prof = nullptr) {
+                                                  const double* __restrict__ B, int ldb, int Klen, double* smem) {
     constexpr int TM = C::TM, KB = C::KB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / C::WC, wn = wave % C::WC;
     const int lr = lane & 15, lq = lane >> 4;
     double* As = smem;
     double* Bs = smem + 2 * C::AS_ELEMS;
-    d2 ra[DMA_A ? 1 : C::A_LD], rb[C::B_LD];
+    d2 rb[C::B_LD];
     const int nkb = Klen / KB;
     auto load_panel = [&](int kb, int buf) {
         const int k0 = kb * KB;
-        if constexpr (DMA_A) {
 #pragma unroll
-            for (int q = 0; q < C::A_PIECES; ++q) {
-                const int k = wave + (C::THREADS / 64) * q;
-                __builtin_amdgcn_global_load_lds(DTO_GLB_PTR(A + (size_t)(k0 + k) * lda + 2 * lane), DTO_LDS_PTR(As + buf * C::AS_ELEMS + k * TM), 16, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < C::A_LD; ++i) {
-                const int idx = tid + C::THREADS * i;
-                ra[i] = *reinterpret_cast<const d2*>(A + (size_t)(k0 + idx / (TM / 2)) * lda + 2 * (idx % (TM / 2)));
-            }
+        for (int q = 0; q < C::A_PIECES; ++q) {
+            const int k = wave + (C::THREADS / 64) * q;
+            __builtin_amdgcn_global_load_lds(DTO_GLB_PTR(A + (size_t)(k0 + k) * lda + 2 * lane), DTO_LDS_PTR(As + buf * C::AS_ELEMS + k * TM), 16, 0, 0);
         }
 #pragma unroll
         for (int i = 0; i < C::B_LD; ++i) {
@@ -297,13 +226,6 @@ __device__ __forceinline__ void gemm_accumulate_p(GemmAccS<C>& acc, const double
         }
     };
     auto store_panel = [&](int buf) {
-        if constexpr (!DMA_A) {
-#pragma unroll
-            for (int i = 0; i < C::A_LD; ++i) {
-                const int idx = tid + C::THREADS * i;
-                *reinterpret_cast<d2*>(As + buf * C::AS_ELEMS + (idx / (TM / 2)) * TM + 2 * (idx % (TM / 2))) = ra[i];
-            }
-        }
 #pragma unroll
         for (int i = 0; i < C::B_LD; ++i) {
             const int idx = tid + C::THREADS * i;
@@ -336,20 +258,6 @@ __device__ __forceinline__ void gemm_accumulate_p(GemmAccS<C>& acc, const double
                                                                              acc.v[ti][tj], 0, 0, 0);
             }
         }
-#ifdef DTO_TUNING
-        if (prof) {  // phase stamps (tools/stamp_analyze.py): cycles this wave waits for the next panel's loads, and at the barrier
-            const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-            __builtin_amdgcn_s_waitcnt(0);
-            const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-            if (kb + 1 < nkb) store_panel(buf ^ 1);
-            const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-            __syncthreads();
-            const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-            prof[0] += t1 - t0;
-            prof[1] += t3 - t2;
-            continue;
-        }
-#endif
         if (kb + 1 < nkb) store_panel(buf ^ 1);
         __syncthreads();
     }

@@ -16,14 +16,13 @@
 //   (2) the GENERATOR SWEEP   exp(A)x, dexp(A)[G_j]x, ... as Taylor recurrences on vectors where
 //       every product with A = dt*sum_j ubar_j G_j is expanded over the SHARED generators, so that
 //       one step for all knots is a single GEMM  [G_0 .. G_m] x (columns of all knots)  (k_sweep).
+#include "dto_bgemm_dispatch.h"
 #include "dto_gemm.hip.h"
 #include "dto_gemm_ring.hip.h"
 #include "dto_kernels.h"
 #include "dto_hostxfer.h"
 
 #include <cstdlib>
-#include <string>
-#include <vector>
 
 namespace dto {
 
@@ -171,55 +170,32 @@ __device__ __forceinline__ void basis_epilogue(const GemmAccS<Cfg>& acc, int npa
     static_assert(Cfg::WTM == 64, "column sums assume 64-row wave tiles");
     const int64_t nn = (int64_t)npad * npad;
     const int wave_row0 = rt * TM + ((threadIdx.x >> 6) / Cfg::WC) * Cfg::WTM;
-    if constexpr (Cfg::PAIRED) {
-        GemmCoordP<Cfg> co;
-        const int row0 = rt * TM + co.row_base, col0 = ct * TN + co.col_base;
+    GemmCoordP<Cfg> co;
+    const int row0 = rt * TM + co.row_base, col0 = ct * TN + co.col_base;
 #pragma unroll
-        for (int tj = 0; tj < Cfg::NT; ++tj)
+    for (int tj = 0; tj < Cfg::NT; ++tj)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int col = col0 + 16 * tj + 4 * r;
-                double asum = 0.0;
+        for (int r = 0; r < 4; ++r) {
+            const int col = col0 + 16 * tj + 4 * r;
+            double asum = 0.0;
 #pragma unroll
-                for (int p = 0; p < Cfg::MT / 2; ++p) {
-                    const d2 v = {acc.v[2 * p][tj][r], acc.v[2 * p + 1][tj][r]};
-                    if (out && col < nb) __builtin_nontemporal_store(v, reinterpret_cast<d2*>(&out[(int64_t)col * nn + row0 + 32 * p]));
-                    asum += fabs(v.x) + fabs(v.y);
-                }
-                if (colsum) {
-#pragma unroll
-                    for (int o = 8; o > 0; o >>= 1) asum += __shfl_xor(asum, o, 64);
-                    if ((threadIdx.x & 15) == 0 && col < nb) colsum[((int64_t)col * npad + wave_row0 / npad) * (npad / 64) + (wave_row0 % npad) / 64] = asum;
-                }
+            for (int p = 0; p < Cfg::MT / 2; ++p) {
+                const d2 v = {acc.v[2 * p][tj][r], acc.v[2 * p + 1][tj][r]};
+                if (out && col < nb) __builtin_nontemporal_store(v, reinterpret_cast<d2*>(&out[(int64_t)col * nn + row0 + 32 * p]));
+                asum += fabs(v.x) + fabs(v.y);
             }
-    } else {
-        GemmCoordS<Cfg> co;
-        const int row0 = rt * TM + co.row_base, col0 = ct * TN + co.col_base;
+            if (colsum) {
 #pragma unroll
-        for (int tj = 0; tj < Cfg::NT; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int col = col0 + 16 * tj + 4 * r;
-                double asum = 0.0;
-#pragma unroll
-                for (int ti = 0; ti < Cfg::MT; ++ti) {
-                    if (out && col < nb) __builtin_nontemporal_store(acc.v[ti][tj][r], &out[(int64_t)col * nn + row0 + 16 * ti]);
-                    asum += fabs(acc.v[ti][tj][r]);
-                }
-                if (colsum) {
-#pragma unroll
-                    for (int o = 8; o > 0; o >>= 1) asum += __shfl_xor(asum, o, 64);
-                    if ((threadIdx.x & 15) == 0 && col < nb) colsum[((int64_t)col * npad + wave_row0 / npad) * (npad / 64) + (wave_row0 % npad) / 64] = asum;
-                }
+                for (int o = 8; o > 0; o >>= 1) asum += __shfl_xor(asum, o, 64);
+                if ((threadIdx.x & 15) == 0 && col < nb) colsum[((int64_t)col * npad + wave_row0 / npad) * (npad / 64) + (wave_row0 % npad) / 64] = asum;
             }
-    }
+        }
 }
 template <class Cfg>
 __device__ __forceinline__ void basis_accumulate(GemmAccS<Cfg>& acc, const BasisSet& bs, int64_t nn, int rt, int ct, double* smem) {
     const double* A = bs.S + (int64_t)rt * Cfg::TM;
     const double* B = bs.coef + (int64_t)ct * Cfg::TN * bs.cntpad;
-    if constexpr (Cfg::PAIRED) gemm_accumulate_p<Cfg, true>(acc, A, (int)nn, B, bs.cntpad, bs.cntpad, smem);
-    else gemm_accumulate_s<Cfg>(acc, A, (int)nn, B, bs.cntpad, bs.cntpad, nullptr, smem);
+    gemm_accumulate_p<Cfg>(acc, A, (int)nn, B, bs.cntpad, bs.cntpad, smem);
 }
 
 // out[:, b] = S * coef[:, b]  for the nb intervals of the chunk (FP64 MFMA, same GEMM core).
@@ -294,14 +270,8 @@ void launch_basis_gemm_multi(hipStream_t st, int npad, int nb, int nbpad, int ns
     M.nsets = nsets;
     for (int q = 0; q < nsets; ++q) { M.bs[q] = bs[q]; M.out[q] = out[q]; M.colsum[q] = colsum[q]; }
     const dim3 grid((unsigned)((nn / 128) * (nbpad / 128) * nsets));
-    static const int core = tune_int("DTO_BASIS_CORE", 1);  // 1: paired-rows core (round 3), 0: the 8-byte core
-    if (core == 1) {
-        using C = GemmShapeP<128, 128, 2, 4>;
-        hipLaunchKernelGGL((k_basis_gemm_multi<C>), grid, dim3(C::THREADS), 0, st, npad, nb, M);
-    } else {
-        using C = GemmShape<128, 128, 2, 4, 16>;
-        hipLaunchKernelGGL((k_basis_gemm_multi<C>), grid, dim3(C::THREADS), 0, st, npad, nb, M);
-    }
+    using C = GemmShapeP<128, 128, 2, 4>;
+    hipLaunchKernelGGL((k_basis_gemm_multi<C>), grid, dim3(C::THREADS), 0, st, npad, nb, M);
 }
 __global__ void k_basis_coef_multi(KProb P, KBil B, BasisMulti M, const double* __restrict__ Z, int64_t int0, int nb) {
     const int b = blockIdx.x;
@@ -365,14 +335,8 @@ void launch_basis_gemm(hipStream_t st, int npad, int nb, int nbpad, const BasisS
     // 8 waves of 64x32 per 128x128 tile: the K loop is only 1..8 panels long, more waves hide its prologue and the
     // store-heavy epilogue better than 4 waves of 64x64 (measured -7 % per launch at 256x2000; 128x64 tiles +9 %)
     const dim3 grid((unsigned)((nn / 128) * (nbpad / 128)));
-    static const int core = tune_int("DTO_BASIS_CORE", 1);
-    if (core == 1) {
-        using C = GemmShapeP<128, 128, 2, 4>;
-        hipLaunchKernelGGL((k_basis_gemm<C>), grid, dim3(C::THREADS), 0, st, npad, nb, bs, out, colsum);
-    } else {
-        using C = GemmShape<128, 128, 2, 4, 16>;
-        hipLaunchKernelGGL((k_basis_gemm<C>), grid, dim3(C::THREADS), 0, st, npad, nb, bs, out, colsum);
-    }
+    using C = GemmShapeP<128, 128, 2, 4>;
+    hipLaunchKernelGGL((k_basis_gemm<C>), grid, dim3(C::THREADS), 0, st, npad, nb, bs, out, colsum);
 }
 
 // One wavefront per column c of the owned knots: walk the column's entries in the structure's order
@@ -591,18 +555,14 @@ struct BGemmArgs {
     KBil Bi;
     int64_t int0;
     double* vals;
-#ifdef DTO_TUNING
-    int stamp_detail;             // 1: also the per-panel waits (perturbs the loop)
-    unsigned long long* stamps;   // phase stamps, 8 per tile (tools/stamp_analyze.py): HW_ID | XCC_ID << 32, cycles at start / loop end / end, 100 MHz ticks at start / end, cycles waiting for panel loads / at the loop barrier
-#endif
 };
 
-// Batched C_b = A_b * B_b over nbatch intervals, npad x npad x npad each (FP64 MFMA).
-// PERSISTENT: the grid is sized to the chip (2 workgroups per CU) and every workgroup walks the
-// (interval, tile) list with a stride of gridDim.x; this removes the workgroup re-dispatch gaps that a
-// one-tile-per-workgroup grid of ~8000 short workgroups shows (measured: 25 % of wall time).
-template <class Cfg, int EPI, bool DMA = false>
-__global__ void __launch_bounds__(Cfg::THREADS, (Cfg::THREADS / 256) * (Cfg::SMEM_DOUBLES * 8 > 80 * 1024 ? 1 : 2))
+// Batched C_b = A_b * B_b over nbatch intervals, npad x npad x npad each (FP64 MFMA), on the 8-byte core of dto_gemm.hip.h; it runs
+// with 64x64 tiles and four waves only (dto_bgemm_dispatch.h says where).  Every workgroup walks the (interval, tile) list with a
+// stride of gridDim.x, so the grid may be one workgroup per tile or PERSISTENT, sized to the chip: that removes the workgroup
+// re-dispatch gaps that a one-tile-per-workgroup grid of ~8000 short workgroups shows (measured: 25 % of wall time).
+template <class Cfg, int EPI>
+__global__ void __launch_bounds__(Cfg::THREADS, 2)
 k_bgemm(BGemmArgs a) {
     __shared__ __attribute__((aligned(1024))) double smem[Cfg::SMEM_DOUBLES];
     constexpr int TM = Cfg::TM, TN = Cfg::TN;
@@ -625,8 +585,7 @@ k_bgemm(BGemmArgs a) {
 
         GemmAccS<Cfg> acc;
         acc.zero();
-        if constexpr (DMA) gemm_accumulate_dma<Cfg>(acc, Ab, a.npad, Bb, a.npad, a.npad, smem);
-        else gemm_accumulate_s<Cfg>(acc, Ab, a.npad, Bb, a.npad, a.npad, nullptr, smem);
+        gemm_accumulate_s<Cfg>(acc, Ab, a.npad, Bb, a.npad, a.npad, nullptr, smem);
 
         const int row0 = tr * TM + co.row_base, col0 = tc * TN + co.col_base;
 
@@ -712,7 +671,7 @@ k_bgemm(BGemmArgs a) {
     }
 }
 
-// Epilogue of the paired-rows accumulator layout, shared by k_bgemm_p and the ring kernel k_bgemm_r: tile (tr, tc) of interval b.
+// Epilogue of the ring kernel k_bgemm_r (paired-rows accumulator layout, dto_gemm.hip.h): tile (tr, tc) of interval b.
 template <class Cfg, int EPI>
 __device__ __forceinline__ void bgemm_p_epilogue(const BGemmArgs& a, const GemmAccS<Cfg>& acc, int b, int tr, int tc, int s_b, int64_t nn) {
     constexpr int TM = Cfg::TM, TN = Cfg::TN, MP = Cfg::MT / 2;
@@ -785,62 +744,6 @@ __device__ __forceinline__ void bgemm_p_epilogue(const BGemmArgs& a, const GemmA
         }
 }
 
-// The same batched product on the paired-rows core (dto_gemm.hip.h, round 3): 16-byte fragment reads, A panels by LDS-DMA
-// (DMA_A) or through registers, every epilogue access 16 bytes per lane.  Epilogue semantics are those of k_bgemm.
-template <class Cfg, int EPI, bool DMA_A>
-__global__ void __launch_bounds__(Cfg::THREADS, (Cfg::THREADS / 256) * 2)
-k_bgemm_p(BGemmArgs a) {
-    __shared__ __attribute__((aligned(1024))) double smem[Cfg::SMEM_DOUBLES];
-    constexpr int TM = Cfg::TM, TN = Cfg::TN;
-    const int tiles_r = a.npad / TM;
-    const int tpm = tiles_r * (a.npad / TN);
-    const int total = batch_tile_count(a.nbatch, tpm);
-    const int64_t nn = (int64_t)a.npad * a.npad;
-    for (int v = blockIdx.x; v < total; v += gridDim.x) {
-        int b, tile;
-        if (!decode_batch_tile(v, a.nbatch, tpm, b, tile)) continue;
-        int s_b = 0;
-        if (EPI == EPI_SQUARE) {
-            s_b = a.s[b];
-            if (a.it >= s_b) continue;  // this interval needs no further squaring
-        }
-        const int tr = tile % tiles_r, tc = tile / tiles_r;
-        const double* Ab = a.A + b * nn + (int64_t)tr * TM;
-        const double* Bb = a.B + b * nn + (int64_t)tc * TN * a.npad;
-#ifdef DTO_TUNING
-        unsigned long long st0 = 0, st1 = 0, rt0 = 0;
-        if (a.stamps) { st0 = __builtin_amdgcn_s_memtime(); rt0 = __builtin_amdgcn_s_memrealtime(); }
-#endif
-
-        GemmAccS<Cfg> acc;
-        acc.zero();
-#ifdef DTO_TUNING
-        unsigned long long waits[2] = {0, 0};
-        gemm_accumulate_p<Cfg, DMA_A>(acc, Ab, a.npad, Bb, a.npad, a.npad, smem, a.stamps && a.stamp_detail ? waits : nullptr);
-#else
-        gemm_accumulate_p<Cfg, DMA_A>(acc, Ab, a.npad, Bb, a.npad, a.npad, smem);
-#endif
-#ifdef DTO_TUNING
-        if (a.stamps) st1 = __builtin_amdgcn_s_memtime();
-        struct StampAtExit {   // every path out of the tile body passes here
-            unsigned long long *dst, st0, st1, rt0, w0, w1;
-            __device__ ~StampAtExit() {
-                if (!dst) return;
-                __builtin_amdgcn_s_waitcnt(0);   // the tile's loads and stores have been issued and the loads are back
-                if (threadIdx.x == 0) {
-                    dst[0] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
-                             ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32);
-                    dst[1] = st0; dst[2] = st1; dst[3] = __builtin_amdgcn_s_memtime(); dst[4] = rt0; dst[5] = __builtin_amdgcn_s_memrealtime();
-                    dst[6] = w0; dst[7] = w1;
-                }
-            }
-        } stamp_at_exit{a.stamps ? a.stamps + 8ll * v : nullptr, st0, st1, rt0, waits[0], waits[1]};
-#endif
-
-        bgemm_p_epilogue<Cfg, EPI>(a, acc, b, tr, tc, s_b, nn);
-    }
-}
-
 // The same products on the ring core (dto_gemm_ring.hip.h): persistent, K panels of all of a workgroup's tiles in one LDS ring.
 template <int EPI, int S>
 __global__ void __launch_bounds__(512, 4) k_bgemm_r(BGemmArgs a) {
@@ -873,147 +776,17 @@ __global__ void __launch_bounds__(512, 4) k_bgemm_r(BGemmArgs a) {
            });
 }
 
-static int bgemm_shape_choice() {
-    static int v = tune_int("DTO_BGEMM_SHAPE", -1);
-    return v;
-}
-static int bgemm_dma_choice() {  // -1: per-epilogue default, 0/1: forced
-    static int v = tune_int("DTO_BGEMM_DMA", -1);
-    return v;
-}
-static int bgemm_wgs_choice() {  // -1: per-epilogue default, 0: one workgroup per tile, k: k persistent workgroups per CU
-    static int v = tune_int("DTO_BGEMM_WGS_PER_CU", -1);
-    return v;
-}
-// Measured in the engine at 256x2000 (ms per launch, fused-polynomial / squaring):
-//   register staging, persistent 1.48 / 1.25    register staging, one WG per tile 1.37 / 1.27
-//   DMA staging,      persistent 1.56 / 1.20    DMA staging,      one WG per tile 1.47 / 1.23
-// so the polynomial products run one workgroup per tile with register staging, the plain products and the
-// squarings run persistent with DMA staging.
-template <class Cfg, int EPI>
-static void launch_bgemm_shape(hipStream_t st, const BGemmArgs& a, int wgs_per_cu) {
-    int grid = batch_tile_count(a.nbatch, (a.npad / Cfg::TM) * (a.npad / Cfg::TN));
-    int wgs = bgemm_wgs_choice();
-    if (wgs < 0) wgs = epi_poly(EPI) ? 0 : wgs_per_cu;
-    else if (wgs > 0) wgs = wgs_per_cu;
-    if (wgs > 0 && grid > wgs * 256) grid = wgs * 256;
-    if constexpr (Cfg::TM == 128 && Cfg::TN == 128 && Cfg::KB == 16) {
-        int dma = bgemm_dma_choice();
-        if (dma < 0) dma = epi_poly(EPI) ? 0 : 1;
-        if (dma) {
-            hipLaunchKernelGGL((k_bgemm<Cfg, EPI, true>), dim3(grid), dim3(Cfg::THREADS), 0, st, a);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((k_bgemm<Cfg, EPI, false>), dim3(grid), dim3(Cfg::THREADS), 0, st, a);
-}
-#ifdef DTO_TUNING
-// DTO_STAMP_FILE=<path> DTO_STAMP_LAUNCH=<k>: launches k .. k+7 of the paired-core GEMM in this process record their phase stamps
-// into <path>.<launch>.epi<EPI> (tools/stamp_analyze.py)
-static unsigned long long* stamps_begin(hipStream_t st, const BGemmArgs& a, size_t& bytes, int& index) {
-    static int launches = 0;
-    static const int which = tune_int("DTO_STAMP_LAUNCH", -1);
-    index = launches++;
-    if (which < 0 || index < which || index >= which + 8 || !getenv("DTO_STAMP_FILE")) return nullptr;
-    bytes = 8ull * 8 * batch_tile_count(a.nbatch, (a.npad / 128) * (a.npad / 128));
-    unsigned long long* d = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-    (void)hipMemsetAsync(d, 0, bytes, st);
-    return d;
-}
-static void stamps_end(hipStream_t st, unsigned long long* d, size_t bytes, int index, int epi) {
-    if (!d) return;
-    (void)hipStreamSynchronize(st);
-    std::vector<unsigned long long> h(bytes / 8);
-    (void)hipMemcpy(h.data(), d, bytes, hipMemcpyDeviceToHost);
-    const std::string path = std::string(getenv("DTO_STAMP_FILE")) + "." + std::to_string(index) + ".epi" + std::to_string(epi);
-    if (FILE* f = fopen(path.c_str(), "wb")) { fwrite(h.data(), 1, bytes, f); fclose(f); }
-    (void)hipFree(d);
-}
-#endif
-// paired-rows core: persistent for the plain products and the squarings (A by DMA), one workgroup per tile for the
-// polynomial products (their epilogues stream 3-4 more matrices; A through registers), as measured for the 8-byte core
-template <class Cfg, int EPI>
-static void launch_bgemm_p(hipStream_t st, const BGemmArgs& a_in) {
-    BGemmArgs a = a_in;
-#ifdef DTO_TUNING
-    size_t stamp_bytes = 0;
-    int stamp_index = 0;
-    a.stamps = stamps_begin(st, a, stamp_bytes, stamp_index);
-    a.stamp_detail = tune_int("DTO_STAMP_DETAIL", 0);
-#endif
-    int grid = batch_tile_count(a.nbatch, (a.npad / Cfg::TM) * (a.npad / Cfg::TN));
-    int wgs = bgemm_wgs_choice();
-    if (wgs < 0) wgs = epi_poly(EPI) ? 0 : 2;
-    if (wgs > 0 && grid > wgs * 256) grid = wgs * 256;
-    int dma = bgemm_dma_choice();
-    if (dma < 0) dma = epi_poly(EPI) ? 0 : 1;
-    if (dma) hipLaunchKernelGGL((k_bgemm_p<Cfg, EPI, true>), dim3(grid), dim3(Cfg::THREADS), 0, st, a);
-    else hipLaunchKernelGGL((k_bgemm_p<Cfg, EPI, false>), dim3(grid), dim3(Cfg::THREADS), 0, st, a);
-#ifdef DTO_TUNING
-    stamps_end(st, a.stamps, stamp_bytes, stamp_index, EPI);
-#endif
-}
+// Which of the two kernels, and with what grid: dto_bgemm_dispatch.h.  Measured for the ring kernel against the double-buffered cores
+// it replaced: 1.47 -> 1.39 ms per squaring at 256 x 2000, 2.28 -> 2.01 at 512 x 500, 8.16 -> 7.65 at 1024 x 500; a polynomial product
+// 1.60 -> 1.535 ms at 256 x 2000, 8.63 -> 8.29 at 1024 x 500 (A/B logs r03ah/ab_ring*.log; three or five ring slots, two or four
+// tiles per workgroup for the polynomial products: all slower, ab_ring5.log).
 template <int EPI>
 static void launch_bgemm(hipStream_t st, const BGemmArgs& a) {
-    // 128x128 tiles (persistent, DMA-staged) win once the launch is large; short trajectories are better served by four
-    // times as many 64x64 workgroups.  Measured crossover (tile-128 workgroups x K panels): 256x200 -17 % with 64-tiles,
-    // 256x500 equal, 256x1000 and 512x100 +5..7 % with 128-tiles (DTO_BGEMM_TILE64=0/1 forces).
-    static const int force64 = tune_int("DTO_BGEMM_TILE64", -1);
-    const long t128 = a.npad / 128;
-    // (with the ring core the 128-tiles win at every launch size from 256 states on, even 30 intervals: 256 x 250 2.12 -> 2.07 ms,
-    // 256 x 100 1.35 -> 1.26 per Jacobian; at 128 states, one tile per matrix, the crossover stands -- gpurun_out/r03ag/ab_tile*.log)
-    const bool small_launch = force64 >= 0 ? force64 != 0 : (t128 == 1 && a.nbatch < 3500);
-    if (a.npad % 128 == 0 && small_launch && bgemm_shape_choice() < 0) {
-        launch_bgemm_shape<GemmShape<64, 64, 2, 2, 16>, EPI>(st, a, 4);
-        return;
-    }
-    // Ring core (K panels in an LDS ring, both operands by LDS-DMA, dto_gemm_ring.hip.h).  The plain products and the squarings run
-    // it PERSISTENT (the next tile's panels in flight during the epilogue): 1.47 -> 1.39 ms per squaring at 256 x 2000, 2.28 -> 2.01
-    // at 512 x 500, 8.16 -> 7.65 at 1024 x 500.  The polynomial products, bound by the bytes of their epilogues, keep one workgroup per
-    // tile (persistent they lose 5-15 %) and still gain from the ring inside the tile: 1.60 -> 1.535 ms at 256 x 2000, 8.63 -> 8.29 at
-    // 1024 x 500 (gpurun_out/r03ah/ab_ring*.log).
-    static const int ring = tune_int("DTO_BGEMM_RING", -1);  // -1: as described, 0: never, 1: everything persistent
-    if (a.npad % 128 == 0 && ring != 0 && bgemm_shape_choice() < 0) {
-        int grid = batch_tile_count(a.nbatch, (a.npad / 128) * (a.npad / 128));
-        if (grid > 2 * 256 && (ring == 1 || !epi_poly(EPI))) grid = 2 * 256;
-        // (three or five slots, two or four tiles per workgroup for the polynomial products: all slower, gpurun_out/r03ah/ab_ring5.log)
-        hipLaunchKernelGGL((k_bgemm_r<EPI, 4>), dim3(grid), dim3(512), 0, st, a);
-        return;
-    }
-    static const int core = tune_int("DTO_BGEMM_CORE", 1);  // 1: paired-rows core (round 3), 0: the 8-byte core
-    if (a.npad % 128 == 0 && core == 1 && bgemm_shape_choice() < 0) {
-        static const int w8 = tune_int("DTO_BGEMM_P_WAVES8", -1);  // -1: 8 waves for the polynomial epilogues only
-        if (w8 > 0 || (w8 < 0 && epi_poly(EPI))) launch_bgemm_p<GemmShapeP<128, 128, 2, 4>, EPI>(st, a);
-        else launch_bgemm_p<GemmShapeP<128, 128, 2, 2>, EPI>(st, a);
-        return;
-    }
-    if (a.npad % 256 == 0) {
-        // shapes measured with tools/bgemm_probe2 (256x2000): see DESIGN.md
-#ifdef DTO_TUNING  // the alternative shapes exist in `make TUNING=1` builds only
-        switch (bgemm_shape_choice()) {
-            case 0: launch_bgemm_shape<GemmShape<128, 128, 2, 2, 16>, EPI>(st, a, 2); return;
-            case 1: launch_bgemm_shape<GemmShape<128, 128, 2, 2, 8>, EPI>(st, a, 2); return;
-            case 2: launch_bgemm_shape<GemmShape<256, 128, 4, 2, 16>, EPI>(st, a, 1); return;
-            case 3: launch_bgemm_shape<GemmShape<256, 128, 4, 2, 8>, EPI>(st, a, 1); return;
-            case 4: launch_bgemm_shape<GemmShape<128, 256, 2, 4, 16>, EPI>(st, a, 1); return;
-            case 5: launch_bgemm_shape<GemmShape<128, 256, 2, 4, 8>, EPI>(st, a, 1); return;
-            case 6: launch_bgemm_shape<GemmShape<128, 128, 2, 4, 16>, EPI>(st, a, 2); return;
-            case 7: launch_bgemm_shape<GemmShape<128, 128, 4, 2, 16>, EPI>(st, a, 2); return;
-            case 8: launch_bgemm_shape<GemmShape<128, 128, 2, 4, 8>, EPI>(st, a, 3); return;
-            default: break;
-        }
-#endif
-        // measured in the engine (256x2000): the fused-polynomial epilogue hides better behind 8 waves,
-        // the plain / squaring products run faster with 4 waves of 64x64
-        if (epi_poly(EPI)) launch_bgemm_shape<GemmShape<128, 128, 2, 4, 16>, EPI>(st, a, 2);
-        else launch_bgemm_shape<GemmShape<128, 128, 2, 2, 16>, EPI>(st, a, 2);
-    } else if (a.npad % 128 == 0) {
-        if (epi_poly(EPI)) launch_bgemm_shape<GemmShape<128, 128, 2, 4, 16>, EPI>(st, a, 2);
-        else launch_bgemm_shape<GemmShape<128, 128, 2, 2, 16>, EPI>(st, a, 2);
-    } else {
-        launch_bgemm_shape<GemmShape<64, 64, 2, 2, 16>, EPI>(st, a, 4);
-    }
+    static const int force64 = tune_int("DTO_BGEMM_TILE64", -1);  // 0 / 1 forces
+    static const int ring = tune_int("DTO_BGEMM_RING", -1);       // 1: everything persistent
+    const BGemmLaunch l = bgemm_dispatch(a.npad, a.nbatch, epi_poly(EPI), force64, ring == 1);
+    if (l.ring) hipLaunchKernelGGL((k_bgemm_r<EPI, 4>), dim3(l.grid), dim3(l.threads), 0, st, a);
+    else hipLaunchKernelGGL((k_bgemm<GemmShape<64, 64, 2, 2, 16>, EPI>), dim3(l.grid), dim3(l.threads), 0, st, a);
 }
 
 void launch_bgemm_plain(hipStream_t st, int npad, int nb, const double* A, const double* Bm, double* C) {
@@ -1045,9 +818,6 @@ void launch_bgemm_square(hipStream_t st, int npad, int nb, const ChainWork& w, i
     BGemmArgs a{};
     a.A = w.W[src]; a.B = w.W[src]; a.C = w.W[dst]; a.npad = npad; a.nbatch = nb;
     a.s = w.s; a.it = it; a.P = P; a.Bi = B; a.int0 = int0; a.vals = vals;
-#ifdef DTO_TUNING
-    if (tune_int("DTO_SQ_PLAIN", 0)) a.it = -1;  // timing experiment (wrong results): the last squaring stores into W like the others
-#endif
     launch_bgemm<EPI_SQUARE>(st, a);
 }
 

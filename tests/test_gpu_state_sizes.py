@@ -1,4 +1,5 @@
-"""GPU: 257..1023 states against the oracle -- the sizes between the 256-state tests and the 1024-state workload.
+"""GPU: 257..1023 states against the oracle -- the sizes between the 256-state tests and the 1024-state workload -- and 65 states
+on 3489 / 3509 intervals, the one place where a launch's LENGTH chooses between the two batched-GEMM kernels.
 
 Above 256 states the engine runs code of its own: padding to npad = pad64(n) with the chain's GEMMs on 64 x 64 tiles where
 npad % 128 != 0 (320, 448, 576, 704, 832, 960) and the sweeps 64 columns wide; the persistent ring core on 128 x 128 tiles
@@ -119,3 +120,50 @@ def test_large_steps_at_384_states_take_substeps_and_leave_the_pairing_path():
     assert big["jac_stats"][0] > small["jac_stats"][0], (big, small)
     # pairing path: the forward p column and the pairing products are two timed regions of kind expmv; second-order columns: one
     assert small["hess"]["expmv"] == 2 and big["hess"]["expmv"] == 1, (big, small)
+
+
+@pytest.mark.parametrize("N,kernel", [(3490, "64-tile"), (3510, "ring")])
+def test_one_tile_per_matrix_on_both_sides_of_the_3500_interval_crossover(N, kernel):
+    """65 states (npad 128: ONE 128-tile per matrix), 1 drive, default options.  With a single tile per matrix the batched GEMMs take
+    the 64-tile kernel below 3500 intervals in the launch and the ring kernel from 3500 on (csrc/dto_bgemm_dispatch.h; the rule
+    itself is checked by test_bgemm_dispatch_header.py): 3489 intervals in one launch run the first, 3509 the second -- the ring
+    kernel with tiles_r = 1, its persistent grid of 512 wrapping round 3512 slots.
+    The launch holds all the intervals only when the chain runs as ONE chunk, which the device-pointer Jacobian does (asserted through
+    the count of generator-subspace launches); the host-pointer eval_constraint_jacobian cuts the chain into four chunks for its early
+    hand-over of finished blocks (880 intervals per launch: the 64-tile kernel at either length).  Both are evaluated and both compared:
+    Jacobian column blocks (and the chain-vs-sweep cross check) of six intervals against two-knot oracle problems -- the first, the
+    last, both sides of the first wrap of the persistent grid (slots 511 | 512), and two inside later rounds."""
+    import torch
+    import dto_amd
+    n, m, K = 65, 1, N - 1
+    ks = (0, 511, 512, 1777, 3072, K - 1)
+    prob = dto_amd.host.synthetic.make_scaled_problem(N, n, m, seed=N)
+    ev = dto_amd.Evaluator(prob, eval_hessian=False)
+    try:
+        Z = prob.trajectory.vec()
+        cons = np.full(ev.n_constraints, np.nan); ev.eval_constraint(cons, Z)
+        assert np.isfinite(cons).all()
+        ev.profile_enable(True)
+        # host pointers, default options (what a solver calls)
+        ev.profile_reset()
+        jac = np.full(ev.n_jacobian_entries, np.nan); ev.eval_constraint_jacobian(jac, Z)
+        host_chunks = _launches(ev, "basis_multi")
+        assert np.isfinite(jac).all() and _launches(ev, "chain64") == 0
+        sampled_checks(prob, ev, n, m, ks, host_getter(jac), None, cons)
+        del jac
+        # device pointers: one chunk, every batched GEMM of the chain a launch of K intervals
+        dev = torch.device("cuda", 0)
+        dZ = torch.from_numpy(Z).to(dev)
+        dj = torch.full((ev.n_jacobian_entries,), float("nan"), dtype=torch.float64, device=dev)
+        ev.profile_reset()
+        ev.eval_jacobian_dev(dZ.data_ptr(), dj.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize()
+        dev_chunks = _launches(ev, "basis_multi")
+        ev.profile_enable(False)
+        print(kernel, "chunks: host form", host_chunks, "device form", dev_chunks, ev.last_stats())
+        assert dev_chunks == 1 and _launches(ev, "chain64") == 0, (host_chunks, dev_chunks)
+        assert bool(torch.isfinite(dj).all())
+        sampled_checks(prob, ev, n, m, ks, lambda lo, hi: dj[lo:hi].cpu().numpy(), None, cons)
+        del dj
+    finally:
+        ev.close()

@@ -1,7 +1,7 @@
 // Tuning probe #5 (round 3): the batched FP64 GEMM core as a RING of K panels filled by LDS-DMA for both operands.
 // Not part of the product.  build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/bgemm_probe5.hip -o tools/bgemm_probe5
 //
-// What tools/stamp_analyze.py showed for the paired-rows core (V1): a workgroup alone on a CU keeps the matrix pipe 75 % busy --
+// What the phase stamps showed for the paired-rows core (V1): a workgroup alone on a CU keeps the matrix pipe 75 % busy --
 // every K panel ends in  wait for the staged loads -> ds_write -> barrier -> fragment reads -> first MFMA,  a chain that all waves
 // of the workgroup walk in step, so nothing covers it.  V2 removes the chain:
 //   * panels of 8 k live in a ring of S slots (A: [k][128] rows, B: [n][8] columns with the 16-byte units XOR-swizzled so that

@@ -41,7 +41,7 @@ def main():
            "algorithmic_per_call_bytes": 8.0 * (275462200 + 530000 + 5 * 256 * 256)}
     i = 0
     for k, v in bg.items():
-        m = re.search(r"k_bgemm_r<(\d+),", k) or re.search(r">, (\d+),", k)   # epilogue kind: ring kernel / double-buffered kernels
+        m = re.search(r"k_bgemm_r<(\d+),", k)   # epilogue kind (at this size every callback product runs the ring kernel)
         epi = m.group(1) if m else "?"
         name = "square" if epi == "2" else f"product{ {'3': 1, '4': 2, '1': 3}.get(epi, 9) }"
         out["per_launch_bytes"][name] = {"read": v["read"], "write": v["write"], "kernel": k[:100]}
