@@ -100,6 +100,62 @@ void find_share_groups(dto_handle* h, const dto_problem_desc* d) {
     }
 }
 
+// The same flag on DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR integrators: groups of equal x_dim, control and time component, scheme
+// (order, substeps), modulations and matrices G_j, H_cj (==).  Never mixed with the bilinear kind.  A group is active when its
+// members run on k_tdb_mfma; its launches take at most `share_cap` members, the largest count whose scratch slot stays within
+// TDB_SHARE_SLOT_BYTES per resident workgroup (the slot is 4 np Ctot + np^2 + the U_q columns, tdb_mfma_group_scratch_doubles).
+constexpr size_t TDB_SHARE_SLOT_BYTES = (size_t)8 << 20;
+
+bool same_time_dependent_system(const dto_integrator_desc& a, const dto_integrator_desc& c) {
+    if (c.x_dim != a.x_dim || c.u_dim != a.u_dim || (a.u_dim > 0 && c.u_off != a.u_off) || c.t_off != a.t_off ||
+        c.spline_order != a.spline_order || c.substeps != a.substeps || c.n_mod != a.n_mod)
+        return false;
+    for (int m = 0; m < a.n_mod; ++m)
+        if (a.mod_kind[m] != c.mod_kind[m] || !(a.mod_omega[m] == c.mod_omega[m])) return false;
+    const size_t len = (size_t)(a.u_dim + 1) * a.x_dim * a.x_dim;
+    for (size_t e = 0; e < len; ++e)
+        if (!(a.G[e] == c.G[e])) return false;
+    for (size_t e = 0; e < len * (size_t)a.n_mod; ++e)
+        if (!(a.H[e] == c.H[e])) return false;
+    return true;
+}
+
+void find_time_dependent_share_groups(dto_handle* h, const dto_problem_desc* d) {
+    for (int i = 0; i < d->n_integrators; ++i)
+        if (h->integ_kind[i] == DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) h->tdb[h->integ_index[i]].list_pos = i;
+    if (!(d->flags & DTO_FLAG_SHARED_GENERATORS)) return;
+    for (int i = 0; i < d->n_integrators; ++i) {
+        if (h->integ_kind[i] != DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) continue;
+        const int ti = h->integ_index[i];
+        if (h->tdb[ti].share_leader >= 0) continue;  // a member of an earlier group
+        std::vector<int> members{ti};
+        for (int j = i + 1; j < d->n_integrators; ++j) {
+            if (h->integ_kind[j] != DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) continue;
+            const int tj = h->integ_index[j];
+            // (a structured member groups with its like only; the dense paths follow from x_dim)
+            if (h->tdb[tj].share_leader < 0 && h->tdb[tj].kron == h->tdb[ti].kron && same_time_dependent_system(d->integrators[i], d->integrators[j]))
+                members.push_back(tj);
+        }
+        if (members.size() < 2) continue;
+        const TdbHost& lead = h->tdb[ti];
+        int cap = 1;
+        if (lead.mfma && !lead.kron)
+            for (int g = 2; g <= std::min<int>((int)members.size(), TDB_SHARE_MAX); ++g) {
+                size_t slot = std::max(tdb_mfma_group_scratch_doubles(lead.k, 0, g), tdb_mfma_group_scratch_doubles(lead.k, 1, g));
+                if (d->eval_hessian) slot = std::max(slot, tdb_mfma_group_scratch_doubles(lead.k, 2, g));
+                if (slot * sizeof(double) > TDB_SHARE_SLOT_BYTES) break;
+                cap = g;
+            }
+        for (int mb : members) {
+            h->tdb[mb].share_leader = ti;
+            h->tdb[mb].share_size = (int)members.size();
+            h->tdb[mb].share_active = cap >= 2;
+            h->tdb[mb].share_cap = cap;
+        }
+        if (cap >= 2) h->tdb[ti].share_members = members;
+    }
+}
+
 double con_jac_value(const ConHost& c, const double* zk, int comp_i) {
     if (c.k.kind == DTO_CONSTRAINT_QUADFORM_MINUS_C) {  // 2 (M v)_c, summed over j ascending with an unfused multiply-add: the
         const size_t n = c.comps.size();                // arithmetic of the device's row walk (dto_quadform.hip, qf_row)
@@ -1008,6 +1064,12 @@ void alloc_tdb(dto_handle* h) {
             t.stride = scratch_stride(std::max({tdb_mfma_scratch_doubles(t.k, 1), tdb_mfma_scratch_doubles(t.k, 3), tdb_mfma_scratch_doubles(t.k, 4)}),
                                       tdb_mfma_scratch_doubles(t.k, 2), hess);
             t.d_scratch = own(h, dalloc<double>(t.stride * (size_t)t.resident));
+            if (!t.share_members.empty()) {   // leader of an active group: the slots of the group launches
+                const int g = t.share_cap;
+                t.share_stride = scratch_stride(std::max(tdb_mfma_group_scratch_doubles(t.k, 0, g), tdb_mfma_group_scratch_doubles(t.k, 1, g)),
+                                                tdb_mfma_group_scratch_doubles(t.k, 2, g), hess);
+                t.d_share_scratch = own(h, dalloc<double>(t.share_stride * (size_t)t.resident));
+            }
             continue;
         }
         t.stride = scratch_stride(std::max({tdb_scratch_doubles(t.k, 1), tdb_scratch_doubles(t.k, 3), tdb_scratch_doubles(t.k, 4)}),
@@ -1131,6 +1193,7 @@ extern "C" int dto_create(const dto_problem_desc* d, dto_handle** out) {
         set_dimensions(h.get(), d);
         add_integrators(h.get(), d);
         find_share_groups(h.get(), d);
+        find_time_dependent_share_groups(h.get(), d);
         if (h->integ_kind.size() > 8) throw HipError{"at most 8 integrators"};
         add_constraints(h.get(), d);
         add_external_objectives(h.get(), d);

@@ -762,6 +762,43 @@ void tdb_eval(dto_handle* h, TdbHost& t, const double* dZ, const double* dmu, in
     HIP_CHECK(launch_tdb(st, P, t.k, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch, t.stride));
 }
 
+// members per launch of an active time-dependent group: its cap from create, lowered by option "tdb_share_members"
+int tdb_share_cap(const dto_handle* h, const TdbHost& t) {
+    return h->tdb_share_members > 0 ? std::min(h->tdb_share_members, t.share_cap) : t.share_cap;
+}
+
+// Calls `f(first, count)` for the consecutive launches of an active group led by `lead`: `count` members from position `first` of
+// lead.share_members, at most the cap each.
+template <class F>
+void tdb_share_launches(const dto_handle* h, const TdbHost& lead, F&& f) {
+    const int cap = tdb_share_cap(h, lead), size = (int)lead.share_members.size();
+    for (int first = 0; first < size; first += cap) f(first, std::min(cap, size - first));
+}
+
+// The blocks of integrator `t` as tdb_eval leaves them, through its group where it has an active one (DTO_FLAG_SHARED_GENERATORS,
+// DESIGN 4.22): the group's launches run at the leader's turn -- the first member in list order, which every caller reaches first --
+// and write the blocks of all members; a follower's turn finds its blocks written.  A launch left with one member is the lone kernel.
+void tdb_eval_shared(dto_handle* h, TdbHost& t, const double* dZ, const double* dmu, int need, hipStream_t st) {
+    if (!t.share_active || tdb_share_cap(h, t) < 2) return tdb_eval(h, t, dZ, dmu, need, st);
+    TdbHost& lead = h->tdb[t.share_leader];
+    if (&t != &lead) return;
+    const KProb& P = h->P;
+    const int64_t lo = need == 0 ? P.kn_lo : std::max<int64_t>(0, P.kn_lo - 1);
+    const int64_t hi = need == 0 ? P.kn_lo + P.n_int : std::min<int64_t>(P.K, P.kn_lo + P.n_knots);
+    tdb_share_launches(h, lead, [&](int first, int count) {
+        if (count == 1) return tdb_eval(h, h->tdb[lead.share_members[first]], dZ, dmu, need, st);
+        KTdbGroup g{};
+        g.count = count;
+        for (int i = 0; i < count; ++i) {
+            const TdbHost& mb = h->tdb[lead.share_members[first + i]];
+            g.m[i] = KTdbMember{mb.k.x_off, mb.k.row_off, mb.d_vals, mb.d_jac, mb.d_hess};
+        }
+        ProfScope ps(h, st, CAT_TDB_MFMA, tdb_mfma_group_flops(lead.k, need, count) * (double)std::max<int64_t>(hi - lo, 0));
+        HIP_CHECK(launch_tdb_mfma_group(st, P, lead.k, g, lead.d_Bp, lead.d_BpT, dZ, dmu, need, lo, hi - lo, lead.d_share_scratch,
+                                        lead.share_stride, lead.resident));
+    });
+}
+
 // Matrix-free products of a dense device time-dependent integrator (option "tdb_matrix_free_products"): its rows of J w, or its
 // part of J' w added into the zero-filled dy -- staged per interval, then placed by one thread per entry.  No block, no slab.
 void tdb_product(dto_handle* h, TdbHost& t, const double* dZ, const double* dw, double* dy, int transpose, hipStream_t st) {
@@ -874,7 +911,7 @@ void do_constraint(dto_handle* h, const double* dZ, double* dg, hipStream_t st) 
     for (size_t i = 0; i < h->ext_int.size(); ++i)
         if (h->P.n_int > 0) launch_extint_cons(st, h->P, h->ext_int[i], ext_upload(h, (int)i, 0, st), dg);
     for (auto& t : h->tdb)
-        if (h->P.n_int > 0) { tdb_eval(h, t, dZ, nullptr, 0, st); launch_extint_cons(st, h->P, t.place, t.d_vals, dg); }
+        if (h->P.n_int > 0) { tdb_eval_shared(h, t, dZ, nullptr, 0, st); launch_extint_cons(st, h->P, t.place, t.d_vals, dg); }
     for (auto& c : h->con) {
         if (!c.external) launch_cons_knot(st, h->P, c.k, dZ, dg);
         else if (c.k.n_times > 0) launch_ext_cons(st, c.k, ext_upload(h, c.ext_slot, 0, st), dg);
@@ -1058,7 +1095,7 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
     for (auto& d : h->der) launch_jac_derivative(st, h->P, d, dZ, dvals);
     for (size_t i = 0; i < h->ext_int.size(); ++i)
         launch_extint_jac(st, h->P, h->ext_int[i], ext_upload(h, (int)i, 1, st), dvals);
-    for (auto& t : h->tdb) { tdb_eval(h, t, dZ, nullptr, 1, st); launch_extint_jac(st, h->P, t.place, t.d_jac, dvals); }
+    for (auto& t : h->tdb) { tdb_eval_shared(h, t, dZ, nullptr, 1, st); launch_extint_jac(st, h->P, t.place, t.d_jac, dvals); }
     for (auto& c : h->con) {
         if (!c.external) launch_jac_knot(st, h->P, c.k, dZ, dvals);
         else if (c.k.n_times > 0) launch_ext_jac(st, c.k, ext_upload(h, c.ext_slot, 1, st), dvals);
@@ -1207,7 +1244,7 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
         } else if (h->integ_kind[i] == DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) {
             need_zero();
             TdbHost& t = h->tdb[h->integ_index[i]];
-            tdb_eval(h, t, dZ, dmu, 2, st);
+            tdb_eval_shared(h, t, dZ, dmu, 2, st);
             launch_extint_hess(st, h->P, t.place, t.d_hess, dH);
         } else {  // the caller's blocks already carry mu_k (eval_hessian_of_lagrangian(integrator, traj, mu_slice))
             need_zero();
@@ -1871,10 +1908,15 @@ int dto_interval_costs(const dto_handle* h, const double* Z, int64_t first, int6
         }
     }
     // time-dependent bilinear integrators of 65..256 states: the flops of one Jacobian call of k_tdb_mfma (fixed steps: the same
-    // for every interval)
+    // for every interval); an active group by the flops of its launches, counted at its leader
     for (const TdbHost& t : h->tdb)
         if (t.kron || t.mfma) {   // (the structured path by its own flops)
-            const double c = t.kron ? tdb_kron_flops(t.k, t.kk, 1) : tdb_mfma_flops(t.k, 1);
+            double c = t.kron ? tdb_kron_flops(t.k, t.kk, 1) : tdb_mfma_flops(t.k, 1);
+            if (t.share_active && tdb_share_cap(h, t) >= 2) {
+                c = 0.0;
+                if (!t.share_members.empty())
+                    tdb_share_launches(h, t, [&](int, int n) { c += n == 1 ? tdb_mfma_flops(t.k, 1) : tdb_mfma_group_flops(t.k, 1, n); });
+            }
             for (int64_t i = 0; i < count; ++i) cost[i] += c;
         }
     // every other term kind costs O(z) per knot: a constant that keeps intervals without a bilinear integrator from counting as free
@@ -1905,6 +1947,10 @@ int dto_integrator_share(const dto_handle* h, int32_t integrator, int32_t* leade
     if (h->integ_kind[integrator] == DTO_INTEGRATOR_BILINEAR) {
         const BilHost& b = h->bil[h->integ_index[integrator]];
         if (b.share_leader >= 0) { lead = h->bil[b.share_leader].list_pos; size = b.share_size; on = b.share_active ? 1 : 0; }
+    }
+    if (h->integ_kind[integrator] == DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) {
+        const TdbHost& t = h->tdb[h->integ_index[integrator]];
+        if (t.share_leader >= 0) { lead = h->tdb[t.share_leader].list_pos; size = t.share_size; on = t.share_active ? 1 : 0; }
     }
     if (leader) *leader = lead;
     if (group_size) *group_size = size;
@@ -2436,6 +2482,15 @@ int dto_set_option(dto_handle* h, const char* name, int64_t value) {
         if (value != 0 && value != 1)
             return fail(h, "dto_set_option: tdb_matrix_free_products takes 0 (J w / J' w of time-dependent integrators through the value slab) or 1 (matrix-free)");
         h->tdb_matrix_free_products = (int)value;
+        return 0;
+    }
+    if (std::string(name) == "tdb_share_members") {
+        int cap = 1;
+        for (const TdbHost& t : h->tdb) cap = std::max(cap, t.share_active ? t.share_cap : 1);
+        if (value < 1 || value > cap)
+            return fail(h, "dto_set_option: tdb_share_members takes 1 (one launch per member) .. " + std::to_string(cap) +
+                               ", the largest group launch this handle was created for");
+        h->tdb_share_members = (int)value;
         return 0;
     }
     if (std::string(name) == "expm_form") {

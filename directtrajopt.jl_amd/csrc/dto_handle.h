@@ -163,6 +163,15 @@ struct TdbHost {
     int kb = 0, kr = 1;
     bool kron = false;
     KKron kk{};
+    // DTO_FLAG_SHARED_GENERATORS: the group of time-dependent integrators of one system (indices into dto_handle::tdb; the leader is
+    // the first member in list order, -1: no partner).  ACTIVE groups (k_tdb_mfma members, two or more) are evaluated by the group
+    // form of the kernel, at most `share_cap` members per launch.  Leader only: `share_members` (all of them, itself first) and the
+    // group launches' scratch, `resident` slots of `share_stride` doubles.  `list_pos`: position in the integrator list.
+    int share_leader = -1, share_size = 1, share_cap = 1, list_pos = 0;
+    bool share_active = false;
+    std::vector<int> share_members;
+    double* d_share_scratch = nullptr;
+    size_t share_stride = 0;
 };
 
 struct ProfRec {
@@ -294,6 +303,7 @@ struct dto_handle {
     int chain_form = 0;   // option "chain_form": 0 = the one-launch chain of 33..64-state integrators where it applies, 1 = batched-GEMM launches only
     int n_cu = 256;
     int chain_chunk = 0;  // option "chain_chunk": upper bound on the intervals per chain chunk (0: workspace capacity)
+    int tdb_share_members = 0;  // option of that name: members per group launch of k_tdb_mfma (0: each group's cap from create)
     int tdb_matrix_free_products = 0;  // option of that name: J w / J' w of dense device time-dependent integrators without a slab
     int deterministic = 0;  // option "deterministic": results independent of overlap_sweep and of the entry-point family
     // deferred errors of the `*_dev` entry points (dto_engine.h, error convention): the sweep statistics of the last

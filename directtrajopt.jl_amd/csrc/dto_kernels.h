@@ -389,6 +389,26 @@ hipError_t launch_tdb_mfma(hipStream_t st, const KProb& P, const KTdb& T, const 
 hipError_t launch_tdb_mfma_product(hipStream_t st, const KProb& P, const KTdb& T, const double* Bp, const double* BpT, const double* dZ,
                                    const double* dw, int need, double* out, double* scratch, size_t scratch_stride, int resident);
 
+// The group form of k_tdb_mfma (DTO_FLAG_SHARED_GENERATORS on time-dependent integrators): `G.count` members (2 .. TDB_SHARE_MAX)
+// that differ in their state component and rows only, evaluated by ONE launch that forms every M0, coefficient table and (Jacobian)
+// the Phi block once.  T is the leader's description; each member's blocks go to its own vals / jac / hess, bit for bit what
+// launch_tdb_mfma writes for it.  need 0 .. 2; the scratch slot is tdb_mfma_group_scratch_doubles, the flops are as executed.
+constexpr int TDB_SHARE_MAX = 8;
+struct KTdbMember {
+    int32_t x_off;
+    int64_t row_off;
+    double *vals, *jac, *hess;
+};
+struct KTdbGroup {
+    int32_t count;
+    KTdbMember m[TDB_SHARE_MAX];
+};
+size_t tdb_mfma_group_scratch_doubles(const KTdb& T, int need, int members);
+double tdb_mfma_group_flops(const KTdb& T, int need, int members);
+hipError_t launch_tdb_mfma_group(hipStream_t st, const KProb& P, const KTdb& T, const KTdbGroup& G, const double* Bp, const double* BpT,
+                                 const double* dZ, const double* dmu, int need, int64_t i_lo, int64_t count, double* scratch,
+                                 size_t scratch_stride, int resident);
+
 // BilinearIntegrator with replicated-block generators G_j = I_r (x) B_j (dto_kron.hip): one workgroup per interval sweeps b-row
 // column groups against the b x b blocks and writes defect, Jacobian block or Hessian block of mu_k' f straight to their positions
 struct KKron {

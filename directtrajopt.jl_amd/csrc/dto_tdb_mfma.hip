@@ -22,6 +22,9 @@
 //   * PERSISTENT GRID.  `resident` workgroups walk the intervals (interval i of the launch goes to workgroup i mod resident); the
 //     scratch is one slot per workgroup, so it is sized by the grid and not by the number of intervals.
 //
+//   * GROUPS.  Integrators of one system (DTO_FLAG_SHARED_GENERATORS) go through k_tdb_mfma_group further down: the same scheme with
+//     the members' vector blocks side by side and everything that does not depend on the ket formed once.
+//
 // Numerical rules: what a workgroup computes is a function of its interval's data alone (not of the grid, the shard or the slot);
 // every sum has a fixed order; there is no floating-point atomic.  Output entries that share a position (a component that serves
 // twice, e.g. the timestep listed as the time variable) are added by one thread in a fixed order.  Padded rows and columns are
@@ -382,6 +385,317 @@ __global__ void __launch_bounds__(256, 2) k_tdb_mfma(TdbmArgs a) {
     }
 }
 
+
+// ---- the group form (DTO_FLAG_SHARED_GENERATORS): `Pm` integrators of one system -- equal B_q, controls, time and
+// scheme, each with its own state component and rows -- in ONE launch.  Everything that does not depend on the ket is done once per
+// stage time or stage: the coefficient table, M0 / M0', and in a Jacobian call the Phi block.  Columns of one call:
+//         defect    x^1 .. x^Pm | zeros to 32
+//         Jacobian  [x^i, x^i_b (p)] member after member | zeros to a multiple of 32 | Phi (np columns, one for the group)
+//         Hessian   [x^i, x^i_b, x^i_ab | zeros to a multiple of 32] member after member; the adjoint: one 32-column tile
+//                   [lambda^i, lambda^i_b] per member, from that member's mu rows
+// A member's columns go through the arithmetic they have in k_tdb_mfma: a GEMM column is a chain of MFMAs over k that does not
+// depend on its neighbours or on the tile it sits in, the epilogues and the vector pass keep their expressions and sum orders.  So a
+// member's output has the bits of the lone kernel's, whatever the group, the member's position, the grid or the slot.
+struct TdbgLayout {
+    int np, p, P2, Q, C1, cstride, Cv, Ctot, ustep, ucols;
+    size_t oY, oACC, oTA, oTB, oM0, oU, oUB, oCoef, total;
+};
+inline __host__ __device__ TdbgLayout tdbg_layout(const KTdb& T, int need, int Pm) {
+    TdbgLayout L;
+    L.np = pad32(T.n);
+    L.p = tdb_num_params(T.m, T.order);
+    L.P2 = tdb_num_pairs(L.p);
+    L.Q = tdb_num_shared(T.m, T.nmod);
+    L.C1 = need == 0 ? 1 : (need == 1 ? 1 + L.p : 1 + L.p + L.P2);   // meaningful columns of one member
+    L.cstride = need == 2 ? pad32(L.C1) : L.C1;                       // columns from one member to the next
+    L.Cv = pad32(Pm * L.cstride);
+    L.Ctot = L.Cv + (need == 1 ? L.np : 0);
+    L.ustep = need == 2 ? TDBM_VEC : 1;                               // U columns of one member and q
+    L.ucols = Pm * L.ustep;
+    const size_t cols = (size_t)L.np * L.Ctot;
+    L.oY = 0; L.oACC = cols; L.oTA = 2 * cols; L.oTB = 3 * cols;
+    L.oM0 = 4 * cols;
+    L.oU = L.oM0 + (size_t)L.np * L.np;
+    L.oUB = L.oU + (size_t)L.Q * L.ucols * L.np;
+    L.oCoef = L.oUB + (need == 2 ? (size_t)L.np * TDBM_VEC * Pm : 0);
+    L.total = L.oCoef + (size_t)(1 + L.p + L.P2) * L.Q;
+    L.total = (L.total + 1) & ~(size_t)1;
+    return L;
+}
+
+struct TdbgArgs {
+    KProb P;
+    KTdb T;           // the leader's: everything but x_off and row_off is the group's
+    KTdbGroup G;
+    const double* Bp;
+    const double* BpT;
+    const double* Z;
+    const double* mu;
+    int need;
+    int64_t i_lo, count;
+    double* scratch;
+    int64_t scratch_stride;
+};
+
+template <int TM>
+__global__ void __launch_bounds__(256, 2) k_tdb_mfma_group(TdbgArgs a) {
+    const int n = a.T.n, z = a.P.z, need = a.need, Pm = a.G.count;
+    const TdbgLayout L = tdbg_layout(a.T, need, Pm);
+    const int np = L.np, p = L.p, P2 = L.P2, Q = L.Q, C1 = L.C1, cstride = L.cstride, Ctot = L.Ctot, ustep = L.ustep, ucols = L.ucols;
+    const int tid = threadIdx.x;
+    const size_t nn = (size_t)np * np;
+    __shared__ __attribute__((aligned(16))) double smem[GemmShape<TM, 64, 2, 2>::SMEM_DOUBLES];
+    __shared__ double vsh[TDB_SHARE_MAX * 256];                // the members' vectors of a vector pass
+    __shared__ unsigned char pair_a[TDBM_MAX_PAIRS], pair_b[TDBM_MAX_PAIRS];
+    for (int e = tid; e < P2; e += 256) {
+        int aa, bb;
+        tdb_pair_unrank(e, p, &aa, &bb);
+        pair_a[e] = (unsigned char)aa; pair_b[e] = (unsigned char)bb;
+    }
+    double* S = a.scratch + (int64_t)blockIdx.x * a.scratch_stride;
+    double* Y = S + L.oY;
+    double* ACC = S + L.oACC;
+    double* TA = S + L.oTA;
+    double* TB = S + L.oTB;
+    double* M0 = S + L.oM0;
+    double* U = S + L.oU;         // [Q][Pm][ustep][np]
+    double* UB = S + L.oUB;       // [Pm][32][np] (Hessian calls)
+    double* coefs = S + L.oCoef;  // [jets][Q]
+    __syncthreads();
+
+    for (int64_t it = blockIdx.x; it < a.count; it += gridDim.x) {
+        const int64_t kn = a.i_lo + it;
+        const double* zk = a.Z + kn * z;
+        const double* zk1 = zk + z;
+        const double tk = zk[a.T.t_off], dt = zk[a.P.dt_idx];
+
+        // as in k_tdb_mfma, once for the group
+        auto form_m0 = [&](double tau, int njet, const double* __restrict__ B) {
+            for (int e = tid; e < njet * Q; e += 256) coefs[e] = tdbm_coef(a.T, zk, zk1, tk, dt, tau, p, e / Q, e % Q);
+            __syncthreads();
+            for (size_t e = 2 * (size_t)tid; e < nn; e += 512) {
+                d2 acc = d2{0.0, 0.0};
+                for (int q = 0; q < Q; ++q) {
+                    const double cf = coefs[q];
+                    const d2 b = *reinterpret_cast<const d2*>(B + q * nn + e);
+                    acc.x += cf * b.x; acc.y += cf * b.y;
+                }
+                *reinterpret_cast<d2*>(M0 + e) = acc;
+            }
+            __syncthreads();
+        };
+        // U[q][i][0][:] = B_q v^i for the members' vectors v^i = v + i vstride: thread per (q, row), every B_q entry read once and
+        // used for all members; per vector the four partial sums over k mod 4 of k_tdb_mfma's pass, joined in its order
+        auto vec_pass = [&](const double* __restrict__ B, const double* __restrict__ v, size_t vstride) {
+            for (int i = 0; i < Pm; ++i)
+                for (int r = tid; r < np; r += 256) vsh[i * 256 + r] = v[i * vstride + r];
+            __syncthreads();
+            for (int e = tid; e < Q * np; e += 256) {
+                const int q = e / np, r = e - q * np;
+                const double* col = B + q * nn + r;
+                double s0[TDB_SHARE_MAX], s1[TDB_SHARE_MAX], s2[TDB_SHARE_MAX], s3[TDB_SHARE_MAX];
+#pragma unroll
+                for (int i = 0; i < TDB_SHARE_MAX; ++i) s0[i] = s1[i] = s2[i] = s3[i] = 0.0;
+                for (int k = 0; k < np; k += 4) {
+                    const double b0 = col[(size_t)k * np], b1 = col[(size_t)(k + 1) * np], b2 = col[(size_t)(k + 2) * np],
+                                 b3 = col[(size_t)(k + 3) * np];
+#pragma unroll
+                    for (int i = 0; i < TDB_SHARE_MAX; ++i)
+                        if (i < Pm) {
+                            const double* vv = vsh + i * 256 + k;
+                            s0[i] += b0 * vv[0];
+                            s1[i] += b1 * vv[1];
+                            s2[i] += b2 * vv[2];
+                            s3[i] += b3 * vv[3];
+                        }
+                }
+#pragma unroll
+                for (int i = 0; i < TDB_SHARE_MAX; ++i)
+                    if (i < Pm) U[((size_t)q * ucols + (size_t)i * ustep) * np + r] = (s0[i] + s1[i]) + (s2[i] + s3[i]);
+            }
+            __syncthreads();
+        };
+
+        // initial values: x^i = x^i_k, Phi = I, everything else (padding included) 0
+        for (size_t e = tid; e < (size_t)np * Ctot; e += 256) {
+            const int c = (int)(e / np), r = (int)(e - (size_t)c * np);
+            Y[e] = (c >= L.Cv && c - L.Cv == r && r < n) ? 1.0 : 0.0;
+        }
+        __syncthreads();
+        for (int i = 0; i < Pm; ++i)
+            for (int r = tid; r < n; r += 256) Y[(size_t)i * cstride * np + r] = zk[a.G.m[i].x_off + r];
+        __syncthreads();
+
+        const double h = 1.0 / a.T.substeps;
+        const int njet_fwd = need == 0 ? 1 : (need == 1 ? 1 + p : 1 + p + P2);
+        for (int step = 0; step < a.T.substeps; ++step) {
+            for (int stage = 0; stage < 4; ++stage) {
+                const TdbFwdStage sg = tdb_fwd_stage(step, stage, h);
+                const double* IN = tdb_fwd_in(stage, Y, TA, TB);
+                double* OUT = tdb_fwd_out(stage, Y, TA, TB);
+                if (tdb_fwd_new_jets(stage)) form_m0(sg.tau, njet_fwd, a.Bp);
+                // U_q = B_q y for the vectors whose jets enter this call: x^i (Jacobian), x^i and x^i_b (Hessian)
+                if (need == 1) vec_pass(a.Bp, IN, (size_t)cstride * np);
+                else if (need == 2) {
+                    for (int q = 0; q < Q; ++q)
+                        for (int i = 0; i < Pm; ++i)
+                            mm_cols<TM>(a.Bp + q * nn, IN + (size_t)i * cstride * np, np, TDBM_VEC, smem, [&](int row, int col, double v) {
+                                U[((size_t)q * ucols + (size_t)i * TDBM_VEC + col) * np + row] = v;
+                            });
+                    __syncthreads();
+                }
+                // K = M0 IN (+ the jets' terms of the column's member), then the RK4 update of this stage
+                mm_cols<TM>(M0, IN, np, Ctot, smem, [&](int row, int col, double K) {
+                    if (need >= 1 && col < Pm * cstride) {
+                        const int i = col / cstride, lc = col - i * cstride;   // member, and the column inside its block
+                        const double* ui = U + (size_t)i * ustep * np + row;
+                        if (lc >= 1 && lc <= p) {
+                            const double* cf = coefs + (size_t)lc * Q;   // jet 1 + b, b = lc - 1
+                            double s = 0.0;
+                            for (int q = 0; q < Q; ++q) s += cf[q] * ui[(size_t)q * ucols * np];
+                            K += s;
+                        } else if (need == 2 && lc > p && lc < C1) {
+                            const int e = lc - 1 - p, aa = pair_a[e], bb = pair_b[e];
+                            const double *ca = coefs + (size_t)(1 + aa) * Q, *cb = coefs + (size_t)(1 + bb) * Q, *cab = coefs + (size_t)(1 + p + e) * Q;
+                            double s = 0.0;
+                            for (int q = 0; q < Q; ++q) {
+                                const double* uq = ui + (size_t)q * ucols * np;
+                                s += ca[q] * uq[(size_t)(1 + bb) * np] + cb[q] * uq[(size_t)(1 + aa) * np] + cab[q] * uq[0];
+                            }
+                            K += s;
+                        }
+                    }
+                    const size_t e = (size_t)col * np + row;
+                    const double y0 = Y[e];
+                    if (stage == 0) { ACC[e] = y0 + sg.w_acc * K; OUT[e] = y0 + sg.w_tmp * K; }
+                    else if (stage < 3) { ACC[e] += sg.w_acc * K; OUT[e] = y0 + sg.w_tmp * K; }
+                    else OUT[e] = ACC[e] + sg.w_acc * K;
+                });
+                __syncthreads();
+            }
+        }
+
+        // ---- outputs: every member's own blocks, laid out as k_tdb_mfma writes them
+        for (int i = 0; i < Pm; ++i) {
+            const int xo = a.G.m[i].x_off;
+            const double* yi = Y + (size_t)i * cstride * np;
+            for (int r = tid; r < n; r += 256) a.G.m[i].vals[kn * n + r] = zk1[xo + r] - yi[r];
+        }
+        auto zz_of = [&](int b) { return tdb_param_entry(a.T, z, a.P.dt_idx, b); };
+        if (need == 1) {
+            for (int i = 0; i < Pm; ++i) {
+                double* J = a.G.m[i].jac + kn * (int64_t)n * 2 * z;
+                for (int64_t e = tid; e < (int64_t)n * 2 * z; e += 256) J[e] = 0.0;
+            }
+            __syncthreads();
+            const double* PHI = Y + (size_t)L.Cv * np;
+            for (int i = 0; i < Pm; ++i) {   // -Phi to every member, the identity at its own z_{k+1} columns
+                const int xo = a.G.m[i].x_off;
+                double* J = a.G.m[i].jac + kn * (int64_t)n * 2 * z;
+                for (int e = tid; e < n * n; e += 256) {
+                    const int c = e / n, r = e - c * n;
+                    J[(int64_t)(xo + c) * n + r] = -PHI[(size_t)c * np + r];
+                }
+                for (int r = tid; r < n; r += 256) J[(int64_t)(z + xo + r) * n + r] = 1.0;
+            }
+            __syncthreads();
+            // parameter columns ADD (a component may serve twice); row r belongs to one thread, b in order
+            for (int i = 0; i < Pm; ++i) {
+                double* J = a.G.m[i].jac + kn * (int64_t)n * 2 * z;
+                const double* yi = Y + (size_t)i * cstride * np;
+                for (int r = tid; r < n; r += 256)
+                    for (int b = 0; b < p; ++b) J[(int64_t)zz_of(b) * n + r] -= yi[(size_t)(1 + b) * np + r];
+            }
+        } else if (need == 2) {
+            // the discrete adjoint of k_tdb_mfma, one 32-column tile [lambda^i, lambda^i_b] per member; Y keeps x^i_ab
+            double* W = TA;
+            double* WN = TB;
+            double* KB = ACC;
+            const int CA = 1 + p, nv = np * TDBM_VEC, nvg = nv * Pm;
+            for (int e = tid; e < nvg; e += 256) { W[e] = 0.0; UB[e] = 0.0; }
+            __syncthreads();
+            for (int i = 0; i < Pm; ++i) {
+                const double* muk = a.mu + a.G.m[i].row_off + kn * n;
+                for (int r = tid; r < n; r += 256) W[(size_t)i * nv + r] = muk[r];
+            }
+            __syncthreads();
+            for (int step = a.T.substeps - 1; step >= 0; --step) {
+                for (int e = tid; e < nvg; e += 256) WN[e] = W[e];
+                for (int stage = 3; stage >= 0; --stage) {
+                    const TdbBwdStage sg = tdb_bwd_stage(step, stage, h);
+                    if (tdb_bwd_new_jets(stage)) form_m0(sg.tau, CA, a.BpT);
+                    const double cw = sg.cw, cu = sg.cu;
+                    for (int e = tid; e < nvg; e += 256) KB[e] = cw * W[e] + (cu != 0.0 ? cu * UB[e] : 0.0);
+                    __syncthreads();
+                    vec_pass(a.BpT, KB, (size_t)nv);   // U_q = B_q' kbar^i_0 (column 0 of each member and q)
+                    // ubar_c = M0' kbar_c (+ M_b' kbar_0 of the column's member for the sensitivity columns)
+                    mm_cols<TM>(M0, KB, np, TDBM_VEC * Pm, smem, [&](int row, int col, double u) {
+                        const int i = col / TDBM_VEC, lc = col - i * TDBM_VEC;
+                        if (lc >= 1 && lc <= p) {
+                            const double* cf = coefs + (size_t)lc * Q;
+                            const double* ui = U + (size_t)i * ustep * np + row;
+                            double s = 0.0;
+                            for (int q = 0; q < Q; ++q) s += cf[q] * ui[(size_t)q * ucols * np];
+                            u += s;
+                        }
+                        const size_t e = (size_t)col * np + row;
+                        UB[e] = u;
+                        WN[e] += u;
+                    });
+                    __syncthreads();
+                }
+                for (int e = tid; e < nvg; e += 256) W[e] = WN[e];
+                __syncthreads();
+            }
+
+            const int ld = 2 * z;
+            for (int i = 0; i < Pm; ++i) {
+                double* Hb = a.G.m[i].hess + kn * (int64_t)4 * z * z;
+                for (int64_t e = tid; e < (int64_t)4 * z * z; e += 256) Hb[e] = 0.0;
+            }
+            __syncthreads();
+            // (x_i, theta_b) = -d lambda_i / d theta_b: thread r owns row x_r in the first pass and column x_r in the second, b in order
+            for (int i = 0; i < Pm; ++i) {
+                const int xo = a.G.m[i].x_off;
+                double* Hb = a.G.m[i].hess + kn * (int64_t)4 * z * z;
+                const double* Wi = W + (size_t)i * nv;
+                for (int r = tid; r < n; r += 256)
+                    for (int b = 0; b < p; ++b) Hb[(xo + r) + (int64_t)ld * zz_of(b)] -= Wi[(size_t)(1 + b) * np + r];
+            }
+            __syncthreads();
+            for (int i = 0; i < Pm; ++i) {
+                const int xo = a.G.m[i].x_off;
+                double* Hb = a.G.m[i].hess + kn * (int64_t)4 * z * z;
+                const double* Wi = W + (size_t)i * nv;
+                for (int r = tid; r < n; r += 256)
+                    for (int b = 0; b < p; ++b) Hb[zz_of(b) + (int64_t)ld * (xo + r)] -= Wi[(size_t)(1 + b) * np + r];
+            }
+            __syncthreads();
+            // (theta_a, theta_b) = -mu' x_ab: the dot products in parallel (into UB), then one thread per member adds them in order
+            for (int i = 0; i < Pm; ++i) {
+                const double* muk = a.mu + a.G.m[i].row_off + kn * n;
+                for (int e = tid; e < P2; e += 256) {
+                    double s = 0.0;
+                    const double* xab = Y + ((size_t)i * cstride + 1 + p + e) * np;
+                    for (int r = 0; r < n; ++r) s += muk[r] * xab[r];
+                    UB[(size_t)i * nv + e] = s;
+                }
+            }
+            __syncthreads();
+            if (tid < Pm) {
+                double* Hb = a.G.m[tid].hess + kn * (int64_t)4 * z * z;
+                const double* dots = UB + (size_t)tid * nv;
+                for (int e = 0; e < P2; ++e) {
+                    const int ra = zz_of(pair_a[e]), rb = zz_of(pair_b[e]);
+                    Hb[ra + (int64_t)ld * rb] -= dots[e];
+                    if (pair_a[e] != pair_b[e]) Hb[rb + (int64_t)ld * ra] -= dots[e];
+                }
+            }
+        }
+        __syncthreads();   // the slot is reused by this workgroup's next interval
+    }
+}
+
 }  // namespace
 
 int tdb_mfma_npad(int n) { return pad32(n); }
@@ -438,6 +752,36 @@ hipError_t launch_tdb_mfma_product(hipStream_t st, const KProb& P, const KTdb& T
     const unsigned grid = (unsigned)std::min<int64_t>(P.K, resident);
     if (pad32(T.n) % 64 == 0) hipLaunchKernelGGL((k_tdb_mfma<64, true>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_tdb_mfma<32, true>), dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+size_t tdb_mfma_group_scratch_doubles(const KTdb& T, int need, int members) { return tdbg_layout(T, need, members).total; }
+
+// as tdb_mfma_flops, for one interval of a group launch: M0 and (Jacobian) the Phi block once, the vector blocks of all members
+double tdb_mfma_group_flops(const KTdb& T, int need, int members) {
+    const TdbgLayout L = tdbg_layout(T, need, members);
+    const double np2 = (double)L.np * L.np, S = T.substeps;
+    const double form = 2.0 * L.Q * np2;
+    double fwd = 4.0 * 2.0 * np2 * L.Ctot + 3.0 * form;
+    if (need == 1) fwd += 4.0 * 2.0 * L.Q * np2 * members;
+    if (need == 2) fwd += 4.0 * 2.0 * L.Q * np2 * TDBM_VEC * members;
+    double bwd = 0.0;
+    if (need == 2) bwd = 4.0 * (2.0 * np2 * TDBM_VEC * members + 2.0 * L.Q * np2 * members) + 3.0 * form;
+    return S * (fwd + bwd);
+}
+
+hipError_t launch_tdb_mfma_group(hipStream_t st, const KProb& P, const KTdb& T, const KTdbGroup& G, const double* Bp, const double* BpT,
+                                 const double* dZ, const double* dmu, int need, int64_t i_lo, int64_t count, double* scratch,
+                                 size_t scratch_stride, int resident) {
+    if (count <= 0) return hipSuccess;
+    if (need < 0 || need > 2 || G.count < 2 || G.count > TDB_SHARE_MAX || resident < 1 || tdbg_layout(T, need, G.count).total > scratch_stride)
+        return hipErrorInvalidValue;
+    TdbgArgs a{};
+    a.P = P; a.T = T; a.G = G; a.Bp = Bp; a.BpT = BpT; a.Z = dZ; a.mu = dmu; a.need = need; a.i_lo = i_lo; a.count = count;
+    a.scratch = scratch; a.scratch_stride = (int64_t)scratch_stride;
+    const unsigned grid = (unsigned)std::min<int64_t>(count, resident);
+    if (pad32(T.n) % 64 == 0) hipLaunchKernelGGL((k_tdb_mfma_group<64>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_tdb_mfma_group<32>), dim3(grid), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

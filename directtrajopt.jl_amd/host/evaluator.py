@@ -62,7 +62,14 @@ class Evaluator:
 
     Extra keyword arguments select the device and, for multi-GPU runs, the owned knot range
     ``k_lo..k_hi`` (1-based, inclusive).  Inputs ``Z`` and ``mu`` are always the GLOBAL vectors;
-    value outputs are the shard-local slabs described by ``shard`` (whole vectors when unsharded)."""
+    value outputs are the shard-local slabs described by ``shard`` (whole vectors when unsharded).
+
+    ``shared_generators=True`` (DTO_FLAG_SHARED_GENERATORS) groups integrators driven by one system -- the kets of a multi-state
+    problem.  BilinearIntegrators with equal generators and controls share the Jacobian's propagator chain (33 states and up).
+    Device TimeDependentBilinearIntegrators with the same family (every G_j and H_cj, modulation kinds and frequencies), controls,
+    time component, spline order and sub-steps share one propagation per eval_constraint, Jacobian and Hessian call at 65..256
+    states: one launch per group instead of one per integrator.  Values are bit-identical to the unflagged handle's either way;
+    ``integrator_share`` tells what was found."""
 
     # options applied to every new handle (dto_set_option name -> value); the repository's tests switch "host_xfer_check" on here
     default_options = {}
@@ -251,8 +258,10 @@ class Evaluator:
 
     def integrator_share(self, i):
         """(leader, group_size, active) of integrator i (0-based): the group of bilinear integrators with the same generators and
-        controls found at create with ``shared_generators=True``, its first member in list order, and whether the group shares
-        one propagator chain in eval_constraint_jacobian; (i, 1, 0) otherwise."""
+        controls -- or of time-dependent bilinear integrators with the same family, controls, time component and scheme -- found at
+        create with ``shared_generators=True``, its first member in list order, and whether the group shares: one propagator chain
+        in eval_constraint_jacobian (bilinear), one propagation per callback (time-dependent, 65..256 states on the dense path);
+        (i, 1, 0) otherwise.  The two kinds are never grouped with each other."""
         l, n, a = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._lib.dto_integrator_share(self._h, int(i), C.byref(l), C.byref(n), C.byref(a)))
         return l.value, n.value, a.value
@@ -492,7 +501,8 @@ class Evaluator:
         """dto_set_option: ``reuse_forward_sweep`` (solver loops evaluate g, J, H at the same point), ``expm_form``
         (0 = by cost, 2 / 3 = two- / three-product form of the Jacobian's matrix exponential), ``tdb_matrix_free_products`` (0 | 1,
         default 0: 1 evaluates J w / J' w of dense device TimeDependentBilinearIntegrators without forming a Jacobian -- the scheme
-        applied to two vectors, or to 1 + p forward vectors and one adjoint vector); include/dto_engine.h lists every option."""
+        applied to two vectors, or to 1 + p forward vectors and one adjoint vector), ``tdb_share_members`` (members per launch of a
+        shared group of time-dependent integrators, 1 = one launch per member); include/dto_engine.h lists every option."""
         self._check(self._lib.dto_set_option(self._h, name.encode(), int(value)))
 
     # ---- measurement

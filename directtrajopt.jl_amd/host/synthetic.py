@@ -194,3 +194,36 @@ def multi_ket_problem(n, kets, drives, N, seed=42, dt=0.1, u_bound=None, extra_k
     if u_bound is not None:
         cons.append(NonlinearKnotPointConstraint("sqnorm", "u", traj, c=float(u_bound), equality=False, times=range(2, N)))
     return DirectTrajOptProblem(traj, J, integrators, constraints=cons)
+
+
+def multi_ket_modulated_problem(n, kets, drives, N, order=1, substeps=16, n_mods=2, seed=42, dt=0.1, derivative_between=False):
+    """``multi_ket_problem`` in the lab frame: ``kets`` states driven by ONE time-dependent system.  Components psi1..psiP (n
+    each), u (drives), du, t, dt; skew-symmetric drift and drive generators G_j (scaled as ``multi_ket_problem``'s) and ``n_mods``
+    carrier terms (cos 1.7 t, sin 0.6 t) H_cj of the same shape at half the scale, shared by P TimeDependentBilinearIntegrators of
+    spline order ``order`` with ``substeps`` RK4 steps -- what ``Evaluator(..., shared_generators=True)`` groups and, at 65..256
+    states, evaluates with one propagation per group -- plus DerivativeIntegrator(u, du); QuadraticRegularizers on u and du and a
+    terminal ||psi_i - goal_i||^2 per ket.  ``derivative_between``: the derivative integrator sits between the first ket's
+    integrator and the others in the list instead of at its end."""
+    rng = np.random.Generator(np.random.Philox(seed))
+    def generators(scale):
+        M = rng.standard_normal((drives + 1, n, n))
+        return (M - M.transpose(0, 2, 1)) * (scale / np.sqrt(2.0 * n))
+    G = generators(1.0)
+    mods = [("cos", 1.7, generators(0.5)), ("sin", 0.6, generators(0.5))][:n_mods]
+    comps = {"u": 0.1 * rng.standard_normal((drives, N)), "du": rng.standard_normal((drives, N))}
+    kets_c = {}
+    for i in range(kets):
+        v = rng.standard_normal((n, N))
+        kets_c[f"psi{i + 1}"] = v / np.linalg.norm(v, axis=0)
+    dts = np.full((1, N), float(dt))
+    comps = {**kets_c, **comps, "t": np.concatenate([[0.0], np.cumsum(dts[0])[:-1]])[None, :], "dt": dts}
+    traj = NamedTrajectory(comps, timestep="dt")
+    fam = ModulatedGenerators(G, mods)
+    kets_int = [TimeDependentBilinearIntegrator(fam, name, "u", "t", traj, spline_order=order, substeps=substeps) for name in kets_c]
+    der = DerivativeIntegrator("u", "du", traj)
+    integrators = kets_int[:1] + [der] + kets_int[1:] if derivative_between else kets_int + [der]
+    J = QuadraticRegularizer("u", traj, 1e-2) + QuadraticRegularizer("du", traj, 1e-2)
+    for name in kets_c:
+        goal = rng.standard_normal(n)
+        J = J + KnotPointObjective("sqdist", name, traj, times=[N], Qs=[10.0], params=(goal / np.linalg.norm(goal))[None, :])
+    return DirectTrajOptProblem(traj, J, integrators)

@@ -191,7 +191,19 @@ typedef struct dto_constraint_desc {
                                         integrators on the small path or the structured path are reported as grouped but keep their
                                         evaluation.  Same structure, same value layout, the followers' blocks bit-identical to the leader's
                                         (dto_integrator_share tells).  eval_constraint, the Hessian and the matrix-free J w / J' w form
-                                        no propagator and are not changed */
+                                        no propagator and are not changed.
+                                        DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR integrators are grouped among themselves (never with the
+                                        bilinear kind): equal x_dim, the same control component (u_off, u_dim) and time component t_off,
+                                        equal spline_order, substeps and n_mod, every modulation's kind and omega equal, and all
+                                        (m+1)(1+n_mod) matrices G_j, H_cj equal entry by entry (==).  A group is ACTIVE when it has two
+                                        members or more on the dense MFMA path (65..256 states, not on the structured path): one launch per
+                                        group and callback (eval_constraint, Jacobian, Hessian) then forms every M0 = sum_q c_q B_q, every
+                                        coefficient table and the Jacobian's Phi block once and carries each member's own vectors beside
+                                        them (csrc/dto_tdb_mfma.hip, group form).  A member's values are bit-identical to the unflagged
+                                        handle's.  A launch takes as many members as an 8 MiB scratch slot per resident workgroup admits
+                                        (at most 8), larger groups run in consecutive launches; option "tdb_share_members" lowers the
+                                        count.  Groups of 1..64 states or on the structured path are reported as grouped, inactive, and
+                                        evaluated as with the flag clear; the matrix-free J w / J' w stay one launch per member */
 
 typedef struct dto_problem_desc {
     int32_t abi_version;    /* DTO_ABI_VERSION */
@@ -250,8 +262,9 @@ int dto_shard_rows(const dto_handle* h, int64_t* start1, int64_t* len);
 int dto_integrator_blocks(const dto_handle* h, int32_t integrator, int32_t* block_dim, int32_t* reps, int32_t* active);
 
 /* the group of integrator i (0-based) under DTO_FLAG_SHARED_GENERATORS: its leader (0-based position in the integrator list), the
-   number of members, and whether the group shares one propagator chain; (i, 1, 0) when the flag is clear, the kind is not
-   bilinear, or the integrator has no partner */
+   number of members, and whether the group shares -- one propagator chain (bilinear), one propagation per callback
+   (time-dependent bilinear); (i, 1, 0) when the flag is clear, the kind is neither bilinear nor time-dependent bilinear, or the
+   integrator has no partner */
 int dto_integrator_share(const dto_handle* h, int32_t integrator, int32_t* leader, int32_t* group_size, int32_t* active);
 
 /* Cost model of one eval_constraint_jacobian for intervals first .. first+count-1 (0-based, GLOBAL numbering; Z is the whole NLP
@@ -430,6 +443,9 @@ int dto_bind_output_dev(dto_handle* h, int32_t vector, double* dptr);
  *   "host_xfer_check" (default 0): every host-pointer dto_eval_jacobian / dto_eval_hessian also copies the whole device slab and
  *   compares it bit for bit with the vector it assembled from the variable runs and the constants; a difference (a kernel that
  *   wrote an entry the hand-off plan does not list) fails the call.  The repository's GPU tests run with it on.
+ *   "tdb_share_members" (default: the largest count the handle was created for): members per launch of an active group of
+ *   time-dependent integrators (DTO_FLAG_SHARED_GENERATORS), 1 .. that count; 1 is one launch per member through the lone kernel,
+ *   the A/B switch.  Values outside the range are refused.  The results do not depend on it, bit for bit.
  *   "tdb_matrix_free_products" (default 0): 1 makes dto_eval_jacobian_product / _transpose_product (and their _dev forms) of a handle
  *   whose TimeDependentBilinearIntegrators all run on a dense device path (1..256 states without DTO_FLAG_BLOCK_GENERATORS structure)
  *   matrix-free: J w is the discrete scheme applied to two vectors, J' w to 1 + p forward vectors and one adjoint vector -- no

@@ -41,7 +41,7 @@ const lib = get(ENV, "DTO_ENGINE_LIB", "libdto_engine.so")
 const DTO_ABI_VERSION = Int32(8)
 
 const DTO_FLAG_BLOCK_GENERATORS = Int32(2)
-const DTO_FLAG_SHARED_GENERATORS = Int32(4)
+const DTO_FLAG_SHARED_GENERATORS = Int32(4)  # integrators of one system: bilinear ones share the propagator chain, time-dependent ones one propagation per call
 const DTO_INTEGRATOR_BILINEAR = Int32(1)
 const DTO_INTEGRATOR_DERIVATIVE = Int32(2)
 const DTO_INTEGRATOR_EXTERNAL = Int32(3)
@@ -746,7 +746,11 @@ end
 `(leader, group_size, active)` of integrator `i` (1-based): the group of `BilinearIntegrator`s whose extracted generators and control
 component are equal (`GPUEvaluator(prob; shared_generators = true)`: the kets `ψ̃1 … ψ̃P` of a multi-state problem, all built from
 one closure `G`), its first member in list order, and whether the group shares one propagator chain in
-`eval_constraint_jacobian`; `(i, 1, false)` otherwise.
+`eval_constraint_jacobian`; `(i, 1, false)` otherwise.  The flag also groups device `TimeDependentBilinearIntegrator`s among
+themselves -- the same generator family (every `G_j`, `H_cj`, modulation kind and frequency), control and time component, spline
+order and sub-steps: at 65..256 states on the dense path such a group runs one propagation per `eval_constraint`, Jacobian and
+Hessian call instead of one per ket (`set_option!(ev, "tdb_share_members", 1)` is one launch per member), with values bit-identical
+to the unflagged evaluator's.
 """
 function integrator_share(ev::GPUEvaluator, i::Integer)
     l, n, a = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
