@@ -742,6 +742,12 @@ const double* ext_upload(dto_handle* h, int slot, int which, hipStream_t st) {
     return e.d[which];
 }
 
+// workgroups of a persistent-grid launch of `t` (k_tdb_mfma, its group and product forms, k_tdb_kron): its `resident`, lowered by
+// option "tdb_resident" -- the scratch holds `resident` slots, a smaller grid uses the first ones
+int tdb_grid(const dto_handle* h, const TdbHost& t) {
+    return h->tdb_resident > 0 ? std::min(h->tdb_resident, t.resident) : t.resident;
+}
+
 // blocks of a device-evaluated time-dependent bilinear integrator: the owned intervals for the defect; for the Jacobian /
 // Hessian also the interval left of the first owned knot, whose z_{k+1} half lands in that knot's columns
 void tdb_eval(dto_handle* h, TdbHost& t, const double* dZ, const double* dmu, int need, hipStream_t st) {
@@ -750,13 +756,13 @@ void tdb_eval(dto_handle* h, TdbHost& t, const double* dZ, const double* dmu, in
     const int64_t hi = need == 0 ? P.kn_lo + P.n_int : std::min<int64_t>(P.K, P.kn_lo + P.n_knots);
     if (t.kron) {
         ProfScope ps(h, st, CAT_TDB_KRON, tdb_kron_flops(t.k, t.kk, need) * (double)std::max<int64_t>(hi - lo, 0));
-        HIP_CHECK(launch_tdb_kron(st, P, t.k, t.kk, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch, t.stride, t.resident));
+        HIP_CHECK(launch_tdb_kron(st, P, t.k, t.kk, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch, t.stride, tdb_grid(h, t)));
         return;
     }
     if (t.mfma) {
         ProfScope ps(h, st, CAT_TDB_MFMA, tdb_mfma_flops(t.k, need) * (double)std::max<int64_t>(hi - lo, 0));
         HIP_CHECK(launch_tdb_mfma(st, P, t.k, t.d_Bp, t.d_BpT, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch,
-                                  t.stride, t.resident));
+                                  t.stride, tdb_grid(h, t)));
         return;
     }
     HIP_CHECK(launch_tdb(st, P, t.k, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch, t.stride));
@@ -795,7 +801,7 @@ void tdb_eval_shared(dto_handle* h, TdbHost& t, const double* dZ, const double* 
         }
         ProfScope ps(h, st, CAT_TDB_MFMA, tdb_mfma_group_flops(lead.k, need, count) * (double)std::max<int64_t>(hi - lo, 0));
         HIP_CHECK(launch_tdb_mfma_group(st, P, lead.k, g, lead.d_Bp, lead.d_BpT, dZ, dmu, need, lo, hi - lo, lead.d_share_scratch,
-                                        lead.share_stride, lead.resident));
+                                        lead.share_stride, tdb_grid(h, lead)));
     });
 }
 
@@ -806,7 +812,7 @@ void tdb_product(dto_handle* h, TdbHost& t, const double* dZ, const double* dw, 
     const int need = transpose ? 4 : 3;
     ProfScope ps(h, st, CAT_TDB_PRODUCT, (t.mfma ? tdb_mfma_flops(t.k, need) : tdb_product_flops(t.k, need)) * (double)std::max<int64_t>(P.K, 0));
     double* out = transpose ? t.d_jtv : dy;
-    if (t.mfma) HIP_CHECK(launch_tdb_mfma_product(st, P, t.k, t.d_Bp, t.d_BpT, dZ, dw, need, out, t.d_scratch, t.stride, t.resident));
+    if (t.mfma) HIP_CHECK(launch_tdb_mfma_product(st, P, t.k, t.d_Bp, t.d_BpT, dZ, dw, need, out, t.d_scratch, t.stride, tdb_grid(h, t)));
     else HIP_CHECK(launch_tdb_product(st, P, t.k, dZ, dw, need, out, t.d_scratch, t.stride));
     if (transpose) HIP_CHECK(launch_tdb_jtv_place(st, P, t.k, dw, t.d_jtv, dy));
 }
@@ -2491,6 +2497,16 @@ int dto_set_option(dto_handle* h, const char* name, int64_t value) {
             return fail(h, "dto_set_option: tdb_share_members takes 1 (one launch per member) .. " + std::to_string(cap) +
                                ", the largest group launch this handle was created for");
         h->tdb_share_members = (int)value;
+        return 0;
+    }
+    if (std::string(name) == "tdb_resident") {
+        int most = 0;
+        for (const TdbHost& t : h->tdb)
+            if (t.mfma || t.kron) most = std::max(most, t.resident);
+        if (value < 0 || value > most)
+            return fail(h, "dto_set_option: tdb_resident takes 0 (the default grid) .. " + std::to_string(most) +
+                               ", the largest persistent grid of this handle's k_tdb_mfma / k_tdb_kron integrators");
+        h->tdb_resident = (int)value;
         return 0;
     }
     if (std::string(name) == "expm_form") {

@@ -304,6 +304,7 @@ struct dto_handle {
     int n_cu = 256;
     int chain_chunk = 0;  // option "chain_chunk": upper bound on the intervals per chain chunk (0: workspace capacity)
     int tdb_share_members = 0;  // option of that name: members per group launch of k_tdb_mfma (0: each group's cap from create)
+    int tdb_resident = 0;  // option of that name: cap on the persistent grid of k_tdb_mfma / k_tdb_kron launches (0: each integrator's `resident`)
     int tdb_matrix_free_products = 0;  // option of that name: J w / J' w of dense device time-dependent integrators without a slab
     int deterministic = 0;  // option "deterministic": results independent of overlap_sweep and of the entry-point family
     // deferred errors of the `*_dev` entry points (dto_engine.h, error convention): the sweep statistics of the last

@@ -502,7 +502,9 @@ class Evaluator:
         (0 = by cost, 2 / 3 = two- / three-product form of the Jacobian's matrix exponential), ``tdb_matrix_free_products`` (0 | 1,
         default 0: 1 evaluates J w / J' w of dense device TimeDependentBilinearIntegrators without forming a Jacobian -- the scheme
         applied to two vectors, or to 1 + p forward vectors and one adjoint vector), ``tdb_share_members`` (members per launch of a
-        shared group of time-dependent integrators, 1 = one launch per member); include/dto_engine.h lists every option."""
+        shared group of time-dependent integrators, 1 = one launch per member), ``tdb_resident`` (cap on the persistent grid of the
+        k_tdb_mfma / k_tdb_kron launches, 0 = the default grid; for tests and measurements, the results do not depend on it);
+        include/dto_engine.h lists every option."""
         self._check(self._lib.dto_set_option(self._h, name.encode(), int(value)))
 
     # ---- measurement

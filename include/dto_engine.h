@@ -446,6 +446,13 @@ int dto_bind_output_dev(dto_handle* h, int32_t vector, double* dptr);
  *   "tdb_share_members" (default: the largest count the handle was created for): members per launch of an active group of
  *   time-dependent integrators (DTO_FLAG_SHARED_GENERATORS), 1 .. that count; 1 is one launch per member through the lone kernel,
  *   the A/B switch.  Values outside the range are refused.  The results do not depend on it, bit for bit.
+ *   "tdb_resident" (default 0 = every integrator's own grid): upper bound on the workgroups of the persistent-grid launches of
+ *   time-dependent integrators -- k_tdb_mfma, its group form and its matrix-free products, k_tdb_kron -- which by default start
+ *   min(owned knots + 1, two per compute unit) workgroups that walk the intervals, one scratch slot each.  1 .. the largest such grid
+ *   among the handle's integrators on these kernels caps the grid (a launch takes the smaller of the value and its own grid, and the
+ *   first slots of the scratch it already has); values outside the range are refused, and a handle without such an integrator takes
+ *   0 only.  For tests and measurements: a small problem then makes a workgroup walk several intervals.  The results do not depend
+ *   on it, bit for bit.
  *   "tdb_matrix_free_products" (default 0): 1 makes dto_eval_jacobian_product / _transpose_product (and their _dev forms) of a handle
  *   whose TimeDependentBilinearIntegrators all run on a dense device path (1..256 states without DTO_FLAG_BLOCK_GENERATORS structure)
  *   matrix-free: J w is the discrete scheme applied to two vectors, J' w to 1 + p forward vectors and one adjoint vector -- no

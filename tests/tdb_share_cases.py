@@ -14,12 +14,16 @@ def family(n, m, n_mods, seed):
     G = rng.standard_normal((m + 1, n, n)) / np.sqrt(n / 4.0)
     mods = [("cos", 1.7, 0.5 * rng.standard_normal((m + 1, n, n)) / np.sqrt(n / 4.0)),
             ("sin", 0.6, 0.5 * rng.standard_normal((m + 1, n, n)) / np.sqrt(n / 4.0))][:n_mods]
+    # further carriers (wide coefficient tables), drawn after the two above: ("cos" | "sin", 0.25 + 0.4 c), a quarter of the weight
+    mods += [(("cos", "sin")[c % 2], 0.25 + 0.4 * c, 0.25 * rng.standard_normal((m + 1, n, n)) / np.sqrt(n / 4.0)) for c in range(2, n_mods)]
     return G, mods
 
 
-def problem(n, P, m=2, order=1, substeps=2, n_mods=2, N=3, derivative_between=False, members=None, bilinear_first=False):
+def problem(n, P, m=2, order=1, substeps=2, n_mods=2, N=3, derivative_between=False, members=None, bilinear_first=False,
+            derivative=True):
     """`members[i]`: dict with any of G, mods, order, substeps, u (0: u, 1: v), t (0: t, 1: s), dim.  `bilinear_first`: a
-    BilinearIntegrator with the family's G on x_1 leads the list (member 0 of the time-dependent kind then sits on x_2)."""
+    BilinearIntegrator with the family's G on x_1 leads the list (member 0 of the time-dependent kind then sits on x_2).
+    `derivative=False`: no DerivativeIntegrator (a handle takes eight integrators: the only way to eight members)."""
     members = [{} for _ in range(P)] if members is None else members
     nx = P + (1 if bilinear_first else 0)
     dims = [n] * nx
@@ -45,7 +49,7 @@ def problem(n, P, m=2, order=1, substeps=2, n_mods=2, N=3, derivative_between=Fa
         integ.append(it)
         if derivative_between and i == 0:
             integ.append(O.DerivativeIntegrator(u0, m, u0 + 2 * m))
-    if not derivative_between:
+    if derivative and not derivative_between:
         integ.append(O.DerivativeIntegrator(u0, m, u0 + 2 * m))
     rng = np.random.default_rng(7 + n + P)
     rows = [rng.standard_normal((u0, N)), 0.4 * rng.standard_normal((2 * m, N)), rng.standard_normal((m, N)),
@@ -64,6 +68,37 @@ CASES = [(65, 2, 1, 0, 2, 2, False),
 
 def case(n, P, m, order, substeps, n_mods, derivative_between, N=3):
     return problem(n, P, m=m, order=order, substeps=substeps, n_mods=n_mods, N=N, derivative_between=derivative_between)
+
+
+def lone(n, m, order, substeps, n_mods, N):
+    """One integrator of the family on x_1 (and the DerivativeIntegrator): what k_tdb_mfma runs alone."""
+    return problem(n, 1, m=m, order=order, substeps=substeps, n_mods=n_mods, N=N)
+
+
+# ---- the scratch cap of a group launch, restated from DESIGN 4.22 (host arithmetic; the engine's is tdbg_layout and
+# find_time_dependent_share_groups)
+
+
+def slot_doubles(n, m, order, n_mods, need, P):
+    """Scratch slot of a group launch of P members in doubles ("Group size"); need 0 / 1 / 2: defect, Jacobian, Hessian."""
+    pad32 = lambda v: (v + 31) // 32 * 32
+    np_, p, Q = pad32(n), m + 2 + (m if order else 0), (m + 1) * (1 + n_mods)
+    P2 = p * (p + 1) // 2
+    C1 = (1, 1 + p, 1 + p + P2)[need]
+    Ctot = pad32(P * (pad32(C1) if need == 2 else C1)) + (np_ if need == 1 else 0)
+    ucols = 32 * P if need == 2 else P
+    total = 4 * np_ * Ctot + np_ * np_ + Q * ucols * np_ + (32 * np_ * P if need == 2 else 0) + (1 + p + P2) * Q
+    return total + total % 2
+
+
+def launch_cap(n, m, order, n_mods, members, hessian):
+    """Members per launch: the largest count up to 8 whose slot of every callback the handle has stays within 8 MiB; 1: inactive."""
+    cap = 1
+    for g in range(2, min(members, 8) + 1):
+        if 8 * max(slot_doubles(n, m, order, n_mods, need, g) for need in ((0, 1, 2) if hessian else (0, 1))) > 8 << 20:
+            break
+        cap = g
+    return cap
 
 
 def reference(prob, key):
