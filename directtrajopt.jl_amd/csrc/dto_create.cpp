@@ -103,7 +103,7 @@ void find_share_groups(dto_handle* h, const dto_problem_desc* d) {
 // The same flag on DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR integrators: groups of equal x_dim, control and time component, scheme
 // (order, substeps), modulations and matrices G_j, H_cj (==).  Never mixed with the bilinear kind.  A group is active when its
 // members run on k_tdb_mfma; its launches take at most `share_cap` members, the largest count whose scratch slot stays within
-// TDB_SHARE_SLOT_BYTES per resident workgroup (the slot is 4 np Ctot + np^2 + the U_q columns, tdb_mfma_group_scratch_doubles).
+// TDB_SHARE_SLOT_BYTES per resident workgroup (the slot is 4 np Ctot + np^2 + the U_q columns, tdb_mfma_scratch_doubles).
 constexpr size_t TDB_SHARE_SLOT_BYTES = (size_t)8 << 20;
 
 bool same_time_dependent_system(const dto_integrator_desc& a, const dto_integrator_desc& c) {
@@ -141,8 +141,8 @@ void find_time_dependent_share_groups(dto_handle* h, const dto_problem_desc* d) 
         int cap = 1;
         if (lead.mfma && !lead.kron)
             for (int g = 2; g <= std::min<int>((int)members.size(), TDB_SHARE_MAX); ++g) {
-                size_t slot = std::max(tdb_mfma_group_scratch_doubles(lead.k, 0, g), tdb_mfma_group_scratch_doubles(lead.k, 1, g));
-                if (d->eval_hessian) slot = std::max(slot, tdb_mfma_group_scratch_doubles(lead.k, 2, g));
+                size_t slot = std::max(tdb_mfma_scratch_doubles(lead.k, 0, g), tdb_mfma_scratch_doubles(lead.k, 1, g));
+                if (d->eval_hessian) slot = std::max(slot, tdb_mfma_scratch_doubles(lead.k, 2, g));
                 if (slot * sizeof(double) > TDB_SHARE_SLOT_BYTES) break;
                 cap = g;
             }
@@ -1066,8 +1066,8 @@ void alloc_tdb(dto_handle* h) {
             t.d_scratch = own(h, dalloc<double>(t.stride * (size_t)t.resident));
             if (!t.share_members.empty()) {   // leader of an active group: the slots of the group launches
                 const int g = t.share_cap;
-                t.share_stride = scratch_stride(std::max(tdb_mfma_group_scratch_doubles(t.k, 0, g), tdb_mfma_group_scratch_doubles(t.k, 1, g)),
-                                                tdb_mfma_group_scratch_doubles(t.k, 2, g), hess);
+                t.share_stride = scratch_stride(std::max(tdb_mfma_scratch_doubles(t.k, 0, g), tdb_mfma_scratch_doubles(t.k, 1, g)),
+                                                tdb_mfma_scratch_doubles(t.k, 2, g), hess);
                 t.d_share_scratch = own(h, dalloc<double>(t.share_stride * (size_t)t.resident));
             }
             continue;

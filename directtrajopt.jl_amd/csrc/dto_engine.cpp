@@ -742,30 +742,10 @@ const double* ext_upload(dto_handle* h, int slot, int which, hipStream_t st) {
     return e.d[which];
 }
 
-// workgroups of a persistent-grid launch of `t` (k_tdb_mfma, its group and product forms, k_tdb_kron): its `resident`, lowered by
+// workgroups of a persistent-grid launch of `t` (k_tdb_mfma and its product form, k_tdb_kron): its `resident`, lowered by
 // option "tdb_resident" -- the scratch holds `resident` slots, a smaller grid uses the first ones
 int tdb_grid(const dto_handle* h, const TdbHost& t) {
     return h->tdb_resident > 0 ? std::min(h->tdb_resident, t.resident) : t.resident;
-}
-
-// blocks of a device-evaluated time-dependent bilinear integrator: the owned intervals for the defect; for the Jacobian /
-// Hessian also the interval left of the first owned knot, whose z_{k+1} half lands in that knot's columns
-void tdb_eval(dto_handle* h, TdbHost& t, const double* dZ, const double* dmu, int need, hipStream_t st) {
-    const KProb& P = h->P;
-    const int64_t lo = need == 0 ? P.kn_lo : std::max<int64_t>(0, P.kn_lo - 1);
-    const int64_t hi = need == 0 ? P.kn_lo + P.n_int : std::min<int64_t>(P.K, P.kn_lo + P.n_knots);
-    if (t.kron) {
-        ProfScope ps(h, st, CAT_TDB_KRON, tdb_kron_flops(t.k, t.kk, need) * (double)std::max<int64_t>(hi - lo, 0));
-        HIP_CHECK(launch_tdb_kron(st, P, t.k, t.kk, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch, t.stride, tdb_grid(h, t)));
-        return;
-    }
-    if (t.mfma) {
-        ProfScope ps(h, st, CAT_TDB_MFMA, tdb_mfma_flops(t.k, need) * (double)std::max<int64_t>(hi - lo, 0));
-        HIP_CHECK(launch_tdb_mfma(st, P, t.k, t.d_Bp, t.d_BpT, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch,
-                                  t.stride, tdb_grid(h, t)));
-        return;
-    }
-    HIP_CHECK(launch_tdb(st, P, t.k, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch, t.stride));
 }
 
 // members per launch of an active time-dependent group: its cap from create, lowered by option "tdb_share_members"
@@ -781,28 +761,43 @@ void tdb_share_launches(const dto_handle* h, const TdbHost& lead, F&& f) {
     for (int first = 0; first < size; first += cap) f(first, std::min(cap, size - first));
 }
 
-// The blocks of integrator `t` as tdb_eval leaves them, through its group where it has an active one (DTO_FLAG_SHARED_GENERATORS,
-// DESIGN 4.22): the group's launches run at the leader's turn -- the first member in list order, which every caller reaches first --
-// and write the blocks of all members; a follower's turn finds its blocks written.  A launch left with one member is the lone kernel.
-void tdb_eval_shared(dto_handle* h, TdbHost& t, const double* dZ, const double* dmu, int need, hipStream_t st) {
-    if (!t.share_active || tdb_share_cap(h, t) < 2) return tdb_eval(h, t, dZ, dmu, need, st);
-    TdbHost& lead = h->tdb[t.share_leader];
-    if (&t != &lead) return;
+// One launch of k_tdb_mfma for `count` integrators of one system (indices into h->tdb), intervals lo .. hi - 1.  A launch of one
+// runs on that integrator's own description and scratch, a larger one on the leader's and the slots of the group launches.
+void tdb_mfma_eval(dto_handle* h, const TdbHost& lead, const int* members, int count, const double* dZ, const double* dmu, int need,
+                   int64_t lo, int64_t hi, hipStream_t st) {
+    const TdbHost& t = count == 1 ? h->tdb[members[0]] : lead;
+    KTdbGroup g{};
+    g.count = count;
+    for (int i = 0; i < count; ++i) {
+        const TdbHost& mb = h->tdb[members[i]];
+        g.m[i] = KTdbMember{mb.k.x_off, mb.k.row_off, mb.d_vals, mb.d_jac, mb.d_hess};
+    }
+    ProfScope ps(h, st, CAT_TDB_MFMA, tdb_mfma_flops(t.k, need, count) * (double)std::max<int64_t>(hi - lo, 0));
+    HIP_CHECK(launch_tdb_mfma(st, h->P, t.k, g, t.d_Bp, t.d_BpT, dZ, dmu, need, lo, hi - lo, count == 1 ? t.d_scratch : t.d_share_scratch,
+                              count == 1 ? t.stride : t.share_stride, tdb_grid(h, t)));
+}
+
+// blocks of a device-evaluated time-dependent bilinear integrator: the owned intervals for the defect; for the Jacobian /
+// Hessian also the interval left of the first owned knot, whose z_{k+1} half lands in that knot's columns.  An active group
+// (DTO_FLAG_SHARED_GENERATORS) is evaluated at its leader's turn -- the first member in list order, which every caller
+// reaches first -- by launches that write the blocks of all members; a follower's turn finds its blocks written.
+void tdb_eval(dto_handle* h, TdbHost& t, const double* dZ, const double* dmu, int need, hipStream_t st) {
     const KProb& P = h->P;
     const int64_t lo = need == 0 ? P.kn_lo : std::max<int64_t>(0, P.kn_lo - 1);
     const int64_t hi = need == 0 ? P.kn_lo + P.n_int : std::min<int64_t>(P.K, P.kn_lo + P.n_knots);
-    tdb_share_launches(h, lead, [&](int first, int count) {
-        if (count == 1) return tdb_eval(h, h->tdb[lead.share_members[first]], dZ, dmu, need, st);
-        KTdbGroup g{};
-        g.count = count;
-        for (int i = 0; i < count; ++i) {
-            const TdbHost& mb = h->tdb[lead.share_members[first + i]];
-            g.m[i] = KTdbMember{mb.k.x_off, mb.k.row_off, mb.d_vals, mb.d_jac, mb.d_hess};
-        }
-        ProfScope ps(h, st, CAT_TDB_MFMA, tdb_mfma_group_flops(lead.k, need, count) * (double)std::max<int64_t>(hi - lo, 0));
-        HIP_CHECK(launch_tdb_mfma_group(st, P, lead.k, g, lead.d_Bp, lead.d_BpT, dZ, dmu, need, lo, hi - lo, lead.d_share_scratch,
-                                        lead.share_stride, tdb_grid(h, lead)));
-    });
+    if (t.kron) {
+        ProfScope ps(h, st, CAT_TDB_KRON, tdb_kron_flops(t.k, t.kk, need) * (double)std::max<int64_t>(hi - lo, 0));
+        HIP_CHECK(launch_tdb_kron(st, P, t.k, t.kk, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch, t.stride, tdb_grid(h, t)));
+    } else if (!t.mfma) {
+        HIP_CHECK(launch_tdb(st, P, t.k, dZ, dmu, need, lo, hi - lo, t.d_vals, t.d_jac, t.d_hess, t.d_scratch, t.stride));
+    } else if (!t.share_active || tdb_share_cap(h, t) < 2) {
+        const int self = (int)(&t - h->tdb.data());
+        tdb_mfma_eval(h, t, &self, 1, dZ, dmu, need, lo, hi, st);
+    } else if (t.share_leader == (int)(&t - h->tdb.data())) {
+        tdb_share_launches(h, t, [&](int first, int count) {
+            tdb_mfma_eval(h, t, t.share_members.data() + first, count, dZ, dmu, need, lo, hi, st);
+        });
+    }
 }
 
 // Matrix-free products of a dense device time-dependent integrator (option "tdb_matrix_free_products"): its rows of J w, or its
@@ -917,7 +912,7 @@ void do_constraint(dto_handle* h, const double* dZ, double* dg, hipStream_t st) 
     for (size_t i = 0; i < h->ext_int.size(); ++i)
         if (h->P.n_int > 0) launch_extint_cons(st, h->P, h->ext_int[i], ext_upload(h, (int)i, 0, st), dg);
     for (auto& t : h->tdb)
-        if (h->P.n_int > 0) { tdb_eval_shared(h, t, dZ, nullptr, 0, st); launch_extint_cons(st, h->P, t.place, t.d_vals, dg); }
+        if (h->P.n_int > 0) { tdb_eval(h, t, dZ, nullptr, 0, st); launch_extint_cons(st, h->P, t.place, t.d_vals, dg); }
     for (auto& c : h->con) {
         if (!c.external) launch_cons_knot(st, h->P, c.k, dZ, dg);
         else if (c.k.n_times > 0) launch_ext_cons(st, c.k, ext_upload(h, c.ext_slot, 0, st), dg);
@@ -1101,7 +1096,7 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
     for (auto& d : h->der) launch_jac_derivative(st, h->P, d, dZ, dvals);
     for (size_t i = 0; i < h->ext_int.size(); ++i)
         launch_extint_jac(st, h->P, h->ext_int[i], ext_upload(h, (int)i, 1, st), dvals);
-    for (auto& t : h->tdb) { tdb_eval_shared(h, t, dZ, nullptr, 1, st); launch_extint_jac(st, h->P, t.place, t.d_jac, dvals); }
+    for (auto& t : h->tdb) { tdb_eval(h, t, dZ, nullptr, 1, st); launch_extint_jac(st, h->P, t.place, t.d_jac, dvals); }
     for (auto& c : h->con) {
         if (!c.external) launch_jac_knot(st, h->P, c.k, dZ, dvals);
         else if (c.k.n_times > 0) launch_ext_jac(st, c.k, ext_upload(h, c.ext_slot, 1, st), dvals);
@@ -1250,7 +1245,7 @@ void do_hessian(dto_handle* h, const double* dZ, double sigma, const double* dmu
         } else if (h->integ_kind[i] == DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) {
             need_zero();
             TdbHost& t = h->tdb[h->integ_index[i]];
-            tdb_eval_shared(h, t, dZ, dmu, 2, st);
+            tdb_eval(h, t, dZ, dmu, 2, st);
             launch_extint_hess(st, h->P, t.place, t.d_hess, dH);
         } else {  // the caller's blocks already carry mu_k (eval_hessian_of_lagrangian(integrator, traj, mu_slice))
             need_zero();
@@ -1921,7 +1916,7 @@ int dto_interval_costs(const dto_handle* h, const double* Z, int64_t first, int6
             if (t.share_active && tdb_share_cap(h, t) >= 2) {
                 c = 0.0;
                 if (!t.share_members.empty())
-                    tdb_share_launches(h, t, [&](int, int n) { c += n == 1 ? tdb_mfma_flops(t.k, 1) : tdb_mfma_group_flops(t.k, 1, n); });
+                    tdb_share_launches(h, t, [&](int, int n) { c += tdb_mfma_flops(t.k, 1, n); });
             }
             for (int64_t i = 0; i < count; ++i) cost[i] += c;
         }

@@ -376,23 +376,12 @@ hipError_t launch_tdb_jtv_place(hipStream_t st, const KProb& P, const KTdb& T, c
 // applied as scalar combinations of B_q y; a persistent grid of `resident` workgroups, one scratch slot of `scratch_stride` doubles
 // each.  Bp / BpT: the Q = (m+1)(1+nmod) matrices G_j, H_cj (q = j (1 + nmod) + c) and their transposes, zero-padded to
 // tdb_mfma_npad(n) rows and columns, column-major.  tdb_mfma_refusal: nullptr, or which limit of the device kernels (either of
-// them: 1..256 states, substeps, coefficient table) a description exceeds.  tdb_mfma_flops: flops of one interval as executed.
-int tdb_mfma_npad(int n);
-const char* tdb_mfma_refusal(const KTdb& T);
-bool tdb_mfma_supported(const KTdb& T);
-size_t tdb_mfma_scratch_doubles(const KTdb& T, int need);
-double tdb_mfma_flops(const KTdb& T, int need);
-hipError_t launch_tdb_mfma(hipStream_t st, const KProb& P, const KTdb& T, const double* Bp, const double* BpT, const double* dZ,
-                           const double* dmu, int need, int64_t i_lo, int64_t count, double* vals, double* jac, double* hess,
-                           double* scratch, size_t scratch_stride, int resident);
-// ... and its product modes (need 3 / 4, `out` as launch_tdb_product's; tdb_mfma_scratch_doubles and tdb_mfma_flops cover them)
-hipError_t launch_tdb_mfma_product(hipStream_t st, const KProb& P, const KTdb& T, const double* Bp, const double* BpT, const double* dZ,
-                                   const double* dw, int need, double* out, double* scratch, size_t scratch_stride, int resident);
-
-// The group form of k_tdb_mfma (DTO_FLAG_SHARED_GENERATORS on time-dependent integrators): `G.count` members (2 .. TDB_SHARE_MAX)
-// that differ in their state component and rows only, evaluated by ONE launch that forms every M0, coefficient table and (Jacobian)
-// the Phi block once.  T is the leader's description; each member's blocks go to its own vals / jac / hess, bit for bit what
-// launch_tdb_mfma writes for it.  need 0 .. 2; the scratch slot is tdb_mfma_group_scratch_doubles, the flops are as executed.
+// them: 1..256 states, substeps, coefficient table) a description exceeds.
+// One launch evaluates `G.count` integrators of one system (1 .. TDB_SHARE_MAX; more than one under DTO_FLAG_SHARED_GENERATORS):
+// members that differ in their state component and rows only, with every M0, coefficient table and (Jacobian) the Phi block formed
+// once.  T is any member's description; each member's blocks go to its own vals / jac / hess, bit for bit what a launch of that
+// member alone writes.  need 0 .. 2.  tdb_mfma_scratch_doubles: the slot of one workgroup; tdb_mfma_flops: flops of one interval as
+// executed; both for a launch of `members`, and at one member also for the product modes.
 constexpr int TDB_SHARE_MAX = 8;
 struct KTdbMember {
     int32_t x_off;
@@ -403,11 +392,17 @@ struct KTdbGroup {
     int32_t count;
     KTdbMember m[TDB_SHARE_MAX];
 };
-size_t tdb_mfma_group_scratch_doubles(const KTdb& T, int need, int members);
-double tdb_mfma_group_flops(const KTdb& T, int need, int members);
-hipError_t launch_tdb_mfma_group(hipStream_t st, const KProb& P, const KTdb& T, const KTdbGroup& G, const double* Bp, const double* BpT,
-                                 const double* dZ, const double* dmu, int need, int64_t i_lo, int64_t count, double* scratch,
-                                 size_t scratch_stride, int resident);
+int tdb_mfma_npad(int n);
+const char* tdb_mfma_refusal(const KTdb& T);
+bool tdb_mfma_supported(const KTdb& T);
+size_t tdb_mfma_scratch_doubles(const KTdb& T, int need, int members = 1);
+double tdb_mfma_flops(const KTdb& T, int need, int members = 1);
+hipError_t launch_tdb_mfma(hipStream_t st, const KProb& P, const KTdb& T, const KTdbGroup& G, const double* Bp, const double* BpT,
+                           const double* dZ, const double* dmu, int need, int64_t i_lo, int64_t count, double* scratch,
+                           size_t scratch_stride, int resident);
+// ... and the product modes of one integrator (need 3 / 4, `out` as launch_tdb_product's)
+hipError_t launch_tdb_mfma_product(hipStream_t st, const KProb& P, const KTdb& T, const double* Bp, const double* BpT, const double* dZ,
+                                   const double* dw, int need, double* out, double* scratch, size_t scratch_stride, int resident);
 
 // BilinearIntegrator with replicated-block generators G_j = I_r (x) B_j (dto_kron.hip): one workgroup per interval sweeps b-row
 // column groups against the b x b blocks and writes defect, Jacobian block or Hessian block of mu_k' f straight to their positions

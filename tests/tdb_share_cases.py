@@ -75,7 +75,7 @@ def lone(n, m, order, substeps, n_mods, N):
     return problem(n, 1, m=m, order=order, substeps=substeps, n_mods=n_mods, N=N)
 
 
-# ---- the scratch cap of a group launch, restated from DESIGN 4.22 (host arithmetic; the engine's is tdbg_layout and
+# ---- the scratch cap of a group launch, restated from DESIGN 4.22 (host arithmetic; the engine's is tdbm_layout and
 # find_time_dependent_share_groups)
 
 

@@ -14,7 +14,7 @@ and complex steps): 1e-10 relative for g and the Jacobian, 1e-8 for the Hessian,
 else is compared bit for bit: an interval's bits depend on its data alone.  Outputs are filled with NaN beforehand, so an entry
 without a writer fails; the handles run with "host_xfer_check" on (conftest.py).
 
-What part a would catch, from the kernels' code (k_tdb_mfma; the group form and k_tdb_kron have the same loop):
+What part a would catch, from the kernels' code (k_tdb_mfma, for one integrator and for a group; k_tdb_kron has the same loop):
   * the loop body starts by writing all np * Ctot entries of Y -- x_k, the identity of the Phi block, zeros in the parameter
     columns and in the padding ("initial values: ...").  Without it an interval's second trip would start its RK4 steps from the
     Y the slot's previous interval ended with: x and Phi of interval it - grid instead of x_k and I, and padding columns that are no
@@ -131,7 +131,7 @@ def test_a_group_kernel_second_and_third_trips(case):
         tdb = [i for i, it in enumerate(po.integrators) if isinstance(it, O.TimeDependentBilinearIntegrator)]
         assert [ev.integrator_share(i) for i in tdb] == [(tdb[0], case[1], 1)] * case[1]
         _same_structure(ev, ev_r)
-        _check_grids("k_tdb_mfma_group %s" % (case,), ev, po.Z0, mu, (g_r, j_r, h_r), 3, (0, 1, 2))
+        _check_grids("k_tdb_mfma, group %s" % (case,), ev, po.Z0, mu, (g_r, j_r, h_r), 3, (0, 1, 2))
         ev.set_option("tdb_resident", 3)
         assert _launches(ev, po.Z0, mu) == [1, 1, 1]
     finally:
@@ -232,7 +232,7 @@ def test_b_lone_kernel_at_the_real_grid():
 
 
 def test_b_group_kernel_at_the_real_grid():
-    """k_tdb_mfma_group at the default grid, N_L knots as above (two and three trips per workgroup): 65 states x 2 kets of the same
+    """k_tdb_mfma's group launch at the default grid, N_L knots as above (two and three trips per workgroup): 65 states x 2 kets of the same
     family, bit for bit the unflagged handle, whose kernel test_b_lone_kernel_at_the_real_grid holds to the reference."""
     import dto_amd
     N_L = _n_long()
@@ -243,7 +243,7 @@ def test_b_group_kernel_at_the_real_grid():
     try:
         assert ev.integrator_share(1) == (0, 2, 1)
         mu = np.random.default_rng(2).standard_normal(ev.n_constraints)
-        _same_bits("k_tdb_mfma_group, %d knots against the unflagged handle" % N_L, _all(ev, long.Z0, mu), _all(plain, long.Z0, mu))
+        _same_bits("k_tdb_mfma, group, %d knots against the unflagged handle" % N_L, _all(ev, long.Z0, mu), _all(plain, long.Z0, mu))
         assert _launches(ev, long.Z0, mu) == [1, 1, 1] and _launches(plain, long.Z0, mu) == [2, 2, 2]
     finally:
         ev.close(); plain.close()
@@ -334,7 +334,7 @@ def test_d_the_scratch_cap_splits_five_members_into_three_and_two():
 
 
 def test_d_the_cap_follows_eval_hessian():
-    """Four members: with the Hessian 3 + 1 (the last one through the lone kernel), without it one launch of four; the unflagged
+    """Four members: with the Hessian 3 + 1 (the last one as a group of one), without it one launch of four; the unflagged
     handle's bits either way."""
     import dto_amd
     assert S.launch_cap(*CAP_SHAPE, 4, True) == 3 and S.launch_cap(*CAP_SHAPE, 4, False) == 4
@@ -360,7 +360,7 @@ def test_d_the_cap_follows_eval_hessian():
 
 def test_d_a_group_the_cap_leaves_inactive():
     """256 states, 7 drives, 12 modulations: two members already take 14.7 MiB, so the group is reported and evaluated member by
-    member (the lone kernel at this shape is tests/test_gpu_tdb_parameters.py's business: no reference here)."""
+    member (a lone integrator at this shape is tests/test_gpu_tdb_parameters.py's business: no reference here)."""
     import dto_amd
     assert S.launch_cap(256, 7, 0, 12, 2, True) == 1
     po = S.problem(256, 2, m=7, order=0, substeps=2, n_mods=12, N=3)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One propagation per group of TimeDependentBilinearIntegrators (Evaluator(..., shared_generators=True), the group form of
+"""One propagation per group of TimeDependentBilinearIntegrators (Evaluator(..., shared_generators=True), the group launches of
 k_tdb_mfma in csrc/dto_tdb_mfma.hip) against one launch per integrator, timed with HIP events (a tools/ probe; GPU).
 
 Per shape, in ONE process: a flagged and an unflagged handle on ``synthetic.multi_ket_modulated_problem(n, kets, drives, N, order,
@@ -37,7 +37,7 @@ def one_call_ms(fn):
 
 
 def group_scratch_MB(n, drives, order, n_mods, members, need):
-    """Doubles of one resident workgroup's slot in a group launch (tdbg_layout of csrc/dto_tdb_mfma.hip), in MB."""
+    """Doubles of one resident workgroup's slot in a group launch (tdbm_layout of csrc/dto_tdb_mfma_layout.h), in MB."""
     pad32 = lambda v: (v + 31) // 32 * 32
     np_, p = pad32(n), drives + 2 + (drives if order else 0)
     P2, Q = p * (p + 1) // 2, (drives + 1) * (1 + n_mods)
