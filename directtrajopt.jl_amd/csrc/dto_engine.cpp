@@ -73,8 +73,7 @@ struct ProfScope {
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
        CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16 };
-// the form a generator sweep took (dto_profile_get "sweep_gs" .. "sweep_step"): one count per run_sweep call, not per launch
-enum { SWEEP_GS = 0, SWEEP_FUSED = 1, SWEEP_S64 = 2, SWEEP_CLUSTER = 3, SWEEP_STEP = 4 };
+// the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
 inline void count_sweep_form(dto_handle* h, int form) {
     if (h->profiling) ++h->sweep_forms[form];
 }
@@ -138,32 +137,8 @@ namespace {
 // sweeps and chain
 // ------------------------------------------------------------------------------------------
 
-SweepTypes make_types(int m, bool second_order) {
-    SweepTypes ty{};
-    int T = 0;
-    ty.t[T++] = TypeDesc{0, {0, 0}, {0, 0}, {0, 0}};  // p
-    for (int j = 0; j < m; ++j) {                    // d^j: + E_j p
-        TypeDesc d{};
-        d.n_extra = 1; d.gen[0] = 1 + j; d.src[0] = 0; d.mult[0] = 1.0;
-        ty.t[T++] = d;
-    }
-    if (second_order) {
-        for (int i = 0; i < m; ++i)
-            for (int j = i; j < m; ++j) {  // h^{ij}: + E_i d^j + E_j d^i
-                TypeDesc d{};
-                if (i == j) {
-                    d.n_extra = 1; d.gen[0] = 1 + i; d.src[0] = 1 + i; d.mult[0] = 2.0;
-                } else {
-                    d.n_extra = 2;
-                    d.gen[0] = 1 + i; d.src[0] = 1 + j; d.mult[0] = 1.0;
-                    d.gen[1] = 1 + j; d.src[1] = 1 + i; d.mult[1] = 1.0;
-                }
-                ty.t[T++] = d;
-            }
-    }
-    ty.T = T;
-    return ty;
-}
+// Step budget, launch shapes and the form a sweep takes: dto_sweep_plan.h (plain C++, testable without a GPU).  What stays here
+// enqueues work or reads the handle.
 
 struct Bounds {
     double beta, b1;
@@ -182,33 +157,10 @@ Bounds get_bounds(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st) {
     return read_bounds(h);
 }
 
-struct SweepPlan {
-    int q, d_ub;
-    int tc = -1;   // first step at which the termination test runs (-1: d_ub / 2 - 1)
-};
 void read_hump(dto_handle* h, BilHost& b);
 SweepPlan plan_hump(const BilHost& b, double beta_fallback);
-
-// Step budget of one round of radius br: the Taylor terms of exp(br) down to 1e-19 (8 to 200 of them), and six more
-int taylor_budget(double br) {
-    int t = 8;
-    double term = 1.0;
-    for (int i = 1; i <= t; ++i) term *= br / i;
-    while (term > 1e-19 && t < 200) { ++t; term *= br / t; }
-    return t + 6;
-}
-
-SweepPlan plan_sweep(double beta) {
-    SweepPlan p{1, 12};
-    if (!(beta == beta) || beta > 1e6) {  // non-finite iterate: bounded work, NaN/Inf propagates to the output
-        p.q = 1; p.d_ub = 30;
-        return p;
-    }
-    static const double theta_v = tune_double("DTO_THETA_V", 9.0);  // worst-case cancellation budget e^9 ~ 1e4 on the Taylor sums (tolerance 1e-10)
-    p.q = std::max(1, (int)std::ceil(beta / theta_v));
-    p.d_ub = taylor_budget(beta / p.q);
-    return p;
-}
+SweepPlan plan_sweep(double beta) { return dto::plan_sweep(beta, sweep_theta_v()); }
+bool cheap_plan(const Bounds& bd, bool loose, SweepPlan& out) { return dto::cheap_plan(bd.beta, loose, sweep_theta_v(), out); }
 
 // Taylor steps a fused sweep (already enqueued on st) actually took: waits for it.
 int fused_sweep_steps(dto_handle* h, const SweepBuf& w, int d_ub, hipStream_t st) {
@@ -219,63 +171,12 @@ int fused_sweep_steps(dto_handle* h, const SweepBuf& w, int d_ub, hipStream_t st
 }
 bool ensure_bind_runs(dto_handle* h, int which);
 
-// The form a generator sweep takes and that form's launch plan.  choose_sweep is the one place that decides it: run_sweep executes
-// a choice, and a caller whose streams or bookkeeping depend on the form asks first and hands the same choice on.
-struct SweepChoice {
-    int form = SWEEP_STEP;
-    GsSweepPlan gs;            // form == SWEEP_GS
-    FusedSweepPlan fused;      // form == SWEEP_FUSED, SWEEP_S64
-    ClusterSweepPlan cluster;  // form == SWEEP_CLUSTER
-    bool store = false, shared_chip = false;  // as asked (SweepArgs::as_chosen takes them from here)
-    bool one_workgroup() const { return form == SWEEP_FUSED || form == SWEEP_S64; }  // the single-workgroup forms (these read plan_dev)
-    SweepChoice& is(int f) { form = f; return *this; }
-};
-
-// store: every Taylor term is kept in w.Zt; shared_chip: another stream's kernels run beside the sweep (the propagator chain, the
-// Hessian's adjoint sweep); step_only: the caller has initialised the sweep itself (the products' extra start vector).
-// In order: generator-stationary, fused (64 states: its generator-stationary instance), row-split cluster, one launch per Taylor step.
+// The form a sweep takes: choose_sweep(const SweepSituation&) of dto_sweep_plan.h, asked with what the handle, the integrator, the
+// sweep's buffers and the plan say
 SweepChoice choose_sweep(const dto_handle* h, const BilHost& b, const SweepBuf& w, const SweepTypes& ty, const SweepPlan& plan,
                          bool store, bool shared_chip, bool step_only = false) {
-    SweepChoice c{};
-    c.store = store;
-    c.shared_chip = shared_chip;
-    // no one-launch form: by option, with frozen p terms, where the term store cannot hold the step budget, and for a stored
-    // single column under reuse_forward_sweep (a frozen sweep reads nterms_p in blocks of TN intervals)
-    if (step_only || h->sweep_form == 1 || w.frozen) return c;
-    if (store && (!(w.Zt && plan.d_ub + 1 <= w.dcap) || (ty.T == 1 && h->reuse))) return c;
-    // the fused planner's answer for a sweep that has the chip to itself: asked by the generator-stationary and the fused form
-    const bool fused_alone = sweep_fused_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, c.fused);
-    // Generator-stationary form (dto_sweep_gs.hip): clusters of npad / 32 workgroups with the generators resident in their registers.
-    // It needs the whole chip to itself (one 512-register workgroup per CU, all cluster members resident): not beside the chain
-    // (`shared_chip`), not with sub-stepping.  It is taken where the single-workgroup form cannot fill the chip: single-column sweeps
-    // (eval_constraint, the Hessian's forward column) and sweeps the fused planner refuses (short shards); measured
-    // (tools/sweep_gs_probe, 256 states): p column of 2000 knots 0.77 ms against 1.38 ms for the split-K step launches, Jacobian
-    // sweep of 250 knots 0.80 against 1.15 ms for the row-split cluster form.
-    static const int gs_on = tune_int("DTO_SWEEP_GS", 1);  // A/B runs (TUNING builds): 0 = never, 2 = wherever it can run
-    if (gs_on && plan.q == 1 && h->n_cu >= 64 && !(shared_chip && gs_on != 2) &&
-        (size_t)ty.T * w.Kpad * w.npad * 8 < (1ull << 31) &&   // 32-bit buffer offsets into a term slab
-        sweep_gs_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, c.gs) && (gs_on == 2 || ty.T == 1 || !fused_alone))
-        return c.is(SWEEP_GS);
-    // Fused form (dto_sweep_fused.hip): the whole series in one persistent launch, a workgroup per few intervals; single-column
-    // sweeps only in the 64-state generator-stationary instance.  Beside another stream's kernels the planner is asked again for
-    // the shape it takes there (a refusal would fall through to the cluster form; see sweep_with in do_jacobian).
-    if (fused_alone && (ty.T != 1 || c.fused.S64) &&
-        (!shared_chip || sweep_fused_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, c.fused, shared_chip)))
-        return c.is(c.fused.S64 ? SWEEP_S64 : SWEEP_FUSED);
-    // Row-split cluster form: where the single-workgroup form has too few interval groups for the chip -- short shards of 128-
-    // and 256-state problems (the 250-knot share of the 2000-knot metric on 8 GPUs).  Measured per Jacobian / Hessian,
-    // cluster against step per launch (tools/cluster_time.py): 256 x 250 2.12 / 2.02 against 2.22 / 2.04 ms, 128 x 250 0.74 /
-    // 1.02 against 0.93 / 1.18 ms.  NOT used where it measured slower: single-column sweeps (eval_constraint 0.94 against
-    // 0.62 ms at 250 knots, 1.52 against 1.45 at 2000: the rendezvous + slice exchange costs ~10 us per Taylor step, as much
-    // as the step's MFMA work there) and 512 / 1024 states (23.6 against 18.7 ms, 57 against 47 ms per Jacobian: the step
-    // launches tile the 2500 columns 32 wide, a cluster member is held to 16 by its LDS).
-    static const int cluster_on = tune_int("DTO_SWEEP_CLUSTER", 1);  // A/B runs (TUNING builds): 0 = never
-    static const int cluster_big = tune_int("DTO_SWEEP_CLUSTER_BIG", 0);  // 512 and 1024 states as well
-    static const int cluster_t1 = tune_int("DTO_SWEEP_CLUSTER_T1", 0);    // single-column sweeps too
-    if (cluster_on && (ty.T != 1 || cluster_t1) && (w.npad <= 256 || cluster_big) &&
-        sweep_cluster_plan(w.npad, b.k.m, ty, h->P.n_int, h->n_cu, c.cluster))
-        return c.is(SWEEP_CLUSTER);
-    return c;   // one launch per Taylor step: what remains, and the form for frozen p terms and the products' extra start vector
+    return dto::choose_sweep(SweepSituation{w.npad, w.Kpad, b.k.m, ty, h->P.n_int, h->n_cu, h->sweep_form, h->reuse, /*frozen=*/w.frozen != nullptr,
+                                            /*has_term_store=*/w.Zt != nullptr, w.dcap, plan.q, plan.d_ub, store, shared_chip, step_only});
 }
 
 // Does this sweep run in the 64-state generator-stationary form, which can read its step budget from device memory?  (No term
@@ -329,12 +230,8 @@ int run_sweep(dto_handle* h, BilHost& b, SweepBuf& w, const SweepTypes& ty, cons
         for (int t = w.frozen ? w.first_type : 0; t < ty.T; ++t) segs += b.k.m + 1;  // an extra term rides in the segment of its generator
         return 2.0 * b.k.npad * (double)b.k.npad * w.Kpad * segs;
     }();
-    // The termination test cannot fire early in the series: it is first run at step tc = d_ub/2 - 1 (d_ub comes from an
-    // upper bound on the terms needed at this very Z, so tc is a function of Z alone and results stay reproducible; a
-    // column block that would pass earlier merely adds a few terms below 1e-16 of its sum).
     static const int tc_env = tune_int("DTO_SWEEP_TC", -1);
-    int tc = tc_env >= 0 ? tc_env : (plan.tc >= 0 ? plan.tc : plan.d_ub / 2 - 1);
-    if (tc < 2) tc = 0;
+    const int tc = sweep_tc(plan, tc_env);   // first step of the termination test
     count_sweep_form(h, c.form);
     if (c.form != SWEEP_STEP) {
         // the one-launch forms: the whole series, termination tests included, in one persistent launch
@@ -644,37 +541,8 @@ void read_hump(dto_handle* h, BilHost& b) {
     }
 }
 SweepPlan plan_hump(const BilHost& b, double beta_fallback) {
-    static const double theta_v = tune_double("DTO_THETA_V", 9.0);
     static const bool on = tune_int("DTO_HUMP_PLAN", 1) != 0;
-    if (on && b.hump_valid)
-        for (int q = 1; q <= 4; ++q)
-            if (b.hump_logH[q - 1] <= theta_v) return SweepPlan{q, std::min(200, b.hump_kend[q - 1] + 6)};
-    return plan_sweep(beta_fallback);
-}
-
-// `loose`: the caller keeps no Taylor terms (eval_constraint without reuse_forward_sweep), so a generous step budget costs nothing --
-// the one-launch sweeps end by their own termination test.  Then the hump criterion is applied to the cheap bound itself
-// (max_k beta^k / k! <= e^9, the same four digits plan_hump allows): at the benchmark shape the triangle-inequality bound on
-// ||A^2||^(1/2) is 9.5, just past the beta <= 9 rule, and the exact norm (a store-less basis GEMM, a kernel for the hump and two
-// host round trips: 0.2 of the callback's 1.1 ms) was bought only to learn what this already shows.
-// The step budget the cheap generator-norm bound alone gives, where that is a single round (q = 1): no exact norm needed.
-bool cheap_plan(const Bounds& bd, bool loose, SweepPlan& out) {
-    out = plan_sweep(bd.beta);
-    if (out.q == 1) return true;  // the cheap bound already gives one round
-    if (loose && bd.beta == bd.beta && bd.beta < 40.0) {
-        double lh = 0.0;
-        for (int k = 1; k < 200; ++k) lh = std::max(lh, k * std::log(bd.beta) - std::lgamma(k + 1.0));
-        if (lh <= 9.0) {   // (the literal e^9, where plan_sweep and plan_hump read DTO_THETA_V: they differ in TUNING builds that set it)
-            SweepPlan p{1, taylor_budget(bd.beta)};
-            // the terms of the series grow up to index ~beta and fall from there: the test (two successive terms below 1.1e-16 of the
-            // sum, Al-Mohy & Higham's own criterion, which they apply from the first term on) starts a few terms past the peak
-            // of the BOUND -- a function of Z alone, like d_ub / 2 - 1, but not inflated by the bound's slack in the tail
-            p.tc = std::min(p.d_ub / 2 - 1, std::max(2, (int)std::ceil(bd.beta) + 4));
-            out = p;
-            return true;
-        }
-    }
-    return false;
+    return dto::plan_hump(on && b.hump_valid, b.hump_logH, b.hump_kend, sweep_theta_v(), beta_fallback);
 }
 
 SweepPlan plan_from(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st, bool loose = false) {
@@ -686,7 +554,7 @@ SweepPlan plan_from(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st,
     // pass was 1.4 of the 6.4 ms the exact norms cost a Hessian or an eval_constraint there)
     const bool straight = b.use_basis && bd.beta == bd.beta && bd.beta > 22.5;
     double d2 = exact_d2(h, b, dZ, st, straight);
-    auto plan = [&] { return plan_hump(b, d2 == d2 ? std::min(bd.beta, d2) : d2); };
+    auto plan = [&] { return plan_hump(b, growth_rate(bd.beta, d2)); };
     if (!straight && d2 == d2 && plan().q > 1 && b.use_basis) d2 = exact_d2(h, b, dZ, st, true);  // ||A^3||, ||A^4|| sharpen the bound
     return plan();
 }
@@ -1077,7 +945,7 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                 // ||A^t|| <= ||A^2||^floor(t/2) ||A||^(t mod 2): the exact d2 of the chain is the sharper
                 // (and still rigorous) growth rate for the sweep's step budget
                 if (swept) return;
-                const SweepPlan from_chain = plan_hump(b, d2 == d2 ? std::min(bd.beta, d2) : d2);
+                const SweepPlan from_chain = plan_hump(b, growth_rate(bd.beta, d2));
                 if (h->reuse)   // a Hessian at this very point need not buy the norms again
                     for (int i = 0; i < n_members; ++i) members[i]->cache.chain_planned(from_chain.q, from_chain.d_ub);
                 sweep_with(from_chain);

@@ -6,28 +6,9 @@
 
 #include <cstdlib>
 
-namespace dto {
+#include "dto_sweep_plan.h"   // sweep planning: step budget, launch shapes (SweepTypes, the *SweepPlan structs and planners), form choice
 
-// Tuning switches for A/B measurements exist only in builds with -DDTO_TUNING (`make TUNING=1`); the product
-// library reads no environment variable.
-inline int tune_int(const char* name, int dflt) {
-#ifdef DTO_TUNING
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-#else
-    (void)name;
-    return dflt;
-#endif
-}
-inline double tune_double(const char* name, double dflt) {
-#ifdef DTO_TUNING
-    const char* e = getenv(name);
-    return e ? atof(e) : dflt;
-#else
-    (void)name;
-    return dflt;
-#endif
-}
+namespace dto {
 
 constexpr int TAYLOR_M = 16;                 // degree of the matrix Taylor polynomial
 constexpr double THETA_16 = 0.78028743;      // backward-error radius of T_16 in double (Al-Mohy & Higham 2011, Table 3.1 method)
@@ -61,7 +42,6 @@ constexpr double EXPM3_E[5] = {-0.0814706004657684, 0.10462167443095102, 0.00829
 constexpr double EXPM3_AL = 0.009959087291030108, EXPM3_BE = 3.6322128429901483;
 static_assert(EXPM3_A[4] == 0.0 && EXPM3_C[4] == 0.0 && EXPM3_D[4] == 0.0, "the second product's epilogue does not read A^4");
 constexpr int PAIR_DCAP = 80;               // Taylor terms the Hessian's pairing path can store per sweep (rows / columns of its Beta table)
-constexpr int MAX_TYPES = 36;                // column types of a generator sweep (p, d^i, h^{ij})
 constexpr int MAX_DRIVES = 7;
 
 // Problem-level constants every kernel may need.
@@ -136,18 +116,6 @@ __host__ __device__ inline int64_t hess_pos(const KProb& P, int64_t kn, int a, i
         colstart = tri + (kn - 1) * (z * z + tri) + (int64_t)b * z + (int64_t)b * (b + 1) / 2 + z;
     return colstart + a - P.hess_lo;
 }
-
-struct TypeDesc {     // one column type of a generator sweep
-    int32_t n_extra;  // extra segments G_gen * Z_src * scaleE * mult
-    int32_t gen[2];
-    int32_t src[2];
-    double mult[2];
-};
-
-struct SweepTypes {
-    int32_t T;
-    TypeDesc t[MAX_TYPES];
-};
 
 // ------------------------------------------------------------------ launch wrappers (dto_kernels.hip)
 struct ChainWork {   // per-chunk workspace of the propagator chain: C matrices npad x npad each
@@ -238,35 +206,22 @@ void launch_jtv_bilinear(hipStream_t st, const KProb& P, const KBil& B, const Sw
 void launch_jv_derivative(hipStream_t st, const KProb& P, const KDer& D, const double* dZ, const double* w, double* y, int transpose);
 
 // ---- the whole sweep in one persistent launch (dto_sweep_fused.hip): a workgroup owns `ipw` intervals, all rows, all types
-struct FusedSweepPlan {
-    int MT, NT, ipw, nslot, nblocks;
-    int WC = 1;  // column groups of wavefronts (4 WC wavefronts per workgroup), NT column tiles per group
-    int WK = 1;  // 2: two wavefronts per SIMD split the K loop of a wave tile (256 states)
-    int S64 = 0; // 1: the generator-stationary 64-state form (k_sweep_s64), NX = most inhomogeneous sources of a column type
-    int NX = 0;
-    size_t lds_bytes;
-};
+// (FusedSweepPlan and sweep_fused_plan: dto_sweep_plan.h)
 hipError_t sweep_fused_prepare();  // per-device opt-in to the kernels' dynamic LDS (dto_create)
-bool sweep_fused_plan(int npad, int m, const SweepTypes& ty, int64_t n_int, int n_cu, FusedSweepPlan& out, bool shared_chip = false);
 // Runs q rounds of at most d_ub Taylor steps (termination test from step tc on, per workgroup), terms into w.Zt (store) or
 // ping-pong w.Z[0/1], sums into w.S, scale factors into w.scale*, valid term counts into w.nterms[workgroup],
 // w.stats[0] += workgroups that did not converge, w.stats[1] = max terms used (the caller zeroes w.stats).
 hipError_t launch_sweep_fused(hipStream_t st, const KProb& P, const KBil& B, const SweepBuf& w, const SweepTypes& ty,
                               const FusedSweepPlan& pl, const double* dZ, const double* dmu, int src_kind, int transposed,
                               int q, int d_ub, int tc, bool store, double tol, const int32_t* plan_dev = nullptr);
-// {q, d_ub, tc} of a sweep from the norm bound (bit pattern in bounds[0]), computed on the device: launch_sweep_fused(..., plan_dev)
+// {q, d_ub, tc} of a sweep from the norm bound (bit pattern in bounds[0]), computed on the device by device_plan (dto_sweep_plan.h) with
+// the host's theta_v: launch_sweep_fused(..., plan_dev)
 void launch_plan_dev(hipStream_t st, const unsigned long long* bounds, int32_t* out);
 
 // ---- the same sweep with the rows of the matrix split over a cluster of R workgroups that exchange their slices of every new
 // term through global memory (dto_sweep_fused.hip): short shards, single-column sweeps, 512+ states
-struct ClusterSweepPlan {
-    int MT, NT, R, ipw, n_groups, n_clusters, nblocks;
-    size_t lds_bytes;
-    double step_us;  // the cost model's time per Taylor step and round of clusters
-};
+// (ClusterSweepPlan, sweep_cluster_plan and sweep_cluster_workspace_doubles: dto_sweep_plan.h)
 hipError_t sweep_cluster_prepare();
-bool sweep_cluster_plan(int npad, int m, const SweepTypes& ty, int64_t n_int, int n_cu, ClusterSweepPlan& out);
-size_t sweep_cluster_workspace_doubles(int npad, const ClusterSweepPlan& pl);
 hipError_t launch_sweep_cluster(hipStream_t st, const KProb& P, const KBil& B, const SweepBuf& w, const SweepTypes& ty,
                                 const ClusterSweepPlan& pl, double* X, unsigned* arrive, const double* dZ, const double* dmu,
                                 int src_kind, int transposed, int q, int d_ub, int tc, bool store, double tol);
@@ -274,14 +229,8 @@ hipError_t launch_sweep_cluster(hipStream_t st, const KProb& P, const KBil& B, c
 // ---- the sweep with the generators STATIONARY in registers (dto_sweep_gs.hip, round 4): a cluster of npad / 32 workgroups shares an
 // interval group, each member holding 32 rows of every generator for the whole launch; only the term slices move (through the
 // sweep's own term slabs, sc1 on both sides).  128 and 256 states, at most 4 drives, no sub-stepping (q = 1).
-struct GsSweepPlan {
-    int KU, MP, NT, ipw, has_src, n_groups, n_clusters, nblocks, cap;
-    size_t lds_bytes;
-    double term_us;  // the cost model's time per Taylor term
-};
+// (GsSweepPlan, sweep_gs_plan and sweep_gs_norm_doubles, the exchange slab of the partial column norms: dto_sweep_plan.h)
 hipError_t sweep_gs_prepare();
-bool sweep_gs_plan(int npad, int m, const SweepTypes& ty, int64_t n_int, int n_cu, GsSweepPlan& out);
-size_t sweep_gs_norm_doubles(const GsSweepPlan& pl);   // exchange slab of the partial column norms
 // arrive: n_groups (rounded up to 4) counters, zeroed by the launch; terms into w.Zt (store) or ping-pong w.Z[0/1], sums into w.S,
 // valid term counts into w.nterms[group], w.stats as launch_sweep_fused
 hipError_t launch_sweep_gs(hipStream_t st, const KProb& P, const KBil& B, const SweepBuf& w, const SweepTypes& ty, const GsSweepPlan& pl,

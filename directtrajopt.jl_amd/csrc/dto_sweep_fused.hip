@@ -52,27 +52,7 @@ struct FusedSweepArgs {
 
 constexpr int PF = 4;  // k-steps (of 4) the A fragments are loaded ahead
 
-// LDS carve-up shared by host and device
-struct FusedLds {
-    int zs, scr, cg, se, tn, sn, xn, xg, xs, xm, flag, total;  // offsets in doubles
-    __host__ __device__ FusedLds(int npad, int T, int m, int ipw, int nslot, int MT) {
-        const int NC = T * ipw, ZS = npad + 2;
-        (void)nslot; (void)MT;
-        int o = 0;
-        zs = o; o += NC * ZS + 40; // the B-fragment prefetch runs up to two groups of four k-steps past the last column (K split)
-        scr = o;
-        cg = o; o += (m + 1) * ipw;
-        se = o; o += ipw;
-        tn = o; o += 3 * NC;
-        sn = o; o += NC;
-        xm = o; o += 2 * T;
-        xn = o; o += (T + 1) / 2;          // ints, two per double
-        xg = o; o += T;                    // 2 ints per type
-        xs = o; o += T;
-        flag = o; o += 2;
-        total = o;
-    }
-};
+// (the LDS carve-up shared by host and device: FusedLds, dto_sweep_plan.h)
 
 // npad == 64 MT: one row pass of the four wavefronts covers the matrix.  The sums live in registers and the new term goes
 // from the accumulators straight into the LDS columns; global memory sees the terms only in store mode and the sums once,
@@ -543,24 +523,7 @@ __global__ void __launch_bounds__(256 * WC * WK, WC * WK) k_sweep_fused(FusedSwe
 //                (t, t+1) runs there -- after the partial products of term t+2 were formed, before anything of them is used:
 //                same sums, same term count as the other forms, one wasted product per workgroup.
 // Bound: FP64 MFMA, 80 per wavefront and term (5120 cycles) + ~1000 cycles of everything else.
-struct S64Lds {
-    static constexpr int ZS = 66;   // column pitch: the B-fragment reads of a half-wave fall on 32 distinct 8-byte banks
-    int zs, pb, cg, se, tn, sn, xm, xn, xg, xs, total;  // offsets in doubles
-    __host__ __device__ S64Lds(int T, int m, int ipw) {
-        int o = 0;
-        zs = o; o += 16 * ZS;
-        pb = o; o += 2 * 4 * 4 * 2 * 64 * 2;   // [term parity][row tile][source wavefront][half][lane] 16 bytes
-        cg = o; o += (m + 1) * ipw;
-        se = o; o += ipw;
-        tn = o; o += 4 * 16;
-        sn = o; o += 4 * 16;
-        xm = o; o += 2 * T;
-        xn = o; o += (T + 1) / 2;   // ints, two per double
-        xg = o; o += T;
-        xs = o; o += T;
-        total = o;
-    }
-};
+// (the LDS carve-up: S64Lds, dto_sweep_plan.h)
 
 // Column norms travel as the HIGH WORD of |v| (non-negative doubles order like their bit patterns, a NaN's exceeds every
 // finite one): the norm is rounded down by at most 2^-20 of itself, which the termination test does not notice, and the
@@ -1314,7 +1277,7 @@ hipError_t prepare_one(int bytes) {
 }  // namespace
 
 hipError_t sweep_fused_prepare() {
-    const int bytes = 160 * 1024;
+    const int bytes = (int)SWEEP_LDS_OPT_IN;
     hipError_t e = hipSuccess;
 #define DTO_PREP(MT, NT) if (e == hipSuccess) e = prepare_one<MT, NT>(bytes)
     DTO_PREP(4, 1); DTO_PREP(4, 2); DTO_PREP(4, 3);
@@ -1331,94 +1294,7 @@ hipError_t sweep_fused_prepare() {
     return e;
 }
 
-// Shape of the launch for a sweep over T column types of an integrator padded to npad states, n_int intervals:
-// intervals per workgroup (ipw) and tile counts.  Returns false when the fused form does not apply.
-bool sweep_fused_plan(int npad, int m, const SweepTypes& ty, int64_t n_int, int n_cu, FusedSweepPlan& out, bool shared_chip) {
-    const int T = ty.T;
-    if (T < 1 || n_int <= 0) return false;
-    // One row pass must cover the matrix (npad = 64, 128 or 256: 4 wavefronts x 16 MT rows).  Larger matrices offer their
-    // parallelism in the ROW dimension, which a workgroup-per-interval-group form cannot use without exchanging the term
-    // columns between workgroups every step: there the step-per-launch sweep is faster (measured: 512 states 19.0 against
-    // 22.6 ms, 1024 states 109 against 128 ms per Jacobian), as it is when the intervals are too few to give half the CUs a
-    // workgroup (256 states x 200 knots: 2.25 against 2.50 ms).
-    if (npad != 64 && npad != 128 && npad != 256) return false;
-    const int MT = npad / 64;
-    int nslot = 0;
-    for (int g = 0; g <= m; ++g) {
-        int mask = 0;
-        for (int t = 0; t < T; ++t)
-            for (int x = 0; x < ty.t[t].n_extra; ++x)
-                if (ty.t[t].gen[x] == g) mask |= 1 << ty.t[t].src[x];
-        nslot = nslot > __builtin_popcount(mask) ? nslot : __builtin_popcount(mask);
-    }
-    // cost model, 256 states: one workgroup per CU and round; a round takes NT units of MFMA time, and a narrow column tile
-    // streams the generators from L2 at 512 / (16 NT) bytes per cycle and CU, which at NT = 1 is more than a CU sustains.
-    // 64 and 128 states: the steps are latency-bound (two barriers and an epilogue per handful of MFMAs), several workgroups
-    // share a CU, and one column tile per workgroup is fastest -- measured per sweep at 1000 knots, NT = 1 / 2 / 3:
-    // 0.24 / 0.30 / 0.44 ms (64 states), 0.61 / 0.73 / 0.86 ms (128 states); three workgroups per CU count as one round.
-    // 64 states, at most 16 columns per interval: the generator-stationary form, as many intervals as a 16-column tile holds
-    // (measured per 1000-knot Jacobian sweep: see DESIGN.md section 4)
-    static const int s64_env = tune_int("DTO_SWEEP_S64", 1);
-    if (npad == 64 && s64_env && m + 1 <= 5 && T <= 16) {
-        int nx = 0;
-        for (int t = 0; t < T; ++t) nx = nx > ty.t[t].n_extra ? nx : ty.t[t].n_extra;
-        // a workgroup's Taylor step costs the same for 1 or 16 live columns, so few intervals are spread over the CUs first
-        // (one round of workgroups) and only then packed into the tile
-        // (beside another kernel -- the Hessian's forward column next to its adjoint sweep -- the CU time is what counts: full tiles)
-        int ipw = shared_chip ? 16 / T : (int)((n_int + n_cu - 1) / n_cu);
-        ipw = ipw < 1 ? 1 : (ipw > 16 / T ? 16 / T : ipw);
-        const long nblocks = (long)((n_int + ipw - 1) / ipw);
-        if (nx <= 2) {
-            out.MT = 1; out.NT = 1; out.WC = 1; out.WK = 1; out.ipw = ipw; out.nslot = nslot; out.nblocks = (int)nblocks;
-            out.S64 = 1; out.NX = nx;
-            out.lds_bytes = (size_t)S64Lds(T, m, ipw).total * sizeof(double);
-            return true;
-        }
-    }
-    out.S64 = 0;
-    static const double l2_factor[4] = {0.0, 1.6, 1.15, 1.0};
-    static const double t_small[2][4] = {{0.0, 0.24, 0.30, 0.44}, {0.0, 0.61, 0.73, 0.86}};
-    static const int ipw_env = tune_int("DTO_SWEEP_IPW", 0);  // A/B runs (TUNING builds)
-    auto search = [&](int WC) {
-        bool found = false;
-        double best = 0.0;
-        for (int ipw = 1; ipw <= 48; ++ipw) {
-            const int NC = T * ipw;
-            int NT = (NC + 15) / 16;
-            if (WC == 2) {
-                if (NT > 4) break;
-                if (NT != 4) continue;  // two column groups of two tiles each
-                NT = 2;
-            } else if (NT > 3) break;
-            if (ipw_env > 0 && ipw != ipw_env && T == 1 + m) continue;
-            const FusedLds L(npad, T, m, ipw, nslot, MT);
-            const size_t bytes = (size_t)L.total * sizeof(double);
-            if (bytes > 156 * 1024) break;
-            const long nblocks = (long)((n_int + ipw - 1) / ipw);
-            const long slots = MT <= 2 ? 3L * n_cu : n_cu;
-            const long rounds = (nblocks + slots - 1) / slots;
-            // ties go to the fewer workgroups (less MFMA work issued in total)
-            const double cost = (MT <= 2 ? (double)rounds * t_small[MT - 1][NT] : (double)rounds * NT * l2_factor[NT]) + 1e-6 * (double)nblocks * NT;
-            if (!found || cost < best) {
-                found = true; best = cost;
-                out.MT = MT; out.NT = NT; out.WC = WC; out.ipw = ipw; out.nslot = nslot; out.lds_bytes = bytes; out.nblocks = (int)nblocks;
-            }
-        }
-        return found && 2 * out.nblocks >= n_cu;
-    };
-    // Eight wavefronts in two column groups (256 states, 49..64 columns: 12 intervals of a Jacobian sweep per workgroup): two
-    // wavefronts per SIMD hide each other's operand traffic, +10 % MFMA rate per CU -- but a third fewer workgroups, each a
-    // fifth longer (256 x 2000: 167 workgroups, 4.0 ms against 223, 3.3 ms).  It pays when the CUs the sweep leaves free are
-    // used by another stream (`shared_chip`: the Jacobian's sweep next to the propagator chain), not when the sweep runs alone.
-    static const int wk_env = tune_int("DTO_SWEEP_WK", 2);  // A/B runs (TUNING builds): 1 = one wave per SIMD as up to round 3
-    out.WK = 1;
-    if (shared_chip && npad == 256 && search(2)) return true;
-    if (!search(1)) return false;
-    if (npad == 256 && out.WC == 1 && wk_env == 2) out.WK = 2;   // two waves per SIMD splitting the K loop
-    return true;
-}
-
-// ---- row-split cluster form: plan, workspace, launch
+// ---- row-split cluster form: launch (its plan and workspace size: dto_sweep_plan.h)
 namespace {
 template <int MT, int NT, int R>
 hipError_t launch_cluster_one(hipStream_t st, const ClusterArgs& a, int nblocks, size_t lds) {
@@ -1433,7 +1309,7 @@ hipError_t prepare_cluster_one(int bytes) {
 }  // namespace
 
 hipError_t sweep_cluster_prepare() {
-    const int bytes = 160 * 1024;
+    const int bytes = (int)SWEEP_LDS_OPT_IN;
     hipError_t e = hipSuccess;
 #define DTO_PREPC(MT, NT, R) if (e == hipSuccess) e = prepare_cluster_one<MT, NT, R>(bytes)
     DTO_PREPC(1, 1, 2); DTO_PREPC(1, 2, 2); DTO_PREPC(1, 3, 2);   // 128 states
@@ -1444,56 +1320,6 @@ hipError_t sweep_cluster_prepare() {
     DTO_PREPC(4, 1, 4);                                           // 1024 states over 4
 #undef DTO_PREPC
     return e;
-}
-
-// Shape of the cluster launch: R members per interval group, NT column tiles (ipw = 16 NT / T intervals per group), as many
-// clusters as the chip holds with ONE workgroup per CU (a multiple of 8, one per XCD and slot); each cluster walks the groups
-// cluster, cluster + n_clusters, ...  Cost model per Taylor step, in MFMA units of one 16-column tile over 64 MT rows: the
-// tile count times the same L2 factor as the single-workgroup form (a narrow tile streams the generators faster than a CU
-// takes them in) plus the exchange (rendezvous + slice traffic), which does not shrink with the tile.
-bool sweep_cluster_plan(int npad, int m, const SweepTypes& ty, int64_t n_int, int n_cu, ClusterSweepPlan& out) {
-    const int T = ty.T;
-    if (T < 1 || n_int <= 0 || n_cu < 16) return false;
-    static const double l2_factor[4] = {0.0, 1.6, 1.15, 1.0};
-    static const int force_r = tune_int("DTO_CLUSTER_R", 0), force_nt = tune_int("DTO_CLUSTER_NT", 0);
-    bool found = false;
-    double best = 0.0;
-    for (int R = 2; R <= 4; R += 2) {
-        if (npad % (64 * R) != 0) continue;
-        const int MT = npad / (64 * R);
-        if (MT != 1 && MT != 2 && MT != 4) continue;
-        if (force_r && R != force_r) continue;
-        for (int NT = 1; NT <= 3; ++NT) {
-            if (force_nt && NT != force_nt) continue;
-            const int ipw = (16 * NT) / T;
-            if (ipw < 1) continue;
-            if (NT > 1 && (16 * (NT - 1)) / T == ipw) continue;  // the narrower shape holds as many intervals
-            if (NT == 3 || (MT == 4 && NT > 1)) continue;  // three-tile shapes and 256 rows x 2 tiles spill beside the exchange registers
-            const FusedLds L(npad, T, m, ipw, 0, MT);
-            size_t bytes = (size_t)L.total * sizeof(double);
-            if (bytes > 156 * 1024) continue;
-            if (bytes < 82 * 1024) bytes = 82 * 1024;   // more than half a CU's LDS: one workgroup per CU (the hand-off's condition)
-            const long n_groups = (long)((n_int + ipw - 1) / ipw);
-            long n_clusters = ((long)(n_cu / R) / 8) * 8;
-            if (n_clusters > ((n_groups + 7) / 8) * 8) n_clusters = ((n_groups + 7) / 8) * 8;
-            if (n_clusters < 8) continue;
-            const long rounds = (n_groups + n_clusters - 1) / n_clusters;
-            const double step_us = MT * NT * l2_factor[NT] * (m + 1) * npad * 7.3e-3;   // 64 cycles per MFMA at 2.2 GHz
-            const double exch_us = 3.0 + 16.0 * NT * npad * 8.0 * 1e-3 / 60.0;           // rendezvous + slices at ~60 GB/s per CU
-            const double cost = rounds * (step_us + exch_us);
-            if (!found || cost < best) {
-                found = true; best = cost;
-                out.MT = MT; out.NT = NT; out.R = R; out.ipw = ipw; out.n_groups = (int)n_groups; out.n_clusters = (int)n_clusters;
-                out.nblocks = (int)(n_clusters * R); out.lds_bytes = bytes; out.step_us = step_us + exch_us;
-            }
-        }
-    }
-    return found;
-}
-
-size_t sweep_cluster_workspace_doubles(int npad, const ClusterSweepPlan& pl) {
-    const size_t NCP = 16 * (size_t)pl.NT;
-    return (size_t)pl.n_clusters * 2 * (NCP * npad + 8 * NCP);
 }
 
 hipError_t launch_sweep_cluster(hipStream_t st, const KProb& P, const KBil& B, const SweepBuf& w, const SweepTypes& ty,
@@ -1528,42 +1354,16 @@ hipError_t launch_sweep_cluster(hipStream_t st, const KProb& P, const KBil& B, c
     return hipErrorInvalidValue;
 }
 
-// The step budget of a sweep from the cheap norm bound alone, on the device (one lane): the host's cheap_plan(loose) where it gives a
-// single round, else its plan_sweep -- same formulas, same constants (dto_engine.cpp), so the numbers are those a host that waited
-// for the bound would have used.  out = {q, d_ub, tc}.
-__global__ void k_plan_dev(const unsigned long long* __restrict__ bounds, int32_t* __restrict__ out) {
-    const double beta = __longlong_as_double((long long)bounds[0]);
-    auto budget = [](double br) {
-        int t = 8;
-        double term = 1.0;
-        for (int i = 1; i <= t; ++i) term *= br / i;
-        while (term > 1e-19 && t < 200) { ++t; term *= br / t; }
-        return t + 6;
-    };
-    int q = 1, d_ub = 30, tc = -1;
-    if (beta == beta && beta <= 1e6) {
-        q = (int)ceil(beta / 9.0);
-        if (q < 1) q = 1;
-        d_ub = budget(beta / q);
-        if (q > 1 && beta < 40.0) {
-            // the hump criterion on the bound itself: max_k beta^k / k! <= e^9 (the maximum sits at k = floor(beta) or next to it)
-            double lh = 0.0;
-            const int k0 = (int)floor(beta);
-            for (int k = (k0 > 1 ? k0 - 1 : 1); k <= k0 + 1; ++k) lh = fmax(lh, k * log(beta) - lgamma(k + 1.0));
-            if (lh <= 9.0) {
-                q = 1;
-                d_ub = budget(beta);
-                const int a0 = d_ub / 2 - 1, a1 = (int)ceil(beta) + 4;
-                tc = a0 < (a1 > 2 ? a1 : 2) ? a0 : (a1 > 2 ? a1 : 2);
-            }
-        }
-    }
-    if (tc < 0) tc = d_ub / 2 - 1;
-    if (tc < 2) tc = 0;
-    out[0] = q; out[1] = d_ub; out[2] = tc;
+// The step budget of a sweep from the cheap norm bound alone, on the device (one lane): device_plan (dto_sweep_plan.h), the very
+// functions the host runs -- cheap_plan(loose) where it gives a single round, else plan_sweep -- so the numbers are those a host that
+// waited for the bound would have used.  theta_v is the host's (9.0 in the product build; in TUNING builds the device plan follows
+// DTO_THETA_V as the host's plans do, where it used to keep the literal 9).  out = {q, d_ub, tc}.
+__global__ void k_plan_dev(const unsigned long long* __restrict__ bounds, int32_t* __restrict__ out, double theta_v) {
+    const SweepPlan p = device_plan(__longlong_as_double((long long)bounds[0]), theta_v);
+    out[0] = p.q; out[1] = p.d_ub; out[2] = p.tc;
 }
 void launch_plan_dev(hipStream_t st, const unsigned long long* bounds, int32_t* out) {
-    hipLaunchKernelGGL(k_plan_dev, dim3(1), dim3(1), 0, st, bounds, out);
+    hipLaunchKernelGGL(k_plan_dev, dim3(1), dim3(1), 0, st, bounds, out, sweep_theta_v());
 }
 
 hipError_t launch_sweep_fused(hipStream_t st, const KProb& P, const KBil& B, const SweepBuf& w, const SweepTypes& ty,

@@ -99,23 +99,7 @@ struct GsArgs {
 #endif
 constexpr int GS_AUX_SC1 = 16;  // raw_buffer aux bit: sc1 (agent-scope: write-through stores, L1-bypassing loads)
 
-// LDS carve-up shared by host and device (doubles)
-struct GsLds {
-    int slot, nmax, tyt, colt, gct, flag, cgt, total;   // total: without the coefficient table [(MP + 1)][cap] that follows at cgt
-    __host__ __device__ constexpr GsLds(int KU, int MP, int NT) : slot(0), nmax(0), tyt(0), colt(0), gct(0), flag(0), cgt(0), total(0) {
-        const int NPAD = 32 * KU, ZS = NPAD + 2, NCP = 16 * NT;
-        (void)MP;
-        slot = NCP * ZS + 8;            // one column slot (also the scratch of the partial tiles [4][NCP][32]); two of them
-        int o = 2 * slot;
-        nmax = o; o += 2 * 3 * NCP;     // [2][3][NCP] cluster-wide column norms: term t-1, term t, sum (bit patterns)
-        tyt = o; o += 5 * MAX_TYPES;    // per column type: multipliers [2] (doubles), then n_extra, generators [2], sources [2] (ints)
-        colt = o; o += NCP;             // per column: {offset of the column inside a term slab for interval group 0, interval within the group} (ints)
-        gct = o; o += MP * NCP + (MP * NCP + 1) / 2;   // per (generator, column): multiplier of the inhomogeneous term (0: none), its source column (ints)
-        flag = o; o += 2;               // ints: [0] a rendezvous timed out
-        cgt = o;                        // [(MP + 1)][cap]: dt ubar_g of every interval of the cluster (row MP: dt), built once
-        total = o;
-    }
-};
+// (the LDS carve-up shared by host and device: GsLds and gs_lds_bytes, dto_sweep_plan.h)
 
 // KU = npad / 32 = members per cluster; a wavefront holds KW = 2 KU k-steps of every generator; MP >= m + 1 generator slots (absent
 // ones are zero); NT column tiles per group (two column slots in LDS: NT <= 2 at 256 states); HAS_SRC: some column type has an
@@ -659,12 +643,6 @@ hipError_t gs_prepare_one(int bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep_gs<KU, MP, NT, HAS_SRC>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-size_t gs_lds_bytes(int KU, int MP, int NT, int cap) {
-    size_t bytes = ((size_t)GsLds(KU, MP, NT).total + (size_t)(MP + 1) * cap) * sizeof(double);
-    if (bytes < 82 * 1024) bytes = 82 * 1024;   // more than half a CU's LDS: one workgroup per CU (the hand-off's condition)
-    return bytes;
-}
-
 }  // namespace
 
 #ifdef GS_STAMP
@@ -672,7 +650,7 @@ static unsigned long long* gs_stamp_buffer = nullptr;
 #endif
 
 hipError_t sweep_gs_prepare() {
-    const int bytes = 160 * 1024;
+    const int bytes = (int)SWEEP_LDS_OPT_IN;
     hipError_t e = hipSuccess;
 #define DTO_PREPG(KU, MP, NT) \
     if (e == hipSuccess) e = gs_prepare_one<KU, MP, NT, false>(bytes); \
@@ -682,53 +660,6 @@ hipError_t sweep_gs_prepare() {
 #undef DTO_PREPG
     return e;
 }
-
-// Shape of the launch: KU = npad / 32 members per cluster, as many clusters as the chip holds with one workgroup per CU (a multiple
-// of 8: one per XCD and slot), NT column tiles per group (ipw = 16 NT / T intervals), each cluster walking the groups cluster,
-// cluster + n_clusters, ... round-robin.  Cost per Taylor term: rounds x (product + collect / reduce / publish), in us.
-bool sweep_gs_plan(int npad, int m, const SweepTypes& ty, int64_t n_int, int n_cu, GsSweepPlan& out) {
-    const int T = ty.T;
-    if (T < 1 || n_int <= 0) return false;
-    if (npad != 256 && npad != 128) return false;   // clusters of 8 / 4 members of 32 rows each
-    if (m + 1 > 5) return false;
-    const int KU = npad / 32, R = KU;
-    bool has_src = false;
-    for (int t = 0; t < T; ++t) {
-        if (ty.t[t].n_extra > 2) return false;
-        if (ty.t[t].n_extra > 0) has_src = true;
-    }
-    static const int force_nt = tune_int("DTO_GS_NT", 0);
-    bool found = false;
-    double best = 0.0;
-    for (int NT = 1; NT <= 2; ++NT) {
-        if (force_nt && NT != force_nt) continue;
-        const int ipw = (16 * NT) / T;
-        if (ipw < 1) continue;
-        const long n_groups = (long)((n_int + ipw - 1) / ipw);
-        long n_clusters = ((long)(n_cu / R) / 8) * 8;
-        if (n_clusters > ((n_groups + 7) / 8) * 8) n_clusters = ((n_groups + 7) / 8) * 8;
-        if (n_clusters < 8) continue;
-        const long rounds = (n_groups + n_clusters - 1) / n_clusters;
-        if (rounds > 64) continue;
-        const int MPs = m + 1 <= 3 ? 3 : 5;
-        const int cap = (int)(rounds * ipw);
-        if (gs_lds_bytes(KU, MPs, NT, cap) > 160 * 1024) continue;
-        const double prod_us = 2.0 * NT * (m + 1) * 2 * KU * 64.0 / 2200.0;   // MFMAs per wave x 64 cycles at 2.2 GHz
-        const double fix_us = rounds > 1 ? 3.5 : 9.0;   // reduce + publish; a lone group per cluster also exposes its rendezvous and collect
-        // (the two-tile instance with source terms at 4 drives is the one the register file cannot quite hold: 35 spilled registers,
-        // measured 7 % slower per column than the one-tile instance)
-        const double cost = rounds * (prod_us + fix_us) * (has_src && NT == 2 && MPs == 5 ? 1.08 : 1.0);
-        if (!found || cost < best) {
-            found = true; best = cost;
-            out.KU = KU; out.MP = m + 1 <= 3 ? 3 : 5; out.NT = NT; out.ipw = ipw; out.has_src = has_src ? 1 : 0;
-            out.n_groups = (int)n_groups; out.n_clusters = (int)n_clusters; out.nblocks = (int)(n_clusters * R);
-            out.cap = cap; out.lds_bytes = gs_lds_bytes(KU, out.MP, NT, cap); out.term_us = cost;
-        }
-    }
-    return found;
-}
-
-size_t sweep_gs_norm_doubles(const GsSweepPlan& pl) { return (size_t)pl.n_groups * 3 * pl.KU * 2 * 16 * pl.NT; }
 
 hipError_t launch_sweep_gs(hipStream_t st, const KProb& P, const KBil& B, const SweepBuf& w, const SweepTypes& ty, const GsSweepPlan& pl,
                            double* Xn, unsigned* arrive, const double* dZ, const double* dmu, int src_kind, int transposed, int d_ub,

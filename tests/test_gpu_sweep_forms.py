@@ -1,6 +1,6 @@
 """GPU: the form every generator sweep takes, and every instance of the two forms that hand data between workgroups.
 
-`run_sweep` (csrc/dto_engine.cpp) runs a sweep in the form `choose_sweep` picked, one of five, and counts it (dto_profile_get "sweep_gs",
+`run_sweep` (csrc/dto_engine.cpp) runs a sweep in the form `choose_sweep` (csrc/dto_sweep_plan.h) picked, one of five, and counts it (dto_profile_get "sweep_gs",
 "sweep_fused", "sweep_s64", "sweep_cluster", "sweep_step"): generator-stationary (k_sweep_gs, csrc/dto_sweep_gs.hip), fused
 (k_sweep_fused), the 64-state fused form (k_sweep_s64), row-split cluster (k_sweep_cluster) and one launch per Taylor step
 (k_sweep).  Every case below asserts, per callback, the form through those counters (the other forms 0), compares eval_constraint,
@@ -250,7 +250,7 @@ def test_cluster_instances(R, NT):
 # ---- long horizons
 
 def _gs_lds_bytes(KU, MP, NT, cap):
-    """gs_lds_bytes of dto_sweep_gs.hip: the GsLds carve-up (doubles) and the coefficient table [(MP + 1)][cap]."""
+    """gs_lds_bytes of dto_sweep_plan.h: the GsLds carve-up (doubles) and the coefficient table [(MP + 1)][cap]."""
     ncp, zs, max_types = 16 * NT, 32 * KU + 2, 36
     total = 2 * (ncp * zs + 8) + 2 * 3 * ncp + 5 * max_types + ncp + MP * ncp + (MP * ncp + 1) // 2 + 2
     return max((total + (MP + 1) * cap) * 8, 82 * 1024)
