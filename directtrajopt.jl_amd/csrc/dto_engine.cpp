@@ -4,6 +4,7 @@
 // propagator chain, the callbacks, the transfer plans, the extern "C" entry points other than dto_create, the communicator and
 // profiling.  There is NO CPU fallback: every evaluation runs on the GPU or fails with an error code.
 #include "dto_handle.h"
+#include "dto_rollout_plan.h"
 
 #include <chrono>
 #include <cmath>
@@ -72,7 +73,11 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19 };
+// CAT_ROLLOUT .. CAT_ROLLOUT_DESCENT ("rollout" = its parts "rollout_gather" + "rollout_tree" + "rollout_descent"): the gather, the
+// tree's products and the descent (with the start and the copy into the caller's layout) of dto_rollout[_dev], flops as executed with
+// padding; the tree's products run launch_bgemm_plain and count HERE, not under "bgemm_plain"; they feed no other name, "all" included
+inline bool is_rollout_cat(int cat) { return cat >= CAT_ROLLOUT && cat <= CAT_ROLLOUT_DESCENT; }
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
 inline void count_sweep_form(dto_handle* h, int form) {
     if (h->profiling) ++h->sweep_forms[form];
@@ -2110,14 +2115,20 @@ static bool jac_product_is_matrix_free(const dto_handle* h, int transpose) {
     return mfree && mfree_on;
 }
 
+// The handle's private Jacobian value slab (the slab route of the products, the rollout): allocated at the first use
+static double* jac_scratch(dto_handle* h) {
+    if (!h->d_jac_scratch) h->d_jac_scratch = own(h, dalloc<double>((size_t)h->info.jac_len));
+    return h->d_jac_scratch;
+}
+
 // The device routine both entry-point families run: everything on `st`, dZ / dw / dy device pointers.
 static void jac_product(dto_handle* h, const double* dZ, const double* dw, double* dy, int transpose, hipStream_t st) {
     if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{"Jacobian-vector products need an unsharded handle"};
     if (jac_product_is_matrix_free(h, transpose)) return jac_product_matrix_free(h, dZ, dw, dy, transpose, st);
     if (h->integ_kind.size() > 8) throw HipError{"Jacobian-vector products support at most 8 integrators"};
     const int64_t n_out = transpose ? h->n_vars : h->n_cons;
-    if (!h->d_jac_scratch) {
-        h->d_jac_scratch = own(h, dalloc<double>((size_t)h->info.jac_len));
+    jac_scratch(h);
+    if (!h->d_conbase) {
         std::vector<int64_t> base((size_t)h->n_vars + 1, 0);
         for (size_t e = 0; e < h->con_cols.size(); ++e) base[(size_t)h->con_cols[e] + 1]++;
         for (int64_t c = 0; c < h->n_vars; ++c) base[(size_t)c + 1] += base[(size_t)c];
@@ -2176,6 +2187,129 @@ int dto_eval_jacobian_product_dev(dto_handle* h, const double* dZ, const double*
 }
 int dto_eval_jacobian_transpose_product_dev(dto_handle* h, const double* dZ, const double* dw, double* dy, void* stream) {
     return guarded(h, [&] { jac_product(h, dZ, dw, dy, 1, (hipStream_t)stream); }, G_ASYNC, (hipStream_t)stream);
+}
+
+// ---- open-loop rollout: X_{k+1} = E_k(Z) X_k through every interval (dto_rollout.hip, dto_rollout_plan.h)
+
+// grow-only device workspace: a failed allocation throws and leaves the old buffer in place
+static double* grow_workspace(dto_handle* h, double*& p, size_t& cap, size_t doubles) {
+    if (doubles <= cap && p) return p;
+    double* q = dalloc<double>(doubles);
+    if (p) {
+        h->owned.erase(std::find(h->owned.begin(), h->owned.end(), (void*)p));
+        (void)hipFree(p);   // (waits for whatever still reads it)
+    }
+    p = own(h, q);
+    cap = doubles;
+    return p;
+}
+
+// What a rollout call names: refused with text before anything is enqueued.  Returns the kernels' record of the integrator.
+static KRollout rollout_args(const dto_handle* h, int32_t integrator, int32_t n_cols, int32_t mode, bool has_X0) {
+    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{"dto_rollout needs an unsharded handle (k_lo, k_hi = the whole trajectory)"};
+    if (integrator < 0 || integrator >= (int32_t)h->integ_kind.size())
+        throw HipError{"dto_rollout: integrator " + std::to_string(integrator) + " is out of range (the handle has " +
+                       std::to_string(h->integ_kind.size()) + ")"};
+    if (mode != DTO_ROLLOUT_ALL && mode != DTO_ROLLOUT_FINAL) throw HipError{"dto_rollout: mode takes DTO_ROLLOUT_ALL (0) or DTO_ROLLOUT_FINAL (1)"};
+    KRollout R{};
+    const int kind = h->integ_kind[integrator], idx = h->integ_index[integrator];
+    if (kind == DTO_INTEGRATOR_BILINEAR) {
+        const KBil& k = h->bil[idx].k;
+        R.n = k.n; R.x_off = k.x_off; R.pre = k.pre;
+    } else if (kind == DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) {
+        const TdbHost& t = h->tdb[idx];
+        R.n = t.k.n; R.x_off = t.k.x_off; R.pre = t.place.pre;
+    } else if (kind == DTO_INTEGRATOR_DERIVATIVE) {
+        throw HipError{"dto_rollout: integrator " + std::to_string(integrator) + " is a DerivativeIntegrator: it has no propagator"};
+    } else {
+        throw HipError{"dto_rollout: integrator " + std::to_string(integrator) + " is evaluated on the host (DTO_INTEGRATOR_EXTERNAL): its "
+                       "Jacobian block is not known to be a propagator"};
+    }
+    if (n_cols < 1 || n_cols > R.n)
+        throw HipError{"dto_rollout: n_cols = " + std::to_string(n_cols) + ", allowed 1 .. x_dim = " + std::to_string(R.n)};
+    if (!has_X0 && n_cols != 1) throw HipError{"dto_rollout: X0 = NULL (the state of knot 1 of Z) takes n_cols = 1"};
+    R.npad = pad64(R.n);
+    R.n_cols = n_cols;
+    R.col_pad = rollout_col_pad(n_cols);
+    R.K = h->K;
+    R.L = rollout_levels(std::max<int64_t>(R.K, 1));
+    return R;
+}
+
+// The device routine both entry-point families run: everything on `st`, dZ / dX0 / dX device pointers.
+static void rollout(dto_handle* h, const KRollout& R, const double* dZ, const double* dX0, int mode, double* dX, hipStream_t st) {
+    const int npad = R.npad, L = R.L;
+    const int64_t K = R.K;
+    const size_t nn = (size_t)npad * npad;
+    double* S = grow_workspace(h, h->d_roll_S, h->roll_S_cap, rollout_traj_bytes(npad, K, R.n_cols) / sizeof(double));
+    if (K < 1) {   // a single knot: the rollout is X0
+        ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, 0.0);
+        launch_rollout_start(st, R, dZ, dX0, S);
+        launch_rollout_compact(st, R, 0, 1, S, dX);
+        return;
+    }
+    double* tree = grow_workspace(h, h->d_roll_tree, h->roll_tree_cap, rollout_tree_bytes(npad, K) / sizeof(double));
+    double* slab = jac_scratch(h);
+    // the whole Jacobian, tangent sweep included: the x_k columns of the integrator then hold -E_k on every path
+    do_jacobian(h, dZ, slab, st);   // (external blocks are staged as for dto_eval_jacobian_dev)
+    { ProfScope ps(h, st, CAT_ROLLOUT, 0.0); launch_rollout_leaves(st, h->P, R, slab, tree); }
+    // up-sweep: level l + 1 = (second half of level l) * (first half), one contiguous batch
+    for (int l = 0; l < L; ++l) {
+        const int nb = (int)rollout_level_len(L, l + 1);
+        const double* lo = tree + (size_t)rollout_level_off(L, l) * nn;
+        ProfScope ps(h, st, CAT_ROLLOUT_TREE, 2.0 * npad * (double)nn * nb);
+        launch_bgemm_plain(st, npad, nb, lo + (size_t)nb * nn, lo, tree + (size_t)rollout_level_off(L, l + 1) * nn);
+    }
+    { ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, 0.0); launch_rollout_start(st, R, dZ, dX0, S); }
+    const double item_flops = 2.0 * (double)nn * R.col_pad;
+    if (mode == DTO_ROLLOUT_ALL) {
+        for (int l = L + 1; l >= 1; --l) {
+            const int64_t live = l == L + 1 ? (K == ((int64_t)1 << L) ? 1 : 0) : (((K >> (l - 1)) + 1) >> 1);
+            if (live == 0) continue;
+            ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, item_flops * (double)live);
+            launch_rollout_descend(st, R, l, -1, tree, S);
+        }
+        ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, 0.0);
+        launch_rollout_compact(st, R, 0, K + 1, S, dX);
+    } else {
+        // the final state alone: the items on the way from knot K back to knot 0, highest level first -- the same launches on the
+        // same operands as in the full descent, so the same bits
+        int lv[64];
+        int64_t ix[64];
+        int cnt = 0;
+        for (int64_t t = K; t > 0; t = rollout_item(L, K, lv[cnt - 1], ix[cnt - 1]).start) { rollout_writer(L, t, lv[cnt], ix[cnt]); ++cnt; }
+        for (int c = cnt - 1; c >= 0; --c) {
+            ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, item_flops);
+            launch_rollout_descend(st, R, lv[c], ix[c], tree, S);
+        }
+        ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, 0.0);
+        launch_rollout_compact(st, R, K, 1, S, dX);
+    }
+}
+
+int dto_rollout(dto_handle* h, int32_t integrator, const double* Z, const double* X0, int32_t n_cols, int32_t mode, double* X) {
+    return guarded(h, [&] {
+        const KRollout R = rollout_args(h, integrator, n_cols, mode, X0 != nullptr);
+        upload_Z(h, Z);
+        const double* dX0 = nullptr;
+        if (X0) {
+            double* d = grow_workspace(h, h->d_roll_X0, h->roll_X0_cap, (size_t)R.n * R.n_cols);
+            HIP_CHECK(hipMemcpyAsync(d, X0, sizeof(double) * (size_t)R.n * R.n_cols, hipMemcpyHostToDevice, h->stream));
+            dX0 = d;
+        }
+        const size_t n_out = (size_t)(mode == DTO_ROLLOUT_ALL ? h->N : 1) * R.n_cols * R.n;
+        double* o = staging(h, n_out);
+        rollout(h, R, h->d_Z, dX0, mode, o, h->stream);
+        HIP_CHECK(hipMemcpyAsync(X, o, sizeof(double) * n_out, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_rollout_dev(dto_handle* h, int32_t integrator, const double* dZ, const double* dX0, int32_t n_cols, int32_t mode,
+                    double* dX, void* stream) {
+    return guarded(h, [&] {
+        const KRollout R = rollout_args(h, integrator, n_cols, mode, dX0 != nullptr);
+        rollout(h, R, dZ, dX0, mode, dX, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
 }
 
 // ---- multi-GPU: ranges, gather plans, collectives (dto_comm.h)
@@ -2403,7 +2537,7 @@ int dto_profile_reset(dto_handle* h) {
 int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launches, double* flops) {
     return guarded(h, [&] {
         int cat = -1;
-        bool any_gemm = false, any_basis = false;
+        bool any_gemm = false, any_basis = false, any_rollout = false;
         if (!strcmp(name, "bgemm")) any_gemm = true;
         else if (!strcmp(name, "bgemm_horner")) cat = CAT_BGEMM_HORNER;
         else if (!strcmp(name, "bgemm_square")) cat = CAT_BGEMM_SQUARE;
@@ -2423,6 +2557,10 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "tdb_kron")) cat = CAT_TDB_KRON;
         else if (!strcmp(name, "jac_product")) cat = CAT_JAC_PRODUCT;
         else if (!strcmp(name, "tdb_product")) cat = CAT_TDB_PRODUCT;
+        else if (!strcmp(name, "rollout")) any_rollout = true;
+        else if (!strcmp(name, "rollout_gather")) cat = CAT_ROLLOUT;
+        else if (!strcmp(name, "rollout_tree")) cat = CAT_ROLLOUT_TREE;
+        else if (!strcmp(name, "rollout_descent")) cat = CAT_ROLLOUT_DESCENT;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -2449,6 +2587,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (any_gemm && r.cat != CAT_BGEMM && r.cat != CAT_BGEMM_HORNER && r.cat != CAT_BGEMM_SQUARE && r.cat != CAT_CHAIN64) continue;
             if (any_basis && r.cat != CAT_OTHER && r.cat != CAT_BASIS_MULTI) continue;
             if (!any_gemm && !any_basis && cat >= 0 && r.cat != cat) continue;
+            if (is_rollout_cat(r.cat) ? !(any_rollout || r.cat == cat) : any_rollout) continue;   // ("all": the rollout is no callback)
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));

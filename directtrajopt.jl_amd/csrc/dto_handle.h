@@ -277,6 +277,10 @@ struct dto_handle {
     int32_t* d_plan = nullptr;   // [4] {q, d_ub, tc} of a sweep planned on the device from d_bounds (launch_plan_dev)
     double* d_jac_scratch = nullptr;     // value slab for the Jacobian-vector products (lazy)
     double* d_w = nullptr;               // product input
+    // open-loop rollout (dto_rollout[_dev]): product tree, padded trajectory and the host-pointer form's X0; allocated at the first
+    // rollout, grow-only (capacities in doubles)
+    double *d_roll_tree = nullptr, *d_roll_S = nullptr, *d_roll_X0 = nullptr;
+    size_t roll_tree_cap = 0, roll_S_cap = 0, roll_X0_cap = 0;
     int64_t* d_conbase = nullptr;        // [n_vars+1] first constraint-pattern entry of each column
     int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
     int64_t* d_crow_col = nullptr;

@@ -435,6 +435,21 @@ struct KShare {
 };
 void launch_share_E(hipStream_t st, const KProb& P, const KShare& S, int64_t int0, int nb, double* vals);
 
+// Open-loop rollout X_{k+1} = E_k X_k of one integrator (dto_rollout.hip; index plan: dto_rollout_plan.h).  The -E_k blocks are read
+// from the x_k columns of a Jacobian value slab (x_off / pre as in KBil, KExtInt), the product tree holds 2^(L+1) - 1 matrices of
+// npad x npad, the padded trajectory S is [K + 1][col_pad][npad].
+struct KRollout {
+    int32_t n, npad, x_off, pre;
+    int32_t n_cols, col_pad;
+    int32_t L;      // tree levels: 2^L >= K
+    int64_t K;      // intervals
+};
+void launch_rollout_leaves(hipStream_t st, const KProb& P, const KRollout& R, const double* vals, double* tree);
+void launch_rollout_start(hipStream_t st, const KRollout& R, const double* dZ, const double* X0, double* S);
+// level l of the descent (L + 1: the root's item, then L .. 1); only >= 0: that item alone
+void launch_rollout_descend(hipStream_t st, const KRollout& R, int l, int64_t only, const double* tree, double* S);
+void launch_rollout_compact(hipStream_t st, const KRollout& R, int64_t k0, int64_t nk, const double* S, double* X);
+
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);
 

@@ -111,6 +111,7 @@ class Evaluator:
             else:
                 raise NotImplementedError(f"{type(it).__name__}: wrap it in HostIntegrator to have it merged")
 
+        self._integrator_dims = [it.x_dim for it in prob.integrators]
         self._ext_con, self._ext_obj, self._ext_keep = [], [], None
         terms = _flatten_objective(prob.objective)
         objs = (capi.ObjectiveDesc * max(1, len(terms)))()
@@ -395,6 +396,32 @@ class Evaluator:
         self._stage_external(Z, con_need=1)
         self._check(self._lib.dto_eval_jacobian_transpose_product(self._h, _dp(Z), _dp(w), _out(y, self.n_variables, "y")))
 
+    def rollout(self, Z, integrator=0, X0=None, all_knots=True):
+        """Open-loop rollout X_{k+1} = E_k(Z) X_k of integrator ``integrator`` (0-based position in the integrator list) on the
+        device: the states its dynamics reach from X0 under the controls, timesteps and times of Z, whatever states Z holds -- what
+        the reference's rollout-fidelity callbacks score.  ``X0``: (n_cols, x_dim), one start state per row (or a single vector),
+        1 <= n_cols <= x_dim; None takes the integrator's state at knot 1 of Z.  Returns (N, n_cols, x_dim), knot 1 a copy of X0, or
+        with ``all_knots=False`` the (n_cols, x_dim) states at knot N (bit for bit the last block)."""
+        Z = self._Z(Z)
+        x0 = None
+        n_cols = 1
+        if X0 is not None:
+            x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(X0, dtype=np.float64)))
+            n_cols = x0.shape[0]
+        its = self._integrator_dims
+        if not 0 <= integrator < len(its):
+            x_dim = 1   # (the engine refuses the index with text)
+        else:
+            x_dim = its[integrator]
+            if x0 is not None and x0.shape[1] != x_dim:
+                raise ValueError(f"X0: rows of length {x0.shape[1]}, the integrator has {x_dim} states")
+        N = self.trajectory.N
+        X = np.full((N, n_cols, x_dim) if all_knots else (n_cols, x_dim), np.nan)
+        self._stage_external(Z, con_need=1)
+        self._check(self._lib.dto_rollout(self._h, int(integrator), _dp(Z), None if x0 is None else _dp(x0), n_cols,
+                                          capi.ROLLOUT_ALL if all_knots else capi.ROLLOUT_FINAL, _dp(X)))
+        return X
+
     def constraint_bounds(self):  # get_nonlinear_constraints, src/solvers/solve.jl:30-65
         lo = np.empty(self.n_constraints)
         hi = np.empty(self.n_constraints)
@@ -441,6 +468,14 @@ class Evaluator:
     def eval_jacobian_transpose_product_dev(self, dZ, dw, dy, stream=0, Z_host=None):  # y = J' w, dw [n_constraints], dy [n_variables]
         self._stage_external(Z_host, con_need=1)
         self._check(self._lib.dto_eval_jacobian_transpose_product_dev(self._h, dZ, dw, dy, stream))
+
+    def rollout_dev(self, dZ, dX0, n_cols, dX, integrator=0, all_knots=True, stream=0, Z_host=None):
+        """``rollout`` on device pointers: dX0 (n_cols, x_dim) or 0 / None (the state of knot 1 of dZ, n_cols = 1), dX
+        (N, n_cols, x_dim) or, with ``all_knots=False``, (n_cols, x_dim); enqueued on `stream`, errors deferred as for every `_dev`
+        call.  Same bits as ``rollout``."""
+        self._stage_external(Z_host, con_need=1)
+        self._check(self._lib.dto_rollout_dev(self._h, int(integrator), dZ, dX0 or None, int(n_cols),
+                                              capi.ROLLOUT_ALL if all_knots else capi.ROLLOUT_FINAL, dX, stream))
 
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod

@@ -348,6 +348,35 @@ int dto_eval_hessian_product_dev(dto_handle* h, const double* dZ, double sigma, 
 int dto_eval_jacobian_product_dev(dto_handle* h, const double* dZ, const double* dw, double* dy, void* stream);
 int dto_eval_jacobian_transpose_product_dev(dto_handle* h, const double* dZ, const double* dw, double* dy, void* stream);
 
+/* ---- Open-loop rollout: X_{k+1} = E_k(Z) X_k, k = 1 .. N-1, X_1 = X0 -- the states an integrator's dynamics reach from X0 under the
+ * controls, timesteps and (time-dependent kind) times of Z, whatever states Z itself holds.  This is what the reference's rollout
+ * callbacks evaluate every few iterations (callback_rollout_fidelity_factory / callback_best_rollout_fidelity_factory,
+ * src/solvers/ipopt_solver/callbacks.jl:264-361: `fid_fn(problem.trajectory, system)`): while the dynamics constraints are still
+ * violated, the fidelity of the ROLLED-OUT final state tells more than the objective does.
+ *   E_k is the propagator of interval k of integrator `integrator` (0-based position in the integrator list) at Z: exactly the
+ *   matrix whose negative dto_eval_jacobian stores in that integrator's x_k columns -- exp(dt_k G(u_k)) for DTO_INTEGRATOR_BILINEAR on
+ *   every path (small, 33..64 states, general, structured, leader or follower of a shared group), the RK4 map Phi_k for
+ *   DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR on every device path.  The state components of Z are not read, unless X0 is NULL.
+ *   X0: x_dim x n_cols column-major, 1 <= n_cols <= x_dim (a full basis gives the cumulative propagators: the unitary rollout);
+ *   NULL takes the integrator's state components of knot 1 of Z and requires n_cols = 1.
+ *   X:  DTO_ROLLOUT_ALL   [N][n_cols][x_dim] -- knot-major, then column, rows contiguous; knot 1 is a copy of X0
+ *       DTO_ROLLOUT_FINAL [n_cols][x_dim], the states at knot N: bit for bit the last block of DTO_ROLLOUT_ALL
+ * The call evaluates the Jacobian at Z into a private device slab (shared with the slab route of the Jacobian-vector products),
+ * gathers the N-1 blocks into a balanced binary tree of batched FP64 matrix products (ceil(log2(N-1)) launches) and descends the tree
+ * with one launch per level.  Every entry of X has one writer and a fixed summation order: a column has the same bits alone and
+ * among others, repeated calls are bit-identical, and both entry-point families return the same bits.  Workspaces are allocated at
+ * the first rollout, grow only and are freed with the handle: the tree, (2^(L+1) - 1) npad^2 doubles with 2^L >= N-1 and npad =
+ * x_dim rounded up to 64, a padded trajectory of N x n_cols (rounded up to 16; to 64 from 49 on) x npad doubles, and the Jacobian slab.
+ * Refused with text, the handle stays usable: a DerivativeIntegrator or external integrator, an index out of range, a sharded handle,
+ * a structure-only handle, n_cols out of range, a mode other than the two, a failed workspace allocation.
+ * The `_dev` form works on the caller's stream with outputs in HBM, may wait on the same small readbacks as dto_eval_jacobian_dev,
+ * and defers device-side errors as every `_dev` call; the host-pointer form uploads, runs the same device routine, downloads and blocks. */
+#define DTO_ROLLOUT_ALL 0
+#define DTO_ROLLOUT_FINAL 1
+int dto_rollout(dto_handle* h, int32_t integrator, const double* Z, const double* X0, int32_t n_cols, int32_t mode, double* X);
+int dto_rollout_dev(dto_handle* h, int32_t integrator, const double* dZ, const double* dX0, int32_t n_cols, int32_t mode,
+                    double* dX, void* stream);
+
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
  * communicator (SURVEY.md §8b "Ownership").  No callback needs a collective: every rank's Jacobian / Hessian / gradient
@@ -491,7 +520,11 @@ int dto_profile_reset(dto_handle* h);
  * copies of the leader's -E_k blocks to the followers of a DTO_FLAG_SHARED_GENERATORS group; its bytes are the bytes WRITTEN, one
  * block per follower and interval -- each launch reads a further block per interval -- and stay out of the third output of "all"),
  * "tdb_product" (the matrix-free J w / J' w of time-dependent integrators, option "tdb_matrix_free_products": one record per
- * integrator and product, flops as executed with padding; these launches do not count under "tdb_mfma").
+ * integrator and product, flops as executed with padding; these launches do not count under "tdb_mfma"),
+ * "rollout" (dto_rollout / dto_rollout_dev: the gather of the -E_k blocks, the tree's batched products and the descent, flops as
+ * executed with padding; its parts "rollout_gather" / "rollout_tree" / "rollout_descent", the last with the start and the copy into
+ * the caller's layout; the tree's products do not count under "bgemm" / "bgemm_plain", and these names feed no other, "all" included;
+ * the Jacobian evaluation inside a rollout counts under its own names).
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the
  * third output is the launches' algorithmic BYTES (what they must read and write), not FLOPs.
  * "hess_product_setup" returns the host milliseconds of the products' index build (once per handle), 0 launches, and the device

@@ -59,6 +59,8 @@ const DTO_VECTOR_JACOBIAN = Int32(1)
 const DTO_VECTOR_HESSIAN = Int32(2)
 const DTO_VECTOR_GRADIENT = Int32(3)
 const DTO_VECTOR_CONSTRAINT = Int32(4)
+const DTO_ROLLOUT_ALL = Int32(0)    # rollout: the states of every knot, x_dim x n_cols x N
+const DTO_ROLLOUT_FINAL = Int32(1)  # rollout: the states of knot N alone, x_dim x n_cols
 
 # ---- plain-C structs, field for field as in include/dto_engine.h ----------------------------------------------------
 struct IntegratorDesc
@@ -638,6 +640,44 @@ function MOI.eval_constraint_jacobian_transpose_product(ev::GPUEvaluator, y::Abs
     stage_external!(ev, Z; con_need = 1)
     GC.@preserve y Z w check(ev, @ccall lib.dto_eval_jacobian_transpose_product(ev.handle::Ptr{Cvoid}, Z::Ptr{Float64}, w::Ptr{Float64}, y::Ptr{Float64})::Cint)
     return nothing
+end
+
+# ---- open-loop rollout on the device (include/dto_engine.h, "Open-loop rollout") ---------------------------------------------------
+# X_{k+1} = E_k(Z) X_k through every interval of integrator `integrator` (0-based position in `prob.integrators`), E_k the propagator
+# whose negative eval_constraint_jacobian stores: the states the dynamics reach from X0 under the controls of the iterate Z, whatever
+# states Z holds.  The reference's rollout callbacks (callback_rollout_fidelity_factory, callback_best_rollout_fidelity_factory:
+# src/solvers/ipopt_solver/callbacks.jl:264-361) call `fid_fn(problem.trajectory, system)` every `freq` iterations; a `fid_fn` on the
+# engine closes over the evaluator and scores the rolled-out final state with the caller's own fidelity, e.g. for a ket
+#     fid_fn = (traj, sys) -> iso_fidelity(vec(rollout(ev, vec(traj); all_knots = false)), ψ̃_goal)
+# and for a unitary X0 = the identity of the isomorphic state (n_cols = x_dim) gives the cumulative propagator.
+# `X0`: x_dim x n_cols (a Vector is one column); `nothing` takes the integrator's state at knot 1 of Z.  Returns x_dim x n_cols x N
+# (knot 1 is a copy of X0), or x_dim x n_cols with `all_knots = false`: bit for bit the last slice.
+function rollout(ev::GPUEvaluator, Z::AbstractVector{Float64}; integrator::Integer = 0, X0::Union{Nothing,AbstractVecOrMat{Float64}} = nothing,
+                 all_knots::Bool = true)
+    stage_external!(ev, Z; con_need = 1)
+    i0 = Int32(integrator)
+    b = Ref{Int32}(0); reps = Ref{Int32}(0); active = Ref{Int32}(0)
+    check(ev, @ccall lib.dto_integrator_blocks(ev.handle::Ptr{Cvoid}, i0::Int32, b::Ptr{Int32}, reps::Ptr{Int32}, active::Ptr{Int32})::Cint)
+    x_dim = Int(b[]) * Int(reps[])
+    X0m = X0 === nothing ? nothing : Matrix{Float64}(reshape(X0, size(X0, 1), :))
+    nc = Int32(X0m === nothing ? 1 : size(X0m, 2))
+    mode = all_knots ? DTO_ROLLOUT_ALL : DTO_ROLLOUT_FINAL
+    X = all_knots ? fill(NaN, x_dim, Int(nc), ev.trajectory.N) : fill(NaN, x_dim, Int(nc))
+    p0 = X0m === nothing ? Ptr{Float64}(C_NULL) : pointer(X0m)
+    GC.@preserve X Z X0m check(ev, @ccall lib.dto_rollout(ev.handle::Ptr{Cvoid}, i0::Int32, Z::Ptr{Float64}, p0::Ptr{Float64}, nc::Int32, mode::Int32,
+                                                          X::Ptr{Float64})::Cint)
+    return X
+end
+
+# the same on device pointers: dX0 x_dim x n_cols (or C_NULL with n_cols = 1), dX x_dim x n_cols x N (or x_dim x n_cols); enqueued on `stream`
+function rollout_dev!(ev::GPUEvaluator, dX::Ptr{Float64}, dZ::Ptr{Float64}, dX0::Ptr{Float64}, n_cols::Integer, stream::Ptr{Cvoid};
+                      integrator::Integer = 0, all_knots::Bool = true, Z_host = nothing)
+    Z_host === nothing || stage_external!(ev, Z_host; con_need = 1)
+    i0 = Int32(integrator)
+    nc = Int32(n_cols)
+    mode = all_knots ? DTO_ROLLOUT_ALL : DTO_ROLLOUT_FINAL
+    check(ev, @ccall lib.dto_rollout_dev(ev.handle::Ptr{Cvoid}, i0::Int32, dZ::Ptr{Float64}, dX0::Ptr{Float64}, nc::Int32, mode::Int32,
+                                         dX::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 end
 
 # row bounds handed to the solver (src/solvers/solve.jl:30-65)
