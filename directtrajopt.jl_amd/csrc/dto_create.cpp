@@ -1096,10 +1096,9 @@ void alloc_kron(dto_handle* h, BilHost& b) {
 void alloc_pairing_store(dto_handle* h, BilHost& b) {
     const int m = b.k.m, dcap = PAIR_DCAP, T1 = 1 + m;
     const double bytes = (double)dcap * T1 * b.fw.Kpad * b.k.npad * 8.0;
-    static const bool pair_on = tune_int("DTO_HESS_PAIRING", 1) != 0;
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    if (!(pair_on && m >= 1 && bytes * (3.0 + 1.0 * m / T1) < 0.4 * (double)free_b)) return;
+    if (!(m >= 1 && bytes * (3.0 + 1.0 * m / T1) < 0.4 * (double)free_b)) return;
     const size_t store = (size_t)dcap * T1 * b.fw.Kpad * b.k.npad;
     for (SweepBuf* w : {&b.fw, &b.ad}) {
         w->Zt = own(h, dalloc<double>(store));
@@ -1141,15 +1140,13 @@ void generator_product_norms(dto_handle* h, BilHost& b) {
 }
 
 // generator-subspace powers pay off while the number of symmetrised products stays well below the 3n columns the three GEMMs
-// would process (DTO_BASIS_POWERS=0/1 overrides)
+// would process
 bool basis_pays_off(const BilHost& b) {
     const long m1 = b.k.m + 1;
     const long c2 = m1 * (m1 + 1) / 2, c3 = c2 * (m1 + 2) / 3, c4 = c3 * (m1 + 3) / 4;
     // (npad is a multiple of 64: npad^2 is a multiple of the kernel's 128-row tiles and every wave's 64 rows of
     // vec(A^r) stay inside one matrix column, which is all k_basis_gemm's fused column sums need)
-    bool want = (c2 + c3 + c4) * 2 <= 3L * b.k.npad;
-    { const int f = tune_int("DTO_BASIS_POWERS", -1); if (f >= 0) want = f != 0; }
-    return want;
+    return (c2 + c3 + c4) * 2 <= 3L * b.k.npad;
 }
 
 // per-bilinear workspaces + generator product norms

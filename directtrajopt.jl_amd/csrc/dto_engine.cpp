@@ -188,8 +188,7 @@ SweepChoice choose_sweep(const dto_handle* h, const BilHost& b, const SweepBuf& 
 // store, no reuse: the host then needs nothing of the plan.)  `alone`: the choice of such a sweep with the chip to itself.
 const SweepPlan PLAN_ON_DEVICE{1, 200};  // what the host passes where launch_plan_dev's {q, d_ub, tc} are read instead
 bool s64_plans_itself(const dto_handle* h, const BilHost& b, const SweepBuf& w, const SweepTypes& ty, SweepChoice* alone = nullptr) {
-    static const int on = tune_int("DTO_PLAN_DEV", 1);  // A/B runs (TUNING builds)
-    if (!on || h->reuse) return false;
+    if (h->reuse) return false;
     const SweepChoice c = choose_sweep(h, b, w, ty, PLAN_ON_DEVICE, /*store=*/false, /*shared_chip=*/false);
     if (alone) *alone = c;
     return c.form == SWEEP_S64;
@@ -235,8 +234,7 @@ int run_sweep(dto_handle* h, BilHost& b, SweepBuf& w, const SweepTypes& ty, cons
         for (int t = w.frozen ? w.first_type : 0; t < ty.T; ++t) segs += b.k.m + 1;  // an extra term rides in the segment of its generator
         return 2.0 * b.k.npad * (double)b.k.npad * w.Kpad * segs;
     }();
-    static const int tc_env = tune_int("DTO_SWEEP_TC", -1);
-    const int tc = sweep_tc(plan, tc_env);   // first step of the termination test
+    const int tc = sweep_tc(plan);   // first step of the termination test
     count_sweep_form(h, c.form);
     if (c.form != SWEEP_STEP) {
         // the one-launch forms: the whole series, termination tests included, in one persistent launch
@@ -320,61 +318,72 @@ int run_sweep(dto_handle* h, BilHost& b, SweepBuf& w, const SweepTypes& ty, cons
     return launched;
 }
 
+// What a caller of the chain asks for per chunk of intervals: a cap on the chunk (0: none; ignored under option "deterministic")
+// and `done(first local interval, count)`, run on the host when the -E_k of a chunk are final behind what is enqueued.
+struct ChainChunks {
+    int cap = 0;
+    std::function<void(int64_t, int)> done;
+};
+
+// Everything one call of run_chain takes from its caller; every callback may be empty.
+struct ChainCall {
+    ChainChunks chunks;
+    // runs on the host while the GPU works on the first chunk's factor K (one-launch chain: on the launch itself) and the host
+    // would otherwise only wait for the readback: independent work to enqueue
+    std::function<void()> in_bubble;
+    // `after_last_enqueue(d2max)` runs on the host once every kernel of the chain has been enqueued (the GPU is then busy with
+    // the Taylor products and squarings): the caller uses it to drive the generator sweep on a second stream so that both
+    // proceed concurrently.  d2max = max_k ||A_k^2||_1^(1/2) (exact) bounds the growth of the Taylor terms of the sweep.
+    std::function<void(double)> after_last_enqueue;
+    bool nothing_waits = false;   // one-launch chain: the caller's sweep is planned and enqueued, the host reads nothing back
+};
+
 // exp(dt G(u_k)) for every owned interval; -E_k goes straight into the Jacobian slab.
-// Returns max_k ||A_k^2||_1^(1/2) (exact), which bounds the growth of the Taylor terms of the sweep.
-// `after_last_enqueue(d2max)` runs on the host once every kernel of the chain has been enqueued (the GPU
-// is then busy with the Taylor products and squarings): the caller uses it to drive the generator sweep on a
-// second stream so that both proceed concurrently.
-double run_chain(dto_handle* h, BilHost& b, const double* dZ, double* vals, double b1max, hipStream_t st,
-                 const std::function<void(double)>& after_last_enqueue = nullptr, const std::function<void()>& in_bubble = nullptr,
-                 bool nothing_waits = false) {
+void run_chain(dto_handle* h, BilHost& b, const double* dZ, double* vals, hipStream_t st, const ChainCall& call) {
     const int npad = b.k.npad;
     const int64_t nint = h->P.n_int;
     double d2max = 0.0;
-    if (nint <= 0) return d2max;
+    if (nint <= 0) return;
     int cap = h->chain_chunk > 0 ? std::min(h->chain_chunk, b.chain_cap) : b.chain_cap;
-    if (h->xfer_cap > 0 && !h->deterministic) cap = std::min(cap, h->xfer_cap);
-    int s_ub = 1;
-    if (b1max == b1max && b1max > THETA_16) s_ub = std::isinf(b1max) ? 60 : std::max(1, (int)std::ceil(std::log2(b1max / THETA_16)));
-    s_ub = std::min(s_ub, 60);
+    if (call.chunks.cap > 0 && !h->deterministic) cap = std::min(cap, call.chunks.cap);
+    const int s_ub = 60;   // squarings per interval at the most (a NaN iterate gets one)
     // 33..64 states: the whole chain in ONE launch, a workgroup per interval (dto_chain64.hip) -- no batched-GEMM launches, no
     // workspace chunks, the evaluation form chosen per interval on the device; the host reads back only what plans the sweep
     if (chain64_applies(h, b)) {
         ChainWork& w = b.chain;
         HIP_CHECK(hipMemsetAsync(w.smax, 0, 8 * sizeof(int32_t), st));
         HIP_CHECK(hipMemsetAsync(b.d_hump, 0, 8 * sizeof(unsigned long long), st));
-        int want_form = 0;
-        if (h->expm_form == 2 || h->expm_form == 3) want_form = h->expm_form;
+        const int want_form = h->expm_form == 2 || h->expm_form == 3 ? h->expm_form : 0;
         {
             // priced at three powers + three more products per interval (either form, with its squarings, is 5..7 at these norms)
             ProfScope ps(h, st, CAT_CHAIN64, 6.0 * 2.0 * 64.0 * 64.0 * 64.0 * (double)nint);
             HIP_CHECK(launch_chain64(st, h->P, b.k, dZ, vals, w.norms, w.smax, w.d2max, w.s, s_ub, want_form, h->n_cu));
         }
-        if (nothing_waits) {
+        if (call.nothing_waits) {
             // the caller has planned and enqueued its sweep already: nothing on the host depends on this launch, the call stays
             // enqueue-only; the squaring count (a diagnostic) is read with the sweep statistics at the next entry point
             HIP_CHECK(hipMemcpyAsync(&h->mailbox->deferred_smax, w.smax, sizeof(int32_t), hipMemcpyDeviceToHost, st));
             h->smax_pending = true;
             h->last_form = 0;
-            if (in_bubble) in_bubble();
-            if (h->on_chain_chunk) h->on_chain_chunk(0, (int)nint);
-            if (after_last_enqueue) after_last_enqueue(0.0);
-            return 0.0;
+            if (call.in_bubble) call.in_bubble();
+            if (call.chunks.done) call.chunks.done(0, (int)nint);
+            if (call.after_last_enqueue) call.after_last_enqueue(0.0);
+            return;
         }
         launch_hump(st, h->P, b.k, dZ, b.d_g1, h->P.kn_lo, (int)nint, w.norms, b.d_hump);
         const ChainReadback& rb = h->mailbox->chain;
         HIP_CHECK(hipMemcpyAsync(&h->mailbox->chain, w.smax, sizeof(ChainReadback), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipMemcpyAsync(h->mailbox->hump, b.d_hump, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipEventRecord(h->ev_chain, st));
-        if (in_bubble) in_bubble();
+        if (call.in_bubble) call.in_bubble();
         HIP_CHECK(hipEventSynchronize(h->ev_chain));
         h->last_form = 0;   // per interval
         h->last_smax = rb.s_max2;
         read_hump(h, b);
         d2max = rb.d2max;
-        if (h->on_chain_chunk) h->on_chain_chunk(0, (int)nint);
-        if (after_last_enqueue) after_last_enqueue(d2max);
-        return d2max;
+        if (call.chunks.done) call.chunks.done(0, (int)nint);
+        if (call.after_last_enqueue) call.after_last_enqueue(d2max);
+        return;
     }
     const double gemm_flops = 2.0 * npad * (double)npad * npad;
     h->last_smax = 0;
@@ -423,26 +432,15 @@ double run_chain(dto_handle* h, BilHost& b, const double* dZ, double* vals, doub
         // squarings, summed over the chunk) unless an option pins it, so the factor K of the first product can be
         // enqueued before the host knows the outcome; the host needs it only for the launch sequence that follows and reads
         // it back (with the squaring counts, 32 bytes) while the GPU works on K -- `in_bubble` adds more independent work.
-        static const int env_form = tune_int("DTO_EXPM_FORM", 0);  // A/B runs
-        int want_form = 0;
-        if (env_form == 2 || env_form == 3) want_form = env_form;
-        if (h->expm_form == 2 || h->expm_form == 3) want_form = h->expm_form;
-        launch_expm_coef(st, nb, w, want_form);
+        launch_expm_coef(st, nb, w, h->expm_form == 2 || h->expm_form == 3 ? h->expm_form : 0);
         // ... and it leaves on a stream of its own right behind k_expm_coef, so the host learns the form while the GPU is still
         // busy with K's GEMM (0.65 ms at 256 x 2000) and has the products enqueued before that GEMM ends: no bubble
         const ChainReadback& rb = h->mailbox->chain;
-        static const int rb_side = tune_int("DTO_RB_STREAM", 1);  // 0: the readback follows K's GEMM on the call's stream (round 2)
-        hipEvent_t ev_s = h->ev_chain;
-        auto readback = [&](hipStream_t rs) {
-            HIP_CHECK(hipMemcpyAsync(&h->mailbox->chain, w.smax, sizeof(ChainReadback), hipMemcpyDeviceToHost, rs));
-            HIP_CHECK(hipMemcpyAsync(h->mailbox->hump, b.d_hump, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, rs));
-            HIP_CHECK(hipEventRecord(ev_s, rs));
-        };
-        if (rb_side) {
-            HIP_CHECK(hipEventRecord(h->ev_rb, st));
-            HIP_CHECK(hipStreamWaitEvent(h->stream_rb, h->ev_rb, 0));
-            readback(h->stream_rb);
-        }
+        HIP_CHECK(hipEventRecord(h->ev_rb, st));
+        HIP_CHECK(hipStreamWaitEvent(h->stream_rb, h->ev_rb, 0));
+        HIP_CHECK(hipMemcpyAsync(&h->mailbox->chain, w.smax, sizeof(ChainReadback), hipMemcpyDeviceToHost, h->stream_rb));
+        HIP_CHECK(hipMemcpyAsync(h->mailbox->hump, b.d_hump, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream_rb));
+        HIP_CHECK(hipEventRecord(h->ev_chain, h->stream_rb));
         if (b.use_basis) {
             launch_basis_coef(st, h->P, b.k, b.basis_all, dZ, int0, nb, nbpad, w.coef);
             ProfScope ps(h, st, CAT_OTHER, 2.0 * npad * (double)npad * b.basis_all.cntpad * nb);
@@ -450,9 +448,8 @@ double run_chain(dto_handle* h, BilHost& b, const double* dZ, double* vals, doub
         } else {
             launch_poly_h3(st, npad, nb, w);
         }
-        if (!rb_side) readback(st);
-        if (c0 == 0 && in_bubble) in_bubble();
-        HIP_CHECK(hipEventSynchronize(ev_s));
+        if (c0 == 0 && call.in_bubble) call.in_bubble();
+        HIP_CHECK(hipEventSynchronize(h->ev_chain));
         const int form = rb.form;
         if (form != 2 && form != 3) throw HipError{"propagator chain: the evaluation form did not come back from the device"};
         h->last_form = form;
@@ -481,10 +478,9 @@ double run_chain(dto_handle* h, BilHost& b, const double* dZ, double* vals, doub
             launch_bgemm_square(st, npad, nb, w, src, src == 4 ? 5 : 4, it, h->P, b.k, int0, vals);
             src = src == 4 ? 5 : 4;
         }
-        if (h->on_chain_chunk) h->on_chain_chunk(c0, nb);  // the -E_k of these intervals are final behind what is enqueued now
+        if (call.chunks.done) call.chunks.done(c0, nb);  // the -E_k of these intervals are final behind what is enqueued now
     }
-    if (after_last_enqueue) after_last_enqueue(d2max);
-    return d2max;
+    if (call.after_last_enqueue) call.after_last_enqueue(d2max);
 }
 
 // max_k ||A_k^2||_1^(1/2), exact, for callbacks that do not run the propagator chain: A_k and A_k^2 only
@@ -546,8 +542,7 @@ void read_hump(dto_handle* h, BilHost& b) {
     }
 }
 SweepPlan plan_hump(const BilHost& b, double beta_fallback) {
-    static const bool on = tune_int("DTO_HUMP_PLAN", 1) != 0;
-    return dto::plan_hump(on && b.hump_valid, b.hump_logH, b.hump_kend, sweep_theta_v(), beta_fallback);
+    return dto::plan_hump(b.hump_valid, b.hump_logH, b.hump_kend, sweep_theta_v(), beta_fallback);
 }
 
 SweepPlan plan_from(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st, bool loose = false) {
@@ -804,11 +799,19 @@ void share_blocks(dto_handle* h, BilHost* const* members, int n_members, int64_t
     launch_share_E(st, h->P, sh, int0, nb, dvals);
 }
 
-void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st) {
+// A single bilinear integrator, on the general path, with intervals to own: the propagator chain alone writes its -E_k blocks, so
+// do_jacobian clears around them and build_jac_plan hands each block over with its chain chunk -- one predicate for both
+bool lone_general_bilinear(const dto_handle* h) {
+    return h->bil.size() == 1 && h->P.n_int > 0 && !h->bil[0].small && !h->bil[0].kron;
+}
+
+// `caller`: a cap on the chain's chunks and a callback per finished chunk, for every chain this call runs (the host-pointer
+// Jacobian ships a lone integrator's blocks early with them)
+void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st, const ChainChunks& caller = {}) {
     // fill!(∂, 0), evaluator.jl:497 -- the -E_k block of a lone bilinear integrator is skipped: the chain
     // overwrites all of it
     // (enqueued inside the chain, where it fills the GPU while the host waits for the scaling decision)
-    const bool lone = h->bil.size() == 1 && h->P.n_int > 0 && !h->bil[0].small && !h->bil[0].kron;
+    const bool lone = lone_general_bilinear(h);
     // bound and primed output (dto_bind_output_dev): constants are in place, clear only the runs kernels accumulate into
     const bool keep_constants = h->bound[0] == dvals && h->primed[0] && ensure_bind_runs(h, 0);
     if (keep_constants) launch_zero_runs(st, h->d_bind_start[0], h->d_bind_len[0], h->n_bind_runs[0], dvals);
@@ -929,23 +932,17 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                 }
             }
             const bool nothing_waits = swept && chain64_applies(h, b);
-            // the copy follows each chunk of the chain (run_chain's hook for a finished chunk; the host-pointer Jacobian's own hook,
-            // which ships a lone integrator's blocks early, comes after it)
-            struct ChunkHook {
-                dto_handle* h;
-                bool installed = false;
-                std::function<void(int64_t, int)> outer;
-                ~ChunkHook() { if (installed) h->on_chain_chunk = std::move(outer); }
-            } chunk_hook{h};
-            if (n_members > 1) {
-                chunk_hook.outer = std::move(h->on_chain_chunk);
-                chunk_hook.installed = true;
-                h->on_chain_chunk = [&](int64_t c0, int nb) {
+            ChainCall call;
+            call.chunks = caller;
+            // a group's copy follows each chunk of the chain; the caller's own callback comes after it
+            if (n_members > 1)
+                call.chunks.done = [&](int64_t c0, int nb) {
                     share_blocks(h, members, n_members, h->P.kn_lo + c0, nb, dvals, st);
-                    if (chunk_hook.outer) chunk_hook.outer(c0, nb);
+                    if (caller.done) caller.done(c0, nb);
                 };
-            }
-            run_chain(h, b, dZ, dvals, INFINITY, st, [&](double d2) {
+            call.in_bubble = [&] { zero_around_blocks(st); };
+            call.nothing_waits = nothing_waits;
+            call.after_last_enqueue = [&](double d2) {
                 bd = read_bounds(h);  // copied before the chain's readback event
                 // ||A^t|| <= ||A^2||^floor(t/2) ||A||^(t mod 2): the exact d2 of the chain is the sharper
                 // (and still rigorous) growth rate for the sweep's step budget
@@ -954,7 +951,8 @@ void do_jacobian(dto_handle* h, const double* dZ, double* dvals, hipStream_t st)
                 if (h->reuse)   // a Hessian at this very point need not buy the norms again
                     for (int i = 0; i < n_members; ++i) members[i]->cache.chain_planned(from_chain.q, from_chain.d_ub);
                 sweep_with(from_chain);
-            }, [&] { zero_around_blocks(st); }, nothing_waits);
+            };
+            run_chain(h, b, dZ, dvals, st, call);
             if (overlap) {
                 HIP_CHECK(hipEventRecord(h->ev_join, ss));
                 HIP_CHECK(hipStreamWaitEvent(st, h->ev_join, 0));
@@ -1159,7 +1157,7 @@ void build_jac_plan(dto_handle* h) {
     auto one = [&](int64_t at, double v) { p.one_pos.push_back(at); p.one_val.push_back(v); };
     // the -E_k block of a lone general-path bilinear integrator is written by the propagator chain alone (do_jacobian): final
     // with its chain chunk
-    const bool lone = h->bil.size() == 1 && P.n_int > 0 && !h->bil[0].small && !h->bil[0].kron;
+    const bool lone = lone_general_bilinear(h);
     for (int64_t kn = P.kn_lo; kn < P.kn_lo + P.n_knots; ++kn) {
         const int has_prev = kn >= 1, has_own = kn < h->K;
         const int cnt = has_prev + has_own;
@@ -1994,21 +1992,18 @@ int dto_eval_jacobian(dto_handle* h, const double* Z, double* vals) {
             // constants are filled by host threads while the GPU computes; only the variable runs cross PCIe, and the -E_k
             // blocks start crossing as soon as their chain chunk is done (dto_hostxfer.h)
             const XferPlan& pl = h->jac_plan;
-            struct Reset {
-                dto_handle* h;
-                ~Reset() { h->xfer_cap = 0; h->on_chain_chunk = nullptr; }
-            } reset{h};
             h->xfer->begin(pl, o, vals);
             try {
+                ChainChunks early;
                 if (pl.n_early() > 0) {
-                    static const int chunks = std::max(1, tune_int("DTO_XFER_CHUNKS", 4));
+                    // from 512 intervals on the chain runs in four chunks (multiples of 8 intervals), each handed over when done
                     const int64_t nint = h->P.n_int;
-                    if (nint >= 512 && chunks > 1) h->xfer_cap = (int)(((nint + chunks - 1) / chunks + 7) / 8 * 8);
-                    h->on_chain_chunk = [&](int64_t c0, int nb) {
+                    if (nint >= 512) early.cap = (int)(((nint + 3) / 4 + 7) / 8 * 8);
+                    early.done = [&](int64_t c0, int nb) {
                         h->xfer->submit(pl.early_off[(size_t)c0], pl.early_off[(size_t)(c0 + nb)], h->stream);
                     };
                 }
-                do_jacobian(h, h->d_Z, o, h->stream);
+                do_jacobian(h, h->d_Z, o, h->stream, early);
                 h->xfer->submit(pl.n_early(), pl.n_runs(), h->stream);
                 h->xfer->finish();
             } catch (...) {
@@ -2111,8 +2106,7 @@ static bool jac_product_is_matrix_free(const dto_handle* h, int transpose) {
         if (!b.kron && !b.small) mfree = mfree && (transpose == 0 || (h->eval_hessian != 0 && b.ad.S != nullptr));
     }
     for (auto& c : h->con) mfree = mfree && !c.external;
-    static const bool mfree_on = tune_int("DTO_JV_MATRIX_FREE", 1) != 0;
-    return mfree && mfree_on;
+    return mfree;
 }
 
 // The handle's private Jacobian value slab (the slab route of the products, the rollout): allocated at the first use

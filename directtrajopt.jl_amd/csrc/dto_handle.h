@@ -216,7 +216,6 @@ struct dto_handle {
     dto::KProb P{};
     std::vector<int64_t> colptr;            // host copy
     std::vector<int64_t> con_cols, con_rows;  // constraint pattern entries sorted by (col,row), 0-based
-    std::vector<int64_t> con_colstart;      // index into con_* of each column with entries (map col -> range)
     std::vector<dto::BilHost> bil;
     std::vector<dto::KDer> der;
     std::vector<int> integ_kind, integ_index;  // reference order -> (kind, index into bil/der)
@@ -238,8 +237,6 @@ struct dto_handle {
     // host-pointer Jacobian / Hessian call, option "host_xfer" = 0 keeps the plain whole-slab copy
     std::unique_ptr<dto::HostXfer> xfer;
     dto::XferPlan jac_plan, hess_plan;
-    int xfer_cap = 0;                                         // host-pointer Jacobian: chain chunk (intervals) for the early hand-over, 0 = off
-    std::function<void(int64_t, int)> on_chain_chunk;         // ... and its hook: (first local interval, count) of a finished chunk
     bool plans_built = false;
     bool raw_plans_built = false;
     // dto_bind_output_dev: a device buffer the caller passes again and again (MadNLP's value vectors in GPU mode).  Once a call

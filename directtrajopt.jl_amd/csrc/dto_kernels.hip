@@ -524,8 +524,7 @@ __global__ void __launch_bounds__(256) k_build_A(KProb P, KBil B, const double* 
 void launch_build_A(hipStream_t st, const KProb& P, const KBil& B, const double* dZ, int64_t int0, int nb, double* A) {
     const int64_t nn2 = (int64_t)B.npad * B.npad / 2;
     int gx = (int)((nn2 + 255) / 256);
-    static const int cap = tune_int("DTO_BUILDA_GX", 16);
-    if (gx > cap) gx = cap;
+    if (gx > 16) gx = 16;
     hipLaunchKernelGGL(k_build_A, dim3(gx, nb), dim3(256), 0, st, P, B, dZ, int0, A);
 }
 
@@ -1298,55 +1297,20 @@ __global__ void __launch_bounds__(256, (TM * TN <= 64 * 64 ? 4 : 2)) k_sweep(Swe
     sweep_epilogue<TM, TN>(a, acc, rt, ct, ty);
 }
 
-static int sweep_tile_choice() {
-    static int v = tune_int("DTO_SWEEP_TILE", -1);
-    return v;
-}
+// the tile: enough workgroups to cover 256 CUs a few times over (the per-step GEMM is small)
+// (a DMA-staged variant of the 64 x 32 tile with per-segment accumulators was measured 12 % slower)
 static void launch_sweep_kernel(hipStream_t st, const SweepArgs& a, int ny) {
-    const int npad = a.w.npad;
-    // tile choice: enough workgroups to cover 256 CUs a few times over (the per-step GEMM is small)
-    int choice = sweep_tile_choice();
-    if (choice < 0) {
-        // 64x32 measured fastest at 256x2000 (1280 workgroups = 5 per CU: balanced); smaller problems get 32x32 tiles
-        // so that the launch still covers the chip (-5..10 % per step at 64 and 128 states)
-        const long wgs = (long)(npad / 64) * (a.w.Kpad / 32) * ny;
-        choice = wgs >= 1024 ? 5 : 6;
+    const int npad = a.w.npad, rows = sweep_step_tile_rows(npad, a.w.Kpad, ny);
+    const bool frozen = a.mode == 0 && a.w.frozen;
+#define DTO_GO(TM, TN) \
+    if (rows == TM) { \
+        const dim3 grid((npad / TM) * (a.w.Kpad / TN), ny); \
+        if (frozen) hipLaunchKernelGGL((k_sweep<TM, TN, true>), grid, dim3(256), 0, st, a); \
+        else hipLaunchKernelGGL((k_sweep<TM, TN>), grid, dim3(256), 0, st, a); \
+        return; \
     }
-    static const bool relax = tune_int("DTO_SWEEP_TILE_RELAX", 1) != 0;
-    if (!relax && (npad % 128 != 0 || a.w.TN != 128)) choice = 0;
-    if ((choice == 3 || choice == 1) && npad % 128 != 0) choice = 0;  // 128-row tiles need npad % 128 == 0
-    if ((choice == 3 || choice == 2) && a.w.Kpad % 128 != 0) choice = 0;
-    if (a.mode == 0 && a.w.frozen) {
-        if (choice != 6) choice = 5;
-        if (choice == 6)
-            hipLaunchKernelGGL((k_sweep<32, 32, true>), dim3((npad / 32) * (a.w.Kpad / 32), ny), dim3(256), 0, st, a);
-        else
-            hipLaunchKernelGGL((k_sweep<64, 32, true>), dim3((npad / 64) * (a.w.Kpad / 32), ny), dim3(256), 0, st, a);
-        return;
-    }
-    switch (choice) {
-        case 3:
-            hipLaunchKernelGGL((k_sweep<128, 128>), dim3((npad / 128) * (a.w.Kpad / 128), ny), dim3(256), 0, st, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL((k_sweep<64, 128>), dim3((npad / 64) * (a.w.Kpad / 128), ny), dim3(256), 0, st, a);
-            break;
-        case 1:
-            hipLaunchKernelGGL((k_sweep<128, 64>), dim3((npad / 128) * (a.w.Kpad / 64), ny), dim3(256), 0, st, a);
-            break;
-        case 4:
-            hipLaunchKernelGGL((k_sweep<32, 64>), dim3((npad / 32) * (a.w.Kpad / 64), ny), dim3(256), 0, st, a);
-            break;
-        case 6:
-            hipLaunchKernelGGL((k_sweep<32, 32>), dim3((npad / 32) * (a.w.Kpad / 32), ny), dim3(256), 0, st, a);
-            break;
-        case 5:
-            // (a DMA-staged variant of this tile with per-segment accumulators was measured 12 % slower)
-            hipLaunchKernelGGL((k_sweep<64, 32>), dim3((npad / 64) * (a.w.Kpad / 32), ny), dim3(256), 0, st, a);
-            break;
-        default:
-            hipLaunchKernelGGL((k_sweep<64, 64>), dim3((npad / 64) * (a.w.Kpad / 64), ny), dim3(256), 0, st, a);
-    }
+    DTO_SWEEP_STEP_TILES(DTO_GO)
+#undef DTO_GO
 }
 
 // Second half of a split-K step: term_{t+1} = 1/(t+1) * sum_g partial_g in fixed order (deterministic), sums and
@@ -1389,10 +1353,9 @@ void launch_sweep_step(hipStream_t st, const KBil& B, const SweepBuf& w, const S
     a.B = B; a.w = w; a.ty = ty; a.G = transposed ? B.GT : B.G;
     a.Zin = w.Z[in_buf]; a.Zout = w.Z[in_buf ^ 1]; a.t = t; a.mode = 0;
     // a single column type (eval_constraint) offers few tiles with a long K loop each: split K by generator into the
-    // unused type slots of the output buffer, then sum the partials (DTO_SWEEP_SPLITK=0 disables)
-    static const bool splitk = tune_int("DTO_SWEEP_SPLITK", 1) != 0;
+    // unused type slots of the output buffer, then sum the partials
     // (store mode with one type: the slots of the NEXT m+1 terms serve as scratch -- the caller vouches for the room)
-    if (splitk && ty.T == 1 && B.m >= 1 && (split_store || (w.T_alloc >= B.m + 2 && w.Z[0] != w.Zt && a.Zin != w.Zt))) {
+    if (ty.T == 1 && B.m >= 1 && (split_store || (w.T_alloc >= B.m + 2 && w.Z[0] != w.Zt && a.Zin != w.Zt))) {
         const int64_t typesz = (int64_t)w.Kpad * w.npad;
         a.mode = 3; a.V = a.Zin; a.out = a.Zout + typesz;
         launch_sweep_kernel(st, a, B.m + 1);

@@ -1263,13 +1263,13 @@ __global__ void __launch_bounds__(256, 1) k_sweep_cluster(ClusterArgs ca) {
     }
 }
 
-template <int MT, int NT, int WC = 1, int WK = 1>
+template <int MT, int NT, int WC, int WK>
 hipError_t launch_one(hipStream_t st, const FusedSweepArgs& a, int nblocks, size_t lds) {
     if (a.w.npad != 64 * MT) return hipErrorInvalidValue;
     hipLaunchKernelGGL((k_sweep_fused<MT, NT, WC, WK>), dim3(nblocks), dim3(256 * WC * WK), lds, st, a);
     return hipGetLastError();
 }
-template <int MT, int NT, int WC = 1, int WK = 1>
+template <int MT, int NT, int WC, int WK>
 hipError_t prepare_one(int bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep_fused<MT, NT, WC, WK>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
@@ -1279,17 +1279,11 @@ hipError_t prepare_one(int bytes) {
 hipError_t sweep_fused_prepare() {
     const int bytes = (int)SWEEP_LDS_OPT_IN;
     hipError_t e = hipSuccess;
-#define DTO_PREP(MT, NT) if (e == hipSuccess) e = prepare_one<MT, NT>(bytes)
-    DTO_PREP(4, 1); DTO_PREP(4, 2); DTO_PREP(4, 3);
-    DTO_PREP(2, 1); DTO_PREP(2, 2); DTO_PREP(2, 3);
-    DTO_PREP(1, 1); DTO_PREP(1, 2); DTO_PREP(1, 3);
+#define DTO_PREP(MT, NT, WC, WK) if (e == hipSuccess) e = prepare_one<MT, NT, WC, WK>(bytes);
+    DTO_SWEEP_FUSED_INSTANCES(DTO_PREP)
 #undef DTO_PREP
-    if (e == hipSuccess) e = prepare_one<4, 2, 2>(bytes);
-    if (e == hipSuccess) e = prepare_one<4, 1, 1, 2>(bytes);
-    if (e == hipSuccess) e = prepare_one<4, 2, 1, 2>(bytes);
-    if (e == hipSuccess) e = prepare_one<4, 3, 1, 2>(bytes);
-#define DTO_PREP64(MP, NX) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep_s64<MP, NX>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
-    DTO_PREP64(5, 0); DTO_PREP64(5, 1); DTO_PREP64(5, 2); DTO_PREP64(3, 0); DTO_PREP64(3, 1); DTO_PREP64(3, 2);
+#define DTO_PREP64(MP, NX) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep_s64<MP, NX>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    DTO_SWEEP_S64_INSTANCES(DTO_PREP64)
 #undef DTO_PREP64
     return e;
 }
@@ -1311,13 +1305,8 @@ hipError_t prepare_cluster_one(int bytes) {
 hipError_t sweep_cluster_prepare() {
     const int bytes = (int)SWEEP_LDS_OPT_IN;
     hipError_t e = hipSuccess;
-#define DTO_PREPC(MT, NT, R) if (e == hipSuccess) e = prepare_cluster_one<MT, NT, R>(bytes)
-    DTO_PREPC(1, 1, 2); DTO_PREPC(1, 2, 2); DTO_PREPC(1, 3, 2);   // 128 states
-    DTO_PREPC(2, 1, 2); DTO_PREPC(2, 2, 2); DTO_PREPC(2, 3, 2);   // 256 states over 2
-    DTO_PREPC(1, 1, 4); DTO_PREPC(1, 2, 4); DTO_PREPC(1, 3, 4);   // 256 states over 4
-    DTO_PREPC(4, 1, 2); DTO_PREPC(4, 2, 2);                       // 512 states over 2
-    DTO_PREPC(2, 1, 4); DTO_PREPC(2, 2, 4);                       // 512 states over 4
-    DTO_PREPC(4, 1, 4);                                           // 1024 states over 4
+#define DTO_PREPC(MT, NT, R) if (e == hipSuccess) e = prepare_cluster_one<MT, NT, R>(bytes);
+    DTO_SWEEP_CLUSTER_INSTANCES(DTO_PREPC)
 #undef DTO_PREPC
     return e;
 }
@@ -1334,23 +1323,9 @@ hipError_t launch_sweep_cluster(hipStream_t st, const KProb& P, const KBil& B, c
     c.X = X; c.arrive = arrive; c.n_groups = pl.n_groups; c.n_clusters = pl.n_clusters;
     hipError_t e = hipMemsetAsync(arrive, 0, sizeof(unsigned) * (size_t)pl.n_clusters, st);
     if (e != hipSuccess) return e;
-    const int key = pl.MT * 100 + pl.NT * 10 + pl.R;
-    switch (key) {
-        case 112: return launch_cluster_one<1, 1, 2>(st, c, pl.nblocks, pl.lds_bytes);
-        case 122: return launch_cluster_one<1, 2, 2>(st, c, pl.nblocks, pl.lds_bytes);
-        case 132: return launch_cluster_one<1, 3, 2>(st, c, pl.nblocks, pl.lds_bytes);
-        case 212: return launch_cluster_one<2, 1, 2>(st, c, pl.nblocks, pl.lds_bytes);
-        case 222: return launch_cluster_one<2, 2, 2>(st, c, pl.nblocks, pl.lds_bytes);
-        case 232: return launch_cluster_one<2, 3, 2>(st, c, pl.nblocks, pl.lds_bytes);
-        case 114: return launch_cluster_one<1, 1, 4>(st, c, pl.nblocks, pl.lds_bytes);
-        case 124: return launch_cluster_one<1, 2, 4>(st, c, pl.nblocks, pl.lds_bytes);
-        case 134: return launch_cluster_one<1, 3, 4>(st, c, pl.nblocks, pl.lds_bytes);
-        case 412: return launch_cluster_one<4, 1, 2>(st, c, pl.nblocks, pl.lds_bytes);
-        case 422: return launch_cluster_one<4, 2, 2>(st, c, pl.nblocks, pl.lds_bytes);
-        case 214: return launch_cluster_one<2, 1, 4>(st, c, pl.nblocks, pl.lds_bytes);
-        case 224: return launch_cluster_one<2, 2, 4>(st, c, pl.nblocks, pl.lds_bytes);
-        case 414: return launch_cluster_one<4, 1, 4>(st, c, pl.nblocks, pl.lds_bytes);
-    }
+#define DTO_GOC(MT_, NT_, R_) if (pl.MT == MT_ && pl.NT == NT_ && pl.R == R_) return launch_cluster_one<MT_, NT_, R_>(st, c, pl.nblocks, pl.lds_bytes);
+    DTO_SWEEP_CLUSTER_INSTANCES(DTO_GOC)
+#undef DTO_GOC
     return hipErrorInvalidValue;
 }
 
@@ -1378,37 +1353,19 @@ hipError_t launch_sweep_fused(hipStream_t st, const KProb& P, const KBil& B, con
     a.q = q; a.d_ub = d_ub; a.tc = tc; a.ipw = pl.ipw; a.store = store ? 1 : 0; a.nslot = pl.nslot; a.tol = tol;
     if (pl.S64) {
         if (w.npad != 64 || B.m + 1 > 5 || ty.T * pl.ipw > 16) return hipErrorInvalidValue;
-#define DTO_GO64(MP, NX) hipLaunchKernelGGL((k_sweep_s64<MP, NX>), dim3(pl.nblocks), dim3(256), pl.lds_bytes, st, a)
-        switch ((B.m + 1 <= 3 ? 0 : 10) + pl.NX) {
-            case 0: DTO_GO64(3, 0); break;
-            case 1: DTO_GO64(3, 1); break;
-            case 2: DTO_GO64(3, 2); break;
-            case 10: DTO_GO64(5, 0); break;
-            case 11: DTO_GO64(5, 1); break;
-            case 12: DTO_GO64(5, 2); break;
-            default: return hipErrorInvalidValue;
-        }
+#define DTO_GO64(MP_, NX_) \
+    if (s64_generator_slots(B.m) == MP_ && pl.NX == NX_) { \
+        hipLaunchKernelGGL((k_sweep_s64<MP_, NX_>), dim3(pl.nblocks), dim3(256), pl.lds_bytes, st, a); \
+        return hipGetLastError(); \
+    }
+        DTO_SWEEP_S64_INSTANCES(DTO_GO64)
 #undef DTO_GO64
-        return hipGetLastError();
+        return hipErrorInvalidValue;
     }
-    if (pl.WC == 2 && pl.MT == 4 && pl.NT == 2) return launch_one<4, 2, 2>(st, a, pl.nblocks, pl.lds_bytes);
-    if (pl.WK == 2 && pl.MT == 4 && pl.WC == 1) {
-        if (pl.NT == 1) return launch_one<4, 1, 1, 2>(st, a, pl.nblocks, pl.lds_bytes);
-        if (pl.NT == 2) return launch_one<4, 2, 1, 2>(st, a, pl.nblocks, pl.lds_bytes);
-        if (pl.NT == 3) return launch_one<4, 3, 1, 2>(st, a, pl.nblocks, pl.lds_bytes);
-    }
-    const int key = pl.MT * 10 + pl.NT;
-    switch (key) {
-        case 41: return launch_one<4, 1>(st, a, pl.nblocks, pl.lds_bytes);
-        case 42: return launch_one<4, 2>(st, a, pl.nblocks, pl.lds_bytes);
-        case 43: return launch_one<4, 3>(st, a, pl.nblocks, pl.lds_bytes);
-        case 21: return launch_one<2, 1>(st, a, pl.nblocks, pl.lds_bytes);
-        case 22: return launch_one<2, 2>(st, a, pl.nblocks, pl.lds_bytes);
-        case 23: return launch_one<2, 3>(st, a, pl.nblocks, pl.lds_bytes);
-        case 11: return launch_one<1, 1>(st, a, pl.nblocks, pl.lds_bytes);
-        case 12: return launch_one<1, 2>(st, a, pl.nblocks, pl.lds_bytes);
-        case 13: return launch_one<1, 3>(st, a, pl.nblocks, pl.lds_bytes);
-    }
+#define DTO_GO(MT_, NT_, WC_, WK_) \
+    if (pl.MT == MT_ && pl.NT == NT_ && pl.WC == WC_ && pl.WK == WK_) return launch_one<MT_, NT_, WC_, WK_>(st, a, pl.nblocks, pl.lds_bytes);
+    DTO_SWEEP_FUSED_INSTANCES(DTO_GO)
+#undef DTO_GO
     return hipErrorInvalidValue;
 }
 

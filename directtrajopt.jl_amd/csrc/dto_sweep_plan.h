@@ -1,8 +1,9 @@
 // dto_sweep_plan.h -- everything that decides how a generator sweep runs: how many Taylor steps it may take, which of the five forms
-// it takes and what launch shape that form gets.  All of it is host arithmetic on a few integers and one norm bound.  Plain C++ (no
-// HIP header, no engine header): the same functions serve the host driver (dto_engine.cpp), the launchers and kernels
-// (dto_sweep_fused.hip, dto_sweep_gs.hip: the LDS carve-ups, and k_plan_dev, which runs device_plan on one lane) and a g++-built test
-// (tests/test_sweep_plan_header.py).  Three groups: 1. step budget (host and device), 2. launch shapes, 3. form choice.
+// it takes, what launch shape that form gets and which kernel instantiations exist for it.  All of it is host arithmetic on a few
+// integers and one norm bound.  Plain C++ (no HIP header, no engine header): the same functions serve the host driver
+// (dto_engine.cpp), the launchers and kernels (dto_sweep_fused.hip, dto_sweep_gs.hip: the LDS carve-ups, and k_plan_dev, which runs
+// device_plan on one lane) and a g++-built test (tests/test_sweep_plan_header.py).  Four groups: 1. step budget (host and device),
+// 2. launch shapes, 3. form choice, 4. kernel instantiations.
 #pragma once
 
 #include <cmath>
@@ -119,7 +120,7 @@ SWP_HD inline bool cheap_plan(double beta, bool loose, double theta_v, SweepPlan
 // The termination test cannot fire early in the series: it is first run at step tc = d_ub/2 - 1 (d_ub comes from an
 // upper bound on the terms needed at this very Z, so tc is a function of Z alone and results stay reproducible; a
 // column block that would pass earlier merely adds a few terms below 1e-16 of its sum).  The plan's own tc goes first; a value
-// below 2 means "from the first step on".  `forced` >= 0 (DTO_SWEEP_TC, TUNING builds) replaces both.
+// below 2 means "from the first step on".  `forced` >= 0 replaces both.
 SWP_HD inline int sweep_tc(const SweepPlan& plan, int forced = -1) {
     const int tc = forced >= 0 ? forced : (plan.tc >= 0 ? plan.tc : plan.d_ub / 2 - 1);
     return tc < 2 ? 0 : tc;
@@ -332,7 +333,6 @@ inline bool sweep_fused_plan(int npad, int m, const SweepTypes& ty, int64_t n_in
     }
     out.S64 = 0;
     static const double t_small[2][4] = {{0.0, 0.24, 0.30, 0.44}, {0.0, 0.61, 0.73, 0.86}};
-    static const int ipw_env = tune_int("DTO_SWEEP_IPW", 0);  // A/B runs (TUNING builds)
     auto search = [&](int WC) {
         bool found = false;
         double best = 0.0;
@@ -344,7 +344,6 @@ inline bool sweep_fused_plan(int npad, int m, const SweepTypes& ty, int64_t n_in
                 if (NT != 4) continue;  // two column groups of two tiles each
                 NT = 2;
             } else if (NT > 3) break;
-            if (ipw_env > 0 && ipw != ipw_env && T == 1 + m) continue;
             const FusedLds L(npad, T, m, ipw, nslot, MT);
             const size_t bytes = (size_t)L.total * sizeof(double);
             if (bytes > SWEEP_LDS_LIMIT) break;
@@ -364,16 +363,15 @@ inline bool sweep_fused_plan(int npad, int m, const SweepTypes& ty, int64_t n_in
     // wavefronts per SIMD hide each other's operand traffic, +10 % MFMA rate per CU -- but a third fewer workgroups, each a
     // fifth longer (256 x 2000: 167 workgroups, 4.0 ms against 223, 3.3 ms).  It pays when the CUs the sweep leaves free are
     // used by another stream (`shared_chip`: the Jacobian's sweep next to the propagator chain), not when the sweep runs alone.
-    static const int wk_env = tune_int("DTO_SWEEP_WK", 2);  // A/B runs (TUNING builds): 1 = one wave per SIMD as up to round 3
     out.WK = 1;
     if (shared_chip && npad == 256 && search(2)) return true;
     if (!search(1)) return false;
-    if (npad == 256 && out.WC == 1 && wk_env == 2) out.WK = 2;   // two waves per SIMD splitting the K loop
+    if (npad == 256) out.WK = 2;   // (WC == 1) two waves per SIMD splitting the K loop
     return true;
 }
 
 // ---- the same sweep with the rows of the matrix split over a cluster of R workgroups that exchange their slices of every new
-// term through global memory (dto_sweep_fused.hip): short shards, single-column sweeps, 512+ states
+// term through global memory (dto_sweep_fused.hip): short shards of 128- and 256-state problems
 struct ClusterSweepPlan {
     int MT, NT, R, ipw, n_groups, n_clusters, nblocks;
     size_t lds_bytes;
@@ -388,20 +386,19 @@ struct ClusterSweepPlan {
 inline bool sweep_cluster_plan(int npad, int m, const SweepTypes& ty, int64_t n_int, int n_cu, ClusterSweepPlan& out) {
     const int T = ty.T;
     if (T < 1 || n_int <= 0 || n_cu < 16) return false;
+    if (npad != 128 && npad != 256) return false;   // (512 and 1024 states measured slower than the step launches: choose_sweep)
     static const int force_r = tune_int("DTO_CLUSTER_R", 0), force_nt = tune_int("DTO_CLUSTER_NT", 0);
     bool found = false;
     double best = 0.0;
     for (int R = 2; R <= 4; R += 2) {
         if (npad % (64 * R) != 0) continue;
         const int MT = npad / (64 * R);
-        if (MT != 1 && MT != 2 && MT != 4) continue;
         if (force_r && R != force_r) continue;
-        for (int NT = 1; NT <= 3; ++NT) {
+        for (int NT = 1; NT <= 2; ++NT) {   // (three-tile shapes spill beside the exchange registers)
             if (force_nt && NT != force_nt) continue;
             const int ipw = (16 * NT) / T;
             if (ipw < 1) continue;
             if (NT > 1 && (16 * (NT - 1)) / T == ipw) continue;  // the narrower shape holds as many intervals
-            if (NT == 3 || (MT == 4 && NT > 1)) continue;  // three-tile shapes and 256 rows x 2 tiles spill beside the exchange registers
             const FusedLds L(npad, T, m, ipw, 0, MT);
             const size_t bytes = (size_t)L.total * sizeof(double);
             if (bytes > SWEEP_LDS_LIMIT) continue;
@@ -552,13 +549,29 @@ inline SweepChoice choose_sweep(const SweepSituation& s) {
     // 0.62 ms at 250 knots, 1.52 against 1.45 at 2000: the rendezvous + slice exchange costs ~10 us per Taylor step, as much
     // as the step's MFMA work there) and 512 / 1024 states (23.6 against 18.7 ms, 57 against 47 ms per Jacobian: the step
     // launches tile the 2500 columns 32 wide, a cluster member is held to 16 by its LDS).
-    static const int cluster_on = tune_int("DTO_SWEEP_CLUSTER", 1);  // A/B runs (TUNING builds): 0 = never
-    static const int cluster_big = tune_int("DTO_SWEEP_CLUSTER_BIG", 0);  // 512 and 1024 states as well
-    static const int cluster_t1 = tune_int("DTO_SWEEP_CLUSTER_T1", 0);    // single-column sweeps too
-    if (cluster_on && (ty.T != 1 || cluster_t1) && (s.npad <= 256 || cluster_big) &&
-        sweep_cluster_plan(s.npad, s.m, ty, s.n_int, s.n_cu, c.cluster))
-        return c.is(SWEEP_CLUSTER);
+    if (ty.T != 1 && sweep_cluster_plan(s.npad, s.m, ty, s.n_int, s.n_cu, c.cluster)) return c.is(SWEEP_CLUSTER);
     return c;   // one launch per Taylor step: what remains, and the form for frozen p terms and the products' extra start vector
 }
+
+// ------------------------------------------------------------------------------------------ 4. kernel instantiations
+
+// One list per kernel family: what its *_prepare opts into the whole CU's LDS, what its launch dispatches over, and what
+// tests/test_sweep_plan_header.py holds against everything choose_sweep returns.  A plan outside its list is an error of the launch.
+// k_sweep_fused<MT, NT, WC, WK>: 64 MT states; WC = 2 column groups of wavefronts or WK = 2 waves per SIMD only at 256 states
+#define DTO_SWEEP_FUSED_INSTANCES(X) \
+    X(1, 1, 1, 1) X(1, 2, 1, 1) X(1, 3, 1, 1) X(2, 1, 1, 1) X(2, 2, 1, 1) X(2, 3, 1, 1) X(4, 1, 1, 2) X(4, 2, 1, 2) X(4, 3, 1, 2) X(4, 2, 2, 1)
+// k_sweep_s64<MP, NX>: generator slots (s64_generator_slots) and the most inhomogeneous sources of a column type
+#define DTO_SWEEP_S64_INSTANCES(X) X(3, 0) X(3, 1) X(3, 2) X(5, 0) X(5, 1) X(5, 2)
+// k_sweep_cluster<MT, NT, R>: 128 states over 2 members, 256 states over 2 and over 4
+#define DTO_SWEEP_CLUSTER_INSTANCES(X) X(1, 1, 2) X(1, 2, 2) X(2, 1, 2) X(2, 2, 2) X(1, 1, 4) X(1, 2, 4)
+// k_sweep<TM, TN> and its FROZEN form: the tiles of the step-per-launch sweep (sweep_step_tile_rows)
+#define DTO_SWEEP_STEP_TILES(X) X(64, 32) X(32, 32)
+
+inline int s64_generator_slots(int m) { return m + 1 <= 3 ? 3 : 5; }
+
+// Rows of a step launch's tile (32 columns either way) for `ny` column types or generators in grid.y: 64 x 32 measured fastest at
+// 256 x 2000 (1280 workgroups = 5 per CU: balanced); smaller problems get 32 x 32 tiles so that the launch still covers the chip
+// (-5..10 % per step at 64 and 128 states)
+inline int sweep_step_tile_rows(int npad, int Kpad, int ny) { return (long)(npad / 64) * (Kpad / 32) * ny >= 1024 ? 64 : 32; }
 
 }  // namespace dto

@@ -189,7 +189,8 @@ def test_a_shard_is_a_slice_of_the_whole():
 def test_chunks_of_the_chain_are_each_followed_by_their_copy():
     """chain_chunk = 8 on 25 intervals: four chunks, a copy behind each.  Bit for bit the unflagged handle's Jacobian in the same
     chunks, the followers' blocks the leader's bits, and the values of the call in one chunk (to the oracle's tolerance: with
-    fewer intervals per launch the chain's launches may take another tile shape)."""
+    fewer intervals per launch the chain's launches may take another tile shape).  The host-pointer Jacobian of the chunked group,
+    host_xfer on and off: the device Jacobian's bits."""
     import torch
     pe = multi_ket(128, 3, 26, seed=12)
     Z = pe.trajectory.vec()
@@ -207,6 +208,22 @@ def test_chunks_of_the_chain_are_each_followed_by_their_copy():
         idx = [torch.from_numpy(e_block_index(pe, c, i)).to(Jc.device) for i in range(3)]
         assert torch.equal(Jc[idx[1]], Jc[idx[0]]) and torch.equal(Jc[idx[2]], Jc[idx[0]])
         assert rel_err(Jc.cpu().numpy(), J1.cpu().numpy()) <= TOL
+        # the host-pointer Jacobian of the chunked group -- the entry point that owns the other per-chunk callback, here on a chain
+        # whose chunks the group's copy follows -- with the run-wise hand-over and with the whole-slab copy: into garbage, the device
+        # Jacobian's bits either way
+        # (a handle each: the option is fixed at a handle's first host-pointer call)
+        for on in (1, 0):
+            hp = dto_amd.Evaluator(pe, shared_generators=True)
+            try:
+                for name, value in (("deterministic", 1), ("chain_chunk", 8), ("host_xfer", on)):
+                    hp.set_option(name, value)
+                Jh = np.full(hp.n_jacobian_entries, np.nan)
+                hp.eval_constraint_jacobian(Jh, Z)
+            finally:
+                hp.close()
+            differ = int((Jh.view(np.uint64) != Jc.cpu().numpy().view(np.uint64)).sum())
+            print("host_xfer", on, "entries that differ from the device Jacobian:", differ)
+            assert differ == 0
     finally:
         one.close(); c.close(); d.close()
 

@@ -36,9 +36,8 @@ k_sweep_cluster<MT, NT, R> (npad = 64 MT R), in children with DTO_SWEEP_GS=0 and
     212, 222        256 states      test_cluster_instances[R2-NT1], [R2-NT2]
     114, 124        256 states      test_cluster_instances[R4-NT1], [R4-NT2]
 
-The planner's own picks (q > 1) are in tests/test_gpu_cluster_sweep.py.  The NT = 3 instances (132, 232, 134) are compiled but
-sweep_cluster_plan never picks them (three-tile shapes spill beside the exchange registers): not forced here.  The 512 / 1024-state
-and single-column cluster modes are TUNING-only switches that production never takes."""
+The planner's own picks (q > 1) are in tests/test_gpu_cluster_sweep.py.  These six are every instance there is
+(DTO_SWEEP_CLUSTER_INSTANCES, csrc/dto_sweep_plan.h; tests/test_sweep_plan_header.py holds the list against the planner)."""
 import atexit
 import json
 import os

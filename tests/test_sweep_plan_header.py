@@ -8,7 +8,10 @@ a. Step budget.  The program restates, verbatim, the two texts the header replac
 b. Launch shapes.  A table of the three planners' outputs, every field.  The expected values were printed by the planners of the
    library built from the commit before the header existed (they touch no device), never by the header.
 c. Form choice.  One row per rule of choose_sweep; the expected forms are those the GPU tests assert through the profile counters
-   (cited per row)."""
+   (cited per row).
+d. Kernel instantiations.  A second program walks choose_sweep over every shape the callbacks can ask for and prints each
+   (form, instantiation) it names, and the header's four lists (the X-macros prepare and launch read): the two sets must be equal in
+   the product build, and under the pins of tests/test_gpu_sweep_forms.py (-DDTO_TUNING) nothing outside the lists may appear."""
 import os
 import shutil
 import subprocess
@@ -61,10 +64,11 @@ SHAPES = [
     ((64, 2, 1, 1999, 32, 0), "1 1 1 5 1 400 1 1 1 1 75280", "0", "0"),
     ((192, 2, 1, 999, 256, 0), "0", "0", "0"),
     ((192, 4, 0, 249, 256, 0), "0", "0", "0"),
-    ((512, 2, 1, 999, 256, 0), "0", "1 2 2 4 10 100 64 256 125088 56.763413333333332 2129920", "0"),
-    ((512, 4, 1, 249, 256, 0), "0", "1 2 2 4 6 42 48 192 125128 91.149333333333331 1597440", "0"),
+    # (512 states: the cluster planner answers for 128 and 256 states alone)
+    ((512, 2, 1, 999, 256, 0), "0", "0", "0"),
+    ((512, 4, 1, 249, 256, 0), "0", "0", "0"),
     ((512, 1, 0, 1999, 256, 1), "0", None, None),
-    ((512, 4, 2, 39, 32, 0), "0", "1 2 2 4 2 20 8 32 125296 91.149333333333331 266240", "0"),
+    ((512, 4, 2, 39, 32, 0), "0", "0", "0"),
 ]
 
 # label -> form.  Situation fields not named by a row: 256 CUs, sweep_form 0, no reuse, not frozen, a term store of 80 terms, q = 1,
@@ -331,6 +335,135 @@ int main() {
     return 0;
 }
 """
+
+
+# ---------------------------------------------------------------- d. kernel instantiations
+# The shapes: npad 64 .. 1024, 1 .. 7 drives, the four column-type sets of the callbacks (type_set above), store and shared_chip
+# both ways, q = 1 and 2, EVERY interval count from 1 to 4000 (the planners' answers change at interval counts that depend on the
+# type count and the CUs, so no coarser grid is argued for; a walk takes under two seconds) -- on 256 CUs, and once more on 48.
+# The second CU count is there for k_sweep_cluster<2, 1, 2>: on 256 CUs four members with two tiles (124) or two members with two
+# tiles (222) always cost less in sweep_cluster_plan's model, so that instance is reached only where four-member clusters are too
+# few (fewer than 32 CUs) or too coarse (48 CUs: 8 clusters of 4 against 24 of 2) -- a partitioned chip -- and under the pins.
+# Situation fields not walked: as in `situation` above.  The step form names its tile per launch: grid.y is the type count, or the
+# generators of a split-K step / launch_apply_generators.
+ENUM_PROGRAM = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <initializer_list>
+#include "dto_sweep_plan.h"
+using namespace dto;
+
+static SweepTypes type_set(int m, int set) {
+    SweepTypes ty = make_types(set == 0 ? 0 : m, set == 2);
+    if (set == 3) ty.t[ty.T++] = TypeDesc{0, {0, 0}, {0, 0}, {0, 0}};
+    return ty;
+}
+int main(int argc, char** argv) {   // the CU counts to walk
+    static const char* names[5] = {"gs", "fused", "s64", "cluster", "step"};
+    static bool seen[2][5][1 << 16];   // [CU count][form][four numbers below 16]
+    const int n_cus = argc - 1 < 2 ? argc - 1 : 2;
+    int cus[2] = {0, 0};
+    for (int ci = 0; ci < n_cus; ++ci) cus[ci] = atoi(argv[1 + ci]);
+    for (int ci = 0; ci < n_cus; ++ci) {
+        auto saw = [&](int form, int a, int b, int c, int d) { seen[ci][form][((a * 16 + b) * 16 + c) * 16 + d] = true; };
+        for (int npad : {64, 128, 256, 512, 1024})
+            for (int m = 1; m <= 7; ++m)
+                for (int set = 0; set < 4; ++set) {
+                    SweepSituation s{};
+                    const int TN = npad % 128 == 0 ? 128 : 64;
+                    s.npad = npad; s.m = m; s.types = type_set(m, set); s.n_cu = cus[ci];
+                    s.has_term_store = true; s.dcap = 80; s.d_ub = 40;
+                    for (int store = 0; store < 2; ++store)
+                        for (int shared = 0; shared < 2; ++shared)
+                            for (int q = 1; q <= 2; ++q)
+                                for (long n_int = 1; n_int <= 4000; ++n_int) {
+                                    s.Kpad = (int)((n_int + TN - 1) / TN * TN); s.n_int = n_int;
+                                    s.store = store != 0; s.shared_chip = shared != 0; s.q = q;
+                                    const SweepChoice c = choose_sweep(s);
+                                    if (c.form == SWEEP_GS) saw(c.form, 0, 0, 0, 0);   // (k_sweep_gs keeps its list in dto_sweep_gs.hip)
+                                    else if (c.form == SWEEP_FUSED) saw(c.form, c.fused.MT, c.fused.NT, c.fused.WC, c.fused.WK);
+                                    else if (c.form == SWEEP_S64) saw(c.form, s64_generator_slots(m), c.fused.NX, 0, 0);
+                                    else if (c.form == SWEEP_CLUSTER) saw(c.form, c.cluster.MT, c.cluster.NT, c.cluster.R, 0);
+                                    else
+                                        for (int ny : {s.types.T, m + 1}) saw(c.form, sweep_step_tile_rows(npad, s.Kpad, ny) / 16, 32 / 16, 0, 0);
+                                }
+                }
+    }
+    static const int count[5] = {0, 4, 2, 3, 2};   // numbers that name an instantiation of the form
+    for (int ci = 0; ci < n_cus; ++ci)
+        for (int form = 0; form < 5; ++form)
+            for (int k = 0; k < (1 << 16); ++k) {
+                if (!seen[ci][form][k]) continue;
+                const int v[4] = {k >> 12, (k >> 8) & 15, (k >> 4) & 15, k & 15};
+                printf("inst %d %s", cus[ci], names[form]);
+                for (int i = 0; i < count[form]; ++i) printf(" %d", form == SWEEP_STEP ? 16 * v[i] : v[i]);
+                printf("\n");
+            }
+#define F(MT, NT, WC, WK) printf("list fused %d %d %d %d\n", MT, NT, WC, WK);
+    DTO_SWEEP_FUSED_INSTANCES(F)
+#define S(MP, NX) printf("list s64 %d %d\n", MP, NX);
+    DTO_SWEEP_S64_INSTANCES(S)
+#define C(MT, NT, R) printf("list cluster %d %d %d\n", MT, NT, R);
+    DTO_SWEEP_CLUSTER_INSTANCES(C)
+#define K(TM, TN) printf("list step %d %d\n", TM, TN);
+    DTO_SWEEP_STEP_TILES(K)
+    return 0;
+}
+"""
+
+# the pins of tests/test_gpu_sweep_forms.py (test_gs_instances_two_tiles, test_cluster_instances)
+PINS = [{"DTO_GS_NT": "2"}] + [{"DTO_SWEEP_GS": "0", "DTO_CLUSTER_R": str(R), "DTO_CLUSTER_NT": str(NT)} for R in (2, 4) for NT in (1, 2)]
+
+
+def _build(tmp, name, program, flags):
+    src, exe = str(tmp / (name + ".cpp")), str(tmp / name)
+    with open(src, "w") as f:
+        f.write(program)
+    subprocess.run(["g++", "-std=c++17", "-g", "-Wall", "-Werror", "-I", CSRC, src, "-o", exe] + flags, check=True)
+    return exe
+
+
+def _instances(lines, prefix):
+    return {l[len(prefix):] for l in lines if l.startswith(prefix)}
+
+
+@pytest.fixture(scope="module")
+def enumeration(tmp_path_factory):
+    assert shutil.which("g++") is not None, "g++ is needed (the engine's own build needs a C++ compiler too)"
+    tmp = tmp_path_factory.mktemp("sweep_instances")
+    product = _build(tmp, "product", ENUM_PROGRAM, ["-O2"])
+    tuning = _build(tmp, "tuning", ENUM_PROGRAM, ["-O2", "-DDTO_TUNING"])
+    env = {k: v for k, v in os.environ.items() if not k.startswith("DTO_")}
+    start = lambda exe, cus, pins: subprocess.Popen([exe] + cus, stdout=subprocess.PIPE, text=True, env=dict(env, **pins))
+    walks = [start(product, ["256"], {}), start(product, ["48"], {})] + [start(tuning, ["256"], pins) for pins in PINS]   # side by side
+    lines = [w.communicate()[0].splitlines() for w in walks]
+    assert all(w.returncode == 0 for w in walks)
+    return lines[0] + lines[1], list(zip(PINS, lines[2:]))
+
+
+def test_the_instantiation_lists_are_what_the_planner_names(enumeration):
+    """Product build: every (form, instantiation) choose_sweep returns over the shapes above is in the header's list of its family,
+    and every listed kernel is returned for some shape.  On 256 CUs alone the lists hold one kernel more than the planner names,
+    k_sweep_cluster<2, 1, 2> (see the note above ENUM_PROGRAM); everything else is named there."""
+    lines, _ = enumeration
+    listed = _instances(lines, "list ")
+    at_256, at_48 = _instances(lines, "inst 256 "), _instances(lines, "inst 48 ")
+    print(sorted(at_256), sorted(at_48), sorted(listed), sep="\n")
+    assert "gs" in at_256
+    assert listed - (at_256 - {"gs"}) == {"cluster 2 1 2"}
+    assert (at_256 | at_48) - {"gs"} == listed
+
+
+def test_pinned_shapes_stay_inside_the_lists(enumeration):
+    """TUNING build under each set of pins tests/test_gpu_sweep_forms.py runs its children with: nothing outside the lists."""
+    _, pinned = enumeration
+    for pins, lines in pinned:
+        named = _instances(lines, "inst 256 ")
+        print(pins, sorted(named))
+        assert named - {"gs"} <= _instances(lines, "list "), pins
+    # (the pins do reach what they are for: both tile counts of both cluster sizes at 256 states)
+    reached = set().union(*[_instances(lines, "inst 256 ") for _, lines in pinned])
+    assert {"cluster 2 1 2", "cluster 2 2 2", "cluster 1 1 4", "cluster 1 2 4", "cluster 1 1 2", "cluster 1 2 2"} <= reached
 
 
 @pytest.fixture(scope="module")

@@ -75,7 +75,7 @@ int main(int argc, char** argv) {
         // too few workgroups for the planner's taste (single-column sweeps, short shards): still a valid reference
         const int ipw = std::max(1, 16 / ty.T);
         fp = FusedSweepPlan{};
-        fp.MT = 4; fp.NT = 1; fp.WC = 1; fp.WK = 1; fp.ipw = ipw; fp.nslot = 0; fp.nblocks = (K + ipw - 1) / ipw;
+        fp.MT = 4; fp.NT = 1; fp.WC = 1; fp.WK = 2; fp.ipw = ipw; fp.nslot = 0; fp.nblocks = (K + ipw - 1) / ipw;
         fp.lds_bytes = (size_t)FusedLds(npad, ty.T, m, ipw, 0, 4).total * 8;
         have_fused = true;
     }
