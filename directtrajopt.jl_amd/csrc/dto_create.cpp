@@ -1046,18 +1046,20 @@ void alloc_tdb(dto_handle* h) {
         t.d_vals = own(h, dalloc<double>(K * n));
         t.d_jac = own(h, dalloc<double>(K * n * 2 * z));
         if (hess) t.d_hess = own(h, dalloc<double>(K * 4 * z * z));
+        // the product modes (need 3, 4) share the scratch below with the value calls; their J' w stages n + p doubles per interval
+        const int p = tdb_num_params(t.k.m, t.k.order);
+        t.d_jtv = own(h, dalloc<double>(std::max<size_t>(K, 1) * (n + (size_t)p)));
         if (t.kron) {
             // the kernel assigns the entries it owns and nothing else: the constant zeros of the blocks are written here, once
             HIP_CHECK(hipMemset(t.d_jac, 0, K * n * 2 * z * sizeof(double)));
             if (hess) HIP_CHECK(hipMemset(t.d_hess, 0, K * 4 * z * z * sizeof(double)));
             t.resident = (int)std::min<int64_t>(h->P.n_knots + 1, 2 * (int64_t)std::max(h->n_cu, 1));
-            t.stride = scratch_stride(tdb_kron_scratch_doubles(t.k, t.kk, 1), tdb_kron_scratch_doubles(t.k, t.kk, 2), hess);
+            t.stride = scratch_stride(std::max({tdb_kron_scratch_doubles(t.k, t.kk, 1), tdb_kron_scratch_doubles(t.k, t.kk, 3),
+                                                tdb_kron_scratch_doubles(t.k, t.kk, 4)}),
+                                      tdb_kron_scratch_doubles(t.k, t.kk, 2), hess);
             t.d_scratch = own(h, dalloc<double>(t.stride * (size_t)t.resident));
             continue;
         }
-        // the product modes (need 3, 4) share the scratch below with the value calls; their J' w stages n + p doubles per interval
-        const int p = tdb_num_params(t.k.m, t.k.order);
-        t.d_jtv = own(h, dalloc<double>(std::max<size_t>(K, 1) * (n + (size_t)p)));
         if (t.mfma) {
             // sized by the persistent grid (two workgroups per compute unit), not by the number of intervals
             t.resident = (int)std::min<int64_t>(h->P.n_knots + 1, 2 * (int64_t)std::max(h->n_cu, 1));

@@ -610,7 +610,7 @@ const double* ext_upload(dto_handle* h, int slot, int which, hipStream_t st) {
     return e.d[which];
 }
 
-// workgroups of a persistent-grid launch of `t` (k_tdb_mfma and its product form, k_tdb_kron): its `resident`, lowered by
+// workgroups of a persistent-grid launch of `t` (k_tdb_mfma, k_tdb_kron and their product forms): its `resident`, lowered by
 // option "tdb_resident" -- the scratch holds `resident` slots, a smaller grid uses the first ones
 int tdb_grid(const dto_handle* h, const TdbHost& t) {
     return h->tdb_resident > 0 ? std::min(h->tdb_resident, t.resident) : t.resident;
@@ -668,14 +668,17 @@ void tdb_eval(dto_handle* h, TdbHost& t, const double* dZ, const double* dmu, in
     }
 }
 
-// Matrix-free products of a dense device time-dependent integrator (option "tdb_matrix_free_products"): its rows of J w, or its
-// part of J' w added into the zero-filled dy -- staged per interval, then placed by one thread per entry.  No block, no slab.
+// Matrix-free products of a device time-dependent integrator, dense or structured (option "tdb_matrix_free_products"): its rows of
+// J w, or its part of J' w added into the zero-filled dy -- staged per interval, then placed by one thread per entry.  No block, no
+// slab.  One record under "tdb_product" whichever kernel runs (the structured one does not count under "tdb_kron").
 void tdb_product(dto_handle* h, TdbHost& t, const double* dZ, const double* dw, double* dy, int transpose, hipStream_t st) {
     const KProb& P = h->P;
     const int need = transpose ? 4 : 3;
-    ProfScope ps(h, st, CAT_TDB_PRODUCT, (t.mfma ? tdb_mfma_flops(t.k, need) : tdb_product_flops(t.k, need)) * (double)std::max<int64_t>(P.K, 0));
+    const double flops = t.kron ? tdb_kron_flops(t.k, t.kk, need) : (t.mfma ? tdb_mfma_flops(t.k, need) : tdb_product_flops(t.k, need));
+    ProfScope ps(h, st, CAT_TDB_PRODUCT, flops * (double)std::max<int64_t>(P.K, 0));
     double* out = transpose ? t.d_jtv : dy;
-    if (t.mfma) HIP_CHECK(launch_tdb_mfma_product(st, P, t.k, t.d_Bp, t.d_BpT, dZ, dw, need, out, t.d_scratch, t.stride, tdb_grid(h, t)));
+    if (t.kron) HIP_CHECK(launch_tdb_kron_product(st, P, t.k, t.kk, dZ, dw, need, out, t.d_scratch, t.stride, tdb_grid(h, t)));
+    else if (t.mfma) HIP_CHECK(launch_tdb_mfma_product(st, P, t.k, t.d_Bp, t.d_BpT, dZ, dw, need, out, t.d_scratch, t.stride, tdb_grid(h, t)));
     else HIP_CHECK(launch_tdb_product(st, P, t.k, dZ, dw, need, out, t.d_scratch, t.stride));
     if (transpose) HIP_CHECK(launch_tdb_jtv_place(st, P, t.k, dw, t.d_jtv, dy));
 }
@@ -2094,13 +2097,12 @@ static void jac_product_matrix_free(dto_handle* h, const double* dZ, const doubl
 }
 
 // Which route a product takes.  The slab route keeps: external integrators, time-dependent integrators unless the option
-// "tdb_matrix_free_products" is 1 and every one of them is on a dense device path (k_tdb, k_tdb_mfma; the structured path of
-// dto_tdb_kron.hip has no product modes), external constraints (their blocks are placed into the value slab), m + 2 > MAX_TYPES, and
-// a transpose product without adjoint buffers on the general path (they exist only with eval_hessian; structured and small
-// integrators need none, nor do the time-dependent ones).
+// "tdb_matrix_free_products" is 1 (every device path of theirs has product modes: k_tdb, k_tdb_mfma and the structured
+// k_tdb_kron_product), external constraints (their blocks are placed into the value slab), m + 2 > MAX_TYPES, and a transpose
+// product without adjoint buffers on the general path (they exist only with eval_hessian; structured and small integrators need
+// none, nor do the time-dependent ones).
 static bool jac_product_is_matrix_free(const dto_handle* h, int transpose) {
     bool mfree = h->ext_int.empty() && (h->tdb.empty() || h->tdb_matrix_free_products != 0);
-    for (auto& t : h->tdb) mfree = mfree && !t.kron;
     for (auto& b : h->bil) {
         mfree = mfree && b.k.m + 2 <= MAX_TYPES;
         if (!b.kron && !b.small) mfree = mfree && (transpose == 0 || (h->eval_hessian != 0 && b.ad.S != nullptr));

@@ -152,7 +152,7 @@ struct TdbHost {
     KExtInt place{};
     double *d_vals = nullptr, *d_jac = nullptr, *d_hess = nullptr, *d_scratch = nullptr;
     size_t stride = 0;
-    double* d_jtv = nullptr;   // dense paths: staging of the matrix-free J' w, [K][n + p] (option "tdb_matrix_free_products")
+    double* d_jtv = nullptr;   // every device path: staging of the matrix-free J' w, [K][n + p] (option "tdb_matrix_free_products")
     // 65..256 states: zero-padded generators and their transposes, and the scratch slots (= workgroups) of the persistent grid
     bool mfma = false;
     double *d_Bp = nullptr, *d_BpT = nullptr;
@@ -305,8 +305,8 @@ struct dto_handle {
     int n_cu = 256;
     int chain_chunk = 0;  // option "chain_chunk": upper bound on the intervals per chain chunk (0: workspace capacity)
     int tdb_share_members = 0;  // option of that name: members per group launch of k_tdb_mfma (0: each group's cap from create)
-    int tdb_resident = 0;  // option of that name: cap on the persistent grid of k_tdb_mfma / k_tdb_kron launches (0: each integrator's `resident`)
-    int tdb_matrix_free_products = 0;  // option of that name: J w / J' w of dense device time-dependent integrators without a slab
+    int tdb_resident = 0;  // option of that name: cap on the persistent grid of k_tdb_mfma / k_tdb_kron launches, product forms included (0: each integrator's `resident`)
+    int tdb_matrix_free_products = 0;  // option of that name: J w / J' w of device time-dependent integrators (dense or structured) without a slab
     int deterministic = 0;  // option "deterministic": results independent of overlap_sweep and of the entry-point family
     // deferred errors of the `*_dev` entry points (dto_engine.h, error convention): the sweep statistics of the last
     // asynchronous call are copied to pinned memory behind its kernels and looked at by the next call through the ABI

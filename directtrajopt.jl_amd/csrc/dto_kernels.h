@@ -381,6 +381,10 @@ double tdb_kron_flops(const KTdb& T, const KKron& K, int need);
 hipError_t launch_tdb_kron(hipStream_t st, const KProb& P, const KTdb& T, const KKron& K, const double* dZ, const double* dmu, int need,
                            int64_t i_lo, int64_t count, double* vals, double* jac, double* hess, double* scratch, size_t scratch_stride,
                            int resident);
+// ... and its product modes (k_tdb_kron_product; need 3 / 4, `out` as launch_tdb_product's, all K intervals): no Phi~, no block, no
+// slab.  tdb_kron_scratch_doubles and tdb_kron_flops cover need 3 and 4 as well; the J' w staging goes through launch_tdb_jtv_place.
+hipError_t launch_tdb_kron_product(hipStream_t st, const KProb& P, const KTdb& T, const KKron& K, const double* dZ, const double* dw, int need,
+                                   double* out, double* scratch, size_t scratch_stride, int resident);
 
 // host-evaluated knot terms (DTO_CONSTRAINT_EXTERNAL / DTO_OBJECTIVE_EXTERNAL_KNOT): scatter of caller-supplied blocks
 void launch_ext_cons(hipStream_t st, const KCon& C, const double* vals, double* g);

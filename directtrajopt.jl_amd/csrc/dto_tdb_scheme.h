@@ -4,9 +4,9 @@
 // Who uses what: the counts and the table check serve the host code of all three kernels (dto_tdb.hip, dto_tdb_mfma.hip,
 // dto_tdb_kron.hip) and the layouts of the latter two; the pair unranking serves the jet-coefficient table (dto_tdb_coef.hip.h) and
 // those two kernels.  The TABLEAU is the statement of the scheme, tied forward-to-adjoint by tests/test_tdb_scheme_header.py.
-// k_tdb_mfma (dto_tdb_mfma.hip: the forward loop, the Hessian's adjoint and the one-column adjoint of J' w) calls it.  The six
-// other stage loops (dto_tdb.hip: k_tdb forward and adjoint, k_tdb_product forward and adjoint; dto_tdb_kron.hip: forward and
-// adjoint) spell tau, w_acc / w_tmp, cw / cu, the IN / OUT rotation and the stage update out: calling these helpers moved the
+// k_tdb_mfma (dto_tdb_mfma.hip: the forward loop, the Hessian's adjoint and the one-column adjoint of J' w) and k_tdb_kron_product
+// (dto_tdb_kron.hip: its forward loop and its one-group adjoint) call it.  The six other stage loops (dto_tdb.hip: k_tdb forward
+// and adjoint, k_tdb_product forward and adjoint; dto_tdb_kron.hip: k_tdb_kron forward and adjoint) spell tau, w_acc / w_tmp, cw / cu, the IN / OUT rotation and the stage update out: calling these helpers moved the
 // register allocation of k_tdb_kron, and the shared forward / adjoint passes built on them made k_tdb slower at 4 states (DESIGN
 // 4.21, last paragraph).  A change to the tableau below has to be repeated in those six loops.
 #pragma once

@@ -535,10 +535,11 @@ class Evaluator:
     def set_option(self, name, value):
         """dto_set_option: ``reuse_forward_sweep`` (solver loops evaluate g, J, H at the same point), ``expm_form``
         (0 = by cost, 2 / 3 = two- / three-product form of the Jacobian's matrix exponential), ``tdb_matrix_free_products`` (0 | 1,
-        default 0: 1 evaluates J w / J' w of dense device TimeDependentBilinearIntegrators without forming a Jacobian -- the scheme
-        applied to two vectors, or to 1 + p forward vectors and one adjoint vector), ``tdb_share_members`` (members per launch of a
+        default 0: 1 evaluates J w / J' w of device TimeDependentBilinearIntegrators, on the dense paths and on the structured
+        path of ``block_generators`` alike, without forming a Jacobian -- the scheme applied to two vectors, or to 1 + p forward
+        vectors and one adjoint vector; column groups of the b x b map on the structured path), ``tdb_share_members`` (members per launch of a
         shared group of time-dependent integrators, 1 = one launch per member), ``tdb_resident`` (cap on the persistent grid of the
-        k_tdb_mfma / k_tdb_kron launches, 0 = the default grid; for tests and measurements, the results do not depend on it);
+        k_tdb_mfma / k_tdb_kron launches and of their product forms, 0 = the default grid; for tests and measurements, the results do not depend on it);
         include/dto_engine.h lists every option."""
         self._check(self._lib.dto_set_option(self._h, name.encode(), int(value)))
 

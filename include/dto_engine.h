@@ -317,9 +317,10 @@ int dto_eval_hessian(dto_handle* h, const double* Z, double sigma, const double*
 /* y = J w  /  y = J' w without materialising J on the host (evaluator.jl:406-456).  Unsharded handles only.  y is written in
    full.  Handles made of bilinear integrators (structured, small or general), DerivativeIntegrators and built-in knot constraints
    form no Jacobian at all: each integrator contracts its sweep with w and the handle never holds a jac_len-sized
-   allocation for the products.  Handles with a time-dependent or external integrator, an external constraint, more than
-   MAX_TYPES - 2 drives, or (J' w only) a general-path integrator created with eval_hessian = 0 evaluate the Jacobian into a
-   private device slab, allocated at the first product, and contract that.  The `_dev` forms below run the same device routine on
+   allocation for the products.  Handles with a time-dependent integrator (unless option "tdb_matrix_free_products" is 1, which
+   serves every device path of theirs, the structured one of DTO_FLAG_BLOCK_GENERATORS included) or an external integrator, an
+   external constraint, more than MAX_TYPES - 2 drives, or (J' w only) a general-path integrator created with eval_hessian = 0
+   evaluate the Jacobian into a private device slab, allocated at the first product, and contract that.  The `_dev` forms below run the same device routine on
    the caller's pointers and stream: both families return the same bits. */
 int dto_eval_jacobian_product(dto_handle* h, const double* Z, const double* w, double* y);
 int dto_eval_jacobian_transpose_product(dto_handle* h, const double* Z, const double* w, double* y);
@@ -476,19 +477,21 @@ int dto_bind_output_dev(dto_handle* h, int32_t vector, double* dptr);
  *   time-dependent integrators (DTO_FLAG_SHARED_GENERATORS), 1 .. that count; 1 is one launch per member through the lone kernel,
  *   the A/B switch.  Values outside the range are refused.  The results do not depend on it, bit for bit.
  *   "tdb_resident" (default 0 = every integrator's own grid): upper bound on the workgroups of the persistent-grid launches of
- *   time-dependent integrators -- k_tdb_mfma, its group form and its matrix-free products, k_tdb_kron -- which by default start
+ *   time-dependent integrators -- k_tdb_mfma, its group form and its matrix-free products, k_tdb_kron and its matrix-free products
+ *   (k_tdb_kron_product) -- which by default start
  *   min(owned knots + 1, two per compute unit) workgroups that walk the intervals, one scratch slot each.  1 .. the largest such grid
  *   among the handle's integrators on these kernels caps the grid (a launch takes the smaller of the value and its own grid, and the
  *   first slots of the scratch it already has); values outside the range are refused, and a handle without such an integrator takes
  *   0 only.  For tests and measurements: a small problem then makes a workgroup walk several intervals.  The results do not depend
  *   on it, bit for bit.
  *   "tdb_matrix_free_products" (default 0): 1 makes dto_eval_jacobian_product / _transpose_product (and their _dev forms) of a handle
- *   whose TimeDependentBilinearIntegrators all run on a dense device path (1..256 states without DTO_FLAG_BLOCK_GENERATORS structure)
- *   matrix-free: J w is the discrete scheme applied to two vectors, J' w to 1 + p forward vectors and one adjoint vector -- no
- *   propagator block, no staged Jacobian block, no value slab; a product then costs about a constraint call, not a Jacobian call.
- *   Such a handle may also hold bilinear and derivative integrators and built-in knot constraints; external integrators and
- *   constraints, and integrators on the structured time-dependent path, keep the slab route whatever the option says.  0 leaves every
- *   call as it was; values other than 0 and 1 are refused.  Results of the two routes agree to rounding (another summation order).
+ *   with device TimeDependentBilinearIntegrators matrix-free, on every device path of theirs: the dense ones (1..256 states) and the
+ *   structured one (DTO_FLAG_BLOCK_GENERATORS structure found and used: replicated-block generators, 33..512 states).  J w is the
+ *   discrete scheme applied to two vectors, J' w to 1 + p forward vectors and one adjoint vector -- on the structured path to as
+ *   many column groups of the b x b map -- with no propagator block, no staged Jacobian block, no value slab; a product then costs
+ *   about a constraint call, not a Jacobian call.  Such a handle may mix structured and dense time-dependent integrators and also
+ *   hold bilinear and derivative integrators and built-in knot constraints: it goes matrix-free as a whole.  External integrators
+ *   and constraints keep the slab route whatever the option says.  0 leaves every call as it was; values other than 0 and 1 are refused.  Results of the two routes agree to rounding (another summation order).
  *   "debug_bad_launch": TUNING builds only (libdto_engine_t.so) -- 1 gives the next callbacks' kernels an invalid launch
  *   configuration, which must come back as a non-zero return code with text (test of the error convention); the product
  *   library refuses the name. */
@@ -520,7 +523,8 @@ int dto_profile_reset(dto_handle* h);
  * copies of the leader's -E_k blocks to the followers of a DTO_FLAG_SHARED_GENERATORS group; its bytes are the bytes WRITTEN, one
  * block per follower and interval -- each launch reads a further block per interval -- and stay out of the third output of "all"),
  * "tdb_product" (the matrix-free J w / J' w of time-dependent integrators, option "tdb_matrix_free_products": one record per
- * integrator and product, flops as executed with padding; these launches do not count under "tdb_mfma"),
+ * integrator and product, dense or structured, flops as executed with padding; these launches do not count under "tdb_mfma" or
+ * "tdb_kron"),
  * "rollout" (dto_rollout / dto_rollout_dev: the gather of the -E_k blocks, the tree's batched products and the descent, flops as
  * executed with padding; its parts "rollout_gather" / "rollout_tree" / "rollout_descent", the last with the start and the copy into
  * the caller's layout; the tree's products do not count under "bgemm" / "bgemm_plain", and these names feed no other, "all" included;

@@ -843,8 +843,8 @@ function balanced_knot_ranges(cost::AbstractVector{Float64}, world::Integer)
     return best[1]                            # [(k_lo, k_hi)] 1-based inclusive, one per rank
 end
 
-# dto_set_option (include/dto_engine.h lists the names), e.g. set_option!(ev, "tdb_matrix_free_products", 1): J w / J' w of dense device
-# TimeDependentBilinearIntegrators without a value slab
+# dto_set_option (include/dto_engine.h lists the names), e.g. set_option!(ev, "tdb_matrix_free_products", 1): J w / J' w of device
+# TimeDependentBilinearIntegrators (dense or structured path) without a value slab
 function set_option!(ev::GPUEvaluator, name::AbstractString, value::Integer)
     v64 = Int64(value)
     check(ev, @ccall lib.dto_set_option(ev.handle::Ptr{Cvoid}, name::Cstring, v64::Int64)::Cint)

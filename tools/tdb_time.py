@@ -17,6 +17,11 @@ the same problem, through host pointers, one call each.  One JSON line per shape
                                                               # handles alternated in one process; order 1; 72 x 500, 128 x 500,
                                                               # 162 x 250 both ways, 512 x 100 flagged only (the dense kernels stop
                                                               # at 256 states)
+    python tools/tdb_time.py --block 1 --products 1           # the structured path's device-pointer J w / J' w (k_tdb_kron_product):
+                                                              # two flagged handles of one problem, option "tdb_matrix_free_products"
+                                                              # 1 and 0 (the slab route), their calls alternated in one process,
+                                                              # beside each handle's eval_constraint and Jacobian; --products-route
+                                                              # slab times the slab handle alone
     python tools/tdb_time.py --products 1 --shapes 4x1000,64x1000,128x500,256x250 --orders 1 --host ""
                                                               # adds the device-pointer J w / J' w with the handle option
                                                               # "tdb_matrix_free_products" on (csrc/dto_tdb.hip and dto_tdb_mfma.hip,
@@ -100,6 +105,59 @@ def measure_block(prob, reps, with_dense, sigma=0.7):
             for k, ev in evs.items():
                 out[f"{k}_{name}_ms"] = round(statistics.median(ts[k]), 4)
                 prof = "tdb_kron" if k == "flagged" else "tdb_mfma"
+                ev.profile_enable(True); ev.profile_reset(); fns[k][name](); torch.cuda.synchronize()
+                ms, launches, fl = ev.profile_get(prof)
+                ev.profile_enable(False)
+                out[f"{k}_{name}_{prof}_ms"] = round(ms, 4)
+                out[f"{k}_{name}_{prof}_TFLOPs"] = round(fl / ms * 1e-9, 3) if ms > 0 else None
+        return out
+    finally:
+        for ev in evs.values():
+            ev.close()
+
+
+def measure_block_products(prob, reps, route):
+    """Flagged handles of one problem with option "tdb_matrix_free_products" at 1 and at 0 (route "slab": the latter alone), their
+    timed calls alternated as in measure_block; eval_constraint, the Jacobian, J w and J' w through device pointers.  Kernel time
+    and rate of the products from "tdb_product" (matrix-free) or "tdb_kron" (slab: the Jacobian call inside the product)."""
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    evs = {}
+    if route == "matrix_free":
+        evs["matrix_free"] = dto_amd.Evaluator(prob, eval_hessian=True, block_generators=True)
+        evs["matrix_free"].set_option("tdb_matrix_free_products", 1)
+    evs["slab"] = dto_amd.Evaluator(prob, eval_hessian=True, block_generators=True)
+    try:
+        e0 = evs["slab"]
+        Z = torch.from_numpy(prob.trajectory.vec()).to(dev)
+        gen = torch.Generator(device="cpu").manual_seed(2)
+        w = torch.randn(e0.n_variables, generator=gen, dtype=torch.float64).to(dev)
+        wt = torch.randn(e0.n_constraints, generator=gen, dtype=torch.float64).to(dev)
+        con = torch.empty(e0.n_constraints, dtype=torch.float64, device=dev)
+        J = torch.empty(e0.n_jacobian_entries, dtype=torch.float64, device=dev)
+        y = torch.empty(e0.n_constraints, dtype=torch.float64, device=dev)
+        yt = torch.empty(e0.n_variables, dtype=torch.float64, device=dev)
+        out = {"blocks": e0.integrator_blocks(0), "jac_slab_MiB": round(8.0 * e0.n_jacobian_entries / 2**20, 1)}
+
+        def calls(ev):
+            return {"constraint": lambda: ev.eval_constraint_dev(Z.data_ptr(), con.data_ptr(), st),
+                    "jacobian": lambda: ev.eval_jacobian_dev(Z.data_ptr(), J.data_ptr(), st),
+                    "jw": lambda: ev.eval_jacobian_product_dev(Z.data_ptr(), w.data_ptr(), y.data_ptr(), st),
+                    "jtw": lambda: ev.eval_jacobian_transpose_product_dev(Z.data_ptr(), wt.data_ptr(), yt.data_ptr(), st)}
+
+        fns = {k: calls(ev) for k, ev in evs.items()}
+        for name in ("constraint", "jacobian", "jw", "jtw"):
+            for k in evs:
+                spent = 0.0
+                while spent < 30.0:
+                    spent += one_call_ms(fns[k][name])
+            ts = {k: [] for k in evs}
+            for _ in range(reps):
+                for k in evs:
+                    ts[k].append(one_call_ms(fns[k][name]))
+            for k, ev in evs.items():
+                out[f"{k}_{name}_ms"] = round(statistics.median(ts[k]), 4)
+                prof = "tdb_product" if k == "matrix_free" and name in ("jw", "jtw") else "tdb_kron"
                 ev.profile_enable(True); ev.profile_reset(); fns[k][name](); torch.cuda.synchronize()
                 ms, launches, fl = ev.profile_get(prof)
                 ev.profile_enable(False)
@@ -197,7 +255,7 @@ def main():
     ap.add_argument("--small", type=int, default=0, help="1: 4 .. 64 states (k_tdb), 2 drives, order 1, host pointers; nothing else")
     ap.add_argument("--block", type=int, default=0, help="1: replicated-block generators, flagged against unflagged handles; nothing else")
     ap.add_argument("--block-shapes", default="6x500,8x500,9x250,16x100", help="with --block: comma-separated levels x knots (states = 2 levels^2)")
-    ap.add_argument("--products", type=int, default=0, help="1: time the device-pointer J w / J' w (option tdb_matrix_free_products on) instead of the Hessian")
+    ap.add_argument("--products", type=int, default=0, help="1: time the device-pointer J w / J' w (option tdb_matrix_free_products on) instead of the Hessian; with --block 1 on flagged handles")
     ap.add_argument("--products-route", default="matrix_free", choices=["matrix_free", "slab"], help="with --products: slab leaves the option alone")
     a = ap.parse_args()
     if a.block:
@@ -205,7 +263,11 @@ def main():
             levels, N = (int(x) for x in s.lower().split("x"))
             n = 2 * levels * levels
             out = {"n": n, "levels": levels, "knots": N, "drives": a.drives, "substeps": a.substeps, "order": 1}
-            out.update(measure_block(block_problem(levels, N, a.drives, 1, a.substeps), a.reps, with_dense=n <= 256))
+            prob = block_problem(levels, N, a.drives, 1, a.substeps)
+            if a.products:
+                out.update(measure_block_products(prob, a.reps, a.products_route))
+            else:
+                out.update(measure_block(prob, a.reps, with_dense=n <= 256))
             print(json.dumps(out), flush=True)
         return
     if a.small:
