@@ -203,17 +203,12 @@ void build_structure(dto_handle* h, const double* Z0) {
         extra[ent[i].first]++;
     }
     h->colptr.assign(nv + 1, 0);
-    for (int64_t kn = 0; kn < h->N; ++kn) {
-        const int64_t per = (int64_t)h->D * col_cnt(h, kn);
-        for (int j = 0; j < h->z; ++j) {
-            const int64_t c = kn * h->z + j;
-            h->colptr[c + 1] = h->colptr[c] + per + extra[c];
-        }
-    }
-    for (int64_t c = h->N * h->z; c < nv; ++c) h->colptr[c + 1] = h->colptr[c] + extra[c];  // global columns: only NonlinearGlobalConstraint rows
-    h->jac_nnz = h->colptr[nv];
+    const SlabDims L = slab_dims(h);
     const int64_t z = h->z;
-    h->hess_block_nnz = h->N * (z * (z + 1) / 2) + h->K * z * z;  // evaluator.jl:201-202 on the block pattern
+    // (global columns, kn >= N: only NonlinearGlobalConstraint rows)
+    for (int64_t c = 0; c < nv; ++c) h->colptr[c + 1] = h->colptr[c] + jac_con_off(L, c / z) + extra[c];
+    h->jac_nnz = h->colptr[nv];
+    h->hess_block_nnz = hess_block_start(L, h->N);  // N tri + K z^2: evaluator.jl:201-202 on the block pattern
     // tail: entries whose column is a global variable (global columns follow every knot column in the CSC order).
     // GlobalObjective / GlobalKnotPointObjective mark their whole index block (global_objectives.jl:89-101, 277-300),
     // NonlinearGlobalConstraint contributes the non-zeros of its Hessian at mu = ones (evaluator.jl:166)
@@ -786,7 +781,6 @@ void add_external_objectives(dto_handle* h, const dto_problem_desc* d) {
 
 // the listings of constraint c at owned knots: their local rows (from lrow on) and their places in the Jacobian slab
 void place_constraint(dto_handle* h, ConHost& c, int64_t& lrow) {
-    const KProb& P = h->P;
     std::vector<int64_t> times, lrows, tidx, jpos;
     std::vector<int32_t> hess_on;
     for (int64_t i = 0; i < c.n_times_total; ++i) {
@@ -804,7 +798,7 @@ void place_constraint(dto_handle* h, ConHost& c, int64_t& lrow) {
                 int64_t pos = -1;
                 for (size_t e = lo; e < h->con_cols.size() && h->con_cols[e] == col; ++e)
                     if (h->con_rows[e] == c.row_off + i * c.g_dim + r) {
-                        pos = h->colptr[col] + (int64_t)h->D * col_cnt(h, kn) + (int64_t)(e - lo) - P.jac_lo;
+                        pos = con_entry_pos(h, col, (int64_t)(e - lo));
                         break;
                     }
                 jpos.push_back(pos);

@@ -83,16 +83,11 @@ inline void count_sweep_form(dto_handle* h, int form) {
     if (h->profiling) ++h->sweep_forms[form];
 }
 
+}  // namespace
+
 // ------------------------------------------------------------------------------------------
 // structure
 // ------------------------------------------------------------------------------------------
-
-int64_t hess_block_start(const dto_handle* h, int64_t kn) {
-    const int64_t z = h->z, tri = z * (z + 1) / 2;
-    return kn == 0 ? 0 : tri + (kn - 1) * (z * z + tri);
-}
-
-}  // namespace
 
 namespace dto {
 
@@ -106,8 +101,8 @@ ShardExtents shard_extents(const dto_handle* h, int64_t k_lo, int64_t k_hi) {
     e.grad_len = c_hi - c_lo + (last ? h->gd : 0);
     e.jac_lo = h->colptr[c_lo];
     e.jac_len = h->colptr[last ? h->n_vars : c_hi] - e.jac_lo;
-    e.hess_lo = hess_block_start(h, kn_lo);
-    e.hess_len = hess_block_start(h, kn_lo + n_knots) - e.hess_lo + (last ? (int64_t)h->tail_rows.size() : 0);
+    e.hess_lo = hess_block_start(slab_dims(h), kn_lo);
+    e.hess_len = hess_block_start(slab_dims(h), kn_lo + n_knots) - e.hess_lo + (last ? (int64_t)h->tail_rows.size() : 0);
     return e;
 }
 
@@ -1161,16 +1156,16 @@ void build_jac_plan(dto_handle* h) {
     // the -E_k block of a lone general-path bilinear integrator is written by the propagator chain alone (do_jacobian): final
     // with its chain chunk
     const bool lone = lone_general_bilinear(h);
+    const SlabDims L = slab_dims(h);
     for (int64_t kn = P.kn_lo; kn < P.kn_lo + P.n_knots; ++kn) {
-        const int has_prev = kn >= 1, has_own = kn < h->K;
-        const int cnt = has_prev + has_own;
+        const bool has_prev = jac_has_part(L, kn, 0), has_own = jac_has_part(L, kn, 1);
         for (int j = 0; j < z; ++j) {
             const int64_t c = kn * z + j;
             const int64_t base = h->colptr[c] - P.jac_lo;
             int pre = 0;
             for (size_t i = 0; i < h->integ_kind.size(); ++i) {
                 const int d = h->integ_dim[i];
-                const int64_t prev_at = base + (int64_t)pre * cnt, own_at = prev_at + (has_prev ? d : 0);
+                const int64_t prev_at = base + jac_part_off(L, kn, pre, d, 0), own_at = base + jac_part_off(L, kn, pre, d, 1);
                 const int kind = h->integ_kind[i];
                 if (kind == DTO_INTEGRATOR_BILINEAR) {
                     const BilHost& bh = h->bil[h->integ_index[i]];
@@ -1198,7 +1193,7 @@ void build_jac_plan(dto_handle* h) {
                 }
                 pre += d;
             }
-            var(base + (int64_t)h->D * cnt, h->colptr[c + 1] - h->colptr[c] - (int64_t)h->D * cnt);  // constraint entries
+            var(base + jac_con_off(L, kn), h->colptr[c + 1] - h->colptr[c] - jac_con_off(L, kn));  // constraint entries
         }
     }
     if (h->k_hi == h->N) {  // global-variable columns ride with the last knot: constraint entries only
@@ -1255,7 +1250,7 @@ void build_hess_plan(dto_handle* h) {
     for (auto& c : h->con)
         if (!c.global)
             for (int64_t kn : c.times0) add_pairs(kn, c.comps);
-    const int64_t tri = (int64_t)z * (z + 1) / 2;
+    const SlabDims L = slab_dims(h);
     std::vector<uint8_t> mask((size_t)z * z);
     auto var = [&](int64_t at, int64_t n) { if (n > 0) { p.start.push_back(at); p.len.push_back(n); } };
     for (int64_t kn = P.kn_lo; kn < P.kn_lo + P.n_knots; ++kn) {
@@ -1280,13 +1275,11 @@ void build_hess_plan(dto_handle* h) {
             }
             for (auto& ab : extra[(size_t)(kn - P.kn_lo)]) set(ab.first, ab.second);
         }
-        const int64_t blk0 = hess_block_start(h, kn) - P.hess_lo;
+        const int64_t blk0 = hess_block_start(L, kn) - P.hess_lo;
         for (int b = 0; b < z; ++b) {
-            int64_t col = blk0 + (kn == 0 ? (int64_t)b * (b + 1) / 2 : (int64_t)b * z + (int64_t)b * (b + 1) / 2);
-            if (kn >= 1) {
-                if (dense_blocks) var(col, z);  // off-diagonal block (kn-1, kn): the cross part of interval kn-1
-                col += z;
-            }
+            int64_t col = blk0 + hess_col_start(L, kn, b);
+            if (dense_blocks) var(col, hess_off_width(L, kn));  // off-diagonal block (kn-1, kn): the cross part of interval kn-1
+            col += hess_off_width(L, kn);
             int a = 0;
             while (a <= b) {
                 while (a <= b && !mask[(size_t)a + (size_t)z * b]) ++a;
@@ -1295,7 +1288,6 @@ void build_hess_plan(dto_handle* h) {
                 var(col + a0, a - a0);
             }
         }
-        (void)tri;
     }
     if (h->k_hi == h->N) var(h->hess_block_nnz - P.hess_lo, (int64_t)h->tail_rows.size());  // global-column tail
 }
@@ -1526,50 +1518,26 @@ void upload_Z(dto_handle* h, const double* Z) {
 
 // ---- Hessian-vector products (dto_eval_hessian_product[_dev], dto_hess_product.hip)
 
-// Walks positions of the unsharded Hessian slab in slab order and names the (row, col) of each, 0-based: the closed forms
-// dto_hessian_structure emits (knot blocks column by column, then the CSC tail of the global-variable columns).
+// Walks positions of the unsharded Hessian slab in slab order and names the (row, col) of each, 0-based: the knot blocks
+// (HessBlockCursor, dto_slab_layout.h), then the CSC tail of the global-variable columns.
 struct HessCursor {
     const dto_handle* h;
-    int64_t z, tri, blk;
-    int64_t kn = 0, b = 0, r = 0;  // knot block, column inside it, entry inside that column
-    int64_t j = 0, e = -1;         // e >= 0: entry e of the tail, in global column j
-    explicit HessCursor(const dto_handle* h_) : h(h_), z(h_->z), tri(h_->z * (int64_t)(h_->z + 1) / 2), blk(h_->z * (int64_t)h_->z + tri) {}
-    int64_t col_off(int64_t bb) const { return kn == 0 ? bb * (bb + 1) / 2 : bb * z + bb * (bb + 1) / 2; }
+    HessBlockCursor blk;
+    int64_t j = 0, e = 0;  // past the blocks: entry e of the tail, in global column j
+    explicit HessCursor(const dto_handle* h_) : h(h_), blk(slab_dims(h_)) {}
     void tail_col() { while (j < h->gd && e >= h->tail_colptr[(size_t)j + 1]) ++j; }
     void seek(int64_t pos) {
-        if (pos >= h->hess_block_nnz) {
-            e = pos - h->hess_block_nnz;
-            j = 0;
-            tail_col();
-            return;
-        }
-        e = -1;
-        kn = pos < tri ? 0 : 1 + (pos - tri) / blk;
-        const int64_t local = pos - hess_block_start(h, kn);
-        int64_t lo = 0, hi = z - 1;  // the last column whose entries start at or before `local`
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) / 2;
-            if (col_off(mid) <= local) lo = mid; else hi = mid - 1;
-        }
-        b = lo;
-        r = local - col_off(b);
+        blk.seek(std::min(pos, h->hess_block_nnz));
+        e = std::max<int64_t>(pos - h->hess_block_nnz, 0);
+        j = 0;
+        if (!blk.in_blocks()) tail_col();
     }
     void next() {
-        if (e >= 0) { ++e; tail_col(); return; }
-        if (++r < (kn == 0 ? b + 1 : z + b + 1)) return;
-        r = 0;
-        if (++b < z) return;
-        b = 0;
-        if (++kn < h->N) return;
-        e = 0;
-        j = 0;
-        tail_col();
+        if (blk.in_blocks()) blk.next(); else ++e;
+        if (!blk.in_blocks()) tail_col();
     }
-    void at(int64_t& row, int64_t& col) const {
-        if (e >= 0) { row = h->tail_rows[(size_t)e]; col = h->N * z + j; return; }
-        col = kn * z + b;
-        row = kn == 0 ? r : (r < z ? (kn - 1) * z + r : kn * z + (r - z));
-    }
+    int64_t row() const { return blk.in_blocks() ? blk.row() : h->tail_rows[(size_t)e]; }
+    int64_t col() const { return blk.in_blocks() ? blk.col() : h->N * h->z + j; }
 };
 
 // Once per handle, on the host: the row-major copy of both triangles.  Its entries are the slab positions that can be non-zero
@@ -1597,8 +1565,7 @@ void build_hp_index(dto_handle* h) {
             if (a < 0 || end > h->info.hess_len) throw HipError{"Hessian-vector products: hand-off plan outside the slab"};
             cur.seek(a);
             for (int64_t q = a; q < end; ++q, cur.next()) {
-                int64_t row, col;
-                cur.at(row, col);
+                const int64_t row = cur.row(), col = cur.col();
                 if (row < 0 || row >= nv || col < 0 || col >= nv) throw HipError{"Hessian-vector products: entry outside the matrix"};
                 emit(row, col, q);
             }
@@ -1838,36 +1805,29 @@ int dto_jacobian_structure(const dto_handle* h, int64_t first, int64_t count, in
     if (count == 0) return 0;
     // column containing `first`
     int64_t c = std::upper_bound(h->colptr.begin(), h->colptr.end(), first) - h->colptr.begin() - 1;
+    const SlabDims L = slab_dims(h);
     int64_t written = 0;
-    const int64_t nzcols = h->N * h->z;
-    for (; c < nzcols && written < count; ++c) {
-        const int64_t kn = c / h->z;
-        int64_t pos = h->colptr[c];
-        auto emit = [&](int64_t row0) {
-            if (pos >= first && written < count) {
-                rows[written] = row0 + 1;
-                cols[written] = c + 1;
-                ++written;
-            }
-            ++pos;
+    for (; c < h->n_vars && h->colptr[c] < first + count; ++c) {
+        const int64_t kn = c / h->z;  // >= N: a global-variable column, NonlinearGlobalConstraint rows only
+        auto put = [&](int64_t pos, int64_t row0) {
+            if (pos < first || pos >= first + count) return;
+            rows[pos - first] = row0 + 1;
+            cols[pos - first] = c + 1;
+            ++written;
         };
-        // integrator rows: for each integrator, interval kn-1 then interval kn
+        // integrator rows: for each integrator, interval kn-1 (part 0) then interval kn (part 1)
+        int pre = 0;
         for (size_t i = 0; i < h->integ_kind.size(); ++i) {
             const int d = h->integ_dim[i];
-            const int64_t off = h->integ_row_off[i];
-            if (kn >= 1) for (int r = 0; r < d; ++r) emit(off + (kn - 1) * d + r);
-            if (kn < h->K) for (int r = 0; r < d; ++r) emit(off + kn * d + r);
+            for (int part = 0; part < 2; ++part)
+                if (jac_has_part(L, kn, part))
+                    for (int r = 0; r < d; ++r)
+                        put(h->colptr[c] + jac_part_off(L, kn, pre, d, part) + r, h->integ_row_off[i] + (kn - 1 + part) * d + r);
+            pre += d;
         }
-        for (size_t e = con_lower(h, c); e < h->con_cols.size() && h->con_cols[e] == c; ++e) emit(h->con_rows[e]);
-    }
-    for (; c < h->n_vars && written < count; ++c) {  // global-variable columns: NonlinearGlobalConstraint rows only
-        int64_t pos = h->colptr[c];
-        for (size_t e = con_lower(h, c); e < h->con_cols.size() && h->con_cols[e] == c; ++e, ++pos)
-            if (pos >= first && written < count) {
-                rows[written] = h->con_rows[e] + 1;
-                cols[written] = c + 1;
-                ++written;
-            }
+        const size_t e0 = con_lower(h, c);
+        for (size_t e = e0; e < h->con_cols.size() && h->con_cols[e] == c; ++e)
+            put(h->colptr[c] + jac_con_off(L, kn) + (int64_t)(e - e0), h->con_rows[e]);
     }
     return written == count ? 0 : 1;
 }
@@ -1875,33 +1835,13 @@ int dto_jacobian_structure(const dto_handle* h, int64_t first, int64_t count, in
 int dto_hessian_structure(const dto_handle* h, int64_t first, int64_t count, int64_t* rows, int64_t* cols) {
     if (!h || !rows || !cols || first < 0 || count < 0 || first + count > h->hess_nnz) return 1;
     if (count == 0) return 0;
-    const int64_t z = h->z, tri = z * (z + 1) / 2, blk = z * z + tri;
-    int64_t kn = first < tri ? 0 : 1 + (first - tri) / blk;
-    int64_t written = 0;
-    for (; kn < h->N && written < count; ++kn) {
-        int64_t pos = hess_block_start(h, kn);
-        for (int b = 0; b < z && written < count; ++b) {
-            const int64_t c = kn * z + b;
-            auto emit = [&](int64_t row0) {
-                if (pos >= first && written < count) {
-                    rows[written] = row0 + 1;
-                    cols[written] = c + 1;
-                    ++written;
-                }
-                ++pos;
-            };
-            if (kn >= 1) for (int a = 0; a < z; ++a) emit((kn - 1) * z + a);
-            for (int a = 0; a <= b; ++a) emit(kn * z + a);
-        }
+    HessCursor cur(h);
+    cur.seek(first);
+    for (int64_t i = 0; i < count; ++i, cur.next()) {
+        rows[i] = cur.row() + 1;
+        cols[i] = cur.col() + 1;
     }
-    for (int j = 0; j < h->gd && written < count; ++j)  // tail: global-variable columns
-        for (int64_t e = h->tail_colptr[j]; e < h->tail_colptr[j + 1] && written < count; ++e)
-            if (h->hess_block_nnz + e >= first) {
-                rows[written] = h->tail_rows[e] + 1;
-                cols[written] = h->N * z + j + 1;
-                ++written;
-            }
-    return written == count ? 0 : 1;
+    return 0;
 }
 
 int dto_constraint_bounds(const dto_handle* h, double* lower, double* upper) {
@@ -2139,10 +2079,9 @@ static void jac_product(dto_handle* h, const double* dZ, const double* dw, doubl
         std::vector<int64_t> fill(rptr.begin(), rptr.end() - 1);
         for (size_t e = 0; e < h->con_rows.size(); ++e) {   // CSC order: ascending column, so every row's list ends up ascending too
             const int64_t col = h->con_cols[e], r = h->con_rows[e] - h->n_dyn;
-            const int64_t kn = col / h->z;
             const int64_t at = fill[(size_t)r]++;
             rcol[(size_t)at] = col;
-            rpos[(size_t)at] = h->colptr[col] + (int64_t)h->D * col_cnt(h, kn) + ((int64_t)e - base[(size_t)col]) - h->P.jac_lo;
+            rpos[(size_t)at] = con_entry_pos(h, col, (int64_t)e - base[(size_t)col]);
         }
         h->d_crow_ptr = own(h, dupload(rptr));
         h->d_crow_col = own(h, dupload(rcol));

@@ -364,12 +364,17 @@ inline int fail(dto_handle* h, const std::string& m) {
 
 inline int pad64(int n) { return ((n + 63) / 64) * 64; }
 
-// number of integrator rows touching a column of knot kn (0-based): D per adjacent interval
-inline int col_cnt(const dto_handle* h, int64_t kn) { return kn >= h->N ? 0 : (kn >= 1 ? 1 : 0) + (kn < h->K ? 1 : 0); }
+// the dimensions every position in the two value slabs follows from (dto_slab_layout.h states the layout)
+inline SlabDims slab_dims(const dto_handle* h) { return SlabDims{h->N, h->K, (int32_t)h->z, (int32_t)h->D}; }
 
 // first constraint-pattern entry of column c
 inline size_t con_lower(const dto_handle* h, int64_t c) {
     return std::lower_bound(h->con_cols.begin(), h->con_cols.end(), c) - h->con_cols.begin();
+}
+
+// position in this handle's Jacobian slab of the i-th constraint-pattern entry of column col
+inline int64_t con_entry_pos(const dto_handle* h, int64_t col, int64_t i) {
+    return h->colptr[col] + jac_con_off(slab_dims(h), col / h->z) + i - h->P.jac_lo;
 }
 
 // value slabs of the handle that owns knots k_lo..k_hi (1-based, inclusive): positions inside the global vectors

@@ -6,6 +6,7 @@
 
 #include <cstdlib>
 
+#include "dto_slab_layout.h"  // where every Jacobian and Hessian entry sits in its value slab
 #include "dto_sweep_plan.h"   // sweep planning: step budget, launch shapes (SweepTypes, the *SweepPlan structs and planners), form choice
 
 namespace dto {
@@ -90,31 +91,26 @@ struct KDer {  // DerivativeIntegrator (derivative_integrator.jl:26-49)
     int64_t row_off, lrow_off;
 };
 
-// position (inside the shard-local value slab) of Jacobian entry (row r of integrator block,
-// column `comp` of knot kn); part 0 = rows of interval kn-1, part 1 = rows of interval kn.
+// Positions inside the shard-local value slabs.  The layout is stated in dto_slab_layout.h; its functions read N, K, z, D of whatever
+// they are handed, and the kernels hand them their KProb, so no field is loaded that was not loaded before.
+// Jacobian entry (row r of integrator block, column `comp` of knot kn); part 0 = rows of interval kn-1, part 1 = rows of interval kn.
 __host__ __device__ inline int64_t jac_pos(const KProb& P, const int64_t* colptr, int64_t kn, int comp,
                                            int pre, int d_i, int part, int r) {
-    const int has_prev = kn >= 1, has_own = kn < P.K;
-    const int cnt = has_prev + has_own;
-    return colptr[kn * P.z + comp] + (int64_t)pre * cnt + ((part == 1 && has_prev) ? d_i : 0) + r - P.jac_lo;
+    const int cnt = jac_knot_cnt(P, kn);
+    return colptr[kn * P.z + comp] + jac_part_off_cnt(cnt, kn, pre, d_i, part) + r - P.jac_lo;
 }
 
-// position of upper-triangular Hessian entry (a <= b, knot-local comps) of diagonal block kn
-// entry (row a of knot kn-1, column b of knot kn) of the off-diagonal block, kn >= 1
+// Hessian entry (row a of knot kn-1, column b of knot kn) of the off-diagonal block, kn >= 1.  This is hess_inner_col_pos of
+// dto_slab_layout.h spelled out: as a forward to it, k_extint_hess adds the two halves of its last address in the other order
+// (DESIGN 3.1).  tests/test_slab_layout_header.py holds the two together.
 __host__ __device__ inline int64_t hess_pos_off(const KProb& P, int64_t kn, int a, int b) {
     const int64_t z = P.z;
     const int64_t tri = z * (z + 1) / 2;
     return tri + (kn - 1) * (z * z + tri) + (int64_t)b * z + (int64_t)b * (b + 1) / 2 + a - P.hess_lo;
 }
+// upper-triangular Hessian entry (a <= b, knot-local comps) of diagonal block kn
 __host__ __device__ inline int64_t hess_pos(const KProb& P, int64_t kn, int a, int b) {
-    const int64_t z = P.z;
-    const int64_t tri = z * (z + 1) / 2;
-    int64_t colstart;
-    if (kn == 0)
-        colstart = (int64_t)b * (b + 1) / 2;
-    else
-        colstart = tri + (kn - 1) * (z * z + tri) + (int64_t)b * z + (int64_t)b * (b + 1) / 2 + z;
-    return colstart + a - P.hess_lo;
+    return hess_diag_pos(P, kn, b) + a - P.hess_lo;
 }
 
 // ------------------------------------------------------------------ launch wrappers (dto_kernels.hip)

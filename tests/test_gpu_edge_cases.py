@@ -101,6 +101,32 @@ def test_minimum_sizes():
     _compare(p)
 
 
+@pytest.mark.parametrize("N", [2, 3])
+def test_four_states_one_drive_at_two_and_three_knots(N):
+    """The shortest horizons of the value-slab layout (csrc/dto_slab_layout.h): N = 2 has no knot with two adjacent intervals, N = 3
+    is the first with one.  Host-pointer Jacobian and Hessian (structure bit-exact, values at 1e-10 / 1e-8 max(1, |ref|)) and the
+    Hessian-vector product (1e-8, the Hessian's bar), each against the oracle."""
+    import dto_amd
+    import scipy.sparse as sp
+    p = O.make_scaled_problem(N, 4, 1, seed=40 + N, with_constraint=True)
+    _compare(p)
+    ev_o = O.OracleEvaluator(p)
+    ev = dto_amd.Evaluator(to_engine(p))
+    try:
+        rng = np.random.default_rng(N)
+        mu, v = rng.standard_normal(ev.n_constraints), rng.standard_normal(ev.n_variables)
+        y = np.full(ev.n_variables, np.nan)
+        ev.eval_hessian_lagrangian_product(y, p.Z0, v, 0.7, mu)
+        r1, c1 = ev_o.hessian_structure1()   # the upper triangle; an off-diagonal entry counts for (i, j) and (j, i)
+        H = sp.coo_matrix((ev_o.eval_hessian_lagrangian(p.Z0, 0.7, mu), (np.asarray(r1) - 1, np.asarray(c1) - 1)),
+                          shape=(v.size, v.size)).tocsr()
+        err = rel_err(y, H @ v + H.T @ v - H.diagonal() * v)
+        print(N, err)
+        assert np.all(np.isfinite(y)) and err <= 1e-8, err
+    finally:
+        ev.close()
+
+
 def test_zero_controls_and_zero_state():
     p = O.make_scaled_problem(5, 6, 2, seed=4)
     Z = p.Z0.copy()
