@@ -73,11 +73,15 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21 };
 // CAT_ROLLOUT .. CAT_ROLLOUT_DESCENT ("rollout" = its parts "rollout_gather" + "rollout_tree" + "rollout_descent"): the gather, the
 // tree's products and the descent (with the start and the copy into the caller's layout) of dto_rollout[_dev], flops as executed with
 // padding; the tree's products run launch_bgemm_plain and count HERE, not under "bgemm_plain"; they feed no other name, "all" included
 inline bool is_rollout_cat(int cat) { return cat >= CAT_ROLLOUT && cat <= CAT_ROLLOUT_DESCENT; }
+// CAT_DYNSOLVE_TREE, CAT_DYNSOLVE_SCAN ("dynsolve" = "dynsolve_tree" + "dynsolve_scan"): of dto_dynamics_solve[_dev], the gather and
+// the tree's products of a rebuild, and the loader, the offsets' up-sweep, the descent and the copy into the caller's layout; flops as
+// executed with padding.  Like the rollout's they feed no other name, "all" included.
+inline bool is_dynsolve_cat(int cat) { return cat == CAT_DYNSOLVE_TREE || cat == CAT_DYNSOLVE_SCAN; }
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
 inline void count_sweep_form(dto_handle* h, int form) {
     if (h->profiling) ++h->sweep_forms[form];
@@ -2140,12 +2144,13 @@ static double* grow_workspace(dto_handle* h, double*& p, size_t& cap, size_t dou
 }
 
 // What a rollout call names: refused with text before anything is enqueued.  Returns the kernels' record of the integrator.
-static KRollout rollout_args(const dto_handle* h, int32_t integrator, int32_t n_cols, int32_t mode, bool has_X0) {
-    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{"dto_rollout needs an unsharded handle (k_lo, k_hi = the whole trajectory)"};
+static KRollout rollout_args(const dto_handle* h, int32_t integrator, int32_t n_cols, int32_t mode, bool has_X0, const char* who_ = "dto_rollout") {
+    const std::string who(who_);
+    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{who + " needs an unsharded handle (k_lo, k_hi = the whole trajectory)"};
     if (integrator < 0 || integrator >= (int32_t)h->integ_kind.size())
-        throw HipError{"dto_rollout: integrator " + std::to_string(integrator) + " is out of range (the handle has " +
+        throw HipError{who + ": integrator " + std::to_string(integrator) + " is out of range (the handle has " +
                        std::to_string(h->integ_kind.size()) + ")"};
-    if (mode != DTO_ROLLOUT_ALL && mode != DTO_ROLLOUT_FINAL) throw HipError{"dto_rollout: mode takes DTO_ROLLOUT_ALL (0) or DTO_ROLLOUT_FINAL (1)"};
+    if (mode != DTO_ROLLOUT_ALL && mode != DTO_ROLLOUT_FINAL) throw HipError{who + ": mode takes DTO_ROLLOUT_ALL (0) or DTO_ROLLOUT_FINAL (1)"};
     KRollout R{};
     const int kind = h->integ_kind[integrator], idx = h->integ_index[integrator];
     if (kind == DTO_INTEGRATOR_BILINEAR) {
@@ -2155,20 +2160,40 @@ static KRollout rollout_args(const dto_handle* h, int32_t integrator, int32_t n_
         const TdbHost& t = h->tdb[idx];
         R.n = t.k.n; R.x_off = t.k.x_off; R.pre = t.place.pre;
     } else if (kind == DTO_INTEGRATOR_DERIVATIVE) {
-        throw HipError{"dto_rollout: integrator " + std::to_string(integrator) + " is a DerivativeIntegrator: it has no propagator"};
+        throw HipError{who + ": integrator " + std::to_string(integrator) + " is a DerivativeIntegrator: it has no propagator"};
     } else {
-        throw HipError{"dto_rollout: integrator " + std::to_string(integrator) + " is evaluated on the host (DTO_INTEGRATOR_EXTERNAL): its "
+        throw HipError{who + ": integrator " + std::to_string(integrator) + " is evaluated on the host (DTO_INTEGRATOR_EXTERNAL): its "
                        "Jacobian block is not known to be a propagator"};
     }
     if (n_cols < 1 || n_cols > R.n)
-        throw HipError{"dto_rollout: n_cols = " + std::to_string(n_cols) + ", allowed 1 .. x_dim = " + std::to_string(R.n)};
-    if (!has_X0 && n_cols != 1) throw HipError{"dto_rollout: X0 = NULL (the state of knot 1 of Z) takes n_cols = 1"};
+        throw HipError{who + ": n_cols = " + std::to_string(n_cols) + ", allowed 1 .. x_dim = " + std::to_string(R.n)};
+    if (!has_X0 && n_cols != 1) throw HipError{who + ": X0 = NULL (the state of knot 1 of Z) takes n_cols = 1"};
     R.npad = pad64(R.n);
     R.n_cols = n_cols;
     R.col_pad = rollout_col_pad(n_cols);
     R.K = h->K;
     R.L = rollout_levels(std::max<int64_t>(R.K, 1));
     return R;
+}
+
+// Gather and up-sweep, for the rollout and the solves alike: the product tree of R's integrator at dZ, in d_roll_tree.  The launches
+// count under `cat_gather` and `cat_tree`.
+static double* build_rollout_tree(dto_handle* h, const KRollout& R, const double* dZ, hipStream_t st, int cat_gather, int cat_tree) {
+    const int npad = R.npad, L = R.L;
+    const size_t nn = (size_t)npad * npad;
+    double* tree = grow_workspace(h, h->d_roll_tree, h->roll_tree_cap, rollout_tree_bytes(npad, R.K) / sizeof(double));
+    double* slab = jac_scratch(h);
+    // the whole Jacobian, tangent sweep included: the x_k columns of the integrator then hold -E_k on every path
+    do_jacobian(h, dZ, slab, st);   // (external blocks are staged as for dto_eval_jacobian_dev)
+    { ProfScope ps(h, st, cat_gather, 0.0); launch_rollout_leaves(st, h->P, R, slab, tree); }
+    // up-sweep: level l + 1 = (second half of level l) * (first half), one contiguous batch
+    for (int l = 0; l < L; ++l) {
+        const int nb = (int)rollout_level_len(L, l + 1);
+        const double* lo = tree + (size_t)rollout_level_off(L, l) * nn;
+        ProfScope ps(h, st, cat_tree, 2.0 * npad * (double)nn * nb);
+        launch_bgemm_plain(st, npad, nb, lo + (size_t)nb * nn, lo, tree + (size_t)rollout_level_off(L, l + 1) * nn);
+    }
+    return tree;
 }
 
 // The device routine both entry-point families run: everything on `st`, dZ / dX0 / dX device pointers.
@@ -2183,18 +2208,8 @@ static void rollout(dto_handle* h, const KRollout& R, const double* dZ, const do
         launch_rollout_compact(st, R, 0, 1, S, dX);
         return;
     }
-    double* tree = grow_workspace(h, h->d_roll_tree, h->roll_tree_cap, rollout_tree_bytes(npad, K) / sizeof(double));
-    double* slab = jac_scratch(h);
-    // the whole Jacobian, tangent sweep included: the x_k columns of the integrator then hold -E_k on every path
-    do_jacobian(h, dZ, slab, st);   // (external blocks are staged as for dto_eval_jacobian_dev)
-    { ProfScope ps(h, st, CAT_ROLLOUT, 0.0); launch_rollout_leaves(st, h->P, R, slab, tree); }
-    // up-sweep: level l + 1 = (second half of level l) * (first half), one contiguous batch
-    for (int l = 0; l < L; ++l) {
-        const int nb = (int)rollout_level_len(L, l + 1);
-        const double* lo = tree + (size_t)rollout_level_off(L, l) * nn;
-        ProfScope ps(h, st, CAT_ROLLOUT_TREE, 2.0 * npad * (double)nn * nb);
-        launch_bgemm_plain(st, npad, nb, lo + (size_t)nb * nn, lo, tree + (size_t)rollout_level_off(L, l + 1) * nn);
-    }
+    h->dyn_valid = false;   // (the tree the solves keep per point is overwritten)
+    double* tree = build_rollout_tree(h, R, dZ, st, CAT_ROLLOUT, CAT_ROLLOUT_TREE);
     { ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, 0.0); launch_rollout_start(st, R, dZ, dX0, S); }
     const double item_flops = 2.0 * (double)nn * R.col_pad;
     if (mode == DTO_ROLLOUT_ALL) {
@@ -2244,6 +2259,106 @@ int dto_rollout_dev(dto_handle* h, int32_t integrator, const double* dZ, const d
     return guarded(h, [&] {
         const KRollout R = rollout_args(h, integrator, n_cols, mode, dX0 != nullptr);
         rollout(h, R, dZ, dX0, mode, dX, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
+// ---- solves with the dynamics block: M Y = B (Y_{k+1} = E_k Y_k + B_{k+1}) and M' Lam = B (Lam_k = E_k' Lam_{k+1} + B_k), affine
+// scans over the rollout's tree (dto_dynsolve.hip, dto_rollout_plan.h)
+
+static KRollout dynsolve_args(const dto_handle* h, int32_t integrator, int32_t direction, const double* B, int32_t n_cols, int32_t mode) {
+    const KRollout R = rollout_args(h, integrator, n_cols, mode, true, "dto_dynamics_solve");
+    if (direction != DTO_SOLVE_FORWARD && direction != DTO_SOLVE_ADJOINT)
+        throw HipError{"dto_dynamics_solve: direction takes DTO_SOLVE_FORWARD (0) or DTO_SOLVE_ADJOINT (1)"};
+    if (!B) throw HipError{"dto_dynamics_solve: B = NULL (the right-hand side [N][n_cols][x_dim] is required)"};
+    return R;
+}
+
+// The device routine both entry-point families run: everything on `st`, dZ / dB / dY device pointers.  The tree is rebuilt (do_jacobian
+// into the private slab, leaves, products) unless the one in d_roll_tree belongs to this integrator at this point: Z bit for bit the
+// point of the build (one compare with a 4-byte readback), no dto_set_external / dto_set_option / failed call and no rollout since.
+static void dynamics_solve(dto_handle* h, const KRollout& R, int32_t integrator, const double* dZ, int adjoint, const double* dB, int mode,
+                           double* dY, hipStream_t st) {
+    const int npad = R.npad, L = R.L;
+    const int64_t K = R.K;
+    if (K < 1) {   // a single knot: M is the identity
+        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
+        HIP_CHECK(hipMemcpyAsync(dY, dB, sizeof(double) * (size_t)R.n_cols * R.n, hipMemcpyDeviceToDevice, st));
+        return;
+    }
+    double* S = grow_workspace(h, h->d_roll_S, h->roll_S_cap, rollout_traj_bytes(npad, K, R.n_cols) / sizeof(double));
+    double* off = grow_workspace(h, h->d_dyn_off, h->dyn_off_cap, dynsolve_offset_bytes(npad, K, R.n_cols) / sizeof(double));
+    if (!h->d_dyn_Z) {
+        h->d_dyn_Z = own(h, dalloc<double>((size_t)h->n_vars));
+        h->d_dyn_eq = own(h, dalloc<int32_t>(1));
+    }
+    bool hit = h->dyn_valid && h->dyn_integrator == integrator && h->dyn_gen == h->gen;
+    if (hit) hit = bits_equal(st, {{dZ, h->d_dyn_Z, h->n_vars}}, h->d_dyn_eq, &h->mailbox->dyn_flag);
+    if (!hit) {
+        h->dyn_valid = false;
+        build_rollout_tree(h, R, dZ, st, CAT_DYNSOLVE_TREE, CAT_DYNSOLVE_TREE);
+        HIP_CHECK(hipMemcpyAsync(h->d_dyn_Z, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
+        h->dyn_integrator = integrator;
+        h->dyn_gen = h->gen;
+        h->dyn_valid = true;
+    }
+    const double* tree = h->d_roll_tree;
+    { ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0); launch_dynsolve_load(st, R, adjoint, dB, off, S); }
+    const double item_flops = 2.0 * (double)npad * npad * R.col_pad;
+    for (int l = 0; l < L; ++l) {
+        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, item_flops * (double)rollout_level_len(L, l + 1));
+        launch_dynsolve_up(st, R, adjoint, l, tree, off);
+    }
+    if (mode == DTO_ROLLOUT_ALL) {
+        for (int l = L + 1; l >= 1; --l) {
+            if (dynsolve_live_items(L, K, adjoint, l) == 0) continue;
+            ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, item_flops * (double)dynsolve_product_items(L, K, adjoint, l));
+            launch_dynsolve_descend(st, R, adjoint, l, -1, tree, off, S);
+        }
+        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
+        launch_rollout_compact(st, R, 0, K + 1, S, dY);
+    } else if (adjoint) {
+        // knot 1 alone: the root's item -- the same launch on the same operands as in the full descent, so the same bits
+        {
+            ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, item_flops * (double)dynsolve_product_items(L, K, 1, L + 1));
+            launch_dynsolve_descend(st, R, 1, L + 1, 0, tree, off, S);
+        }
+        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
+        launch_rollout_compact(st, R, 0, 1, S, dY);
+    } else {
+        // knot N alone: the items on the way from knot K back to knot 0, highest level first, as dto_rollout's final mode runs them
+        int lv[64];
+        int64_t ix[64];
+        int cnt = 0;
+        for (int64_t t = K; t > 0; t = rollout_item(L, K, lv[cnt - 1], ix[cnt - 1]).start) { rollout_writer(L, t, lv[cnt], ix[cnt]); ++cnt; }
+        for (int c = cnt - 1; c >= 0; --c) {
+            ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, item_flops);
+            launch_dynsolve_descend(st, R, 0, lv[c], ix[c], tree, off, S);
+        }
+        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
+        launch_rollout_compact(st, R, K, 1, S, dY);
+    }
+}
+
+int dto_dynamics_solve(dto_handle* h, int32_t integrator, const double* Z, int32_t direction, const double* B, int32_t n_cols, int32_t mode,
+                       double* Y) {
+    return guarded(h, [&] {
+        const KRollout R = dynsolve_args(h, integrator, direction, B, n_cols, mode);
+        upload_Z(h, Z);
+        const size_t n_in = (size_t)h->N * R.n_cols * R.n;
+        double* dB = grow_workspace(h, h->d_dyn_B, h->dyn_B_cap, n_in);
+        HIP_CHECK(hipMemcpyAsync(dB, B, sizeof(double) * n_in, hipMemcpyHostToDevice, h->stream));
+        const size_t n_out = (size_t)(mode == DTO_ROLLOUT_ALL ? h->N : 1) * R.n_cols * R.n;
+        double* o = staging(h, n_out);
+        dynamics_solve(h, R, integrator, h->d_Z, direction == DTO_SOLVE_ADJOINT, dB, mode, o, h->stream);
+        HIP_CHECK(hipMemcpyAsync(Y, o, sizeof(double) * n_out, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_dynamics_solve_dev(dto_handle* h, int32_t integrator, const double* dZ, int32_t direction, const double* dB, int32_t n_cols,
+                           int32_t mode, double* dY, void* stream) {
+    return guarded(h, [&] {
+        const KRollout R = dynsolve_args(h, integrator, direction, dB, n_cols, mode);
+        dynamics_solve(h, R, integrator, dZ, direction == DTO_SOLVE_ADJOINT, dB, mode, dY, (hipStream_t)stream);
     }, G_ASYNC, (hipStream_t)stream);
 }
 
@@ -2472,7 +2587,7 @@ int dto_profile_reset(dto_handle* h) {
 int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launches, double* flops) {
     return guarded(h, [&] {
         int cat = -1;
-        bool any_gemm = false, any_basis = false, any_rollout = false;
+        bool any_gemm = false, any_basis = false, any_rollout = false, any_dynsolve = false;
         if (!strcmp(name, "bgemm")) any_gemm = true;
         else if (!strcmp(name, "bgemm_horner")) cat = CAT_BGEMM_HORNER;
         else if (!strcmp(name, "bgemm_square")) cat = CAT_BGEMM_SQUARE;
@@ -2496,6 +2611,9 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "rollout_gather")) cat = CAT_ROLLOUT;
         else if (!strcmp(name, "rollout_tree")) cat = CAT_ROLLOUT_TREE;
         else if (!strcmp(name, "rollout_descent")) cat = CAT_ROLLOUT_DESCENT;
+        else if (!strcmp(name, "dynsolve")) any_dynsolve = true;
+        else if (!strcmp(name, "dynsolve_tree")) cat = CAT_DYNSOLVE_TREE;
+        else if (!strcmp(name, "dynsolve_scan")) cat = CAT_DYNSOLVE_SCAN;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -2523,6 +2641,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (any_basis && r.cat != CAT_OTHER && r.cat != CAT_BASIS_MULTI) continue;
             if (!any_gemm && !any_basis && cat >= 0 && r.cat != cat) continue;
             if (is_rollout_cat(r.cat) ? !(any_rollout || r.cat == cat) : any_rollout) continue;   // ("all": the rollout is no callback)
+            if (is_dynsolve_cat(r.cat) ? !(any_dynsolve || r.cat == cat) : any_dynsolve) continue;   // (nor are the solves)
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));

@@ -162,6 +162,85 @@ __device__ __forceinline__ void gemm_accumulate_s(GemmAccS<C>& acc, const double
         __syncthreads();
     }
 }
+
+// acc += A[0:Klen, 0:TM]' * B[0:Klen, 0:TN]: the 8-byte core with a TRANSPOSED left operand (the adjoint scan of dto_dynsolve.hip).
+//   At : pointer to row 0 of the K range, the tile's first COLUMN of A (column-major, ldat): column m of A is row m of the product's
+//        left operand and is contiguous in k, exactly as a column of B is
+// The left operand is therefore staged as B is, Ats[m][k] with row pitch KB+2: 16-byte global loads and LDS stores along k, and
+// fragment reads at (16 ti + lr) * (KB+2) + kk + lq, the Bs pattern (36*c mod 64 distinct for c < 16: conflict-free).  It lies in
+// the As region of the same Shape (TM (KB+2) <= KB (TM+16) up to TM = 128).  Accumulator layout, k order (ascending, four per MFMA
+// step) and the closing barrier are gemm_accumulate_s's.
+template <class C>
+__device__ __forceinline__ void gemm_accumulate_st(GemmAccS<C>& acc, const double* __restrict__ At, int ldat,
+                                                   const double* __restrict__ B, int ldb, int Klen, double* smem) {
+    static_assert(C::TM * C::LDB_S <= C::AS_ELEMS, "the transposed left operand must fit the As region");
+    constexpr int ATS_ELEMS = C::TM * C::LDB_S;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int wm = wave / C::WC, wn = wave % C::WC;
+    const int lr = lane & 15, lq = lane >> 4;
+
+    double* Ats = smem;
+    double* Bs = smem + 2 * C::AS_ELEMS;
+
+    d2 ra[C::A_LD], rb[C::B_LD];
+    int a_m[C::A_LD], a_k[C::A_LD], b_n[C::B_LD], b_k[C::B_LD];
+#pragma unroll
+    for (int i = 0; i < C::A_LD; ++i) {
+        const int idx = tid + C::THREADS * i;
+        a_m[i] = idx / (C::KB / 2);
+        a_k[i] = 2 * (idx % (C::KB / 2));
+    }
+#pragma unroll
+    for (int i = 0; i < C::B_LD; ++i) {
+        const int idx = tid + C::THREADS * i;
+        b_n[i] = idx / (C::KB / 2);
+        b_k[i] = 2 * (idx % (C::KB / 2));
+    }
+    const int nkb = Klen / C::KB;
+
+    auto load_panel = [&](int kb) {
+        const int k0 = kb * C::KB;
+#pragma unroll
+        for (int i = 0; i < C::A_LD; ++i) ra[i] = *reinterpret_cast<const d2*>(At + (size_t)a_m[i] * ldat + k0 + a_k[i]);
+#pragma unroll
+        for (int i = 0; i < C::B_LD; ++i) rb[i] = *reinterpret_cast<const d2*>(B + (size_t)b_n[i] * ldb + k0 + b_k[i]);
+    };
+    auto store_panel = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < C::A_LD; ++i) *reinterpret_cast<d2*>(Ats + buf * ATS_ELEMS + a_m[i] * C::LDB_S + a_k[i]) = ra[i];
+#pragma unroll
+        for (int i = 0; i < C::B_LD; ++i) *reinterpret_cast<d2*>(Bs + buf * C::BS_ELEMS + b_n[i] * C::LDB_S + b_k[i]) = rb[i];
+    };
+
+    load_panel(0);
+    store_panel(0);
+    __syncthreads();
+
+    for (int kb = 0; kb < nkb; ++kb) {
+        const int buf = kb & 1;
+        if (kb + 1 < nkb) load_panel(kb + 1);
+        const double* as = Ats + buf * ATS_ELEMS + (wm * C::WTM + lr) * C::LDB_S;
+        const double* bs = Bs + buf * C::BS_ELEMS + (wn * C::WTN + lr) * C::LDB_S;
+#pragma unroll
+        for (int kk = 0; kk < C::KB; kk += 4) {
+            double af[C::MT], bf[C::NT];
+#pragma unroll
+            for (int ti = 0; ti < C::MT; ++ti) af[ti] = as[16 * ti * C::LDB_S + kk + lq];
+#pragma unroll
+            for (int tj = 0; tj < C::NT; ++tj) bf[tj] = bs[16 * tj * C::LDB_S + kk + lq];
+#pragma unroll
+            for (int ti = 0; ti < C::MT; ++ti)
+#pragma unroll
+                for (int tj = 0; tj < C::NT; ++tj)
+                    acc.v[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[tj], af[ti], acc.v[ti][tj], 0, 0, 0);
+        }
+        if (kb + 1 < nkb) store_panel(buf ^ 1);
+        __syncthreads();
+    }
+}
+
 // an LDS / a global address for `global_load_lds_dwordx4` (LDS-DMA: 1 KB per wave-instruction, no staging registers, no ds_write)
 #define DTO_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define DTO_GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))

@@ -200,6 +200,7 @@ struct PinnedMailbox {
     unsigned long long hump[8];    // k_hump's output (read_hump)
     int32_t same_flag;             // same_point's bit compare
     int32_t hp_flag;               // hess_product's bit compare
+    int32_t dyn_flag;              // dynamics_solve's bit compare
     int32_t deferred_smax;         // the one-launch chain's squaring count of an enqueue-only call (smax_pending)
 };
 }  // namespace dto
@@ -278,6 +279,15 @@ struct dto_handle {
     // rollout, grow-only (capacities in doubles)
     double *d_roll_tree = nullptr, *d_roll_S = nullptr, *d_roll_X0 = nullptr;
     size_t roll_tree_cap = 0, roll_S_cap = 0, roll_X0_cap = 0;
+    // solves with the dynamics block (dto_dynamics_solve[_dev]): they keep the product tree in d_roll_tree per point -- integrator,
+    // Z bit for bit (d_dyn_Z: the copy taken at the build) and `gen`; a rollout overwrites the tree and clears dyn_valid.  The offset
+    // tree and the host-pointer form's B are grow-only like the rollout's buffers.
+    double *d_dyn_off = nullptr, *d_dyn_B = nullptr, *d_dyn_Z = nullptr;
+    size_t dyn_off_cap = 0, dyn_B_cap = 0;
+    int32_t* d_dyn_eq = nullptr;
+    bool dyn_valid = false;
+    int32_t dyn_integrator = -1;
+    uint64_t dyn_gen = 0;
     int64_t* d_conbase = nullptr;        // [n_vars+1] first constraint-pattern entry of each column
     int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
     int64_t* d_crow_col = nullptr;

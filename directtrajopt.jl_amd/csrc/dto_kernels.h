@@ -450,6 +450,15 @@ void launch_rollout_start(hipStream_t st, const KRollout& R, const double* dZ, c
 void launch_rollout_descend(hipStream_t st, const KRollout& R, int l, int64_t only, const double* tree, double* S);
 void launch_rollout_compact(hipStream_t st, const KRollout& R, int64_t k0, int64_t nk, const double* S, double* X);
 
+// Solves with the dynamics block, Y_{k+1} = E_k Y_k + B_{k+1} or (adjoint) Lam_k = E_k' Lam_{k+1} + B_k (dto_dynsolve.hip; index plan:
+// dto_rollout_plan.h): affine scans over the rollout's tree and an offset tree `off` of 2^(L+1) - 1 blocks [col_pad][npad].
+// B: [K + 1][n_cols][n], the caller's layout
+void launch_dynsolve_load(hipStream_t st, const KRollout& R, int adjoint, const double* B, double* off, double* S);
+// level l of the offsets into level l + 1, l = 0 .. L - 1
+void launch_dynsolve_up(hipStream_t st, const KRollout& R, int adjoint, int l, const double* tree, double* off);
+// level l of the descent (L + 1: the root's item, then L .. 1); only >= 0: that item alone
+void launch_dynsolve_descend(hipStream_t st, const KRollout& R, int adjoint, int l, int64_t only, const double* tree, double* off, double* S);
+
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);
 

@@ -66,6 +66,7 @@ class GatherLayout(C.Structure):
 COMM_ID_BYTES = 128
 VECTOR_JACOBIAN, VECTOR_HESSIAN, VECTOR_GRADIENT, VECTOR_CONSTRAINT = 1, 2, 3, 4
 ROLLOUT_ALL, ROLLOUT_FINAL = 0, 1
+SOLVE_FORWARD, SOLVE_ADJOINT = 0, 1
 
 H = C.c_void_p
 
@@ -108,6 +109,8 @@ SYMBOLS = {
     "dto_eval_jacobian_transpose_product_dev": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dto_rollout": (C.c_int, [H, C.c_int32, c_double_p, c_double_p, C.c_int32, C.c_int32, c_double_p]),
     "dto_rollout_dev": (C.c_int, [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "dto_dynamics_solve": (C.c_int, [H, C.c_int32, c_double_p, C.c_int32, c_double_p, C.c_int32, C.c_int32, c_double_p]),
+    "dto_dynamics_solve_dev": (C.c_int, [H, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "dto_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dto_comm_create": (C.c_int, [H, C.c_void_p, C.c_int32, C.c_int32]),
     "dto_comm_set_ranges": (C.c_int, [H, C.c_int32, C.c_int32, c_int64_p, c_int64_p]),

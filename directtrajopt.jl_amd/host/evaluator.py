@@ -112,6 +112,9 @@ class Evaluator:
                 raise NotImplementedError(f"{type(it).__name__}: wrap it in HostIntegrator to have it merged")
 
         self._integrator_dims = [it.x_dim for it in prob.integrators]
+        # per integrator: its first row of g and (device kinds) the position of its states inside a knot
+        self._integrator_row0 = [sum(p.dim for p in prob.integrators[:i]) for i in range(len(prob.integrators))]
+        self._integrator_x_off = [getattr(it, "x_off", None) for it in prob.integrators]
         self._ext_con, self._ext_obj, self._ext_keep = [], [], None
         terms = _flatten_objective(prob.objective)
         objs = (capi.ObjectiveDesc * max(1, len(terms)))()
@@ -422,6 +425,63 @@ class Evaluator:
                                           capi.ROLLOUT_ALL if all_knots else capi.ROLLOUT_FINAL, _dp(X)))
         return X
 
+    def _solve_shape(self, B, integrator):
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        N = self.trajectory.N
+        if B.ndim == 2 and B.shape[0] == N:
+            B = B.reshape(N, 1, B.shape[1])
+        if B.ndim != 3 or B.shape[0] != N:
+            raise ValueError(f"B: (N, n_cols, x_dim) or (N, x_dim) with N = {N} expected, got {B.shape}")
+        its = self._integrator_dims
+        if 0 <= integrator < len(its) and B.shape[2] != its[integrator]:
+            raise ValueError(f"B: rows of length {B.shape[2]}, the integrator has {its[integrator]} states")
+        return B
+
+    def dynamics_solve(self, Z, B, integrator=0, adjoint=False, all_knots=True):
+        """Solve with the dynamics block M of integrator ``integrator`` at Z (I on the diagonal, -E_k(Z) below it), on the device.
+        Forward: M Y = B, the linearised rollout Y_1 = B_1, Y_{k+1} = E_k Y_k + B_{k+1}.  ``adjoint=True``: M' L = B, the costate
+        recursion L_N = B_N, L_k = E_k' L_{k+1} + B_k.  ``B``: (N, n_cols, x_dim), or (N, x_dim) for one column.  Returns
+        (N, n_cols, x_dim), or with ``all_knots=False`` the (n_cols, x_dim) block at knot N (forward) or knot 1 (adjoint), bit for bit
+        that block.  A second solve at the same Z, in either direction, reuses the product tree of the first."""
+        Z = self._Z(Z)
+        B = self._solve_shape(B, integrator)
+        N, n_cols, x_dim = B.shape
+        Y = np.full((N, n_cols, x_dim) if all_knots else (n_cols, x_dim), np.nan)
+        self._stage_external(Z, con_need=1)
+        self._check(self._lib.dto_dynamics_solve(self._h, int(integrator), _dp(Z), capi.SOLVE_ADJOINT if adjoint else capi.SOLVE_FORWARD,
+                                                 _dp(B), n_cols, capi.ROLLOUT_ALL if all_knots else capi.ROLLOUT_FINAL, _dp(Y)))
+        return Y
+
+    def rollout_gradient(self, Z, C, integrator=0):
+        """Gradient of a loss phi of the ROLLED-OUT states of integrator ``integrator`` (``rollout(Z)``: start state = knot 1 of Z)
+        with respect to everything but that integrator's states: controls, timesteps, times.  ``C``: (N, x_dim), row k the
+        derivative of phi with respect to the rolled-out state of knot k + 1.  One adjoint solve L = M'^{-1} C, then -J' w with
+        L_2 .. L_N in the integrator's rows of a zero w; the integrator's state components of the result are set to zero.  J' w is
+        taken at Z with the ROLLED-OUT states in the integrator's components (d(E_k x_k)/du acts on the state the loss saw, whatever
+        states Z holds): they come from a forward solve with B = [x_1; 0; ...], the rollout's bits, which also leaves the tree for
+        the adjoint solve.  Host vectors; returns (n_variables,)."""
+        Z = self._Z(Z)
+        N, dim = self.trajectory.N, self.trajectory.dim
+        Cm = np.ascontiguousarray(C, dtype=np.float64)
+        x_dim = self._integrator_dims[integrator]
+        if Cm.shape != (N, x_dim):
+            raise ValueError(f"C: ({N}, {x_dim}) expected, got {Cm.shape}")
+        row0, x_off = self._integrator_row0[integrator], self._integrator_x_off[integrator]
+        B = np.zeros((N, 1, x_dim))
+        if x_off is not None:
+            B[0, 0] = Z[x_off:x_off + x_dim]
+        X = self.dynamics_solve(Z, B, integrator=integrator)[:, 0]
+        lam = self.dynamics_solve(Z, Cm.reshape(N, 1, x_dim), integrator=integrator, adjoint=True)[:, 0]
+        Zr = Z.copy()
+        Zr[:N * dim].reshape(N, dim)[:, x_off:x_off + x_dim] = X
+        w = np.zeros(self.n_constraints)
+        w[row0:row0 + (N - 1) * x_dim] = lam[1:].reshape(-1)
+        y = np.full(self.n_variables, np.nan)
+        self.eval_constraint_jacobian_transpose_product(y, Zr, w)
+        grad = -y
+        grad[:N * dim].reshape(N, dim)[:, x_off:x_off + x_dim] = 0.0
+        return grad
+
     def constraint_bounds(self):  # get_nonlinear_constraints, src/solvers/solve.jl:30-65
         lo = np.empty(self.n_constraints)
         hi = np.empty(self.n_constraints)
@@ -476,6 +536,13 @@ class Evaluator:
         self._stage_external(Z_host, con_need=1)
         self._check(self._lib.dto_rollout_dev(self._h, int(integrator), dZ, dX0 or None, int(n_cols),
                                               capi.ROLLOUT_ALL if all_knots else capi.ROLLOUT_FINAL, dX, stream))
+
+    def dynamics_solve_dev(self, dZ, dB, n_cols, dY, integrator=0, adjoint=False, all_knots=True, stream=0, Z_host=None):
+        """``dynamics_solve`` on device pointers: dB (N, n_cols, x_dim), dY (N, n_cols, x_dim) or, with ``all_knots=False``,
+        (n_cols, x_dim); enqueued on `stream`, errors deferred as for every `_dev` call.  Same bits as ``dynamics_solve``."""
+        self._stage_external(Z_host, con_need=1)
+        self._check(self._lib.dto_dynamics_solve_dev(self._h, int(integrator), dZ, capi.SOLVE_ADJOINT if adjoint else capi.SOLVE_FORWARD,
+                                                     dB or None, int(n_cols), capi.ROLLOUT_ALL if all_knots else capi.ROLLOUT_FINAL, dY, stream))
 
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod

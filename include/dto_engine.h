@@ -378,6 +378,36 @@ int dto_rollout(dto_handle* h, int32_t integrator, const double* Z, const double
 int dto_rollout_dev(dto_handle* h, int32_t integrator, const double* dZ, const double* dX0, int32_t n_cols, int32_t mode,
                     double* dX, void* stream);
 
+/* ---- Solves with the dynamics block: linearised and adjoint rollouts.  M is the block of the Jacobian formed by integrator
+ * `integrator`'s rows and its own state columns, with the identity row of knot 1 on top: I on the diagonal, -E_k(Z) below it (E_k as
+ * for dto_rollout above; the state components of Z are not read).
+ *   DTO_SOLVE_FORWARD  M Y = B:    Y_1 = B_1,  Y_{k+1} = E_k Y_k + B_{k+1} -- the linearised rollout.  B = -(defect of Z) gives the
+ *                      state correction that makes a trajectory dynamically feasible under its controls; B = [X0; 0; ...] is
+ *                      dto_rollout, bit for bit.
+ *   DTO_SOLVE_ADJOINT  M' Lam = B: Lam_N = B_N,  Lam_k = E_k' Lam_{k+1} + B_k -- the costate recursion.  With B the gradient of a loss of
+ *                      the rolled-out states and w holding Lam_2 .. Lam_N in the integrator's rows, -J' w (dto_eval_jacobian_transpose_
+ *                      product) is the gradient of that loss with respect to the controls and timesteps.
+ *   B, Y: [N][n_cols][x_dim] in the layout of dto_rollout's X, 1 <= n_cols <= x_dim; they must not overlap.  `mode` is dto_rollout's:
+ *   DTO_ROLLOUT_FINAL returns [n_cols][x_dim], the block at knot N (forward) or at knot 1 (adjoint), bit for bit that block of
+ *   DTO_ROLLOUT_ALL.  N = 1 returns B.
+ * Both solves are affine scans over dto_rollout's product tree: an offset block per node, one launch per level up and one per level
+ * down, the adjoint through a transposed left operand (no second tree).  Every entry has one writer and a fixed summation order: a
+ * column has the same bits alone and among others, repeated calls are bit-identical, both entry-point families return the same bits.
+ * The tree is kept per point: a solve at the Z of the last one -- bit for bit, the same integrator, with no dto_set_external,
+ * dto_set_option, failed call or dto_rollout since -- runs its scan alone, after one device-side compare with a 4-byte readback;
+ * otherwise the call evaluates the Jacobian into the private slab and rebuilds the tree as dto_rollout does.  Workspaces beside
+ * dto_rollout's (shared with it), grow-only, freed with the handle: the offset tree, (2^(L+1) - 1) x n_cols (padded as the trajectory)
+ * x npad doubles, and a copy of Z.
+ * Refused with text, the handle stays usable: everything dto_rollout refuses, a direction other than the two, B = NULL.
+ * The `_dev` form works on the caller's stream and defers device-side errors as every `_dev` call; solves at one point enqueued on
+ * different streams are the caller's to order. */
+#define DTO_SOLVE_FORWARD 0
+#define DTO_SOLVE_ADJOINT 1
+int dto_dynamics_solve(dto_handle* h, int32_t integrator, const double* Z, int32_t direction, const double* B, int32_t n_cols, int32_t mode,
+                       double* Y);
+int dto_dynamics_solve_dev(dto_handle* h, int32_t integrator, const double* dZ, int32_t direction, const double* dB, int32_t n_cols,
+                           int32_t mode, double* dY, void* stream);
+
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
  * communicator (SURVEY.md §8b "Ownership").  No callback needs a collective: every rank's Jacobian / Hessian / gradient
@@ -528,7 +558,11 @@ int dto_profile_reset(dto_handle* h);
  * "rollout" (dto_rollout / dto_rollout_dev: the gather of the -E_k blocks, the tree's batched products and the descent, flops as
  * executed with padding; its parts "rollout_gather" / "rollout_tree" / "rollout_descent", the last with the start and the copy into
  * the caller's layout; the tree's products do not count under "bgemm" / "bgemm_plain", and these names feed no other, "all" included;
- * the Jacobian evaluation inside a rollout counts under its own names).
+ * the Jacobian evaluation inside a rollout counts under its own names),
+ * "dynsolve" (dto_dynamics_solve / dto_dynamics_solve_dev; its parts "dynsolve_tree", the gather and the tree's products of a rebuild
+ * -- no launches at a cached point -- and "dynsolve_scan", the loader, the offsets' up-sweep, the descent and the copy into the
+ * caller's layout; flops as executed with padding; like the rollout's these names feed no other, "all" included, and the Jacobian
+ * evaluation inside a rebuild counts under its own names).
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the
  * third output is the launches' algorithmic BYTES (what they must read and write), not FLOPs.
  * "hess_product_setup" returns the host milliseconds of the products' index build (once per handle), 0 launches, and the device

@@ -61,6 +61,8 @@ const DTO_VECTOR_GRADIENT = Int32(3)
 const DTO_VECTOR_CONSTRAINT = Int32(4)
 const DTO_ROLLOUT_ALL = Int32(0)    # rollout: the states of every knot, x_dim x n_cols x N
 const DTO_ROLLOUT_FINAL = Int32(1)  # rollout: the states of knot N alone, x_dim x n_cols
+const DTO_SOLVE_FORWARD = Int32(0)  # dynamics_solve: Y_{k+1} = E_k Y_k + B_{k+1}
+const DTO_SOLVE_ADJOINT = Int32(1)  # dynamics_solve: Λ_k = E_k' Λ_{k+1} + B_k
 
 # ---- plain-C structs, field for field as in include/dto_engine.h ----------------------------------------------------
 struct IntegratorDesc
@@ -678,6 +680,40 @@ function rollout_dev!(ev::GPUEvaluator, dX::Ptr{Float64}, dZ::Ptr{Float64}, dX0:
     mode = all_knots ? DTO_ROLLOUT_ALL : DTO_ROLLOUT_FINAL
     check(ev, @ccall lib.dto_rollout_dev(ev.handle::Ptr{Cvoid}, i0::Int32, dZ::Ptr{Float64}, dX0::Ptr{Float64}, nc::Int32, mode::Int32,
                                          dX::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
+# ---- solves with the dynamics block (include/dto_engine.h, "Solves with the dynamics block") ----------------------------------------
+# Forward, the linearised rollout Y_1 = B_1, Y_{k+1} = E_k(Z) Y_k + B_{k+1}; with `adjoint = true` the costate recursion Λ_N = B_N,
+# Λ_k = E_k(Z)' Λ_{k+1} + B_k.  `B`: x_dim x n_cols x N (a Matrix is one column per knot).  Returns x_dim x n_cols x N, or with
+# `all_knots = false` the x_dim x n_cols block at knot N (forward) or knot 1 (adjoint), bit for bit that slice.  A second solve at the
+# same Z -- in either direction -- reuses the product tree of the first and runs its scan alone.
+function dynamics_solve(ev::GPUEvaluator, Z::AbstractVector{Float64}, B::AbstractArray{Float64}; integrator::Integer = 0, adjoint::Bool = false,
+                        all_knots::Bool = true)
+    stage_external!(ev, Z; con_need = 1)
+    i0 = Int32(integrator)
+    N = ev.trajectory.N
+    Bm = Array{Float64,3}(ndims(B) == 3 ? B : reshape(B, size(B, 1), 1, :))
+    size(Bm, 3) == N || error("dynamics_solve: B holds $(size(Bm, 3)) knots, the trajectory has $N")
+    x_dim = size(Bm, 1)
+    nc = Int32(size(Bm, 2))
+    dir = adjoint ? DTO_SOLVE_ADJOINT : DTO_SOLVE_FORWARD
+    mode = all_knots ? DTO_ROLLOUT_ALL : DTO_ROLLOUT_FINAL
+    Y = all_knots ? fill(NaN, x_dim, Int(nc), N) : fill(NaN, x_dim, Int(nc))
+    GC.@preserve Y Z Bm check(ev, @ccall lib.dto_dynamics_solve(ev.handle::Ptr{Cvoid}, i0::Int32, Z::Ptr{Float64}, dir::Int32, Bm::Ptr{Float64}, nc::Int32,
+                                                                mode::Int32, Y::Ptr{Float64})::Cint)
+    return Y
+end
+
+# the same on device pointers: dB x_dim x n_cols x N, dY x_dim x n_cols x N (or x_dim x n_cols); enqueued on `stream`
+function dynamics_solve_dev!(ev::GPUEvaluator, dY::Ptr{Float64}, dZ::Ptr{Float64}, dB::Ptr{Float64}, n_cols::Integer, stream::Ptr{Cvoid};
+                             integrator::Integer = 0, adjoint::Bool = false, all_knots::Bool = true, Z_host = nothing)
+    Z_host === nothing || stage_external!(ev, Z_host; con_need = 1)
+    i0 = Int32(integrator)
+    nc = Int32(n_cols)
+    dir = adjoint ? DTO_SOLVE_ADJOINT : DTO_SOLVE_FORWARD
+    mode = all_knots ? DTO_ROLLOUT_ALL : DTO_ROLLOUT_FINAL
+    check(ev, @ccall lib.dto_dynamics_solve_dev(ev.handle::Ptr{Cvoid}, i0::Int32, dZ::Ptr{Float64}, dir::Int32, dB::Ptr{Float64}, nc::Int32,
+                                                mode::Int32, dY::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 end
 
 # row bounds handed to the solver (src/solvers/solve.jl:30-65)
