@@ -2,6 +2,9 @@
 fixed-point reference tests/hp_reference.py.  Minutes of CPU, no GPU, nothing but numpy:
 
     python tests/golden/make_hp_golden.py [case ...]
+
+The 130-state case takes a minute and a half, the 250- and 330-state cases seven to eleven minutes each on one core; the cases are
+independent, so give each a process of its own.
 """
 import os
 import sys

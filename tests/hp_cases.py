@@ -3,7 +3,14 @@ their seeds, the dt ladder, the expected callback vectors from tests/hp_referenc
 metric -- the NORMWISE error per interval and quantity class, max|a - b| / max|b| over the entries of the class in that interval.
 
 One BilinearIntegrator per problem (the DerivativeIntegrator of the scaling generator is dropped: it has no exponential), seven
-knots, skew-symmetric generators, and dt_k chosen so that ||A_k||_2 walks the ladder below in shuffled knot order."""
+knots, skew-symmetric generators, and dt_k chosen so that ||A_k||_2 walks the ladder below in shuffled knot order.
+
+From 130 states on (`sample_E` in CASES) a whole E_k = exp(A_k) is out of the reference's reach (minutes per interval, 500 KB per
+fixture), so the expected Jacobian holds 16 sampled columns of each E_k block -- the same columns in every interval, as the action
+of exp(A_k) on unit vectors -- and NaN elsewhere in the block; the fixture's `jac_known` marks what is known, and the "E" class is
+measured over those entries alone (every other entry of the block must still be a number).  Every u_j column, dt column, identity and structural zero is known and checked as before.  The
+rest of the block is still exercised in aggregate: J w and J' w contract all of it with random vectors, and on the value-slab route
+(tests/test_gpu_accuracy_budget.py) they contract the engine's own stored E_k entries."""
 import hashlib
 import os
 
@@ -15,6 +22,7 @@ import hp_reference as HP
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 LADDER = (0.5, 4.0, 8.0, 11.0, 14.0, 20.0)   # ||A_k||_2: no squaring / the chain's radii / one round / q = 1 -> 2 / several rounds
 N_KNOTS = 7
+Q1_TOP = 6.0        # hp_ring256_q1: the largest of 6, 5, 4, 3 at which every callback's sweeps run one round
 CASES = {
     "hp_small": dict(kind="dense", n=9, m=2, seed=901),       # k_small
     "hp_s64": dict(kind="dense", n=40, m=2, seed=902),        # k_chain64 + k_sweep_s64
@@ -23,6 +31,15 @@ CASES = {
     # at 24 it runs two rounds of radius 12 (over the bar) where theta_v = 9 runs three of radius 8
     "hp_general": dict(kind="dense", n=66, m=1, seed=903, ladder=(0.5, 4.0, 8.0, 11.0, 14.0, 24.0)),
     "hp_kron": dict(kind="kron", b=16, r=4, m=2, seed=904),   # dto_kron.hip (block_generators=True)
+    # npad = 192: three 64-tiles a side in the chain's GEMM, no one-launch sweep form (step launches only)
+    "hp_tile192": dict(kind="dense", n=130, m=1, seed=905, ladder=(0.5, 4.0, 8.0, 11.0, 14.0, 24.0), sample_E=16),
+    # npad = 256, the benchmark's size: the ring GEMM on 2 x 2 tiles with 6 dead rows; sub-stepped sweeps, non-pairing Hessian
+    "hp_ring256": dict(kind="dense", n=250, m=2, seed=906, ladder=(0.5, 4.0, 8.0, 11.0, 14.0, 24.0), sample_E=16),
+    # ... and the same chain with every sweep in one round: the generator-stationary form, the pairing Hessian (DESIGN section 2
+    # records how the top rung was chosen)
+    "hp_ring256_q1": dict(kind="dense", n=250, m=2, seed=907, ladder=(0.5, 1.0, 2.0, 3.0, 4.0, Q1_TOP), sample_E=16),
+    # npad = 384: the ring GEMM's odd 3 x 3 tile walk with 54 dead rows, step-launch sweeps beside the chain
+    "hp_ring384": dict(kind="dense", n=330, m=1, seed=908, ladder=(0.5, 4.0, 8.0, 11.0, 14.0, 24.0), sample_E=16),
 }
 ENGINE_KW = {"hp_kron": dict(block_generators=True)}
 
@@ -76,6 +93,18 @@ def ladder(name, p):
     return Zk.reshape(-1).copy(), Zk[:, p.dt_idx].copy()
 
 
+def E_columns(name):
+    """The sampled columns of every E_k block of a `sample_E` case (None for a case whose E_k is known whole): columns 0, 15, 16,
+    63, 64, n - 1, both sides of every 128-column boundary below n, and the rest drawn from the case's seed."""
+    c = CASES[name]
+    if "sample_E" not in c:
+        return None
+    n = c["n"]
+    must = {0, 15, 16, 63, 64, n - 1} | {b + s for b in range(128, n, 128) for s in (-1, 0)}
+    rest = [int(j) for j in np.random.default_rng(c["seed"] + 29).permutation(n) if int(j) not in must]
+    return np.array(sorted(must | set(rest[:c["sample_E"] - len(must)])), dtype=np.int64)
+
+
 def inputs(name):
     """Everything a fixture stores that a seed does not give back: Z (with the ladder), mu, w, wt, dt."""
     p = problem(name)
@@ -113,7 +142,10 @@ def expected(name, d):
     cols = lambda v: np.asarray(v, dtype=np.float64).reshape(r, b).T          # x of n = r b entries -> (b, r) columns
     flat = lambda M: M.T.reshape(-1)                                           # and back, fixed point or float
     loc = np.concatenate([np.arange(it.x_off, it.x_off + n), np.arange(it.u_off, it.u_off + m), [p.dt_idx]])
+    ecols = E_columns(name)       # None: the whole E_k; else the sampled columns, everything else of the block NaN / unknown
+    assert ecols is None or r == 1
     J = np.zeros((n * K, p.n_vars))
+    known = np.ones(J.shape, dtype=bool)
     Hd = np.zeros((p.n_vars, p.n_vars))
     cons, Jw = np.zeros(n * K), np.zeros(n * K)
     JTw = HP.zeros((p.N, z))
@@ -122,24 +154,32 @@ def expected(name, d):
     norm2, norm1 = np.zeros(K), np.zeros(K)
     for k in range(K):
         u, dt = Zk[k, it.u_off:it.u_off + m], Zk[k, p.dt_idx]
-        R = HP.interval(G, cols(Zk[k, xs]), u, dt, cols(Zk[k + 1, xs]), mu=cols(d["mu"][k * n:(k + 1) * n]))
+        R = HP.interval(G, cols(Zk[k, xs]), u, dt, cols(Zk[k + 1, xs]), mu=cols(d["mu"][k * n:(k + 1) * n]),
+                        want_E=ecols is None, E_cols=ecols)
         A = HP.to_float(R["A"])
         norm2[k], norm1[k] = np.linalg.norm(A, 2), np.linalg.norm(A, 1)
         rows = slice(k * n, (k + 1) * n)
-        E = HP.to_float(R["E"])
-        J[rows, k * z + it.x_off:k * z + it.x_off + n] = -np.kron(np.eye(r), E)
+        WT = HP.fx(cols(d["wt"][rows]))
+        if ecols is None:
+            J[rows, k * z + it.x_off:k * z + it.x_off + n] = -np.kron(np.eye(r), HP.to_float(R["E"]))
+            Ew, ETwt = HP.mul(R["E"], HP.fx(cols(W[k, xs]))), HP.mul(R["E"].T.copy(), WT)
+        else:
+            J[rows, k * z + it.x_off:k * z + it.x_off + n] = np.nan
+            known[rows, k * z + it.x_off:k * z + it.x_off + n] = False
+            J[rows, k * z + it.x_off + ecols] = -HP.to_float(R["E_cols"])
+            known[rows, k * z + it.x_off + ecols] = True
+            Ew, ETwt = HP.expm_action(R["A"], HP.fx(cols(W[k, xs]))), HP.expm_action(R["A"].T.copy(), WT)
         for j in range(m):
             J[rows, k * z + it.u_off + j] = -flat(HP.to_float(R["LX"][j]))
         J[rows, k * z + p.dt_idx] = -flat(HP.to_float(R["GEX"]))
         J[rows, (k + 1) * z + it.x_off:(k + 1) * z + it.x_off + n] = np.eye(n)
         cons[rows] = flat(HP.to_float(R["defect"]))
         # J w of the interval's rows and the interval's part of J' w, in fixed point, rounded once
-        y = HP.fx(cols(W[k + 1, xs])) - HP.mul(R["E"], HP.fx(cols(W[k, xs]))) - HP.scale(int(HP.fx(W[k, p.dt_idx])), R["GEX"])
+        y = HP.fx(cols(W[k + 1, xs])) - Ew - HP.scale(int(HP.fx(W[k, p.dt_idx])), R["GEX"])
         for j in range(m):
             y = y - HP.scale(int(HP.fx(W[k, it.u_off + j])), R["LX"][j])
         Jw[rows] = flat(HP.to_float(y))
-        WT = HP.fx(cols(d["wt"][rows]))
-        JTw[k, xs] = JTw[k, xs] - flat(HP.mul(R["E"].T.copy(), WT))
+        JTw[k, xs] = JTw[k, xs] - flat(ETwt)
         JTw[k + 1, xs] = JTw[k + 1, xs] + flat(WT)
         for j in range(m):
             JTw[k, it.u_off + j] = -HP._dot(R["LX"][j], WT)
@@ -148,6 +188,10 @@ def expected(name, d):
     out = dict(cons=cons, jac=J[ev_o.jac_rows, ev_o.jac_cols], Jw=Jw, JTw=HP.to_float(JTw).reshape(-1),
                hess=Hd[ev_o.hess_rows, ev_o.hess_cols], norm2=norm2, norm1=norm1)
     assert np.count_nonzero(J) == np.count_nonzero(out["jac"]) and np.count_nonzero(np.triu(Hd)) == np.count_nonzero(out["hess"])
+    if ecols is not None:
+        out["jac_known"] = known[ev_o.jac_rows, ev_o.jac_cols]
+        out["E_cols"] = ecols
+        assert np.array_equal(np.isfinite(out["jac"]), out["jac_known"])
     return out
 
 
@@ -192,10 +236,15 @@ def errors(name, fix, got):
     if "jac" in got:
         shape = (n * K, p.n_vars)
         Ja, Jb = _dense(ev_o.jac_rows, ev_o.jac_cols, got["jac"], shape), _dense(ev_o.jac_rows, ev_o.jac_cols, fix["jac"], shape)
+        # sampled E_k (jac_known): the "E" class over the known entries only -- unknown ones sit nowhere but in the E_k blocks
+        Kn = _dense(ev_o.jac_rows, ev_o.jac_cols, fix["jac_known"], shape).astype(bool) if "jac_known" in fix else None
         for k in range(K):
             rows = slice(k * n, (k + 1) * n)
             xs = slice(k * z + it.x_off, k * z + it.x_off + n)
-            out[("E", k)] = nerr(Ja[rows, xs], Jb[rows, xs])
+            if Kn is None:
+                out[("E", k)] = nerr(Ja[rows, xs], Jb[rows, xs])
+            else:   # (a missing writer must not pass in the unsampled columns either: every entry of the block is a number)
+                out[("E", k)] = nerr(Ja[rows, xs][Kn[rows, xs]], Jb[rows, xs][Kn[rows, xs]]) if np.all(np.isfinite(Ja[rows, xs])) else np.inf
             for j in range(m):
                 out[(f"u{j}", k)] = nerr(Ja[rows, k * z + it.u_off + j], Jb[rows, k * z + it.u_off + j])
             out[("dt", k)] = nerr(Ja[rows, k * z + p.dt_idx], Jb[rows, k * z + p.dt_idx])

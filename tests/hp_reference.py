@@ -144,10 +144,20 @@ def _first_order(Gf, X, u, dt, MU=None):
     return out
 
 
-def interval(G, x, u, dt, x_next, mu=None, want_E=True):
+def unit_columns(n, cols):
+    """The unit vectors e_c, c in cols, as the columns of an (n, len(cols)) fixed-point matrix."""
+    V = zeros((n, len(cols)))
+    for j, c in enumerate(cols):
+        V[int(c), j] = ONE
+    return V
+
+
+def interval(G, x, u, dt, x_next, mu=None, want_E=True, E_cols=None):
     """One interval.  G (m+1, n, n) float64; x, x_next, mu: (n,) or, for generators I_c (x) G acting on c segments alike, (n, c)
     columns; u (m,), dt: float64.  Returns a dict of FIXED-POINT arrays (round with `to_float`):
       A, E (n, n; None unless want_E), EX = exp(A) x, defect = x_next - EX, LX [m] of (n, c), GEX (n, c),
+      with E_cols (a sequence of column indices): E_cols = E[:, E_cols], as the action of exp(A) on those unit vectors -- no
+      exponential is formed for them, so sampled columns of a large E stay affordable (want_E=False),
       and with mu: H, the (nx + m + 1)^2 Hessian of mu'(defect) in (x, u, dt), x column-major over (n, c) flattened as
       segment-major (column c0 of X first) -- its (x, x) block is zero, the defect being linear in x.
     """
@@ -160,6 +170,8 @@ def interval(G, x, u, dt, x_next, mu=None, want_E=True):
     base = _first_order(Gf, X, uf, dtf, MU)
     out = dict(A=base["A"], EX=base["EX"], LX=base["LX"], GEX=base["GEX"], defect=Xn - base["EX"],
                E=expm(base["A"]) if want_E else None)
+    if E_cols is not None:
+        out["E_cols"] = expm_action(base["A"], unit_columns(Gf.shape[1], E_cols))
     if MU is None:
         return out
     nx = X.size

@@ -83,6 +83,21 @@ def test_default_dispatch_matches_the_hand_derived_table(dispatch):
         assert g == row[3:], (row, g)
 
 
+def test_accuracy_budget_fixtures_reach_the_kernel_their_case_names(dispatch):
+    """tests/hp_cases.py: with six intervals the 250- and 330-state fixtures run the chain on the ring kernel, whatever the
+    epilogue; the 130-state one (npad 192: no whole 128-tiles) and the 66-state one (npad 128, far below 3500 intervals) do not."""
+    import sys
+    sys.path[:0] = [p for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")) if p not in sys.path]
+    import hp_cases as C
+    want = {"hp_general": (128, "tile64"), "hp_tile192": (192, "tile64"), "hp_ring256": (256, "ring"),
+            "hp_ring256_q1": (256, "ring"), "hp_ring384": (384, "ring")}
+    nb = C.N_KNOTS - 1
+    for name, (npad, kernel) in want.items():
+        assert -(-C.CASES[name]["n"] // 64) * 64 == npad, name
+        got = dispatch([(npad, nb, poly, -1, 0) for poly in (0, 1)])
+        assert [g[0] for g in got] == [kernel, kernel], (name, got)
+
+
 def test_forced_tile_and_all_persistent_ring(dispatch):
     got = dispatch([(npad, nb, int(epi == "poly"), force, ring) for npad, nb, epi, force, ring, *_ in SWITCHED])
     for row, g in zip(SWITCHED, got):

@@ -1,6 +1,8 @@
 """CPU: the 320-bit reference (tests/hp_reference.py) is pinned, the accuracy-budget fixtures (tests/golden/hp_*.npz) come out of
 their generator, and the fp64 oracle sits within 1e-13 of every fixture in the normwise metric per interval and quantity class
-(tests/hp_cases.py).  The oracle's Hessian error is printed per interval; DESIGN section 2 records it."""
+(tests/hp_cases.py).  The oracle's Hessian error is printed per interval; DESIGN section 2 records it.  From 130 states on a
+fixture's Jacobian knows 16 sampled columns of each E_k block (`jac_known`); the cap holds there as well, measured: worst class
+4.2e-14 (J' w of hp_ring256)."""
 import functools
 import importlib.util
 import os
@@ -68,6 +70,27 @@ def test_differenced_hessian_is_symmetric_and_matches_the_gradient_in_x():
         assert max(abs(int(a) + int(b)) for a, b in zip(H[:n, n + j], LT.reshape(-1))) / HP.ONE <= 1e-40
 
 
+@pytest.mark.parametrize("n", [6, 12])
+@pytest.mark.parametrize("kind", ["skew", "general"])
+def test_sampled_propagator_columns_are_the_columns_of_the_exponential(n, kind):
+    """interval(E_cols=...) forms the columns as actions of exp(A) on unit vectors and calls no expm: they equal the same columns
+    of expm(A) to 1e-80, the bar the action is held to against expm above."""
+    rng = np.random.default_rng(9 + n)
+    m = 2
+    G = rng.standard_normal((m + 1, n, n))
+    if kind == "skew":
+        G = G - G.transpose(0, 2, 1)
+    x, xn, u = rng.standard_normal(n), rng.standard_normal(n), rng.standard_normal(m)
+    cols = [0, n - 1, 3, 2]      # unsorted on purpose: column j of the result is column cols[j] of E
+    R = HP.interval(G, x, u, 0.6, xn, want_E=False, E_cols=cols)
+    assert R["E"] is None and R["E_cols"].shape == (n, len(cols))
+    E = HP.expm(R["A"])
+    assert max(abs(int(v)) for v in (R["E_cols"] - E[:, cols]).reshape(-1)) / HP.ONE <= 1e-80
+    # and a whole E beside them is the one interval() always returned
+    R2 = HP.interval(G, x, u, 0.6, xn, E_cols=cols[:1])
+    assert all(int(a) == int(b) for a, b in zip(R2["E"].reshape(-1), E.reshape(-1)))
+
+
 def _generator():
     spec = importlib.util.spec_from_file_location("make_hp_golden", os.path.join(C.GOLDEN, "make_hp_golden.py"))
     mod = importlib.util.module_from_spec(spec)
@@ -90,7 +113,39 @@ def test_fixture_inputs_are_the_seeds_and_the_ladder(name):
     assert os.path.getsize(os.path.join(C.GOLDEN, name + ".npz")) < 512 * 1024
     # every rung of the ladder once, to the rounding of the 2-norm
     assert np.allclose(np.sort(fix["norm2"]), C.CASES[name].get("ladder", C.LADDER), rtol=1e-12, atol=0)
-    assert all(np.all(np.isfinite(fix[k])) for k in ("cons", "jac", "Jw", "JTw", "hess"))
+    assert all(np.all(np.isfinite(fix[k])) for k in ("cons", "Jw", "JTw", "hess"))
+    if "jac_known" not in fix:
+        assert np.all(np.isfinite(fix["jac"]))
+        return
+    # sampled E_k: the Jacobian is finite exactly where it is known, and what is unknown lies in the E_k blocks' other columns
+    assert fix["jac_known"].dtype == bool and np.array_equal(np.isfinite(fix["jac"]), fix["jac_known"])
+    cols = C.E_columns(name)
+    assert np.array_equal(fix["E_cols"], cols) and len(cols) == 16
+    n = C.CASES[name]["n"]
+    assert {0, 15, 16, 63, 64, n - 1} | {b + s for b in range(128, n, 128) for s in (-1, 0)} <= set(cols.tolist())
+    p, ev_o = C.at_point(name, fix["Z"])
+    it = p.integrators[0]
+    unknown_cols = np.unique((ev_o.jac_cols[~fix["jac_known"]] % p.z) - it.x_off)
+    assert np.array_equal(unknown_cols, np.setdiff1d(np.arange(n), cols))
+    assert np.count_nonzero(~fix["jac_known"]) == p.K * n * (n - 16)
+
+
+def test_sampled_metric_reads_known_entries_and_lets_no_nan_through():
+    """Under `jac_known` the E class compares the sampled columns alone, but an entry nobody wrote (NaN) anywhere in the block
+    still fails it."""
+    name = "hp_tile192"
+    fix = C.load(name)
+    unknown = np.flatnonzero(~fix["jac_known"])
+    got = np.where(fix["jac_known"], fix["jac"], 123.0)           # exact where known, anything finite elsewhere
+    errs = C.errors(name, fix, dict(jac=got))
+    assert all(v == 0.0 for (cls, k), v in errs.items())
+    got[unknown[len(unknown) // 2]] = np.nan
+    errs = C.errors(name, fix, dict(jac=got))
+    assert sorted(v for (cls, k), v in errs.items() if cls == "E")[-2:] == [0.0, np.inf]
+    known_E = np.flatnonzero(fix["jac_known"] & (np.abs(fix["jac"]) < 0.9) & (fix["jac"] != 0.0))
+    got = np.where(fix["jac_known"], fix["jac"], 123.0)
+    got[known_E[0]] += 1e-9                                       # a sampled entry off by 1e-9 shows
+    assert max(v for (cls, k), v in C.errors(name, fix, dict(jac=got)).items() if cls in ("E", "u0", "dt")) > 1e-10
 
 
 @functools.lru_cache(maxsize=None)
