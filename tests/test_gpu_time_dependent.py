@@ -8,7 +8,11 @@ Richardson-extrapolated differences.  tests/test_oracle_pinning.py ties that res
 rtol 1e-12: fourth-order convergence, 1e-11 at 16 sub-steps on the reference's own carrier test) and to 40-digit arithmetic;
 tests/golden/tdb_*.npz freeze its outputs (the engine is checked against those in test_gpu_golden_and_shards.py).  Bars:
 1e-10 values / Jacobian, 1e-8 Hessian.  The reference itself integrates adaptively (Tsit5 at 1e-3 / 1e-6), so its own outputs
-are only that close to any fixed scheme: parity against a running Julia reference is unpinned here as everywhere."""
+are only that close to any fixed scheme: parity against a running Julia reference is unpinned here as everywhere.
+
+These bars say that the kernel computes the oracle's map, not how accurately: the oracle's differenced Hessian is itself off by
+1e-12 .. 6e-12.  Accuracy is held in tests/test_gpu_tdb_accuracy_budget.py, against 320-bit fixtures of the discrete map at bars of
+7e-15 .. 2e-13 per interval and quantity class."""
 import numpy as np
 import pytest
 

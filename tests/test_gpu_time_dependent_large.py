@@ -4,7 +4,11 @@ M0 = sum_q c_q B_q, derivative jets applied as scalar combinations of B_q y, a p
 Reference: tests/tdb_large_cases.py -- `O.OracleEvaluator` with the integrator's blocks in a fast, finite-difference-free form of
 the same discrete map; tests/test_tdb_large_reference.py pins it to the oracle at 8 and 24 states.  Bars are those of
 tests/test_gpu_time_dependent.py: 1e-10 relative for values and Jacobian, 1e-8 for the Hessian.  Shapes are the smallest at which
-the path can go wrong: N = 3 (two intervals), N = 5 where sharded."""
+the path can go wrong: N = 3 (two intervals), N = 5 where sharded.
+
+These bars compare two fp64 codes; accuracy is held in tests/test_gpu_tdb_accuracy_budget.py, where k_tdb_mfma's 32- and 64-row
+tile bodies (72 and 128 states) meet 320-bit fixtures of the discrete map at bars of 7e-15 .. 2e-13 per interval and quantity
+class, and where tests/tdb_large_cases.py, the reference used here, is itself measured against those fixtures (at most 1.5e-14)."""
 import numpy as np
 import pytest
 
