@@ -3,9 +3,10 @@ values from the 320-bit reference of the discrete map (tests/tdb_hp_reference.py
 fp64 yardstick (tests/tdb_large_cases.py) with the bars derived from it (`classes`, `yard`, `bars`).  CPU only, nothing but numpy:
 
     python tests/golden/make_tdbhp_golden.py [case ...]
+    python tests/golden/make_tdbhp_golden.py --scan [case ...]  # tdbhp_scan_*.npz: the rollout and both solves (tests/scan_cases.py)
 
 Seconds for the cases up to 36 states, about a minute each for 128 states and for 72 states with its second member; the cases are
-independent, so give each a process of its own.
+independent, so give each a process of its own.  `--scan` also needs g++ (the scan's index plan): 20 s at most (128 states).
 """
 import os
 import sys
@@ -46,5 +47,26 @@ def main(names):
             print(f"  {c:20s} yardstick worst {np.nanmax(y):.2e}  bar {b:.2e}")
 
 
+def build_scan(case):
+    """The scan fixture of a case of tests/scan_cases.py: X0, B, the 320-bit rollout and both solves, the yardstick and the bars."""
+    import scan_cases as S
+    return S.build_fixture(case)
+
+
+def main_scan(cases):
+    import scan_cases as S
+    for case in cases or [c for c in S.CASES if c.startswith("tdbhp_")]:
+        t = time.time()
+        arrays = build_scan(case)
+        path = os.path.join(HERE, S.fixture_name(case) + ".npz")
+        np.savez_compressed(path, **arrays)
+        print(f"{case}: {os.path.getsize(path)} bytes, {time.time() - t:.1f} s, rho = {arrays['rho']}, a-priori bound {float(arrays['rho_bound']):.2e}")
+        for q, y, b in zip(S.QUANTITIES, arrays["yard"], arrays["bars"]):
+            print(f"  {q:4s} sequential fp64 worst {y.max():.2e}  bars {np.array2string(b, precision=2)}")
+
+
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    if sys.argv[1:2] == ["--scan"]:
+        main_scan(sys.argv[2:])
+    else:
+        main(sys.argv[1:])

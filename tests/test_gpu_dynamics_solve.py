@@ -18,7 +18,7 @@ import dto_oracle as O
 from helpers import TOL, rel_err, to_engine
 from multi_ket_cases import multi_ket
 from test_gpu_block_generators import kron_problem
-from test_gpu_rollout import bar, scaled_case
+from test_gpu_rollout import WHERE, bar, places, scaled_case  # noqa: F401  (`places`: the module-scoped fixture, one set of handles per module)
 
 pytestmark = pytest.mark.gpu
 
@@ -212,44 +212,51 @@ def test_a_column_has_the_same_bits_alone_and_among_others(ev70, adjoint):
                 assert np.array_equal(among[:, c], a), (n_cols, c)
 
 
-def test_repeated_calls_and_both_pointer_families_are_bit_identical(ev40):
+@pytest.mark.parametrize("where", WHERE)
+def test_repeated_calls_and_both_pointer_families_are_bit_identical(places, where):
     import torch
-    p = scaled_case(6, 40, 40)[0]
+    ev, p, Z, q, X0 = places(where)
+    n, N = X0.shape[1], p.N
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev).cuda_stream
-    dZ = torch.from_numpy(np.array(p.Z0)).to(dev)
+    dZ = torch.from_numpy(np.array(Z)).to(dev)
     for n_cols, adjoint, all_knots in ((17, False, True), (17, True, True), (3, False, False), (3, True, False), (40, True, True)):
-        B = rhs(6, n_cols, 40, seed=n_cols)
-        a = ev40.dynamics_solve(p.Z0, B, adjoint=adjoint, all_knots=all_knots)
-        b = ev40.dynamics_solve(p.Z0, B, adjoint=adjoint, all_knots=all_knots)
+        n_cols = min(n_cols, n)
+        B = rhs(N, n_cols, n, seed=n_cols)
+        a = ev.dynamics_solve(Z, B, integrator=q, adjoint=adjoint, all_knots=all_knots)
+        b = ev.dynamics_solve(Z, B, integrator=q, adjoint=adjoint, all_knots=all_knots)
         assert np.array_equal(a, b) and not np.isnan(a).any()
+        if not all_knots:     # FINAL is that block of ALL, bit for bit
+            assert np.array_equal(a, ev.dynamics_solve(Z, B, integrator=q, adjoint=adjoint)[0 if adjoint else -1])
         dB = torch.from_numpy(B).to(dev)
         dY = torch.full(a.shape, float("nan"), dtype=torch.float64, device=dev)
-        ev40.dynamics_solve_dev(dZ.data_ptr(), dB.data_ptr(), n_cols, dY.data_ptr(), adjoint=adjoint, all_knots=all_knots, stream=st)
+        ev.dynamics_solve_dev(dZ.data_ptr(), dB.data_ptr(), n_cols, dY.data_ptr(), integrator=q, adjoint=adjoint, all_knots=all_knots, stream=st)
         torch.cuda.synchronize()
         assert np.array_equal(dY.cpu().numpy(), a), (n_cols, adjoint, all_knots)
 
 
-def test_a_reused_tree_gives_the_bits_of_a_rebuilt_one(ev40):
-    p = scaled_case(6, 40, 40)[0]
-    B = rhs(6, 3, 40, seed=8)
-    Z2 = np.array(p.Z0)
+@pytest.mark.parametrize("where", WHERE)
+def test_a_reused_tree_gives_the_bits_of_a_rebuilt_one(places, where):
+    ev, p, Z, q, X0 = places(where)
+    n = X0.shape[1]
+    B = rhs(p.N, 3, n, seed=8)
+    Z2 = np.array(Z)
     Z2[p.dt_idx] *= 1.5
-    ev40.profile_enable(True)
+    ev.profile_enable(True)
     try:
         rebuilt, reused = {}, {}
         for adjoint in (False, True):
-            ev40.dynamics_solve(Z2, B, adjoint=adjoint)
-            ev40.profile_reset()
-            rebuilt[adjoint] = ev40.dynamics_solve(p.Z0, B, adjoint=adjoint)          # Z -> Z' -> Z: a rebuild
-            assert ev40.profile_get("dynsolve_tree")[1] > 0
-            ev40.profile_reset()
-            reused[adjoint] = ev40.dynamics_solve(p.Z0, B, adjoint=adjoint)
-            assert ev40.profile_get("dynsolve_tree")[1] == 0
+            ev.dynamics_solve(Z2, B, integrator=q, adjoint=adjoint)
+            ev.profile_reset()
+            rebuilt[adjoint] = ev.dynamics_solve(Z, B, integrator=q, adjoint=adjoint)          # Z -> Z' -> Z: a rebuild
+            assert ev.profile_get("dynsolve_tree")[1] > 0
+            ev.profile_reset()
+            reused[adjoint] = ev.dynamics_solve(Z, B, integrator=q, adjoint=adjoint)
+            assert ev.profile_get("dynsolve_tree")[1] == 0
             assert np.array_equal(rebuilt[adjoint], reused[adjoint])
-        assert not np.array_equal(rebuilt[False], ev40.dynamics_solve(Z2, B))     # (the other point is another point)
+        assert not np.array_equal(rebuilt[False], ev.dynamics_solve(Z2, B, integrator=q))     # (the other point is another point)
     finally:
-        ev40.profile_enable(False)
+        ev.profile_enable(False)
 
 
 # ------------------------------------------------------------------------------------------------------------ the cache

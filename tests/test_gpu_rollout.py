@@ -13,10 +13,12 @@ import scipy.linalg
 
 import dto_amd
 import dto_oracle as O
+import scan_cases as S
 from helpers import TOL, rel_err, to_engine
 from multi_ket_cases import multi_ket
 from test_gpu_block_generators import kron_problem
 from test_gpu_jacobian_products import case as products_case
+from test_gpu_scan_accuracy_budget import open_case
 
 pytestmark = pytest.mark.gpu
 
@@ -199,32 +201,61 @@ def test_no_X0_takes_the_state_of_knot_1(ev40):
 
 
 # ------------------------------------------------------------------------------------------------ modes and determinism
-def test_final_mode_and_repeated_calls_are_bit_identical(ev40):
-    p, X0, _ = scaled_case(6, 40, 40)
-    a = ev40.rollout(p.Z0, X0=X0[:17])
-    b = ev40.rollout(p.Z0, X0=X0[:17])
-    f = ev40.rollout(p.Z0, X0=X0[:17], all_knots=False)
+WHERE = ["n40"] + list(S.CASES)
+
+
+@pytest.fixture(scope="module")
+def places(ev40):
+    """where -> (handle, oracle problem, Z, integrator, up to 40 start states): the 40-state handle, and one handle per case of
+    tests/scan_cases.py at its fixture's point (every path the rollout serves; tdbhp_n72: the follower of the group of two),
+    opened on first use and closed with the module."""
+    opened = {}
+
+    def get(where):
+        if where == "n40":
+            p, X0, _ = scaled_case(6, 40, 40)
+            return ev40, p, p.Z0, 0, X0
+        if where not in opened:
+            ev, Z, q, p, fix = open_case(where)
+            n = fix["X0"].shape[1]
+            opened[where] = (ev, p, Z, q, S.more_columns(where, min(n, 40), fix["X0"], fix["B"])[0])
+        return opened[where]
+
+    yield get
+    for place in opened.values():
+        place[0].close()
+
+
+@pytest.mark.parametrize("where", WHERE)
+def test_final_mode_and_repeated_calls_are_bit_identical(places, where):
+    ev, p, Z, q, X0 = places(where)
+    a = ev.rollout(Z, integrator=q, X0=X0[:17])
+    b = ev.rollout(Z, integrator=q, X0=X0[:17])
+    f = ev.rollout(Z, integrator=q, X0=X0[:17], all_knots=False)
     assert np.array_equal(a, b) and np.array_equal(f, a[-1]) and not np.isnan(a).any()
 
 
-def test_device_pointer_form_gives_the_bits_of_the_host_pointer_form(ev40):
+@pytest.mark.parametrize("where", WHERE)
+def test_device_pointer_form_gives_the_bits_of_the_host_pointer_form(places, where):
     import torch
-    p, X0, _ = scaled_case(6, 40, 40)
+    ev, p, Z, q, X0 = places(where)
+    n = X0.shape[1]
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev).cuda_stream
-    dZ = torch.from_numpy(np.array(p.Z0)).to(dev)
+    dZ = torch.from_numpy(np.array(Z)).to(dev)
     for n_cols, all_knots in ((17, True), (17, False), (1, True)):
         x0 = np.array(X0[:n_cols])
+        n_cols = x0.shape[0]      # (fewer than 17 states: every one of them)
         dX0 = torch.from_numpy(x0).to(dev)
-        shape = (p.N, n_cols, 40) if all_knots else (n_cols, 40)
+        shape = (p.N, n_cols, n) if all_knots else (n_cols, n)
         dX = torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
-        ev40.rollout_dev(dZ.data_ptr(), dX0.data_ptr(), n_cols, dX.data_ptr(), all_knots=all_knots, stream=st)
+        ev.rollout_dev(dZ.data_ptr(), dX0.data_ptr(), n_cols, dX.data_ptr(), integrator=q, all_knots=all_knots, stream=st)
         torch.cuda.synchronize()
-        assert np.array_equal(dX.cpu().numpy(), ev40.rollout(p.Z0, X0=x0, all_knots=all_knots)), (n_cols, all_knots)
-    dX = torch.full((p.N, 1, 40), float("nan"), dtype=torch.float64, device=dev)
-    ev40.rollout_dev(dZ.data_ptr(), 0, 1, dX.data_ptr(), stream=st)   # X0 = NULL
+        assert np.array_equal(dX.cpu().numpy(), ev.rollout(Z, integrator=q, X0=x0, all_knots=all_knots)), (n_cols, all_knots)
+    dX = torch.full((p.N, 1, n), float("nan"), dtype=torch.float64, device=dev)
+    ev.rollout_dev(dZ.data_ptr(), 0, 1, dX.data_ptr(), integrator=q, stream=st)   # X0 = NULL
     torch.cuda.synchronize()
-    assert np.array_equal(dX.cpu().numpy(), ev40.rollout(p.Z0))
+    assert np.array_equal(dX.cpu().numpy(), ev.rollout(Z, integrator=q))
 
 
 # --------------------------------------------------------------------------------------------------- several integrators
