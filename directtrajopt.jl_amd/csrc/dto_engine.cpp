@@ -73,7 +73,7 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23 };
 // CAT_ROLLOUT .. CAT_ROLLOUT_DESCENT ("rollout" = its parts "rollout_gather" + "rollout_tree" + "rollout_descent"): the gather, the
 // tree's products and the descent (with the start and the copy into the caller's layout) of dto_rollout[_dev], flops as executed with
 // padding; the tree's products run launch_bgemm_plain and count HERE, not under "bgemm_plain"; they feed no other name, "all" included
@@ -82,6 +82,10 @@ inline bool is_rollout_cat(int cat) { return cat >= CAT_ROLLOUT && cat <= CAT_RO
 // the tree's products of a rebuild, and the loader, the offsets' up-sweep, the descent and the copy into the caller's layout; flops as
 // executed with padding.  Like the rollout's they feed no other name, "all" included.
 inline bool is_dynsolve_cat(int cat) { return cat == CAT_DYNSOLVE_TREE || cat == CAT_DYNSOLVE_SCAN; }
+// CAT_DYNSOLVE_COUPLE ("dynsolve_couple"), CAT_DYNSOLVE_DERIV ("dynsolve_deriv"): of dto_dynamics_solve_all[_dev], the gather of the
+// coupling blocks with the contractions against them, and the DerivativeIntegrators' block solves; the third output carries BYTES as
+// executed.  (Its other block solves count under "dynsolve_tree" / "dynsolve_scan".)  They feed no other name, "all" included.
+inline bool is_elim_cat(int cat) { return cat == CAT_DYNSOLVE_COUPLE || cat == CAT_DYNSOLVE_DERIV; }
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
 inline void count_sweep_form(dto_handle* h, int form) {
     if (h->profiling) ++h->sweep_forms[form];
@@ -2176,15 +2180,11 @@ static KRollout rollout_args(const dto_handle* h, int32_t integrator, int32_t n_
     return R;
 }
 
-// Gather and up-sweep, for the rollout and the solves alike: the product tree of R's integrator at dZ, in d_roll_tree.  The launches
+// Leaves and up-sweep: the product tree of R's integrator from the -E_k blocks of a Jacobian value slab, into `tree`.  The launches
 // count under `cat_gather` and `cat_tree`.
-static double* build_rollout_tree(dto_handle* h, const KRollout& R, const double* dZ, hipStream_t st, int cat_gather, int cat_tree) {
+static void rollout_tree_from_slab(dto_handle* h, const KRollout& R, const double* slab, double* tree, hipStream_t st, int cat_gather, int cat_tree) {
     const int npad = R.npad, L = R.L;
     const size_t nn = (size_t)npad * npad;
-    double* tree = grow_workspace(h, h->d_roll_tree, h->roll_tree_cap, rollout_tree_bytes(npad, R.K) / sizeof(double));
-    double* slab = jac_scratch(h);
-    // the whole Jacobian, tangent sweep included: the x_k columns of the integrator then hold -E_k on every path
-    do_jacobian(h, dZ, slab, st);   // (external blocks are staged as for dto_eval_jacobian_dev)
     { ProfScope ps(h, st, cat_gather, 0.0); launch_rollout_leaves(st, h->P, R, slab, tree); }
     // up-sweep: level l + 1 = (second half of level l) * (first half), one contiguous batch
     for (int l = 0; l < L; ++l) {
@@ -2193,6 +2193,16 @@ static double* build_rollout_tree(dto_handle* h, const KRollout& R, const double
         ProfScope ps(h, st, cat_tree, 2.0 * npad * (double)nn * nb);
         launch_bgemm_plain(st, npad, nb, lo + (size_t)nb * nn, lo, tree + (size_t)rollout_level_off(L, l + 1) * nn);
     }
+}
+
+// Jacobian, gather and up-sweep, for the rollout and the single-integrator solves alike: the product tree of R's integrator at dZ, in
+// d_roll_tree.
+static double* build_rollout_tree(dto_handle* h, const KRollout& R, const double* dZ, hipStream_t st, int cat_gather, int cat_tree) {
+    double* tree = grow_workspace(h, h->d_roll_tree, h->roll_tree_cap, rollout_tree_bytes(R.npad, R.K) / sizeof(double));
+    double* slab = jac_scratch(h);
+    // the whole Jacobian, tangent sweep included: the x_k columns of the integrator then hold -E_k on every path
+    do_jacobian(h, dZ, slab, st);   // (external blocks are staged as for dto_eval_jacobian_dev)
+    rollout_tree_from_slab(h, R, slab, tree, st, cat_gather, cat_tree);
     return tree;
 }
 
@@ -2273,6 +2283,29 @@ static KRollout dynsolve_args(const dto_handle* h, int32_t integrator, int32_t d
     return R;
 }
 
+// The scan's two halves, for the single-integrator solves and the whole-dynamics solves alike (every launch counts under
+// "dynsolve_scan"): the loader with the offsets' up-sweep, and the full descent with the copy into the caller's layout.
+static void dynsolve_load_and_up(dto_handle* h, const KRollout& R, int adjoint, const double* tree, const double* dB, double* off, double* S,
+                                 hipStream_t st) {
+    { ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0); launch_dynsolve_load(st, R, adjoint, dB, off, S); }
+    const double item_flops = 2.0 * (double)R.npad * R.npad * R.col_pad;
+    for (int l = 0; l < R.L; ++l) {
+        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, item_flops * (double)rollout_level_len(R.L, l + 1));
+        launch_dynsolve_up(st, R, adjoint, l, tree, off);
+    }
+}
+static void dynsolve_descend_all(dto_handle* h, const KRollout& R, int adjoint, const double* tree, double* off, double* S, double* dY,
+                                 hipStream_t st) {
+    const double item_flops = 2.0 * (double)R.npad * R.npad * R.col_pad;
+    for (int l = R.L + 1; l >= 1; --l) {
+        if (dynsolve_live_items(R.L, R.K, adjoint, l) == 0) continue;
+        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, item_flops * (double)dynsolve_product_items(R.L, R.K, adjoint, l));
+        launch_dynsolve_descend(st, R, adjoint, l, -1, tree, off, S);
+    }
+    ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
+    launch_rollout_compact(st, R, 0, R.K + 1, S, dY);
+}
+
 // The device routine both entry-point families run: everything on `st`, dZ / dB / dY device pointers.  The tree is rebuilt (do_jacobian
 // into the private slab, leaves, products) unless the one in d_roll_tree belongs to this integrator at this point: Z bit for bit the
 // point of the build (one compare with a 4-byte readback), no dto_set_external / dto_set_option / failed call and no rollout since.
@@ -2302,20 +2335,10 @@ static void dynamics_solve(dto_handle* h, const KRollout& R, int32_t integrator,
         h->dyn_valid = true;
     }
     const double* tree = h->d_roll_tree;
-    { ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0); launch_dynsolve_load(st, R, adjoint, dB, off, S); }
+    dynsolve_load_and_up(h, R, adjoint, tree, dB, off, S, st);
     const double item_flops = 2.0 * (double)npad * npad * R.col_pad;
-    for (int l = 0; l < L; ++l) {
-        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, item_flops * (double)rollout_level_len(L, l + 1));
-        launch_dynsolve_up(st, R, adjoint, l, tree, off);
-    }
     if (mode == DTO_ROLLOUT_ALL) {
-        for (int l = L + 1; l >= 1; --l) {
-            if (dynsolve_live_items(L, K, adjoint, l) == 0) continue;
-            ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, item_flops * (double)dynsolve_product_items(L, K, adjoint, l));
-            launch_dynsolve_descend(st, R, adjoint, l, -1, tree, off, S);
-        }
-        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
-        launch_rollout_compact(st, R, 0, K + 1, S, dY);
+        dynsolve_descend_all(h, R, adjoint, tree, off, S, dY, st);
     } else if (adjoint) {
         // knot 1 alone: the root's item -- the same launch on the same operands as in the full descent, so the same bits
         {
@@ -2359,6 +2382,216 @@ int dto_dynamics_solve_dev(dto_handle* h, int32_t integrator, const double* dZ, 
     return guarded(h, [&] {
         const KRollout R = dynsolve_args(h, integrator, direction, dB, n_cols, mode);
         dynamics_solve(h, R, integrator, dZ, direction == DTO_SOLVE_ADJOINT, dB, mode, dY, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
+// ---- whole-dynamics solves: the Jacobian block of ALL integrators' rows and state columns, by block elimination in dependency order
+// (dto_elim.hip, dto_elim_plan.h).  Each integrator's own block is solved as above -- an affine scan over a tree of its own, or the
+// DerivativeIntegrator's serial sum -- after the coupling blocks have carried the finished slices into its right-hand side.
+
+// The plan, from what dto_create kept on the host (a structure-only handle has it too).  A handle with a host-evaluated integrator
+// gets a plan that holds only the refusal.
+static const ElimPlan& elim_plan_of(dto_handle* h) {
+    if (h->elim) return *h->elim;
+    std::vector<ElimIntegrator> its;
+    std::string external;
+    for (size_t i = 0; i < h->integ_kind.size(); ++i) {
+        const int kind = h->integ_kind[i], idx = h->integ_index[i];
+        if (kind == DTO_INTEGRATOR_BILINEAR) {
+            const KBil& k = h->bil[idx].k;
+            its.push_back(ElimIntegrator{ELIM_BILINEAR, k.x_off, k.n, k.u_off, k.m, -1});
+        } else if (kind == DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) {
+            const KTdb& k = h->tdb[idx].k;
+            its.push_back(ElimIntegrator{ELIM_TIME_DEPENDENT, k.x_off, k.n, k.u_off, k.m, k.t_off});
+        } else if (kind == DTO_INTEGRATOR_DERIVATIVE) {
+            const KDer& k = h->der[idx];
+            its.push_back(ElimIntegrator{ELIM_DERIVATIVE, k.x_off, k.d, k.xdot_off, k.d, -1});
+        } else if (external.empty()) {
+            external = "integrator " + std::to_string(i) + " is evaluated on the host (DTO_INTEGRATOR_EXTERNAL): its Jacobian block is "
+                       "not known to be a propagator";
+        }
+    }
+    std::unique_ptr<ElimPlan> p(new ElimPlan);
+    if (external.empty()) *p = elim_plan(its, h->dt_idx, h->K);
+    else p->refusal = external;
+    h->elim = std::move(p);
+    return *h->elim;
+}
+
+static bool elim_has_tree(const dto_handle* h, int i) { return h->integ_kind[i] != DTO_INTEGRATOR_DERIVATIVE; }
+// first state component of integrator i (a device kind: the plan refuses the others)
+static int elim_x_off(const dto_handle* h, int i) {
+    const int idx = h->integ_index[i], kind = h->integ_kind[i];
+    return kind == DTO_INTEGRATOR_BILINEAR ? h->bil[idx].k.x_off : kind == DTO_INTEGRATOR_DERIVATIVE ? h->der[idx].x_off : h->tdb[idx].k.x_off;
+}
+
+// the block solve's record of integrator i (bilinear or time-dependent)
+static KRollout elim_rollout_args(const dto_handle* h, const ElimPlan& p, int i, int n_cols) {
+    KRollout R{};
+    R.n = h->integ_dim[i];
+    R.x_off = elim_x_off(h, i);
+    R.pre = p.pre[i];
+    R.npad = pad64(R.n);
+    R.n_cols = n_cols;
+    R.col_pad = rollout_col_pad(n_cols);
+    R.K = h->K;
+    R.L = rollout_levels(std::max<int64_t>(R.K, 1));
+    return R;
+}
+
+// What a whole-dynamics solve names: refused with text before anything is enqueued.
+static const ElimPlan& elim_args(dto_handle* h, int32_t direction, const double* B, int32_t n_cols) {
+    const std::string who = "dto_dynamics_solve_all";
+    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{who + " needs an unsharded handle (k_lo, k_hi = the whole trajectory)"};
+    const ElimPlan& p = elim_plan_of(h);
+    if (!p.refusal.empty()) throw HipError{who + ": " + p.refusal};
+    if (direction != DTO_SOLVE_FORWARD && direction != DTO_SOLVE_ADJOINT)
+        throw HipError{who + ": direction takes DTO_SOLVE_FORWARD (0) or DTO_SOLVE_ADJOINT (1)"};
+    if (!B) throw HipError{who + ": B = NULL (the right-hand side [N][n_cols][n_states] is required)"};
+    int cap = 0;   // each block solve's own limit: the smallest x_dim among the integrators with a propagator
+    for (size_t i = 0; i < h->integ_kind.size(); ++i)
+        if (elim_has_tree(h, (int)i)) cap = cap ? std::min(cap, h->integ_dim[i]) : h->integ_dim[i];
+    if (!cap) cap = 64;
+    if (n_cols < 1 || n_cols > cap) throw HipError{who + ": n_cols = " + std::to_string(n_cols) + ", allowed 1 .. " + std::to_string(cap)};
+    return p;
+}
+
+// the contractions' term tables: per integrator its dependencies (forward) and its dependents (adjoint), once per handle
+static void elim_upload_terms(dto_handle* h, const ElimPlan& p) {
+    if (h->d_elim_terms) return;
+    const int I = (int)p.pre.size();
+    std::vector<KElimTerm> terms;
+    h->elim_fw_term0.assign(1, 0);
+    for (int a = 0; a < I; ++a) {
+        for (const ElimDep& d : p.deps[a])
+            terms.push_back(KElimTerm{p.store_off[a], p.width[a], h->integ_dim[a], d.col, p.pre[d.b], h->integ_dim[d.b]});
+        h->elim_fw_term0.push_back((int)terms.size());
+    }
+    h->elim_ad_term0.assign(1, (int)terms.size());
+    for (int a = 0; a < I; ++a) {
+        for (int b : p.dependents[a])
+            for (const ElimDep& d : p.deps[b])
+                if (d.b == a) terms.push_back(KElimTerm{p.store_off[b], p.width[b], h->integ_dim[b], d.col, p.pre[b], h->integ_dim[b]});
+        h->elim_ad_term0.push_back((int)terms.size());
+    }
+    h->d_elim_terms = own(h, dupload(terms));
+}
+
+// The device routine both entry-point families run: everything on `st`, dZ / dB / dY device pointers, dB and dY [N][n_cols][D].  At a
+// new point: ONE do_jacobian into the private slab, then per integrator with a propagator the leaves and products of its own tree,
+// the gather of every coupling block, and a copy of Z.  At the point of the last call -- Z bit for bit, `gen` unchanged -- none of it.
+static void dynamics_solve_all(dto_handle* h, const ElimPlan& p, const double* dZ, int adjoint, const double* dB, int n_cols, double* dY,
+                               hipStream_t st) {
+    const int I = (int)p.pre.size(), D = p.n_states;
+    const int64_t K = h->K, N = h->N;
+    if (K < 1) {   // a single knot: the block is the identity
+        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
+        HIP_CHECK(hipMemcpyAsync(dY, dB, sizeof(double) * (size_t)n_cols * D, hipMemcpyDeviceToDevice, st));
+        return;
+    }
+    // every workspace first: a failed allocation is refused before anything is enqueued
+    int n_max = 1, npad_max = 0;
+    for (int i = 0; i < I; ++i) {
+        n_max = std::max(n_max, h->integ_dim[i]);
+        if (elim_has_tree(h, i)) npad_max = std::max(npad_max, pad64(h->integ_dim[i]));
+    }
+    double* Bp = grow_workspace(h, h->d_elim_Bp, h->elim_Bp_cap, (size_t)N * n_cols * n_max);
+    double* Yp = grow_workspace(h, h->d_elim_Yp, h->elim_Yp_cap, (size_t)N * n_cols * n_max);
+    double *S = nullptr, *off = nullptr;
+    if (npad_max) {
+        S = grow_workspace(h, h->d_roll_S, h->roll_S_cap, rollout_traj_bytes(npad_max, K, n_cols) / sizeof(double));
+        off = grow_workspace(h, h->d_dyn_off, h->dyn_off_cap, dynsolve_offset_bytes(npad_max, K, n_cols) / sizeof(double));
+    }
+    double* store = grow_workspace(h, h->d_elim_store, h->elim_store_cap, (size_t)p.store_off[I]);
+    h->elim_tree.resize(I, nullptr);
+    h->elim_tree_cap.resize(I, 0);
+    for (int i = 0; i < I; ++i)
+        if (elim_has_tree(h, i))
+            grow_workspace(h, h->elim_tree[i], h->elim_tree_cap[i], rollout_tree_bytes(pad64(h->integ_dim[i]), K) / sizeof(double));
+    elim_upload_terms(h, p);
+    if (!h->d_elim_Z) {
+        h->d_elim_Z = own(h, dalloc<double>((size_t)h->n_vars));
+        h->d_elim_eq = own(h, dalloc<int32_t>(1));
+    }
+    bool hit = h->elim_valid && h->elim_gen == h->gen;
+    if (hit) hit = bits_equal(st, {{dZ, h->d_elim_Z, h->n_vars}}, h->d_elim_eq, &h->mailbox->dyn_flag);
+    if (!hit) {
+        h->elim_valid = false;
+        double* slab = jac_scratch(h);
+        do_jacobian(h, dZ, slab, st);   // once, however many integrators there are
+        for (int i = 0; i < I; ++i)
+            if (elim_has_tree(h, i))
+                rollout_tree_from_slab(h, elim_rollout_args(h, p, i, n_cols), slab, h->elim_tree[i], st, CAT_DYNSOLVE_TREE, CAT_DYNSOLVE_TREE);
+        for (int a = 0; a < I; ++a)
+            for (const ElimDep& d : p.deps[a]) {
+                const int n_a = h->integ_dim[a], n_b = h->integ_dim[d.b];
+                ProfScope ps(h, st, CAT_DYNSOLVE_COUPLE, 16.0 * (double)K * 2.0 * n_a * n_b);
+                launch_elim_gather(st, h->P, KElimPair{n_a, p.pre[a], elim_x_off(h, d.b), n_b, d.col, p.width[a]}, K, slab, store + p.store_off[a]);
+            }
+        HIP_CHECK(hipMemcpyAsync(h->d_elim_Z, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
+        h->elim_gen = h->gen;
+        h->elim_valid = true;
+    }
+    for (int step = 0; step < I; ++step) {
+        const int a = p.order[adjoint ? I - 1 - step : step], n_a = h->integ_dim[a];
+        const std::vector<int>& t0 = adjoint ? h->elim_ad_term0 : h->elim_fw_term0;
+        KElimCouple C{n_a, p.pre[a], D, n_cols, t0[a + 1] - t0[a], K, h->d_elim_terms + t0[a]};
+        {
+            // bytes: B in, Bp out, and per term both halves of the store's columns with the slices they meet
+            double entries = 0.0;
+            for (const ElimDep& d : p.deps[a]) if (!adjoint) entries += 2.0 * n_a * h->integ_dim[d.b];
+            for (int b : p.dependents[a]) if (adjoint) entries += 2.0 * n_a * h->integ_dim[b];
+            ProfScope ps(h, st, CAT_DYNSOLVE_COUPLE, 8.0 * (double)N * n_cols * (2.0 * n_a + 2.0 * entries));
+            launch_elim_couple(st, C, adjoint, store, dB, dY, Bp);
+        }
+        if (!elim_has_tree(h, a)) {
+            ProfScope ps(h, st, CAT_DYNSOLVE_DERIV, 16.0 * (double)N * n_cols * n_a);
+            launch_deriv_scan(st, K, n_a, n_cols, D, p.pre[a], adjoint, Bp, dY);
+            continue;
+        }
+        const KRollout R = elim_rollout_args(h, p, a, n_cols);
+        dynsolve_load_and_up(h, R, adjoint, h->elim_tree[a], Bp, off, S, st);
+        dynsolve_descend_all(h, R, adjoint, h->elim_tree[a], off, S, Yp, st);
+        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
+        launch_elim_collect(st, N, n_a, n_cols, D, p.pre[a], Yp, dY);
+    }
+}
+
+int dto_dynamics_layout(const dto_handle* h, int32_t* n_states, int32_t* n_levels, int32_t* offset, int32_t* level) {
+    if (!h) return fail(nullptr, "null handle");
+    dto_handle* hm = const_cast<dto_handle*>(h);   // (the plan is built at the first question and kept)
+    try {
+        const ElimPlan& p = elim_plan_of(hm);
+        if (!p.refusal.empty()) return fail(hm, "dto_dynamics_layout: " + p.refusal);
+        if (n_states) *n_states = p.n_states;
+        if (n_levels) *n_levels = p.n_levels;
+        for (size_t i = 0; i < p.pre.size(); ++i) {
+            if (offset) offset[i] = p.pre[i];
+            if (level) level[i] = p.level[i];
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(hm, e.what());
+    }
+}
+
+int dto_dynamics_solve_all(dto_handle* h, const double* Z, int32_t direction, const double* B, int32_t n_cols, double* Y) {
+    return guarded(h, [&] {
+        const ElimPlan& p = elim_args(h, direction, B, n_cols);
+        upload_Z(h, Z);
+        const size_t n = (size_t)h->N * n_cols * p.n_states;
+        double* dB = grow_workspace(h, h->d_elim_B, h->elim_B_cap, n);
+        HIP_CHECK(hipMemcpyAsync(dB, B, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+        double* o = staging(h, n);
+        dynamics_solve_all(h, p, h->d_Z, direction == DTO_SOLVE_ADJOINT, dB, n_cols, o, h->stream);
+        HIP_CHECK(hipMemcpyAsync(Y, o, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_dynamics_solve_all_dev(dto_handle* h, const double* dZ, int32_t direction, const double* dB, int32_t n_cols, double* dY, void* stream) {
+    return guarded(h, [&] {
+        const ElimPlan& p = elim_args(h, direction, dB, n_cols);
+        dynamics_solve_all(h, p, dZ, direction == DTO_SOLVE_ADJOINT, dB, n_cols, dY, (hipStream_t)stream);
     }, G_ASYNC, (hipStream_t)stream);
 }
 
@@ -2614,6 +2847,8 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "dynsolve")) any_dynsolve = true;
         else if (!strcmp(name, "dynsolve_tree")) cat = CAT_DYNSOLVE_TREE;
         else if (!strcmp(name, "dynsolve_scan")) cat = CAT_DYNSOLVE_SCAN;
+        else if (!strcmp(name, "dynsolve_couple")) cat = CAT_DYNSOLVE_COUPLE;
+        else if (!strcmp(name, "dynsolve_deriv")) cat = CAT_DYNSOLVE_DERIV;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -2642,6 +2877,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (!any_gemm && !any_basis && cat >= 0 && r.cat != cat) continue;
             if (is_rollout_cat(r.cat) ? !(any_rollout || r.cat == cat) : any_rollout) continue;   // ("all": the rollout is no callback)
             if (is_dynsolve_cat(r.cat) ? !(any_dynsolve || r.cat == cat) : any_dynsolve) continue;   // (nor are the solves)
+            if (is_elim_cat(r.cat) && r.cat != cat) continue;
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "dto_comm.h"
+#include "dto_elim_plan.h"
 #include "dto_hostxfer.h"
 #include "dto_kernels.h"
 #include "dto_sweep_cache.h"
@@ -288,6 +289,20 @@ struct dto_handle {
     bool dyn_valid = false;
     int32_t dyn_integrator = -1;
     uint64_t dyn_gen = 0;
+    // whole-dynamics solves (dto_dynamics_solve_all[_dev]; plan: dto_elim_plan.h): a product tree per bilinear / time-dependent
+    // integrator (list position -> buffer, null for a DerivativeIntegrator), the compact coupling store and a copy of Z, all the
+    // call's own and kept per point -- Z bit for bit (d_elim_Z) and `gen`; neither dto_rollout nor dto_dynamics_solve touches them.
+    // Bp / Yp: one block solve's right-hand side and result; d_elim_B: the host-pointer form's B.  Grow-only (capacities in doubles).
+    std::unique_ptr<dto::ElimPlan> elim;
+    std::vector<double*> elim_tree;
+    std::vector<size_t> elim_tree_cap;
+    dto::KElimTerm* d_elim_terms = nullptr;          // forward terms of every integrator, then the adjoint terms
+    std::vector<int> elim_fw_term0, elim_ad_term0;   // [I + 1] ranges in d_elim_terms
+    double *d_elim_store = nullptr, *d_elim_Z = nullptr, *d_elim_Bp = nullptr, *d_elim_Yp = nullptr, *d_elim_B = nullptr;
+    size_t elim_store_cap = 0, elim_Bp_cap = 0, elim_Yp_cap = 0, elim_B_cap = 0;
+    int32_t* d_elim_eq = nullptr;
+    bool elim_valid = false;
+    uint64_t elim_gen = 0;
     int64_t* d_conbase = nullptr;        // [n_vars+1] first constraint-pattern entry of each column
     int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
     int64_t* d_crow_col = nullptr;

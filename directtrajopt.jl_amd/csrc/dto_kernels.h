@@ -459,6 +459,28 @@ void launch_dynsolve_up(hipStream_t st, const KRollout& R, int adjoint, int l, c
 // level l of the descent (L + 1: the root's item, then L .. 1); only >= 0: that item alone
 void launch_dynsolve_descend(hipStream_t st, const KRollout& R, int adjoint, int l, int64_t only, const double* tree, double* off, double* S);
 
+// Whole-dynamics solves (dto_elim.hip; plan and the coupling store's layout: dto_elim_plan.h).
+struct KElimPair {   // the coupling blocks of integrator a in the state columns of its dependency b
+    int32_t n_a, pre_a, x_off_b, n_b;
+    int32_t col, width;   // first column of S_b inside a's W_a columns, and W_a
+};
+struct KElimTerm {   // one contraction of k_elim_couple: a store and the slice of the result it meets
+    int64_t store;               // first double of the store read (C_a forward, C_b of a dependent b adjoint)
+    int32_t width, n_rows, col;  // that store's W and rows, and the first column read
+    int32_t off, n;              // the other integrator's slice [off, off + n) of the D axis
+};
+struct KElimCouple {
+    int32_t n_a, pre_a, D, n_cols, n_terms;
+    int64_t K;
+    const KElimTerm* terms;   // device
+};
+void launch_elim_gather(hipStream_t st, const KProb& P, const KElimPair& G, int64_t K, const double* vals, double* store);
+// Bp [K + 1][n_cols][n_a] from B and the finished slices of Y, both [K + 1][n_cols][D]
+void launch_elim_couple(hipStream_t st, const KElimCouple& C, int adjoint, const double* store, const double* B, const double* Y, double* Bp);
+// the block solve of a DerivativeIntegrator into its slice [pre, pre + n) of Y
+void launch_deriv_scan(hipStream_t st, int64_t K, int n, int n_cols, int D, int pre, int adjoint, const double* Bp, double* Y);
+void launch_elim_collect(hipStream_t st, int64_t N, int n, int n_cols, int D, int pre, const double* Yp, double* Y);
+
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);
 

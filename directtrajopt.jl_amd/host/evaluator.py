@@ -115,6 +115,7 @@ class Evaluator:
         # per integrator: its first row of g and (device kinds) the position of its states inside a knot
         self._integrator_row0 = [sum(p.dim for p in prob.integrators[:i]) for i in range(len(prob.integrators))]
         self._integrator_x_off = [getattr(it, "x_off", None) for it in prob.integrators]
+        self._integrator_list = list(prob.integrators)
         self._ext_con, self._ext_obj, self._ext_keep = [], [], None
         terms = _flatten_objective(prob.objective)
         objs = (capi.ObjectiveDesc * max(1, len(terms)))()
@@ -482,6 +483,91 @@ class Evaluator:
         grad[:N * dim].reshape(N, dim)[:, x_off:x_off + x_dim] = 0.0
         return grad
 
+    def dynamics_layout(self):
+        """(n_states, n_levels, offset, level) of the whole-dynamics solves: D = the sum of the integrators' state dimensions, the
+        number of dependency levels, and per integrator (list order) its offset on the D axis and its level -- 0 for an integrator
+        that reads no other integrator's states, else 1 + the highest level among those it reads.  Needs no device."""
+        n = len(self._integrator_dims)
+        ns, nl = C.c_int32(), C.c_int32()
+        off, lev = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        self._check(self._lib.dto_dynamics_layout(self._h, C.byref(ns), C.byref(nl), off.ctypes.data_as(capi.c_int32_p),
+                                                  lev.ctypes.data_as(capi.c_int32_p)))
+        return ns.value, nl.value, off[:n].copy(), lev[:n].copy()
+
+    def _solve_all_shape(self, B):
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        N, D = self.trajectory.N, sum(self._integrator_dims)
+        if B.ndim == 2 and B.shape[0] == N:
+            B = B.reshape(N, 1, B.shape[1])
+        if B.ndim != 3 or B.shape[0] != N or B.shape[2] != D:
+            raise ValueError(f"B: (N, n_cols, n_states) or (N, n_states) with N = {N}, n_states = {D} expected, got {B.shape}")
+        return B
+
+    def dynamics_solve_all(self, Z, B, adjoint=False):
+        """Solve with the Jacobian block of ALL integrators' rows and ALL their state columns at Z (identity rows for knot 1 on top),
+        on the device, by block elimination in dependency order.  Forward: the linearised rollout of the whole trajectory under
+        fixed controls (B = -defect with zero knot-1 rows: the Newton state correction).  ``adjoint=True``: the costates of all
+        dynamics rows; block 1 is the derivative with respect to the initial states.  ``B``: (N, n_cols, n_states), or
+        (N, n_states) for one column, the last axis listing the integrators in list order (``dynamics_layout``).  Returns
+        (N, n_cols, n_states).  A second call at the same Z, in either direction, launches no Jacobian, gather or tree kernel."""
+        Z = self._Z(Z)
+        B = self._solve_all_shape(B)
+        Y = np.full(B.shape, np.nan)
+        self._stage_external(Z, con_need=1)
+        self._check(self._lib.dto_dynamics_solve_all(self._h, _dp(Z), capi.SOLVE_ADJOINT if adjoint else capi.SOLVE_FORWARD, _dp(B),
+                                                     B.shape[1], _dp(Y)))
+        return Y
+
+    def feasible_trajectory(self, Z):
+        """Z with every integrator's states replaced by what its dynamics reach from the states of knot 1 under the controls,
+        timesteps and times of Z: levels ascending (``dynamics_layout``), a DerivativeIntegrator by its exact recurrence
+        x_{k+1} = x_k + dt_k xdot_k, the others by ``rollout`` at the Z updated so far.  Host vectors; returns a copy."""
+        Z = self._Z(Z).copy()
+        N, dim = self.trajectory.N, self.trajectory.dim
+        dt = self.trajectory.components[self.trajectory.timestep][0]
+        Zk = Z[:N * dim].reshape(N, dim)
+        _, n_levels, _, level = self.dynamics_layout()
+        for lv in range(n_levels):
+            for i, it in enumerate(self._integrator_list):
+                if level[i] != lv:
+                    continue
+                if isinstance(it, DerivativeIntegrator):
+                    for k in range(N - 1):
+                        Zk[k + 1, it.x_off:it.x_off + it.x_dim] = (Zk[k, it.x_off:it.x_off + it.x_dim]
+                                                                   + Zk[k, dt] * Zk[k, it.xdot_off:it.xdot_off + it.x_dim])
+                else:
+                    Zk[:, it.x_off:it.x_off + it.x_dim] = self.rollout(Z, integrator=i)[:, 0]
+        return Z
+
+    def reduced_gradient(self, Z):
+        """Gradient of the objective along the dynamically feasible manifold at a FEASIBLE Z (``feasible_trajectory``'s result):
+        the derivative of f(feasible_trajectory(.)) with respect to everything the states of knots 2 .. N are a function of.  One
+        objective gradient, one adjoint whole-dynamics solve L = MM'^{-1} df/ds, one J' w with L_2 .. L_N in the dynamics rows of a
+        zero w.  Entries of controls, timesteps, times and globals: df/dc - (J' w)_c; state entries of knot 1: L_1; the other state
+        entries: 0.  Host vectors; returns (n_variables,)."""
+        Z = self._Z(Z)
+        N, dim = self.trajectory.N, self.trajectory.dim
+        D, _, offset, _ = self.dynamics_layout()
+        g = np.full(self.n_variables, np.nan)
+        self.eval_objective_gradient(g, Z)
+        gk = g[:N * dim].reshape(N, dim)
+        B = np.zeros((N, 1, D))
+        for i, it in enumerate(self._integrator_list):
+            B[:, 0, offset[i]:offset[i] + it.x_dim] = gk[:, it.x_off:it.x_off + it.x_dim]
+        lam = self.dynamics_solve_all(Z, B, adjoint=True)[:, 0]
+        w = np.zeros(self.n_constraints)
+        for i, it in enumerate(self._integrator_list):
+            row0 = self._integrator_row0[i]
+            w[row0:row0 + (N - 1) * it.x_dim] = lam[1:, offset[i]:offset[i] + it.x_dim].reshape(-1)
+        y = np.full(self.n_variables, np.nan)
+        self.eval_constraint_jacobian_transpose_product(y, Z, w)
+        grad = g - y
+        rk = grad[:N * dim].reshape(N, dim)
+        for i, it in enumerate(self._integrator_list):
+            rk[:, it.x_off:it.x_off + it.x_dim] = 0.0
+            rk[0, it.x_off:it.x_off + it.x_dim] = lam[0, offset[i]:offset[i] + it.x_dim]
+        return grad
+
     def constraint_bounds(self):  # get_nonlinear_constraints, src/solvers/solve.jl:30-65
         lo = np.empty(self.n_constraints)
         hi = np.empty(self.n_constraints)
@@ -543,6 +629,13 @@ class Evaluator:
         self._stage_external(Z_host, con_need=1)
         self._check(self._lib.dto_dynamics_solve_dev(self._h, int(integrator), dZ, capi.SOLVE_ADJOINT if adjoint else capi.SOLVE_FORWARD,
                                                      dB or None, int(n_cols), capi.ROLLOUT_ALL if all_knots else capi.ROLLOUT_FINAL, dY, stream))
+
+    def dynamics_solve_all_dev(self, dZ, dB, n_cols, dY, adjoint=False, stream=0, Z_host=None):
+        """``dynamics_solve_all`` on device pointers: dB and dY (N, n_cols, n_states), not overlapping; enqueued on `stream`, errors
+        deferred as for every `_dev` call.  Same bits as ``dynamics_solve_all``."""
+        self._stage_external(Z_host, con_need=1)
+        self._check(self._lib.dto_dynamics_solve_all_dev(self._h, dZ, capi.SOLVE_ADJOINT if adjoint else capi.SOLVE_FORWARD, dB or None,
+                                                         int(n_cols), dY, stream))
 
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod

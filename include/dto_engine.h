@@ -408,6 +408,42 @@ int dto_dynamics_solve(dto_handle* h, int32_t integrator, const double* Z, int32
 int dto_dynamics_solve_dev(dto_handle* h, int32_t integrator, const double* dZ, int32_t direction, const double* dB, int32_t n_cols,
                            int32_t mode, double* dY, void* stream);
 
+/* ---- Whole-dynamics solves: all integrators' states at once.  With I integrators of state components S_i = [x_off, x_off + x_dim),
+ * D = sum x_dim and pre_i the sum of the dimensions before i in list order, MM is the N D x N D block of the Jacobian formed by ALL
+ * integrators' rows and ALL their state columns: per integrator an identity row block for knot 1, below it its defect rows of
+ * intervals 1 .. N-1 restricted to the columns S_j of every knot -- entry for entry what dto_eval_jacobian returns at Z.  Besides the
+ * diagonal blocks M_i of dto_dynamics_solve it holds the couplings: the controls of a bilinear integrator that a DerivativeIntegrator
+ * integrates, du / ddu chains, a time-dependent integrator of spline order 1 reaching u_{k+1}.
+ *   DTO_SOLVE_FORWARD  MM Y = B.  B = -(defect of Z) with zero knot-1 rows gives the first-order state correction of the whole
+ *                      trajectory under fixed controls.
+ *   DTO_SOLVE_ADJOINT  MM' Lam = B: the costates of all dynamics rows; Lam_1 is the derivative with respect to the initial states.
+ *   B, Y: [N][n_cols][D], the D axis listing the integrators in list order, x_dim contiguous each (dto_dynamics_layout); they must
+ *   not overlap.  1 <= n_cols <= the smallest x_dim among the bilinear and time-dependent integrators (each block solve's own limit);
+ *   1 .. 64 on a handle with DerivativeIntegrators only.  All knots are returned.
+ * MM is block-triangular in DEPENDENCY order: integrator a depends on b != a when S_b meets a's inputs -- the controls and the
+ * timestep component (bilinear), these and the time component (time-dependent), the derivative's components and the timestep
+ * component (derivative).  level(a) = 0 without dependencies, else 1 + max level(deps).  The forward solve visits the integrators by
+ * (level, list position) ascending: B'_{k+1} = B_{k+1} - C_{a,k} [Y^deps_k ; Y^deps_{k+1}], then a's own block solve; the adjoint solve
+ * in the reverse order with B'_k = B_k - sum over a's dependents b of C_b' Lam^b (dependents in list order, interval k-1 before k, rows
+ * ascending).  Every entry has one writer and a fixed summation order, without atomics: repeated calls are bit-identical, both
+ * entry-point families return the same bits, a column has the same bits alone and among others, a rebuilt point gives the bits of a
+ * cached one.  The block of a level-0 DerivativeIntegrator is the serial sum Y_{k+1} = Y_k + B_{k+1} (Lam_k = Lam_{k+1} + B_k) in
+ * double, bit for bit.
+ * At a new point the call evaluates the Jacobian ONCE into the private slab, builds a product tree per bilinear and time-dependent
+ * integrator, copies the coupling blocks into a compact store and keeps a copy of Z.  These are the call's own workspaces -- one tree
+ * of (2^(L+1) - 1) npad^2 doubles PER integrator (members of a shared-generator group included), the store of
+ * (N-1) x 2 x x_dim_a x (sum of its dependencies' x_dim) doubles per integrator a -- grow-only, freed with the handle; dto_rollout and
+ * dto_dynamics_solve neither read nor disturb them.  They are kept per point as dto_dynamics_solve keeps its tree: a call at the Z of
+ * the last one, bit for bit, with no dto_set_external, dto_set_option or failed call since, launches no Jacobian, gather or tree kernel.
+ * Refused with text, the handle stays usable: a host-evaluated integrator anywhere in the handle, a sharded or structure-only handle,
+ * integrators whose states overlap, an integrator whose inputs meet its own states, a dependency cycle, n_cols out of range, a
+ * direction other than the two, B = NULL, a failed workspace allocation.
+ * dto_dynamics_layout: D, the number of levels, and per integrator its offset pre_i on the D axis and its level (either array may be
+ * NULL); it needs no device and answers on structure-only handles too. */
+int dto_dynamics_layout(const dto_handle* h, int32_t* n_states, int32_t* n_levels, int32_t* offset /*[n_integrators]*/, int32_t* level /*[n_integrators]*/);
+int dto_dynamics_solve_all(dto_handle* h, const double* Z, int32_t direction, const double* B, int32_t n_cols, double* Y);
+int dto_dynamics_solve_all_dev(dto_handle* h, const double* dZ, int32_t direction, const double* dB, int32_t n_cols, double* dY, void* stream);
+
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
  * communicator (SURVEY.md §8b "Ownership").  No callback needs a collective: every rank's Jacobian / Hessian / gradient
@@ -562,7 +598,10 @@ int dto_profile_reset(dto_handle* h);
  * "dynsolve" (dto_dynamics_solve / dto_dynamics_solve_dev; its parts "dynsolve_tree", the gather and the tree's products of a rebuild
  * -- no launches at a cached point -- and "dynsolve_scan", the loader, the offsets' up-sweep, the descent and the copy into the
  * caller's layout; flops as executed with padding; like the rollout's these names feed no other, "all" included, and the Jacobian
- * evaluation inside a rebuild counts under its own names).
+ * evaluation inside a rebuild counts under its own names),
+ * "dynsolve_couple" and "dynsolve_deriv" (dto_dynamics_solve_all / dto_dynamics_solve_all_dev: the gather of the coupling blocks with
+ * the contractions against them, and the DerivativeIntegrators' block solves -- third output: BYTES as executed; the call's other
+ * block solves count under "dynsolve_tree" and "dynsolve_scan"; neither name feeds another, "dynsolve" and "all" included).
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the
  * third output is the launches' algorithmic BYTES (what they must read and write), not FLOPs.
  * "hess_product_setup" returns the host milliseconds of the products' index build (once per handle), 0 launches, and the device

@@ -716,6 +716,47 @@ function dynamics_solve_dev!(ev::GPUEvaluator, dY::Ptr{Float64}, dZ::Ptr{Float64
                                                 mode::Int32, dY::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 end
 
+# ---- whole-dynamics solves (include/dto_engine.h, "Whole-dynamics solves") -----------------------------------------------------------
+# The Jacobian block of ALL integrators' rows and ALL their state columns, with identity rows for knot 1: what a reduced-space method
+# eliminates the states with.  `dynamics_layout` returns (n_states, n_levels, offset, level): D = the sum of the integrators' state
+# dimensions and, per integrator of `prob.integrators` (`n_integrators` = their number), its 0-based offset on the D axis and its
+# dependency level.  It needs no device.
+function dynamics_layout(ev::GPUEvaluator, n_integrators::Integer)
+    n = Int(n_integrators)
+    ns = Ref{Int32}(0); nl = Ref{Int32}(0)
+    offset = zeros(Int32, max(n, 1)); level = zeros(Int32, max(n, 1))
+    GC.@preserve offset level check(ev, @ccall lib.dto_dynamics_layout(ev.handle::Ptr{Cvoid}, ns::Ptr{Int32}, nl::Ptr{Int32}, offset::Ptr{Int32},
+                                                                       level::Ptr{Int32})::Cint)
+    return Int(ns[]), Int(nl[]), offset[1:n], level[1:n]
+end
+
+# Forward, the linearised rollout of the whole trajectory under fixed controls (B = -defect with zero knot-1 columns: the Newton state
+# correction); with `adjoint = true` the costates of all dynamics rows, slice 1 the derivative with respect to the initial states.
+# `B`: n_states x n_cols x N (a Matrix is one column per knot).  Returns n_states x n_cols x N.  A second solve at the same Z -- in
+# either direction -- launches no Jacobian, gather or tree kernel.
+function dynamics_solve_all(ev::GPUEvaluator, Z::AbstractVector{Float64}, B::AbstractArray{Float64}; adjoint::Bool = false)
+    stage_external!(ev, Z; con_need = 1)
+    N = ev.trajectory.N
+    Bm = Array{Float64,3}(ndims(B) == 3 ? B : reshape(B, size(B, 1), 1, :))
+    size(Bm, 3) == N || error("dynamics_solve_all: B holds $(size(Bm, 3)) knots, the trajectory has $N")
+    nc = Int32(size(Bm, 2))
+    dir = adjoint ? DTO_SOLVE_ADJOINT : DTO_SOLVE_FORWARD
+    Y = fill(NaN, size(Bm, 1), Int(nc), N)
+    GC.@preserve Y Z Bm check(ev, @ccall lib.dto_dynamics_solve_all(ev.handle::Ptr{Cvoid}, Z::Ptr{Float64}, dir::Int32, Bm::Ptr{Float64}, nc::Int32,
+                                                                    Y::Ptr{Float64})::Cint)
+    return Y
+end
+
+# the same on device pointers: dB and dY n_states x n_cols x N, not overlapping; enqueued on `stream`
+function dynamics_solve_all_dev!(ev::GPUEvaluator, dY::Ptr{Float64}, dZ::Ptr{Float64}, dB::Ptr{Float64}, n_cols::Integer, stream::Ptr{Cvoid};
+                                 adjoint::Bool = false, Z_host = nothing)
+    Z_host === nothing || stage_external!(ev, Z_host; con_need = 1)
+    nc = Int32(n_cols)
+    dir = adjoint ? DTO_SOLVE_ADJOINT : DTO_SOLVE_FORWARD
+    check(ev, @ccall lib.dto_dynamics_solve_all_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, dir::Int32, dB::Ptr{Float64}, nc::Int32,
+                                                    dY::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
 # row bounds handed to the solver (src/solvers/solve.jl:30-65)
 function constraint_bounds(ev::GPUEvaluator)
     lo = Vector{Float64}(undef, ev.n_constraints)
