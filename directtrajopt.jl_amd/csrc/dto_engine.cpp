@@ -73,7 +73,7 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24 };
 // CAT_ROLLOUT .. CAT_ROLLOUT_DESCENT ("rollout" = its parts "rollout_gather" + "rollout_tree" + "rollout_descent"): the gather, the
 // tree's products and the descent (with the start and the copy into the caller's layout) of dto_rollout[_dev], flops as executed with
 // padding; the tree's products run launch_bgemm_plain and count HERE, not under "bgemm_plain"; they feed no other name, "all" included
@@ -86,6 +86,9 @@ inline bool is_dynsolve_cat(int cat) { return cat == CAT_DYNSOLVE_TREE || cat ==
 // coupling blocks with the contractions against them, and the DerivativeIntegrators' block solves; the third output carries BYTES as
 // executed.  (Its other block solves count under "dynsolve_tree" / "dynsolve_scan".)  They feed no other name, "all" included.
 inline bool is_elim_cat(int cat) { return cat == CAT_DYNSOLVE_COUPLE || cat == CAT_DYNSOLVE_DERIV; }
+// CAT_REDUCED_PACK ("reduced_pack"): the packers of dto_reduced_gradient / dto_reduced_hessian_product and their _dev forms
+// (dto_reduced.hip); the third output carries BYTES as executed.  It feeds no other name, "all" included; the routines the operators
+// are made of count under their own names.
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
 inline void count_sweep_form(dto_handle* h, int form) {
     if (h->profiling) ++h->sweep_forms[form];
@@ -2595,6 +2598,160 @@ int dto_dynamics_solve_all_dev(dto_handle* h, const double* dZ, int32_t directio
     }, G_ASYNC, (hipStream_t)stream);
 }
 
+// ---- reduced-space operators: the gradient and the Hessian-vector product of the problem with the states eliminated by the dynamics
+// (include/dto_engine.h, "Reduced-space operators"; dto_reduced.hip, dto_reduced_plan.h).  Compositions of do_gradient, jac_product,
+// dynamics_solve_all (one column) and hess_product, all on `st` and all unchanged; the packers keep every vector on the device.
+
+// What a reduced-space call names: refused with text before anything is enqueued.
+static const ElimPlan& reduced_args(dto_handle* h, const std::string& who, bool hessian) {
+    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{who + " needs an unsharded handle (k_lo, k_hi = the whole trajectory)"};
+    const ElimPlan& p = elim_plan_of(h);
+    if (!p.refusal.empty()) throw HipError{who + ": " + p.refusal};
+    if (h->n_ext_int + h->n_ext_con + h->n_ext_obj > 0)
+        throw HipError{who + ": the handle holds host-evaluated terms (" + std::to_string(h->n_ext_int) + " integrators, " +
+                       std::to_string(h->n_ext_con) + " constraints, " + std::to_string(h->n_ext_obj) +
+                       " objectives): the reduced-space operators run on device-evaluated terms only"};
+    if (hessian && !h->eval_hessian) throw HipError{who + ": handle was created with eval_hessian = 0"};
+    if (p.n_states < 1) throw HipError{who + ": the handle has no integrator, so no states to eliminate"};
+    int64_t rows = 0;
+    for (size_t i = 0; i < h->integ_dim.size(); ++i) rows = std::max(rows, h->integ_row_off[i] + h->K * h->integ_dim[i]);
+    if (h->n_dyn != h->K * p.n_states || rows > h->n_dyn) throw HipError{who + ": the dynamics rows are not the first (N - 1) n_states rows"};
+    return p;
+}
+
+// The operators' one block of device memory and the plan's tables, once per handle and before anything is enqueued.
+static void reduced_workspaces(dto_handle* h, const ElimPlan& p) {
+    if (h->d_red) return;
+    std::vector<ReducedIntegrator> its;
+    for (size_t i = 0; i < h->integ_kind.size(); ++i)
+        its.push_back(ReducedIntegrator{elim_x_off(h, (int)i), h->integ_dim[i], p.pre[i], h->integ_row_off[i]});
+    const ReducedPlan rp = reduced_plan(its, h->z);
+    const size_t nv = (size_t)h->n_vars, nc = (size_t)std::max<int64_t>(h->n_cons, 1), nd = (size_t)h->N * p.n_states;
+    double* blk = dalloc<double>(7 * nv + 4 * nc + 3 * nd);
+    int32_t *comp_pos = nullptr, *pos_comp = nullptr, *pos_dim = nullptr, *eq = nullptr;
+    int64_t* pos_row = nullptr;
+    try {
+        comp_pos = dupload(rp.comp_pos); pos_comp = dupload(rp.pos_comp); pos_dim = dupload(rp.pos_dim); pos_row = dupload(rp.pos_row);
+        eq = dalloc<int32_t>(1);
+    } catch (...) {
+        for (void* q : {(void*)blk, (void*)comp_pos, (void*)pos_comp, (void*)pos_dim, (void*)pos_row}) if (q) (void)hipFree(q);
+        throw;
+    }
+    h->red = KReduced{own(h, comp_pos), own(h, pos_comp), own(h, pos_dim), own(h, pos_row), h->z, p.n_states, h->N, h->n_vars, h->n_cons, h->n_dyn};
+    h->d_red_eq = own(h, eq);
+    double* q = blk;
+    auto take = [&](size_t n) { double* r = q; q += n; return r; };
+    h->red_Z = take(nv); h->red_g = take(nv); h->red_r = take(nv); h->red_a = take(nv); h->red_b = take(nv); h->red_hv = take(nv); h->red_out = take(nv);
+    h->red_mu = take(nc); h->red_mut = take(nc); h->red_w = take(nc); h->red_hmu = take(nc);
+    h->red_lam = take(nd); h->red_s1 = take(nd); h->red_s2 = take(nd);
+    h->d_red = own(h, blk);
+}
+
+// The reduced point: g, Lam, mu~ and the reduced gradient at (Z, sigma, mu), computed unless the ones kept belong to this point --
+// Z and mu bit for bit (one compare with a 4-byte readback), sigma, the "mu = NULL" mark and `gen`.
+static void reduced_point(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, hipStream_t st) {
+    const KReduced& R = h->red;
+    const double nv = 8.0 * (double)h->n_vars, nc = 8.0 * (double)h->n_cons, nd = 8.0 * (double)h->N * R.D;
+    bool hit = h->red_valid && h->red_gen == h->gen && memcmp(&sigma, &h->red_sigma, sizeof(double)) == 0 && (dmu == nullptr) == h->red_mu_null;
+    if (hit)
+        hit = dmu ? bits_equal(st, {{dZ, h->red_Z, h->n_vars}, {dmu, h->red_mu, h->n_cons}}, h->d_red_eq, &h->mailbox->red_flag)
+                  : bits_equal(st, {{dZ, h->red_Z, h->n_vars}}, h->d_red_eq, &h->mailbox->red_flag);
+    if (hit) return;
+    h->red_valid = false;
+    do_gradient(h, dZ, h->red_a, st);
+    const double* t1 = nullptr;
+    if (dmu) {   // J' w1, w1 = mu with its dynamics rows zeroed
+        { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nc); launch_red_multipliers(st, R, nullptr, dmu, 1, h->red_w, nullptr); }
+        jac_product(h, dZ, h->red_w, h->red_b, 1, st);
+        t1 = h->red_b;
+    }
+    { ProfScope ps(h, st, CAT_REDUCED_PACK, (t1 ? 3.0 : 2.0) * nv + nd); launch_red_gradient(st, R, sigma, h->red_a, t1, h->red_g, h->red_s1); }
+    dynamics_solve_all(h, p, dZ, 1, h->red_s1, 1, h->red_lam, st);
+    { ProfScope ps(h, st, CAT_REDUCED_PACK, nd + (dmu ? 3.0 : 2.0) * nc); launch_red_multipliers(st, R, h->red_lam, dmu, 0, h->red_w, h->red_mut); }
+    jac_product(h, dZ, h->red_w, h->red_b, 1, st);
+    { ProfScope ps(h, st, CAT_REDUCED_PACK, 3.0 * nv); launch_red_finish(st, R, h->red_g, h->red_b, h->red_lam, h->red_r); }
+    HIP_CHECK(hipMemcpyAsync(h->red_Z, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
+    if (dmu && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->red_mu, dmu, sizeof(double) * (size_t)h->n_cons, hipMemcpyDeviceToDevice, st));
+    h->red_mu_null = dmu == nullptr;
+    h->red_sigma = sigma;
+    h->red_gen = h->gen;
+    h->red_valid = true;
+}
+
+// The device routines both entry-point families run: everything on `st`, every pointer a device pointer.
+static void reduced_gradient(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, double* dgrad, double* dlam,
+                             hipStream_t st) {
+    reduced_point(h, p, dZ, sigma, dmu, st);
+    if (dgrad) HIP_CHECK(hipMemcpyAsync(dgrad, h->red_r, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
+    if (dlam) HIP_CHECK(hipMemcpyAsync(dlam, h->red_lam, sizeof(double) * (size_t)h->N * h->red.D, hipMemcpyDeviceToDevice, st));
+}
+
+// y = T' H(Z; sigma, mu~) T v.  At the reduced point's (Z, sigma, mu): steps 1 .. 8 of the header alone.
+static void reduced_hessian_product(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, const double* dv,
+                                    double* dy, hipStream_t st) {
+    reduced_point(h, p, dZ, sigma, dmu, st);
+    const KReduced& R = h->red;
+    const double nv = 8.0 * (double)h->n_vars, nc = 8.0 * (double)h->n_cons, nd = 8.0 * (double)h->N * R.D;
+    { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_vhat(st, R, dv, h->red_a); }
+    jac_product(h, dZ, h->red_a, h->red_w, 0, st);                          // rho = J v^
+    { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nd); launch_red_rhs(st, R, dv, h->red_w, h->red_s1); }
+    dynamics_solve_all(h, p, dZ, 0, h->red_s1, 1, h->red_s2, st);           // MM Y = B
+    { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_zhat(st, R, dv, h->red_s2, h->red_a); }
+    hess_product(h, dZ, sigma, h->red_mut, h->red_a, h->red_b, st);         // q = H(mu~) z^
+    { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nd); launch_red_gather(st, R, h->red_b, h->red_s1); }
+    dynamics_solve_all(h, p, dZ, 1, h->red_s1, 1, h->red_s2, st);           // MM' Gam = q_S
+    { ProfScope ps(h, st, CAT_REDUCED_PACK, nd + nc); launch_red_multipliers(st, R, h->red_s2, nullptr, 0, h->red_w, nullptr); }
+    jac_product(h, dZ, h->red_w, h->red_a, 1, st);                          // t = J' w
+    { ProfScope ps(h, st, CAT_REDUCED_PACK, 3.0 * nv); launch_red_finish(st, R, h->red_b, h->red_a, h->red_s2, dy); }
+}
+
+int dto_reduced_gradient(dto_handle* h, const double* Z, double sigma, const double* mu, double* grad, double* lam) {
+    return guarded(h, [&] {
+        const std::string who = "dto_reduced_gradient";
+        const ElimPlan& p = reduced_args(h, who, false);
+        if (!Z || !grad) throw HipError{who + ": Z and grad are required (NULL given)"};
+        reduced_workspaces(h, p);
+        upload_Z(h, Z);
+        if (mu && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->red_hmu, mu, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        reduced_point(h, p, h->d_Z, sigma, mu ? h->red_hmu : nullptr, h->stream);
+        HIP_CHECK(hipMemcpyAsync(grad, h->red_r, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToHost, h->stream));
+        if (lam) HIP_CHECK(hipMemcpyAsync(lam, h->red_lam, sizeof(double) * (size_t)h->N * p.n_states, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_reduced_gradient_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, double* dgrad, double* dlam, void* stream) {
+    return guarded(h, [&] {
+        const std::string who = "dto_reduced_gradient_dev";
+        const ElimPlan& p = reduced_args(h, who, false);
+        if (!dZ || !dgrad) throw HipError{who + ": dZ and dgrad are required (NULL given)"};
+        reduced_workspaces(h, p);
+        reduced_gradient(h, p, dZ, sigma, dmu, dgrad, dlam, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+int dto_reduced_hessian_product(dto_handle* h, const double* Z, double sigma, const double* mu, const double* v, double* y) {
+    return guarded(h, [&] {
+        const std::string who = "dto_reduced_hessian_product";
+        const ElimPlan& p = reduced_args(h, who, true);
+        if (!Z || !v || !y) throw HipError{who + ": Z, v and y are required (NULL given)"};
+        reduced_workspaces(h, p);
+        upload_Z(h, Z);
+        if (mu && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->red_hmu, mu, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(h->red_hv, v, sizeof(double) * (size_t)h->n_vars, hipMemcpyHostToDevice, h->stream));
+        reduced_hessian_product(h, p, h->d_Z, sigma, mu ? h->red_hmu : nullptr, h->red_hv, h->red_out, h->stream);
+        HIP_CHECK(hipMemcpyAsync(y, h->red_out, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_reduced_hessian_product_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dv, double* dy, void* stream) {
+    return guarded(h, [&] {
+        const std::string who = "dto_reduced_hessian_product_dev";
+        const ElimPlan& p = reduced_args(h, who, true);
+        if (!dZ || !dv || !dy) throw HipError{who + ": dZ, dv and dy are required (NULL given)"};
+        reduced_workspaces(h, p);
+        reduced_hessian_product(h, p, dZ, sigma, dmu, dv, dy, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
 // ---- multi-GPU: ranges, gather plans, collectives (dto_comm.h)
 int dto_comm_unique_id(void* id128) {
     if (!id128) return fail(nullptr, "dto_comm_unique_id: null argument");
@@ -2849,6 +3006,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "dynsolve_scan")) cat = CAT_DYNSOLVE_SCAN;
         else if (!strcmp(name, "dynsolve_couple")) cat = CAT_DYNSOLVE_COUPLE;
         else if (!strcmp(name, "dynsolve_deriv")) cat = CAT_DYNSOLVE_DERIV;
+        else if (!strcmp(name, "reduced_pack")) cat = CAT_REDUCED_PACK;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -2878,6 +3036,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (is_rollout_cat(r.cat) ? !(any_rollout || r.cat == cat) : any_rollout) continue;   // ("all": the rollout is no callback)
             if (is_dynsolve_cat(r.cat) ? !(any_dynsolve || r.cat == cat) : any_dynsolve) continue;   // (nor are the solves)
             if (is_elim_cat(r.cat) && r.cat != cat) continue;
+            if (r.cat == CAT_REDUCED_PACK && r.cat != cat) continue;
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));

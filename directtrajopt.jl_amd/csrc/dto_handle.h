@@ -202,6 +202,7 @@ struct PinnedMailbox {
     int32_t same_flag;             // same_point's bit compare
     int32_t hp_flag;               // hess_product's bit compare
     int32_t dyn_flag;              // dynamics_solve's bit compare
+    int32_t red_flag;              // the reduced point's bit compare
     int32_t deferred_smax;         // the one-launch chain's squaring count of an enqueue-only call (smax_pending)
 };
 }  // namespace dto
@@ -303,6 +304,21 @@ struct dto_handle {
     int32_t* d_elim_eq = nullptr;
     bool elim_valid = false;
     uint64_t elim_gen = 0;
+    // reduced-space operators (dto_reduced_gradient[_dev], dto_reduced_hessian_product[_dev]; plan: dto_reduced_plan.h).  One block
+    // d_red holds every vector; its sizes depend on the handle alone, so it is allocated once, before anything is enqueued, and freed
+    // with the handle.  The reduced POINT is kept like the other per-point caches -- Z bit for bit (red_Z), sigma, mu bit for bit
+    // (red_mu) or the mark "mu was NULL", and `gen` -- and holds g (red_g), the costates Lam [N][D] (red_lam), the multipliers mu~
+    // (red_mut) and the reduced gradient (red_r).  a, b [n_vars], w [n_cons], s1, s2 [N D]: scratch of one call; hv, hmu: v and mu
+    // of the host-pointer forms; out: their y.
+    dto::KReduced red{};   // device tables
+    double* d_red = nullptr;
+    double *red_Z = nullptr, *red_mu = nullptr, *red_g = nullptr, *red_lam = nullptr, *red_mut = nullptr, *red_r = nullptr;
+    double *red_a = nullptr, *red_b = nullptr, *red_w = nullptr, *red_s1 = nullptr, *red_s2 = nullptr;
+    double *red_hv = nullptr, *red_hmu = nullptr, *red_out = nullptr;
+    int32_t* d_red_eq = nullptr;
+    bool red_valid = false, red_mu_null = false;
+    double red_sigma = 0.0;
+    uint64_t red_gen = 0;
     int64_t* d_conbase = nullptr;        // [n_vars+1] first constraint-pattern entry of each column
     int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
     int64_t* d_crow_col = nullptr;

@@ -6,6 +6,7 @@
 
 #include <cstdlib>
 
+#include "dto_reduced_plan.h"  // index plan of the reduced-space operators (KReduced)
 #include "dto_slab_layout.h"  // where every Jacobian and Hessian entry sits in its value slab
 #include "dto_sweep_plan.h"   // sweep planning: step budget, launch shapes (SweepTypes, the *SweepPlan structs and planners), form choice
 
@@ -480,6 +481,19 @@ void launch_elim_couple(hipStream_t st, const KElimCouple& C, int adjoint, const
 // the block solve of a DerivativeIntegrator into its slice [pre, pre + n) of Y
 void launch_deriv_scan(hipStream_t st, int64_t K, int n, int n_cols, int D, int pre, int adjoint, const double* Bp, double* Y);
 void launch_elim_collect(hipStream_t st, int64_t N, int n, int n_cols, int D, int pre, const double* Yp, double* Y);
+
+// Reduced-space operators (dto_reduced.hip; index plan: dto_reduced_plan.h): the packers between the Z layout (n_vars), the
+// constraint rows (n_cons) and the solves' [N][1][D].  R's tables are device pointers.
+// g = sigma * gf (+ t, nullable) [n_vars]; gS: its state entries as [N][1][D]
+void launch_red_gradient(hipStream_t st, const KReduced& R, double sigma, const double* gf, const double* t, double* g, double* gS);
+// w [n_cons]: lam_{k+1} (nullable: 0) in the dynamics rows of interval k, mu (w_takes_mu, mu not null) or 0 in the other rows;
+// mut [n_cons] (nullable): -lam_{k+1} in the dynamics rows, mu (null: 0) in the other rows
+void launch_red_multipliers(hipStream_t st, const KReduced& R, const double* lam, const double* mu, int w_takes_mu, double* w, double* mut);
+void launch_red_vhat(hipStream_t st, const KReduced& R, const double* v, double* vh);                                  // states zeroed
+void launch_red_rhs(hipStream_t st, const KReduced& R, const double* v, const double* rho, double* B);                 // [v_S0 ; -rho_dyn]
+void launch_red_zhat(hipStream_t st, const KReduced& R, const double* v, const double* Y, double* zh);                 // states <- Y
+void launch_red_gather(hipStream_t st, const KReduced& R, const double* q, double* qS);                                // states of q
+void launch_red_finish(hipStream_t st, const KReduced& R, const double* q, const double* t, const double* lam, double* y);
 
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);

@@ -568,6 +568,38 @@ class Evaluator:
             rk[0, it.x_off:it.x_off + it.x_dim] = lam[0, offset[i]:offset[i] + it.x_dim]
         return grad
 
+    def reduced_lagrangian_gradient(self, Z, sigma=1.0, mu=None, costates=False):
+        """Reduced-space gradient on the device (``dto_reduced_gradient``): with the states of knots 2 .. N (the set S) eliminated by
+        the dynamics, the gradient of phi = sigma f + sum over the non-dynamics rows of mu_r g_r.  g = sigma grad f + J' w1 (w1 = mu
+        with its dynamics rows zeroed; ``mu=None``: zeros, the product is skipped), MM' Lam = g_S, t = J' w2 (Lam_2 .. Lam_N in the
+        dynamics rows).  Returns (n_variables,): g - t on controls, timesteps, times and globals, Lam_1 on the states of knot 1, 0 on
+        S; with ``costates=True`` also Lam as (N, n_states) (``dynamics_layout``).  With sigma = 1 and mu = None the bits of
+        ``reduced_gradient``.  The point -- costates, multipliers, gradient -- is kept per (Z, sigma, mu) for
+        ``reduced_hessian_product``; a repeated call copies the kept result."""
+        Z = self._Z(Z)
+        if mu is not None:
+            mu = _in(mu, self.n_constraints, "mu")
+        grad = np.full(self.n_variables, np.nan)
+        lam = np.full((self.trajectory.N, sum(self._integrator_dims)), np.nan) if costates else None
+        self._check(self._lib.dto_reduced_gradient(self._h, _dp(Z), float(sigma), None if mu is None else _dp(mu), _dp(grad),
+                                                   None if lam is None else _dp(lam)))
+        return (grad, lam) if costates else grad
+
+    def reduced_hessian_product(self, Z, v, sigma=1.0, mu=None):
+        """y = T' H(Z; sigma, mu~) T v on the device (``dto_reduced_hessian_product``): the Hessian-vector product of the reduced
+        problem, T the tangent map of the feasible manifold and mu~ = mu on the non-dynamics rows, minus the costates of
+        ``reduced_lagrangian_gradient`` on the dynamics rows.  ``v``: (n_variables,), its entries at the states of knots 2 .. N are
+        not read.  Returns (n_variables,), zero at those entries.  At a dynamically feasible Z (``feasible_trajectory``) this is the
+        Hessian of phi(feasible_trajectory(.)); symmetric at any Z.  Products at the (Z, sigma, mu) of the last call run one J w, one
+        J' w, two whole-dynamics scans and one H v: no Jacobian chain, tree build or Hessian assembly."""
+        Z = self._Z(Z)
+        v = _in(v, self.n_variables, "v")
+        if mu is not None:
+            mu = _in(mu, self.n_constraints, "mu")
+        y = np.full(self.n_variables, np.nan)
+        self._check(self._lib.dto_reduced_hessian_product(self._h, _dp(Z), float(sigma), None if mu is None else _dp(mu), _dp(v), _dp(y)))
+        return y
+
     def constraint_bounds(self):  # get_nonlinear_constraints, src/solvers/solve.jl:30-65
         lo = np.empty(self.n_constraints)
         hi = np.empty(self.n_constraints)
@@ -636,6 +668,16 @@ class Evaluator:
         self._stage_external(Z_host, con_need=1)
         self._check(self._lib.dto_dynamics_solve_all_dev(self._h, dZ, capi.SOLVE_ADJOINT if adjoint else capi.SOLVE_FORWARD, dB or None,
                                                          int(n_cols), dY, stream))
+
+    def reduced_gradient_dev(self, dZ, sigma, dmu, dgrad, dlam=0, stream=0):
+        """``reduced_lagrangian_gradient`` on device pointers: dmu (n_constraints) or 0 / None for zeros, dgrad (n_variables), dlam
+        (N, n_states) or 0 / None; enqueued on `stream`, errors deferred as for every `_dev` call.  Same bits as the host form."""
+        self._check(self._lib.dto_reduced_gradient_dev(self._h, dZ, float(sigma), dmu or None, dgrad or None, dlam or None, stream))
+
+    def reduced_hessian_product_dev(self, dZ, sigma, dmu, dv, dy, stream=0):
+        """``reduced_hessian_product`` on device pointers: dmu (n_constraints) or 0 / None for zeros, dv and dy (n_variables), not
+        overlapping; enqueued on `stream`, errors deferred as for every `_dev` call.  Same bits as the host form."""
+        self._check(self._lib.dto_reduced_hessian_product_dev(self._h, dZ, float(sigma), dmu or None, dv or None, dy or None, stream))
 
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod

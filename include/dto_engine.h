@@ -444,6 +444,57 @@ int dto_dynamics_layout(const dto_handle* h, int32_t* n_states, int32_t* n_level
 int dto_dynamics_solve_all(dto_handle* h, const double* Z, int32_t direction, const double* B, int32_t n_cols, double* Y);
 int dto_dynamics_solve_all_dev(dto_handle* h, const double* dZ, int32_t direction, const double* dB, int32_t n_cols, double* dY, void* stream);
 
+/* ---- Reduced-space operators: the gradient and the Hessian-vector product of the problem with the states eliminated by the dynamics
+ * -- the control-only view a GRAPE-style or truncated-Newton method works in.  S is the set of DEPENDENT entries of Z: the state
+ * components [x_off, x_off + x_dim) of every integrator at knots 2 .. N; C is every other entry (controls, timesteps, times, the states
+ * of knot 1, globals).  MM, D, pre_i and the [N][n_cols][D] layout are those of dto_dynamics_solve_all; the dynamics rows of integrator
+ * i start at its row offset, interval k (0-based) taking x_dim rows from row0_i + k x_dim.  With sigma and mu (length n_cons, or NULL
+ * for zeros; its dynamics-row entries are never read),  phi(Z) = sigma f(Z) + sum over the non-dynamics rows r of mu_r g_r(Z).
+ *   dto_reduced_gradient   g = sigma grad f(Z) + J' w1, w1 = mu with its dynamics rows set to 0 (mu = NULL: the product is skipped);
+ *                          MM' Lam = g_S, g_S the state entries of g at all knots as [N][1][D];  t = J' w2, w2 zero except
+ *                          Lam_2 .. Lam_N in the dynamics rows.  grad [n_vars]: g - t on C except the states of knot 1, Lam_1 on the
+ *                          states of knot 1, 0 on S.  lam (may be NULL): Lam as [N][D], the costates.
+ *   dto_reduced_hessian_product   y = T' H(Z; sigma, mu~) T v, T the tangent map of the feasible manifold (identity on C,
+ *                          -J_S^-1 J_C on S) and mu~ = mu on the non-dynamics rows, -Lam_{k+1} on the dynamics rows of interval k:
+ *                            1. v^ = v with the state entries of ALL knots zeroed, rho = J v^          (the S entries of v are not read)
+ *                            2. B_1 = the knot-1 state entries of v, B_{k+1} = -rho[dynamics rows of interval k]
+ *                            3. MM Y = B                     4. z^ = v^ with the state entries of all knots set to Y
+ *                            5. q = H(Z; sigma, mu~) z^      6. MM' Gam = q_S
+ *                            7. t = J' w, w zero except Gam_2 .. Gam_N in the dynamics rows
+ *                            8. y = q - t on C except the states of knot 1, Gam_1 on the states of knot 1, 0 on S.
+ *                          v, y [n_vars]; they must not overlap.
+ * At a dynamically feasible Z the gradient is that of phi(feasible trajectory(.)) and the product its Hessian; at any other Z they are
+ * the reduced gradient and Hessian of an SQP method.  The product is symmetric either way.
+ * The arithmetic outside the engine's own routines is sigma * (.), one addition, one subtraction and negations, each rounded on its
+ * own: the results are, bit for bit, those of the same steps written with dto_eval_gradient, dto_eval_jacobian_product,
+ * dto_eval_jacobian_transpose_product, dto_dynamics_solve_all (one column) and dto_eval_hessian_product and repacked on the host.
+ * Repeated calls, both entry-point families and a rebuilt point against a kept one return the same bits.
+ * Cache rule.  The REDUCED POINT -- g, Lam, mu~ and the reduced gradient -- is kept per (Z, sigma, mu): Z and mu bit for bit (mu = NULL
+ * is a point of its own), with no dto_set_external, dto_set_option or failed call since; one device-side compare with a 4-byte
+ * readback decides.  The kept copies are written on the stream of the call that computed them and compared on the stream of the next
+ * call, as for the per-point caches of the routines inside: use ONE stream at a time per handle, or order the streams yourself
+ * (an event, a synchronize) before a call on another one.  A gradient at the kept point copies its results; a product at a new point first computes the gradient's
+ * quantities; a product at the kept point runs steps 1 .. 8 alone.  The routines inside keep their own per-point caches and their own
+ * 4-byte readbacks (three per product at the kept point: two solves, one H v): both solves reuse the trees from the first product on,
+ * and since mu~ is then bit-identical the Hessian is assembled for the first product only -- until a dto_eval_hessian_product at
+ * another (Z, sigma, mu) takes its slab, which costs the next reduced product one re-assembly and changes no bit.
+ * Costs at the kept point: one J w, one J' w, two whole-dynamics scans, one H v and six packer launches (O(n_vars + n_cons + N D)
+ * bytes each); no Jacobian chain, tree build or Hessian assembly -- EXCEPT on handles whose J w / J' w take the slab route (a
+ * time-dependent integrator without the option "tdb_matrix_free_products", more than MAX types of drives, ...): there each of the two
+ * products evaluates the Jacobian.  At a new point add: the objective gradient, one or two J' w, the Jacobian with the trees and the
+ * coupling store (dto_dynamics_solve_all), one adjoint scan, the Hessian assembly.
+ * Workspaces: one block of 7 n_vars + 4 n_cons + 3 N D doubles, allocated at the first call before anything is enqueued and freed
+ * with the handle, besides those of the routines inside.
+ * Refused with text, the handle stays usable and nothing is enqueued: everything dto_dynamics_solve_all refuses (a host-evaluated
+ * integrator, a sharded or structure-only handle, overlapping states, an integrator reading its own states, a dependency cycle); any
+ * host-evaluated constraint or objective; a handle without integrators; Z, grad, v or y = NULL; for the product a handle created
+ * with eval_hessian = 0 (the gradient still works there).  The _dev forms take device pointers (dmu and dlam may be NULL), enqueue on
+ * `stream` and defer device-side errors like every _dev call. */
+int dto_reduced_gradient(dto_handle* h, const double* Z, double sigma, const double* mu, double* grad, double* lam);
+int dto_reduced_gradient_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, double* dgrad, double* dlam, void* stream);
+int dto_reduced_hessian_product(dto_handle* h, const double* Z, double sigma, const double* mu, const double* v, double* y);
+int dto_reduced_hessian_product_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dv, double* dy, void* stream);
+
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
  * communicator (SURVEY.md §8b "Ownership").  No callback needs a collective: every rank's Jacobian / Hessian / gradient
@@ -601,7 +652,9 @@ int dto_profile_reset(dto_handle* h);
  * evaluation inside a rebuild counts under its own names),
  * "dynsolve_couple" and "dynsolve_deriv" (dto_dynamics_solve_all / dto_dynamics_solve_all_dev: the gather of the coupling blocks with
  * the contractions against them, and the DerivativeIntegrators' block solves -- third output: BYTES as executed; the call's other
- * block solves count under "dynsolve_tree" and "dynsolve_scan"; neither name feeds another, "dynsolve" and "all" included).
+ * block solves count under "dynsolve_tree" and "dynsolve_scan"; neither name feeds another, "dynsolve" and "all" included),
+ * "reduced_pack" (the packer launches of dto_reduced_gradient / dto_reduced_hessian_product and their _dev forms -- third output:
+ * BYTES as executed; it feeds no other name, "all" included, and the routines the operators are made of count under their own names).
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the
  * third output is the launches' algorithmic BYTES (what they must read and write), not FLOPs.
  * "hess_product_setup" returns the host milliseconds of the products' index build (once per handle), 0 launches, and the device

@@ -757,6 +757,71 @@ function dynamics_solve_all_dev!(ev::GPUEvaluator, dY::Ptr{Float64}, dZ::Ptr{Flo
                                                     dY::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 end
 
+# ---- reduced-space operators (include/dto_engine.h, "Reduced-space operators") ---------------------------------------------------------
+# The gradient and the Hessian-vector product of the problem with the states eliminated by the dynamics: the control-only view of a
+# GRAPE-style or truncated-Newton method.  `μ`: multipliers of all constraint rows (its dynamics rows are never read) or `nothing` for
+# zeros.  The reduced point -- costates, multipliers, gradient -- is kept per (Z, σ, μ): products at the point of the last call run no
+# Jacobian chain, tree build or Hessian assembly.
+# Returns the reduced gradient (n_variables: zero on the states of knots 2 .. N, the costates of knot 1 on the states of knot 1), with
+# `costates = true` also the costates as n_states x N, n_states asked of the handle (`dto_dynamics_layout`).
+function reduced_check_lengths(ev::GPUEvaluator, who::String, Z, μ, v = nothing)
+    length(Z) == ev.n_variables || error("$who: Z has $(length(Z)) entries, the problem has $(ev.n_variables) variables")
+    μ === nothing || length(μ) == ev.n_constraints || error("$who: μ has $(length(μ)) entries, the problem has $(ev.n_constraints) constraints")
+    v === nothing || length(v) == ev.n_variables || error("$who: v has $(length(v)) entries, the problem has $(ev.n_variables) variables")
+    return nothing
+end
+
+function reduced_gradient(ev::GPUEvaluator, Z::AbstractVector{Float64}; σ::Float64 = 1.0, μ::Union{Nothing,AbstractVector{Float64}} = nothing,
+                          costates::Bool = false)
+    reduced_check_lengths(ev, "reduced_gradient", Z, μ)
+    Zv = Vector{Float64}(Z)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    grad = fill(NaN, ev.n_variables)
+    lam = zeros(Float64, 0, 0)
+    if costates   # the costates' first dimension is the handle's own D (every array of dto_dynamics_layout may be NULL)
+        ns = Ref{Int32}(0)
+        check(ev, @ccall lib.dto_dynamics_layout(ev.handle::Ptr{Cvoid}, ns::Ptr{Int32}, C_NULL::Ptr{Int32}, C_NULL::Ptr{Int32},
+                                                 C_NULL::Ptr{Int32})::Cint)
+        lam = fill(NaN, Int(ns[]), ev.trajectory.N)
+    end
+    GC.@preserve grad lam Zv μv begin
+        μp = μ === nothing ? Ptr{Float64}(C_NULL) : pointer(μv)
+        lp = costates ? pointer(lam) : Ptr{Float64}(C_NULL)
+        check(ev, @ccall lib.dto_reduced_gradient(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μp::Ptr{Float64},
+                                                  grad::Ptr{Float64}, lp::Ptr{Float64})::Cint)
+    end
+    return costates ? (grad, lam) : grad
+end
+
+# y = T' H(Z; σ, μ~) T v: `v` and the result have n_variables entries; the entries of `v` at the states of knots 2 .. N are not read,
+# those of the result are zero.
+function reduced_hessian_product(ev::GPUEvaluator, Z::AbstractVector{Float64}, v::AbstractVector{Float64}; σ::Float64 = 1.0,
+                                 μ::Union{Nothing,AbstractVector{Float64}} = nothing)
+    reduced_check_lengths(ev, "reduced_hessian_product", Z, μ, v)
+    Zv, vv = Vector{Float64}(Z), Vector{Float64}(v)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    y = fill(NaN, ev.n_variables)
+    GC.@preserve y Zv vv μv begin
+        μp = μ === nothing ? Ptr{Float64}(C_NULL) : pointer(μv)
+        check(ev, @ccall lib.dto_reduced_hessian_product(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μp::Ptr{Float64},
+                                                         vv::Ptr{Float64}, y::Ptr{Float64})::Cint)
+    end
+    return y
+end
+
+# the same on device pointers, enqueued on `stream`; dμ and dlam may be C_NULL
+function reduced_gradient_dev!(ev::GPUEvaluator, dgrad::Ptr{Float64}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dlam::Ptr{Float64},
+                               stream::Ptr{Cvoid})
+    check(ev, @ccall lib.dto_reduced_gradient_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dgrad::Ptr{Float64},
+                                                  dlam::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
+function reduced_hessian_product_dev!(ev::GPUEvaluator, dy::Ptr{Float64}, dZ::Ptr{Float64}, dv::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64},
+                                      stream::Ptr{Cvoid})
+    check(ev, @ccall lib.dto_reduced_hessian_product_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dv::Ptr{Float64},
+                                                         dy::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
 # row bounds handed to the solver (src/solvers/solve.jl:30-65)
 function constraint_bounds(ev::GPUEvaluator)
     lo = Vector{Float64}(undef, ev.n_constraints)
