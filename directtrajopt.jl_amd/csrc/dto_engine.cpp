@@ -73,7 +73,7 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25 };
 // CAT_ROLLOUT .. CAT_ROLLOUT_DESCENT ("rollout" = its parts "rollout_gather" + "rollout_tree" + "rollout_descent"): the gather, the
 // tree's products and the descent (with the start and the copy into the caller's layout) of dto_rollout[_dev], flops as executed with
 // padding; the tree's products run launch_bgemm_plain and count HERE, not under "bgemm_plain"; they feed no other name, "all" included
@@ -89,6 +89,8 @@ inline bool is_elim_cat(int cat) { return cat == CAT_DYNSOLVE_COUPLE || cat == C
 // CAT_REDUCED_PACK ("reduced_pack"): the packers of dto_reduced_gradient / dto_reduced_hessian_product and their _dev forms
 // (dto_reduced.hip); the third output carries BYTES as executed.  It feeds no other name, "all" included; the routines the operators
 // are made of count under their own names.
+// CAT_REDUCED_INPUT ("reduced_input"): with the option "reduced_input_store", the gather of the input blocks and the two products with
+// them (dto_reduced.hip); BYTES as executed; it feeds no other name either.
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
 inline void count_sweep_form(dto_handle* h, int form) {
     if (h->profiling) ++h->sweep_forms[form];
@@ -2394,10 +2396,8 @@ int dto_dynamics_solve_dev(dto_handle* h, int32_t integrator, const double* dZ, 
 
 // The plan, from what dto_create kept on the host (a structure-only handle has it too).  A handle with a host-evaluated integrator
 // gets a plan that holds only the refusal.
-static const ElimPlan& elim_plan_of(dto_handle* h) {
-    if (h->elim) return *h->elim;
+static std::vector<ElimIntegrator> elim_integrators(const dto_handle* h, std::string& external) {
     std::vector<ElimIntegrator> its;
-    std::string external;
     for (size_t i = 0; i < h->integ_kind.size(); ++i) {
         const int kind = h->integ_kind[i], idx = h->integ_index[i];
         if (kind == DTO_INTEGRATOR_BILINEAR) {
@@ -2414,6 +2414,12 @@ static const ElimPlan& elim_plan_of(dto_handle* h) {
                        "not known to be a propagator";
         }
     }
+    return its;
+}
+static const ElimPlan& elim_plan_of(dto_handle* h) {
+    if (h->elim) return *h->elim;
+    std::string external;
+    const std::vector<ElimIntegrator> its = elim_integrators(h, external);
     std::unique_ptr<ElimPlan> p(new ElimPlan);
     if (external.empty()) *p = elim_plan(its, h->dt_idx, h->K);
     else p->refusal = external;
@@ -2482,16 +2488,52 @@ static void elim_upload_terms(dto_handle* h, const ElimPlan& p) {
 
 // The device routine both entry-point families run: everything on `st`, dZ / dB / dY device pointers, dB and dY [N][n_cols][D].  At a
 // new point: ONE do_jacobian into the private slab, then per integrator with a propagator the leaves and products of its own tree,
-// the gather of every coupling block, and a copy of Z.  At the point of the last call -- Z bit for bit, `gen` unchanged -- none of it.
-static void dynamics_solve_all(dto_handle* h, const ElimPlan& p, const double* dZ, int adjoint, const double* dB, int n_cols, double* dY,
-                               hipStream_t st) {
-    const int I = (int)p.pre.size(), D = p.n_states;
-    const int64_t K = h->K, N = h->N;
-    if (K < 1) {   // a single knot: the block is the identity
-        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
-        HIP_CHECK(hipMemcpyAsync(dY, dB, sizeof(double) * (size_t)n_cols * D, hipMemcpyDeviceToDevice, st));
-        return;
+// the gather of every coupling block (with the option "reduced_input_store" of every input block too), and a copy of Z.  At the point
+// of the last call -- Z bit for bit, `gen` unchanged -- none of it.
+// dynamics_solve_all = elim_point (the workspaces, the point check and the rebuild) + elim_solve (the block elimination at the kept
+// point).  The reduced-space operators' input-store route calls the halves itself: its first kernel reads what the rebuild gathers.
+struct ElimWork {
+    double *Bp, *Yp, *S, *off, *store;
+};
+
+// the input-block store's plan and device tables (option "reduced_input_store"), once per handle
+static const InputPlan& input_plan_of(dto_handle* h, const ElimPlan& p) {
+    if (h->input) return *h->input;
+    std::string external;
+    const std::vector<ElimIntegrator> its = elim_integrators(h, external);
+    std::unique_ptr<InputPlan> ip(new InputPlan(input_plan(its, h->dt_idx, h->z, h->K)));
+    const int I = (int)its.size();
+    std::vector<KInputInt> integ;
+    std::vector<int32_t> fin, pos_int((size_t)p.n_states, 0), term0(1, 0), read;
+    std::vector<KInputTerm> terms;
+    for (int a = 0; a < I; ++a) {
+        integ.push_back(KInputInt{ip->store_off[a], p.pre[a], its[a].x_dim, ip->width[a], (int32_t)fin.size()});
+        fin.insert(fin.end(), ip->fin[a].begin(), ip->fin[a].end());
+        for (int r = 0; r < its[a].x_dim; ++r) pos_int[(size_t)(p.pre[a] + r)] = a;
     }
+    for (int c = 0; c < h->z; ++c) {
+        for (const InputTerm& t : ip->terms[c]) terms.push_back(KInputTerm{ip->store_off[t.a], ip->width[t.a], its[t.a].x_dim, t.j, p.pre[t.a]});
+        term0.push_back((int32_t)terms.size());
+        if (!ip->terms[c].empty()) read.push_back(c);
+    }
+    KInput in{};
+    in.integ = own(h, dupload(integ));
+    in.fin = own(h, dupload(fin));
+    in.pos_int = own(h, dupload(pos_int));
+    in.term0 = own(h, dupload(term0));
+    in.terms = own(h, dupload(terms));
+    in.read = own(h, dupload(read));
+    in.n_read = (int32_t)read.size();
+    in.n_int = I;
+    in.K = h->K;
+    h->in = in;
+    h->input = std::move(ip);
+    return *h->input;
+}
+
+static ElimWork elim_point(dto_handle* h, const ElimPlan& p, const double* dZ, int n_cols, hipStream_t st) {
+    const int I = (int)p.pre.size();
+    const int64_t K = h->K, N = h->N;
     // every workspace first: a failed allocation is refused before anything is enqueued
     int n_max = 1, npad_max = 0;
     for (int i = 0; i < I; ++i) {
@@ -2506,6 +2548,8 @@ static void dynamics_solve_all(dto_handle* h, const ElimPlan& p, const double* d
         off = grow_workspace(h, h->d_dyn_off, h->dyn_off_cap, dynsolve_offset_bytes(npad_max, K, n_cols) / sizeof(double));
     }
     double* store = grow_workspace(h, h->d_elim_store, h->elim_store_cap, (size_t)p.store_off[I]);
+    const InputPlan* ip = h->reduced_input_store ? &input_plan_of(h, p) : nullptr;
+    if (ip) grow_workspace(h, h->d_in_store, h->in_store_cap, (size_t)ip->store_off[I]);
     h->elim_tree.resize(I, nullptr);
     h->elim_tree_cap.resize(I, 0);
     for (int i = 0; i < I; ++i)
@@ -2531,10 +2575,23 @@ static void dynamics_solve_all(dto_handle* h, const ElimPlan& p, const double* d
                 ProfScope ps(h, st, CAT_DYNSOLVE_COUPLE, 16.0 * (double)K * 2.0 * n_a * n_b);
                 launch_elim_gather(st, h->P, KElimPair{n_a, p.pre[a], elim_x_off(h, d.b), n_b, d.col, p.width[a]}, K, slab, store + p.store_off[a]);
             }
+        if (ip)   // the input blocks sit beside the coupling blocks, in the same knot columns of the same slab
+            for (int a = 0; a < I; ++a)
+                if (ip->width[a] > 0) {
+                    ProfScope ps(h, st, CAT_REDUCED_INPUT, 16.0 * (double)K * 2.0 * ip->width[a] * h->integ_dim[a]);
+                    launch_red_input_gather(st, h->P, h->in, a, slab, h->d_in_store);
+                }
         HIP_CHECK(hipMemcpyAsync(h->d_elim_Z, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
         h->elim_gen = h->gen;
         h->elim_valid = true;
     }
+    return ElimWork{Bp, Yp, S, off, store};
+}
+
+static void elim_solve(dto_handle* h, const ElimPlan& p, const ElimWork& W, int adjoint, const double* dB, int n_cols, double* dY, hipStream_t st) {
+    const int I = (int)p.pre.size(), D = p.n_states;
+    const int64_t K = h->K, N = h->N;
+    double *Bp = W.Bp, *Yp = W.Yp, *S = W.S, *off = W.off, *store = W.store;
     for (int step = 0; step < I; ++step) {
         const int a = p.order[adjoint ? I - 1 - step : step], n_a = h->integ_dim[a];
         const std::vector<int>& t0 = adjoint ? h->elim_ad_term0 : h->elim_fw_term0;
@@ -2558,6 +2615,17 @@ static void dynamics_solve_all(dto_handle* h, const ElimPlan& p, const double* d
         ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
         launch_elim_collect(st, N, n_a, n_cols, D, p.pre[a], Yp, dY);
     }
+}
+
+static void dynamics_solve_all(dto_handle* h, const ElimPlan& p, const double* dZ, int adjoint, const double* dB, int n_cols, double* dY,
+                               hipStream_t st) {
+    if (h->K < 1) {   // a single knot: the block is the identity
+        ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
+        HIP_CHECK(hipMemcpyAsync(dY, dB, sizeof(double) * (size_t)n_cols * p.n_states, hipMemcpyDeviceToDevice, st));
+        return;
+    }
+    const ElimWork W = elim_point(h, p, dZ, n_cols, st);
+    elim_solve(h, p, W, adjoint, dB, n_cols, dY, st);
 }
 
 int dto_dynamics_layout(const dto_handle* h, int32_t* n_states, int32_t* n_levels, int32_t* offset, int32_t* level) {
@@ -2601,6 +2669,8 @@ int dto_dynamics_solve_all_dev(dto_handle* h, const double* dZ, int32_t directio
 // ---- reduced-space operators: the gradient and the Hessian-vector product of the problem with the states eliminated by the dynamics
 // (include/dto_engine.h, "Reduced-space operators"; dto_reduced.hip, dto_reduced_plan.h).  Compositions of do_gradient, jac_product,
 // dynamics_solve_all (one column) and hess_product, all on `st` and all unchanged; the packers keep every vector on the device.
+// With the option "reduced_input_store" the two jac_product calls on the dynamics rows give way to products with the input blocks
+// kept beside the coupling blocks (dto_input_plan.h).
 
 // What a reduced-space call names: refused with text before anything is enqueued.
 static const ElimPlan& reduced_args(dto_handle* h, const std::string& who, bool hessian) {
@@ -2647,6 +2717,15 @@ static void reduced_workspaces(dto_handle* h, const ElimPlan& p) {
     h->d_red = own(h, blk);
 }
 
+// bytes of the two products with the input blocks (h->input exists: the solves' point was ensured with the option on): the store once,
+// the free inputs of v and B, or q, Gam and y
+static double input_forward_bytes(const dto_handle* h) {
+    return 8.0 * ((double)h->input->store_off.back() + (double)h->N * (h->in.n_read + 2.0 * h->red.D));
+}
+static double input_transposed_bytes(const dto_handle* h) {
+    return 8.0 * ((double)h->input->store_off.back() + 2.0 * (double)h->n_vars + (double)h->N * h->red.D);
+}
+
 // The reduced point: g, Lam, mu~ and the reduced gradient at (Z, sigma, mu), computed unless the ones kept belong to this point --
 // Z and mu bit for bit (one compare with a 4-byte readback), sigma, the "mu = NULL" mark and `gen`.
 static void reduced_point(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, hipStream_t st) {
@@ -2668,8 +2747,13 @@ static void reduced_point(dto_handle* h, const ElimPlan& p, const double* dZ, do
     { ProfScope ps(h, st, CAT_REDUCED_PACK, (t1 ? 3.0 : 2.0) * nv + nd); launch_red_gradient(st, R, sigma, h->red_a, t1, h->red_g, h->red_s1); }
     dynamics_solve_all(h, p, dZ, 1, h->red_s1, 1, h->red_lam, st);
     { ProfScope ps(h, st, CAT_REDUCED_PACK, nd + (dmu ? 3.0 : 2.0) * nc); launch_red_multipliers(st, R, h->red_lam, dmu, 0, h->red_w, h->red_mut); }
-    jac_product(h, dZ, h->red_w, h->red_b, 1, st);
-    { ProfScope ps(h, st, CAT_REDUCED_PACK, 3.0 * nv); launch_red_finish(st, R, h->red_g, h->red_b, h->red_lam, h->red_r); }
+    if (h->reduced_input_store && h->K >= 1) {   // t = J' w2 from the input blocks the adjoint solve's point holds
+        ProfScope ps(h, st, CAT_REDUCED_INPUT, input_transposed_bytes(h));
+        launch_red_input_transposed(st, R, h->in, h->d_in_store, h->red_g, h->red_lam, h->red_r);
+    } else {
+        jac_product(h, dZ, h->red_w, h->red_b, 1, st);
+        { ProfScope ps(h, st, CAT_REDUCED_PACK, 3.0 * nv); launch_red_finish(st, R, h->red_g, h->red_b, h->red_lam, h->red_r); }
+    }
     HIP_CHECK(hipMemcpyAsync(h->red_Z, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
     if (dmu && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->red_mu, dmu, sizeof(double) * (size_t)h->n_cons, hipMemcpyDeviceToDevice, st));
     h->red_mu_null = dmu == nullptr;
@@ -2692,6 +2776,21 @@ static void reduced_hessian_product(dto_handle* h, const ElimPlan& p, const doub
     reduced_point(h, p, dZ, sigma, dmu, st);
     const KReduced& R = h->red;
     const double nv = 8.0 * (double)h->n_vars, nc = 8.0 * (double)h->n_cons, nd = 8.0 * (double)h->N * R.D;
+    if (h->reduced_input_store && h->K >= 1) {
+        // The reduced point and the solves' point are kept apart: a dto_dynamics_solve_all at another Z in between leaves the first
+        // valid and the input blocks stale.  So the solves' point is made this Z BEFORE the first kernel reads the store (one compare;
+        // after such a call one rebuild with one Jacobian evaluation), and both solves then run at it without a compare of their own.
+        const ElimWork W = elim_point(h, p, dZ, 1, st);
+        { ProfScope ps(h, st, CAT_REDUCED_INPUT, input_forward_bytes(h)); launch_red_input_forward(st, R, h->in, h->d_in_store, dv, h->red_s1); }
+        elim_solve(h, p, W, 0, h->red_s1, 1, h->red_s2, st);                    // MM Y = B
+        { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_zhat(st, R, dv, h->red_s2, h->red_a); }
+        hess_product(h, dZ, sigma, h->red_mut, h->red_a, h->red_b, st);         // q = H(mu~) z^
+        { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nd); launch_red_gather(st, R, h->red_b, h->red_s1); }
+        elim_solve(h, p, W, 1, h->red_s1, 1, h->red_s2, st);                    // MM' Gam = q_S
+        ProfScope ps(h, st, CAT_REDUCED_INPUT, input_transposed_bytes(h));
+        launch_red_input_transposed(st, R, h->in, h->d_in_store, h->red_b, h->red_s2, dy);
+        return;
+    }
     { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_vhat(st, R, dv, h->red_a); }
     jac_product(h, dZ, h->red_a, h->red_w, 0, st);                          // rho = J v^
     { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nd); launch_red_rhs(st, R, dv, h->red_w, h->red_s1); }
@@ -2927,6 +3026,12 @@ int dto_set_option(dto_handle* h, const char* name, int64_t value) {
         h->tdb_matrix_free_products = (int)value;
         return 0;
     }
+    if (std::string(name) == "reduced_input_store") {
+        if (value != 0 && value != 1)
+            return fail(h, "dto_set_option: reduced_input_store takes 0 (J v^ and J' w of the reduced-space operators through dto_eval_jacobian_product / _transpose_product) or 1 (from the kept input blocks)");
+        h->reduced_input_store = (int)value;
+        return 0;
+    }
     if (std::string(name) == "tdb_share_members") {
         int cap = 1;
         for (const TdbHost& t : h->tdb) cap = std::max(cap, t.share_active ? t.share_cap : 1);
@@ -3007,6 +3112,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "dynsolve_couple")) cat = CAT_DYNSOLVE_COUPLE;
         else if (!strcmp(name, "dynsolve_deriv")) cat = CAT_DYNSOLVE_DERIV;
         else if (!strcmp(name, "reduced_pack")) cat = CAT_REDUCED_PACK;
+        else if (!strcmp(name, "reduced_input")) cat = CAT_REDUCED_INPUT;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -3036,7 +3142,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (is_rollout_cat(r.cat) ? !(any_rollout || r.cat == cat) : any_rollout) continue;   // ("all": the rollout is no callback)
             if (is_dynsolve_cat(r.cat) ? !(any_dynsolve || r.cat == cat) : any_dynsolve) continue;   // (nor are the solves)
             if (is_elim_cat(r.cat) && r.cat != cat) continue;
-            if (r.cat == CAT_REDUCED_PACK && r.cat != cat) continue;
+            if ((r.cat == CAT_REDUCED_PACK || r.cat == CAT_REDUCED_INPUT) && r.cat != cat) continue;
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));

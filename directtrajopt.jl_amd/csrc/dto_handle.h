@@ -19,6 +19,7 @@
 #include "dto_comm.h"
 #include "dto_elim_plan.h"
 #include "dto_hostxfer.h"
+#include "dto_input_plan.h"
 #include "dto_kernels.h"
 #include "dto_sweep_cache.h"
 
@@ -319,7 +320,14 @@ struct dto_handle {
     bool red_valid = false, red_mu_null = false;
     double red_sigma = 0.0;
     uint64_t red_gen = 0;
-    int64_t* d_conbase = nullptr;        // [n_vars+1] first constraint-pattern entry of each column
+    // the operators' input-block store (option "reduced_input_store"; plan: dto_input_plan.h): the tables once per handle, the store
+    // F grow-only and kept with the whole-dynamics solves' point (elim_valid, elim_gen: gathered in the same rebuild, from the same slab)
+    int reduced_input_store = 0;   // option of that name: 1 takes J v^ and J' w of the reduced operators from the kept input blocks
+    std::unique_ptr<dto::InputPlan> input;
+    dto::KInput in{};              // device tables
+    double* d_in_store = nullptr;
+    size_t in_store_cap = 0;
+    int64_t* d_conbase = nullptr;       // [n_vars+1] first constraint-pattern entry of each column
     int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
     int64_t* d_crow_col = nullptr;
     int64_t* d_crow_pos = nullptr;

@@ -495,6 +495,33 @@ void launch_red_zhat(hipStream_t st, const KReduced& R, const double* v, const d
 void launch_red_gather(hipStream_t st, const KReduced& R, const double* q, double* qS);                                // states of q
 void launch_red_finish(hipStream_t st, const KReduced& R, const double* q, const double* t, const double* lam, double* y);
 
+// Input-block store of the reduced-space operators (option "reduced_input_store"; dto_reduced.hip; plan and layout: dto_input_plan.h).
+struct KInputInt {   // one integrator: its store F_a [K][2][wf][n] and its free inputs fin[fin0 .. fin0 + wf)
+    int64_t store;
+    int32_t pre, n, wf, fin0;
+};
+struct KInputTerm {   // one reader of a knot component: column j of F_a, the rows [pre, pre + n) of the D axis
+    int64_t store;
+    int32_t wf, n, j, pre;
+};
+struct KInput {   // every table is a device pointer
+    const KInputInt* integ;    // [n_int]
+    const int32_t* fin;        // [sum of wf]
+    const int32_t* pos_int;    // [D] the integrator that owns a D position
+    const int32_t* term0;      // [z + 1] a component's terms are terms[term0[c] .. term0[c + 1])
+    const KInputTerm* terms;
+    const int32_t* read;       // [n_read] the components with terms, ascending
+    int32_t n_read, n_int;
+    int64_t K;
+};
+// F_a of integrator a from the Jacobian value slab
+void launch_red_input_gather(hipStream_t st, const KProb& P, const KInput& In, int a, const double* vals, double* store);
+// B [N][1][D]: knot 0 the knot-1 state entries of v, knot k >= 1 minus the input blocks of interval k - 1 times the free inputs of v
+void launch_red_input_forward(hipStream_t st, const KReduced& R, const KInput& In, const double* store, const double* v, double* B);
+// y [n_vars]: q - F' Gam on the read components, q on the unread ones and the globals, Gam_0 on the states of knot 0, 0 on the dependent entries
+void launch_red_input_transposed(hipStream_t st, const KReduced& R, const KInput& In, const double* store, const double* q, const double* gam,
+                                 double* y);
+
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);
 

@@ -15,8 +15,26 @@
 // One thread per output entry, one writer per entry, plain 8-byte loads and stores, no atomics, no LDS.  The arithmetic is a negation,
 // __dmul_rn, __dadd_rn and __dsub_rn -- each rounded on its own, never contracted -- so the results are those of the same expressions
 // in NumPy, bit for bit.  Entries a kernel does not need are not read: a NaN in a dependent entry of v reaches nothing.
+//
+// Option "reduced_input_store" (plan and the store's layout: dto_input_plan.h) replaces J v^ / k_red_rhs and J' w / k_red_finish by
+// products with the kept input blocks F_a [K][2][Wf_a][x_dim_a] (a's rows of interval k in the columns of its free inputs fin_a at
+// knot k, half 0, and knot k + 1, half 1):
+//   k_red_input_gather      F_a out of the Jacobian value slab (jac_pos), as k_elim_gather copies the coupling blocks
+//   k_red_input_forward     B [N][1][D], one thread per entry.  B_0[d] = the knot-0 state entry of v.  For k >= 1, a the owner of d and
+//                           r = d - pre_a:  acc = 0;  for half = 0, 1: for j = 0 .. Wf_a - 1:
+//                               acc = acc + F_a[k-1][half][j][r] * v[(k - 1 + half) z + fin_a[j]];      B_k[d] = -acc
+//                           (every product and every sum rounded on its own).  No state entry of v past knot 0 is read.
+//   k_red_input_transposed  y [n_vars].  Dependent entries 0; states of knot 0 Gam_0[d]; globals and unread components q - 0.0; a READ
+//                           component c of knot kn:  y = q - t, one wavefront per output.  Lane l starts from p_l = 0 and visits c's
+//                           terms (a, j) in plan order, per term interval kn - 1 through half 1 (where kn >= 1) and then interval kn
+//                           through half 0 (where kn < K), per (term, interval iv) the rows r = l, l + 64, .. < x_dim_a ascending:
+//                               p_l = p_l + F_a[iv][half][j][r] * Gam_{iv+1}[pre_a + r]
+//                           Then the 64 partials are combined by a fixed halving tree, for off = 32, 16, 8, 4, 2, 1:
+//                               p_l = p_l + p_{l+off}   (l < off),          t = p_0
+//                           by wavefront shuffles: no LDS, no atomics.  The order is part of the contract.
 #include <algorithm>
 
+#include "dto_elim_plan.h"
 #include "dto_kernels.h"
 #include "dto_reduced_plan.h"
 
@@ -98,9 +116,114 @@ __global__ void __launch_bounds__(256) k_red_finish(KReduced R, const double* __
     }
 }
 
+// The products and sums of the two input-block kernels, each rounded on its own.  (__dmul_rn and __dadd_rn are plain operators in the
+// compiler's header and carry its leave to contract: a product feeding a sum through them becomes one fused multiply-add, which NumPy
+// cannot restate.  Here contraction is switched off where the operators are written.)
+__device__ __forceinline__ double mul_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ double add_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ double sub_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
+// grid: (K intervals, 2 halves); one launch per integrator with free inputs
+__global__ void __launch_bounds__(256) k_red_input_gather(KProb P, KInput In, int a, const double* __restrict__ vals, double* __restrict__ store) {
+    const KInputInt T = In.integ[a];
+    const int64_t k = blockIdx.x;
+    const int half = blockIdx.y;
+    const int64_t kn = k + half;
+    const int part = half == 0 ? 1 : 0;   // the column of knot k holds interval k as its part 1, that of knot k + 1 as its part 0
+    const int total = T.wf * T.n;
+    for (int e = threadIdx.x; e < total; e += blockDim.x) {
+        const int j = e / T.n, r = e % T.n;
+        store[T.store + elim_block_pos(T.wf, T.n, k, half, j) + r] = vals[jac_pos(P, P.colptr, kn, In.fin[T.fin0 + j], T.pre, T.n, part, r)];
+    }
+}
+
+__global__ void __launch_bounds__(256) k_red_input_forward(KReduced R, KInput In, const double* __restrict__ store, const double* __restrict__ v,
+                                                            double* __restrict__ B) {
+    RED_LOOP(e, R.N * R.D) {
+        const int64_t k = e / R.D;
+        const int d = (int)(e % R.D);
+        if (k == 0) {
+            B[e] = v[reduced_pack_index(R, 0, d)];
+            continue;
+        }
+        const KInputInt T = In.integ[In.pos_int[d]];
+        const int r = d - T.pre;
+        const int32_t* fin = In.fin + T.fin0;
+        double acc = 0.0;
+        for (int half = 0; half < 2; ++half) {
+            const double* f = store + T.store + elim_block_pos(T.wf, T.n, k - 1, half, 0) + r;
+            const double* vk = v + (k - 1 + half) * R.z;
+            for (int j = 0; j < T.wf; ++j) acc = add_rn(acc, mul_rn(f[(size_t)j * T.n], vk[fin[j]]));
+        }
+        B[e] = -acc;
+    }
+}
+
+// blocks [0, wave_blocks): four wavefronts each, one per (knot, read component); the blocks behind them: one thread per other entry
+__global__ void __launch_bounds__(256) k_red_input_transposed(KReduced R, KInput In, unsigned wave_blocks, const double* __restrict__ store,
+                                                               const double* __restrict__ q, const double* __restrict__ gam,
+                                                               double* __restrict__ y) {
+    if (blockIdx.x < wave_blocks) {
+        const int64_t o = (int64_t)blockIdx.x * 4 + threadIdx.x / 64;   // uniform in a wavefront
+        if (o >= R.N * In.n_read) return;
+        const int lane = threadIdx.x % 64;
+        const int64_t kn = o / In.n_read;
+        const int c = In.read[o % In.n_read];
+        double p = 0.0;
+        for (int t = In.term0[c]; t < In.term0[c + 1]; ++t) {
+            const KInputTerm T = In.terms[t];
+            for (int half = 1; half >= 0; --half) {
+                const int64_t iv = half == 1 ? kn - 1 : kn;   // interval kn - 1 reaches knot kn through its half 1, interval kn through half 0
+                if (iv < 0 || iv >= In.K) continue;
+                const double* f = store + T.store + elim_block_pos(T.wf, T.n, iv, half, T.j);
+                const double* g = gam + (iv + 1) * R.D + T.pre;
+                for (int r = lane; r < T.n; r += 64) p = add_rn(p, mul_rn(f[r], g[r]));
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) p = add_rn(p, __shfl_down(p, off, 64));
+        if (lane == 0) y[kn * R.z + c] = sub_rn(q[kn * R.z + c], p);
+        return;
+    }
+    const int64_t first = (int64_t)(blockIdx.x - wave_blocks) * blockDim.x + threadIdx.x, stride = (int64_t)(gridDim.x - wave_blocks) * blockDim.x;
+    for (int64_t e = first; e < R.n_vars; e += stride) {
+        const int d = reduced_state_pos(R, e);
+        if (d >= 0) {
+            y[e] = e < R.z ? gam[d] : 0.0;
+            continue;
+        }
+        if (e < R.N * R.z) {
+            const int c = (int)(e % R.z);
+            if (In.term0[c + 1] > In.term0[c]) continue;   // a read component: its wavefront writes it
+        }
+        y[e] = sub_rn(q[e], 0.0);
+    }
+}
+
 unsigned red_grid(int64_t total) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 4096)); }
 
 }  // namespace
+
+void launch_red_input_gather(hipStream_t st, const KProb& P, const KInput& In, int a, const double* vals, double* store) {
+    hipLaunchKernelGGL(k_red_input_gather, dim3((unsigned)In.K, 2), dim3(256), 0, st, P, In, a, vals, store);
+}
+void launch_red_input_forward(hipStream_t st, const KReduced& R, const KInput& In, const double* store, const double* v, double* B) {
+    hipLaunchKernelGGL(k_red_input_forward, dim3(red_grid(R.N * R.D)), dim3(256), 0, st, R, In, store, v, B);
+}
+void launch_red_input_transposed(hipStream_t st, const KReduced& R, const KInput& In, const double* store, const double* q, const double* gam,
+                                 double* y) {
+    const unsigned wave_blocks = (unsigned)((R.N * In.n_read + 3) / 4);
+    hipLaunchKernelGGL(k_red_input_transposed, dim3(wave_blocks + red_grid(R.n_vars)), dim3(256), 0, st, R, In, wave_blocks, store, q, gam, y);
+}
 
 void launch_red_gradient(hipStream_t st, const KReduced& R, double sigma, const double* gf, const double* t, double* g, double* gS) {
     hipLaunchKernelGGL(k_red_gradient, dim3(red_grid(R.n_vars)), dim3(256), 0, st, R, sigma, gf, t, g, gS);

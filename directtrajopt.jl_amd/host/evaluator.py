@@ -741,7 +741,10 @@ class Evaluator:
         path of ``block_generators`` alike, without forming a Jacobian -- the scheme applied to two vectors, or to 1 + p forward
         vectors and one adjoint vector; column groups of the b x b map on the structured path), ``tdb_share_members`` (members per launch of a
         shared group of time-dependent integrators, 1 = one launch per member), ``tdb_resident`` (cap on the persistent grid of the
-        k_tdb_mfma / k_tdb_kron launches and of their product forms, 0 = the default grid; for tests and measurements, the results do not depend on it);
+        k_tdb_mfma / k_tdb_kron launches and of their product forms, 0 = the default grid; for tests and measurements, the results do not depend on it),
+        ``reduced_input_store`` (0 | 1, default 0: 1 makes ``reduced_lagrangian_gradient`` / ``reduced_hessian_product`` and their
+        ``_dev`` forms take J v^ and J' w from the input blocks kept with ``dynamics_solve_all``'s point -- two small launches instead
+        of a J w and a J' w per product; another summation order, so values agree with the default route to rounding, not in bits);
         include/dto_engine.h lists every option."""
         self._check(self._lib.dto_set_option(self._h, name.encode(), int(value)))
 

@@ -485,6 +485,31 @@ int dto_dynamics_solve_all_dev(dto_handle* h, const double* dZ, int32_t directio
  * coupling store (dto_dynamics_solve_all), one adjoint scan, the Hessian assembly.
  * Workspaces: one block of 7 n_vars + 4 n_cons + 3 N D doubles, allocated at the first call before anything is enqueued and freed
  * with the handle, besides those of the routines inside.
+ * Option "reduced_input_store" (default 0; dto_set_option, values other than 0 and 1 are refused): 1 takes rho = J v^ (steps 1 - 2) and
+ * t = J' w (steps 7 - 8, and t = J' w2 of the gradient) from a kept INPUT-BLOCK STORE instead of dto_eval_jacobian_product /
+ * _transpose_product.  In step 1 only the non-state entries of v^ are non-zero and only the dynamics rows of rho are read; in step 7 w
+ * is zero outside the dynamics rows and only the non-state entries of t are read: both are products with the block
+ * J[dynamics rows, non-state knot components].  A FREE INPUT of integrator a is a component it reads (its controls or the derivative's
+ * components, the timestep, for time-dependent integrators the time) that is no integrator's state; fin_a lists them ascending, Wf_a
+ * is their number.  The store F_a [N - 1][2][Wf_a][x_dim_a] holds a's rows of interval k in the columns fin_a of knot k (half 0) and
+ * knot k + 1 (half 1; non-zero for spline order 1 only), rows contiguous, the integrators' stores one behind the other in list order:
+ * the sum over a of (N - 1) 2 Wf_a x_dim_a doubles, grow-only, allocated before anything is enqueued.  It is gathered from the private
+ * Jacobian slab in the rebuild of dto_dynamics_solve_all's point, beside the coupling blocks, and kept with that point.
+ * Summation orders (every product and sum rounded on its own, never contracted).  B_1 = the knot-1 state entries of v; for k >= 1, a
+ * the owner of D position d and r = d - pre_a:  acc = 0, then half 0 before half 1 and j ascending inside each,
+ * acc += F_a[k-1][half][j][r] v[(k - 1 + half) z + fin_a[j]], and B_{k+1}[d] = -acc.  y: 0 on S, Gam_1 on the states of knot 1, q - 0.0
+ * on globals and on knot components no integrator reads, q - t on a free-input component c of knot kn (0-based), t summed by one
+ * wavefront: lane l adds, over c's readers (a, j) in list order, per reader interval kn - 1 through half 1 (kn >= 1) and then interval
+ * kn through half 0 (kn < N - 1), the rows r = l, l + 64, .. ascending, F_a[iv][half][j][r] Gam_{iv+2}[pre_a + r]; the 64 partial sums
+ * are then combined by a fixed halving tree, p_l += p_{l+32}, p_l += p_{l+16}, .. , p_l += p_{l+1}, and t = p_0.  No atomics.
+ * Results of the two routes agree to rounding (other summation orders); with 1 the bits are those of the sums above over the entries
+ * of dto_eval_jacobian's values.  Repeated calls, both entry-point families and a rebuilt point return the same bits on either route.
+ * Costs with 1, at the kept point: two products with the store (its bytes twice), two whole-dynamics scans, one H v and two packer
+ * launches -- no J w, no J' w, on slab-route handles no Jacobian evaluation; the solves' point is checked once per product (two 4-byte
+ * readbacks instead of three).  At a new point the gradient loses its second J' w and gains the gather.  The reduced point and the
+ * solves' point are kept apart, so a dto_dynamics_solve_all at another Z between two products leaves the store stale: a product
+ * first makes the solves' point its own Z -- after such a call one rebuild with ONE Jacobian evaluation -- and reads the store after that.
+ * J' w1 of the constraint rows (mu given) stays dto_eval_jacobian_transpose_product.  With 0 nothing changes.
  * Refused with text, the handle stays usable and nothing is enqueued: everything dto_dynamics_solve_all refuses (a host-evaluated
  * integrator, a sharded or structure-only handle, overlapping states, an integrator reading its own states, a dependency cycle); any
  * host-evaluated constraint or objective; a handle without integrators; Z, grad, v or y = NULL; for the product a handle created
@@ -609,6 +634,9 @@ int dto_bind_output_dev(dto_handle* h, int32_t vector, double* dptr);
  *   about a constraint call, not a Jacobian call.  Such a handle may mix structured and dense time-dependent integrators and also
  *   hold bilinear and derivative integrators and built-in knot constraints: it goes matrix-free as a whole.  External integrators
  *   and constraints keep the slab route whatever the option says.  0 leaves every call as it was; values other than 0 and 1 are refused.  Results of the two routes agree to rounding (another summation order).
+ *   "reduced_input_store" (default 0): 1 makes dto_reduced_gradient / dto_reduced_hessian_product (and their _dev forms) take their
+ *   J v^ and J' w from input blocks kept with dto_dynamics_solve_all's point ("Reduced-space operators" above states the store, the
+ *   summation orders and the costs).  0 leaves every call as it was; values other than 0 and 1 are refused.
  *   "debug_bad_launch": TUNING builds only (libdto_engine_t.so) -- 1 gives the next callbacks' kernels an invalid launch
  *   configuration, which must come back as a non-zero return code with text (test of the error convention); the product
  *   library refuses the name. */
@@ -654,7 +682,9 @@ int dto_profile_reset(dto_handle* h);
  * the contractions against them, and the DerivativeIntegrators' block solves -- third output: BYTES as executed; the call's other
  * block solves count under "dynsolve_tree" and "dynsolve_scan"; neither name feeds another, "dynsolve" and "all" included),
  * "reduced_pack" (the packer launches of dto_reduced_gradient / dto_reduced_hessian_product and their _dev forms -- third output:
- * BYTES as executed; it feeds no other name, "all" included, and the routines the operators are made of count under their own names).
+ * BYTES as executed; it feeds no other name, "all" included, and the routines the operators are made of count under their own names),
+ * "reduced_input" (option "reduced_input_store": the gather of the input blocks at a rebuilt point, one launch per integrator with free
+ * inputs, and the two products with them, one launch each -- third output: BYTES as executed; it feeds no other name, "all" included).
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the
  * third output is the launches' algorithmic BYTES (what they must read and write), not FLOPs.
  * "hess_product_setup" returns the host milliseconds of the products' index build (once per handle), 0 launches, and the device

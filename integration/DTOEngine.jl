@@ -986,7 +986,8 @@ function balanced_knot_ranges(cost::AbstractVector{Float64}, world::Integer)
 end
 
 # dto_set_option (include/dto_engine.h lists the names), e.g. set_option!(ev, "tdb_matrix_free_products", 1): J w / J' w of device
-# TimeDependentBilinearIntegrators (dense or structured path) without a value slab
+# TimeDependentBilinearIntegrators (dense or structured path) without a value slab; set_option!(ev, "reduced_input_store", 1):
+# reduced_gradient / reduced_hessian_product take J v^ and J' w from the input blocks kept with the whole-dynamics solves' point
 function set_option!(ev::GPUEvaluator, name::AbstractString, value::Integer)
     v64 = Int64(value)
     check(ev, @ccall lib.dto_set_option(ev.handle::Ptr{Cvoid}, name::Cstring, v64::Int64)::Cint)

@@ -13,9 +13,14 @@ the constraint rows; every figure after a warm-up of at least 30 ms of GPU work,
         eval_jacobian_product_dev, eval_jacobian_transpose_product_dev, dynamics_solve_all_dev and eval_hessian_product_dev, with the
         caller's own repacking in torch indexing on the device -- new and cached (cached: mu~ kept by the caller, steps 1 .. 8);
     the profile split of one cached product: "reduced_pack", "hess_product", "dynsolve_scan", "dynsolve_couple", "dynsolve_deriv";
-    with ``--host-shape`` the host-vector Python Evaluator.reduced_gradient(Z) at that shape: what a user had before.
+    with ``--host-shape`` the host-vector Python Evaluator.reduced_gradient(Z) at that shape: what a user had before;
+    the two ROUTES of the operators -- the default one and option "reduced_input_store" = 1 (J v^ and J' w from the kept input
+        blocks) -- on two handles of the same problem in the same process, their single calls ALTERNATING (default, store, default,
+        ...), the median of ``--reps`` each: gradient and product at a new point, product at the kept point; per route the profile
+        split of one kept product with its device total, "reduced_input" with its bytes as executed, the store's size, and the
+        largest difference between the routes' results.
 
-One JSON line per shape.
+One JSON line per shape, and a second one ({"routes": ...}) for the routes; ``--routes only`` prints the second alone.
 
     python tools/reduced_time.py                       # 256 x 2000 and 64 x 1000, host-vector gradient at 64 x 1000
     python tools/reduced_time.py --shapes 128x1000 --reps 9
@@ -36,6 +41,7 @@ import torch  # noqa: E402
 import dto_amd  # noqa: E402
 
 PARTS = ("reduced_pack", "hess_product", "dynsolve_scan", "dynsolve_couple", "dynsolve_deriv", "dynsolve_tree")
+OWN = ("reduced_input", "reduced_pack", "dynsolve_scan", "dynsolve_couple", "dynsolve_deriv", "dynsolve_tree")   # names "all" leaves out
 SIGMA = 0.7
 
 
@@ -202,6 +208,73 @@ def measure(n, N, drives, scale, reps, host_gradient):
         ev.close()
 
 
+def alternating(fns, reps):
+    """medians of `reps` single calls of each function, the functions taking turns; after at least 30 ms of GPU work each"""
+    for fn in fns:
+        spent = 0.0
+        while spent < 30.0:
+            spent += one_call_ms(fn)
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            ts[i].append(one_call_ms(fn))
+    return [round(statistics.median(t), 4) for t in ts]
+
+
+def measure_routes(n, N, drives, scale, reps):
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    prob = dto_amd.host.synthetic.multi_ket_problem(n, 1, drives, N, seed=42, u_bound=4.0, scale=scale or None)
+    evs = [dto_amd.Evaluator(prob), dto_amd.Evaluator(prob)]
+    out = {"n": n, "knots": N, "drives": drives, "scale": scale, "reps": reps, "sigma": SIGMA, "routes": ["default", "reduced_input_store"]}
+    try:
+        evs[1].set_option("reduced_input_store", 1)
+        it = prob.integrators[0]
+        Zh = np.ascontiguousarray(prob.trajectory.vec(), dtype=np.float64)
+        Zh2 = Zh.copy()
+        Zh2[it.u_off] = np.nextafter(Zh2[it.u_off], np.inf)
+        Z, Z2 = torch.from_numpy(Zh).to(dev), torch.from_numpy(Zh2).to(dev)
+        gen = torch.Generator(device=dev); gen.manual_seed(7)
+        mu = torch.randn(evs[0].n_constraints, dtype=torch.float64, device=dev, generator=gen)
+        v = torch.randn(evs[0].n_variables, dtype=torch.float64, device=dev, generator=gen)
+        rs = [torch.full((evs[0].n_variables,), float("nan"), dtype=torch.float64, device=dev) for _ in evs]
+        ys = [torch.full((evs[0].n_variables,), float("nan"), dtype=torch.float64, device=dev) for _ in evs]
+        flips = [[0], [0]]
+
+        def point(i):
+            flips[i][0] ^= 1
+            return Z2 if flips[i][0] else Z
+
+        grad = lambda i, Zp: evs[i].reduced_gradient_dev(Zp.data_ptr(), SIGMA, mu.data_ptr(), rs[i].data_ptr(), 0, st)
+        prod = lambda i, Zp: evs[i].reduced_hessian_product_dev(Zp.data_ptr(), SIGMA, mu.data_ptr(), v.data_ptr(), ys[i].data_ptr(), st)
+        out["gradient_new_ms"] = alternating([lambda i=i: grad(i, point(i)) for i in (0, 1)], reps)
+        out["product_new_ms"] = alternating([lambda i=i: prod(i, point(i)) for i in (0, 1)], reps)
+        for i in (0, 1):
+            grad(i, Z); prod(i, Z)
+        torch.cuda.synchronize()
+        out["product_kept_ms"] = alternating([lambda i=i: prod(i, Z) for i in (0, 1)], reps)
+        scale_y, scale_r = float(ys[0].abs().max()), float(rs[0].abs().max())
+        out["largest_difference_between_routes"] = {"product": float((ys[0] - ys[1]).abs().max()), "product_scale": scale_y,
+                                                    "gradient": float((rs[0] - rs[1]).abs().max()), "gradient_scale": scale_r}
+        splits = []
+        for i, ev in enumerate(evs):
+            ev.profile_enable(True); ev.profile_reset(); prod(i, Z); torch.cuda.synchronize()
+            split, total = {}, ev.profile_get("all")[0]
+            for part in OWN + ("hess_product", "jac_product", "expmv", "all"):
+                ms, launches, work = ev.profile_get(part)
+                split[part] = {"ms": round(ms, 4), "launches": launches, "gflop_or_GB": round(work * 1e-9, 5)}
+                total += ms if part in OWN else 0.0
+            split["device_total_ms"] = round(total, 4)
+            ev.profile_enable(False)
+            splits.append(split)
+        out["split_kept_product"] = splits
+        out["reduced_input_bytes_as_executed"] = evs[1].profile_get("reduced_input")[2]
+        return out
+    finally:
+        for ev in evs:
+            ev.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--shapes", default="256x2000,64x1000", help="comma-separated states x knots")
@@ -210,10 +283,14 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--scale", type=float, default=1.0, help="standard deviation of the generators' entries (1.0: the norms of the\n"
                     "headline benchmark, several squarings per propagator; 0: 1 / sqrt(n), norms of order one)")
+    ap.add_argument("--routes", default="yes", choices=("yes", "no", "only"), help="the default route beside option reduced_input_store = 1")
     a = ap.parse_args()
     for s in a.shapes.split(","):
         n, N = (int(x) for x in s.lower().split("x"))
-        print(json.dumps(measure(n, N, a.drives, a.scale, a.reps, s.lower() == a.host_shape.lower())), flush=True)
+        if a.routes != "only":
+            print(json.dumps(measure(n, N, a.drives, a.scale, a.reps, s.lower() == a.host_shape.lower())), flush=True)
+        if a.routes != "no":
+            print(json.dumps({"routes": measure_routes(n, N, a.drives, a.scale, a.reps)}), flush=True)
 
 
 if __name__ == "__main__":
