@@ -573,10 +573,7 @@ SweepPlan plan_from(dto_handle* h, BilHost& b, const double* dZ, hipStream_t st,
 
 // Is every vector `now` bit-identical to its `cached` copy (both on the device)?  One round trip: the flag (a mailbox member) goes
 // up as 1, one compare launch per pair clears it on a difference, it comes back, the host waits for it.
-struct BitsPair {
-    const double *now, *cached;
-    int64_t n;
-};
+struct BitsPair { const double *now, *cached; int64_t n; };
 bool bits_equal(hipStream_t st, std::initializer_list<BitsPair> pairs, int32_t* d_flag, int32_t* flag) {
     *flag = 1;
     HIP_CHECK(hipMemcpyAsync(d_flag, flag, sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -586,12 +583,36 @@ bool bits_equal(hipStream_t st, std::initializer_list<BitsPair> pairs, int32_t* 
     return *flag != 0;
 }
 
+// The device half of a kept point (dto_kept_point.h; DevicePoint in dto_handle.h).  Its copies and its flag, once.
+void alloc_point(dto_handle* h, DevicePoint& P, bool with_mu) {
+    if (P.d_flag) return;
+    P.d_Z = own(h, dalloc<double>((size_t)h->n_vars));
+    if (with_mu) P.d_mu = own(h, dalloc<double>((size_t)std::max<int64_t>(h->n_cons, 1)));
+    P.d_flag = own(h, dalloc<int32_t>(1));
+}
+// Is (dZ [, sigma] [, dmu] [, tag]) the point P keeps?  The host-side key first; then Z, and mu where the point holds one and one is
+// given, bit for bit against the copies: one round trip.  On a miss the rebuild has BEGUN -- nothing is kept until keep_point.
+bool at_kept_point(dto_handle* h, DevicePoint& P, hipStream_t st, const double* dZ, double sigma = 0.0, const double* dmu = nullptr, int32_t tag = 0) {
+    bool hit = P.rec.may_hit(h->gen, tag, sigma, dmu == nullptr);
+    if (hit && P.d_mu && dmu) hit = bits_equal(st, {{dZ, P.d_Z, h->n_vars}, {dmu, P.d_mu, h->n_cons}}, P.d_flag, &(h->mailbox->*P.flag));
+    else if (hit) hit = bits_equal(st, {{dZ, P.d_Z, h->n_vars}}, P.d_flag, &(h->mailbox->*P.flag));
+    if (!hit) P.rec.begin_rebuild();
+    return hit;
+}
+// Closes the rebuild a miss began: the copies of Z and mu behind the rebuild's kernels, then the record.
+void keep_point(dto_handle* h, DevicePoint& P, hipStream_t st, const double* dZ, double sigma = 0.0, const double* dmu = nullptr, int32_t tag = 0) {
+    HIP_CHECK(hipMemcpyAsync(P.d_Z, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
+    if (P.d_mu && dmu && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(P.d_mu, dmu, sizeof(double) * (size_t)h->n_cons, hipMemcpyDeviceToDevice, st));
+    P.rec.keep(h->gen, tag, sigma, dmu == nullptr);
+}
+
 void invalidate_sweep_caches(dto_handle* h) {
     for (auto& b : h->bil) b.cache.invalidate();
 }
 
 // reuse_forward_sweep: is dZ bit-identical to the point the cached sweeps were computed at?  If not, dZ becomes the new
-// cache point and every integrator's cache is dropped.
+// cache point and every integrator's cache is dropped.  (Not a KeptPoint of dto_kept_point.h and not to be folded into one: no
+// generation, the new Z is adopted BEFORE the compute, and validity lives in SweepCache.)
 bool same_point(dto_handle* h, const double* dZ, hipStream_t st) {
     if (!h->reuse) return false;
     if (!h->d_Zcache) {
@@ -1364,7 +1385,7 @@ double* staging(dto_handle* h, size_t n) {
 
 void drop_caches(dto_handle* h) {
     invalidate_sweep_caches(h);
-    ++h->gen;  // (the Hessian-vector products' cached point as well)
+    ++h->gen;  // (every kept point: dto_kept_point.h)
 }
 void unprime(dto_handle* h) { h->primed[0] = h->primed[1] = false; }
 
@@ -1635,23 +1656,17 @@ void build_hp_index(dto_handle* h) {
     h->d_hp_val = own(h, dalloc<double>(col.size()));
     k.val = h->d_hp_val;
     h->hp_nnz = (int64_t)col.size();
-    h->d_hp_Z = own(h, dalloc<double>((size_t)nv));
-    h->d_hp_mu = own(h, dalloc<double>((size_t)std::max<int64_t>(h->n_cons, 1)));
-    h->d_hp_eq = own(h, dalloc<int32_t>(1));
+    alloc_point(h, h->hp_point, true);
     h->hp_index = true;
     h->hp_bytes = 8.0 * (double)h->info.hess_len + (8.0 + 4.0 + 8.0) * (double)h->hp_nnz + (8.0 + 4.0 + 4.0) * (double)nv;
     h->hp_setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// y = H(Z; sigma, mu) v.  At a new point: do_hessian into the private slab, one gather into the row-major copy; at the cached
-// point (Z, sigma, mu bit for bit, no dto_set_external / dto_set_option / failed call since): the product launch alone, after one
-// device-side compare with a 4-byte readback.
+// y = H(Z; sigma, mu) v.  At a new point: do_hessian into the private slab, one gather into the row-major copy; at the kept point
+// (hp_point: Z, sigma, mu) the product launch alone.
 void hess_product(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dv, double* dy, hipStream_t st) {
     build_hp_index(h);
-    bool hit = h->hp_valid && h->hp_gen == h->gen && memcmp(&sigma, &h->hp_sigma, sizeof(double)) == 0;
-    if (hit) hit = bits_equal(st, {{dZ, h->d_hp_Z, h->n_vars}, {dmu, h->d_hp_mu, h->n_cons}}, h->d_hp_eq, &h->mailbox->hp_flag);
-    if (!hit) {
-        h->hp_valid = false;
+    if (!at_kept_point(h, h->hp_point, st, dZ, sigma, dmu)) {
         if (!h->hp_slab) h->hp_slab = own(h, dalloc<double>((size_t)h->info.hess_len));
         do_hessian(h, dZ, sigma, dmu, h->hp_slab, st);
         h->hp_slab_primed = true;
@@ -1659,11 +1674,7 @@ void hess_product(dto_handle* h, const double* dZ, double sigma, const double* d
             ProfScope ps(h, st, CAT_HESS_PRODUCT, 24.0 * (double)h->hp_nnz);  // position, slab entry, value
             launch_hess_gather(st, h->hp_slab, h->d_hp_pos, h->hp_nnz, h->d_hp_val);
         }
-        HIP_CHECK(hipMemcpyAsync(h->d_hp_Z, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
-        if (h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->d_hp_mu, dmu, sizeof(double) * (size_t)h->n_cons, hipMemcpyDeviceToDevice, st));
-        h->hp_sigma = sigma;
-        h->hp_gen = h->gen;
-        h->hp_valid = true;
+        keep_point(h, h->hp_point, st, dZ, sigma, dmu);
     }
     // bytes: values and columns of every entry, and per row its start, length, id, v and y (v read once: it stays in cache)
     ProfScope ps(h, st, CAT_HESS_PRODUCT, 12.0 * (double)h->hp_nnz + 32.0 * (double)h->n_vars);
@@ -2140,49 +2151,48 @@ int dto_eval_jacobian_transpose_product_dev(dto_handle* h, const double* dZ, con
 // ---- open-loop rollout: X_{k+1} = E_k(Z) X_k through every interval (dto_rollout.hip, dto_rollout_plan.h)
 
 // grow-only device workspace: a failed allocation throws and leaves the old buffer in place
-static double* grow_workspace(dto_handle* h, double*& p, size_t& cap, size_t doubles) {
-    if (doubles <= cap && p) return p;
+static double* grow_workspace(dto_handle* h, Workspace& w, size_t doubles) {
+    if (doubles <= w.cap && w.p) return w.p;
     double* q = dalloc<double>(doubles);
-    if (p) {
-        h->owned.erase(std::find(h->owned.begin(), h->owned.end(), (void*)p));
-        (void)hipFree(p);   // (waits for whatever still reads it)
+    if (w.p) {
+        h->owned.erase(std::find(h->owned.begin(), h->owned.end(), (void*)w.p));
+        (void)hipFree(w.p);   // (waits for whatever still reads it)
     }
-    p = own(h, q);
-    cap = doubles;
-    return p;
+    w.p = own(h, q);
+    w.cap = doubles;
+    return w.p;
+}
+
+static void needs_unsharded(const dto_handle* h, const std::string& who) {   // the rollout, the solves and the reduced operators
+    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{who + " needs an unsharded handle (k_lo, k_hi = the whole trajectory)"};
 }
 
 // What a rollout call names: refused with text before anything is enqueued.  Returns the kernels' record of the integrator.
 static KRollout rollout_args(const dto_handle* h, int32_t integrator, int32_t n_cols, int32_t mode, bool has_X0, const char* who_ = "dto_rollout") {
     const std::string who(who_);
-    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{who + " needs an unsharded handle (k_lo, k_hi = the whole trajectory)"};
+    needs_unsharded(h, who);
     if (integrator < 0 || integrator >= (int32_t)h->integ_kind.size())
         throw HipError{who + ": integrator " + std::to_string(integrator) + " is out of range (the handle has " +
                        std::to_string(h->integ_kind.size()) + ")"};
     if (mode != DTO_ROLLOUT_ALL && mode != DTO_ROLLOUT_FINAL) throw HipError{who + ": mode takes DTO_ROLLOUT_ALL (0) or DTO_ROLLOUT_FINAL (1)"};
-    KRollout R{};
+    int32_t n = 0, x_off = 0, pre = 0;
     const int kind = h->integ_kind[integrator], idx = h->integ_index[integrator];
     if (kind == DTO_INTEGRATOR_BILINEAR) {
         const KBil& k = h->bil[idx].k;
-        R.n = k.n; R.x_off = k.x_off; R.pre = k.pre;
+        n = k.n; x_off = k.x_off; pre = k.pre;
     } else if (kind == DTO_INTEGRATOR_TIME_DEPENDENT_BILINEAR) {
         const TdbHost& t = h->tdb[idx];
-        R.n = t.k.n; R.x_off = t.k.x_off; R.pre = t.place.pre;
+        n = t.k.n; x_off = t.k.x_off; pre = t.place.pre;
     } else if (kind == DTO_INTEGRATOR_DERIVATIVE) {
         throw HipError{who + ": integrator " + std::to_string(integrator) + " is a DerivativeIntegrator: it has no propagator"};
     } else {
         throw HipError{who + ": integrator " + std::to_string(integrator) + " is evaluated on the host (DTO_INTEGRATOR_EXTERNAL): its "
                        "Jacobian block is not known to be a propagator"};
     }
-    if (n_cols < 1 || n_cols > R.n)
-        throw HipError{who + ": n_cols = " + std::to_string(n_cols) + ", allowed 1 .. x_dim = " + std::to_string(R.n)};
+    if (n_cols < 1 || n_cols > n)
+        throw HipError{who + ": n_cols = " + std::to_string(n_cols) + ", allowed 1 .. x_dim = " + std::to_string(n)};
     if (!has_X0 && n_cols != 1) throw HipError{who + ": X0 = NULL (the state of knot 1 of Z) takes n_cols = 1"};
-    R.npad = pad64(R.n);
-    R.n_cols = n_cols;
-    R.col_pad = rollout_col_pad(n_cols);
-    R.K = h->K;
-    R.L = rollout_levels(std::max<int64_t>(R.K, 1));
-    return R;
+    return KRollout(n, x_off, pre, n_cols, h->K);
 }
 
 // Leaves and up-sweep: the product tree of R's integrator from the -E_k blocks of a Jacobian value slab, into `tree`.  The launches
@@ -2203,7 +2213,7 @@ static void rollout_tree_from_slab(dto_handle* h, const KRollout& R, const doubl
 // Jacobian, gather and up-sweep, for the rollout and the single-integrator solves alike: the product tree of R's integrator at dZ, in
 // d_roll_tree.
 static double* build_rollout_tree(dto_handle* h, const KRollout& R, const double* dZ, hipStream_t st, int cat_gather, int cat_tree) {
-    double* tree = grow_workspace(h, h->d_roll_tree, h->roll_tree_cap, rollout_tree_bytes(R.npad, R.K) / sizeof(double));
+    double* tree = grow_workspace(h, h->d_roll_tree, rollout_tree_bytes(R.npad, R.K) / sizeof(double));
     double* slab = jac_scratch(h);
     // the whole Jacobian, tangent sweep included: the x_k columns of the integrator then hold -E_k on every path
     do_jacobian(h, dZ, slab, st);   // (external blocks are staged as for dto_eval_jacobian_dev)
@@ -2216,14 +2226,14 @@ static void rollout(dto_handle* h, const KRollout& R, const double* dZ, const do
     const int npad = R.npad, L = R.L;
     const int64_t K = R.K;
     const size_t nn = (size_t)npad * npad;
-    double* S = grow_workspace(h, h->d_roll_S, h->roll_S_cap, rollout_traj_bytes(npad, K, R.n_cols) / sizeof(double));
+    double* S = grow_workspace(h, h->d_roll_S, rollout_traj_bytes(npad, K, R.n_cols) / sizeof(double));
     if (K < 1) {   // a single knot: the rollout is X0
         ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, 0.0);
         launch_rollout_start(st, R, dZ, dX0, S);
         launch_rollout_compact(st, R, 0, 1, S, dX);
         return;
     }
-    h->dyn_valid = false;   // (the tree the solves keep per point is overwritten)
+    h->dyn_point.rec.drop();   // (the tree the solves keep per point is overwritten)
     double* tree = build_rollout_tree(h, R, dZ, st, CAT_ROLLOUT, CAT_ROLLOUT_TREE);
     { ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, 0.0); launch_rollout_start(st, R, dZ, dX0, S); }
     const double item_flops = 2.0 * (double)nn * R.col_pad;
@@ -2239,11 +2249,9 @@ static void rollout(dto_handle* h, const KRollout& R, const double* dZ, const do
     } else {
         // the final state alone: the items on the way from knot K back to knot 0, highest level first -- the same launches on the
         // same operands as in the full descent, so the same bits
-        int lv[64];
-        int64_t ix[64];
-        int cnt = 0;
-        for (int64_t t = K; t > 0; t = rollout_item(L, K, lv[cnt - 1], ix[cnt - 1]).start) { rollout_writer(L, t, lv[cnt], ix[cnt]); ++cnt; }
-        for (int c = cnt - 1; c >= 0; --c) {
+        int lv[ROLLOUT_MAX_PATH];
+        int64_t ix[ROLLOUT_MAX_PATH];
+        for (int c = 0, cnt = rollout_final_path(L, K, lv, ix); c < cnt; ++c) {
             ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, item_flops);
             launch_rollout_descend(st, R, lv[c], ix[c], tree, S);
         }
@@ -2258,7 +2266,7 @@ int dto_rollout(dto_handle* h, int32_t integrator, const double* Z, const double
         upload_Z(h, Z);
         const double* dX0 = nullptr;
         if (X0) {
-            double* d = grow_workspace(h, h->d_roll_X0, h->roll_X0_cap, (size_t)R.n * R.n_cols);
+            double* d = grow_workspace(h, h->d_roll_X0, (size_t)R.n * R.n_cols);
             HIP_CHECK(hipMemcpyAsync(d, X0, sizeof(double) * (size_t)R.n * R.n_cols, hipMemcpyHostToDevice, h->stream));
             dX0 = d;
         }
@@ -2312,8 +2320,7 @@ static void dynsolve_descend_all(dto_handle* h, const KRollout& R, int adjoint, 
 }
 
 // The device routine both entry-point families run: everything on `st`, dZ / dB / dY device pointers.  The tree is rebuilt (do_jacobian
-// into the private slab, leaves, products) unless the one in d_roll_tree belongs to this integrator at this point: Z bit for bit the
-// point of the build (one compare with a 4-byte readback), no dto_set_external / dto_set_option / failed call and no rollout since.
+// into the private slab, leaves, products) unless the one in d_roll_tree is the kept point's (dyn_point: integrator, Z; no rollout since).
 static void dynamics_solve(dto_handle* h, const KRollout& R, int32_t integrator, const double* dZ, int adjoint, const double* dB, int mode,
                            double* dY, hipStream_t st) {
     const int npad = R.npad, L = R.L;
@@ -2323,23 +2330,14 @@ static void dynamics_solve(dto_handle* h, const KRollout& R, int32_t integrator,
         HIP_CHECK(hipMemcpyAsync(dY, dB, sizeof(double) * (size_t)R.n_cols * R.n, hipMemcpyDeviceToDevice, st));
         return;
     }
-    double* S = grow_workspace(h, h->d_roll_S, h->roll_S_cap, rollout_traj_bytes(npad, K, R.n_cols) / sizeof(double));
-    double* off = grow_workspace(h, h->d_dyn_off, h->dyn_off_cap, dynsolve_offset_bytes(npad, K, R.n_cols) / sizeof(double));
-    if (!h->d_dyn_Z) {
-        h->d_dyn_Z = own(h, dalloc<double>((size_t)h->n_vars));
-        h->d_dyn_eq = own(h, dalloc<int32_t>(1));
-    }
-    bool hit = h->dyn_valid && h->dyn_integrator == integrator && h->dyn_gen == h->gen;
-    if (hit) hit = bits_equal(st, {{dZ, h->d_dyn_Z, h->n_vars}}, h->d_dyn_eq, &h->mailbox->dyn_flag);
-    if (!hit) {
-        h->dyn_valid = false;
+    double* S = grow_workspace(h, h->d_roll_S, rollout_traj_bytes(npad, K, R.n_cols) / sizeof(double));
+    double* off = grow_workspace(h, h->d_dyn_off, dynsolve_offset_bytes(npad, K, R.n_cols) / sizeof(double));
+    alloc_point(h, h->dyn_point, false);
+    if (!at_kept_point(h, h->dyn_point, st, dZ, 0.0, nullptr, integrator)) {
         build_rollout_tree(h, R, dZ, st, CAT_DYNSOLVE_TREE, CAT_DYNSOLVE_TREE);
-        HIP_CHECK(hipMemcpyAsync(h->d_dyn_Z, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
-        h->dyn_integrator = integrator;
-        h->dyn_gen = h->gen;
-        h->dyn_valid = true;
+        keep_point(h, h->dyn_point, st, dZ, 0.0, nullptr, integrator);
     }
-    const double* tree = h->d_roll_tree;
+    const double* tree = h->d_roll_tree.p;
     dynsolve_load_and_up(h, R, adjoint, tree, dB, off, S, st);
     const double item_flops = 2.0 * (double)npad * npad * R.col_pad;
     if (mode == DTO_ROLLOUT_ALL) {
@@ -2354,11 +2352,9 @@ static void dynamics_solve(dto_handle* h, const KRollout& R, int32_t integrator,
         launch_rollout_compact(st, R, 0, 1, S, dY);
     } else {
         // knot N alone: the items on the way from knot K back to knot 0, highest level first, as dto_rollout's final mode runs them
-        int lv[64];
-        int64_t ix[64];
-        int cnt = 0;
-        for (int64_t t = K; t > 0; t = rollout_item(L, K, lv[cnt - 1], ix[cnt - 1]).start) { rollout_writer(L, t, lv[cnt], ix[cnt]); ++cnt; }
-        for (int c = cnt - 1; c >= 0; --c) {
+        int lv[ROLLOUT_MAX_PATH];
+        int64_t ix[ROLLOUT_MAX_PATH];
+        for (int c = 0, cnt = rollout_final_path(L, K, lv, ix); c < cnt; ++c) {
             ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, item_flops);
             launch_dynsolve_descend(st, R, 0, lv[c], ix[c], tree, off, S);
         }
@@ -2373,7 +2369,7 @@ int dto_dynamics_solve(dto_handle* h, int32_t integrator, const double* Z, int32
         const KRollout R = dynsolve_args(h, integrator, direction, B, n_cols, mode);
         upload_Z(h, Z);
         const size_t n_in = (size_t)h->N * R.n_cols * R.n;
-        double* dB = grow_workspace(h, h->d_dyn_B, h->dyn_B_cap, n_in);
+        double* dB = grow_workspace(h, h->d_dyn_B, n_in);
         HIP_CHECK(hipMemcpyAsync(dB, B, sizeof(double) * n_in, hipMemcpyHostToDevice, h->stream));
         const size_t n_out = (size_t)(mode == DTO_ROLLOUT_ALL ? h->N : 1) * R.n_cols * R.n;
         double* o = staging(h, n_out);
@@ -2436,22 +2432,13 @@ static int elim_x_off(const dto_handle* h, int i) {
 
 // the block solve's record of integrator i (bilinear or time-dependent)
 static KRollout elim_rollout_args(const dto_handle* h, const ElimPlan& p, int i, int n_cols) {
-    KRollout R{};
-    R.n = h->integ_dim[i];
-    R.x_off = elim_x_off(h, i);
-    R.pre = p.pre[i];
-    R.npad = pad64(R.n);
-    R.n_cols = n_cols;
-    R.col_pad = rollout_col_pad(n_cols);
-    R.K = h->K;
-    R.L = rollout_levels(std::max<int64_t>(R.K, 1));
-    return R;
+    return KRollout(h->integ_dim[i], elim_x_off(h, i), p.pre[i], n_cols, h->K);
 }
 
 // What a whole-dynamics solve names: refused with text before anything is enqueued.
 static const ElimPlan& elim_args(dto_handle* h, int32_t direction, const double* B, int32_t n_cols) {
     const std::string who = "dto_dynamics_solve_all";
-    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{who + " needs an unsharded handle (k_lo, k_hi = the whole trajectory)"};
+    needs_unsharded(h, who);
     const ElimPlan& p = elim_plan_of(h);
     if (!p.refusal.empty()) throw HipError{who + ": " + p.refusal};
     if (direction != DTO_SOLVE_FORWARD && direction != DTO_SOLVE_ADJOINT)
@@ -2488,13 +2475,10 @@ static void elim_upload_terms(dto_handle* h, const ElimPlan& p) {
 
 // The device routine both entry-point families run: everything on `st`, dZ / dB / dY device pointers, dB and dY [N][n_cols][D].  At a
 // new point: ONE do_jacobian into the private slab, then per integrator with a propagator the leaves and products of its own tree,
-// the gather of every coupling block (with the option "reduced_input_store" of every input block too), and a copy of Z.  At the point
-// of the last call -- Z bit for bit, `gen` unchanged -- none of it.
-// dynamics_solve_all = elim_point (the workspaces, the point check and the rebuild) + elim_solve (the block elimination at the kept
-// point).  The reduced-space operators' input-store route calls the halves itself: its first kernel reads what the rebuild gathers.
-struct ElimWork {
-    double *Bp, *Yp, *S, *off, *store;
-};
+// the gather of every coupling block (with the option "reduced_input_store" of every input block too).  At the kept point: none of it.
+// dynamics_solve_all = elim_point (workspaces, point check, rebuild) + elim_solve (the block elimination at the kept point).  The
+// reduced-space operators' input-store route calls the halves itself: its first kernel reads what the rebuild gathers.
+struct ElimWork { double *Bp, *Yp, *S, *off, *store; };
 
 // the input-block store's plan and device tables (option "reduced_input_store"), once per handle
 static const InputPlan& input_plan_of(dto_handle* h, const ElimPlan& p) {
@@ -2540,35 +2524,28 @@ static ElimWork elim_point(dto_handle* h, const ElimPlan& p, const double* dZ, i
         n_max = std::max(n_max, h->integ_dim[i]);
         if (elim_has_tree(h, i)) npad_max = std::max(npad_max, pad64(h->integ_dim[i]));
     }
-    double* Bp = grow_workspace(h, h->d_elim_Bp, h->elim_Bp_cap, (size_t)N * n_cols * n_max);
-    double* Yp = grow_workspace(h, h->d_elim_Yp, h->elim_Yp_cap, (size_t)N * n_cols * n_max);
+    double* Bp = grow_workspace(h, h->d_elim_Bp, (size_t)N * n_cols * n_max);
+    double* Yp = grow_workspace(h, h->d_elim_Yp, (size_t)N * n_cols * n_max);
     double *S = nullptr, *off = nullptr;
     if (npad_max) {
-        S = grow_workspace(h, h->d_roll_S, h->roll_S_cap, rollout_traj_bytes(npad_max, K, n_cols) / sizeof(double));
-        off = grow_workspace(h, h->d_dyn_off, h->dyn_off_cap, dynsolve_offset_bytes(npad_max, K, n_cols) / sizeof(double));
+        S = grow_workspace(h, h->d_roll_S, rollout_traj_bytes(npad_max, K, n_cols) / sizeof(double));
+        off = grow_workspace(h, h->d_dyn_off, dynsolve_offset_bytes(npad_max, K, n_cols) / sizeof(double));
     }
-    double* store = grow_workspace(h, h->d_elim_store, h->elim_store_cap, (size_t)p.store_off[I]);
+    double* store = grow_workspace(h, h->d_elim_store, (size_t)p.store_off[I]);
     const InputPlan* ip = h->reduced_input_store ? &input_plan_of(h, p) : nullptr;
-    if (ip) grow_workspace(h, h->d_in_store, h->in_store_cap, (size_t)ip->store_off[I]);
-    h->elim_tree.resize(I, nullptr);
-    h->elim_tree_cap.resize(I, 0);
+    if (ip) grow_workspace(h, h->d_in_store, (size_t)ip->store_off[I]);
+    h->elim_tree.resize(I);
     for (int i = 0; i < I; ++i)
         if (elim_has_tree(h, i))
-            grow_workspace(h, h->elim_tree[i], h->elim_tree_cap[i], rollout_tree_bytes(pad64(h->integ_dim[i]), K) / sizeof(double));
+            grow_workspace(h, h->elim_tree[i], rollout_tree_bytes(pad64(h->integ_dim[i]), K) / sizeof(double));
     elim_upload_terms(h, p);
-    if (!h->d_elim_Z) {
-        h->d_elim_Z = own(h, dalloc<double>((size_t)h->n_vars));
-        h->d_elim_eq = own(h, dalloc<int32_t>(1));
-    }
-    bool hit = h->elim_valid && h->elim_gen == h->gen;
-    if (hit) hit = bits_equal(st, {{dZ, h->d_elim_Z, h->n_vars}}, h->d_elim_eq, &h->mailbox->dyn_flag);
-    if (!hit) {
-        h->elim_valid = false;
+    alloc_point(h, h->elim_point, false);
+    if (!at_kept_point(h, h->elim_point, st, dZ)) {
         double* slab = jac_scratch(h);
         do_jacobian(h, dZ, slab, st);   // once, however many integrators there are
         for (int i = 0; i < I; ++i)
             if (elim_has_tree(h, i))
-                rollout_tree_from_slab(h, elim_rollout_args(h, p, i, n_cols), slab, h->elim_tree[i], st, CAT_DYNSOLVE_TREE, CAT_DYNSOLVE_TREE);
+                rollout_tree_from_slab(h, elim_rollout_args(h, p, i, n_cols), slab, h->elim_tree[i].p, st, CAT_DYNSOLVE_TREE, CAT_DYNSOLVE_TREE);
         for (int a = 0; a < I; ++a)
             for (const ElimDep& d : p.deps[a]) {
                 const int n_a = h->integ_dim[a], n_b = h->integ_dim[d.b];
@@ -2579,11 +2556,9 @@ static ElimWork elim_point(dto_handle* h, const ElimPlan& p, const double* dZ, i
             for (int a = 0; a < I; ++a)
                 if (ip->width[a] > 0) {
                     ProfScope ps(h, st, CAT_REDUCED_INPUT, 16.0 * (double)K * 2.0 * ip->width[a] * h->integ_dim[a]);
-                    launch_red_input_gather(st, h->P, h->in, a, slab, h->d_in_store);
+                    launch_red_input_gather(st, h->P, h->in, a, slab, h->d_in_store.p);
                 }
-        HIP_CHECK(hipMemcpyAsync(h->d_elim_Z, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
-        h->elim_gen = h->gen;
-        h->elim_valid = true;
+        keep_point(h, h->elim_point, st, dZ);
     }
     return ElimWork{Bp, Yp, S, off, store};
 }
@@ -2610,8 +2585,8 @@ static void elim_solve(dto_handle* h, const ElimPlan& p, const ElimWork& W, int 
             continue;
         }
         const KRollout R = elim_rollout_args(h, p, a, n_cols);
-        dynsolve_load_and_up(h, R, adjoint, h->elim_tree[a], Bp, off, S, st);
-        dynsolve_descend_all(h, R, adjoint, h->elim_tree[a], off, S, Yp, st);
+        dynsolve_load_and_up(h, R, adjoint, h->elim_tree[a].p, Bp, off, S, st);
+        dynsolve_descend_all(h, R, adjoint, h->elim_tree[a].p, off, S, Yp, st);
         ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
         launch_elim_collect(st, N, n_a, n_cols, D, p.pre[a], Yp, dY);
     }
@@ -2651,7 +2626,7 @@ int dto_dynamics_solve_all(dto_handle* h, const double* Z, int32_t direction, co
         const ElimPlan& p = elim_args(h, direction, B, n_cols);
         upload_Z(h, Z);
         const size_t n = (size_t)h->N * n_cols * p.n_states;
-        double* dB = grow_workspace(h, h->d_elim_B, h->elim_B_cap, n);
+        double* dB = grow_workspace(h, h->d_elim_B, n);
         HIP_CHECK(hipMemcpyAsync(dB, B, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
         double* o = staging(h, n);
         dynamics_solve_all(h, p, h->d_Z, direction == DTO_SOLVE_ADJOINT, dB, n_cols, o, h->stream);
@@ -2674,7 +2649,7 @@ int dto_dynamics_solve_all_dev(dto_handle* h, const double* dZ, int32_t directio
 
 // What a reduced-space call names: refused with text before anything is enqueued.
 static const ElimPlan& reduced_args(dto_handle* h, const std::string& who, bool hessian) {
-    if (h->k_lo != 1 || h->k_hi != h->N) throw HipError{who + " needs an unsharded handle (k_lo, k_hi = the whole trajectory)"};
+    needs_unsharded(h, who);
     const ElimPlan& p = elim_plan_of(h);
     if (!p.refusal.empty()) throw HipError{who + ": " + p.refusal};
     if (h->n_ext_int + h->n_ext_con + h->n_ext_obj > 0)
@@ -2708,11 +2683,11 @@ static void reduced_workspaces(dto_handle* h, const ElimPlan& p) {
         throw;
     }
     h->red = KReduced{own(h, comp_pos), own(h, pos_comp), own(h, pos_dim), own(h, pos_row), h->z, p.n_states, h->N, h->n_vars, h->n_cons, h->n_dyn};
-    h->d_red_eq = own(h, eq);
+    h->red_point.d_flag = own(h, eq);
     double* q = blk;
     auto take = [&](size_t n) { double* r = q; q += n; return r; };
-    h->red_Z = take(nv); h->red_g = take(nv); h->red_r = take(nv); h->red_a = take(nv); h->red_b = take(nv); h->red_hv = take(nv); h->red_out = take(nv);
-    h->red_mu = take(nc); h->red_mut = take(nc); h->red_w = take(nc); h->red_hmu = take(nc);
+    h->red_point.d_Z = take(nv); h->red_g = take(nv); h->red_r = take(nv); h->red_a = take(nv); h->red_b = take(nv); h->red_hv = take(nv); h->red_out = take(nv);
+    h->red_point.d_mu = take(nc); h->red_mut = take(nc); h->red_w = take(nc); h->red_hmu = take(nc);
     h->red_lam = take(nd); h->red_s1 = take(nd); h->red_s2 = take(nd);
     h->d_red = own(h, blk);
 }
@@ -2726,17 +2701,11 @@ static double input_transposed_bytes(const dto_handle* h) {
     return 8.0 * ((double)h->input->store_off.back() + 2.0 * (double)h->n_vars + (double)h->N * h->red.D);
 }
 
-// The reduced point: g, Lam, mu~ and the reduced gradient at (Z, sigma, mu), computed unless the ones kept belong to this point --
-// Z and mu bit for bit (one compare with a 4-byte readback), sigma, the "mu = NULL" mark and `gen`.
+// The reduced point: g, Lam, mu~ and the reduced gradient at (Z, sigma, mu or "mu = NULL"), computed unless red_point keeps them.
 static void reduced_point(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, hipStream_t st) {
     const KReduced& R = h->red;
     const double nv = 8.0 * (double)h->n_vars, nc = 8.0 * (double)h->n_cons, nd = 8.0 * (double)h->N * R.D;
-    bool hit = h->red_valid && h->red_gen == h->gen && memcmp(&sigma, &h->red_sigma, sizeof(double)) == 0 && (dmu == nullptr) == h->red_mu_null;
-    if (hit)
-        hit = dmu ? bits_equal(st, {{dZ, h->red_Z, h->n_vars}, {dmu, h->red_mu, h->n_cons}}, h->d_red_eq, &h->mailbox->red_flag)
-                  : bits_equal(st, {{dZ, h->red_Z, h->n_vars}}, h->d_red_eq, &h->mailbox->red_flag);
-    if (hit) return;
-    h->red_valid = false;
+    if (at_kept_point(h, h->red_point, st, dZ, sigma, dmu)) return;
     do_gradient(h, dZ, h->red_a, st);
     const double* t1 = nullptr;
     if (dmu) {   // J' w1, w1 = mu with its dynamics rows zeroed
@@ -2749,17 +2718,12 @@ static void reduced_point(dto_handle* h, const ElimPlan& p, const double* dZ, do
     { ProfScope ps(h, st, CAT_REDUCED_PACK, nd + (dmu ? 3.0 : 2.0) * nc); launch_red_multipliers(st, R, h->red_lam, dmu, 0, h->red_w, h->red_mut); }
     if (h->reduced_input_store && h->K >= 1) {   // t = J' w2 from the input blocks the adjoint solve's point holds
         ProfScope ps(h, st, CAT_REDUCED_INPUT, input_transposed_bytes(h));
-        launch_red_input_transposed(st, R, h->in, h->d_in_store, h->red_g, h->red_lam, h->red_r);
+        launch_red_input_transposed(st, R, h->in, h->d_in_store.p, h->red_g, h->red_lam, h->red_r);
     } else {
         jac_product(h, dZ, h->red_w, h->red_b, 1, st);
         { ProfScope ps(h, st, CAT_REDUCED_PACK, 3.0 * nv); launch_red_finish(st, R, h->red_g, h->red_b, h->red_lam, h->red_r); }
     }
-    HIP_CHECK(hipMemcpyAsync(h->red_Z, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
-    if (dmu && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->red_mu, dmu, sizeof(double) * (size_t)h->n_cons, hipMemcpyDeviceToDevice, st));
-    h->red_mu_null = dmu == nullptr;
-    h->red_sigma = sigma;
-    h->red_gen = h->gen;
-    h->red_valid = true;
+    keep_point(h, h->red_point, st, dZ, sigma, dmu);
 }
 
 // The device routines both entry-point families run: everything on `st`, every pointer a device pointer.
@@ -2781,14 +2745,14 @@ static void reduced_hessian_product(dto_handle* h, const ElimPlan& p, const doub
         // valid and the input blocks stale.  So the solves' point is made this Z BEFORE the first kernel reads the store (one compare;
         // after such a call one rebuild with one Jacobian evaluation), and both solves then run at it without a compare of their own.
         const ElimWork W = elim_point(h, p, dZ, 1, st);
-        { ProfScope ps(h, st, CAT_REDUCED_INPUT, input_forward_bytes(h)); launch_red_input_forward(st, R, h->in, h->d_in_store, dv, h->red_s1); }
+        { ProfScope ps(h, st, CAT_REDUCED_INPUT, input_forward_bytes(h)); launch_red_input_forward(st, R, h->in, h->d_in_store.p, dv, h->red_s1); }
         elim_solve(h, p, W, 0, h->red_s1, 1, h->red_s2, st);                    // MM Y = B
         { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_zhat(st, R, dv, h->red_s2, h->red_a); }
         hess_product(h, dZ, sigma, h->red_mut, h->red_a, h->red_b, st);         // q = H(mu~) z^
         { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nd); launch_red_gather(st, R, h->red_b, h->red_s1); }
         elim_solve(h, p, W, 1, h->red_s1, 1, h->red_s2, st);                    // MM' Gam = q_S
         ProfScope ps(h, st, CAT_REDUCED_INPUT, input_transposed_bytes(h));
-        launch_red_input_transposed(st, R, h->in, h->d_in_store, h->red_b, h->red_s2, dy);
+        launch_red_input_transposed(st, R, h->in, h->d_in_store.p, h->red_b, h->red_s2, dy);
         return;
     }
     { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_vhat(st, R, dv, h->red_a); }

@@ -20,6 +20,7 @@
 #include "dto_elim_plan.h"
 #include "dto_hostxfer.h"
 #include "dto_input_plan.h"
+#include "dto_kept_point.h"
 #include "dto_kernels.h"
 #include "dto_sweep_cache.h"
 
@@ -201,10 +202,23 @@ struct PinnedMailbox {
     int32_t sweep_stats[2];        // fused_sweep_steps: a sweep's two statistics; step-per-launch sweeps: their checkpoints, alternating
     unsigned long long hump[8];    // k_hump's output (read_hump)
     int32_t same_flag;             // same_point's bit compare
-    int32_t hp_flag;               // hess_product's bit compare
-    int32_t dyn_flag;              // dynamics_solve's bit compare
-    int32_t red_flag;              // the reduced point's bit compare
+    int32_t hp_flag;               // the kept points' bit compares (DevicePoint::flag names its member): hess_product's,
+    int32_t dyn_flag;              // dynamics_solve's,
+    int32_t elim_flag;             // the whole-dynamics solves',
+    int32_t red_flag;              // the reduced point's
     int32_t deferred_smax;         // the one-launch chain's squaring count of an enqueue-only call (smax_pending)
+};
+
+struct Workspace { double* p = nullptr; size_t cap = 0; };   // grow-only device buffer, capacity in doubles (grow_workspace, dto_engine.cpp)
+
+// A kept point (dto_kept_point.h states the protocol): the host record, the device copies of the Z and mu it was built at, the bit
+// compare's device flag and the mailbox member it comes back into.  The handle owns the memory, whichever allocation it lies in.
+struct DevicePoint {
+    KeptPoint rec;
+    int32_t PinnedMailbox::*flag;
+    double *d_Z = nullptr, *d_mu = nullptr;   // d_mu null: mu is no part of the point
+    int32_t* d_flag = nullptr;
+    DevicePoint(unsigned parts, int32_t PinnedMailbox::*f) : rec(parts), flag(f) {}
 };
 }  // namespace dto
 
@@ -278,55 +292,39 @@ struct dto_handle {
     int32_t* d_plan = nullptr;   // [4] {q, d_ub, tc} of a sweep planned on the device from d_bounds (launch_plan_dev)
     double* d_jac_scratch = nullptr;     // value slab for the Jacobian-vector products (lazy)
     double* d_w = nullptr;               // product input
-    // open-loop rollout (dto_rollout[_dev]): product tree, padded trajectory and the host-pointer form's X0; allocated at the first
-    // rollout, grow-only (capacities in doubles)
-    double *d_roll_tree = nullptr, *d_roll_S = nullptr, *d_roll_X0 = nullptr;
-    size_t roll_tree_cap = 0, roll_S_cap = 0, roll_X0_cap = 0;
-    // solves with the dynamics block (dto_dynamics_solve[_dev]): they keep the product tree in d_roll_tree per point -- integrator,
-    // Z bit for bit (d_dyn_Z: the copy taken at the build) and `gen`; a rollout overwrites the tree and clears dyn_valid.  The offset
-    // tree and the host-pointer form's B are grow-only like the rollout's buffers.
-    double *d_dyn_off = nullptr, *d_dyn_B = nullptr, *d_dyn_Z = nullptr;
-    size_t dyn_off_cap = 0, dyn_B_cap = 0;
-    int32_t* d_dyn_eq = nullptr;
-    bool dyn_valid = false;
-    int32_t dyn_integrator = -1;
-    uint64_t dyn_gen = 0;
-    // whole-dynamics solves (dto_dynamics_solve_all[_dev]; plan: dto_elim_plan.h): a product tree per bilinear / time-dependent
-    // integrator (list position -> buffer, null for a DerivativeIntegrator), the compact coupling store and a copy of Z, all the
-    // call's own and kept per point -- Z bit for bit (d_elim_Z) and `gen`; neither dto_rollout nor dto_dynamics_solve touches them.
-    // Bp / Yp: one block solve's right-hand side and result; d_elim_B: the host-pointer form's B.  Grow-only (capacities in doubles).
+    uint64_t gen = 0;   // the generation every kept point (dto_kept_point.h) is keyed by: drop_caches bumps it
+    // open-loop rollout (dto_rollout[_dev]): product tree, padded trajectory and the host-pointer form's X0
+    dto::Workspace d_roll_tree, d_roll_S, d_roll_X0;
+    // solves with the dynamics block (dto_dynamics_solve[_dev]): their kept point is the product tree in d_roll_tree, tagged with the
+    // integrator; a rollout overwrites the tree and drops the point.  The offset tree and the host-pointer form's B.
+    dto::Workspace d_dyn_off, d_dyn_B;
+    dto::DevicePoint dyn_point{dto::KeptPoint::TAG, &dto::PinnedMailbox::dyn_flag};
+    // whole-dynamics solves (dto_dynamics_solve_all[_dev]; plan: dto_elim_plan.h): their kept point is a product tree per integrator
+    // (by list position, empty for a DerivativeIntegrator) and the compact coupling store, all the call's own: neither dto_rollout nor
+    // dto_dynamics_solve touches them.  Bp / Yp: one block solve's right-hand side and result; d_elim_B: the host-pointer form's B.
     std::unique_ptr<dto::ElimPlan> elim;
-    std::vector<double*> elim_tree;
-    std::vector<size_t> elim_tree_cap;
+    std::vector<dto::Workspace> elim_tree;
     dto::KElimTerm* d_elim_terms = nullptr;          // forward terms of every integrator, then the adjoint terms
     std::vector<int> elim_fw_term0, elim_ad_term0;   // [I + 1] ranges in d_elim_terms
-    double *d_elim_store = nullptr, *d_elim_Z = nullptr, *d_elim_Bp = nullptr, *d_elim_Yp = nullptr, *d_elim_B = nullptr;
-    size_t elim_store_cap = 0, elim_Bp_cap = 0, elim_Yp_cap = 0, elim_B_cap = 0;
-    int32_t* d_elim_eq = nullptr;
-    bool elim_valid = false;
-    uint64_t elim_gen = 0;
+    dto::Workspace d_elim_store, d_elim_Bp, d_elim_Yp, d_elim_B;
+    dto::DevicePoint elim_point{0, &dto::PinnedMailbox::elim_flag};
     // reduced-space operators (dto_reduced_gradient[_dev], dto_reduced_hessian_product[_dev]; plan: dto_reduced_plan.h).  One block
     // d_red holds every vector; its sizes depend on the handle alone, so it is allocated once, before anything is enqueued, and freed
-    // with the handle.  The reduced POINT is kept like the other per-point caches -- Z bit for bit (red_Z), sigma, mu bit for bit
-    // (red_mu) or the mark "mu was NULL", and `gen` -- and holds g (red_g), the costates Lam [N][D] (red_lam), the multipliers mu~
-    // (red_mut) and the reduced gradient (red_r).  a, b [n_vars], w [n_cons], s1, s2 [N D]: scratch of one call; hv, hmu: v and mu
-    // of the host-pointer forms; out: their y.
+    // with the handle.  The reduced POINT -- keyed by sigma and the mark "mu was NULL" too, its copies of Z and mu inside d_red -- holds
+    // g (red_g), the costates Lam [N][D] (red_lam), the multipliers mu~ (red_mut) and the reduced gradient (red_r).  a, b [n_vars],
+    // w [n_cons], s1, s2 [N D]: scratch of one call; hv, hmu: v and mu of the host-pointer forms; out: their y.
     dto::KReduced red{};   // device tables
     double* d_red = nullptr;
-    double *red_Z = nullptr, *red_mu = nullptr, *red_g = nullptr, *red_lam = nullptr, *red_mut = nullptr, *red_r = nullptr;
+    double *red_g = nullptr, *red_lam = nullptr, *red_mut = nullptr, *red_r = nullptr;
     double *red_a = nullptr, *red_b = nullptr, *red_w = nullptr, *red_s1 = nullptr, *red_s2 = nullptr;
     double *red_hv = nullptr, *red_hmu = nullptr, *red_out = nullptr;
-    int32_t* d_red_eq = nullptr;
-    bool red_valid = false, red_mu_null = false;
-    double red_sigma = 0.0;
-    uint64_t red_gen = 0;
+    dto::DevicePoint red_point{dto::KeptPoint::SIGMA | dto::KeptPoint::MU_MARK, &dto::PinnedMailbox::red_flag};
     // the operators' input-block store (option "reduced_input_store"; plan: dto_input_plan.h): the tables once per handle, the store
-    // F grow-only and kept with the whole-dynamics solves' point (elim_valid, elim_gen: gathered in the same rebuild, from the same slab)
+    // F grow-only and kept with the whole-dynamics solves' point (elim_point: gathered in the same rebuild, from the same slab)
     int reduced_input_store = 0;   // option of that name: 1 takes J v^ and J' w of the reduced operators from the kept input blocks
     std::unique_ptr<dto::InputPlan> input;
     dto::KInput in{};              // device tables
-    double* d_in_store = nullptr;
-    size_t in_store_cap = 0;
+    dto::Workspace d_in_store;
     int64_t* d_conbase = nullptr;       // [n_vars+1] first constraint-pattern entry of each column
     int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
     int64_t* d_crow_col = nullptr;
@@ -375,8 +373,7 @@ struct dto_handle {
     int64_t* d_ranges = nullptr;
     // Hessian-vector products (dto_eval_hessian_product[_dev]): H is assembled once per point into a private slab, its entries
     // that can be non-zero are gathered into a row-major copy of both triangles, and every product at that point is one launch
-    // (dto_hess_product.hip).  The point is (Z, sigma, mu) bit for bit plus `gen`, which every dto_set_external, dto_set_option and
-    // failed call bumps.
+    // (dto_hess_product.hip).  The kept point is keyed by sigma and always holds a mu.
     double* hp_slab = nullptr;       // [hess_len], allocated at the first product
     bool hp_slab_primed = false;     // written in full once: later points clear only the variable runs (as a bound output)
     bool hp_index = false;
@@ -384,13 +381,8 @@ struct dto_handle {
     int64_t hp_nnz = 0;              // entries of the row-major copy (odd rows padded)
     int64_t* d_hp_pos = nullptr;     // [hp_nnz] slab position of every entry, -1 for padding
     double* d_hp_val = nullptr;
-    double* d_hp_Z = nullptr;        // the cached point
-    double* d_hp_mu = nullptr;
     double* d_hp_v = nullptr;        // host-pointer form: v
-    int32_t* d_hp_eq = nullptr;
-    double hp_sigma = 0.0;
-    bool hp_valid = false;
-    uint64_t gen = 0, hp_gen = 0;
+    dto::DevicePoint hp_point{dto::KeptPoint::SIGMA, &dto::PinnedMailbox::hp_flag};
     double hp_setup_ms = 0.0;        // host time of the index build ...
     double hp_bytes = 0.0;           // ... and the device bytes of the private slab and the index
     std::vector<void*> owned;  // device allocations to free

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "dto_reduced_plan.h"  // index plan of the reduced-space operators (KReduced)
+#include "dto_rollout_plan.h"  // index plan of the rollout's tree (KRollout's padding and level count)
 #include "dto_slab_layout.h"  // where every Jacobian and Hessian entry sits in its value slab
 #include "dto_sweep_plan.h"   // sweep planning: step budget, launch shapes (SweepTypes, the *SweepPlan structs and planners), form choice
 
@@ -444,6 +445,10 @@ struct KRollout {
     int32_t n_cols, col_pad;
     int32_t L;      // tree levels: 2^L >= K
     int64_t K;      // intervals
+    KRollout() = default;
+    KRollout(int32_t n_, int32_t x_off_, int32_t pre_, int32_t n_cols_, int64_t K_)
+        : n(n_), npad((n_ + 63) / 64 * 64), x_off(x_off_), pre(pre_), n_cols(n_cols_), col_pad(rollout_col_pad(n_cols_)),
+          L(rollout_levels(K_ > 1 ? K_ : 1)), K(K_) {}
 };
 void launch_rollout_leaves(hipStream_t st, const KProb& P, const KRollout& R, const double* vals, double* tree);
 void launch_rollout_start(hipStream_t st, const KRollout& R, const double* dZ, const double* X0, double* S);

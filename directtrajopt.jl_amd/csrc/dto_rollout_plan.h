@@ -84,6 +84,18 @@ RLP_HD inline void rollout_writer(int L, int64_t t, int& l, int64_t& i) {
     while (!((t >> (l - 1)) & 1)) ++l;
     i = t >> l;
 }
+// Those items in the order they are launched, highest level first: the first starts at knot 0, the last writes knot K.  Fills
+// lv[c], ix[c] and returns their count, at most L + 1 (arrays of ROLLOUT_MAX_PATH hold any K).
+constexpr int ROLLOUT_MAX_PATH = 64;
+RLP_HD inline int rollout_final_path(int L, int64_t K, int* lv, int64_t* ix) {
+    int cnt = 0;
+    for (int64_t t = K; t > 0; t = rollout_item(L, K, lv[cnt - 1], ix[cnt - 1]).start) { rollout_writer(L, t, lv[cnt], ix[cnt]); ++cnt; }
+    for (int a = 0, b = cnt - 1; a < b; ++a, --b) {
+        const int l = lv[a]; lv[a] = lv[b]; lv[b] = l;
+        const int64_t i = ix[a]; ix[a] = ix[b]; ix[b] = i;
+    }
+    return cnt;
+}
 
 // columns of the padded trajectory: whole 16-column tiles, whole 64-column tiles from 49 columns on (the descent's two column tiles)
 RLP_HD inline int rollout_col_pad(int n_cols) { return n_cols <= 48 ? (n_cols + 15) / 16 * 16 : (n_cols + 63) / 64 * 64; }

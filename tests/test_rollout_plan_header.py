@@ -1,6 +1,6 @@
 """csrc/dto_rollout_plan.h from plain C++: a stand-alone program is compiled with g++ (address and undefined-behaviour sanitizers on)
 against the header alone (no HIP, no engine header), run without a GPU, and prints for K = 1 .. 70 the leaf slots, the level offsets
-and lengths and the descent items.  The tree is then carried out in NumPy with those indices and nothing else, on random 5 x 5
+and lengths and the descent items, and for PATH_KS what rollout_final_path fills.  The tree is then carried out in NumPy with those indices and nothing else, on random 5 x 5
 matrices, and compared with the sequential product."""
 import os
 import shutil
@@ -12,6 +12,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "directtrajopt.jl_amd", "csrc")
 KS = list(range(1, 71))
+PATH_KS = list(range(1, 18)) + [31, 32, 33, 1023, 1024, 1025]   # every K in 1 .. 17, and 2^L, 2^L +- 1 for L = 5 and 10
 
 PROGRAM = r"""
 #include <cstdio>
@@ -38,6 +39,20 @@ int main() {
             rollout_writer(L, t, l, i);
             printf(" %d:%ld", l, (long)i);
             t = (long)rollout_item(L, K, l, i).start;
+        }
+        printf("\n");
+    }
+    // rollout_final_path: the same items in launch order, as (level:index:start:mid)
+    const long path_ks[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 31, 32, 33, 1023, 1024, 1025};
+    for (long K : path_ks) {
+        const int L = rollout_levels(K);
+        int lv[ROLLOUT_MAX_PATH];
+        int64_t ix[ROLLOUT_MAX_PATH];
+        const int cnt = rollout_final_path(L, K, lv, ix);
+        printf("path %ld %d %d", K, L, cnt);
+        for (int c = 0; c < cnt; ++c) {
+            const RolloutItem it = rollout_item(L, K, lv[c], ix[c]);
+            printf(" %d:%ld:%ld:%ld", lv[c], (long)ix[c], (long)it.start, (long)it.mid);
         }
         printf("\n");
     }
@@ -144,6 +159,44 @@ def test_the_final_state_needs_only_its_chain_of_items(output, K):
         assert live and start in F
         F[mid] = tree[node] @ F[start]
     assert np.array_equal(F[K], S[K])
+
+
+def _follow_start(K):
+    """the items from knot K back to knot 0 as (level, index, start, mid), from the header's opening comment alone: knot
+    t = 2^(l-1) (2 i + 1) is the midpoint of item (l, i), which starts at i 2^l; knot 2^L comes from the root's item (L + 1, 0)"""
+    L = max(K - 1, 0).bit_length()
+    items, t = [], K
+    while t > 0:
+        if t == 1 << L:
+            l, i, start = L + 1, 0, 0
+        else:
+            l = (t & -t).bit_length()
+            i = t >> l
+            start = i << l
+        items.append((l, i, start, t))
+        t = start
+    return L, items[::-1]
+
+
+@pytest.mark.parametrize("K", PATH_KS)
+def test_rollout_final_path_lists_the_chain_in_launch_order(output, K):
+    row = [l.split() for l in output if l.startswith("path %d " % K)][0]
+    L, cnt = int(row[2]), int(row[3])
+    path = [tuple(int(v) for v in c.split(":")) for c in row[4:]]
+    print(K, L, cnt, path)
+    L_ref, ref = _follow_start(K)
+    assert L == L_ref and cnt == len(path) and 1 <= cnt <= L + 1
+    assert path == ref
+    assert path[0][2] == 0 and path[-1][3] == K                   # the first item starts at knot 0, the last writes knot K
+    assert all(a[3] == b[2] for a, b in zip(path, path[1:]))      # each reads what the one before wrote
+    assert [l for l, *_ in path] == sorted({l for l, *_ in path}, reverse=True)   # highest level first, strictly falling
+
+
+def test_rollout_final_path_is_the_chain_the_writers_give(output):
+    """for the K the first program loop covers too: the reverse of the chain printed there"""
+    for K in [k for k in PATH_KS if k in KS]:
+        row = [l.split() for l in output if l.startswith("path %d " % K)][0]
+        assert [tuple(int(v) for v in c.split(":")[:2]) for c in row[4:]] == _plan(output, K)["chain"][::-1]
 
 
 def test_workspace_and_column_padding(output):
