@@ -91,6 +91,8 @@ inline bool is_elim_cat(int cat) { return cat == CAT_DYNSOLVE_COUPLE || cat == C
 // are made of count under their own names.
 // CAT_REDUCED_INPUT ("reduced_input"): with the option "reduced_input_store", the gather of the input blocks and the two products with
 // them (dto_reduced.hip); BYTES as executed; it feeds no other name either.
+// The block products (dto_eval_hessian_products, dto_projected_hessian_products) count under the same names -- "hess_product",
+// "reduced_pack", "reduced_input" -- one launch per chunk each, bytes as executed: the matrices once per tile or chunk, the vectors per column.
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
 inline void count_sweep_form(dto_handle* h, int form) {
     if (h->profiling) ++h->sweep_forms[form];
@@ -1664,7 +1666,8 @@ void build_hp_index(dto_handle* h) {
 
 // y = H(Z; sigma, mu) v.  At a new point: do_hessian into the private slab, one gather into the row-major copy; at the kept point
 // (hp_point: Z, sigma, mu) the product launch alone.
-void hess_product(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dv, double* dy, hipStream_t st) {
+// The Hessian point: the row-major copy at (Z, sigma, mu), rebuilt unless hp_point keeps it.
+void hess_point(dto_handle* h, const double* dZ, double sigma, const double* dmu, hipStream_t st) {
     build_hp_index(h);
     if (!at_kept_point(h, h->hp_point, st, dZ, sigma, dmu)) {
         if (!h->hp_slab) h->hp_slab = own(h, dalloc<double>((size_t)h->info.hess_len));
@@ -1676,9 +1679,20 @@ void hess_product(dto_handle* h, const double* dZ, double sigma, const double* d
         }
         keep_point(h, h->hp_point, st, dZ, sigma, dmu);
     }
+}
+void hess_product(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dv, double* dy, hipStream_t st) {
+    hess_point(h, dZ, sigma, dmu, st);
     // bytes: values and columns of every entry, and per row its start, length, id, v and y (v read once: it stays in cache)
     ProfScope ps(h, st, CAT_HESS_PRODUCT, 12.0 * (double)h->hp_nnz + 32.0 * (double)h->n_vars);
     launch_hess_spmv(st, h->hp, dv, dy);
+}
+// Y = H V for w columns AT the Hessian point (hess_point first): one launch.  Bytes: per tile of columns the values and columns of
+// every entry and the rows' start, length and id; per column v and y.
+void hess_product_block(dto_handle* h, const KHessBlock& B, const double* dV, double* dY, hipStream_t st) {
+    const int T = hess_block_tile(B.w);
+    const double tiles = (double)((B.w + T - 1) / T);
+    ProfScope ps(h, st, CAT_HESS_PRODUCT, tiles * (12.0 * (double)h->hp_nnz + 16.0 * (double)h->n_vars) + 16.0 * (double)h->n_vars * B.w);
+    launch_hess_spmm(st, h->hp, B, dV, dY);
 }
 
 void hess_product_applies(const dto_handle* h) {
@@ -2435,6 +2449,14 @@ static KRollout elim_rollout_args(const dto_handle* h, const ElimPlan& p, int i,
     return KRollout(h->integ_dim[i], elim_x_off(h, i), p.pre[i], n_cols, h->K);
 }
 
+// each block solve's own limit on n_cols: the smallest x_dim among the integrators with a propagator, 64 without one
+static int elim_column_cap(const dto_handle* h) {
+    int cap = 0;
+    for (size_t i = 0; i < h->integ_kind.size(); ++i)
+        if (elim_has_tree(h, (int)i)) cap = cap ? std::min(cap, h->integ_dim[i]) : h->integ_dim[i];
+    return cap ? cap : 64;
+}
+
 // What a whole-dynamics solve names: refused with text before anything is enqueued.
 static const ElimPlan& elim_args(dto_handle* h, int32_t direction, const double* B, int32_t n_cols) {
     const std::string who = "dto_dynamics_solve_all";
@@ -2444,10 +2466,7 @@ static const ElimPlan& elim_args(dto_handle* h, int32_t direction, const double*
     if (direction != DTO_SOLVE_FORWARD && direction != DTO_SOLVE_ADJOINT)
         throw HipError{who + ": direction takes DTO_SOLVE_FORWARD (0) or DTO_SOLVE_ADJOINT (1)"};
     if (!B) throw HipError{who + ": B = NULL (the right-hand side [N][n_cols][n_states] is required)"};
-    int cap = 0;   // each block solve's own limit: the smallest x_dim among the integrators with a propagator
-    for (size_t i = 0; i < h->integ_kind.size(); ++i)
-        if (elim_has_tree(h, (int)i)) cap = cap ? std::min(cap, h->integ_dim[i]) : h->integ_dim[i];
-    if (!cap) cap = 64;
+    const int cap = elim_column_cap(h);
     if (n_cols < 1 || n_cols > cap) throw HipError{who + ": n_cols = " + std::to_string(n_cols) + ", allowed 1 .. " + std::to_string(cap)};
     return p;
 }
@@ -2815,6 +2834,168 @@ int dto_reduced_hessian_product_dev(dto_handle* h, const double* dZ, double sigm
     }, G_ASYNC, (hipStream_t)stream);
 }
 
+// ---- block products: H V and T' H T V for n_cols vectors per call (include/dto_engine.h, "Block products").  Per column the
+// operations of the single products in their order, so the same bits; what a block saves is the re-reading of the matrices: the
+// Hessian copy once per tile of columns, the solves' node matrices and the input blocks once per chunk.
+
+static const int BLOCK_WIDTH_DEFAULT = 64;   // W_max (DESIGN 4.29 holds the table it was chosen from)
+
+static int block_width(const dto_handle* h, int cap) {
+    const int width = h->reduced_block_width > 0 ? h->reduced_block_width : BLOCK_WIDTH_DEFAULT;
+    return std::max(1, std::min(cap, width));
+}
+
+static void block_args(const std::string& who, int32_t n_cols, const double* Z, const double* V, double* Y) {
+    if (n_cols < 1) throw HipError{who + ": n_cols = " + std::to_string(n_cols) + ", at least 1 column is required"};
+    if (!Z || !V || !Y) throw HipError{who + ": Z, V and Y are required (NULL given)"};
+}
+
+// Y = H(Z; sigma, mu) V, V and Y [n_cols][n_vars] on the device: one point check, then one launch per chunk of W columns.
+static void hess_products(dto_handle* h, const double* dZ, double sigma, const double* dmu, int n_cols, const double* dV, double* dY,
+                          hipStream_t st) {
+    const int W = block_width(h, 64);
+    const int64_t nv = h->n_vars;
+    hess_point(h, dZ, sigma, dmu, st);
+    for (int c0 = 0; c0 < n_cols; c0 += W) {
+        const int w = std::min(W, n_cols - c0);
+        hess_product_block(h, KHessBlock{w, 1, nv, 1, nv}, dV + (size_t)c0 * nv, dY + (size_t)c0 * nv, st);
+    }
+}
+
+// the host-pointer forms' copies of V and Y, [n_cols][n_vars] each
+static double* block_host_buffers(dto_handle* h, int n_cols) { return grow_workspace(h, h->d_blk_host, 2 * (size_t)n_cols * (size_t)h->n_vars); }
+
+int dto_eval_hessian_products(dto_handle* h, const double* Z, double sigma, const double* mu, int32_t n_cols, const double* V, double* Y) {
+    return guarded(h, [&] {
+        hess_product_applies(h);
+        block_args("dto_eval_hessian_products", n_cols, Z, V, Y);
+        if (!mu && h->n_cons > 0) throw HipError{"dto_eval_hessian_products: mu = NULL (the multipliers [n_cons] are required)"};
+        const size_t n = (size_t)n_cols * (size_t)h->n_vars;
+        double* dV = block_host_buffers(h, n_cols);
+        upload_Z(h, Z);
+        if (h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->d_mu, mu, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(dV, V, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+        hess_products(h, h->d_Z, sigma, h->d_mu, n_cols, dV, dV + n, h->stream);
+        HIP_CHECK(hipMemcpyAsync(Y, dV + n, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_eval_hessian_products_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, int32_t n_cols, const double* dV, double* dY,
+                                  void* stream) {
+    return guarded(h, [&] {
+        hess_product_applies(h);
+        block_args("dto_eval_hessian_products_dev", n_cols, dZ, dV, dY);
+        hess_products(h, dZ, sigma, dmu, n_cols, dV, dY, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
+// one chunk's vectors inside d_blk
+struct BlockWork { double *s1, *s2, *zh, *q, *rows; };
+
+// Every workspace of a projected block call, before anything is enqueued: d_blk for chunks of W columns (rows only off the store route)
+// and, through elim_point below, what the solves grow for n_cols = W.
+static BlockWork block_workspaces(dto_handle* h, const ElimPlan& p, int W, bool store_route) {
+    const size_t nv = (size_t)h->n_vars, nc = (size_t)std::max<int64_t>(h->n_cons, 1), nd = (size_t)h->N * p.n_states;
+    double* q = grow_workspace(h, h->d_blk, (size_t)W * (2 * nd + 2 * nv + (store_route ? 0 : nc)));
+    BlockWork B{};
+    B.s1 = q; q += W * nd;
+    B.s2 = q; q += W * nd;
+    B.zh = q; q += W * nv;
+    B.q = q; q += W * nv;
+    B.rows = store_route ? nullptr : q;
+    return B;
+}
+
+// columns per chunk of a projected block call: W = min(the solves' limit, the option or W_max), and no more than the call has
+static int projected_width(const dto_handle* h, int n_cols) { return std::min(block_width(h, elim_column_cap(h)), n_cols); }
+
+// Y = T' H(Z; sigma, mu~) T V, V and Y [n_cols][n_vars] on the device.  The three point checks (reduced point, solves' point, Hessian
+// point) once; then per chunk of w <= W columns the steps of reduced_hessian_product in block form.
+static void projected_hessian_products(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, int n_cols,
+                                       const double* dV, double* dY, hipStream_t st) {
+    const KReduced& R = h->red;
+    const int W = projected_width(h, n_cols);
+    const bool store_route = h->reduced_input_store && h->K >= 1;
+    const BlockWork B = block_workspaces(h, p, W, store_route);
+    const int64_t nvars = h->n_vars, ncons = h->n_cons;
+    ElimWork EW{};
+    // the solves' workspaces for W columns first (a failed allocation is refused before anything is enqueued); at a new Z the rebuild
+    // the single product would run at its first solve (on the store route: before its first kernel) runs here
+    reduced_point(h, p, dZ, sigma, dmu, st);
+    if (h->K >= 1) EW = elim_point(h, p, dZ, W, st);
+    hess_point(h, dZ, sigma, h->red_mut, st);
+    auto solve = [&](int adjoint, int w) {
+        if (h->K < 1) {   // a single knot: the block is the identity
+            ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
+            HIP_CHECK(hipMemcpyAsync(B.s2, B.s1, sizeof(double) * (size_t)w * p.n_states, hipMemcpyDeviceToDevice, st));
+            return;
+        }
+        elim_solve(h, p, EW, adjoint, B.s1, w, B.s2, st);
+    };
+    for (int c0 = 0; c0 < n_cols; c0 += W) {
+        const int w = std::min(W, n_cols - c0);
+        const double* v = dV + (size_t)c0 * nvars;
+        double* y = dY + (size_t)c0 * nvars;
+        const double nv = 8.0 * (double)nvars * w, nc = 8.0 * (double)ncons * w, nd = 8.0 * (double)h->N * R.D * w;
+        const KHessBlock HB{w, 1, nvars, 1, nvars};   // z^ and q as planes [w][n_vars], like V and Y (faster than interleaved)
+        if (store_route) {
+            {   // bytes: the store once, per column the free inputs of v and B
+                ProfScope ps(h, st, CAT_REDUCED_INPUT, 8.0 * (double)h->input->store_off.back() + 8.0 * (double)h->N * w * (h->in.n_read + 2.0 * R.D));
+                launch_red_input_forward_block(st, R, h->in, w, h->d_in_store.p, v, B.s1);
+            }
+            solve(0, w);                                                                                   // MM Y = B
+            { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_zhat_block(st, R, w, v, B.s2, B.zh); }
+            hess_product_block(h, HB, B.zh, B.q, st);                                                      // q = H(mu~) z^
+            { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nd); launch_red_gather_block(st, R, w, B.q, B.s1); }
+            solve(1, w);                                                                                   // MM' Gam = q_S
+            // bytes: the store once, per column q, Gam and y
+            ProfScope ps(h, st, CAT_REDUCED_INPUT, 8.0 * (double)h->input->store_off.back() + 2.0 * nv + nd);
+            launch_red_input_transposed_block(st, R, h->in, w, h->d_in_store.p, B.q, B.s2, y);
+            continue;
+        }
+        // z^'s buffer holds v^ and later t, rows holds rho and later w: planes, since J v^ and J' w take one column at a time
+        { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_vhat_block(st, R, w, v, B.zh); }
+        for (int j = 0; j < w; ++j) jac_product(h, dZ, B.zh + (size_t)j * nvars, B.rows + (size_t)j * ncons, 0, st);   // rho = J v^
+        { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nd); launch_red_rhs_block(st, R, w, v, B.rows, B.s1); }
+        solve(0, w);                                                                                       // MM Y = B
+        { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_zhat_block(st, R, w, v, B.s2, B.zh); }
+        hess_product_block(h, HB, B.zh, B.q, st);                                                          // q = H(mu~) z^
+        { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nd); launch_red_gather_block(st, R, w, B.q, B.s1); }
+        solve(1, w);                                                                                       // MM' Gam = q_S
+        { ProfScope ps(h, st, CAT_REDUCED_PACK, nd + nc); launch_red_multipliers_block(st, R, w, B.s2, B.rows); }
+        for (int j = 0; j < w; ++j) jac_product(h, dZ, B.rows + (size_t)j * ncons, B.zh + (size_t)j * nvars, 1, st);   // t = J' w
+        { ProfScope ps(h, st, CAT_REDUCED_PACK, 3.0 * nv); launch_red_finish_block(st, R, w, B.q, B.zh, B.s2, y); }
+    }
+}
+
+int dto_projected_hessian_products(dto_handle* h, const double* Z, double sigma, const double* mu, int32_t n_cols, const double* V, double* Y) {
+    return guarded(h, [&] {
+        const std::string who = "dto_projected_hessian_products";
+        const ElimPlan& p = reduced_args(h, who, true);
+        block_args(who, n_cols, Z, V, Y);
+        reduced_workspaces(h, p);
+        const size_t n = (size_t)n_cols * (size_t)h->n_vars;
+        double* dV = block_host_buffers(h, n_cols);
+        block_workspaces(h, p, projected_width(h, n_cols), h->reduced_input_store && h->K >= 1);   // before the uploads are enqueued
+        upload_Z(h, Z);
+        if (mu && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->red_hmu, mu, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(dV, V, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+        projected_hessian_products(h, p, h->d_Z, sigma, mu ? h->red_hmu : nullptr, n_cols, dV, dV + n, h->stream);
+        HIP_CHECK(hipMemcpyAsync(Y, dV + n, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_projected_hessian_products_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, int32_t n_cols, const double* dV,
+                                       double* dY, void* stream) {
+    return guarded(h, [&] {
+        const std::string who = "dto_projected_hessian_products_dev";
+        const ElimPlan& p = reduced_args(h, who, true);
+        block_args(who, n_cols, dZ, dV, dY);
+        reduced_workspaces(h, p);
+        projected_hessian_products(h, p, dZ, sigma, dmu, n_cols, dV, dY, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
 // ---- multi-GPU: ranges, gather plans, collectives (dto_comm.h)
 int dto_comm_unique_id(void* id128) {
     if (!id128) return fail(nullptr, "dto_comm_unique_id: null argument");
@@ -2994,6 +3175,12 @@ int dto_set_option(dto_handle* h, const char* name, int64_t value) {
         if (value != 0 && value != 1)
             return fail(h, "dto_set_option: reduced_input_store takes 0 (J v^ and J' w of the reduced-space operators through dto_eval_jacobian_product / _transpose_product) or 1 (from the kept input blocks)");
         h->reduced_input_store = (int)value;
+        return 0;
+    }
+    if (std::string(name) == "reduced_block_width") {
+        if (value < 0 || value > 64)
+            return fail(h, "dto_set_option: reduced_block_width takes 0 (the engine's choice) or 1 .. 64, the most columns per chunk of dto_eval_hessian_products / dto_projected_hessian_products");
+        h->reduced_block_width = (int)value;
         return 0;
     }
     if (std::string(name) == "tdb_share_members") {

@@ -325,6 +325,11 @@ struct dto_handle {
     std::unique_ptr<dto::InputPlan> input;
     dto::KInput in{};              // device tables
     dto::Workspace d_in_store;
+    // block products (dto_eval_hessian_products[_dev], dto_projected_hessian_products[_dev]): option "reduced_block_width" caps the
+    // columns per chunk (0: the engine's choice).  d_blk: one chunk's B, Y [N][W][D], z^ and q [W][n_vars] and, off the store route,
+    // rho / w [W][n_cons]; d_blk_host: the host-pointer forms' V and Y.  Both grow-only, sized before anything is enqueued.
+    int reduced_block_width = 0;
+    dto::Workspace d_blk, d_blk_host;
     int64_t* d_conbase = nullptr;       // [n_vars+1] first constraint-pattern entry of each column
     int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
     int64_t* d_crow_col = nullptr;

@@ -499,6 +499,15 @@ void launch_red_rhs(hipStream_t st, const KReduced& R, const double* v, const do
 void launch_red_zhat(hipStream_t st, const KReduced& R, const double* v, const double* Y, double* zh);                 // states <- Y
 void launch_red_gather(hipStream_t st, const KReduced& R, const double* q, double* qS);                                // states of q
 void launch_red_finish(hipStream_t st, const KReduced& R, const double* q, const double* t, const double* lam, double* y);
+// Block forms for w columns (dto_projected_hessian_products[_dev]).  Two layouts: PLANES [w][n] (column j at j * n: the caller's V and
+// Y, z^, q and the vectors J v^ and J' w take one at a time) and the solves' [N][w][D].  One thread per output entry, the arithmetic
+// of the single forms.
+void launch_red_vhat_block(hipStream_t st, const KReduced& R, int w, const double* v, double* vh);                      // planes -> planes
+void launch_red_rhs_block(hipStream_t st, const KReduced& R, int w, const double* v, const double* rho, double* B);     // planes, planes [w][n_cons] -> [N][w][D]
+void launch_red_zhat_block(hipStream_t st, const KReduced& R, int w, const double* v, const double* Y, double* zh);     // planes, [N][w][D] -> planes
+void launch_red_gather_block(hipStream_t st, const KReduced& R, int w, const double* q, double* qS);                    // planes -> [N][w][D]
+void launch_red_multipliers_block(hipStream_t st, const KReduced& R, int w, const double* lam, double* wv);             // [N][w][D] -> planes [w][n_cons]
+void launch_red_finish_block(hipStream_t st, const KReduced& R, int w, const double* q, const double* t, const double* lam, double* y);  // planes, planes, [N][w][D] -> planes
 
 // Input-block store of the reduced-space operators (option "reduced_input_store"; dto_reduced.hip; plan and layout: dto_input_plan.h).
 struct KInputInt {   // one integrator: its store F_a [K][2][wf][n] and its free inputs fin[fin0 .. fin0 + wf)
@@ -526,6 +535,10 @@ void launch_red_input_forward(hipStream_t st, const KReduced& R, const KInput& I
 // y [n_vars]: q - F' Gam on the read components, q on the unread ones and the globals, Gam_0 on the states of knot 0, 0 on the dependent entries
 void launch_red_input_transposed(hipStream_t st, const KReduced& R, const KInput& In, const double* store, const double* q, const double* gam,
                                  double* y);
+// the two products for w columns: v, q and y PLANES, B and gam [N][w][D]; per column the sums of the single forms in their order
+void launch_red_input_forward_block(hipStream_t st, const KReduced& R, const KInput& In, int w, const double* store, const double* v, double* B);
+void launch_red_input_transposed_block(hipStream_t st, const KReduced& R, const KInput& In, int w, const double* store, const double* q,
+                                       const double* gam, double* y);
 
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);
@@ -571,6 +584,14 @@ struct KHessProduct {
 // val[i] = slab[pos[i]] (pos -1: padding, written as 0)
 void launch_hess_gather(hipStream_t st, const double* slab, const int64_t* pos, int64_t n, double* val);
 void launch_hess_spmv(hipStream_t st, const KHessProduct& p, const double* v, double* y);
+// Y = H V for w columns in one launch: entry (i, j) of V at v[i * v_es + j * v_cs], of Y at y[i * y_es + j * y_cs].  Column j of Y has
+// the bits of launch_hess_spmv on column j of V.  The kernel is instantiated for tiles of 1, 2, 4 and 8 columns per lane.
+struct KHessBlock {
+    int32_t w;
+    int64_t v_es, v_cs, y_es, y_cs;
+};
+inline int hess_block_tile(int w) { return w >= 5 ? 8 : w >= 3 ? 4 : w == 2 ? 2 : 1; }
+void launch_hess_spmm(hipStream_t st, const KHessProduct& p, const KHessBlock& B, const double* v, double* y);
 
 // Powers of A_k from the generator subspace: A_k = dt*sum_j ubar_j G_j lives in an (m+1)-dimensional
 // matrix space, so A_k^r = sum over multisets alpha of size r of (dt^r prod ubar_alpha) * S_alpha with

@@ -388,6 +388,25 @@ class Evaluator:
         self._stage_external(Z, con_need=2, obj_need=2 if sigma != 0.0 else -1, mu=mu)
         self._check(self._lib.dto_eval_hessian_product(self._h, _dp(Z), float(sigma), _dp(mu), _dp(v), _out(y, self.n_variables, "y")))
 
+    @staticmethod
+    def _columns(V, n, what):
+        """V as a C-contiguous (n_cols, n) float64 array"""
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        if V.ndim != 2 or V.shape[1] != n:
+            raise ValueError(f"{what}: shape {V.shape}, expected (n_cols, {n})")
+        return V
+
+    def eval_hessian_lagrangian_products(self, Y, Z, V, sigma, mu):
+        """Y[c] = H(Z; sigma, mu) V[c] for every row of V (``dto_eval_hessian_products``): ``V`` and ``Y`` are (n_cols, n_variables),
+        row c one vector.  Bit for bit ``eval_hessian_lagrangian_product`` of every row, at the same kept point; the Hessian copy is
+        read once per tile of columns instead of once per vector (one launch per chunk of ``reduced_block_width`` columns)."""
+        Z = self._Z(Z)
+        mu = _in(mu, self.n_constraints, "mu")
+        V = self._columns(V, self.n_variables, "V")
+        self._stage_external(Z, con_need=2, obj_need=2 if sigma != 0.0 else -1, mu=mu)
+        self._check(self._lib.dto_eval_hessian_products(self._h, _dp(Z), float(sigma), _dp(mu), V.shape[0], _dp(V),
+                                                        _out(Y, V.size, "Y")))
+
     def eval_constraint_jacobian_product(self, y, Z, w):  # evaluator.jl:406 (y = J w)
         Z = self._Z(Z)
         w = _in(w, self.n_variables, "w")
@@ -600,6 +619,46 @@ class Evaluator:
         self._check(self._lib.dto_reduced_hessian_product(self._h, _dp(Z), float(sigma), None if mu is None else _dp(mu), _dp(v), _dp(y)))
         return y
 
+    def reduced_hessian_products(self, Z, V, sigma=1.0, mu=None):
+        """Y[c] = T' H(Z; sigma, mu~) T V[c] for every row of V on the device (``dto_projected_hessian_products``): ``V`` is
+        (n_cols, n_variables), its entries at the states of knots 2 .. N are not read; returns (n_cols, n_variables), zero at those
+        entries.  Bit for bit ``reduced_hessian_product`` of every row with the same ``reduced_input_store`` setting, at the same
+        kept points.  The columns run in chunks (``reduced_block_width``; at most the column limit of ``dynamics_solve_all``): per
+        chunk the solves' node matrices, the input blocks and the Hessian copy are read once, not once per vector.  With
+        ``reduced_input_store`` = 0, J v^ and J' w still run once per column."""
+        Z = self._Z(Z)
+        V = self._columns(V, self.n_variables, "V")
+        if mu is not None:
+            mu = _in(mu, self.n_constraints, "mu")
+        Y = np.full(V.shape, np.nan)
+        self._check(self._lib.dto_projected_hessian_products(self._h, _dp(Z), float(sigma), None if mu is None else _dp(mu), V.shape[0],
+                                                             _dp(V), _dp(Y)))
+        return Y
+
+    def independent_entries(self):
+        """C: the entries of Z that are no state of a knot 2 .. N (controls, timesteps, times, the states of knot 1, globals),
+        ascending, 0-based -- the variables of the reduced problem."""
+        N, dim = self.trajectory.N, self.trajectory.dim
+        free = np.ones(self.n_variables, dtype=bool)
+        fk = free[:N * dim].reshape(N, dim)
+        for it in self._integrator_list:
+            fk[1:, it.x_off:it.x_off + it.x_dim] = False
+        return np.flatnonzero(free)
+
+    def reduced_hessian_matrix(self, Z, sigma=1.0, mu=None, block=64):
+        """The dense reduced Hessian T' H(Z; sigma, mu~) T on the independent entries: returns (Hr, C), Hr (|C|, |C|) and C =
+        ``independent_entries()``; column i of Hr is the product with the unit vector of entry C[i], ``block`` unit vectors per
+        ``reduced_hessian_products`` call.  For control spaces of a few hundred entries (a direct Newton step, a preconditioner)."""
+        Cidx = self.independent_entries()
+        nC = Cidx.size
+        Hr = np.empty((nC, nC))
+        for i0 in range(0, nC, block):
+            i1 = min(nC, i0 + block)
+            V = np.zeros((i1 - i0, self.n_variables))
+            V[np.arange(i1 - i0), Cidx[i0:i1]] = 1.0
+            Hr[:, i0:i1] = self.reduced_hessian_products(Z, V, sigma, mu)[:, Cidx].T
+        return Hr, Cidx
+
     def constraint_bounds(self):  # get_nonlinear_constraints, src/solvers/solve.jl:30-65
         lo = np.empty(self.n_constraints)
         hi = np.empty(self.n_constraints)
@@ -638,6 +697,12 @@ class Evaluator:
     def eval_hessian_product_dev(self, dZ, sigma, dmu, dv, dy, stream=0, Z_host=None, mu_host=None):
         self._stage_external(Z_host, con_need=2, obj_need=2 if sigma != 0.0 else -1, mu=mu_host)
         self._check(self._lib.dto_eval_hessian_product_dev(self._h, dZ, float(sigma), dmu, dv, dy, stream))
+
+    def eval_hessian_products_dev(self, dZ, sigma, dmu, n_cols, dV, dY, stream=0, Z_host=None, mu_host=None):
+        """``eval_hessian_lagrangian_products`` on device pointers: dV and dY (n_cols, n_variables), not overlapping; enqueued on
+        `stream`, errors deferred as for every `_dev` call.  Same bits as the host form."""
+        self._stage_external(Z_host, con_need=2, obj_need=2 if sigma != 0.0 else -1, mu=mu_host)
+        self._check(self._lib.dto_eval_hessian_products_dev(self._h, dZ, float(sigma), dmu or None, int(n_cols), dV or None, dY or None, stream))
 
     def eval_jacobian_product_dev(self, dZ, dw, dy, stream=0, Z_host=None):  # y = J w, dw [n_variables], dy [n_constraints]
         self._stage_external(Z_host, con_need=1)
@@ -678,6 +743,13 @@ class Evaluator:
         """``reduced_hessian_product`` on device pointers: dmu (n_constraints) or 0 / None for zeros, dv and dy (n_variables), not
         overlapping; enqueued on `stream`, errors deferred as for every `_dev` call.  Same bits as the host form."""
         self._check(self._lib.dto_reduced_hessian_product_dev(self._h, dZ, float(sigma), dmu or None, dv or None, dy or None, stream))
+
+    def reduced_hessian_products_dev(self, dZ, sigma, dmu, n_cols, dV, dY, stream=0):
+        """``reduced_hessian_products`` on device pointers: dmu (n_constraints) or 0 / None for zeros, dV and dY
+        (n_cols, n_variables), not overlapping; enqueued on `stream`, errors deferred as for every `_dev` call.  Same bits as the host
+        form."""
+        self._check(self._lib.dto_projected_hessian_products_dev(self._h, dZ, float(sigma), dmu or None, int(n_cols), dV or None,
+                                                                 dY or None, stream))
 
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod
@@ -744,7 +816,9 @@ class Evaluator:
         k_tdb_mfma / k_tdb_kron launches and of their product forms, 0 = the default grid; for tests and measurements, the results do not depend on it),
         ``reduced_input_store`` (0 | 1, default 0: 1 makes ``reduced_lagrangian_gradient`` / ``reduced_hessian_product`` and their
         ``_dev`` forms take J v^ and J' w from the input blocks kept with ``dynamics_solve_all``'s point -- two small launches instead
-        of a J w and a J' w per product; another summation order, so values agree with the default route to rounding, not in bits);
+        of a J w and a J' w per product; another summation order, so values agree with the default route to rounding, not in bits),
+        ``reduced_block_width`` (0 = the engine's choice, or 1 .. 64: the most columns per chunk of ``eval_hessian_lagrangian_products``
+        / ``reduced_hessian_products`` and their ``_dev`` forms; for tests and measurements, the results do not depend on it);
         include/dto_engine.h lists every option."""
         self._check(self._lib.dto_set_option(self._h, name.encode(), int(value)))
 

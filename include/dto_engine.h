@@ -520,6 +520,42 @@ int dto_reduced_gradient_dev(dto_handle* h, const double* dZ, double sigma, cons
 int dto_reduced_hessian_product(dto_handle* h, const double* Z, double sigma, const double* mu, const double* v, double* y);
 int dto_reduced_hessian_product_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dv, double* dy, void* stream);
 
+/* ---- Block products: H V and T' H T V for n_cols vectors per call.  A block-Krylov method, a randomised preconditioner, several
+ * Hessian probes or the explicit reduced Hessian of a small control space ask for many products at ONE point; the single products
+ * read the Hessian copy, the solves' node matrices and the input blocks once per vector, these read them once per tile or chunk.
+ *   dto_eval_hessian_products        column c of Y is H(Z; sigma, mu) V_c            (dto_eval_hessian_product for every column)
+ *   dto_projected_hessian_products   column c of Y is T' H(Z; sigma, mu~) T V_c      (dto_reduced_hessian_product for every column)
+ * Layout.  V and Y are [n_cols][n_vars]: column c contiguous at offset c n_vars.  They must not overlap.  n_cols >= 1, no upper limit.
+ * Bit contract.  Column c of Y is, bit for bit, what the single product returns for V_c on the same handle -- for the projected
+ * product with the same "reduced_input_store" setting.  Per column every kernel runs the single form's operations in the single form's
+ * order (the H product: a lane's pairs l, l + G, .. then the butterfly; the input-block products: the orders stated above), and the
+ * whole-dynamics solves return a column's bits alone or among others.  The results do not depend on n_cols, on the chunk width, on
+ * the entry-point family, or on whether the point was kept or rebuilt.  The S entries of V are not read (a NaN there reaches nothing);
+ * Y is 0 on S.
+ * Chunking.  The engine works through the columns in chunks of W = min(cap, width): cap is dto_dynamics_solve_all's limit on n_cols
+ * (the smallest x_dim among the integrators with a propagator, 64 without one; it does not apply to dto_eval_hessian_products), width
+ * the option "reduced_block_width" (1 .. 64) or, with its default 0, the engine's choice (64).  Inside a chunk the H product and the
+ * transposed input-block product hold tiles of 1, 2, 4 or 8 columns in registers.
+ * Points.  dto_eval_hessian_products uses dto_eval_hessian_product's kept point: ONE point check per call, at the kept point no
+ * assembly and one launch per chunk.  dto_projected_hessian_products uses the reduced point, the solves' point and the Hessian point
+ * under the cache rule above, each checked ONCE per call (three 4-byte readbacks per call, not per chunk or column); a block call
+ * after a single product at the same point, or the other way round, computes no new point.
+ * Costs per chunk at the kept point, "reduced_input_store" = 1: two products with the store (its bytes twice), two whole-dynamics scans
+ * of w columns, one block H product and two packer launches -- the launches of ONE single product; no Jacobian evaluation.  With 0 the
+ * six packers run in block form and J v^ and J' w stay dto_eval_jacobian_product / _transpose_product, called once per column: on
+ * handles whose products take the slab route this evaluates the Jacobian 2 n_cols times per call -- use the store route there.
+ * Workspaces, grow-only and allocated before anything is enqueued: one block of W (2 n_vars + 2 N D) doubles (W n_cons more with
+ * "reduced_input_store" = 0), what dto_dynamics_solve_all grows for n_cols = W, and for the host-pointer forms 2 n_cols n_vars doubles.
+ * The single products' block and entry points are untouched.
+ * Refused with text, the handle stays usable and nothing is enqueued: what the single product refuses; n_cols < 1; V or Y = NULL; a
+ * failed workspace allocation.  The host-pointer forms upload V, run the device routine on the handle's stream, download Y and block;
+ * both families return the same bits.  The _dev forms take device pointers, enqueue on `stream` and defer device-side errors like
+ * every _dev call. */
+int dto_eval_hessian_products(dto_handle* h, const double* Z, double sigma, const double* mu, int32_t n_cols, const double* V, double* Y);
+int dto_eval_hessian_products_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, int32_t n_cols, const double* dV, double* dY, void* stream);
+int dto_projected_hessian_products(dto_handle* h, const double* Z, double sigma, const double* mu, int32_t n_cols, const double* V, double* Y);
+int dto_projected_hessian_products_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, int32_t n_cols, const double* dV, double* dY, void* stream);
+
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
  * communicator (SURVEY.md §8b "Ownership").  No callback needs a collective: every rank's Jacobian / Hessian / gradient
@@ -637,6 +673,9 @@ int dto_bind_output_dev(dto_handle* h, int32_t vector, double* dptr);
  *   "reduced_input_store" (default 0): 1 makes dto_reduced_gradient / dto_reduced_hessian_product (and their _dev forms) take their
  *   J v^ and J' w from input blocks kept with dto_dynamics_solve_all's point ("Reduced-space operators" above states the store, the
  *   summation orders and the costs).  0 leaves every call as it was; values other than 0 and 1 are refused.
+ *   "reduced_block_width" (default 0 = the engine's choice, 64): 1 .. 64 caps the columns per chunk of dto_eval_hessian_products /
+ *   dto_projected_hessian_products and their _dev forms ("Block products" above); other values are refused.  For tests, which then
+ *   exercise the chunk loop on small blocks, and for measurements.  The results do not depend on it, bit for bit.
  *   "debug_bad_launch": TUNING builds only (libdto_engine_t.so) -- 1 gives the next callbacks' kernels an invalid launch
  *   configuration, which must come back as a non-zero return code with text (test of the error convention); the product
  *   library refuses the name. */
@@ -685,6 +724,8 @@ int dto_profile_reset(dto_handle* h);
  * BYTES as executed; it feeds no other name, "all" included, and the routines the operators are made of count under their own names),
  * "reduced_input" (option "reduced_input_store": the gather of the input blocks at a rebuilt point, one launch per integrator with free
  * inputs, and the two products with them, one launch each -- third output: BYTES as executed; it feeds no other name, "all" included).
+ * The block products count under "hess_product", "reduced_pack" and "reduced_input" too, one launch per chunk where a single product
+ * has one, with bytes as executed: matrix bytes once per tile or chunk, vector bytes per column.
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the
  * third output is the launches' algorithmic BYTES (what they must read and write), not FLOPs.
  * "hess_product_setup" returns the host milliseconds of the products' index build (once per handle), 0 launches, and the device

@@ -822,6 +822,61 @@ function reduced_hessian_product_dev!(ev::GPUEvaluator, dy::Ptr{Float64}, dZ::Pt
                                                          dy::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 end
 
+# ---- block products (include/dto_engine.h, "Block products"): many vectors per call ---------------------------------------------------
+# `V` is n_variables x n_cols (a column per vector: the engine's [n_cols][n_variables]); the result has the same shape, sized from the
+# handle.  Column c is, bit for bit, the single product of column c; the engine reads the Hessian copy, the solves' node matrices and
+# the input blocks once per chunk of columns (`set_option!(ev, "reduced_block_width", w)` caps the chunk, 0 = the engine's choice).
+function block_check_lengths(ev::GPUEvaluator, who::String, Z, μ, V)
+    reduced_check_lengths(ev, who, Z, μ)
+    size(V, 1) == ev.n_variables || error("$who: V has $(size(V, 1)) rows, the problem has $(ev.n_variables) variables")
+    size(V, 2) >= 1 || error("$who: V has no column")
+    return nothing
+end
+
+# Y[:, c] = H(Z; σ, μ) V[:, c]
+function eval_hessian_lagrangian_products(ev::GPUEvaluator, Z::AbstractVector{Float64}, V::AbstractMatrix{Float64}, σ::Float64,
+                                          μ::AbstractVector{Float64})
+    block_check_lengths(ev, "eval_hessian_lagrangian_products", Z, μ, V)
+    stage_external!(ev, Z; con_need = 2, obj_need = σ != 0 ? 2 : -1, μ = μ)
+    Zv, Vm, μv = Vector{Float64}(Z), Matrix{Float64}(V), Vector{Float64}(μ)
+    Y = fill(NaN, ev.n_variables, size(Vm, 2))
+    nc = Int32(size(Vm, 2))
+    GC.@preserve Y Zv Vm μv check(ev, @ccall lib.dto_eval_hessian_products(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μv::Ptr{Float64},
+                                                                          nc::Int32, Vm::Ptr{Float64}, Y::Ptr{Float64})::Cint)
+    return Y
+end
+
+# Y[:, c] = T' H(Z; σ, μ~) T V[:, c]: the rows of `V` at the states of knots 2 .. N are not read, those of the result are zero
+function reduced_hessian_products(ev::GPUEvaluator, Z::AbstractVector{Float64}, V::AbstractMatrix{Float64}; σ::Float64 = 1.0,
+                                  μ::Union{Nothing,AbstractVector{Float64}} = nothing)
+    block_check_lengths(ev, "reduced_hessian_products", Z, μ, V)
+    Zv, Vm = Vector{Float64}(Z), Matrix{Float64}(V)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    Y = fill(NaN, ev.n_variables, size(Vm, 2))
+    nc = Int32(size(Vm, 2))
+    GC.@preserve Y Zv Vm μv begin
+        μp = μ === nothing ? Ptr{Float64}(C_NULL) : pointer(μv)
+        check(ev, @ccall lib.dto_projected_hessian_products(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μp::Ptr{Float64}, nc::Int32,
+                                                            Vm::Ptr{Float64}, Y::Ptr{Float64})::Cint)
+    end
+    return Y
+end
+
+# the same on device pointers ([n_cols][n_variables] each, not overlapping), enqueued on `stream`; dμ of the projected form may be C_NULL
+function eval_hessian_products_dev!(ev::GPUEvaluator, dY::Ptr{Float64}, dZ::Ptr{Float64}, dV::Ptr{Float64}, n_cols::Integer, σ::Float64,
+                                    dμ::Ptr{Float64}, stream::Ptr{Cvoid})
+    nc = Int32(n_cols)
+    check(ev, @ccall lib.dto_eval_hessian_products_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, nc::Int32,
+                                                       dV::Ptr{Float64}, dY::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
+function reduced_hessian_products_dev!(ev::GPUEvaluator, dY::Ptr{Float64}, dZ::Ptr{Float64}, dV::Ptr{Float64}, n_cols::Integer, σ::Float64,
+                                       dμ::Ptr{Float64}, stream::Ptr{Cvoid})
+    nc = Int32(n_cols)
+    check(ev, @ccall lib.dto_projected_hessian_products_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, nc::Int32,
+                                                            dV::Ptr{Float64}, dY::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
 # row bounds handed to the solver (src/solvers/solve.jl:30-65)
 function constraint_bounds(ev::GPUEvaluator)
     lo = Vector{Float64}(undef, ev.n_constraints)
@@ -988,6 +1043,7 @@ end
 # dto_set_option (include/dto_engine.h lists the names), e.g. set_option!(ev, "tdb_matrix_free_products", 1): J w / J' w of device
 # TimeDependentBilinearIntegrators (dense or structured path) without a value slab; set_option!(ev, "reduced_input_store", 1):
 # reduced_gradient / reduced_hessian_product take J v^ and J' w from the input blocks kept with the whole-dynamics solves' point
+# set_option!(ev, "reduced_block_width", 8): at most 8 columns per chunk of the block products (0 = the engine's choice)
 function set_option!(ev::GPUEvaluator, name::AbstractString, value::Integer)
     v64 = Int64(value)
     check(ev, @ccall lib.dto_set_option(ev.handle::Ptr{Cvoid}, name::Cstring, v64::Int64)::Cint)

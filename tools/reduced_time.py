@@ -21,9 +21,15 @@ the constraint rows; every figure after a warm-up of at least 30 ms of GPU work,
         largest difference between the routes' results.
 
 One JSON line per shape, and a second one ({"routes": ...}) for the routes; ``--routes only`` prints the second alone.
+``--block`` instead times the BLOCK products at the kept point, both routes in one process: for n_cols in 1, 4, 16, 64 and chunk widths
+(option "reduced_block_width") 16, 32, 64 one reduced_hessian_products_dev call against a loop of n_cols reduced_hessian_product_dev
+calls -- the single path is the yardstick -- the two ALTERNATING, medians of ``--reps``; the same for eval_hessian_products_dev against
+eval_hessian_product_dev; and on the store route the per-name profile of one block of 16 and of one single product with
+"overlap_sweep" = 0.  One JSON line ({"block": ...}) per shape.
 
     python tools/reduced_time.py                       # 256 x 2000 and 64 x 1000, host-vector gradient at 64 x 1000
     python tools/reduced_time.py --shapes 128x1000 --reps 9
+    python tools/reduced_time.py --block
 """
 import argparse
 import json
@@ -275,6 +281,84 @@ def measure_routes(n, N, drives, scale, reps):
             ev.close()
 
 
+BLOCK_COLS = (1, 4, 16, 64)
+BLOCK_WIDTHS = (16, 32, 64)
+BLOCK_PARTS = ("reduced_input", "reduced_pack", "hess_product", "dynsolve_scan", "dynsolve_couple", "dynsolve_deriv", "jac_product", "expmv")
+
+
+def measure_block(n, N, drives, scale, reps):
+    """--block: the block products against loops of single products at the kept point, both routes in one process"""
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    prob = dto_amd.host.synthetic.multi_ket_problem(n, 1, drives, N, seed=42, u_bound=4.0, scale=scale or None)
+    routes = ("default", "reduced_input_store")
+    evs = [dto_amd.Evaluator(prob), dto_amd.Evaluator(prob)]
+    out = {"n": n, "knots": N, "drives": drives, "scale": scale, "reps": reps, "sigma": SIGMA, "n_cols": list(BLOCK_COLS), "widths": list(BLOCK_WIDTHS)}
+    try:
+        evs[1].set_option("reduced_input_store", 1)
+        nv = evs[0].n_variables
+        Z = torch.from_numpy(np.ascontiguousarray(prob.trajectory.vec(), dtype=np.float64)).to(dev)
+        gen = torch.Generator(device=dev); gen.manual_seed(7)
+        mu = torch.randn(evs[0].n_constraints, dtype=torch.float64, device=dev, generator=gen)
+        V = torch.randn(max(BLOCK_COLS), nv, dtype=torch.float64, device=dev, generator=gen)
+        Y = torch.full((max(BLOCK_COLS), nv), float("nan"), dtype=torch.float64, device=dev)
+        Y1 = torch.full((max(BLOCK_COLS), nv), float("nan"), dtype=torch.float64, device=dev)
+        out["n_variables"] = nv
+        for ev, route in zip(evs, routes):
+            def block(k, ev=ev):
+                ev.reduced_hessian_products_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), k, V.data_ptr(), Y.data_ptr(), st)
+
+            def loop(k, ev=ev):
+                for c in range(k):
+                    ev.reduced_hessian_product_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), V[c].data_ptr(), Y1[c].data_ptr(), st)
+
+            table, same = {}, True
+            for width in BLOCK_WIDTHS:
+                ev.set_option("reduced_block_width", width)       # (drops the kept points: the next calls build them again)
+                block(1); loop(1); torch.cuda.synchronize()
+                row = {}
+                for k in BLOCK_COLS:
+                    b, l = alternating([lambda: block(k), lambda: loop(k)], reps)
+                    same = same and bool(torch.equal(Y[:k], Y1[:k]))
+                    row[str(k)] = {"block_ms": b, "singles_ms": l, "ratio": round(b / l, 4), "block_ms_per_column": round(b / k, 4)}
+                table[str(width)] = row
+            out[route] = {"projected": table, "same_bits_as_singles": same}
+            if route == "reduced_input_store":                    # which part scales: the per-name profile of one block of 16 and of one single
+                ev.set_option("overlap_sweep", 0)
+                ev.set_option("reduced_block_width", 16)
+                split = {}
+                for what, fn in (("block_16", lambda: block(16)), ("single", lambda: loop(1))):
+                    fn(); torch.cuda.synchronize()
+                    ev.profile_enable(True); ev.profile_reset(); fn(); torch.cuda.synchronize()
+                    split[what] = {part: {"ms": round(ev.profile_get(part)[0], 4), "launches": ev.profile_get(part)[1],
+                                          "GB": round(ev.profile_get(part)[2] * 1e-9, 5)} for part in BLOCK_PARTS}
+                    ev.profile_enable(False)
+                ev.set_option("overlap_sweep", 1)
+                out["split_store_route"] = split
+        # H V alone (the caller's [n_cols][n_vars] planes), on the default-route handle: the option does not reach it
+        ev = evs[0]
+        htable = {}
+        for width in BLOCK_WIDTHS:
+            ev.set_option("reduced_block_width", width)
+            ev.eval_hessian_product_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), V[0].data_ptr(), Y1[0].data_ptr(), st); torch.cuda.synchronize()
+            row = {}
+            for k in BLOCK_COLS:
+                def hb(k=k):
+                    ev.eval_hessian_products_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), k, V.data_ptr(), Y.data_ptr(), st)
+
+                def hl(k=k):
+                    for c in range(k):
+                        ev.eval_hessian_product_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), V[c].data_ptr(), Y1[c].data_ptr(), st)
+                b, l = alternating([hb, hl], reps)
+                row[str(k)] = {"block_ms": b, "singles_ms": l, "ratio": round(b / l, 4), "same_bits": bool(torch.equal(Y[:k], Y1[:k]))}
+            htable[str(width)] = row
+        out["hessian_products"] = htable
+        return out
+    finally:
+        for ev in evs:
+            ev.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--shapes", default="256x2000,64x1000", help="comma-separated states x knots")
@@ -284,9 +368,14 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0, help="standard deviation of the generators' entries (1.0: the norms of the\n"
                     "headline benchmark, several squarings per propagator; 0: 1 / sqrt(n), norms of order one)")
     ap.add_argument("--routes", default="yes", choices=("yes", "no", "only"), help="the default route beside option reduced_input_store = 1")
+    ap.add_argument("--block", action="store_true", help="the block products (reduced_hessian_products_dev, eval_hessian_products_dev)\n"
+                    "against loops of single products at the kept point, per route, chunk width and column count; nothing else")
     a = ap.parse_args()
     for s in a.shapes.split(","):
         n, N = (int(x) for x in s.lower().split("x"))
+        if a.block:
+            print(json.dumps({"block": measure_block(n, N, a.drives, a.scale, a.reps)}), flush=True)
+            continue
         if a.routes != "only":
             print(json.dumps(measure(n, N, a.drives, a.scale, a.reps, s.lower() == a.host_shape.lower())), flush=True)
         if a.routes != "no":
