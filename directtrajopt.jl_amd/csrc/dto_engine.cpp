@@ -73,7 +73,7 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25, CAT_FEASIBLE = 26 };
 // CAT_ROLLOUT .. CAT_ROLLOUT_DESCENT ("rollout" = its parts "rollout_gather" + "rollout_tree" + "rollout_descent"): the gather, the
 // tree's products and the descent (with the start and the copy into the caller's layout) of dto_rollout[_dev], flops as executed with
 // padding; the tree's products run launch_bgemm_plain and count HERE, not under "bgemm_plain"; they feed no other name, "all" included
@@ -91,6 +91,9 @@ inline bool is_elim_cat(int cat) { return cat == CAT_DYNSOLVE_COUPLE || cat == C
 // are made of count under their own names.
 // CAT_REDUCED_INPUT ("reduced_input"): with the option "reduced_input_store", the gather of the input blocks and the two products with
 // them (dto_reduced.hip); BYTES as executed; it feeds no other name either.
+// CAT_FEASIBLE ("feasible"): the three kernels of dto_feasible.hip -- the DerivativeIntegrators' recurrences, the scatters of the rolled-out
+// states and the merit sum of dto_feasible_trajectory / dto_feasible_merit and their _dev forms; BYTES as executed; it feeds no other
+// name, "all" included.  The Jacobian, tree and descent launches inside count under their own names.
 // The block products (dto_eval_hessian_products, dto_projected_hessian_products) count under the same names -- "hess_product",
 // "reduced_pack", "reduced_input" -- one launch per chunk each, bytes as executed: the matrices once per tile or chunk, the vectors per column.
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
@@ -2996,6 +2999,151 @@ int dto_projected_hessian_products_dev(dto_handle* h, const double* dZ, double s
     }, G_ASYNC, (hipStream_t)stream);
 }
 
+// ---- feasible-trajectory rollout and reduced merit value (include/dto_engine.h, "Feasible trajectory"; dto_feasible.hip,
+// dto_feasible_plan.h): the function the reduced-space operators are derivatives of.  A composition of do_jacobian, the rollout's tree
+// and descent, do_objective and do_constraint, all on `st` and all unchanged; three small kernels keep the states on the device.
+
+// What a feasible-trajectory call names: refused with text before anything is enqueued.
+static const FeasiblePlan& feasible_args(dto_handle* h, const std::string& who, bool merit) {
+    needs_unsharded(h, who);
+    const ElimPlan& p = elim_plan_of(h);
+    if (!p.refusal.empty()) throw HipError{who + ": " + p.refusal};
+    if (merit) {
+        if (h->n_ext_con + h->n_ext_obj > 0)
+            throw HipError{who + ": the handle holds host-evaluated terms (" + std::to_string(h->n_ext_con) + " constraints, " +
+                           std::to_string(h->n_ext_obj) + " objectives): the merit value runs on device-evaluated terms only"};
+        int64_t rows = 0;
+        for (size_t i = 0; i < h->integ_dim.size(); ++i) rows = std::max(rows, h->integ_row_off[i] + h->K * h->integ_dim[i]);
+        if (h->n_dyn != h->K * p.n_states || rows > h->n_dyn) throw HipError{who + ": the dynamics rows are not the first (N - 1) n_states rows"};
+    }
+    if (!h->feas) {
+        std::vector<int> propagates(p.level.size());
+        for (size_t i = 0; i < p.level.size(); ++i) propagates[i] = elim_has_tree(h, (int)i) ? 1 : 0;
+        h->feas.reset(new FeasiblePlan(feasible_plan(p.level, propagates)));
+    }
+    return *h->feas;
+}
+
+// the merit's block d_feas: Zf [n_vars], g [n_cons], the host-pointer form's mu [n_cons], f, phi
+struct FeasWork { double *Zf, *g, *mu, *f, *phi; };
+
+// Every workspace of a call, before anything is enqueued: the private slab, the rollout's tree and padded trajectory for the widest
+// integrator with a propagator, and for the merit its own block.
+static FeasWork feasible_workspaces(dto_handle* h, const FeasiblePlan& fp, bool merit) {
+    int npad_max = 0;
+    for (const FeasibleStep& s : fp.steps)
+        if (s.kind == FEAS_ROLL) npad_max = std::max(npad_max, pad64(h->integ_dim[s.integrator]));
+    if (npad_max && h->K >= 1) {
+        jac_scratch(h);
+        grow_workspace(h, h->d_roll_tree, rollout_tree_bytes(npad_max, h->K) / sizeof(double));
+        grow_workspace(h, h->d_roll_S, rollout_traj_bytes(npad_max, h->K, 1) / sizeof(double));
+    }
+    FeasWork W{};
+    if (!merit) return W;
+    const size_t nv = (size_t)h->n_vars, nc = (size_t)std::max<int64_t>(h->n_cons, 1);
+    double* q = grow_workspace(h, h->d_feas, nv + 2 * nc + 2);
+    W.Zf = q; W.g = q + nv; W.mu = W.g + nc; W.f = W.mu + nc; W.phi = W.f + 1;
+    return W;
+}
+
+// The device routine both entry-point families run: everything on `st`, dZ / dZf device pointers, dZf == dZ works in place.
+static void feasible_trajectory(dto_handle* h, const FeasiblePlan& fp, const double* dZ, double* dZf, hipStream_t st) {
+    const int64_t K = h->K;
+    if (dZf != dZ) HIP_CHECK(hipMemcpyAsync(dZf, dZ, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToDevice, st));
+    if (K < 1) return;   // a single knot: the copy
+    double* slab = nullptr;
+    for (const FeasibleStep& s : fp.steps) {
+        if (s.kind == FEAS_DERIV) {
+            const KDer& d = h->der[h->integ_index[s.integrator]];
+            ProfScope ps(h, st, CAT_FEASIBLE, 8.0 * (double)K * (2.0 * d.d + 1.0) + 8.0 * (double)(K + 1) * d.d);
+            launch_feas_deriv(st, K, h->z, h->dt_idx, d, dZf);
+            continue;
+        }
+        if (s.kind == FEAS_JACOBIAN) {
+            // the whole Jacobian at the trajectory built so far, once per level: the x_k columns of every integrator of the level then
+            // hold -E_k.  (The tree the single-integrator solves keep per point shares the workspaces below and is overwritten.)
+            h->dyn_point.rec.drop();
+            slab = jac_scratch(h);
+            do_jacobian(h, dZf, slab, st);
+            continue;
+        }
+        const KRollout R = rollout_args(h, s.integrator, 1, DTO_ROLLOUT_ALL, false, "dto_feasible_trajectory");
+        double* tree = h->d_roll_tree.p;
+        double* S = h->d_roll_S.p;
+        rollout_tree_from_slab(h, R, slab, tree, st, CAT_ROLLOUT, CAT_ROLLOUT_TREE);
+        { ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, 0.0); launch_rollout_start(st, R, dZf, nullptr, S); }
+        const double item_flops = 2.0 * (double)R.npad * R.npad * R.col_pad;
+        for (int l = R.L + 1; l >= 1; --l) {
+            const int64_t live = dynsolve_live_items(R.L, K, 0, l);
+            if (live == 0) continue;
+            ProfScope ps(h, st, CAT_ROLLOUT_DESCENT, item_flops * (double)live);
+            launch_rollout_descend(st, R, l, -1, tree, S);
+        }
+        ProfScope ps(h, st, CAT_FEASIBLE, 16.0 * (double)K * R.n);
+        launch_feas_scatter(st, R, h->z, S, dZf);
+    }
+}
+
+// phi = sigma f(Zf) + sum over the non-dynamics rows of mu_r g_r(Zf), Zf = the feasible trajectory of dZ.  dZf / dg null: the
+// workspace's (g is evaluated only where dg or dmu asks for it).
+static void feasible_merit(dto_handle* h, const FeasiblePlan& fp, const FeasWork& W, const double* dZ, double sigma, const double* dmu,
+                           double* dphi, double* dZf, double* dg, hipStream_t st) {
+    double* Zf = dZf ? dZf : W.Zf;
+    feasible_trajectory(h, fp, dZ, Zf, st);
+    do_objective(h, Zf, W.f, st);
+    double* g = dg ? dg : W.g;
+    if (dg || dmu) do_constraint(h, Zf, g, st);
+    ProfScope ps(h, st, CAT_FEASIBLE, 16.0 + (dmu ? 16.0 * (double)(h->n_cons - h->n_dyn) : 0.0));
+    launch_feas_merit(st, h->n_dyn, h->n_cons, sigma, W.f, dmu, g, dphi);
+}
+
+int dto_feasible_trajectory(dto_handle* h, const double* Z, double* Zf) {
+    return guarded(h, [&] {
+        const std::string who = "dto_feasible_trajectory";
+        const FeasiblePlan& fp = feasible_args(h, who, false);
+        if (!Z || !Zf) throw HipError{who + ": Z and Zf are required (NULL given)"};
+        feasible_workspaces(h, fp, false);
+        upload_Z(h, Z);
+        feasible_trajectory(h, fp, h->d_Z, h->d_Z, h->stream);   // in place in the handle's copy
+        HIP_CHECK(hipMemcpyAsync(Zf, h->d_Z, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_feasible_trajectory_dev(dto_handle* h, const double* dZ, double* dZf, void* stream) {
+    return guarded(h, [&] {
+        const std::string who = "dto_feasible_trajectory_dev";
+        const FeasiblePlan& fp = feasible_args(h, who, false);
+        if (!dZ || !dZf) throw HipError{who + ": dZ and dZf are required (NULL given)"};
+        feasible_workspaces(h, fp, false);
+        feasible_trajectory(h, fp, dZ, dZf, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+int dto_feasible_merit(dto_handle* h, const double* Z, double sigma, const double* mu, double* phi, double* Zf, double* g) {
+    return guarded(h, [&] {
+        const std::string who = "dto_feasible_merit";
+        const FeasiblePlan& fp = feasible_args(h, who, true);
+        if (!Z || !phi) throw HipError{who + ": Z and phi are required (NULL given)"};
+        const FeasWork W = feasible_workspaces(h, fp, true);
+        upload_Z(h, Z);
+        const bool has_mu = mu && h->n_cons > 0;
+        if (has_mu) HIP_CHECK(hipMemcpyAsync(W.mu, mu, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        feasible_merit(h, fp, W, h->d_Z, sigma, has_mu ? W.mu : nullptr, W.phi, h->d_Z, g ? W.g : nullptr, h->stream);
+        HIP_CHECK(hipMemcpyAsync(phi, W.phi, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (Zf) HIP_CHECK(hipMemcpyAsync(Zf, h->d_Z, sizeof(double) * (size_t)h->n_vars, hipMemcpyDeviceToHost, h->stream));
+        if (g && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(g, W.g, sizeof(double) * (size_t)h->n_cons, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_feasible_merit_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, double* dphi, double* dZf, double* dg, void* stream) {
+    return guarded(h, [&] {
+        const std::string who = "dto_feasible_merit_dev";
+        const FeasiblePlan& fp = feasible_args(h, who, true);
+        if (!dZ || !dphi) throw HipError{who + ": dZ and dphi are required (NULL given)"};
+        const FeasWork W = feasible_workspaces(h, fp, true);
+        feasible_merit(h, fp, W, dZ, sigma, h->n_cons > 0 ? dmu : nullptr, dphi, dZf, dg, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
 // ---- multi-GPU: ranges, gather plans, collectives (dto_comm.h)
 int dto_comm_unique_id(void* id128) {
     if (!id128) return fail(nullptr, "dto_comm_unique_id: null argument");
@@ -3264,6 +3412,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "dynsolve_deriv")) cat = CAT_DYNSOLVE_DERIV;
         else if (!strcmp(name, "reduced_pack")) cat = CAT_REDUCED_PACK;
         else if (!strcmp(name, "reduced_input")) cat = CAT_REDUCED_INPUT;
+        else if (!strcmp(name, "feasible")) cat = CAT_FEASIBLE;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -3293,7 +3442,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (is_rollout_cat(r.cat) ? !(any_rollout || r.cat == cat) : any_rollout) continue;   // ("all": the rollout is no callback)
             if (is_dynsolve_cat(r.cat) ? !(any_dynsolve || r.cat == cat) : any_dynsolve) continue;   // (nor are the solves)
             if (is_elim_cat(r.cat) && r.cat != cat) continue;
-            if ((r.cat == CAT_REDUCED_PACK || r.cat == CAT_REDUCED_INPUT) && r.cat != cat) continue;
+            if ((r.cat == CAT_REDUCED_PACK || r.cat == CAT_REDUCED_INPUT || r.cat == CAT_FEASIBLE) && r.cat != cat) continue;
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));

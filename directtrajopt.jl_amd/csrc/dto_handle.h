@@ -18,6 +18,7 @@
 
 #include "dto_comm.h"
 #include "dto_elim_plan.h"
+#include "dto_feasible_plan.h"
 #include "dto_hostxfer.h"
 #include "dto_input_plan.h"
 #include "dto_kept_point.h"
@@ -330,6 +331,12 @@ struct dto_handle {
     // rho / w [W][n_cons]; d_blk_host: the host-pointer forms' V and Y.  Both grow-only, sized before anything is enqueued.
     int reduced_block_width = 0;
     dto::Workspace d_blk, d_blk_host;
+    // feasible-trajectory rollout and reduced merit value (dto_feasible_trajectory[_dev], dto_feasible_merit[_dev]; schedule:
+    // dto_feasible_plan.h).  The rollout works in the caller's Zf and in dto_rollout's tree and trajectory workspaces.  d_feas, the
+    // merit's own block, grow-only and sized before anything is enqueued: Zf [n_vars] and g [n_cons] where the caller gives none, the
+    // host-pointer form's mu [n_cons], f and phi.
+    std::unique_ptr<dto::FeasiblePlan> feas;
+    dto::Workspace d_feas;
     int64_t* d_conbase = nullptr;       // [n_vars+1] first constraint-pattern entry of each column
     int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
     int64_t* d_crow_col = nullptr;

@@ -540,6 +540,16 @@ void launch_red_input_forward_block(hipStream_t st, const KReduced& R, const KIn
 void launch_red_input_transposed_block(hipStream_t st, const KReduced& R, const KInput& In, int w, const double* store, const double* q,
                                        const double* gam, double* y);
 
+// Feasible-trajectory rollout and reduced merit value (dto_feasible.hip; schedule: dto_feasible_plan.h).  Zf is a Z-layout vector
+// [N][z] (+ globals) that the kernels update in place.
+// a DerivativeIntegrator's recurrence x_{k+1} = x_k + dt_k xdot_k over K intervals, product and sum rounded on their own
+void launch_feas_deriv(hipStream_t st, int64_t K, int z, int dt_idx, const KDer& D, double* Zf);
+// knots 1 .. K of column 0 of the rollout's padded trajectory S into R's state components of Zf
+void launch_feas_scatter(hipStream_t st, const KRollout& R, int z, const double* S, double* Zf);
+// *phi = sigma * *f + sum over the rows r >= n_dyn of mu[r] g[r], one wavefront in a fixed order; mu null: *phi = sigma * *f
+void launch_feas_merit(hipStream_t st, int64_t n_dyn, int64_t n_cons, double sigma, const double* f, const double* mu, const double* g,
+                       double* phi);
+
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);
 

@@ -122,6 +122,10 @@ SYMBOLS = {
     "dto_eval_hessian_products_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dto_projected_hessian_products": (C.c_int, [H, c_double_p, C.c_double, c_double_p, C.c_int32, c_double_p, c_double_p]),
     "dto_projected_hessian_products_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dto_feasible_trajectory": (C.c_int, [H, c_double_p, c_double_p]),
+    "dto_feasible_trajectory_dev": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dto_feasible_merit": (C.c_int, [H, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "dto_feasible_merit_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dto_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dto_comm_create": (C.c_int, [H, C.c_void_p, C.c_int32, C.c_int32]),
     "dto_comm_set_ranges": (C.c_int, [H, C.c_int32, C.c_int32, c_int64_p, c_int64_p]),

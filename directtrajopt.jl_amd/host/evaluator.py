@@ -558,6 +558,35 @@ class Evaluator:
                     Zk[:, it.x_off:it.x_off + it.x_dim] = self.rollout(Z, integrator=i)[:, 0]
         return Z
 
+    def feasible_trajectory_engine(self, Z):
+        """``feasible_trajectory`` as ONE engine call (``dto_feasible_trajectory``): the levels, the DerivativeIntegrators'
+        recurrences, one Jacobian evaluation per level that holds a propagator (not one per integrator), the rollouts and the
+        scatter into the Z layout all run on the device.  Host vectors; returns a copy with the bits of ``feasible_trajectory``."""
+        Z = self._Z(Z)
+        Zf = np.full(self.n_variables, np.nan)
+        self._stage_external(Z, con_need=1)
+        self._check(self._lib.dto_feasible_trajectory(self._h, _dp(Z), _dp(Zf)))
+        return Zf
+
+    def feasible_merit(self, Z, sigma=1.0, mu=None, trajectory=False, constraints=False):
+        """phi = sigma f(Zf) + sum over the non-dynamics rows of mu_r g_r(Zf) at Zf = ``feasible_trajectory_engine(Z)``, in one engine
+        call (``dto_feasible_merit``): the function ``reduced_lagrangian_gradient`` and ``reduced_hessian_product`` are derivatives
+        of, what a line search evaluates per trial step.  ``mu``: (n_constraints,) or None for zeros (phi = sigma f); its
+        dynamics-row entries are not read.  The sum has a fixed order (include/dto_engine.h), so repeated calls return the same
+        bits.  Returns phi; with ``trajectory=True`` and / or ``constraints=True`` a tuple (phi[, Zf][, g]): Zf (n_variables,) and g
+        (n_constraints,), every row at Zf -- the dynamics rows are the defects the rollout leaves.  It keeps the points of the
+        reduced operators: a line search between two ``reduced_hessian_product`` calls costs them nothing."""
+        Z = self._Z(Z)
+        if mu is not None:
+            mu = _in(mu, self.n_constraints, "mu")
+        phi = C.c_double(np.nan)
+        Zf = np.full(self.n_variables, np.nan) if trajectory else None
+        g = np.full(self.n_constraints, np.nan) if constraints else None
+        self._check(self._lib.dto_feasible_merit(self._h, _dp(Z), float(sigma), None if mu is None else _dp(mu), C.byref(phi),
+                                                 None if Zf is None else _dp(Zf), None if g is None else _dp(g)))
+        out = (phi.value,) + (() if Zf is None else (Zf,)) + (() if g is None else (g,))
+        return out if len(out) > 1 else phi.value
+
     def reduced_gradient(self, Z):
         """Gradient of the objective along the dynamically feasible manifold at a FEASIBLE Z (``feasible_trajectory``'s result):
         the derivative of f(feasible_trajectory(.)) with respect to everything the states of knots 2 .. N are a function of.  One
@@ -733,6 +762,19 @@ class Evaluator:
         self._stage_external(Z_host, con_need=1)
         self._check(self._lib.dto_dynamics_solve_all_dev(self._h, dZ, capi.SOLVE_ADJOINT if adjoint else capi.SOLVE_FORWARD, dB or None,
                                                          int(n_cols), dY, stream))
+
+    def feasible_trajectory_dev(self, dZ, dZf, stream=0, Z_host=None):
+        """``feasible_trajectory_engine`` on device pointers: dZ and dZf (n_variables); dZf may equal dZ (in place), otherwise they
+        must not overlap; enqueued on `stream`, errors deferred as for every `_dev` call.  Same bits as the host form."""
+        self._stage_external(Z_host, con_need=1)
+        self._check(self._lib.dto_feasible_trajectory_dev(self._h, dZ or None, dZf or None, stream))
+
+    def feasible_merit_dev(self, dZ, sigma, dmu, dphi, dZf=0, dg=0, stream=0):
+        """``feasible_merit`` on device pointers: dmu (n_constraints) or 0 / None for zeros, dphi one double, dZf (n_variables) and
+        dg (n_constraints) or 0 / None; enqueued on `stream`, errors deferred as for every `_dev` call.  Same bits as the host
+        form."""
+        self._check(self._lib.dto_feasible_merit_dev(self._h, dZ or None, float(sigma), dmu or None, dphi or None, dZf or None,
+                                                     dg or None, stream))
 
     def reduced_gradient_dev(self, dZ, sigma, dmu, dgrad, dlam=0, stream=0):
         """``reduced_lagrangian_gradient`` on device pointers: dmu (n_constraints) or 0 / None for zeros, dgrad (n_variables), dlam

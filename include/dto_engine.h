@@ -556,6 +556,47 @@ int dto_eval_hessian_products_dev(dto_handle* h, const double* dZ, double sigma,
 int dto_projected_hessian_products(dto_handle* h, const double* Z, double sigma, const double* mu, int32_t n_cols, const double* V, double* Y);
 int dto_projected_hessian_products_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, int32_t n_cols, const double* dV, double* dY, void* stream);
 
+/* ---- Feasible trajectory and merit value: the function the operators above are derivatives of, phi(feasible trajectory(Z)) -- what a
+ * truncated-Newton or GRAPE-style method evaluates once per line-search trial, without leaving the device.
+ *   dto_feasible_trajectory   Zf [n_vars] = Z with every integrator's state components at knots 2 .. N replaced by what its dynamics
+ *                          reach from the knot-1 states under the controls, timesteps and times of Z.  Levels (dto_dynamics_layout)
+ *                          run ascending.  Inside a level: first the DerivativeIntegrators in list order, each the recurrence
+ *                          x_{k+1} = x_k + dt_k xdot_k with the product and the sum rounded on their own; then, if the level holds an
+ *                          integrator with a propagator, ONE Jacobian evaluation at the Zf built so far into the private slab; then per
+ *                          such integrator in list order its product tree from that slab (dto_rollout's), the descent through all knots
+ *                          from the knot-1 state of Zf, and the scatter into Zf.  E_k reads no state of its own level, so one evaluation
+ *                          serves every integrator of the level: one for a multi-ket problem, not one per ket.
+ *                          Zf may equal Z (the _dev form then works in place); otherwise they must not overlap.  N = 1 returns a copy.
+ *   dto_feasible_merit     runs the routine above, then the engine's own objective and constraint evaluation at Zf -- f and g have
+ *                          the bits of dto_eval_objective_dev / dto_eval_constraint_dev there -- and
+ *                              phi = sigma f + sum over the non-dynamics rows r of mu_r g_r(Zf)
+ *                          summed by one wavefront in a fixed order: lane l adds mu_r g_r over r = n_dyn + l, n_dyn + l + 64, ..
+ *                          ascending, every product and every sum rounded on its own; the 64 partial sums are combined by the halving
+ *                          tree stated for the input-block product above (p_l += p_{l+32}, .. , p_l += p_{l+1}), t = p_0;
+ *                          phi = sigma * f + t, product and sum rounded on their own.  mu = NULL: phi = sigma * f.  No atomics; the
+ *                          dynamics-row entries of mu are never read.
+ *                          phi: one double.  Zf [n_vars] may be NULL (the engine then works in a buffer of its own).  g may be NULL,
+ *                          else [n_cons]: all rows at Zf -- the dynamics rows are the residual defects, which tell how feasible the
+ *                          rollout is.  Without g and without mu the constraints are not evaluated.
+ * Bits.  A DerivativeIntegrator's states are those of the recurrence written in NumPy; an integrator's rolled-out states are those of
+ * dto_rollout (X0 = NULL) at the Z updated so far, whichever integrators share its level.  Repeated calls and both entry-point
+ * families return the same bits.
+ * Kept points.  The calls reuse dto_rollout's tree and trajectory workspaces and the private slab: like dto_rollout they drop the kept
+ * point of dto_dynamics_solve.  The whole-dynamics solves' point, the reduced point and the Hessian products' point are not touched: a
+ * line search between two reduced products costs those products nothing.
+ * Workspaces, grow-only and allocated before anything is enqueued: dto_rollout's for the widest integrator with a propagator (one
+ * column) and the private slab; for the merit one block of n_vars + 2 n_cons + 2 doubles.
+ * Refused with text, the handle stays usable and nothing is written: everything dto_dynamics_solve_all refuses (a host-evaluated
+ * integrator, a sharded or structure-only handle, overlapping states, an integrator reading its own states, a dependency cycle); Z or
+ * Zf = NULL (the merit: Z or phi = NULL); for the merit any host-evaluated constraint or objective.
+ * The host-pointer forms upload Z, run the device routine on the handle's stream, download and block.  The _dev forms take device
+ * pointers (dmu, dZf and dg may be NULL), enqueue on `stream`, may wait on the small readbacks dto_eval_jacobian_dev waits on, and
+ * defer device-side errors like every _dev call. */
+int dto_feasible_trajectory(dto_handle* h, const double* Z, double* Zf);
+int dto_feasible_trajectory_dev(dto_handle* h, const double* dZ, double* dZf, void* stream);
+int dto_feasible_merit(dto_handle* h, const double* Z, double sigma, const double* mu, double* phi, double* Zf, double* g);
+int dto_feasible_merit_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, double* dphi, double* dZf, double* dg, void* stream);
+
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
  * communicator (SURVEY.md §8b "Ownership").  No callback needs a collective: every rank's Jacobian / Hessian / gradient
@@ -724,6 +765,10 @@ int dto_profile_reset(dto_handle* h);
  * BYTES as executed; it feeds no other name, "all" included, and the routines the operators are made of count under their own names),
  * "reduced_input" (option "reduced_input_store": the gather of the input blocks at a rebuilt point, one launch per integrator with free
  * inputs, and the two products with them, one launch each -- third output: BYTES as executed; it feeds no other name, "all" included).
+ * "feasible" (dto_feasible_trajectory / dto_feasible_merit and their _dev forms: the DerivativeIntegrators' recurrences, the scatters of
+ * the rolled-out states into Zf and the merit sum, one launch each -- third output: BYTES as executed; it feeds no other name, "all"
+ * included; the Jacobian evaluation inside counts under its own names, the trees and descents under "rollout_gather" / "rollout_tree" /
+ * "rollout_descent").
  * The block products count under "hess_product", "reduced_pack" and "reduced_input" too, one launch per chunk where a single product
  * has one, with bytes as executed: matrix bytes once per tile or chunk, vector bytes per column.
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the

@@ -877,6 +877,47 @@ function reduced_hessian_products_dev!(ev::GPUEvaluator, dY::Ptr{Float64}, dZ::P
                                                             dV::Ptr{Float64}, dY::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 end
 
+# ---- feasible trajectory and merit value (include/dto_engine.h, "Feasible trajectory") ------------------------------------------------
+# Zf = Z with every integrator's states of knots 2 .. N replaced by what its dynamics reach from the states of knot 1: one engine call,
+# one Jacobian evaluation per dependency level that holds a propagator.
+function feasible_trajectory(ev::GPUEvaluator, Z::AbstractVector{Float64})
+    reduced_check_lengths(ev, "feasible_trajectory", Z, nothing)
+    stage_external!(ev, Z; con_need = 1)
+    Zv = Vector{Float64}(Z)
+    Zf = fill(NaN, ev.n_variables)
+    GC.@preserve Zv Zf check(ev, @ccall lib.dto_feasible_trajectory(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, Zf::Ptr{Float64})::Cint)
+    return Zf
+end
+
+# φ = σ f(Zf) + Σ over the non-dynamics rows of μ_r g_r(Zf), the function `reduced_gradient` and `reduced_hessian_product` are
+# derivatives of; returns (φ, Zf, g) -- g holds every row at Zf, the dynamics rows being the defects the rollout leaves.
+function feasible_merit(ev::GPUEvaluator, Z::AbstractVector{Float64}; σ::Float64 = 1.0, μ::Union{Nothing,AbstractVector{Float64}} = nothing)
+    reduced_check_lengths(ev, "feasible_merit", Z, μ)
+    Zv = Vector{Float64}(Z)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    φ = Ref{Float64}(NaN)
+    Zf = fill(NaN, ev.n_variables)
+    g = fill(NaN, ev.n_constraints)
+    GC.@preserve Zv μv Zf g begin
+        μp = μ === nothing ? Ptr{Float64}(C_NULL) : pointer(μv)
+        check(ev, @ccall lib.dto_feasible_merit(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μp::Ptr{Float64}, φ::Ptr{Float64},
+                                                Zf::Ptr{Float64}, g::Ptr{Float64})::Cint)
+    end
+    return φ[], Zf, g
+end
+
+# the same on device pointers, enqueued on `stream`; dZf may equal dZ (in place); dμ, and for the merit dZf and dg, may be C_NULL
+function feasible_trajectory_dev!(ev::GPUEvaluator, dZf::Ptr{Float64}, dZ::Ptr{Float64}, stream::Ptr{Cvoid}; Z_host = nothing)
+    Z_host === nothing || stage_external!(ev, Z_host; con_need = 1)
+    check(ev, @ccall lib.dto_feasible_trajectory_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, dZf::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
+function feasible_merit_dev!(ev::GPUEvaluator, dφ::Ptr{Float64}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dZf::Ptr{Float64},
+                             dg::Ptr{Float64}, stream::Ptr{Cvoid})
+    check(ev, @ccall lib.dto_feasible_merit_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dφ::Ptr{Float64},
+                                                dZf::Ptr{Float64}, dg::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
 # row bounds handed to the solver (src/solvers/solve.jl:30-65)
 function constraint_bounds(ev::GPUEvaluator)
     lo = Vector{Float64}(undef, ev.n_constraints)
