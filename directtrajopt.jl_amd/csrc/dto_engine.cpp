@@ -4,6 +4,7 @@
 // propagator chain, the callbacks, the transfer plans, the extern "C" entry points other than dto_create, the communicator and
 // profiling.  There is NO CPU fallback: every evaluation runs on the GPU or fails with an error code.
 #include "dto_handle.h"
+#include "dto_newton_plan.h"
 #include "dto_rollout_plan.h"
 
 #include <chrono>
@@ -73,7 +74,7 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25, CAT_FEASIBLE = 26 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25, CAT_FEASIBLE = 26, CAT_NEWTON = 27 };
 // CAT_ROLLOUT .. CAT_ROLLOUT_DESCENT ("rollout" = its parts "rollout_gather" + "rollout_tree" + "rollout_descent"): the gather, the
 // tree's products and the descent (with the start and the copy into the caller's layout) of dto_rollout[_dev], flops as executed with
 // padding; the tree's products run launch_bgemm_plain and count HERE, not under "bgemm_plain"; they feed no other name, "all" included
@@ -94,6 +95,9 @@ inline bool is_elim_cat(int cat) { return cat == CAT_DYNSOLVE_COUPLE || cat == C
 // CAT_FEASIBLE ("feasible"): the three kernels of dto_feasible.hip -- the DerivativeIntegrators' recurrences, the scatters of the rolled-out
 // states and the merit sum of dto_feasible_trajectory / dto_feasible_merit and their _dev forms; BYTES as executed; it feeds no other
 // name, "all" included.  The Jacobian, tree and descent launches inside count under their own names.
+// CAT_NEWTON ("newton"): the four kernels of dto_newton.hip -- the start, the curvature pass, the step and the direction update of
+// dto_projected_newton_step and its _dev form; BYTES as executed; it feeds no other name, "all" included.  The products of the
+// iterations count under the names of the block products.
 // The block products (dto_eval_hessian_products, dto_projected_hessian_products) count under the same names -- "hess_product",
 // "reduced_pack", "reduced_input" -- one launch per chunk each, bytes as executed: the matrices once per tile or chunk, the vectors per column.
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
@@ -2912,21 +2916,23 @@ static BlockWork block_workspaces(dto_handle* h, const ElimPlan& p, int W, bool 
 // columns per chunk of a projected block call: W = min(the solves' limit, the option or W_max), and no more than the call has
 static int projected_width(const dto_handle* h, int n_cols) { return std::min(block_width(h, elim_column_cap(h)), n_cols); }
 
-// Y = T' H(Z; sigma, mu~) T V, V and Y [n_cols][n_vars] on the device.  The three point checks (reduced point, solves' point, Hessian
-// point) once; then per chunk of w <= W columns the steps of reduced_hessian_product in block form.
-static void projected_hessian_products(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, int n_cols,
-                                       const double* dV, double* dY, hipStream_t st) {
-    const KReduced& R = h->red;
-    const int W = projected_width(h, n_cols);
-    const bool store_route = h->reduced_input_store && h->K >= 1;
-    const BlockWork B = block_workspaces(h, p, W, store_route);
-    const int64_t nvars = h->n_vars, ncons = h->n_cons;
+// The three points a projected product works at -- the reduced point, the solves' point (workspaces for W columns) and the Hessian
+// point at mu~ -- each checked once: at a new Z the rebuild the single product would run at its first solve (on the store route:
+// before its first kernel) runs here.
+static ElimWork projected_points(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, int W, hipStream_t st) {
     ElimWork EW{};
-    // the solves' workspaces for W columns first (a failed allocation is refused before anything is enqueued); at a new Z the rebuild
-    // the single product would run at its first solve (on the store route: before its first kernel) runs here
     reduced_point(h, p, dZ, sigma, dmu, st);
     if (h->K >= 1) EW = elim_point(h, p, dZ, W, st);
     hess_point(h, dZ, sigma, h->red_mut, st);
+    return EW;
+}
+
+// One chunk of w columns at the points projected_points ensured: y = T' H(Z; sigma, mu~) T v, v and y [w][n_vars], in B's vectors --
+// the steps of reduced_hessian_product in block form.
+static void projected_chunk(dto_handle* h, const ElimPlan& p, const BlockWork& B, const ElimWork& EW, bool store_route, const double* dZ,
+                            int w, const double* v, double* y, hipStream_t st) {
+    const KReduced& R = h->red;
+    const int64_t nvars = h->n_vars, ncons = h->n_cons;
     auto solve = [&](int adjoint, int w) {
         if (h->K < 1) {   // a single knot: the block is the identity
             ProfScope ps(h, st, CAT_DYNSOLVE_SCAN, 0.0);
@@ -2935,10 +2941,7 @@ static void projected_hessian_products(dto_handle* h, const ElimPlan& p, const d
         }
         elim_solve(h, p, EW, adjoint, B.s1, w, B.s2, st);
     };
-    for (int c0 = 0; c0 < n_cols; c0 += W) {
-        const int w = std::min(W, n_cols - c0);
-        const double* v = dV + (size_t)c0 * nvars;
-        double* y = dY + (size_t)c0 * nvars;
+    {
         const double nv = 8.0 * (double)nvars * w, nc = 8.0 * (double)ncons * w, nd = 8.0 * (double)h->N * R.D * w;
         const KHessBlock HB{w, 1, nvars, 1, nvars};   // z^ and q as planes [w][n_vars], like V and Y (faster than interleaved)
         if (store_route) {
@@ -2954,7 +2957,7 @@ static void projected_hessian_products(dto_handle* h, const ElimPlan& p, const d
             // bytes: the store once, per column q, Gam and y
             ProfScope ps(h, st, CAT_REDUCED_INPUT, 8.0 * (double)h->input->store_off.back() + 2.0 * nv + nd);
             launch_red_input_transposed_block(st, R, h->in, w, h->d_in_store.p, B.q, B.s2, y);
-            continue;
+            return;
         }
         // z^'s buffer holds v^ and later t, rows holds rho and later w: planes, since J v^ and J' w take one column at a time
         { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_vhat_block(st, R, w, v, B.zh); }
@@ -2969,6 +2972,121 @@ static void projected_hessian_products(dto_handle* h, const ElimPlan& p, const d
         for (int j = 0; j < w; ++j) jac_product(h, dZ, B.rows + (size_t)j * ncons, B.zh + (size_t)j * nvars, 1, st);   // t = J' w
         { ProfScope ps(h, st, CAT_REDUCED_PACK, 3.0 * nv); launch_red_finish_block(st, R, w, B.q, B.zh, B.s2, y); }
     }
+}
+
+// Y = T' H(Z; sigma, mu~) T V, V and Y [n_cols][n_vars] on the device.  The three point checks (reduced point, solves' point, Hessian
+// point) once; then per chunk of w <= W columns the steps of reduced_hessian_product in block form.
+static void projected_hessian_products(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, int n_cols,
+                                       const double* dV, double* dY, hipStream_t st) {
+    const int W = projected_width(h, n_cols);
+    const bool store_route = h->reduced_input_store && h->K >= 1;
+    // the block's and (in projected_points) the solves' workspaces for W columns first: a failed allocation is refused before anything
+    // is enqueued
+    const BlockWork B = block_workspaces(h, p, W, store_route);
+    const ElimWork EW = projected_points(h, p, dZ, sigma, dmu, W, st);
+    for (int c0 = 0; c0 < n_cols; c0 += W)
+        projected_chunk(h, p, B, EW, store_route, dZ, std::min(W, n_cols - c0), dV + (size_t)c0 * h->n_vars, dY + (size_t)c0 * h->n_vars, st);
+}
+
+// ---- truncated-Newton step: Steihaug-Toint CG on A = M (T'HT) M + shift M (include/dto_engine.h, "Truncated-Newton step"; dto_newton.hip,
+// dto_newton_plan.h).  The product of an iteration is the one-column chunk of the block products above -- the single product's bits --
+// at points checked once per call; the dots, the updates and the decisions are four small kernels, and what the host reads per
+// iteration is (status, iterations) through the mailbox.
+
+// What a step names: refused with text before the handle is touched, so a structure-only handle answers these too.
+static std::string newton_refusal(const std::string& who, const double* Z, double radius, double shift, double rtol, double atol, int32_t max_iter,
+                                  const double* p, const double* info) {
+    if (!Z || !p || !info) return who + ": Z, p and info are required (NULL given)";
+    if (max_iter < 1) return who + ": max_iter = " + std::to_string(max_iter) + ", at least 1 iteration is required";
+    if (!std::isfinite(radius) || radius < 0.0) return who + ": radius must be finite and >= 0 (0: no trust region)";
+    if (!std::isfinite(rtol) || rtol < 0.0) return who + ": rtol must be finite and >= 0";
+    if (!std::isfinite(atol) || atol < 0.0) return who + ": atol must be finite and >= 0";
+    if (!std::isfinite(shift)) return who + ": shift must be finite";
+    return "";
+}
+
+// The device routine both entry-point families run: everything on `st`, every pointer a device pointer (dmu, dmask, dtrace may be null).
+static void newton_step(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, const double* dmask, double radius,
+                        double shift, double rtol, double atol, int max_iter, double* dp, double* dinfo, double* dtrace, hipStream_t st) {
+    const KReduced& R = h->red;
+    const int64_t n = h->n_vars, nb = newton_chunks(n);
+    const bool store_route = h->reduced_input_store && h->K >= 1;
+    // every workspace before anything is enqueued
+    double* q = grow_workspace(h, h->d_newton, (size_t)newton_workspace_doubles(n));
+    const BlockWork B = block_workspaces(h, p, 1, store_route);
+    KNewton A{};
+    A.n = n; A.nb = nb;
+    A.p = dp; A.r = q; A.d = q + n; A.w = q + 2 * n;
+    A.part = q + 3 * n; A.state = A.part + NEWTON_SLOTS * nb;
+    A.g = h->red_r; A.mask = dmask; A.info = dinfo; A.trace = dtrace;
+    A.radius = radius; A.shift = shift; A.rtol = rtol; A.atol = atol;
+    static const int combine_launch = tune_int("DTO_NEWTON_COMBINE", 0);   // A/B runs (TUNING builds): 1 = stage 2 of the dots in a launch of its own
+    A.combined = combine_launch ? 1 : 0;
+    auto combine = [&](int slot0, int count) {
+        if (!A.combined) return;
+        ProfScope ps(h, st, CAT_NEWTON, 8.0 * (double)nb * count);
+        launch_newton_combine(st, A, slot0, count);
+    };
+    const ElimWork EW = projected_points(h, p, dZ, sigma, dmu, 1, st);
+    // bytes as executed: the vectors each kernel reads and writes (the mask where one is given), its partial sums, and per workgroup
+    // the partial sums it combines
+    const double v = 8.0 * (double)n, m = dmask ? v : 0.0, part = 8.0 * (double)nb, groups = (double)((nb + 15) / 16);
+    auto running = [&] {   // the one readback per iteration
+        HIP_CHECK(hipMemcpyAsync(h->mailbox->newton, A.state, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return (int)h->mailbox->newton[NWS_STATUS] == NEWTON_CONTINUE;
+    };
+    { ProfScope ps(h, st, CAT_NEWTON, 4.0 * v + m + part); launch_newton_start(st, R, A); }
+    combine(NWT_RR, 1);
+    { ProfScope ps(h, st, CAT_NEWTON, groups * part); launch_newton_dir(st, A, 0, max_iter); }
+    for (int j = 1; j <= max_iter && running(); ++j) {
+        projected_chunk(h, p, B, EW, store_route, dZ, 1, A.d, A.w, st);   // y = T'HT d
+        { ProfScope ps(h, st, CAT_NEWTON, 4.0 * v + m + 4.0 * part); launch_newton_curv(st, R, A); }
+        combine(NWT_KAPPA, 4);
+        { ProfScope ps(h, st, CAT_NEWTON, 7.0 * v + m + 4.0 * part + groups * 4.0 * part); launch_newton_step(st, R, A, j); }
+        combine(NWT_RR, 4);
+        { ProfScope ps(h, st, CAT_NEWTON, 3.0 * v + (groups + 3.0) * part); launch_newton_dir(st, A, j, max_iter); }
+    }
+}
+
+int dto_projected_newton_step(dto_handle* h, const double* Z, double sigma, const double* mu, const double* free_mask, double radius,
+                              double shift, double rtol, double atol, int32_t max_iter, double* p, double* info, double* trace) {
+    const std::string who = "dto_projected_newton_step";
+    if (!h) return fail(nullptr, "null handle");
+    const std::string bad = newton_refusal(who, Z, radius, shift, rtol, atol, max_iter, p, info);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, true);
+        reduced_workspaces(h, ep);
+        const size_t n = (size_t)h->n_vars, nt = 4 * (size_t)max_iter;
+        grow_workspace(h, h->d_newton, (size_t)newton_workspace_doubles(h->n_vars));   // before the uploads are enqueued
+        block_workspaces(h, ep, 1, h->reduced_input_store && h->K >= 1);
+        double* q = grow_workspace(h, h->d_newton_host, 2 * n + 8 + nt);
+        double *dmask = q, *dp = q + n, *dinfo = q + 2 * n, *dtrace = dinfo + 8;
+        upload_Z(h, Z);
+        if (mu && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->red_hmu, mu, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        if (free_mask) HIP_CHECK(hipMemcpyAsync(dmask, free_mask, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+        // the rows of the trace the step does not reach keep the caller's values
+        if (trace) HIP_CHECK(hipMemcpyAsync(dtrace, trace, sizeof(double) * nt, hipMemcpyHostToDevice, h->stream));
+        newton_step(h, ep, h->d_Z, sigma, mu ? h->red_hmu : nullptr, free_mask ? dmask : nullptr, radius, shift, rtol, atol, max_iter, dp, dinfo,
+                    trace ? dtrace : nullptr, h->stream);
+        HIP_CHECK(hipMemcpyAsync(p, dp, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipMemcpyAsync(info, dinfo, sizeof(double) * 8, hipMemcpyDeviceToHost, h->stream));
+        if (trace) HIP_CHECK(hipMemcpyAsync(trace, dtrace, sizeof(double) * nt, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_projected_newton_step_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dfree_mask, double radius,
+                                  double shift, double rtol, double atol, int32_t max_iter, double* dp, double* dinfo, double* dtrace, void* stream) {
+    const std::string who = "dto_projected_newton_step_dev";
+    if (!h) return fail(nullptr, "null handle");
+    const std::string bad = newton_refusal(who, dZ, radius, shift, rtol, atol, max_iter, dp, dinfo);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, true);
+        reduced_workspaces(h, ep);
+        newton_step(h, ep, dZ, sigma, dmu, dfree_mask, radius, shift, rtol, atol, max_iter, dp, dinfo, dtrace, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
 }
 
 int dto_projected_hessian_products(dto_handle* h, const double* Z, double sigma, const double* mu, int32_t n_cols, const double* V, double* Y) {
@@ -3413,6 +3531,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "reduced_pack")) cat = CAT_REDUCED_PACK;
         else if (!strcmp(name, "reduced_input")) cat = CAT_REDUCED_INPUT;
         else if (!strcmp(name, "feasible")) cat = CAT_FEASIBLE;
+        else if (!strcmp(name, "newton")) cat = CAT_NEWTON;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -3442,7 +3561,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (is_rollout_cat(r.cat) ? !(any_rollout || r.cat == cat) : any_rollout) continue;   // ("all": the rollout is no callback)
             if (is_dynsolve_cat(r.cat) ? !(any_dynsolve || r.cat == cat) : any_dynsolve) continue;   // (nor are the solves)
             if (is_elim_cat(r.cat) && r.cat != cat) continue;
-            if ((r.cat == CAT_REDUCED_PACK || r.cat == CAT_REDUCED_INPUT || r.cat == CAT_FEASIBLE) && r.cat != cat) continue;
+            if ((r.cat == CAT_REDUCED_PACK || r.cat == CAT_REDUCED_INPUT || r.cat == CAT_FEASIBLE || r.cat == CAT_NEWTON) && r.cat != cat) continue;
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));

@@ -208,6 +208,7 @@ struct PinnedMailbox {
     int32_t elim_flag;             // the whole-dynamics solves',
     int32_t red_flag;              // the reduced point's
     int32_t deferred_smax;         // the one-launch chain's squaring count of an enqueue-only call (smax_pending)
+    double newton[2];              // the truncated-Newton step's (status, iterations) after every iteration
 };
 
 struct Workspace { double* p = nullptr; size_t cap = 0; };   // grow-only device buffer, capacity in doubles (grow_workspace, dto_engine.cpp)
@@ -337,6 +338,10 @@ struct dto_handle {
     // host-pointer form's mu [n_cons], f and phi.
     std::unique_ptr<dto::FeasiblePlan> feas;
     dto::Workspace d_feas;
+    // truncated-Newton step (dto_projected_newton_step[_dev]; dto_newton_plan.h, dto_newton.hip).  d_newton: r, d and y / w [n_vars], the
+    // partial sums [8][chunks] and the scalars [16]; d_newton_host: the host-pointer form's mask and p [n_vars], info [8] and trace
+    // [max_iter][4].  Both grow-only, sized before anything is enqueued.  The products run in d_blk (one column).
+    dto::Workspace d_newton, d_newton_host;
     int64_t* d_conbase = nullptr;       // [n_vars+1] first constraint-pattern entry of each column
     int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
     int64_t* d_crow_col = nullptr;

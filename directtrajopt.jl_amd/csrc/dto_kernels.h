@@ -550,6 +550,29 @@ void launch_feas_scatter(hipStream_t st, const KRollout& R, int z, const double*
 void launch_feas_merit(hipStream_t st, int64_t n_dyn, int64_t n_cons, double sigma, const double* f, const double* mu, const double* g,
                        double* phi);
 
+// Truncated-Newton step (dto_newton.hip; dot order, decision and the layouts of `part` and `state`: dto_newton_plan.h).  All vectors
+// [n] in the Z layout; g is the reduced gradient, mask the caller's free mask (null: all free), w holds y = T'HT d on entry to
+// launch_newton_curv and w = M (y + shift d) behind it.
+struct KNewton {
+    int64_t n, nb;             // n_vars, newton_chunks(n_vars)
+    double *p, *r, *d, *w;
+    const double *g, *mask;
+    double *part, *state;      // [NEWTON_SLOTS][nb], [NEWTON_STATE]
+    double *info, *trace;      // [8], [max_iter][4] or null
+    double radius, shift, rtol, atol;
+    int combined;              // 0: every workgroup combines the partial sums itself; 1 (A/B, TUNING builds): launch_newton_combine did
+};
+// r = M g, p = 0, d = -r, the partial sums of r . r
+void launch_newton_start(hipStream_t st, const KReduced& R, const KNewton& A);
+// w = M (y + shift d) in place of y, the partial sums of d . w, d . d, p . d, p . p
+void launch_newton_curv(hipStream_t st, const KReduced& R, const KNewton& A);
+// iteration j >= 1: the decision, p += s d, r += s w, the partial sums behind the update, the first three entries of the trace row
+void launch_newton_step(hipStream_t st, const KReduced& R, const KNewton& A, int j);
+// j = 0 behind the start, j >= 1 behind the step: rr', the convergence test, d = beta d - r, status and iteration count, `info` on exit
+void launch_newton_dir(hipStream_t st, const KNewton& A, int j, int max_iter);
+// the A/B form of stage 2: one workgroup combines the slots slot0 .. slot0 + count - 1 (count <= 4) into state[NWS_DOTS ..] for the next launch
+void launch_newton_combine(hipStream_t st, const KNewton& A, int slot0, int count);
+
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);
 

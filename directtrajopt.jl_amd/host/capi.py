@@ -67,6 +67,7 @@ COMM_ID_BYTES = 128
 VECTOR_JACOBIAN, VECTOR_HESSIAN, VECTOR_GRADIENT, VECTOR_CONSTRAINT = 1, 2, 3, 4
 ROLLOUT_ALL, ROLLOUT_FINAL = 0, 1
 SOLVE_FORWARD, SOLVE_ADJOINT = 0, 1
+NEWTON_CONVERGED, NEWTON_BOUNDARY, NEWTON_NEG_CURVATURE, NEWTON_MAX_ITER, NEWTON_NOT_FINITE = 0, 1, 2, 3, 4
 
 H = C.c_void_p
 
@@ -126,6 +127,10 @@ SYMBOLS = {
     "dto_feasible_trajectory_dev": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dto_feasible_merit": (C.c_int, [H, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p]),
     "dto_feasible_merit_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dto_projected_newton_step": (C.c_int, [H, c_double_p, C.c_double, c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double,
+                                            C.c_int32, c_double_p, c_double_p, c_double_p]),
+    "dto_projected_newton_step_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dto_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dto_comm_create": (C.c_int, [H, C.c_void_p, C.c_int32, C.c_int32]),
     "dto_comm_set_ranges": (C.c_int, [H, C.c_int32, C.c_int32, c_int64_p, c_int64_p]),

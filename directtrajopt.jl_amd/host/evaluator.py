@@ -664,6 +664,33 @@ class Evaluator:
                                                              _dp(V), _dp(Y)))
         return Y
 
+    def reduced_newton_step(self, Z, sigma=1.0, mu=None, free=None, radius=0.0, shift=0.0, rtol=1e-6, atol=0.0, max_iter=50, trace=False):
+        """The truncated-Newton step of the reduced problem in ONE engine call (``dto_projected_newton_step``): Steihaug-Toint CG on
+        (M T'HT M + shift M) p = -M g from p = 0, g the ``reduced_lagrangian_gradient`` and T'HT the ``reduced_hessian_product`` at
+        (Z, sigma, mu), M zeroing the states of knots 2 .. N and the entries whose ``free`` value is 0.0 (``free``: (n_variables,) or
+        None for all free).  ``radius`` > 0 is a trust region (0: none); the iteration stops at ``sqrt(r.r) <= max(atol, rtol ||g||)``,
+        at the boundary, at non-positive curvature or after ``max_iter`` products.  The kept points are checked once, every dot has
+        a fixed order and every decision is made on the device (include/dto_engine.h, "Truncated-Newton step"): the same loop written
+        in NumPy around ``reduced_hessian_product`` gives the same bits.  Returns (p, info) -- p (n_variables,), info a dict with
+        ``status`` (``capi.NEWTON_*``), ``iterations``, ``gnorm``, ``rnorm``, ``pnorm``, ``pg`` = p.g, ``predicted`` = -(g'p + p'Ap / 2),
+        ``curvature`` (the last d'Ad / d'd) and ``raw`` (the eight doubles) -- and with ``trace=True`` also (iterations, 4): kappa,
+        d.d, the step along d and r.r behind it, per iteration."""
+        Z = self._Z(Z)
+        if mu is not None:
+            mu = _in(mu, self.n_constraints, "mu")
+        if free is not None:
+            free = _in(free, self.n_variables, "free")
+        max_iter = int(max_iter)
+        p = np.full(self.n_variables, np.nan)
+        raw = np.full(8, np.nan)
+        tr = np.full((max(max_iter, 0), 4), np.nan) if trace else None
+        self._check(self._lib.dto_projected_newton_step(self._h, _dp(Z), float(sigma), None if mu is None else _dp(mu),
+                                                        None if free is None else _dp(free), float(radius), float(shift), float(rtol),
+                                                        float(atol), max_iter, _dp(p), _dp(raw), None if tr is None else _dp(tr)))
+        info = dict(status=int(raw[0]), iterations=int(raw[1]), gnorm=raw[2], rnorm=raw[3], pnorm=raw[4], pg=raw[5], predicted=raw[6],
+                    curvature=raw[7], raw=raw)
+        return (p, info, tr[:info["iterations"]]) if trace else (p, info)
+
     def independent_entries(self):
         """C: the entries of Z that are no state of a knot 2 .. N (controls, timesteps, times, the states of knot 1, globals),
         ascending, 0-based -- the variables of the reduced problem."""
@@ -792,6 +819,14 @@ class Evaluator:
         form."""
         self._check(self._lib.dto_projected_hessian_products_dev(self._h, dZ, float(sigma), dmu or None, int(n_cols), dV or None,
                                                                  dY or None, stream))
+
+    def reduced_newton_step_dev(self, dZ, sigma, dmu, dfree, radius, shift, rtol, atol, max_iter, dp, dinfo, dtrace=0, stream=0):
+        """``reduced_newton_step`` on device pointers: dmu (n_constraints), dfree (n_variables) and dtrace (max_iter, 4) or 0 / None,
+        dp (n_variables), dinfo (8 doubles); works on `stream` and waits on one 16-byte readback per iteration, errors deferred as
+        for every `_dev` call.  Same bits as the host form."""
+        self._check(self._lib.dto_projected_newton_step_dev(self._h, dZ or None, float(sigma), dmu or None, dfree or None, float(radius),
+                                                            float(shift), float(rtol), float(atol), int(max_iter), dp or None,
+                                                            dinfo or None, dtrace or None, stream))
 
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod

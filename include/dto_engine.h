@@ -597,6 +597,59 @@ int dto_feasible_trajectory_dev(dto_handle* h, const double* dZ, double* dZf, vo
 int dto_feasible_merit(dto_handle* h, const double* Z, double sigma, const double* mu, double* phi, double* Zf, double* g);
 int dto_feasible_merit_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, double* dphi, double* dZf, double* dg, void* stream);
 
+/* ---- Truncated-Newton step: the inner solve of a truncated-Newton or trust-region method on the reduced problem, Steihaug-Toint CG on
+ * A p = -g in ONE engine call: the kept points are checked once, every reduction has a fixed order, every decision is made on the device.
+ *   A = M (T' H(Z; sigma, mu~) T) M + shift M, with T, mu~ and the dependent set S as in "Reduced-space operators" above;
+ *   M zeroes the entries of S and every entry i with free_mask[i] == 0.0 (free_mask [n_vars] doubles, NULL: all free; the mask of an S
+ *   entry is not read, a NaN there reaches nothing);  g = M (dto_reduced_gradient at (Z, sigma, mu)).
+ * The loop, from p = 0:
+ *     r = g, d = -r, rr = r . r;  rr == 0: CONVERGED with 0 iterations
+ *     iteration j = 1 .. max_iter:
+ *       y = T'HT d                                   (dto_reduced_hessian_product's bits, same "reduced_input_store" setting)
+ *       w = M (y + shift * d)
+ *       kappa = d . w, dd = d . d, pd = p . d, pp = p . p
+ *       kappa or rr not finite: NOT_FINITE, stop (p and r stay)
+ *       kappa <= 0: NEG_CURVATURE;  s = tau with radius > 0, else s = 1 in iteration 1 and 0 later;  p = p + s * d, r = r + s * w, stop
+ *       alpha = rr / kappa
+ *       radius > 0 and (pp + (2 * alpha) * pd) + (alpha * alpha) * dd >= radius * radius: BOUNDARY;  s = tau;  p = p + s * d, r = r + s * w, stop
+ *       s = alpha;  p = p + s * d, r = r + s * w, rr' = r . r
+ *       sqrt(rr') <= max(atol, rtol * sqrt(rr0)): CONVERGED, stop              (rr0 = g . g)
+ *       beta = rr' / rr, d = beta * d - r, rr = rr'
+ *     after max_iter iterations: MAX_ITER
+ *   tau = (-pd + sqrt(pd * pd + dd * (radius * radius - pp))) / dd, the step to the trust-region boundary.
+ * Every product, sum, difference, quotient and square root above is rounded on its own, never contracted, in the operand order written
+ * (csrc/dto_newton_plan.h holds the decision as one function, newton_decide, that the kernel calls).  A dot x . y over n_vars entries has
+ * a fixed order: the entries are cut into chunks of 256; in chunk b lane l (0 .. 63) starts from a_l = 0 and adds x_i * y_i over
+ * i = 256 b + l, + 64, .. ascending; the 64 lane sums are combined by the halving tree stated for the input-block product above
+ * (a_l += a_{l+32}, .. , a_l += a_{l+1}), P_b = a_0; one wavefront then combines the P_b the same way, lane l adding P_b over b = l,
+ * l + 64, .. ascending, then the halving tree.  No atomics; entries of S and masked entries hold exact zeros in r, d, w and p.  The step
+ * therefore equals the same loop written in NumPy around dto_reduced_hessian_product, bit for bit, and repeated calls and both
+ * entry-point families return the same bits.
+ * Outputs.  p [n_vars]: the step, exactly 0 on S and on masked entries; it must not overlap Z or the mask.  info [8]:
+ *   [0] the status (DTO_NEWTON_*)   [1] iterations run   [2] ||g|| = sqrt(rr0)   [3] the final ||r|| = sqrt(r . r)   [4] ||p|| = sqrt(p . p)
+ *   [5] p . g   [6] the predicted decrease -0.5 * (p . g + p . r), which is -(g'p + p'Ap / 2) because r = g + A p holds on every exit
+ *   [7] the last kappa / dd (0 without an iteration)
+ * trace: NULL, or [max_iter][4] with kappa, dd, s, rr' (r . r behind the update) per iteration run; later rows are left untouched.
+ * Points and costs.  The reduced point, the solves' point and the Hessian point are checked once per call, as by the block products; the
+ * call leaves them as a single product at (Z, sigma, mu) would.  An iteration is the launches of one kept-point single product (on the
+ * default route J v^ and J' w run once per iteration), three small launches and one 16-byte readback of (status, iterations); a call
+ * adds two launches and one readback before the first iteration.
+ * Workspaces, grow-only and allocated before anything is enqueued: 3 n_vars + 8 ceil(n_vars / 256) + 16 doubles, the block products'
+ * for one column, and for the host-pointer form 2 n_vars + 8 + 4 max_iter doubles.
+ * Refused with text, the handle stays usable and nothing is enqueued: what dto_reduced_hessian_product refuses; max_iter < 1; a negative
+ * or non-finite radius, rtol or atol; a non-finite shift; Z, p or info = NULL.  The host-pointer form uploads, runs the device routine on
+ * the handle's stream, downloads and blocks.  The _dev form takes device pointers (dmu, dfree_mask and dtrace may be NULL), works on
+ * `stream`, waits on the readbacks named above and defers device-side errors like every _dev call. */
+#define DTO_NEWTON_CONVERGED 0
+#define DTO_NEWTON_BOUNDARY 1
+#define DTO_NEWTON_NEG_CURVATURE 2
+#define DTO_NEWTON_MAX_ITER 3
+#define DTO_NEWTON_NOT_FINITE 4
+int dto_projected_newton_step(dto_handle* h, const double* Z, double sigma, const double* mu, const double* free_mask, double radius,
+                              double shift, double rtol, double atol, int32_t max_iter, double* p, double* info, double* trace);
+int dto_projected_newton_step_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dfree_mask, double radius,
+                                  double shift, double rtol, double atol, int32_t max_iter, double* dp, double* dinfo, double* dtrace, void* stream);
+
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
  * communicator (SURVEY.md §8b "Ownership").  No callback needs a collective: every rank's Jacobian / Hessian / gradient
@@ -769,6 +822,9 @@ int dto_profile_reset(dto_handle* h);
  * the rolled-out states into Zf and the merit sum, one launch each -- third output: BYTES as executed; it feeds no other name, "all"
  * included; the Jacobian evaluation inside counts under its own names, the trees and descents under "rollout_gather" / "rollout_tree" /
  * "rollout_descent").
+ * "newton" (dto_projected_newton_step and its _dev form: the four kernels of the step -- start, curvature pass, step, direction update --
+ * two launches per call and three per iteration; third output: BYTES as executed; it feeds no other name, "all" included; the products
+ * of the iterations count as the block products do).
  * The block products count under "hess_product", "reduced_pack" and "reduced_input" too, one launch per chunk where a single product
  * has one, with bytes as executed: matrix bytes once per tile or chunk, vector bytes per column.
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the

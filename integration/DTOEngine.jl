@@ -63,6 +63,11 @@ const DTO_ROLLOUT_ALL = Int32(0)    # rollout: the states of every knot, x_dim x
 const DTO_ROLLOUT_FINAL = Int32(1)  # rollout: the states of knot N alone, x_dim x n_cols
 const DTO_SOLVE_FORWARD = Int32(0)  # dynamics_solve: Y_{k+1} = E_k Y_k + B_{k+1}
 const DTO_SOLVE_ADJOINT = Int32(1)  # dynamics_solve: Λ_k = E_k' Λ_{k+1} + B_k
+const DTO_NEWTON_CONVERGED = Int32(0)      # newton_step: status in info[1]
+const DTO_NEWTON_BOUNDARY = Int32(1)
+const DTO_NEWTON_NEG_CURVATURE = Int32(2)
+const DTO_NEWTON_MAX_ITER = Int32(3)
+const DTO_NEWTON_NOT_FINITE = Int32(4)
 
 # ---- plain-C structs, field for field as in include/dto_engine.h ----------------------------------------------------
 struct IntegratorDesc
@@ -916,6 +921,42 @@ function feasible_merit_dev!(ev::GPUEvaluator, dφ::Ptr{Float64}, dZ::Ptr{Float6
                              dg::Ptr{Float64}, stream::Ptr{Cvoid})
     check(ev, @ccall lib.dto_feasible_merit_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dφ::Ptr{Float64},
                                                 dZf::Ptr{Float64}, dg::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
+# ---- truncated-Newton step (include/dto_engine.h, "Truncated-Newton step") ------------------------------------------------------------
+# Steihaug-Toint CG on (M T'HT M + shift M) p = -M g in one engine call: g and T'HT the reduced gradient and Hessian at (Z, σ, μ), M
+# zeroing the states of knots 2 .. N and the entries whose `free` value is 0.0.  Returns (p, info, trace): info the eight doubles of the
+# header (status, iterations, ‖g‖, ‖r‖, ‖p‖, p⋅g, predicted decrease, last curvature), trace 4 x iterations (κ, d⋅d, s, r⋅r per column).
+function newton_step(ev::GPUEvaluator, Z::AbstractVector{Float64}; σ::Float64 = 1.0, μ::Union{Nothing,AbstractVector{Float64}} = nothing,
+                     free::Union{Nothing,AbstractVector{Float64}} = nothing, radius::Float64 = 0.0, shift::Float64 = 0.0,
+                     rtol::Float64 = 1e-6, atol::Float64 = 0.0, max_iter::Integer = 50)
+    reduced_check_lengths(ev, "newton_step", Z, μ, free)
+    max_iter >= 1 || error("newton_step: max_iter = $max_iter, at least 1 iteration is required")
+    Zv = Vector{Float64}(Z)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    fv = free === nothing ? Float64[] : Vector{Float64}(free)
+    p = fill(NaN, ev.n_variables)
+    info = fill(NaN, 8)
+    trace = fill(NaN, 4, Int(max_iter))
+    mi = Int32(max_iter)
+    GC.@preserve Zv μv fv p info trace begin
+        μp = μ === nothing ? Ptr{Float64}(C_NULL) : pointer(μv)
+        fp = free === nothing ? Ptr{Float64}(C_NULL) : pointer(fv)
+        check(ev, @ccall lib.dto_projected_newton_step(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μp::Ptr{Float64}, fp::Ptr{Float64},
+                                                       radius::Float64, shift::Float64, rtol::Float64, atol::Float64, mi::Int32,
+                                                       p::Ptr{Float64}, info::Ptr{Float64}, trace::Ptr{Float64})::Cint)
+    end
+    return p, info, trace[:, 1:Int(info[2])]
+end
+
+# the same on device pointers, on `stream` (one 16-byte readback per iteration); dμ, dfree and dtrace may be C_NULL
+function newton_step_dev!(ev::GPUEvaluator, dp::Ptr{Float64}, dinfo::Ptr{Float64}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64},
+                          dfree::Ptr{Float64}, radius::Float64, shift::Float64, rtol::Float64, atol::Float64, max_iter::Integer,
+                          dtrace::Ptr{Float64}, stream::Ptr{Cvoid})
+    mi = Int32(max_iter)
+    check(ev, @ccall lib.dto_projected_newton_step_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dfree::Ptr{Float64},
+                                                           radius::Float64, shift::Float64, rtol::Float64, atol::Float64, mi::Int32,
+                                                           dp::Ptr{Float64}, dinfo::Ptr{Float64}, dtrace::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 end
 
 # row bounds handed to the solver (src/solvers/solve.jl:30-65)

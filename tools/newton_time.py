@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""The truncated-Newton step as one engine call (Evaluator.reduced_newton_step_dev) beside the same CG written by hand around
+reduced_hessian_product_dev with torch reductions, timed with HIP events (a tools/ probe; GPU).
+
+Per shape, in ONE process, on ``synthetic.multi_ket_problem(n, 1, drives, N, scale)`` -- one ket with skew-symmetric generators, its
+DerivativeIntegrator(u, du) and the knot constraint on u -- with option "reduced_input_store" = 1, at the kept point of
+(Z, sigma = 0.7, a random mu), device-resident inputs and outputs.  shift = 2 max |Rayleigh quotient| over 8 power iterations with the
+engine's product, so A = M T'HT M + shift M is positive definite with a condition number of at most 3; rtol = 0, so both loops run
+exactly ``max_iter`` iterations (10 and 30) and end with MAX_ITER.
+
+The YARDSTICK is what a user writes today: per iteration one reduced_hessian_product_dev (which checks its kept points: two 4-byte
+readbacks on this route), w = mask * (y + shift d), torch.dot for kappa and rr', alpha and beta as Python floats (.item(): a host
+synchronisation each) -- the existing code, not the code under test.  Its result agrees with the engine's to rounding, not to the bit:
+torch's reduction order is its own.
+
+After a warm-up of at least 30 ms of GPU work per member, single calls ALTERNATE (yardstick, engine step, yardstick, ...); medians of
+``--reps`` each with the yardstick's min .. max.  Beside them: the median of a kept-point reduced_hessian_product_dev alone, the
+"newton" profile name of one step (device milliseconds, launches and bytes, and both per iteration), and
+    step_minus_products_ms = step - max_iter x product        (what the step costs beyond its products: the "newton" kernels, the
+                                                               readbacks, and the point checks it does NOT repeat count negative)
+
+A/B of how the step sums the chunk sums of its dots, one process per form on the TUNING library; the line says which
+form ran ("combine_form"):
+
+    DTO_ENGINE_LIB=libdto_engine_t.so DTO_NEWTON_COMBINE=0 python tools/newton_time.py   # every workgroup for itself (the engine's form)
+    DTO_ENGINE_LIB=libdto_engine_t.so DTO_NEWTON_COMBINE=1 python tools/newton_time.py   # a one-workgroup launch of its own
+
+One JSON line per shape.
+
+    python tools/newton_time.py                       # 256 x 2000 and 64 x 1000
+    python tools/newton_time.py --shapes 128x1000 --reps 9 --iters 10,30
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+import dto_amd  # noqa: E402
+
+SIGMA = 0.7
+
+
+def event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def alternating(yardstick, call, reps):
+    """medians of `reps` single calls each, the two alternating; the yardstick's spread"""
+    for fn in (yardstick, call):
+        spent = 0.0
+        while spent < 30.0:          # warm-up: at least 30 ms of work
+            spent += event_ms(fn)
+    ys, cs = [], []
+    for _ in range(reps):
+        ys.append(event_ms(yardstick))
+        cs.append(event_ms(call))
+    return {"yardstick_ms": round(statistics.median(ys), 4), "step_ms": round(statistics.median(cs), 4),
+            "yardstick_min_ms": round(min(ys), 4), "yardstick_max_ms": round(max(ys), 4),
+            "step_min_ms": round(min(cs), 4), "step_max_ms": round(max(cs), 4),
+            "difference_ms": round(statistics.median(cs) - statistics.median(ys), 4)}
+
+
+def measure(n, N, drives, scale, reps, iters):
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    prob = dto_amd.host.synthetic.multi_ket_problem(n, 1, drives, N, seed=42, u_bound=4.0, scale=scale or None)
+    ev = dto_amd.Evaluator(prob)
+    ev.set_option("reduced_input_store", 1)
+    tuning = "_t" in os.environ.get("DTO_ENGINE_LIB", "")   # the product library reads no environment variable
+    form = "own_launch" if tuning and os.environ.get("DTO_NEWTON_COMBINE", "0") not in ("", "0") else "every_workgroup"
+    out = {"n": n, "knots": N, "drives": drives, "scale": scale, "reps": reps, "sigma": SIGMA, "route": "reduced_input_store",
+           "combine_form": form}
+    try:
+        Zh = np.ascontiguousarray(prob.trajectory.vec(), dtype=np.float64)
+        Z = torch.from_numpy(Zh).to(dev)
+        gen = torch.Generator(device=dev); gen.manual_seed(7)
+        mu = torch.randn(ev.n_constraints, dtype=torch.float64, device=dev, generator=gen)
+        f64 = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
+        nv = ev.n_variables
+        g, y, p, info = f64(nv), f64(nv), f64(nv), f64(8)
+        mask = torch.zeros(nv, dtype=torch.float64, device=dev)
+        mask[torch.from_numpy(ev.independent_entries()).to(dev)] = 1.0
+        out["n_variables"], out["chunks"] = nv, -(-nv // 256)
+        prod = lambda v, o: ev.reduced_hessian_product_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), v.data_ptr(), o.data_ptr(), st)
+        ev.reduced_gradient_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), g.data_ptr(), 0, st)
+        v = torch.randn(nv, dtype=torch.float64, device=dev, generator=gen) * mask
+        top = 0.0
+        for _ in range(8):
+            v = v / torch.linalg.norm(v)
+            prod(v, y)
+            top = max(top, abs(float(torch.dot(v, y))))
+            v = y.clone()
+        shift = 2.0 * top
+        out["shift"] = shift
+
+        def product_alone():
+            prod(v, y)
+
+        for _ in range(5):
+            event_ms(product_alone)
+        out["product_kept_ms"] = round(statistics.median(event_ms(product_alone) for _ in range(reps)), 4)
+
+        def hand(max_iter):
+            """the CG a user writes today: the engine's product, torch reductions, decisions on the host"""
+            r = g * mask
+            x = torch.zeros_like(r)
+            d = -r
+            rr = torch.dot(r, r).item()
+            for _ in range(max_iter):
+                prod(d, y)
+                w = mask * (y + shift * d)
+                kappa = torch.dot(d, w).item()
+                if not kappa > 0.0:
+                    break
+                alpha = rr / kappa
+                x += alpha * d
+                r += alpha * w
+                rr_new = torch.dot(r, r).item()
+                d = (rr_new / rr) * d - r
+                rr = rr_new
+            return x
+
+        for max_iter in iters:
+            step = lambda: ev.reduced_newton_step_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), 0, 0.0, shift, 0.0, 0.0, max_iter, p.data_ptr(),
+                                                      info.data_ptr(), 0, st)
+            pair = alternating(lambda: hand(max_iter), step, reps)
+            x = hand(max_iter)
+            step(); torch.cuda.synchronize()
+            raw = info.cpu().numpy()
+            pair["status"], pair["iterations"] = int(raw[0]), int(raw[1])
+            pair["step_against_yardstick_relative"] = float(torch.linalg.norm(p - x) / torch.linalg.norm(x))
+            ev.profile_enable(True); ev.profile_reset(); step(); torch.cuda.synchronize()
+            ms, launches, nbytes = ev.profile_get("newton")
+            ev.profile_enable(False)
+            pair["newton_profile"] = {"ms": round(ms, 4), "launches": launches, "bytes": nbytes, "ms_per_iteration": round(ms / max_iter, 5),
+                                      "bytes_per_iteration": nbytes / max_iter}
+            pair["step_minus_products_ms"] = round(pair["step_ms"] - max_iter * out["product_kept_ms"], 4)
+            out[f"max_iter_{max_iter}"] = pair
+        return out
+    finally:
+        ev.close()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--shapes", default="256x2000,64x1000", help="comma-separated states x knots")
+    ap.add_argument("--drives", type=int, default=4)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--iters", default="10,30", help="comma-separated iteration counts")
+    ap.add_argument("--scale", type=float, default=1.0, help="standard deviation of the generators' entries (1.0: the norms of the\n"
+                    "headline benchmark; 0: 1 / sqrt(n), norms of order one)")
+    a = ap.parse_args()
+    for s in a.shapes.split(","):
+        n, N = (int(x) for x in s.lower().split("x"))
+        print(json.dumps(measure(n, N, a.drives, a.scale, a.reps, [int(i) for i in a.iters.split(",")])), flush=True)
+
+
+if __name__ == "__main__":
+    main()
