@@ -4,6 +4,7 @@
 // propagator chain, the callbacks, the transfer plans, the extern "C" entry points other than dto_create, the communicator and
 // profiling.  There is NO CPU fallback: every evaluation runs on the GPU or fails with an error code.
 #include "dto_handle.h"
+#include "dto_newton_box_plan.h"
 #include "dto_newton_plan.h"
 #include "dto_rollout_plan.h"
 
@@ -74,7 +75,7 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25, CAT_FEASIBLE = 26, CAT_NEWTON = 27 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25, CAT_FEASIBLE = 26, CAT_NEWTON = 27, CAT_NEWTON_BOX = 28 };
 // CAT_ROLLOUT .. CAT_ROLLOUT_DESCENT ("rollout" = its parts "rollout_gather" + "rollout_tree" + "rollout_descent"): the gather, the
 // tree's products and the descent (with the start and the copy into the caller's layout) of dto_rollout[_dev], flops as executed with
 // padding; the tree's products run launch_bgemm_plain and count HERE, not under "bgemm_plain"; they feed no other name, "all" included
@@ -98,6 +99,7 @@ inline bool is_elim_cat(int cat) { return cat == CAT_DYNSOLVE_COUPLE || cat == C
 // CAT_NEWTON ("newton"): the four kernels of dto_newton.hip -- the start, the curvature pass, the step and the direction update of
 // dto_projected_newton_step and its _dev form; BYTES as executed; it feeds no other name, "all" included.  The products of the
 // iterations count under the names of the block products.
+// CAT_NEWTON_BOX ("newton_box"): the four kernels of dto_newton_box.hip, of dto_projected_newton_step_box and its _dev form, likewise.
 // The block products (dto_eval_hessian_products, dto_projected_hessian_products) count under the same names -- "hess_product",
 // "reduced_pack", "reduced_input" -- one launch per chunk each, bytes as executed: the matrices once per tile or chunk, the vectors per column.
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
@@ -3089,6 +3091,122 @@ int dto_projected_newton_step_dev(dto_handle* h, const double* dZ, double sigma,
     }, G_ASYNC, (hipStream_t)stream);
 }
 
+// ---- bound-constrained truncated-Newton step (include/dto_engine.h, "Bound-constrained truncated-Newton step"; dto_newton_box.hip,
+// dto_newton_box_plan.h): newton_step's shape with lower and upper bounds on the independent entries.
+
+// [a, a + n) and [b, b + n) share an entry (a null pointer overlaps nothing)
+static bool ranges_overlap(const double* a, const double* b, size_t n) {
+    if (!a || !b) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = n * sizeof(double);
+    return x < y + len && y < x + len;
+}
+
+// What a box step names beyond newton_refusal: the outputs must not overlap Z, the mask or the bounds.
+static std::string newton_box_refusal(const std::string& who, size_t n, const double* Z, const double* mask, const double* lo, const double* hi,
+                                      const double* p, const double* zp, const double* es) {
+    const std::pair<const char*, const double*> outs[] = {{"p", p}, {"Zp", zp}, {"entry_state", es}};
+    const std::pair<const char*, const double*> ins[] = {{"Z", Z}, {"free_mask", mask}, {"lo", lo}, {"hi", hi}};
+    for (const auto& o : outs)
+        for (const auto& i : ins)
+            if (ranges_overlap(o.second, i.second, n)) return who + ": " + o.first + " overlaps " + i.first;
+    return "";
+}
+
+struct NewtonBoxArgs {
+    const double *mask, *lo, *hi;       // device pointers or null
+    double radius, shift, rtol, atol;
+    int max_iter;
+    double *p, *info, *trace, *entry_state, *zp;
+};
+
+// The device routine both entry-point families run: everything on `st`, every pointer a device pointer.
+static void newton_box_step(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, const NewtonBoxArgs& a, hipStream_t st) {
+    const KReduced& R = h->red;
+    const int64_t n = h->n_vars, nb = newton_chunks(n);
+    const bool store_route = h->reduced_input_store && h->K >= 1;
+    // every workspace before anything is enqueued
+    double* q = grow_workspace(h, h->d_newton_box, (size_t)newton_box_workspace_doubles(n));
+    const BlockWork B = block_workspaces(h, p, 1, store_route);
+    KNewtonBox A{};
+    A.n = n; A.nb = nb;
+    A.p = a.p; A.r = q; A.d = q + n; A.w = q + 2 * n;
+    A.part = q + 3 * n; A.state = A.part + NEWTON_BOX_SLOTS * nb;
+    A.es = (unsigned char*)(A.state + NEWTON_BOX_STATE);
+    A.g = h->red_r; A.mask = a.mask; A.Z = dZ; A.lo = a.lo; A.hi = a.hi;
+    A.info = a.info; A.trace = a.trace; A.zp = a.zp; A.es_out = a.entry_state;
+    A.radius = a.radius; A.shift = a.shift; A.rtol = a.rtol; A.atol = a.atol;
+    const ElimWork EW = projected_points(h, p, dZ, sigma, dmu, 1, st);
+    // bytes as executed: the vectors each kernel reads and writes (mask, bounds and the optional outputs where given), the state bytes,
+    // its partial results, and per workgroup the partial results it combines.  (Z and the bounds are read on free entries only; they
+    // are counted whole.)
+    const double v = 8.0 * (double)n, by = (double)n, m = a.mask ? v : 0.0, bounds = (a.lo ? v : 0.0) + (a.hi ? v : 0.0);
+    const double outs = (a.zp ? v : 0.0) + (a.entry_state ? v : 0.0), part = 8.0 * (double)nb, groups = (double)((nb + 15) / 16);
+    auto running = [&] {   // the one readback per iteration
+        HIP_CHECK(hipMemcpyAsync(h->mailbox->newton, A.state, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return (int)h->mailbox->newton[NBS_STATUS] == NEWTON_CONTINUE;
+    };
+    { ProfScope ps(h, st, CAT_NEWTON_BOX, 5.0 * v + m + bounds + by + outs + 7.0 * part); launch_newton_box_start(st, R, A); }
+    { ProfScope ps(h, st, CAT_NEWTON_BOX, (groups + 6.0) * part); launch_newton_box_dir(st, A, 0, a.max_iter); }
+    for (int j = 1; j <= a.max_iter && running(); ++j) {
+        projected_chunk(h, p, B, EW, store_route, dZ, 1, A.d, A.w, st);   // y = T'HT d
+        { ProfScope ps(h, st, CAT_NEWTON_BOX, 5.0 * v + bounds + by + 5.0 * part); launch_newton_box_curv(st, A); }
+        { ProfScope ps(h, st, CAT_NEWTON_BOX, 8.0 * v + bounds + 2.0 * by + outs + 6.0 * part + groups * 5.0 * part); launch_newton_box_step(st, A, j); }
+        { ProfScope ps(h, st, CAT_NEWTON_BOX, 3.0 * v + by + (2.0 * groups + 5.0) * part); launch_newton_box_dir(st, A, j, a.max_iter); }
+    }
+}
+
+int dto_projected_newton_step_box(dto_handle* h, const double* Z, double sigma, const double* mu, const double* free_mask, const double* lo,
+                                  const double* hi, double radius, double shift, double rtol, double atol, int32_t max_iter, double* p,
+                                  double* info, double* trace, double* entry_state, double* Zp) {
+    const std::string who = "dto_projected_newton_step_box";
+    if (!h) return fail(nullptr, "null handle");
+    std::string bad = newton_refusal(who, Z, radius, shift, rtol, atol, max_iter, p, info);
+    if (bad.empty()) bad = newton_box_refusal(who, (size_t)h->n_vars, Z, free_mask, lo, hi, p, Zp, entry_state);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, true);
+        reduced_workspaces(h, ep);
+        const size_t n = (size_t)h->n_vars, nt = NEWTON_BOX_TRACE * (size_t)max_iter, bytes = sizeof(double) * n;
+        grow_workspace(h, h->d_newton_box, (size_t)newton_box_workspace_doubles(h->n_vars));   // before the uploads are enqueued
+        block_workspaces(h, ep, 1, h->reduced_input_store && h->K >= 1);
+        double* q = grow_workspace(h, h->d_newton_box_host, 6 * n + NEWTON_BOX_INFO + nt);
+        double *dmask = q, *dlo = q + n, *dhi = q + 2 * n, *dp = q + 3 * n, *dzp = q + 4 * n, *des = q + 5 * n, *dinfo = q + 6 * n;
+        double* dtrace = dinfo + NEWTON_BOX_INFO;
+        upload_Z(h, Z);
+        if (mu && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->red_hmu, mu, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        if (free_mask) HIP_CHECK(hipMemcpyAsync(dmask, free_mask, bytes, hipMemcpyHostToDevice, h->stream));
+        if (lo) HIP_CHECK(hipMemcpyAsync(dlo, lo, bytes, hipMemcpyHostToDevice, h->stream));
+        if (hi) HIP_CHECK(hipMemcpyAsync(dhi, hi, bytes, hipMemcpyHostToDevice, h->stream));
+        // the rows of the trace the step does not reach keep the caller's values
+        if (trace) HIP_CHECK(hipMemcpyAsync(dtrace, trace, sizeof(double) * nt, hipMemcpyHostToDevice, h->stream));
+        const NewtonBoxArgs a{free_mask ? dmask : nullptr, lo ? dlo : nullptr, hi ? dhi : nullptr, radius, shift, rtol, atol, max_iter, dp, dinfo,
+                              trace ? dtrace : nullptr, entry_state ? des : nullptr, Zp ? dzp : nullptr};
+        newton_box_step(h, ep, h->d_Z, sigma, mu ? h->red_hmu : nullptr, a, h->stream);
+        HIP_CHECK(hipMemcpyAsync(p, dp, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipMemcpyAsync(info, dinfo, sizeof(double) * NEWTON_BOX_INFO, hipMemcpyDeviceToHost, h->stream));
+        if (trace) HIP_CHECK(hipMemcpyAsync(trace, dtrace, sizeof(double) * nt, hipMemcpyDeviceToHost, h->stream));
+        if (entry_state) HIP_CHECK(hipMemcpyAsync(entry_state, des, bytes, hipMemcpyDeviceToHost, h->stream));
+        if (Zp) HIP_CHECK(hipMemcpyAsync(Zp, dzp, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_projected_newton_step_box_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dfree_mask, const double* dlo,
+                                      const double* dhi, double radius, double shift, double rtol, double atol, int32_t max_iter, double* dp,
+                                      double* dinfo, double* dtrace, double* dentry_state, double* dZp, void* stream) {
+    const std::string who = "dto_projected_newton_step_box_dev";
+    if (!h) return fail(nullptr, "null handle");
+    std::string bad = newton_refusal(who, dZ, radius, shift, rtol, atol, max_iter, dp, dinfo);
+    if (bad.empty()) bad = newton_box_refusal(who, (size_t)h->n_vars, dZ, dfree_mask, dlo, dhi, dp, dZp, dentry_state);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, true);
+        reduced_workspaces(h, ep);
+        const NewtonBoxArgs a{dfree_mask, dlo, dhi, radius, shift, rtol, atol, max_iter, dp, dinfo, dtrace, dentry_state, dZp};
+        newton_box_step(h, ep, dZ, sigma, dmu, a, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
 int dto_projected_hessian_products(dto_handle* h, const double* Z, double sigma, const double* mu, int32_t n_cols, const double* V, double* Y) {
     return guarded(h, [&] {
         const std::string who = "dto_projected_hessian_products";
@@ -3532,6 +3650,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "reduced_input")) cat = CAT_REDUCED_INPUT;
         else if (!strcmp(name, "feasible")) cat = CAT_FEASIBLE;
         else if (!strcmp(name, "newton")) cat = CAT_NEWTON;
+        else if (!strcmp(name, "newton_box")) cat = CAT_NEWTON_BOX;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -3561,7 +3680,8 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (is_rollout_cat(r.cat) ? !(any_rollout || r.cat == cat) : any_rollout) continue;   // ("all": the rollout is no callback)
             if (is_dynsolve_cat(r.cat) ? !(any_dynsolve || r.cat == cat) : any_dynsolve) continue;   // (nor are the solves)
             if (is_elim_cat(r.cat) && r.cat != cat) continue;
-            if ((r.cat == CAT_REDUCED_PACK || r.cat == CAT_REDUCED_INPUT || r.cat == CAT_FEASIBLE || r.cat == CAT_NEWTON) && r.cat != cat) continue;
+            if ((r.cat == CAT_REDUCED_PACK || r.cat == CAT_REDUCED_INPUT || r.cat == CAT_FEASIBLE || r.cat == CAT_NEWTON || r.cat == CAT_NEWTON_BOX) &&
+                r.cat != cat) continue;
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));

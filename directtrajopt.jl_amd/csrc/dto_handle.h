@@ -342,6 +342,10 @@ struct dto_handle {
     // partial sums [8][chunks] and the scalars [16]; d_newton_host: the host-pointer form's mask and p [n_vars], info [8] and trace
     // [max_iter][4].  Both grow-only, sized before anything is enqueued.  The products run in d_blk (one column).
     dto::Workspace d_newton, d_newton_host;
+    // bound-constrained step (dto_projected_newton_step_box[_dev]; dto_newton_box_plan.h, dto_newton_box.hip).  d_newton_box: r, d and
+    // y / w [n_vars], the partial results [12][chunks], the scalars [16] and the state bytes [n_vars]; d_newton_box_host: the
+    // host-pointer form's mask, lo, hi, p, Zp and entry_state [n_vars] each, info [12] and trace [max_iter][6].  Grow-only like the above.
+    dto::Workspace d_newton_box, d_newton_box_host;
     int64_t* d_conbase = nullptr;       // [n_vars+1] first constraint-pattern entry of each column
     int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
     int64_t* d_crow_col = nullptr;

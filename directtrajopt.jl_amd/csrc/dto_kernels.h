@@ -573,6 +573,28 @@ void launch_newton_dir(hipStream_t st, const KNewton& A, int j, int max_iter);
 // the A/B form of stage 2: one workgroup combines the slots slot0 .. slot0 + count - 1 (count <= 4) into state[NWS_DOTS ..] for the next launch
 void launch_newton_combine(hipStream_t st, const KNewton& A, int slot0, int count);
 
+// Bound-constrained truncated-Newton step (dto_newton_box.hip; the entry rules, the decision, the loop and the layouts of `part` and
+// `state`: dto_newton_box_plan.h).  As KNewton; Z the point, lo / hi the bounds (null: none), es the state bytes, zp and es_out the
+// optional outputs (null: not written).
+struct KNewtonBox {
+    int64_t n, nb;
+    double *p, *r, *d, *w;
+    const double *g, *mask, *Z, *lo, *hi;
+    unsigned char* es;         // [n]
+    double *part, *state;      // [NEWTON_BOX_SLOTS][nb], [NEWTON_BOX_STATE]
+    double *info, *trace;      // [12], [max_iter][6] or null
+    double *zp, *es_out;       // [n] or null
+    double radius, shift, rtol, atol;
+};
+// the states, r = g on F0, p = 0, d = -r, the partial sums of r . r and the counts of free and held entries
+void launch_newton_box_start(hipStream_t st, const KReduced& R, const KNewtonBox& A);
+// w = y + shift d on F0 in place of y, the partial sums of d . w, d . d, p . d, p . p and the chunk's smallest breakpoint
+void launch_newton_box_curv(hipStream_t st, const KNewtonBox& A);
+// iteration j >= 1: the decision, the update with its clamps, the states, the optional outputs, the partial results behind the update
+void launch_newton_box_step(hipStream_t st, const KNewtonBox& A, int j);
+// j = 0 behind the start, j >= 1 behind the step: the convergence test, the restart or the beta step, status, counts, `info` on exit
+void launch_newton_box_dir(hipStream_t st, const KNewtonBox& A, int j, int max_iter);
+
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);
 

@@ -68,6 +68,8 @@ VECTOR_JACOBIAN, VECTOR_HESSIAN, VECTOR_GRADIENT, VECTOR_CONSTRAINT = 1, 2, 3, 4
 ROLLOUT_ALL, ROLLOUT_FINAL = 0, 1
 SOLVE_FORWARD, SOLVE_ADJOINT = 0, 1
 NEWTON_CONVERGED, NEWTON_BOUNDARY, NEWTON_NEG_CURVATURE, NEWTON_MAX_ITER, NEWTON_NOT_FINITE = 0, 1, 2, 3, 4
+# entry states of the bound-constrained step (DTO_BOX_* in include/dto_engine.h)
+BOX_FIXED, BOX_FREE, BOX_HELD_LOWER, BOX_HELD_UPPER, BOX_HIT_LOWER, BOX_HIT_UPPER = 0, 1, 2, 3, 4, 5
 
 H = C.c_void_p
 
@@ -131,6 +133,11 @@ SYMBOLS = {
                                             C.c_int32, c_double_p, c_double_p, c_double_p]),
     "dto_projected_newton_step_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
                                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dto_projected_newton_step_box": (C.c_int, [H, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, C.c_double,
+                                                C.c_double, C.c_double, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "dto_projected_newton_step_box_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                                    C.c_double, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]),
     "dto_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dto_comm_create": (C.c_int, [H, C.c_void_p, C.c_int32, C.c_int32]),
     "dto_comm_set_ranges": (C.c_int, [H, C.c_int32, C.c_int32, c_int64_p, c_int64_p]),

@@ -691,6 +691,49 @@ class Evaluator:
                     curvature=raw[7], raw=raw)
         return (p, info, tr[:info["iterations"]]) if trace else (p, info)
 
+    def reduced_newton_step_box(self, Z, sigma=1.0, mu=None, lo=None, hi=None, free=None, radius=0.0, shift=0.0, rtol=1e-6, atol=0.0,
+                                max_iter=50, trace=False, states=False, trajectory=False):
+        """``reduced_newton_step`` with simple bounds ``lo <= Z + p <= hi`` on the independent entries, in ONE engine call
+        (``dto_projected_newton_step_box``).  ``lo``, ``hi``: (n_variables,) or None for none (``Problem.bounds_vectors`` expands
+        per-component bounds); their values at the states of knots 2 .. N and at masked entries are not read.  An entry on a bound whose
+        gradient points outward is held from the start; a step that would leave the box stops at the face, the entries that reached it
+        are fixed there and the solve restarts on the face; a direction of non-positive curvature is followed to the face
+        (include/dto_engine.h, "Bound-constrained truncated-Newton step": the same loop written in NumPy around
+        ``reduced_hessian_product`` gives the same bits, and without bounds the bits of ``reduced_newton_step``).  Returns (p, info
+        [, trace][, states][, Zp]): info as ``reduced_newton_step``'s with ``held``, ``hit``, ``restarts``, ``n_free`` and ``raw`` (twelve
+        doubles); ``trace=True`` adds (iterations, 6): kappa, d.d, s, r.r over the free set, tau_box, entries hit; ``states=True`` the
+        codes ``capi.BOX_*`` per entry as doubles (usable as the next call's ``free``); ``trajectory=True`` Zp = Z + p with the entries
+        that hit a bound holding it exactly -- the point to give ``feasible_merit`` next."""
+        Z = self._Z(Z)
+        if mu is not None:
+            mu = _in(mu, self.n_constraints, "mu")
+        if free is not None:
+            free = _in(free, self.n_variables, "free")
+        if lo is not None:
+            lo = _in(lo, self.n_variables, "lo")
+        if hi is not None:
+            hi = _in(hi, self.n_variables, "hi")
+        max_iter = int(max_iter)
+        opt = lambda a: None if a is None else _dp(a)
+        p = np.full(self.n_variables, np.nan)
+        raw = np.full(12, np.nan)
+        tr = np.full((max(max_iter, 0), 6), np.nan) if trace else None
+        es = np.full(self.n_variables, np.nan) if states else None
+        zp = np.full(self.n_variables, np.nan) if trajectory else None
+        self._check(self._lib.dto_projected_newton_step_box(self._h, _dp(Z), float(sigma), opt(mu), opt(free), opt(lo), opt(hi), float(radius),
+                                                            float(shift), float(rtol), float(atol), max_iter, _dp(p), _dp(raw), opt(tr),
+                                                            opt(es), opt(zp)))
+        info = dict(status=int(raw[0]), iterations=int(raw[1]), gnorm=raw[2], rnorm=raw[3], pnorm=raw[4], pg=raw[5], predicted=raw[6],
+                    curvature=raw[7], held=int(raw[8]), hit=int(raw[9]), restarts=int(raw[10]), n_free=int(raw[11]), raw=raw)
+        out = (p, info)
+        if trace:
+            out += (tr[:info["iterations"]],)
+        if states:
+            out += (es,)
+        if trajectory:
+            out += (zp,)
+        return out
+
     def independent_entries(self):
         """C: the entries of Z that are no state of a knot 2 .. N (controls, timesteps, times, the states of knot 1, globals),
         ascending, 0-based -- the variables of the reduced problem."""
@@ -827,6 +870,16 @@ class Evaluator:
         self._check(self._lib.dto_projected_newton_step_dev(self._h, dZ or None, float(sigma), dmu or None, dfree or None, float(radius),
                                                             float(shift), float(rtol), float(atol), int(max_iter), dp or None,
                                                             dinfo or None, dtrace or None, stream))
+
+    def reduced_newton_step_box_dev(self, dZ, sigma, dmu, dfree, dlo, dhi, radius, shift, rtol, atol, max_iter, dp, dinfo, dtrace=0,
+                                    dstates=0, dZp=0, stream=0):
+        """``reduced_newton_step_box`` on device pointers: dmu (n_constraints), dfree, dlo, dhi, dstates and dZp (n_variables) and
+        dtrace (max_iter, 6) or 0 / None, dp (n_variables), dinfo (12 doubles); works on `stream` and waits on one 16-byte readback
+        per iteration, errors deferred as for every `_dev` call.  Same bits as the host form."""
+        self._check(self._lib.dto_projected_newton_step_box_dev(self._h, dZ or None, float(sigma), dmu or None, dfree or None, dlo or None,
+                                                                dhi or None, float(radius), float(shift), float(rtol), float(atol),
+                                                                int(max_iter), dp or None, dinfo or None, dtrace or None, dstates or None,
+                                                                dZp or None, stream))
 
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod

@@ -485,3 +485,30 @@ class DirectTrajOptProblem:
         self.objective = objective
         self.integrators = [integrators] if not isinstance(integrators, (list, tuple)) else list(integrators)
         self.constraints = list(constraints)
+
+    def bounds_vectors(self, bounds):
+        """Per-component simple bounds ``{name: (lo, hi)}`` expanded over all knots into the two (n_variables,) vectors of
+        ``Evaluator.reduced_newton_step_box``, in the trajectory's layout (knot-major, a knot's components at their offsets, the
+        global components behind the last knot) -- the data a BoundsConstraint of the reference carries
+        (src/constraints/linear/bounds_constraint.jl).  ``lo`` and ``hi`` are scalars or vectors with one value per row of the
+        component; None stands for no bound on that side.  Entries no bound names hold -inf / +inf."""
+        traj = self.trajectory
+        N, dim = traj.N, traj.dim
+        lo = np.full(N * dim + traj.global_dim, -np.inf)
+        hi = np.full(N * dim + traj.global_dim, np.inf)
+        for name, pair in bounds.items():
+            if name in traj.components:
+                idx = np.asarray(traj.components[name])
+                idx = (np.arange(N)[:, None] * dim + idx[None, :])       # (N, rows)
+            elif name in traj.global_components:
+                idx = (N * dim + np.asarray(traj.global_components[name]))[None, :]
+            else:
+                raise KeyError(f"bounds_vectors: the trajectory has no component {name!r}")
+            if len(pair) != 2:
+                raise ValueError(f"bounds_vectors: {name!r} needs a pair (lo, hi)")
+            for vec, value, none in ((lo, pair[0], -np.inf), (hi, pair[1], np.inf)):
+                value = np.asarray(none if value is None else value, dtype=np.float64)
+                if value.ndim > 1 or (value.ndim == 1 and value.size != idx.shape[1]):
+                    raise ValueError(f"bounds_vectors: {name!r} has {idx.shape[1]} rows, the bound has shape {value.shape}")
+                vec[idx] = value       # (a scalar or a row, broadcast over the knots)
+        return lo, hi

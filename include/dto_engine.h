@@ -650,6 +650,73 @@ int dto_projected_newton_step(dto_handle* h, const double* Z, double sigma, cons
 int dto_projected_newton_step_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dfree_mask, double radius,
                                   double shift, double rtol, double atol, int32_t max_iter, double* dp, double* dinfo, double* dtrace, void* stream);
 
+/* ---- Bound-constrained truncated-Newton step: the step above with simple bounds lo <= Z + p <= hi on the independent entries (the
+ * drives' derivatives, the timesteps, the states of knot 1, the drives where no DerivativeIntegrator eliminates them).  A step that would
+ * leave the box stops at the face, the entries that reached it are fixed there, and the solve goes on along the face; a direction of
+ * non-positive curvature is followed to the face.  One engine call; A, M, g, T, mu~ and S as above.
+ *   lo, hi [n_vars] doubles, either may be NULL (all -inf / all +inf); the entries of S and the masked entries are not read.  lo_i > hi_i
+ *   on a free entry is the caller's error and is not detected: the rules below still define the result.
+ * Entry states, one code per entry (the optional output entry_state holds them as doubles, and can be passed back as the next call's
+ * free_mask: every non-zero is free to be decided again):
+ *   0 fixed (in S, or free_mask[i] == 0.0)   1 free   2 / 3 held at the lower / upper bound from the start
+ *   4 / 5 hit the lower / upper bound during the call
+ * F0 is the set of entries in state 1 behind the start (later in state 1, 4 or 5), F the set in state 1 now; F only shrinks.
+ * The loop, from p = 0:
+ *     an entry that is not fixed:  Z_i <= lo_i and g_i > 0: state 2 (tested first);  Z_i >= hi_i and g_i < 0: state 3;  otherwise state 1
+ *     r = g on F0, 0 elsewhere;  d = -r;  rr0 = rr = r . r;  rr == 0: CONVERGED with 0 iterations
+ *     iteration j = 1 .. max_iter:
+ *       y = T'HT d                                   (dto_reduced_hessian_product's bits, same "reduced_input_store" setting)
+ *       w = y + shift * d on F0, 0 elsewhere         (r is kept on all of F0: r = g + A0 p stays true there, A0 = A restricted to F0)
+ *       kappa = d . w, dd = d . d, pd = p . d, pp = p . p
+ *       t_i, for i in F with d_i != 0:  max(0, (hi_i - (Z_i + p_i)) / d_i) for d_i > 0,  max(0, (lo_i - (Z_i + p_i)) / d_i) for d_i < 0
+ *       tau_box = the smallest t_i that is no NaN, +inf where there is none
+ *       (status, s) = the decision of the step above from kappa, dd, pd, pp, rr, radius (NOT_FINITE, NEG_CURVATURE, BOUNDARY or "go on"
+ *                     with s = alpha);  NOT_FINITE: stop (p and r stay)
+ *       NEG_CURVATURE, radius == 0 and tau_box finite:  s = tau_box and the solve goes on
+ *       otherwise s > tau_box:                           s = tau_box and the solve goes on         (BOUNDARY and NEG_CURVATURE included)
+ *       p = p + s * d, r = r + s * w on every entry;  then for i in F, with t_i from the p before the update:
+ *         d_i > 0 and (t_i <= s or Z_i + p_i >= hi_i):  p_i = hi_i - Z_i, state 5
+ *         d_i < 0 and (t_i <= s or Z_i + p_i <= lo_i):  p_i = lo_i - Z_i, state 4           n_hit = the entries fixed so
+ *       (r is not corrected for the rounding of a clamp)
+ *       rr' = r . r over the new F;  p . g (g on F0), p . r, p . p over all entries
+ *       BOUNDARY or NEG_CURVATURE: stop
+ *       sqrt(rr') <= max(atol, rtol * sqrt(rr0)): CONVERGED, stop
+ *       n_hit > 0: restart, d = -r on F and 0 elsewhere;  otherwise beta = rr' / rr, d = beta * d - r, and 0 on states 4 and 5;  rr = rr'
+ *     after max_iter iterations: MAX_ITER
+ * Each iteration is a CG step or takes at least one entry out of F, so the loop ends; a step of length 0 (tau_box = 0) is legal and
+ * costs one product.  Every new product, sum, difference and quotient is rounded on its own in the operand order written; the dots have
+ * the order stated above; a minimum and the integer counts are exact in any order (csrc/dto_newton_box_plan.h holds the rules as
+ * functions the kernels call -- newton_box_classify, newton_box_breakpoint, newton_box_decide, newton_box_update -- and the loop as a
+ * host program).  The step therefore equals the same loop written in NumPy around dto_reduced_hessian_product, bit for bit.  With
+ * lo = -inf and hi = +inf everywhere (or both NULL), p, info [0 .. 7] and the first four columns of the trace are
+ * dto_projected_newton_step's, bit for bit.
+ * Outputs.  p [n_vars]: exactly 0 outside F0.  info [12]:
+ *   [0 .. 7] as above, with [2] = sqrt(rr0) over F0, [3] the final sqrt(rr') over the final F, [6] = -0.5 * (p . g + p . r) with r on F0
+ *   [8] the entries held at a bound from the start   [9] the entries hit   [10] the restarts   [11] |F| at exit
+ * trace: NULL, or [max_iter][6] with kappa, dd, s, rr', tau_box, n_hit per iteration run; later rows are left untouched.
+ * entry_state: NULL, or [n_vars] doubles holding the codes.  Zp: NULL, or [n_vars] with Z_i + p_i, except that the entries in state
+ * 4 / 5 hold lo_i / hi_i EXACTLY: the point to hand to dto_feasible_merit next.  p, Zp and entry_state must not overlap Z, the mask or
+ * the bounds.
+ * Points and costs.  As above: the three kept points are checked once; an iteration is the launches of one kept-point single product,
+ * three small launches (profile name "newton_box") and one 16-byte readback; a call adds two launches and one readback before the
+ * first iteration.  The state codes live in one byte per entry on the device.
+ * Workspaces, grow-only and allocated before anything is enqueued: 3 n_vars + 12 ceil(n_vars / 256) + 16 + ceil(n_vars / 8) doubles, the
+ * block products' for one column, and for the host-pointer form 6 n_vars + 12 + 6 max_iter doubles.
+ * Refused with text, the handle stays usable and nothing is enqueued: what dto_projected_newton_step refuses; p or info = NULL; p, Zp or
+ * entry_state overlapping Z, free_mask, lo or hi.  The two forms behave as above (dlo, dhi, dentry_state and dZp may be NULL). */
+#define DTO_BOX_FIXED 0
+#define DTO_BOX_FREE 1
+#define DTO_BOX_HELD_LOWER 2
+#define DTO_BOX_HELD_UPPER 3
+#define DTO_BOX_HIT_LOWER 4
+#define DTO_BOX_HIT_UPPER 5
+int dto_projected_newton_step_box(dto_handle* h, const double* Z, double sigma, const double* mu, const double* free_mask, const double* lo,
+                                  const double* hi, double radius, double shift, double rtol, double atol, int32_t max_iter, double* p,
+                                  double* info, double* trace, double* entry_state, double* Zp);
+int dto_projected_newton_step_box_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dfree_mask, const double* dlo,
+                                      const double* dhi, double radius, double shift, double rtol, double atol, int32_t max_iter, double* dp,
+                                      double* dinfo, double* dtrace, double* dentry_state, double* dZp, void* stream);
+
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
  * communicator (SURVEY.md §8b "Ownership").  No callback needs a collective: every rank's Jacobian / Hessian / gradient
@@ -825,6 +892,8 @@ int dto_profile_reset(dto_handle* h);
  * "newton" (dto_projected_newton_step and its _dev form: the four kernels of the step -- start, curvature pass, step, direction update --
  * two launches per call and three per iteration; third output: BYTES as executed; it feeds no other name, "all" included; the products
  * of the iterations count as the block products do).
+ * "newton_box" (dto_projected_newton_step_box and its _dev form: its four kernels, counted in the same way; no launch of it counts
+ * under "newton").
  * The block products count under "hess_product", "reduced_pack" and "reduced_input" too, one launch per chunk where a single product
  * has one, with bytes as executed: matrix bytes once per tile or chunk, vector bytes per column.
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the

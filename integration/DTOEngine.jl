@@ -959,6 +959,63 @@ function newton_step_dev!(ev::GPUEvaluator, dp::Ptr{Float64}, dinfo::Ptr{Float64
                                                            dp::Ptr{Float64}, dinfo::Ptr{Float64}, dtrace::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 end
 
+# ---- bound-constrained truncated-Newton step (include/dto_engine.h, "Bound-constrained truncated-Newton step") --------------------------
+# newton_step with simple bounds lo <= Z + p <= hi on the independent entries (`lo`, `hi`: n_variables each or `nothing`; the data of
+# the reference's BoundsConstraint expanded over the knots).  Returns (p, info, trace, states, Zp): info the twelve doubles of the header,
+# trace 6 x iterations (κ, d⋅d, s, r⋅r over the free set, τ_box, entries hit), states the DTO_BOX_* codes as doubles (usable as the next
+# call's `free`), Zp = Z + p with the entries that hit a bound holding it exactly.
+const DTO_BOX_FIXED = Int32(0)
+const DTO_BOX_FREE = Int32(1)
+const DTO_BOX_HELD_LOWER = Int32(2)
+const DTO_BOX_HELD_UPPER = Int32(3)
+const DTO_BOX_HIT_LOWER = Int32(4)
+const DTO_BOX_HIT_UPPER = Int32(5)
+
+function newton_step_box(ev::GPUEvaluator, Z::AbstractVector{Float64}; σ::Float64 = 1.0, μ::Union{Nothing,AbstractVector{Float64}} = nothing,
+                         lo::Union{Nothing,AbstractVector{Float64}} = nothing, hi::Union{Nothing,AbstractVector{Float64}} = nothing,
+                         free::Union{Nothing,AbstractVector{Float64}} = nothing, radius::Float64 = 0.0, shift::Float64 = 0.0,
+                         rtol::Float64 = 1e-6, atol::Float64 = 0.0, max_iter::Integer = 50)
+    reduced_check_lengths(ev, "newton_step_box", Z, μ, free)
+    (lo === nothing || length(lo) == ev.n_variables) || error("newton_step_box: lo has $(length(lo)) entries, n_variables = $(ev.n_variables)")
+    (hi === nothing || length(hi) == ev.n_variables) || error("newton_step_box: hi has $(length(hi)) entries, n_variables = $(ev.n_variables)")
+    max_iter >= 1 || error("newton_step_box: max_iter = $max_iter, at least 1 iteration is required")
+    Zv = Vector{Float64}(Z)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    fv = free === nothing ? Float64[] : Vector{Float64}(free)
+    lov = lo === nothing ? Float64[] : Vector{Float64}(lo)
+    hiv = hi === nothing ? Float64[] : Vector{Float64}(hi)
+    p = fill(NaN, ev.n_variables)
+    info = fill(NaN, 12)
+    trace = fill(NaN, 6, Int(max_iter))
+    states = fill(NaN, ev.n_variables)
+    Zp = fill(NaN, ev.n_variables)
+    mi = Int32(max_iter)
+    GC.@preserve Zv μv fv lov hiv p info trace states Zp begin
+        μp = μ === nothing ? Ptr{Float64}(C_NULL) : pointer(μv)
+        fp = free === nothing ? Ptr{Float64}(C_NULL) : pointer(fv)
+        lop = lo === nothing ? Ptr{Float64}(C_NULL) : pointer(lov)
+        hip = hi === nothing ? Ptr{Float64}(C_NULL) : pointer(hiv)
+        check(ev, @ccall lib.dto_projected_newton_step_box(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μp::Ptr{Float64}, fp::Ptr{Float64},
+                                                           lop::Ptr{Float64}, hip::Ptr{Float64}, radius::Float64, shift::Float64,
+                                                           rtol::Float64, atol::Float64, mi::Int32, p::Ptr{Float64}, info::Ptr{Float64},
+                                                           trace::Ptr{Float64}, states::Ptr{Float64}, Zp::Ptr{Float64})::Cint)
+    end
+    return p, info, trace[:, 1:Int(info[2])], states, Zp
+end
+
+# the same on device pointers, on `stream` (one 16-byte readback per iteration); dμ, dfree, dlo, dhi, dtrace, dstates and dZp may be C_NULL
+function newton_step_box_dev!(ev::GPUEvaluator, dp::Ptr{Float64}, dinfo::Ptr{Float64}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64},
+                              dfree::Ptr{Float64}, dlo::Ptr{Float64}, dhi::Ptr{Float64}, radius::Float64, shift::Float64, rtol::Float64,
+                              atol::Float64, max_iter::Integer, dtrace::Ptr{Float64}, dstates::Ptr{Float64}, dZp::Ptr{Float64},
+                              stream::Ptr{Cvoid})
+    mi = Int32(max_iter)
+    check(ev, @ccall lib.dto_projected_newton_step_box_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dfree::Ptr{Float64},
+                                                               dlo::Ptr{Float64}, dhi::Ptr{Float64}, radius::Float64, shift::Float64,
+                                                               rtol::Float64, atol::Float64, mi::Int32, dp::Ptr{Float64}, dinfo::Ptr{Float64},
+                                                               dtrace::Ptr{Float64}, dstates::Ptr{Float64}, dZp::Ptr{Float64},
+                                                               stream::Ptr{Cvoid})::Cint)
+end
+
 # row bounds handed to the solver (src/solvers/solve.jl:30-65)
 function constraint_bounds(ev::GPUEvaluator)
     lo = Vector{Float64}(undef, ev.n_constraints)

@@ -25,9 +25,19 @@ form ran ("combine_form"):
     DTO_ENGINE_LIB=libdto_engine_t.so DTO_NEWTON_COMBINE=0 python tools/newton_time.py   # every workgroup for itself (the engine's form)
     DTO_ENGINE_LIB=libdto_engine_t.so DTO_NEWTON_COMBINE=1 python tools/newton_time.py   # a one-workgroup launch of its own
 
+``--box`` measures the bound-constrained step (Evaluator.reduced_newton_step_box_dev) instead, in the same way.  The YARDSTICK is then
+the existing step (reduced_newton_step_dev) with its min .. max; beside it, calls alternating,
+    box_inf:     the box step with lo = -inf and hi = +inf vectors (the same iterations, bit for bit, plus the box's own traffic)
+    box_finite:  the box step inside Z -+ half the largest entry of the unbounded step's p on the independent entries
+each with the "newton_box" profile name of one call (device milliseconds, launches, bytes, and both per iteration), the yardstick with
+its "newton" profile, and
+    excess_ms = (box step - yardstick) - (newton_box device ms - newton device ms) - (yardstick max - yardstick min)
+-- what of the difference neither the kernels' own device time nor the yardstick's spread explains (negative: nothing).
+
 One JSON line per shape.
 
     python tools/newton_time.py                       # 256 x 2000 and 64 x 1000
+    python tools/newton_time.py --box                 # the bound-constrained step beside the existing one
     python tools/newton_time.py --shapes 128x1000 --reps 9 --iters 10,30
 """
 import argparse
@@ -70,6 +80,73 @@ def alternating(yardstick, call, reps):
             "yardstick_min_ms": round(min(ys), 4), "yardstick_max_ms": round(max(ys), 4),
             "step_min_ms": round(min(cs), 4), "step_max_ms": round(max(cs), 4),
             "difference_ms": round(statistics.median(cs) - statistics.median(ys), 4)}
+
+
+def measure_box(n, N, drives, scale, reps, iters):
+    """the bound-constrained step beside the existing step (the yardstick): infinite bounds, then a finite box"""
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    prob = dto_amd.host.synthetic.multi_ket_problem(n, 1, drives, N, seed=42, u_bound=4.0, scale=scale or None)
+    ev = dto_amd.Evaluator(prob)
+    ev.set_option("reduced_input_store", 1)
+    out = {"mode": "box", "n": n, "knots": N, "drives": drives, "scale": scale, "reps": reps, "sigma": SIGMA, "route": "reduced_input_store"}
+    try:
+        Zh = np.ascontiguousarray(prob.trajectory.vec(), dtype=np.float64)
+        Z = torch.from_numpy(Zh).to(dev)
+        gen = torch.Generator(device=dev); gen.manual_seed(7)
+        mu = torch.randn(ev.n_constraints, dtype=torch.float64, device=dev, generator=gen)
+        f64 = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
+        nv = ev.n_variables
+        g, y, p, info, pb, info_b = f64(nv), f64(nv), f64(nv), f64(8), f64(nv), f64(12)
+        free = torch.from_numpy(ev.independent_entries()).to(dev)
+        mask = torch.zeros(nv, dtype=torch.float64, device=dev)
+        mask[free] = 1.0
+        out["n_variables"], out["chunks"] = nv, -(-nv // 256)
+        ev.reduced_gradient_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), g.data_ptr(), 0, st)
+        v = torch.randn(nv, dtype=torch.float64, device=dev, generator=gen) * mask
+        top = 0.0
+        for _ in range(8):
+            v = v / torch.linalg.norm(v)
+            ev.reduced_hessian_product_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), v.data_ptr(), y.data_ptr(), st)
+            top = max(top, abs(float(torch.dot(v, y))))
+            v = y.clone()
+        shift = 2.0 * top
+        out["shift"] = shift
+        lo_inf, hi_inf = torch.full_like(Z, float("-inf")), torch.full_like(Z, float("inf"))
+
+        def profile(name, fn, max_iter):
+            ev.profile_enable(True); ev.profile_reset(); fn(); torch.cuda.synchronize()
+            ms, launches, nbytes = ev.profile_get(name)
+            ev.profile_enable(False)
+            return {"ms": round(ms, 4), "launches": launches, "bytes": nbytes, "ms_per_iteration": round(ms / max_iter, 5),
+                    "bytes_per_iteration": nbytes / max_iter}
+
+        for max_iter in iters:
+            step = lambda: ev.reduced_newton_step_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), 0, 0.0, shift, 0.0, 0.0, max_iter, p.data_ptr(),
+                                                      info.data_ptr(), 0, st)
+            box = lambda lo, hi: (lambda: ev.reduced_newton_step_box_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), 0, lo.data_ptr(), hi.data_ptr(), 0.0,
+                                                                         shift, 0.0, 0.0, max_iter, pb.data_ptr(), info_b.data_ptr(), 0, 0, 0, st))
+            step(); torch.cuda.synchronize()
+            half = 0.5 * float(torch.max(torch.abs(p)))
+            lo_f, hi_f = lo_inf.clone(), hi_inf.clone()
+            lo_f[free], hi_f[free] = Z[free] - half, Z[free] + half
+            res = {"half_width": half}
+            for key, fn in (("box_inf", box(lo_inf, hi_inf)), ("box_finite", box(lo_f, hi_f))):
+                pair = alternating(step, fn, reps)
+                fn(); torch.cuda.synchronize()
+                raw = info_b.cpu().numpy()
+                pair.update(status=int(raw[0]), iterations=int(raw[1]), held=int(raw[8]), hit=int(raw[9]), restarts=int(raw[10]), n_free=int(raw[11]))
+                if key == "box_inf":
+                    pair["same_bits_as_yardstick"] = bool(torch.equal(pb, p))
+                pair["newton_box_profile"] = profile("newton_box", fn, max_iter)
+                pair["yardstick_newton_profile"] = profile("newton", step, max_iter)
+                pair["excess_ms"] = round(pair["difference_ms"] - (pair["newton_box_profile"]["ms"] - pair["yardstick_newton_profile"]["ms"])
+                                          - (pair["yardstick_max_ms"] - pair["yardstick_min_ms"]), 4)
+                res[key] = pair
+            out[f"max_iter_{max_iter}"] = res
+        return out
+    finally:
+        ev.close()
 
 
 def measure(n, N, drives, scale, reps, iters):
@@ -161,10 +238,11 @@ def main():
     ap.add_argument("--iters", default="10,30", help="comma-separated iteration counts")
     ap.add_argument("--scale", type=float, default=1.0, help="standard deviation of the generators' entries (1.0: the norms of the\n"
                     "headline benchmark; 0: 1 / sqrt(n), norms of order one)")
+    ap.add_argument("--box", action="store_true", help="measure the bound-constrained step beside the existing step")
     a = ap.parse_args()
     for s in a.shapes.split(","):
         n, N = (int(x) for x in s.lower().split("x"))
-        print(json.dumps(measure(n, N, a.drives, a.scale, a.reps, [int(i) for i in a.iters.split(",")])), flush=True)
+        print(json.dumps((measure_box if a.box else measure)(n, N, a.drives, a.scale, a.reps, [int(i) for i in a.iters.split(",")])), flush=True)
 
 
 if __name__ == "__main__":
