@@ -4,6 +4,7 @@
 // propagator chain, the callbacks, the transfer plans, the extern "C" entry points other than dto_create, the communicator and
 // profiling.  There is NO CPU fallback: every evaluation runs on the GPU or fails with an error code.
 #include "dto_handle.h"
+#include "dto_auglag_plan.h"
 #include "dto_newton_box_plan.h"
 #include "dto_newton_plan.h"
 #include "dto_rollout_plan.h"
@@ -75,7 +76,7 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25, CAT_FEASIBLE = 26, CAT_NEWTON = 27, CAT_NEWTON_BOX = 28 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25, CAT_FEASIBLE = 26, CAT_NEWTON = 27, CAT_NEWTON_BOX = 28, CAT_AUGLAG = 29 };
 // CAT_ROLLOUT .. CAT_ROLLOUT_DESCENT ("rollout" = its parts "rollout_gather" + "rollout_tree" + "rollout_descent"): the gather, the
 // tree's products and the descent (with the start and the copy into the caller's layout) of dto_rollout[_dev], flops as executed with
 // padding; the tree's products run launch_bgemm_plain and count HERE, not under "bgemm_plain"; they feed no other name, "all" included
@@ -100,6 +101,8 @@ inline bool is_elim_cat(int cat) { return cat == CAT_DYNSOLVE_COUPLE || cat == C
 // dto_projected_newton_step and its _dev form; BYTES as executed; it feeds no other name, "all" included.  The products of the
 // iterations count under the names of the block products.
 // CAT_NEWTON_BOX ("newton_box"): the four kernels of dto_newton_box.hip, of dto_projected_newton_step_box and its _dev form, likewise.
+// CAT_AUGLAG ("auglag"): the kernels of dto_auglag.hip -- the row pass, the Gauss-Newton term, the scaling and the addition of the
+// dto_auglag_* calls; BYTES as executed; it feeds no other name, "all" included.
 // The block products (dto_eval_hessian_products, dto_projected_hessian_products) count under the same names -- "hess_product",
 // "reduced_pack", "reduced_input" -- one launch per chunk each, bytes as executed: the matrices once per tile or chunk, the vectors per column.
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
@@ -2898,6 +2901,88 @@ int dto_eval_hessian_products_dev(dto_handle* h, const double* dZ, double sigma,
     }, G_ASYNC, (hipStream_t)stream);
 }
 
+// ---- augmented-Lagrangian terms (include/dto_engine.h, "Augmented-Lagrangian terms"; dto_auglag.hip, dto_auglag_plan.h): the row pass
+// and the Gauss-Newton term the reduced-space calls below take in.
+
+// d_al's vectors: mu_eff, weight, g, the single-column route's rows and the host-pointer forms' mu and rho [n_cons] each, info [8]
+struct AlWork { double *mu_eff, *weight, *g, *rows, *hmu, *hrho, *info; };
+
+// Every workspace of the terms, before anything is enqueued: d_al (once per handle), the planes t for chunks of W columns (W = 0: a call
+// without products) and the rows' equality flags.
+static AlWork auglag_workspaces(dto_handle* h, int W) {
+    const size_t nc = (size_t)std::max<int64_t>(h->n_cons, 1);
+    double* q = grow_workspace(h, h->d_al, 6 * nc + AL_INFO);
+    if (W > 0) grow_workspace(h, h->d_al_t, (size_t)W * (size_t)h->n_vars);
+    if (!h->d_al_eq) {
+        std::vector<unsigned char> eq((size_t)std::max<int64_t>(h->n_cons - h->n_dyn, 1), 0);
+        for (auto& c : h->con)
+            for (int64_t i = 0; i < c.n_times_total * c.g_dim; ++i) eq[(size_t)(c.row_off - h->n_dyn + i)] = c.equality ? 1 : 0;
+        h->d_al_eq = own(h, dupload(eq));
+    }
+    return AlWork{q, q + nc, q + 2 * nc, q + 3 * nc, q + 4 * nc, q + 5 * nc, q + 6 * nc};
+}
+
+// The row pass at g (the non-dynamics rows are read): mu_eff / weight / info where given; with dphi, phi = sigma * f + P.
+static void auglag_row_pass(dto_handle* h, const double* g, const double* dmu, const double* drho, double* mu_eff, double* weight, double* info,
+                            double sigma, const double* f, double* dphi, hipStream_t st) {
+    const double rows = (double)(h->n_cons - h->n_dyn), outs = (mu_eff ? 8.0 : 0.0) + (weight ? 8.0 : 0.0);
+    ProfScope ps(h, st, CAT_AUGLAG, rows * (17.0 + (dmu ? 8.0 : 0.0) + outs) + outs * (double)h->n_dyn + 8.0 * AL_INFO + (dphi ? 16.0 : 0.0));
+    launch_al_rows(st, KAlRows{h->n_dyn, h->n_cons, h->d_al_eq, g, dmu, drho, mu_eff, weight, info, sigma, f, dphi});
+}
+
+// The row pass at Z into the handle's mu_eff and weight: the non-dynamics rows of g from the constraints' value launchers alone -- no
+// sweep, no chain.
+static void auglag_rows_at(dto_handle* h, const AlWork& A, const double* dZ, const double* dmu, const double* drho, double* info, hipStream_t st) {
+    for (auto& c : h->con) launch_cons_knot(st, h->P, c.k, dZ, A.g);
+    auglag_row_pass(h, A.g, dmu, drho, A.mu_eff, A.weight, info, 0.0, nullptr, nullptr, st);
+}
+
+// q_j <- q_j + t_j, t_j = J_c' (W (J_c z^_j)), for the w columns of a chunk; z^ and q planes [w][n_vars].  t is formed from zeros by the
+// constraints in list order: a constraint ||v|| - c or ||v||^2 - c that repeats neither a knot nor a component in ONE launch for all
+// columns, any other (the quadratic form, a repeated knot or component) through the products' own single-column launchers around the
+// scaling.  Then the one rounded addition.
+static void auglag_gauss_newton(dto_handle* h, const AlWork& A, const double* dZ, int w, const double* zh, double* q, hipStream_t st) {
+    const int64_t nv = h->n_vars;
+    const size_t n = (size_t)w * (size_t)nv;
+    double* t = h->d_al_t.p;
+    if (!jac_product_is_matrix_free(h, 0) || !jac_product_is_matrix_free(h, 1)) {
+        // A handle whose public products take the value-slab route (jac_product_is_matrix_free: time-dependent integrators without
+        // "tdb_matrix_free_products", ..) sums a row across lanes, not in k_jv_knot's order.  There the term IS the two public
+        // products around the scaling, one column at a time -- what the same handle's projected_chunk does for J v^ and J' w off
+        // the store route.
+        const int64_t rows = h->n_cons - h->n_dyn;
+        for (int j = 0; j < w; ++j) {
+            jac_product(h, dZ, zh + (size_t)j * nv, A.rows, 0, st);
+            HIP_CHECK(hipMemsetAsync(A.rows, 0, sizeof(double) * (size_t)h->n_dyn, st));
+            { ProfScope ps(h, st, CAT_AUGLAG, 24.0 * (double)rows); launch_al_scale(st, rows, A.weight + h->n_dyn, A.rows + h->n_dyn); }
+            jac_product(h, dZ, A.rows, t + (size_t)j * nv, 1, st);
+        }
+        ProfScope ps(h, st, CAT_AUGLAG, 24.0 * (double)n);
+        launch_al_add(st, (int64_t)n, t, q);
+        return;
+    }
+    HIP_CHECK(hipMemsetAsync(t, 0, sizeof(double) * n, st));
+    for (auto& c : h->con) {
+        const KCon& k = c.k;
+        if (k.n_times <= 0) continue;
+        if ((k.kind == DTO_CONSTRAINT_NORM_MINUS_C || k.kind == DTO_CONSTRAINT_SQNORM_MINUS_C) && !k.repeats && !k.comp_repeats) {
+            // per thread: the listing's components of Z and z^ with their pattern flags, the row's weight, its entry of t twice
+            ProfScope ps(h, st, CAT_AUGLAG, 8.0 * (double)k.n_times * k.n_comps * w * (3.0 * k.n_comps + 3.0));
+            launch_al_gn(st, h->P, k, w, nv, dZ, A.weight, zh, t);
+            continue;
+        }
+        const int64_t rows = c.n_times_total * c.g_dim;
+        for (int j = 0; j < w; ++j) {
+            HIP_CHECK(hipMemsetAsync(A.rows + c.row_off, 0, sizeof(double) * (size_t)rows, st));
+            launch_jv_knot(st, h->P, k, dZ, zh + (size_t)j * nv, A.rows, 0);
+            { ProfScope ps(h, st, CAT_AUGLAG, 24.0 * (double)rows); launch_al_scale(st, rows, A.weight + c.row_off, A.rows + c.row_off); }
+            launch_jv_knot(st, h->P, k, dZ, A.rows, t + (size_t)j * nv, 1);
+        }
+    }
+    ProfScope ps(h, st, CAT_AUGLAG, 24.0 * (double)n);
+    launch_al_add(st, (int64_t)n, t, q);
+}
+
 // one chunk's vectors inside d_blk
 struct BlockWork { double *s1, *s2, *zh, *q, *rows; };
 
@@ -2930,9 +3015,10 @@ static ElimWork projected_points(dto_handle* h, const ElimPlan& p, const double*
 }
 
 // One chunk of w columns at the points projected_points ensured: y = T' H(Z; sigma, mu~) T v, v and y [w][n_vars], in B's vectors --
-// the steps of reduced_hessian_product in block form.
+// the steps of reduced_hessian_product in block form.  With `al` (the dto_auglag_* calls with penalties) the Gauss-Newton term
+// J_c' W J_c z^ joins q behind the Hessian product; without it the launches are the ones they were.
 static void projected_chunk(dto_handle* h, const ElimPlan& p, const BlockWork& B, const ElimWork& EW, bool store_route, const double* dZ,
-                            int w, const double* v, double* y, hipStream_t st) {
+                            int w, const double* v, double* y, hipStream_t st, const AlWork* al = nullptr) {
     const KReduced& R = h->red;
     const int64_t nvars = h->n_vars, ncons = h->n_cons;
     auto solve = [&](int adjoint, int w) {
@@ -2954,6 +3040,7 @@ static void projected_chunk(dto_handle* h, const ElimPlan& p, const BlockWork& B
             solve(0, w);                                                                                   // MM Y = B
             { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_zhat_block(st, R, w, v, B.s2, B.zh); }
             hess_product_block(h, HB, B.zh, B.q, st);                                                      // q = H(mu~) z^
+            if (al) auglag_gauss_newton(h, *al, dZ, w, B.zh, B.q, st);                                     // q += J_c' W J_c z^
             { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nd); launch_red_gather_block(st, R, w, B.q, B.s1); }
             solve(1, w);                                                                                   // MM' Gam = q_S
             // bytes: the store once, per column q, Gam and y
@@ -2968,6 +3055,7 @@ static void projected_chunk(dto_handle* h, const ElimPlan& p, const BlockWork& B
         solve(0, w);                                                                                       // MM Y = B
         { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nv); launch_red_zhat_block(st, R, w, v, B.s2, B.zh); }
         hess_product_block(h, HB, B.zh, B.q, st);                                                          // q = H(mu~) z^
+        if (al) auglag_gauss_newton(h, *al, dZ, w, B.zh, B.q, st);                                         // q += J_c' W J_c z^
         { ProfScope ps(h, st, CAT_REDUCED_PACK, 2.0 * nd); launch_red_gather_block(st, R, w, B.q, B.s1); }
         solve(1, w);                                                                                       // MM' Gam = q_S
         { ProfScope ps(h, st, CAT_REDUCED_PACK, nd + nc); launch_red_multipliers_block(st, R, w, B.s2, B.rows); }
@@ -2979,7 +3067,7 @@ static void projected_chunk(dto_handle* h, const ElimPlan& p, const BlockWork& B
 // Y = T' H(Z; sigma, mu~) T V, V and Y [n_cols][n_vars] on the device.  The three point checks (reduced point, solves' point, Hessian
 // point) once; then per chunk of w <= W columns the steps of reduced_hessian_product in block form.
 static void projected_hessian_products(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, int n_cols,
-                                       const double* dV, double* dY, hipStream_t st) {
+                                       const double* dV, double* dY, hipStream_t st, const AlWork* al = nullptr) {
     const int W = projected_width(h, n_cols);
     const bool store_route = h->reduced_input_store && h->K >= 1;
     // the block's and (in projected_points) the solves' workspaces for W columns first: a failed allocation is refused before anything
@@ -2987,7 +3075,7 @@ static void projected_hessian_products(dto_handle* h, const ElimPlan& p, const d
     const BlockWork B = block_workspaces(h, p, W, store_route);
     const ElimWork EW = projected_points(h, p, dZ, sigma, dmu, W, st);
     for (int c0 = 0; c0 < n_cols; c0 += W)
-        projected_chunk(h, p, B, EW, store_route, dZ, std::min(W, n_cols - c0), dV + (size_t)c0 * h->n_vars, dY + (size_t)c0 * h->n_vars, st);
+        projected_chunk(h, p, B, EW, store_route, dZ, std::min(W, n_cols - c0), dV + (size_t)c0 * h->n_vars, dY + (size_t)c0 * h->n_vars, st, al);
 }
 
 // ---- truncated-Newton step: Steihaug-Toint CG on A = M (T'HT) M + shift M (include/dto_engine.h, "Truncated-Newton step"; dto_newton.hip,
@@ -3120,7 +3208,8 @@ struct NewtonBoxArgs {
 };
 
 // The device routine both entry-point families run: everything on `st`, every pointer a device pointer.
-static void newton_box_step(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, const NewtonBoxArgs& a, hipStream_t st) {
+static void newton_box_step(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, const NewtonBoxArgs& a, hipStream_t st,
+                            const AlWork* al = nullptr) {
     const KReduced& R = h->red;
     const int64_t n = h->n_vars, nb = newton_chunks(n);
     const bool store_route = h->reduced_input_store && h->K >= 1;
@@ -3149,11 +3238,52 @@ static void newton_box_step(dto_handle* h, const ElimPlan& p, const double* dZ, 
     { ProfScope ps(h, st, CAT_NEWTON_BOX, 5.0 * v + m + bounds + by + outs + 7.0 * part); launch_newton_box_start(st, R, A); }
     { ProfScope ps(h, st, CAT_NEWTON_BOX, (groups + 6.0) * part); launch_newton_box_dir(st, A, 0, a.max_iter); }
     for (int j = 1; j <= a.max_iter && running(); ++j) {
-        projected_chunk(h, p, B, EW, store_route, dZ, 1, A.d, A.w, st);   // y = T'HT d
+        projected_chunk(h, p, B, EW, store_route, dZ, 1, A.d, A.w, st, al);   // y = T'HT d (with `al`: T'(H + J_c' W J_c)T d)
         { ProfScope ps(h, st, CAT_NEWTON_BOX, 5.0 * v + bounds + by + 5.0 * part); launch_newton_box_curv(st, A); }
         { ProfScope ps(h, st, CAT_NEWTON_BOX, 8.0 * v + bounds + 2.0 * by + outs + 6.0 * part + groups * 5.0 * part); launch_newton_box_step(st, A, j); }
         { ProfScope ps(h, st, CAT_NEWTON_BOX, 3.0 * v + by + (2.0 * groups + 5.0) * part); launch_newton_box_dir(st, A, j, a.max_iter); }
     }
+}
+
+// The host-pointer form of the box step and, with `rho`, of dto_auglag_newton_step: upload, the device routine, download.
+static int newton_box_host(dto_handle* h, const std::string& who, const double* Z, double sigma, const double* mu, const double* rho,
+                           const double* free_mask, const double* lo, const double* hi, double radius, double shift, double rtol, double atol,
+                           int32_t max_iter, double* p, double* info, double* trace, double* entry_state, double* Zp) {
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, true);
+        reduced_workspaces(h, ep);
+        const size_t n = (size_t)h->n_vars, nt = NEWTON_BOX_TRACE * (size_t)max_iter, bytes = sizeof(double) * n;
+        grow_workspace(h, h->d_newton_box, (size_t)newton_box_workspace_doubles(h->n_vars));   // before the uploads are enqueued
+        block_workspaces(h, ep, 1, h->reduced_input_store && h->K >= 1);
+        AlWork al{};
+        if (rho) al = auglag_workspaces(h, 1);
+        double* q = grow_workspace(h, h->d_newton_box_host, 6 * n + NEWTON_BOX_INFO + nt);
+        double *dmask = q, *dlo = q + n, *dhi = q + 2 * n, *dp = q + 3 * n, *dzp = q + 4 * n, *des = q + 5 * n, *dinfo = q + 6 * n;
+        double* dtrace = dinfo + NEWTON_BOX_INFO;
+        upload_Z(h, Z);
+        const bool has_mu = mu && h->n_cons > 0;
+        if (has_mu) HIP_CHECK(hipMemcpyAsync(h->red_hmu, mu, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        if (rho && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(al.hrho, rho, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        if (free_mask) HIP_CHECK(hipMemcpyAsync(dmask, free_mask, bytes, hipMemcpyHostToDevice, h->stream));
+        if (lo) HIP_CHECK(hipMemcpyAsync(dlo, lo, bytes, hipMemcpyHostToDevice, h->stream));
+        if (hi) HIP_CHECK(hipMemcpyAsync(dhi, hi, bytes, hipMemcpyHostToDevice, h->stream));
+        // the rows of the trace the step does not reach keep the caller's values
+        if (trace) HIP_CHECK(hipMemcpyAsync(dtrace, trace, sizeof(double) * nt, hipMemcpyHostToDevice, h->stream));
+        const NewtonBoxArgs a{free_mask ? dmask : nullptr, lo ? dlo : nullptr, hi ? dhi : nullptr, radius, shift, rtol, atol, max_iter, dp, dinfo,
+                              trace ? dtrace : nullptr, entry_state ? des : nullptr, Zp ? dzp : nullptr};
+        if (rho) {
+            auglag_rows_at(h, al, h->d_Z, has_mu ? h->red_hmu : nullptr, al.hrho, nullptr, h->stream);
+            newton_box_step(h, ep, h->d_Z, sigma, al.mu_eff, a, h->stream, &al);
+        } else {
+            newton_box_step(h, ep, h->d_Z, sigma, mu ? h->red_hmu : nullptr, a, h->stream);
+        }
+        HIP_CHECK(hipMemcpyAsync(p, dp, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipMemcpyAsync(info, dinfo, sizeof(double) * NEWTON_BOX_INFO, hipMemcpyDeviceToHost, h->stream));
+        if (trace) HIP_CHECK(hipMemcpyAsync(trace, dtrace, sizeof(double) * nt, hipMemcpyDeviceToHost, h->stream));
+        if (entry_state) HIP_CHECK(hipMemcpyAsync(entry_state, des, bytes, hipMemcpyDeviceToHost, h->stream));
+        if (Zp) HIP_CHECK(hipMemcpyAsync(Zp, dzp, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
 }
 
 int dto_projected_newton_step_box(dto_handle* h, const double* Z, double sigma, const double* mu, const double* free_mask, const double* lo,
@@ -3164,32 +3294,7 @@ int dto_projected_newton_step_box(dto_handle* h, const double* Z, double sigma, 
     std::string bad = newton_refusal(who, Z, radius, shift, rtol, atol, max_iter, p, info);
     if (bad.empty()) bad = newton_box_refusal(who, (size_t)h->n_vars, Z, free_mask, lo, hi, p, Zp, entry_state);
     if (!bad.empty()) return fail(h, bad);
-    return guarded(h, [&] {
-        const ElimPlan& ep = reduced_args(h, who, true);
-        reduced_workspaces(h, ep);
-        const size_t n = (size_t)h->n_vars, nt = NEWTON_BOX_TRACE * (size_t)max_iter, bytes = sizeof(double) * n;
-        grow_workspace(h, h->d_newton_box, (size_t)newton_box_workspace_doubles(h->n_vars));   // before the uploads are enqueued
-        block_workspaces(h, ep, 1, h->reduced_input_store && h->K >= 1);
-        double* q = grow_workspace(h, h->d_newton_box_host, 6 * n + NEWTON_BOX_INFO + nt);
-        double *dmask = q, *dlo = q + n, *dhi = q + 2 * n, *dp = q + 3 * n, *dzp = q + 4 * n, *des = q + 5 * n, *dinfo = q + 6 * n;
-        double* dtrace = dinfo + NEWTON_BOX_INFO;
-        upload_Z(h, Z);
-        if (mu && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(h->red_hmu, mu, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
-        if (free_mask) HIP_CHECK(hipMemcpyAsync(dmask, free_mask, bytes, hipMemcpyHostToDevice, h->stream));
-        if (lo) HIP_CHECK(hipMemcpyAsync(dlo, lo, bytes, hipMemcpyHostToDevice, h->stream));
-        if (hi) HIP_CHECK(hipMemcpyAsync(dhi, hi, bytes, hipMemcpyHostToDevice, h->stream));
-        // the rows of the trace the step does not reach keep the caller's values
-        if (trace) HIP_CHECK(hipMemcpyAsync(dtrace, trace, sizeof(double) * nt, hipMemcpyHostToDevice, h->stream));
-        const NewtonBoxArgs a{free_mask ? dmask : nullptr, lo ? dlo : nullptr, hi ? dhi : nullptr, radius, shift, rtol, atol, max_iter, dp, dinfo,
-                              trace ? dtrace : nullptr, entry_state ? des : nullptr, Zp ? dzp : nullptr};
-        newton_box_step(h, ep, h->d_Z, sigma, mu ? h->red_hmu : nullptr, a, h->stream);
-        HIP_CHECK(hipMemcpyAsync(p, dp, bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipMemcpyAsync(info, dinfo, sizeof(double) * NEWTON_BOX_INFO, hipMemcpyDeviceToHost, h->stream));
-        if (trace) HIP_CHECK(hipMemcpyAsync(trace, dtrace, sizeof(double) * nt, hipMemcpyDeviceToHost, h->stream));
-        if (entry_state) HIP_CHECK(hipMemcpyAsync(entry_state, des, bytes, hipMemcpyDeviceToHost, h->stream));
-        if (Zp) HIP_CHECK(hipMemcpyAsync(Zp, dzp, bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-    }, G_BLOCKING);
+    return newton_box_host(h, who, Z, sigma, mu, nullptr, free_mask, lo, hi, radius, shift, rtol, atol, max_iter, p, info, trace, entry_state, Zp);
 }
 int dto_projected_newton_step_box_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* dfree_mask, const double* dlo,
                                       const double* dhi, double radius, double shift, double rtol, double atol, int32_t max_iter, double* dp,
@@ -3377,6 +3482,283 @@ int dto_feasible_merit_dev(dto_handle* h, const double* dZ, double sigma, const 
         if (!dZ || !dphi) throw HipError{who + ": dZ and dphi are required (NULL given)"};
         const FeasWork W = feasible_workspaces(h, fp, true);
         feasible_merit(h, fp, W, dZ, sigma, h->n_cons > 0 ? dmu : nullptr, dphi, dZf, dg, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
+// ---- augmented-Lagrangian entry points (include/dto_engine.h, "Augmented-Lagrangian terms").  Each call extends one of the calls above;
+// with rho == NULL it IS that call.
+
+static bool spans_overlap(const double* a, size_t na, const double* b, size_t nb) {
+    if (!a || !b) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb * sizeof(double) && y < x + na * sizeof(double);
+}
+
+struct AlSpan { const char* name; const double* p; size_t n; };
+
+// What every dto_auglag_* call names before the handle is touched: host-evaluated constraints, in the host-pointer forms a penalty that
+// is negative or a NaN, and outputs that overlap inputs.
+static std::string auglag_refusal(const dto_handle* h, const std::string& who, const double* rho_host, std::initializer_list<AlSpan> outs,
+                                  std::initializer_list<AlSpan> ins) {
+    if (h->n_ext_con > 0)
+        return who + ": the handle holds " + std::to_string(h->n_ext_con) +
+               " host-evaluated constraint(s) (global constraints are among these): the augmented-Lagrangian terms run on device-evaluated constraints only";
+    if (rho_host)
+        for (int64_t r = h->n_dyn; r < h->n_cons; ++r)
+            if (!(rho_host[r] >= 0.0))
+                return who + ": rho[" + std::to_string(r) + "] = " + std::to_string(rho_host[r]) + " (row " + std::to_string(r) +
+                       "): a penalty must be >= 0 and no NaN";
+    for (const AlSpan& o : outs)
+        for (const AlSpan& i : ins)
+            if (spans_overlap(o.p, o.n, i.p, i.n)) return who + ": " + o.name + " overlaps " + i.name;
+    return "";
+}
+
+// what a row pass names beyond that
+static void auglag_rows_args(dto_handle* h, const std::string& who) {
+    needs_unsharded(h, who);
+    if (h->n_ext_int > 0) throw HipError{who + ": the handle holds host-evaluated integrators: the row pass runs on device-evaluated terms only"};
+}
+
+int dto_auglag_rows(dto_handle* h, const double* Z, const double* mu, const double* rho, double* mu_eff, double* weight, double* info) {
+    const std::string who = "dto_auglag_rows";
+    if (!h) return fail(nullptr, "null handle");
+    if (!Z) return fail(h, who + ": Z is required (NULL given)");
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars;
+    const std::string bad = auglag_refusal(h, who, rho, {{"mu_eff", mu_eff, nc}, {"weight", weight, nc}, {"info", info, AL_INFO}},
+                                           {{"Z", Z, nv}, {"mu", mu, nc}, {"rho", rho, nc}});
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        auglag_rows_args(h, who);
+        const AlWork A = auglag_workspaces(h, 0);
+        upload_Z(h, Z);
+        const bool has_mu = mu && nc > 0, has_rho = rho && nc > 0;
+        if (has_mu) HIP_CHECK(hipMemcpyAsync(A.hmu, mu, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
+        if (has_rho) HIP_CHECK(hipMemcpyAsync(A.hrho, rho, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
+        auglag_rows_at(h, A, h->d_Z, has_mu ? A.hmu : nullptr, has_rho ? A.hrho : nullptr, A.info, h->stream);
+        if (mu_eff && nc > 0) HIP_CHECK(hipMemcpyAsync(mu_eff, A.mu_eff, sizeof(double) * nc, hipMemcpyDeviceToHost, h->stream));
+        if (weight && nc > 0) HIP_CHECK(hipMemcpyAsync(weight, A.weight, sizeof(double) * nc, hipMemcpyDeviceToHost, h->stream));
+        if (info) HIP_CHECK(hipMemcpyAsync(info, A.info, sizeof(double) * AL_INFO, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_auglag_rows_dev(dto_handle* h, const double* dZ, const double* dmu, const double* drho, double* dmu_eff, double* dweight, double* dinfo,
+                        void* stream) {
+    const std::string who = "dto_auglag_rows_dev";
+    if (!h) return fail(nullptr, "null handle");
+    if (!dZ) return fail(h, who + ": dZ is required (NULL given)");
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars;
+    const std::string bad = auglag_refusal(h, who, nullptr, {{"dmu_eff", dmu_eff, nc}, {"dweight", dweight, nc}, {"dinfo", dinfo, AL_INFO}},
+                                           {{"dZ", dZ, nv}, {"dmu", dmu, nc}, {"drho", drho, nc}});
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        auglag_rows_args(h, who);
+        const AlWork A = auglag_workspaces(h, 0);
+        hipStream_t st = (hipStream_t)stream;
+        for (auto& c : h->con) launch_cons_knot(st, h->P, c.k, dZ, A.g);
+        auglag_row_pass(h, A.g, dmu, drho, dmu_eff, dweight, dinfo, 0.0, nullptr, nullptr, st);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
+int dto_auglag_merit(dto_handle* h, const double* Z, double sigma, const double* mu, const double* rho, double* phi, double* Zf, double* g,
+                     double* info) {
+    const std::string who = "dto_auglag_merit";
+    if (!h) return fail(nullptr, "null handle");
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars;
+    const std::string bad = auglag_refusal(h, who, rho, {{"phi", phi, 1}, {"Zf", Zf, nv}, {"g", g, nc}, {"info", info, AL_INFO}},
+                                           {{"Z", Z, nv}, {"mu", mu, nc}, {"rho", rho, nc}});
+    if (!bad.empty()) return fail(h, bad);
+    if (!rho) return dto_feasible_merit(h, Z, sigma, mu, phi, Zf, g);
+    return guarded(h, [&] {
+        const FeasiblePlan& fp = feasible_args(h, who, true);
+        if (!Z || !phi) throw HipError{who + ": Z and phi are required (NULL given)"};
+        const FeasWork W = feasible_workspaces(h, fp, true);
+        const AlWork A = auglag_workspaces(h, 0);
+        upload_Z(h, Z);
+        const bool has_mu = mu && nc > 0;
+        if (has_mu) HIP_CHECK(hipMemcpyAsync(W.mu, mu, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
+        if (nc > 0) HIP_CHECK(hipMemcpyAsync(A.hrho, rho, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
+        feasible_trajectory(h, fp, h->d_Z, h->d_Z, h->stream);
+        do_objective(h, h->d_Z, W.f, h->stream);
+        do_constraint(h, h->d_Z, W.g, h->stream);
+        auglag_row_pass(h, W.g, has_mu ? W.mu : nullptr, A.hrho, nullptr, nullptr, A.info, sigma, W.f, W.phi, h->stream);
+        HIP_CHECK(hipMemcpyAsync(phi, W.phi, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (Zf) HIP_CHECK(hipMemcpyAsync(Zf, h->d_Z, sizeof(double) * nv, hipMemcpyDeviceToHost, h->stream));
+        if (g && nc > 0) HIP_CHECK(hipMemcpyAsync(g, W.g, sizeof(double) * nc, hipMemcpyDeviceToHost, h->stream));
+        if (info) HIP_CHECK(hipMemcpyAsync(info, A.info, sizeof(double) * AL_INFO, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_auglag_merit_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* drho, double* dphi, double* dZf, double* dg,
+                         double* dinfo, void* stream) {
+    const std::string who = "dto_auglag_merit_dev";
+    if (!h) return fail(nullptr, "null handle");
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars;
+    const std::string bad = auglag_refusal(h, who, nullptr, {{"dphi", dphi, 1}, {"dZf", dZf, nv}, {"dg", dg, nc}, {"dinfo", dinfo, AL_INFO}},
+                                           {{"dmu", dmu, nc}, {"drho", drho, nc}});   // (dZf == dZ works in place, as in dto_feasible_merit_dev)
+    if (!bad.empty()) return fail(h, bad);
+    if (!drho) return dto_feasible_merit_dev(h, dZ, sigma, dmu, dphi, dZf, dg, stream);
+    return guarded(h, [&] {
+        const FeasiblePlan& fp = feasible_args(h, who, true);
+        if (!dZ || !dphi) throw HipError{who + ": dZ and dphi are required (NULL given)"};
+        const FeasWork W = feasible_workspaces(h, fp, true);
+        auglag_workspaces(h, 0);
+        hipStream_t st = (hipStream_t)stream;
+        double* Zf = dZf ? dZf : W.Zf;
+        double* gg = dg ? dg : W.g;
+        feasible_trajectory(h, fp, dZ, Zf, st);
+        do_objective(h, Zf, W.f, st);
+        do_constraint(h, Zf, gg, st);
+        auglag_row_pass(h, gg, nc > 0 ? dmu : nullptr, drho, nullptr, nullptr, dinfo, sigma, W.f, dphi, st);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
+int dto_auglag_gradient(dto_handle* h, const double* Z, double sigma, const double* mu, const double* rho, double* grad, double* lam, double* mu_eff) {
+    const std::string who = "dto_auglag_gradient";
+    if (!h) return fail(nullptr, "null handle");
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars;
+    const std::string bad = auglag_refusal(h, who, rho, {{"grad", grad, nv}, {"mu_eff", mu_eff, nc}}, {{"Z", Z, nv}, {"mu", mu, nc}, {"rho", rho, nc}});
+    if (!bad.empty()) return fail(h, bad);
+    if (!rho) {   // no penalties: the call it extends; mu_eff is mu with its dynamics rows zeroed
+        const int rc = dto_reduced_gradient(h, Z, sigma, mu, grad, lam);
+        if (rc == 0 && mu_eff)
+            for (int64_t r = 0; r < h->n_cons; ++r) mu_eff[r] = (mu && r >= h->n_dyn) ? mu[r] : 0.0;
+        return rc;
+    }
+    return guarded(h, [&] {
+        const ElimPlan& p = reduced_args(h, who, false);
+        if (!Z || !grad) throw HipError{who + ": Z and grad are required (NULL given)"};
+        reduced_workspaces(h, p);
+        const AlWork A = auglag_workspaces(h, 0);
+        upload_Z(h, Z);
+        const bool has_mu = mu && nc > 0;
+        if (has_mu) HIP_CHECK(hipMemcpyAsync(h->red_hmu, mu, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
+        if (nc > 0) HIP_CHECK(hipMemcpyAsync(A.hrho, rho, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
+        auglag_rows_at(h, A, h->d_Z, has_mu ? h->red_hmu : nullptr, A.hrho, nullptr, h->stream);
+        reduced_point(h, p, h->d_Z, sigma, A.mu_eff, h->stream);
+        HIP_CHECK(hipMemcpyAsync(grad, h->red_r, sizeof(double) * nv, hipMemcpyDeviceToHost, h->stream));
+        if (lam) HIP_CHECK(hipMemcpyAsync(lam, h->red_lam, sizeof(double) * (size_t)h->N * p.n_states, hipMemcpyDeviceToHost, h->stream));
+        if (mu_eff && nc > 0) HIP_CHECK(hipMemcpyAsync(mu_eff, A.mu_eff, sizeof(double) * nc, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_auglag_gradient_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* drho, double* dgrad, double* dlam,
+                            double* dmu_eff, void* stream) {
+    const std::string who = "dto_auglag_gradient_dev";
+    if (!h) return fail(nullptr, "null handle");
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars;
+    const std::string bad = auglag_refusal(h, who, nullptr, {{"dgrad", dgrad, nv}, {"dmu_eff", dmu_eff, nc}},
+                                           {{"dZ", dZ, nv}, {"dmu", dmu, nc}, {"drho", drho, nc}});
+    if (!bad.empty()) return fail(h, bad);
+    if (!drho) {
+        const int rc = dto_reduced_gradient_dev(h, dZ, sigma, dmu, dgrad, dlam, stream);
+        if (rc != 0 || !dmu_eff || nc == 0) return rc;
+        return guarded(h, [&] {   // copies, no launch
+            hipStream_t st = (hipStream_t)stream;
+            const size_t nd = (size_t)h->n_dyn;
+            HIP_CHECK(hipMemsetAsync(dmu_eff, 0, sizeof(double) * (dmu ? nd : nc), st));
+            if (dmu && nc > nd) HIP_CHECK(hipMemcpyAsync(dmu_eff + nd, dmu + nd, sizeof(double) * (nc - nd), hipMemcpyDeviceToDevice, st));
+        }, G_ASYNC, (hipStream_t)stream);
+    }
+    return guarded(h, [&] {
+        const ElimPlan& p = reduced_args(h, who, false);
+        if (!dZ || !dgrad) throw HipError{who + ": dZ and dgrad are required (NULL given)"};
+        reduced_workspaces(h, p);
+        const AlWork A = auglag_workspaces(h, 0);
+        hipStream_t st = (hipStream_t)stream;
+        auglag_rows_at(h, A, dZ, nc > 0 ? dmu : nullptr, drho, nullptr, st);
+        reduced_gradient(h, p, dZ, sigma, A.mu_eff, dgrad, dlam, st);
+        if (dmu_eff && nc > 0) HIP_CHECK(hipMemcpyAsync(dmu_eff, A.mu_eff, sizeof(double) * nc, hipMemcpyDeviceToDevice, st));
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
+int dto_auglag_hessian_products(dto_handle* h, const double* Z, double sigma, const double* mu, const double* rho, int32_t n_cols, const double* V,
+                                double* Y) {
+    const std::string who = "dto_auglag_hessian_products";
+    if (!h) return fail(nullptr, "null handle");
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars, nb = (size_t)std::max(n_cols, 0) * nv;
+    const std::string bad = auglag_refusal(h, who, rho, {{"Y", Y, nb}}, {{"Z", Z, nv}, {"mu", mu, nc}, {"rho", rho, nc}, {"V", V, nb}});
+    if (!bad.empty()) return fail(h, bad);
+    if (!rho) return dto_projected_hessian_products(h, Z, sigma, mu, n_cols, V, Y);
+    return guarded(h, [&] {
+        const ElimPlan& p = reduced_args(h, who, true);
+        block_args(who, n_cols, Z, V, Y);
+        reduced_workspaces(h, p);
+        double* dV = block_host_buffers(h, n_cols);
+        block_workspaces(h, p, projected_width(h, n_cols), h->reduced_input_store && h->K >= 1);   // before the uploads are enqueued
+        const AlWork A = auglag_workspaces(h, projected_width(h, n_cols));
+        upload_Z(h, Z);
+        const bool has_mu = mu && nc > 0;
+        if (has_mu) HIP_CHECK(hipMemcpyAsync(h->red_hmu, mu, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
+        if (nc > 0) HIP_CHECK(hipMemcpyAsync(A.hrho, rho, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(dV, V, sizeof(double) * nb, hipMemcpyHostToDevice, h->stream));
+        auglag_rows_at(h, A, h->d_Z, has_mu ? h->red_hmu : nullptr, A.hrho, nullptr, h->stream);
+        projected_hessian_products(h, p, h->d_Z, sigma, A.mu_eff, n_cols, dV, dV + nb, h->stream, &A);
+        HIP_CHECK(hipMemcpyAsync(Y, dV + nb, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_auglag_hessian_products_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* drho, int32_t n_cols,
+                                    const double* dV, double* dY, void* stream) {
+    const std::string who = "dto_auglag_hessian_products_dev";
+    if (!h) return fail(nullptr, "null handle");
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars, nb = (size_t)std::max(n_cols, 0) * nv;
+    const std::string bad = auglag_refusal(h, who, nullptr, {{"dY", dY, nb}}, {{"dZ", dZ, nv}, {"dmu", dmu, nc}, {"drho", drho, nc}, {"dV", dV, nb}});
+    if (!bad.empty()) return fail(h, bad);
+    if (!drho) return dto_projected_hessian_products_dev(h, dZ, sigma, dmu, n_cols, dV, dY, stream);
+    return guarded(h, [&] {
+        const ElimPlan& p = reduced_args(h, who, true);
+        block_args(who, n_cols, dZ, dV, dY);
+        reduced_workspaces(h, p);
+        const int W = projected_width(h, n_cols);
+        block_workspaces(h, p, W, h->reduced_input_store && h->K >= 1);
+        const AlWork A = auglag_workspaces(h, W);
+        hipStream_t st = (hipStream_t)stream;
+        auglag_rows_at(h, A, dZ, nc > 0 ? dmu : nullptr, drho, nullptr, st);
+        projected_hessian_products(h, p, dZ, sigma, A.mu_eff, n_cols, dV, dY, st, &A);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
+int dto_auglag_newton_step(dto_handle* h, const double* Z, double sigma, const double* mu, const double* rho, const double* free_mask,
+                           const double* lo, const double* hi, double radius, double shift, double rtol, double atol, int32_t max_iter, double* p,
+                           double* info, double* trace, double* entry_state, double* Zp) {
+    const std::string who = "dto_auglag_newton_step";
+    if (!h) return fail(nullptr, "null handle");
+    std::string bad = newton_refusal(who, Z, radius, shift, rtol, atol, max_iter, p, info);
+    if (bad.empty()) bad = newton_box_refusal(who, (size_t)h->n_vars, Z, free_mask, lo, hi, p, Zp, entry_state);
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars;
+    if (bad.empty())
+        bad = auglag_refusal(h, who, rho, {{"p", p, nv}, {"Zp", Zp, nv}, {"entry_state", entry_state, nv}, {"info", info, NEWTON_BOX_INFO}},
+                             {{"mu", mu, nc}, {"rho", rho, nc}});
+    if (!bad.empty()) return fail(h, bad);
+    return newton_box_host(h, rho ? who : std::string("dto_projected_newton_step_box"), Z, sigma, mu, rho, free_mask, lo, hi, radius, shift, rtol, atol,
+                           max_iter, p, info, trace, entry_state, Zp);
+}
+int dto_auglag_newton_step_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* drho, const double* dfree_mask,
+                               const double* dlo, const double* dhi, double radius, double shift, double rtol, double atol, int32_t max_iter,
+                               double* dp, double* dinfo, double* dtrace, double* dentry_state, double* dZp, void* stream) {
+    const std::string who = "dto_auglag_newton_step_dev";
+    if (!h) return fail(nullptr, "null handle");
+    std::string bad = newton_refusal(who, dZ, radius, shift, rtol, atol, max_iter, dp, dinfo);
+    if (bad.empty()) bad = newton_box_refusal(who, (size_t)h->n_vars, dZ, dfree_mask, dlo, dhi, dp, dZp, dentry_state);
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars;
+    if (bad.empty())
+        bad = auglag_refusal(h, who, nullptr, {{"dp", dp, nv}, {"dZp", dZp, nv}, {"dentry_state", dentry_state, nv}, {"dinfo", dinfo, NEWTON_BOX_INFO}},
+                             {{"dmu", dmu, nc}, {"drho", drho, nc}});
+    if (!bad.empty()) return fail(h, bad);
+    if (!drho)
+        return dto_projected_newton_step_box_dev(h, dZ, sigma, dmu, dfree_mask, dlo, dhi, radius, shift, rtol, atol, max_iter, dp, dinfo, dtrace,
+                                                 dentry_state, dZp, stream);
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, true);
+        reduced_workspaces(h, ep);
+        grow_workspace(h, h->d_newton_box, (size_t)newton_box_workspace_doubles(h->n_vars));   // before the row pass is enqueued
+        block_workspaces(h, ep, 1, h->reduced_input_store && h->K >= 1);
+        const AlWork A = auglag_workspaces(h, 1);
+        hipStream_t st = (hipStream_t)stream;
+        auglag_rows_at(h, A, dZ, nc > 0 ? dmu : nullptr, drho, nullptr, st);
+        const NewtonBoxArgs a{dfree_mask, dlo, dhi, radius, shift, rtol, atol, max_iter, dp, dinfo, dtrace, dentry_state, dZp};
+        newton_box_step(h, ep, dZ, sigma, A.mu_eff, a, st, &A);
     }, G_ASYNC, (hipStream_t)stream);
 }
 
@@ -3651,6 +4033,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "feasible")) cat = CAT_FEASIBLE;
         else if (!strcmp(name, "newton")) cat = CAT_NEWTON;
         else if (!strcmp(name, "newton_box")) cat = CAT_NEWTON_BOX;
+        else if (!strcmp(name, "auglag")) cat = CAT_AUGLAG;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -3680,8 +4063,8 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (is_rollout_cat(r.cat) ? !(any_rollout || r.cat == cat) : any_rollout) continue;   // ("all": the rollout is no callback)
             if (is_dynsolve_cat(r.cat) ? !(any_dynsolve || r.cat == cat) : any_dynsolve) continue;   // (nor are the solves)
             if (is_elim_cat(r.cat) && r.cat != cat) continue;
-            if ((r.cat == CAT_REDUCED_PACK || r.cat == CAT_REDUCED_INPUT || r.cat == CAT_FEASIBLE || r.cat == CAT_NEWTON || r.cat == CAT_NEWTON_BOX) &&
-                r.cat != cat) continue;
+            if ((r.cat == CAT_REDUCED_PACK || r.cat == CAT_REDUCED_INPUT || r.cat == CAT_FEASIBLE || r.cat == CAT_NEWTON || r.cat == CAT_NEWTON_BOX ||
+                 r.cat == CAT_AUGLAG) && r.cat != cat) continue;
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));

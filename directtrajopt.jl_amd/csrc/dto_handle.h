@@ -346,6 +346,12 @@ struct dto_handle {
     // y / w [n_vars], the partial results [12][chunks], the scalars [16] and the state bytes [n_vars]; d_newton_box_host: the
     // host-pointer form's mask, lo, hi, p, Zp and entry_state [n_vars] each, info [12] and trace [max_iter][6].  Grow-only like the above.
     dto::Workspace d_newton_box, d_newton_box_host;
+    // augmented-Lagrangian terms (dto_auglag_*; dto_auglag_plan.h, dto_auglag.hip).  d_al: mu_eff, weight, g, the rows of the
+    // single-column route and the host-pointer forms' mu and rho [n_cons] each, then info [8]; d_al_t: the planes t [W][n_vars] of the
+    // Gauss-Newton term; d_al_host: the host-pointer forms' lam [N n_states].  d_al_eq: the equality flag of every non-dynamics row,
+    // one byte each, written once.  Grow-only like the above.
+    dto::Workspace d_al, d_al_t, d_al_host;
+    unsigned char* d_al_eq = nullptr;
     int64_t* d_conbase = nullptr;       // [n_vars+1] first constraint-pattern entry of each column
     int64_t* d_crow_ptr = nullptr;       // the constraint pattern in row order (J w gathers rows): [rows+1], columns, slab positions
     int64_t* d_crow_col = nullptr;

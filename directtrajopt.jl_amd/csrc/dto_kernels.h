@@ -595,6 +595,27 @@ void launch_newton_box_step(hipStream_t st, const KNewtonBox& A, int j);
 // j = 0 behind the start, j >= 1 behind the step: the convergence test, the restart or the beta step, status, counts, `info` on exit
 void launch_newton_box_dir(hipStream_t st, const KNewtonBox& A, int j, int max_iter);
 
+// Augmented-Lagrangian terms (dto_auglag.hip; the row rules, the order of the sums and the eight scalars: dto_auglag_plan.h).
+struct KAlRows {
+    int64_t n_dyn, n_cons;
+    const unsigned char* is_eq;      // [n_cons - n_dyn], non-zero: equality row
+    const double *g, *mu, *rho;      // [n_cons]; mu null: zeros; the dynamics rows are not read
+    double *mu_eff, *weight;         // [n_cons] or null: mult / weight in the non-dynamics rows, 0 in the dynamics rows
+    double* info;                    // [AL_INFO] or null
+    double sigma;                    // the merit: phi = sigma * f + P where phi is given
+    const double* f;
+    double* phi;
+};
+// the row pass: one wavefront over the non-dynamics rows, further workgroups for the zeros of the dynamics rows
+void launch_al_rows(hipStream_t st, const KAlRows& A);
+// t_j += J_c' (weight .* (J_c z^_j)) for the w columns of one constraint of kind 1 or 2 without repeats; z^ and t planes [w][n_vars]
+void launch_al_gn(hipStream_t st, const KProb& P, const KCon& C, int w, int64_t n_vars, const double* dZ, const double* weight, const double* zh,
+                  double* t);
+// c_r = weight_r * c_r, r < n
+void launch_al_scale(hipStream_t st, int64_t n, const double* weight, double* c);
+// q = q + t, n entries
+void launch_al_add(hipStream_t st, int64_t n, const double* t, double* q);
+
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);
 

@@ -138,6 +138,22 @@ SYMBOLS = {
     "dto_projected_newton_step_box_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                                     C.c_double, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p]),
+    "dto_auglag_rows": (C.c_int, [H, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "dto_auglag_rows_dev": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dto_auglag_merit": (C.c_int, [H, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "dto_auglag_merit_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "dto_auglag_gradient": (C.c_int, [H, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "dto_auglag_gradient_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dto_auglag_hessian_products": (C.c_int, [H, c_double_p, C.c_double, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p]),
+    "dto_auglag_hessian_products_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
+    "dto_auglag_newton_step": (C.c_int, [H, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double,
+                                         C.c_double, C.c_double, C.c_double, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
+                                         c_double_p]),
+    "dto_auglag_newton_step_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                             C.c_double, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     "dto_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dto_comm_create": (C.c_int, [H, C.c_void_p, C.c_int32, C.c_int32]),
     "dto_comm_set_ranges": (C.c_int, [H, C.c_int32, C.c_int32, c_int64_p, c_int64_p]),

@@ -734,6 +734,110 @@ class Evaluator:
             out += (zp,)
         return out
 
+    # ---- augmented-Lagrangian terms (include/dto_engine.h, "Augmented-Lagrangian terms"): the calls above with a penalty rho_r on the
+    # non-dynamics rows.  ``rho``: (n_constraints,) or None for no penalties (the call is then the one it extends, bit for bit and
+    # launch for launch); ``Problem.penalty_vector`` expands a value per constraint over the rows.
+    def _mu_rho(self, mu, rho):
+        mu = None if mu is None else _in(mu, self.n_constraints, "mu")
+        rho = None if rho is None else _in(rho, self.n_constraints, "rho")
+        return mu, rho
+
+    @staticmethod
+    def _al_info(raw):
+        return dict(P=raw[0], active=int(raw[1]), max_viol=raw[2], sum_viol2=raw[3], max_dmult=raw[4], penalised=int(raw[5]), raw=raw)
+
+    def auglag_rows(self, Z, mu=None, rho=None):
+        """The row pass at Z (``dto_auglag_rows``): per non-dynamics row the Powell-Hestenes-Rockafellar multiplier
+        ``mult = mu + rho g`` (0 on an inactive inequality row, ``mu`` where ``rho`` is 0) and weight (``rho`` on active rows).
+        Returns (mu_eff, weight, info): (n_constraints,) each with zeros in the dynamics rows -- ``mu_eff`` is the first-order
+        multiplier update -- and info a dict with ``P`` (the sum of the rows' terms psi), ``active``, ``max_viol``, ``sum_viol2``,
+        ``max_dmult``, ``penalised`` and ``raw`` (eight doubles)."""
+        Z = self._Z(Z)
+        mu, rho = self._mu_rho(mu, rho)
+        opt = lambda a: None if a is None else _dp(a)
+        mu_eff = np.full(self.n_constraints, np.nan)
+        weight = np.full(self.n_constraints, np.nan)
+        raw = np.full(8, np.nan)
+        self._check(self._lib.dto_auglag_rows(self._h, _dp(Z), opt(mu), opt(rho), _dp(mu_eff), _dp(weight), _dp(raw)))
+        return mu_eff, weight, self._al_info(raw)
+
+    def auglag_merit(self, Z, sigma=1.0, mu=None, rho=None, trajectory=False, constraints=False, info=False):
+        """Phi = sigma f(Zf) + sum over the non-dynamics rows of psi_r(g_r(Zf)) at the feasible trajectory Zf of Z
+        (``dto_auglag_merit``): ``feasible_merit`` with the rows' augmented-Lagrangian terms.  Returns Phi, or a tuple
+        (Phi[, Zf][, g][, info]); ``info`` as ``auglag_rows`` returns it (with ``rho=None`` its values are NaN: no row pass runs)."""
+        Z = self._Z(Z)
+        mu, rho = self._mu_rho(mu, rho)
+        opt = lambda a: None if a is None else _dp(a)
+        phi = C.c_double(np.nan)
+        Zf = np.full(self.n_variables, np.nan) if trajectory else None
+        g = np.full(self.n_constraints, np.nan) if constraints else None
+        raw = np.full(8, np.nan) if info else None
+        self._check(self._lib.dto_auglag_merit(self._h, _dp(Z), float(sigma), opt(mu), opt(rho), C.byref(phi), opt(Zf), opt(g), opt(raw)))
+        out = (phi.value,) + (() if Zf is None else (Zf,)) + (() if g is None else (g,)) + (() if raw is None else (self._al_info(raw),))
+        return out if len(out) > 1 else phi.value
+
+    def auglag_gradient(self, Z, sigma=1.0, mu=None, rho=None, costates=False, multipliers=False):
+        """The reduced gradient of Phi (``dto_auglag_gradient``): ``reduced_lagrangian_gradient`` at ``mu_eff``, bit for bit.
+        Returns grad, or (grad[, Lam][, mu_eff])."""
+        Z = self._Z(Z)
+        mu, rho = self._mu_rho(mu, rho)
+        opt = lambda a: None if a is None else _dp(a)
+        grad = np.full(self.n_variables, np.nan)
+        lam = np.full((self.trajectory.N, sum(self._integrator_dims)), np.nan) if costates else None
+        mu_eff = np.full(self.n_constraints, np.nan) if multipliers else None
+        self._check(self._lib.dto_auglag_gradient(self._h, _dp(Z), float(sigma), opt(mu), opt(rho), _dp(grad), opt(lam), opt(mu_eff)))
+        out = (grad,) + (() if lam is None else (lam,)) + (() if mu_eff is None else (mu_eff,))
+        return out if len(out) > 1 else grad
+
+    def auglag_hessian_products(self, Z, V, sigma=1.0, mu=None, rho=None):
+        """Y[c] = T'(H(Z; sigma, mu~_eff) + J_c' W J_c) T V[c] (``dto_auglag_hessian_products``): ``reduced_hessian_products`` at
+        ``mu_eff`` with the Gauss-Newton term of the penalised rows, W = diag(weight).  Every row has the bits of the call with that
+        row alone."""
+        Z = self._Z(Z)
+        V = self._columns(V, self.n_variables, "V")
+        mu, rho = self._mu_rho(mu, rho)
+        opt = lambda a: None if a is None else _dp(a)
+        Y = np.full(V.shape, np.nan)
+        self._check(self._lib.dto_auglag_hessian_products(self._h, _dp(Z), float(sigma), opt(mu), opt(rho), V.shape[0], _dp(V), _dp(Y)))
+        return Y
+
+    def auglag_hessian_product(self, Z, v, sigma=1.0, mu=None, rho=None):
+        """``auglag_hessian_products`` of one vector; returns (n_variables,)."""
+        return self.auglag_hessian_products(Z, _in(v, self.n_variables, "v")[None, :], sigma, mu, rho)[0]
+
+    def auglag_newton_step(self, Z, sigma=1.0, mu=None, rho=None, lo=None, hi=None, free=None, radius=0.0, shift=0.0, rtol=1e-6, atol=0.0,
+                           max_iter=50, trace=False, states=False, trajectory=False):
+        """``reduced_newton_step_box`` on the augmented Lagrangian (``dto_auglag_newton_step``): the gradient is ``auglag_gradient``,
+        the operator ``auglag_hessian_product``; arguments and results as there."""
+        Z = self._Z(Z)
+        mu, rho = self._mu_rho(mu, rho)
+        if free is not None:
+            free = _in(free, self.n_variables, "free")
+        if lo is not None:
+            lo = _in(lo, self.n_variables, "lo")
+        if hi is not None:
+            hi = _in(hi, self.n_variables, "hi")
+        max_iter = int(max_iter)
+        opt = lambda a: None if a is None else _dp(a)
+        p = np.full(self.n_variables, np.nan)
+        raw = np.full(12, np.nan)
+        tr = np.full((max(max_iter, 0), 6), np.nan) if trace else None
+        es = np.full(self.n_variables, np.nan) if states else None
+        zp = np.full(self.n_variables, np.nan) if trajectory else None
+        self._check(self._lib.dto_auglag_newton_step(self._h, _dp(Z), float(sigma), opt(mu), opt(rho), opt(free), opt(lo), opt(hi),
+                                                     float(radius), float(shift), float(rtol), float(atol), max_iter, _dp(p), _dp(raw),
+                                                     opt(tr), opt(es), opt(zp)))
+        info = dict(status=int(raw[0]), iterations=int(raw[1]), gnorm=raw[2], rnorm=raw[3], pnorm=raw[4], pg=raw[5], predicted=raw[6],
+                    curvature=raw[7], held=int(raw[8]), hit=int(raw[9]), restarts=int(raw[10]), n_free=int(raw[11]), raw=raw)
+        out = (p, info)
+        if trace:
+            out += (tr[:info["iterations"]],)
+        if states:
+            out += (es,)
+        if trajectory:
+            out += (zp,)
+        return out
+
     def independent_entries(self):
         """C: the entries of Z that are no state of a knot 2 .. N (controls, timesteps, times, the states of knot 1, globals),
         ascending, 0-based -- the variables of the reduced problem."""
@@ -880,6 +984,34 @@ class Evaluator:
                                                                 dhi or None, float(radius), float(shift), float(rtol), float(atol),
                                                                 int(max_iter), dp or None, dinfo or None, dtrace or None, dstates or None,
                                                                 dZp or None, stream))
+
+    def auglag_rows_dev(self, dZ, dmu, drho, dmu_eff=0, dweight=0, dinfo=0, stream=0):
+        """``auglag_rows`` on device pointers: dmu, drho, dmu_eff, dweight (n_constraints) and dinfo (8 doubles), any but dZ may be 0."""
+        self._check(self._lib.dto_auglag_rows_dev(self._h, dZ or None, dmu or None, drho or None, dmu_eff or None, dweight or None,
+                                                  dinfo or None, stream))
+
+    def auglag_merit_dev(self, dZ, sigma, dmu, drho, dphi, dZf=0, dg=0, dinfo=0, stream=0):
+        """``auglag_merit`` on device pointers (dphi one double, dinfo 8 doubles); drho = 0: ``feasible_merit_dev``."""
+        self._check(self._lib.dto_auglag_merit_dev(self._h, dZ or None, float(sigma), dmu or None, drho or None, dphi or None, dZf or None,
+                                                   dg or None, dinfo or None, stream))
+
+    def auglag_gradient_dev(self, dZ, sigma, dmu, drho, dgrad, dlam=0, dmu_eff=0, stream=0):
+        """``auglag_gradient`` on device pointers; drho = 0: ``reduced_gradient_dev``."""
+        self._check(self._lib.dto_auglag_gradient_dev(self._h, dZ or None, float(sigma), dmu or None, drho or None, dgrad or None,
+                                                      dlam or None, dmu_eff or None, stream))
+
+    def auglag_hessian_products_dev(self, dZ, sigma, dmu, drho, n_cols, dV, dY, stream=0):
+        """``auglag_hessian_products`` on device pointers, dV and dY (n_cols, n_variables); drho = 0: ``reduced_hessian_products_dev``."""
+        self._check(self._lib.dto_auglag_hessian_products_dev(self._h, dZ or None, float(sigma), dmu or None, drho or None, int(n_cols),
+                                                              dV or None, dY or None, stream))
+
+    def auglag_newton_step_dev(self, dZ, sigma, dmu, drho, dfree, dlo, dhi, radius, shift, rtol, atol, max_iter, dp, dinfo, dtrace=0,
+                               dstates=0, dZp=0, stream=0):
+        """``auglag_newton_step`` on device pointers, arguments as ``reduced_newton_step_box_dev`` with drho behind dmu."""
+        self._check(self._lib.dto_auglag_newton_step_dev(self._h, dZ or None, float(sigma), dmu or None, drho or None, dfree or None,
+                                                         dlo or None, dhi or None, float(radius), float(shift), float(rtol), float(atol),
+                                                         int(max_iter), dp or None, dinfo or None, dtrace or None, dstates or None,
+                                                         dZp or None, stream))
 
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod

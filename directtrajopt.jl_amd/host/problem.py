@@ -512,3 +512,26 @@ class DirectTrajOptProblem:
                     raise ValueError(f"bounds_vectors: {name!r} has {idx.shape[1]} rows, the bound has shape {value.shape}")
                 vec[idx] = value       # (a scalar or a row, broadcast over the knots)
         return lo, hi
+
+    def penalty_vector(self, value):
+        """Penalties for ``Evaluator.auglag_*`` expanded over the constraint rows: the (n_constraints,) vector ``rho`` with 0 in the
+        dynamics rows (every integrator's rows, which come first) and, on the rows of constraint ``i`` of ``self.constraints``, the
+        scalar ``value`` or ``value[i]`` of a dict ``{constraint index: value}``; constraints a dict does not name keep 0 (they are
+        not penalised).  A value may be a scalar or one entry per row of its constraint."""
+        n_dyn = sum(it.dim for it in self.integrators)
+        rho = np.zeros(n_dyn + sum(c.dim for c in self.constraints))
+        row = n_dyn
+        for i, c in enumerate(self.constraints):
+            v = value.get(i, 0.0) if isinstance(value, dict) else value
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.size != c.dim):
+                raise ValueError(f"penalty_vector: constraint {i} has {c.dim} rows, the penalty has shape {v.shape}")
+            if np.any(~(v >= 0.0)):
+                raise ValueError(f"penalty_vector: the penalty of constraint {i} must be >= 0 and no NaN")
+            rho[row:row + c.dim] = v
+            row += c.dim
+        if isinstance(value, dict):
+            unknown = [i for i in value if not (isinstance(i, (int, np.integer)) and 0 <= i < len(self.constraints))]
+            if unknown:
+                raise KeyError(f"penalty_vector: no constraint with index {unknown}")
+        return rho

@@ -717,6 +717,67 @@ int dto_projected_newton_step_box_dev(dto_handle* h, const double* dZ, double si
                                       const double* dhi, double radius, double shift, double rtol, double atol, int32_t max_iter, double* dp,
                                       double* dinfo, double* dtrace, double* dentry_state, double* dZp, void* stream);
 
+/* ---- Augmented-Lagrangian terms: the reduced-space calls above with a penalty on the non-dynamics rows (the knot constraints), so that
+ * the trust-region loop of dto_projected_newton_step_box / dto_feasible_merit becomes the inner loop of an augmented-Lagrangian method.
+ * A non-dynamics row r is an equality row (g_r = 0) or an inequality row (g_r <= 0) by its constraint's `equality` flag
+ * (dto_constraint_bounds reports it); it has a multiplier mu_r and a penalty rho_r.  The row rules (Powell, Hestenes, Rockafellar;
+ * csrc/dto_auglag_plan.h holds them as the function al_row the kernels call, every product, sum and quotient rounded on its own):
+ *     rho_r == 0                       psi = mu g,  mult = mu,  weight = 0            (the row is not penalised, as in the calls above)
+ *     s = mu + rho g
+ *     equality row, or s > 0           psi = (mu + (0.5 rho) g) g,  mult = s,  weight = rho          (active)
+ *     inequality row, s <= 0           psi = -(mu mu) / (2 rho),    mult = 0,  weight = 0            (inactive)
+ *     viol = |g| (equality), max(0, g) (inequality);  a NaN in g, mu or rho, or rho < 0, gives NaN in psi, mult and weight
+ * mult = psi'(g), weight = psi''(g).  P = sum_r psi_r is summed in dto_feasible_merit's order (lane l of 64 adds r = n_dyn + l, + 64, ..,
+ * then the halving tree), so with every rho_r = 0 the merit below has dto_feasible_merit's bits.
+ *   mu, rho [n_cons] doubles; the dynamics rows are not read.  mu may be NULL (zeros).  rho == NULL means no penalties: every call then
+ *   makes the launches, and returns the bits, of the call it extends (named with each).
+ *   info [8]: [0] P  [1] active rows  [2] max viol  [3] sum viol^2  [4] max |mult - mu|  [5] penalised rows (rho != 0)  [6], [7] 0;
+ *   the maxima are exact and the counts integers held in doubles.
+ * dto_auglag_rows: the row pass at Z.  mu_eff [n_cons]: mult in the non-dynamics rows (the first-order multiplier update), 0 in the
+ *   dynamics rows; weight [n_cons] likewise; any of mu_eff, weight, info may be NULL.  The rows of g come from the constraints' value
+ *   kernels alone: no sweep and no chain runs.
+ * dto_auglag_merit: Phi = sigma f(Zf) + P(g(Zf)), Zf = the feasible trajectory of Z; dto_feasible_merit with the row pass in place of its
+ *   sum (rho == NULL: dto_feasible_merit itself, info is then left untouched).  Zf, g, info optional.
+ * dto_auglag_gradient: the reduced gradient of Phi: dto_reduced_gradient at mu_eff, bit for bit (rho == NULL: dto_reduced_gradient at mu;
+ *   mu_eff is then mu with its dynamics rows zeroed).  lam, mu_eff optional.
+ * dto_auglag_hessian_products: Y = T'(H(Z; sigma, mu~_eff) + J_c' W J_c) T V for n_cols vectors, J_c the non-dynamics rows of the Jacobian
+ *   and W = diag(weight): dto_projected_hessian_products at mu_eff, with the Gauss-Newton term t_j = J_c' (W (J_c z^_j)) added to
+ *   q_j = H z^_j by one rounded addition before q_S is gathered.  The bits of t_j are those of dto_eval_jacobian_product (non-dynamics
+ *   rows), the scaling weight_r * c_r and dto_eval_jacobian_transpose_product of [0; c] on the same handle: a row's sum in the knot
+ *   kernels' component order (pattern entries only), the constraints in list order, a constraint that repeats a knot walking its
+ *   listings in order; on a handle whose products take the value-slab route, the slab products themselves.  Column c has the bits of
+ *   the call with that column alone.  (rho == NULL: dto_projected_hessian_products.)
+ * dto_auglag_newton_step: dto_projected_newton_step_box with that operator and that gradient; arguments, outputs, info [12] and trace as
+ *   there, NULL bounds mean none.  (rho == NULL: dto_projected_newton_step_box.)
+ * Points and costs.  A call runs the row pass once (one launch and the constraints' value kernels), then works at the three kept points
+ *   of the call it extends with mu_eff as the multipliers: the points compare contents, so a second call at the same (Z, sigma, mu, rho)
+ *   rebuilds nothing.  A chunk of w columns adds one launch per constraint ||v|| - c or ||v||^2 - c whose times and comps repeat nothing,
+ *   whatever w is, and one addition launch; a quadratic-form constraint and a constraint that repeats a knot or a component go through
+ *   the single-column product kernels, one column at a time.  Profile name "auglag".
+ * Refused with text, the handle stays usable and nothing is enqueued: what the extended call refuses; a handle with a host-evaluated
+ *   constraint (global constraints are among these); in the host-pointer forms a rho_r that is negative or a NaN, naming the row; outputs
+ *   that overlap inputs.  The _dev forms take device pointers and work on `stream`, errors deferred as for every _dev call. */
+int dto_auglag_rows(dto_handle* h, const double* Z, const double* mu, const double* rho, double* mu_eff, double* weight, double* info);
+int dto_auglag_rows_dev(dto_handle* h, const double* dZ, const double* dmu, const double* drho, double* dmu_eff, double* dweight, double* dinfo,
+                        void* stream);
+int dto_auglag_merit(dto_handle* h, const double* Z, double sigma, const double* mu, const double* rho, double* phi, double* Zf, double* g,
+                     double* info);
+int dto_auglag_merit_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* drho, double* dphi, double* dZf, double* dg,
+                         double* dinfo, void* stream);
+int dto_auglag_gradient(dto_handle* h, const double* Z, double sigma, const double* mu, const double* rho, double* grad, double* lam, double* mu_eff);
+int dto_auglag_gradient_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* drho, double* dgrad, double* dlam,
+                            double* dmu_eff, void* stream);
+int dto_auglag_hessian_products(dto_handle* h, const double* Z, double sigma, const double* mu, const double* rho, int32_t n_cols, const double* V,
+                                double* Y);
+int dto_auglag_hessian_products_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* drho, int32_t n_cols,
+                                    const double* dV, double* dY, void* stream);
+int dto_auglag_newton_step(dto_handle* h, const double* Z, double sigma, const double* mu, const double* rho, const double* free_mask,
+                           const double* lo, const double* hi, double radius, double shift, double rtol, double atol, int32_t max_iter, double* p,
+                           double* info, double* trace, double* entry_state, double* Zp);
+int dto_auglag_newton_step_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* drho, const double* dfree_mask,
+                               const double* dlo, const double* dhi, double radius, double shift, double rtol, double atol, int32_t max_iter,
+                               double* dp, double* dinfo, double* dtrace, double* dentry_state, double* dZp, void* stream);
+
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
  * communicator (SURVEY.md §8b "Ownership").  No callback needs a collective: every rank's Jacobian / Hessian / gradient
@@ -894,6 +955,8 @@ int dto_profile_reset(dto_handle* h);
  * of the iterations count as the block products do).
  * "newton_box" (dto_projected_newton_step_box and its _dev form: its four kernels, counted in the same way; no launch of it counts
  * under "newton").
+ * "auglag" (the dto_auglag_* calls: the row pass, the Gauss-Newton term's launches, the scaling and the addition; third output: BYTES as
+ * executed; it feeds no other name, "all" included; with rho == NULL no launch counts here).
  * The block products count under "hess_product", "reduced_pack" and "reduced_input" too, one launch per chunk where a single product
  * has one, with bytes as executed: matrix bytes once per tile or chunk, vector bytes per column.
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the

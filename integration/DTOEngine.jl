@@ -1016,6 +1016,174 @@ function newton_step_box_dev!(ev::GPUEvaluator, dp::Ptr{Float64}, dinfo::Ptr{Flo
                                                                stream::Ptr{Cvoid})::Cint)
 end
 
+# ---- augmented-Lagrangian terms (include/dto_engine.h, "Augmented-Lagrangian terms") ----------------------------------------------------
+# The reduced-space calls above with a penalty ρ_r on the non-dynamics rows (Powell-Hestenes-Rockafellar: inequality rows g_r ≤ 0 by the
+# constraint's `equality = false`).  `μ`, `ρ`: n_constraints each or `nothing` (μ: zeros; ρ: no penalties, the call is then the one it
+# extends).  `penalty_vector(ev, value)` expands a value per constraint over the rows.
+function auglag_ptr(x::Union{Nothing,AbstractVector{Float64}}, xv::Vector{Float64})
+    return x === nothing ? Ptr{Float64}(C_NULL) : pointer(xv)
+end
+
+function auglag_check_lengths(ev::GPUEvaluator, who::String, Z, μ, ρ)
+    reduced_check_lengths(ev, who, Z, μ)
+    ρ === nothing || length(ρ) == ev.n_constraints || error("$who: ρ has $(length(ρ)) entries, the problem has $(ev.n_constraints) constraints")
+    return nothing
+end
+
+# ρ over the rows: 0 in the dynamics rows, which come first; on the rows of constraint i (`constraint_rows[i]` of them, the constraints
+# in list order) `value`, a number, or `value[i]` of a vector with one entry per constraint
+function penalty_vector(ev::GPUEvaluator, value, constraint_rows::AbstractVector{<:Integer})
+    n_dyn = ev.n_constraints - sum(constraint_rows)
+    ρ = zeros(Float64, ev.n_constraints)
+    row = n_dyn
+    for (i, n) in enumerate(constraint_rows)
+        ρ[row+1:row+n] .= value isa Number ? Float64(value) : Float64(value[i])
+        row += n
+    end
+    return ρ
+end
+
+# the row pass at Z: (μ_eff, weight, info); μ_eff is the first-order multiplier update, info the eight doubles of the header
+function auglag_rows(ev::GPUEvaluator, Z::AbstractVector{Float64}; μ::Union{Nothing,AbstractVector{Float64}} = nothing,
+                     ρ::Union{Nothing,AbstractVector{Float64}} = nothing)
+    auglag_check_lengths(ev, "auglag_rows", Z, μ, ρ)
+    Zv = Vector{Float64}(Z)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    ρv = ρ === nothing ? Float64[] : Vector{Float64}(ρ)
+    μ_eff, weight, info = fill(NaN, ev.n_constraints), fill(NaN, ev.n_constraints), fill(NaN, 8)
+    GC.@preserve Zv μv ρv μ_eff weight info begin
+        μp, ρp = auglag_ptr(μ, μv), auglag_ptr(ρ, ρv)
+        check(ev, @ccall lib.dto_auglag_rows(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, μp::Ptr{Float64}, ρp::Ptr{Float64}, μ_eff::Ptr{Float64},
+                                             weight::Ptr{Float64}, info::Ptr{Float64})::Cint)
+    end
+    return μ_eff, weight, info
+end
+
+# Φ = σ f(Zf) + Σ ψ_r(g_r(Zf)) at the feasible trajectory Zf of Z: (Φ, Zf, g, info)
+function auglag_merit(ev::GPUEvaluator, Z::AbstractVector{Float64}; σ::Float64 = 1.0, μ::Union{Nothing,AbstractVector{Float64}} = nothing,
+                      ρ::Union{Nothing,AbstractVector{Float64}} = nothing)
+    auglag_check_lengths(ev, "auglag_merit", Z, μ, ρ)
+    Zv = Vector{Float64}(Z)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    ρv = ρ === nothing ? Float64[] : Vector{Float64}(ρ)
+    Φ = Ref{Float64}(NaN)
+    Zf, g, info = fill(NaN, ev.n_variables), fill(NaN, ev.n_constraints), fill(NaN, 8)
+    GC.@preserve Zv μv ρv Zf g info begin
+        μp, ρp = auglag_ptr(μ, μv), auglag_ptr(ρ, ρv)
+        check(ev, @ccall lib.dto_auglag_merit(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μp::Ptr{Float64}, ρp::Ptr{Float64},
+                                              Φ::Ptr{Float64}, Zf::Ptr{Float64}, g::Ptr{Float64}, info::Ptr{Float64})::Cint)
+    end
+    return Φ[], Zf, g, info
+end
+
+# the reduced gradient of Φ: (grad, μ_eff)
+function auglag_gradient(ev::GPUEvaluator, Z::AbstractVector{Float64}; σ::Float64 = 1.0, μ::Union{Nothing,AbstractVector{Float64}} = nothing,
+                         ρ::Union{Nothing,AbstractVector{Float64}} = nothing)
+    auglag_check_lengths(ev, "auglag_gradient", Z, μ, ρ)
+    Zv = Vector{Float64}(Z)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    ρv = ρ === nothing ? Float64[] : Vector{Float64}(ρ)
+    grad, μ_eff = fill(NaN, ev.n_variables), fill(NaN, ev.n_constraints)
+    lam = Ptr{Float64}(C_NULL)
+    GC.@preserve Zv μv ρv grad μ_eff begin
+        μp, ρp = auglag_ptr(μ, μv), auglag_ptr(ρ, ρv)
+        check(ev, @ccall lib.dto_auglag_gradient(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μp::Ptr{Float64}, ρp::Ptr{Float64},
+                                                 grad::Ptr{Float64}, lam::Ptr{Float64}, μ_eff::Ptr{Float64})::Cint)
+    end
+    return grad, μ_eff
+end
+
+# Y[:, c] = T'(H(Z; σ, μ~_eff) + J_c' W J_c) T V[:, c]
+function auglag_hessian_products(ev::GPUEvaluator, Z::AbstractVector{Float64}, V::AbstractMatrix{Float64}; σ::Float64 = 1.0,
+                                 μ::Union{Nothing,AbstractVector{Float64}} = nothing, ρ::Union{Nothing,AbstractVector{Float64}} = nothing)
+    block_check_lengths(ev, "auglag_hessian_products", Z, μ, V)
+    auglag_check_lengths(ev, "auglag_hessian_products", Z, μ, ρ)
+    Zv, Vm = Vector{Float64}(Z), Matrix{Float64}(V)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    ρv = ρ === nothing ? Float64[] : Vector{Float64}(ρ)
+    Y = fill(NaN, ev.n_variables, size(Vm, 2))
+    nc = Int32(size(Vm, 2))
+    GC.@preserve Y Zv Vm μv ρv begin
+        μp, ρp = auglag_ptr(μ, μv), auglag_ptr(ρ, ρv)
+        check(ev, @ccall lib.dto_auglag_hessian_products(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μp::Ptr{Float64}, ρp::Ptr{Float64},
+                                                         nc::Int32, Vm::Ptr{Float64}, Y::Ptr{Float64})::Cint)
+    end
+    return Y
+end
+
+function auglag_hessian_product(ev::GPUEvaluator, Z::AbstractVector{Float64}, v::AbstractVector{Float64}; σ::Float64 = 1.0,
+                                μ::Union{Nothing,AbstractVector{Float64}} = nothing, ρ::Union{Nothing,AbstractVector{Float64}} = nothing)
+    return vec(auglag_hessian_products(ev, Z, reshape(Vector{Float64}(v), :, 1); σ = σ, μ = μ, ρ = ρ))
+end
+
+# newton_step_box on the augmented Lagrangian: (p, info, trace, states, Zp) as there
+function auglag_newton_step(ev::GPUEvaluator, Z::AbstractVector{Float64}; σ::Float64 = 1.0, μ::Union{Nothing,AbstractVector{Float64}} = nothing,
+                            ρ::Union{Nothing,AbstractVector{Float64}} = nothing, lo::Union{Nothing,AbstractVector{Float64}} = nothing,
+                            hi::Union{Nothing,AbstractVector{Float64}} = nothing, free::Union{Nothing,AbstractVector{Float64}} = nothing,
+                            radius::Float64 = 0.0, shift::Float64 = 0.0, rtol::Float64 = 1e-6, atol::Float64 = 0.0, max_iter::Integer = 50)
+    reduced_check_lengths(ev, "auglag_newton_step", Z, μ, free)
+    auglag_check_lengths(ev, "auglag_newton_step", Z, μ, ρ)
+    (lo === nothing || length(lo) == ev.n_variables) || error("auglag_newton_step: lo has $(length(lo)) entries, n_variables = $(ev.n_variables)")
+    (hi === nothing || length(hi) == ev.n_variables) || error("auglag_newton_step: hi has $(length(hi)) entries, n_variables = $(ev.n_variables)")
+    max_iter >= 1 || error("auglag_newton_step: max_iter = $max_iter, at least 1 iteration is required")
+    Zv = Vector{Float64}(Z)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    ρv = ρ === nothing ? Float64[] : Vector{Float64}(ρ)
+    fv = free === nothing ? Float64[] : Vector{Float64}(free)
+    lov = lo === nothing ? Float64[] : Vector{Float64}(lo)
+    hiv = hi === nothing ? Float64[] : Vector{Float64}(hi)
+    p, info, trace = fill(NaN, ev.n_variables), fill(NaN, 12), fill(NaN, 6, Int(max_iter))
+    states, Zp = fill(NaN, ev.n_variables), fill(NaN, ev.n_variables)
+    mi = Int32(max_iter)
+    GC.@preserve Zv μv ρv fv lov hiv p info trace states Zp begin
+        μp, ρp, fp, lop, hip = auglag_ptr(μ, μv), auglag_ptr(ρ, ρv), auglag_ptr(free, fv), auglag_ptr(lo, lov), auglag_ptr(hi, hiv)
+        check(ev, @ccall lib.dto_auglag_newton_step(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μp::Ptr{Float64}, ρp::Ptr{Float64},
+                                                    fp::Ptr{Float64}, lop::Ptr{Float64}, hip::Ptr{Float64}, radius::Float64, shift::Float64,
+                                                    rtol::Float64, atol::Float64, mi::Int32, p::Ptr{Float64}, info::Ptr{Float64},
+                                                    trace::Ptr{Float64}, states::Ptr{Float64}, Zp::Ptr{Float64})::Cint)
+    end
+    return p, info, trace[:, 1:Int(info[2])], states, Zp
+end
+
+# the same on device pointers, enqueued on `stream`; every pointer but dZ (and the required outputs) may be C_NULL
+function auglag_rows_dev!(ev::GPUEvaluator, dμ_eff::Ptr{Float64}, dweight::Ptr{Float64}, dinfo::Ptr{Float64}, dZ::Ptr{Float64}, dμ::Ptr{Float64},
+                          dρ::Ptr{Float64}, stream::Ptr{Cvoid})
+    check(ev, @ccall lib.dto_auglag_rows_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, dμ::Ptr{Float64}, dρ::Ptr{Float64}, dμ_eff::Ptr{Float64},
+                                             dweight::Ptr{Float64}, dinfo::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
+function auglag_merit_dev!(ev::GPUEvaluator, dΦ::Ptr{Float64}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dρ::Ptr{Float64}, dZf::Ptr{Float64},
+                           dg::Ptr{Float64}, dinfo::Ptr{Float64}, stream::Ptr{Cvoid})
+    check(ev, @ccall lib.dto_auglag_merit_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dρ::Ptr{Float64},
+                                              dΦ::Ptr{Float64}, dZf::Ptr{Float64}, dg::Ptr{Float64}, dinfo::Ptr{Float64},
+                                              stream::Ptr{Cvoid})::Cint)
+end
+
+function auglag_gradient_dev!(ev::GPUEvaluator, dgrad::Ptr{Float64}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dρ::Ptr{Float64},
+                              dlam::Ptr{Float64}, dμ_eff::Ptr{Float64}, stream::Ptr{Cvoid})
+    check(ev, @ccall lib.dto_auglag_gradient_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dρ::Ptr{Float64},
+                                                 dgrad::Ptr{Float64}, dlam::Ptr{Float64}, dμ_eff::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
+function auglag_hessian_products_dev!(ev::GPUEvaluator, dY::Ptr{Float64}, dZ::Ptr{Float64}, dV::Ptr{Float64}, n_cols::Integer, σ::Float64,
+                                      dμ::Ptr{Float64}, dρ::Ptr{Float64}, stream::Ptr{Cvoid})
+    nc = Int32(n_cols)
+    check(ev, @ccall lib.dto_auglag_hessian_products_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dρ::Ptr{Float64},
+                                                         nc::Int32, dV::Ptr{Float64}, dY::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
+function auglag_newton_step_dev!(ev::GPUEvaluator, dp::Ptr{Float64}, dinfo::Ptr{Float64}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64},
+                                 dρ::Ptr{Float64}, dfree::Ptr{Float64}, dlo::Ptr{Float64}, dhi::Ptr{Float64}, radius::Float64, shift::Float64,
+                                 rtol::Float64, atol::Float64, max_iter::Integer, dtrace::Ptr{Float64}, dstates::Ptr{Float64}, dZp::Ptr{Float64},
+                                 stream::Ptr{Cvoid})
+    mi = Int32(max_iter)
+    check(ev, @ccall lib.dto_auglag_newton_step_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dρ::Ptr{Float64},
+                                                    dfree::Ptr{Float64}, dlo::Ptr{Float64}, dhi::Ptr{Float64}, radius::Float64,
+                                                    shift::Float64, rtol::Float64, atol::Float64, mi::Int32, dp::Ptr{Float64},
+                                                    dinfo::Ptr{Float64}, dtrace::Ptr{Float64}, dstates::Ptr{Float64}, dZp::Ptr{Float64},
+                                                    stream::Ptr{Cvoid})::Cint)
+end
+
 # row bounds handed to the solver (src/solvers/solve.jl:30-65)
 function constraint_bounds(ev::GPUEvaluator)
     lo = Vector{Float64}(undef, ev.n_constraints)

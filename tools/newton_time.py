@@ -34,10 +34,18 @@ its "newton" profile, and
     excess_ms = (box step - yardstick) - (newton_box device ms - newton device ms) - (yardstick max - yardstick min)
 -- what of the difference neither the kernels' own device time nor the yardstick's spread explains (negative: nothing).
 
+``--auglag`` measures the augmented-Lagrangian step (Evaluator.auglag_newton_step_dev) with rho = 10 on the rows of the tool's knot
+constraint and infinite bounds, in the same way.  The YARDSTICK is the box step (reduced_newton_step_box_dev) at the same (Z, sigma, mu):
+another operator (the step adds the Gauss-Newton term and works at mu_eff), so the iterates differ; both run exactly ``max_iter``
+iterations (rtol = 0, shift from the power iterations with the augmented operator).  Beside the two medians: the "auglag" profile name
+of one call (device milliseconds, launches, bytes, and all three per iteration), the yardstick's "newton_box" profile, the active rows, and
+    excess_ms = (auglag step - yardstick) - auglag device ms - (yardstick max - yardstick min)
+
 One JSON line per shape.
 
     python tools/newton_time.py                       # 256 x 2000 and 64 x 1000
     python tools/newton_time.py --box                 # the bound-constrained step beside the existing one
+    python tools/newton_time.py --auglag              # the augmented-Lagrangian step beside the bound-constrained one
     python tools/newton_time.py --shapes 128x1000 --reps 9 --iters 10,30
 """
 import argparse
@@ -149,6 +157,65 @@ def measure_box(n, N, drives, scale, reps, iters):
         ev.close()
 
 
+def measure_auglag(n, N, drives, scale, reps, iters, rho_value=10.0):
+    """the augmented-Lagrangian step beside the box step (the yardstick), infinite bounds, rho on the knot constraint's rows"""
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    prob = dto_amd.host.synthetic.multi_ket_problem(n, 1, drives, N, seed=42, u_bound=4.0, scale=scale or None)
+    ev = dto_amd.Evaluator(prob)
+    ev.set_option("reduced_input_store", 1)
+    out = {"mode": "auglag", "n": n, "knots": N, "drives": drives, "scale": scale, "reps": reps, "sigma": SIGMA, "rho": rho_value,
+           "route": "reduced_input_store"}
+    try:
+        Zh = np.ascontiguousarray(prob.trajectory.vec(), dtype=np.float64)
+        Z = torch.from_numpy(Zh).to(dev)
+        gen = torch.Generator(device=dev); gen.manual_seed(7)
+        mu = torch.randn(ev.n_constraints, dtype=torch.float64, device=dev, generator=gen)
+        rho = torch.from_numpy(prob.penalty_vector(rho_value)).to(dev)
+        f64 = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
+        nv = ev.n_variables
+        y, p, info, pa, info_a, rows_info = f64(1, nv), f64(nv), f64(12), f64(nv), f64(12), f64(8)
+        mask = torch.zeros(nv, dtype=torch.float64, device=dev)
+        mask[torch.from_numpy(ev.independent_entries()).to(dev)] = 1.0
+        out["n_variables"], out["chunks"], out["rows"] = nv, -(-nv // 256), ev.n_constraints - ev.n_dynamics_constraints
+        ev.auglag_rows_dev(Z.data_ptr(), mu.data_ptr(), rho.data_ptr(), 0, 0, rows_info.data_ptr(), st)
+        torch.cuda.synchronize()
+        out["active_rows"], out["max_viol"] = int(rows_info[1]), float(rows_info[2])
+        v = (torch.randn(nv, dtype=torch.float64, device=dev, generator=gen) * mask).reshape(1, nv)
+        top = 0.0
+        for _ in range(8):
+            v = v / torch.linalg.norm(v)
+            ev.auglag_hessian_products_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), rho.data_ptr(), 1, v.data_ptr(), y.data_ptr(), st)
+            top = max(top, abs(float(torch.sum(v * y))))
+            v = y.clone()
+        shift = 2.0 * top
+        out["shift"] = shift
+
+        def profile(name, fn, max_iter):
+            ev.profile_enable(True); ev.profile_reset(); fn(); torch.cuda.synchronize()
+            ms, launches, nbytes = ev.profile_get(name)
+            ev.profile_enable(False)
+            return {"ms": round(ms, 4), "launches": launches, "bytes": nbytes, "ms_per_iteration": round(ms / max_iter, 5),
+                    "launches_per_iteration": launches / max_iter, "bytes_per_iteration": nbytes / max_iter}
+
+        for max_iter in iters:
+            box = lambda: ev.reduced_newton_step_box_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), 0, 0, 0, 0.0, shift, 0.0, 0.0, max_iter, p.data_ptr(),
+                                                         info.data_ptr(), 0, 0, 0, st)
+            al = lambda: ev.auglag_newton_step_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), rho.data_ptr(), 0, 0, 0, 0.0, shift, 0.0, 0.0, max_iter,
+                                                   pa.data_ptr(), info_a.data_ptr(), 0, 0, 0, st)
+            pair = alternating(box, al, reps)
+            al(); torch.cuda.synchronize()
+            raw = info_a.cpu().numpy()
+            pair.update(status=int(raw[0]), iterations=int(raw[1]))
+            pair["auglag_profile"] = profile("auglag", al, max_iter)
+            pair["yardstick_newton_box_profile"] = profile("newton_box", box, max_iter)
+            pair["excess_ms"] = round(pair["difference_ms"] - pair["auglag_profile"]["ms"] - (pair["yardstick_max_ms"] - pair["yardstick_min_ms"]), 4)
+            out[f"max_iter_{max_iter}"] = pair
+        return out
+    finally:
+        ev.close()
+
+
 def measure(n, N, drives, scale, reps, iters):
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -239,10 +306,12 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0, help="standard deviation of the generators' entries (1.0: the norms of the\n"
                     "headline benchmark; 0: 1 / sqrt(n), norms of order one)")
     ap.add_argument("--box", action="store_true", help="measure the bound-constrained step beside the existing step")
+    ap.add_argument("--auglag", action="store_true", help="measure the augmented-Lagrangian step beside the bound-constrained step")
     a = ap.parse_args()
+    run = measure_auglag if a.auglag else measure_box if a.box else measure
     for s in a.shapes.split(","):
         n, N = (int(x) for x in s.lower().split("x"))
-        print(json.dumps((measure_box if a.box else measure)(n, N, a.drives, a.scale, a.reps, [int(i) for i in a.iters.split(",")])), flush=True)
+        print(json.dumps(run(n, N, a.drives, a.scale, a.reps, [int(i) for i in a.iters.split(",")])), flush=True)
 
 
 if __name__ == "__main__":
