@@ -6,6 +6,7 @@
 #include "dto_handle.h"
 #include "dto_auglag_plan.h"
 #include "dto_newton_box_plan.h"
+#include "dto_precond_plan.h"
 #include "dto_newton_plan.h"
 #include "dto_rollout_plan.h"
 
@@ -76,7 +77,7 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25, CAT_FEASIBLE = 26, CAT_NEWTON = 27, CAT_NEWTON_BOX = 28, CAT_AUGLAG = 29 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25, CAT_FEASIBLE = 26, CAT_NEWTON = 27, CAT_NEWTON_BOX = 28, CAT_AUGLAG = 29, CAT_PRECOND = 30 };
 // CAT_ROLLOUT .. CAT_ROLLOUT_DESCENT ("rollout" = its parts "rollout_gather" + "rollout_tree" + "rollout_descent"): the gather, the
 // tree's products and the descent (with the start and the copy into the caller's layout) of dto_rollout[_dev], flops as executed with
 // padding; the tree's products run launch_bgemm_plain and count HERE, not under "bgemm_plain"; they feed no other name, "all" included
@@ -103,6 +104,9 @@ inline bool is_elim_cat(int cat) { return cat == CAT_DYNSOLVE_COUPLE || cat == C
 // CAT_NEWTON_BOX ("newton_box"): the four kernels of dto_newton_box.hip, of dto_projected_newton_step_box and its _dev form, likewise.
 // CAT_AUGLAG ("auglag"): the kernels of dto_auglag.hip -- the row pass, the Gauss-Newton term, the scaling and the addition of the
 // dto_auglag_* calls; BYTES as executed; it feeds no other name, "all" included.
+// CAT_PRECOND ("precond"): every launch of dto_preconditioned_newton_step, dto_newton_precondition and dto_newton_pairs_push_dev that is
+// no product -- the kernels of dto_precond.hip and the box step's start and curvature pass where the preconditioned step runs them;
+// BYTES as executed; it feeds no other name, "all" included.
 // The block products (dto_eval_hessian_products, dto_projected_hessian_products) count under the same names -- "hess_product",
 // "reduced_pack", "reduced_input" -- one launch per chunk each, bytes as executed: the matrices once per tile or chunk, the vectors per column.
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
@@ -3762,6 +3766,292 @@ int dto_auglag_newton_step_dev(dto_handle* h, const double* dZ, double sigma, co
     }, G_ASYNC, (hipStream_t)stream);
 }
 
+// ---- L-BFGS-preconditioned truncated-Newton step (include/dto_engine.h, "Preconditioned truncated-Newton step"; dto_precond.hip,
+// dto_precond_plan.h): newton_box_step's shape with z = P H P r behind the start and behind every update, the pairs in a two-bank store
+// on the handle.
+
+// The kernels' record over the routine's workspace and the store as it stands.  The workspace is sized for the capacity, so it is
+// allocated once per option value; the store is allocated whole where a pair may be written.
+static KPrecond precond_kernel_args(dto_handle* h, bool writes_pairs) {
+    const int64_t n = h->n_vars, nb = newton_chunks(n);
+    const int m = h->newton_pairs, cnt = h->pairs_count;
+    double* q = grow_workspace(h, h->d_precond, (size_t)precond_workspace_doubles(n, m));
+    if (writes_pairs) grow_workspace(h, h->d_pairs, (size_t)precond_store_doubles(n, m));
+    KPrecond K{};
+    KNewtonBox& A = K.B;
+    A.n = n; A.nb = nb;
+    A.r = q; A.d = q + n; A.w = q + 2 * n; K.z = q + 3 * n;
+    A.part = q + 4 * n;
+    K.uv = A.part + PRECOND_SLOTS * nb;
+    K.gram = K.uv + 2 * (int64_t)cnt * nb;
+    A.state = K.gram + (int64_t)precond_gram_count(cnt) * nb;
+    K.pc = A.state + PRECOND_STATE;
+    A.es = (unsigned char*)(K.pc + PRECOND_PC);
+    K.m = m; K.head = h->pairs_head; K.cnt = cnt; K.harvest = 0;
+    if (h->d_pairs.p && m > 0) {
+        const size_t bank = 2 * (size_t)m * (size_t)n;
+        K.S = h->d_pairs.p + (size_t)h->pairs_bank * bank;
+        K.Y = K.S + (size_t)m * (size_t)n;
+        K.HS = h->d_pairs.p + (size_t)(h->pairs_bank ^ 1) * bank;
+        K.HY = K.HS + (size_t)m * (size_t)n;
+    }
+    return K;
+}
+
+// the preparation behind the entry states, and the application to r behind the start (or to a column of dto_newton_precondition)
+static void precond_prepare_launches(dto_handle* h, const KPrecond& K, hipStream_t st) {
+    if (K.cnt == 0) return;
+    const double v = 8.0 * (double)K.B.n, part = 8.0 * (double)K.B.nb, g = (double)precond_gram_count(K.cnt);
+    { ProfScope ps(h, st, CAT_PRECOND, 2.0 * K.cnt * v + (double)K.B.n + g * part); launch_precond_gram(st, K); }
+    { ProfScope ps(h, st, CAT_PRECOND, g * part + 8.0 * PRECOND_PC); launch_precond_prep(st, K); }
+}
+static void precond_apply_launches(dto_handle* h, const KPrecond& K, const double* r, double* z, int j, bool dots, hipStream_t st) {
+    const double v = 8.0 * (double)K.B.n, by = (double)K.B.n, part = 8.0 * (double)K.B.nb, groups = (double)((K.B.nb + 15) / 16);
+    if (dots && K.cnt > 0) { ProfScope ps(h, st, CAT_PRECOND, (2.0 * K.cnt + 1.0) * v + by + 2.0 * K.cnt * part); launch_precond_dots(st, K, r); }
+    ProfScope ps(h, st, CAT_PRECOND, (2.0 * K.cnt + 2.0) * v + by + part + groups * (2.0 * K.cnt * part + 8.0 * PRECOND_PC));
+    launch_precond_comb(st, K, r, z, j);
+}
+
+// The device routine both entry-point families run: everything on `st`, every pointer a device pointer.
+static void precond_step(dto_handle* h, const ElimPlan& p, const double* dZ, double sigma, const double* dmu, const NewtonBoxArgs& a, int harvest,
+                         hipStream_t st, const AlWork* al = nullptr) {
+    const KReduced& R = h->red;
+    const bool store_route = h->reduced_input_store && h->K >= 1;
+    // every workspace before anything is enqueued
+    KPrecond K = precond_kernel_args(h, harvest != 0);
+    const BlockWork B = block_workspaces(h, p, 1, store_route);
+    KNewtonBox& A = K.B;
+    K.harvest = harvest ? 1 : 0;
+    A.p = a.p; A.g = h->red_r; A.mask = a.mask; A.Z = dZ; A.lo = a.lo; A.hi = a.hi;
+    A.info = a.info; A.trace = a.trace; A.zp = a.zp; A.es_out = a.entry_state;
+    A.radius = a.radius; A.shift = a.shift; A.rtol = a.rtol; A.atol = a.atol;
+    const ElimWork EW = projected_points(h, p, dZ, sigma, dmu, 1, st);
+    const int64_t nb = A.nb;
+    const double v = 8.0 * (double)A.n, by = (double)A.n, m = a.mask ? v : 0.0, bounds = (a.lo ? v : 0.0) + (a.hi ? v : 0.0);
+    const double outs = (a.zp ? v : 0.0) + (a.entry_state ? v : 0.0), part = 8.0 * (double)nb, groups = (double)((nb + 15) / 16);
+    const double pairs = 2.0 * K.cnt;
+    auto read_back = [&] {   // the one readback per iteration: status, iterations, pairs taken
+        HIP_CHECK(hipMemcpyAsync(h->mailbox->precond, A.state, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return (int)h->mailbox->precond[NPS_STATUS] == NEWTON_CONTINUE;
+    };
+    { ProfScope ps(h, st, CAT_PRECOND, 5.0 * v + m + bounds + by + outs + 7.0 * part); launch_newton_box_start(st, R, A); }
+    precond_prepare_launches(h, K, st);
+    precond_apply_launches(h, K, A.r, K.z, 0, true, st);
+    { ProfScope ps(h, st, CAT_PRECOND, 2.0 * v + by + (3.0 * groups + 5.0) * part); launch_precond_dir(st, K, 0, a.max_iter); }
+    for (int j = 1; j <= a.max_iter && read_back(); ++j) {
+        projected_chunk(h, p, B, EW, store_route, dZ, 1, A.d, A.w, st, al);   // y = T'HT d (with `al`: T'(H + J_c' W J_c)T d)
+        { ProfScope ps(h, st, CAT_PRECOND, 5.0 * v + bounds + by + 5.0 * part); launch_newton_box_curv(st, A); }
+        {   // the box step's bytes, the harvest copy where a pair may be taken, the multi-dot pass (counted as if the preconditioner is on)
+            ProfScope ps(h, st, CAT_PRECOND,
+                         (8.0 + (harvest ? 2.0 : 0.0) + pairs) * v + bounds + 2.0 * by + outs + (6.0 + pairs) * part + groups * 5.0 * part);
+            launch_precond_step(st, K, j);
+        }
+        precond_apply_launches(h, K, A.r, K.z, j, false, st);
+        { ProfScope ps(h, st, CAT_PRECOND, 3.0 * v + by + (3.0 * groups + 5.0) * part); launch_precond_dir(st, K, j, a.max_iter); }
+    }
+    if (!harvest) return;
+    read_back();
+    const int64_t taken = (int64_t)h->mailbox->precond[NPS_TAKEN_OUT];
+    if (taken < 1) return;
+    h->pairs_bank ^= 1;
+    h->pairs_count = (int)std::min<int64_t>(K.m, taken);
+    h->pairs_head = taken > K.m ? (int)(taken % K.m) : 0;
+}
+
+static std::string precond_refusal(const dto_handle* h, const std::string& who, int32_t harvest) {
+    if (harvest != 0 && h->newton_pairs == 0)
+        return who + ": harvest needs a pair store: set the option newton_pairs to 1 .. " + std::to_string(PRECOND_MAX_PAIRS) + " first (it is 0)";
+    return "";
+}
+
+int dto_preconditioned_newton_step(dto_handle* h, const double* Z, double sigma, const double* mu, const double* rho, const double* free_mask,
+                                   const double* lo, const double* hi, double radius, double shift, double rtol, double atol, int32_t max_iter,
+                                   int32_t harvest, double* p, double* info, double* trace, double* entry_state, double* Zp) {
+    const std::string who = "dto_preconditioned_newton_step";
+    if (!h) return fail(nullptr, "null handle");
+    std::string bad = newton_refusal(who, Z, radius, shift, rtol, atol, max_iter, p, info);
+    if (bad.empty()) bad = newton_box_refusal(who, (size_t)h->n_vars, Z, free_mask, lo, hi, p, Zp, entry_state);
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars;
+    if (bad.empty() && rho)
+        bad = auglag_refusal(h, who, rho, {{"p", p, nv}, {"Zp", Zp, nv}, {"entry_state", entry_state, nv}, {"info", info, PRECOND_INFO}},
+                             {{"mu", mu, nc}, {"rho", rho, nc}});
+    if (bad.empty()) bad = precond_refusal(h, who, harvest);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, true);
+        reduced_workspaces(h, ep);
+        const size_t n = (size_t)h->n_vars, nt = PRECOND_TRACE * (size_t)max_iter, bytes = sizeof(double) * n;
+        precond_kernel_args(h, harvest != 0);   // before the uploads are enqueued
+        block_workspaces(h, ep, 1, h->reduced_input_store && h->K >= 1);
+        AlWork al{};
+        if (rho) al = auglag_workspaces(h, 1);
+        double* q = grow_workspace(h, h->d_precond_host, 6 * n + PRECOND_INFO + nt);
+        double *dmask = q, *dlo = q + n, *dhi = q + 2 * n, *dp = q + 3 * n, *dzp = q + 4 * n, *des = q + 5 * n, *dinfo = q + 6 * n;
+        double* dtrace = dinfo + PRECOND_INFO;
+        upload_Z(h, Z);
+        const bool has_mu = mu && h->n_cons > 0;
+        if (has_mu) HIP_CHECK(hipMemcpyAsync(h->red_hmu, mu, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        if (rho && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(al.hrho, rho, sizeof(double) * (size_t)h->n_cons, hipMemcpyHostToDevice, h->stream));
+        if (free_mask) HIP_CHECK(hipMemcpyAsync(dmask, free_mask, bytes, hipMemcpyHostToDevice, h->stream));
+        if (lo) HIP_CHECK(hipMemcpyAsync(dlo, lo, bytes, hipMemcpyHostToDevice, h->stream));
+        if (hi) HIP_CHECK(hipMemcpyAsync(dhi, hi, bytes, hipMemcpyHostToDevice, h->stream));
+        // the rows of the trace the step does not reach keep the caller's values
+        if (trace) HIP_CHECK(hipMemcpyAsync(dtrace, trace, sizeof(double) * nt, hipMemcpyHostToDevice, h->stream));
+        const NewtonBoxArgs a{free_mask ? dmask : nullptr, lo ? dlo : nullptr, hi ? dhi : nullptr, radius, shift, rtol, atol, max_iter, dp, dinfo,
+                              trace ? dtrace : nullptr, entry_state ? des : nullptr, Zp ? dzp : nullptr};
+        if (rho) {
+            auglag_rows_at(h, al, h->d_Z, has_mu ? h->red_hmu : nullptr, al.hrho, nullptr, h->stream);
+            precond_step(h, ep, h->d_Z, sigma, al.mu_eff, a, harvest, h->stream, &al);
+        } else {
+            precond_step(h, ep, h->d_Z, sigma, mu ? h->red_hmu : nullptr, a, harvest, h->stream);
+        }
+        HIP_CHECK(hipMemcpyAsync(p, dp, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipMemcpyAsync(info, dinfo, sizeof(double) * PRECOND_INFO, hipMemcpyDeviceToHost, h->stream));
+        if (trace) HIP_CHECK(hipMemcpyAsync(trace, dtrace, sizeof(double) * nt, hipMemcpyDeviceToHost, h->stream));
+        if (entry_state) HIP_CHECK(hipMemcpyAsync(entry_state, des, bytes, hipMemcpyDeviceToHost, h->stream));
+        if (Zp) HIP_CHECK(hipMemcpyAsync(Zp, dzp, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_preconditioned_newton_step_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* drho, const double* dfree_mask,
+                                       const double* dlo, const double* dhi, double radius, double shift, double rtol, double atol,
+                                       int32_t max_iter, int32_t harvest, double* dp, double* dinfo, double* dtrace, double* dentry_state,
+                                       double* dZp, void* stream) {
+    const std::string who = "dto_preconditioned_newton_step_dev";
+    if (!h) return fail(nullptr, "null handle");
+    std::string bad = newton_refusal(who, dZ, radius, shift, rtol, atol, max_iter, dp, dinfo);
+    if (bad.empty()) bad = newton_box_refusal(who, (size_t)h->n_vars, dZ, dfree_mask, dlo, dhi, dp, dZp, dentry_state);
+    const size_t nc = (size_t)h->n_cons, nv = (size_t)h->n_vars;
+    if (bad.empty() && drho)
+        bad = auglag_refusal(h, who, nullptr, {{"dp", dp, nv}, {"dZp", dZp, nv}, {"dentry_state", dentry_state, nv}, {"dinfo", dinfo, PRECOND_INFO}},
+                             {{"dmu", dmu, nc}, {"drho", drho, nc}});
+    if (bad.empty()) bad = precond_refusal(h, who, harvest);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, true);
+        reduced_workspaces(h, ep);
+        precond_kernel_args(h, harvest != 0);   // before the row pass is enqueued
+        block_workspaces(h, ep, 1, h->reduced_input_store && h->K >= 1);
+        hipStream_t st = (hipStream_t)stream;
+        const NewtonBoxArgs a{dfree_mask, dlo, dhi, radius, shift, rtol, atol, max_iter, dp, dinfo, dtrace, dentry_state, dZp};
+        if (drho) {
+            const AlWork A = auglag_workspaces(h, 1);
+            auglag_rows_at(h, A, dZ, nc > 0 ? dmu : nullptr, drho, nullptr, st);
+            precond_step(h, ep, dZ, sigma, A.mu_eff, a, harvest, st, &A);
+        } else {
+            precond_step(h, ep, dZ, sigma, dmu, a, harvest, st);
+        }
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
+// z_c = P H P r_c for n_cols vectors at the store as it stands: the entry states from the mask, the preparation once, then per column
+// the application's two launches -- the single application's bits
+static void precondition_columns(dto_handle* h, const double* dmask, int n_cols, const double* dR, double* dZout, hipStream_t st) {
+    KPrecond K = precond_kernel_args(h, false);
+    K.B.mask = dmask;
+    const size_t n = (size_t)h->n_vars;
+    { ProfScope ps(h, st, CAT_PRECOND, (dmask ? 9.0 : 1.0) * (double)n); launch_precond_states(st, h->red, K.B); }
+    precond_prepare_launches(h, K, st);
+    for (int c = 0; c < n_cols; ++c) precond_apply_launches(h, K, dR + (size_t)c * n, dZout + (size_t)c * n, 0, true, st);
+}
+static std::string precondition_refusal(const std::string& who, size_t n, int32_t n_cols, const double* mask, const double* r, const double* z) {
+    if (!r || !z) return who + ": r and z are required (NULL given)";
+    if (n_cols < 1) return who + ": n_cols = " + std::to_string(n_cols) + ", at least 1 vector is required";
+    if (spans_overlap(z, (size_t)n_cols * n, r, (size_t)n_cols * n)) return who + ": z overlaps r";
+    if (spans_overlap(z, (size_t)n_cols * n, mask, n)) return who + ": z overlaps free_mask";
+    return "";
+}
+int dto_newton_precondition(dto_handle* h, const double* free_mask, int32_t n_cols, const double* r, double* z) {
+    const std::string who = "dto_newton_precondition";
+    if (!h) return fail(nullptr, "null handle");
+    const std::string bad = precondition_refusal(who, (size_t)h->n_vars, n_cols, free_mask, r, z);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, false);
+        reduced_workspaces(h, ep);
+        const size_t n = (size_t)h->n_vars, nc = (size_t)n_cols * n;
+        precond_kernel_args(h, false);
+        double* q = grow_workspace(h, h->d_precond_host, n + 2 * nc);
+        double *dmask = q, *dr = q + n, *dz = dr + nc;
+        if (free_mask) HIP_CHECK(hipMemcpyAsync(dmask, free_mask, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(dr, r, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
+        precondition_columns(h, free_mask ? dmask : nullptr, n_cols, dr, dz, h->stream);
+        HIP_CHECK(hipMemcpyAsync(z, dz, sizeof(double) * nc, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }, G_BLOCKING);
+}
+int dto_newton_precondition_dev(dto_handle* h, const double* dfree_mask, int32_t n_cols, const double* dr, double* dz, void* stream) {
+    const std::string who = "dto_newton_precondition_dev";
+    if (!h) return fail(nullptr, "null handle");
+    const std::string bad = precondition_refusal(who, (size_t)h->n_vars, n_cols, dfree_mask, dr, dz);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, false);
+        reduced_workspaces(h, ep);
+        precondition_columns(h, dfree_mask, n_cols, dr, dz, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
+// the slot a pushed pair goes to, and the store's record behind the push (the oldest pair drops at capacity)
+static int pairs_push_slot(const dto_handle* h) {
+    return h->pairs_count < h->newton_pairs ? precond_slot(h->pairs_head, h->pairs_count, h->newton_pairs) : h->pairs_head;
+}
+static void pairs_pushed(dto_handle* h) {
+    if (h->pairs_count < h->newton_pairs) ++h->pairs_count;
+    else h->pairs_head = (h->pairs_head + 1) % h->newton_pairs;
+}
+static std::string pairs_push_refusal(const dto_handle* h, const std::string& who, const double* s, const double* y, bool host) {
+    if (!s || !y) return who + ": s and y are required (NULL given)";
+    if (h->newton_pairs == 0)
+        return who + ": the pair store has no capacity: set the option newton_pairs to 1 .. " + std::to_string(PRECOND_MAX_PAIRS) + " first (it is 0)";
+    if (host)
+        for (int64_t i = 0; i < h->n_vars; ++i) {
+            if (!std::isfinite(s[i])) return who + ": s[" + std::to_string(i) + "] is not finite";
+            if (!std::isfinite(y[i])) return who + ": y[" + std::to_string(i) + "] is not finite";
+        }
+    return "";
+}
+int dto_newton_pairs_push(dto_handle* h, const double* s, const double* y) {
+    const std::string who = "dto_newton_pairs_push";
+    if (!h) return fail(nullptr, "null handle");
+    const std::string bad = pairs_push_refusal(h, who, s, y, true);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const KPrecond K = precond_kernel_args(h, true);
+        const size_t n = (size_t)h->n_vars, slot = (size_t)pairs_push_slot(h);
+        HIP_CHECK(hipMemcpyAsync((double*)K.S + slot * n, s, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync((double*)K.Y + slot * n, y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        pairs_pushed(h);
+    }, G_BLOCKING);
+}
+int dto_newton_pairs_push_dev(dto_handle* h, const double* ds, const double* dy, void* stream) {
+    const std::string who = "dto_newton_pairs_push_dev";
+    if (!h) return fail(nullptr, "null handle");
+    const std::string bad = pairs_push_refusal(h, who, ds, dy, false);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const KPrecond K = precond_kernel_args(h, true);
+        const size_t n = (size_t)h->n_vars, slot = (size_t)pairs_push_slot(h);
+        hipStream_t st = (hipStream_t)stream;
+        { ProfScope ps(h, st, CAT_PRECOND, 16.0 * (double)n); launch_precond_copy(st, (int64_t)n, ds, (double*)K.S + slot * n); }
+        { ProfScope ps(h, st, CAT_PRECOND, 16.0 * (double)n); launch_precond_copy(st, (int64_t)n, dy, (double*)K.Y + slot * n); }
+        pairs_pushed(h);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+int dto_newton_pairs_clear(dto_handle* h) {
+    if (!h) return fail(nullptr, "null handle");
+    h->pairs_count = h->pairs_head = 0;
+    return 0;
+}
+int dto_newton_pairs_info(dto_handle* h, int32_t* count, int32_t* capacity) {
+    if (!h) return fail(nullptr, "null handle");
+    if (count) *count = h->pairs_count;
+    if (capacity) *capacity = h->newton_pairs;
+    return 0;
+}
+
 // ---- multi-GPU: ranges, gather plans, collectives (dto_comm.h)
 int dto_comm_unique_id(void* id128) {
     if (!id128) return fail(nullptr, "dto_comm_unique_id: null argument");
@@ -3937,6 +4227,14 @@ int dto_set_option(dto_handle* h, const char* name, int64_t value) {
         h->tdb_matrix_free_products = (int)value;
         return 0;
     }
+    if (std::string(name) == "newton_pairs") {
+        if (value < 0 || value > PRECOND_MAX_PAIRS)
+            return fail(h, "dto_set_option: newton_pairs takes 0 (no preconditioner) .. " + std::to_string(PRECOND_MAX_PAIRS) +
+                               ", the most pairs dto_preconditioned_newton_step keeps");
+        h->newton_pairs = (int)value;
+        h->pairs_bank = h->pairs_count = h->pairs_head = 0;   // setting the option clears the store
+        return 0;
+    }
     if (std::string(name) == "reduced_input_store") {
         if (value != 0 && value != 1)
             return fail(h, "dto_set_option: reduced_input_store takes 0 (J v^ and J' w of the reduced-space operators through dto_eval_jacobian_product / _transpose_product) or 1 (from the kept input blocks)");
@@ -4034,6 +4332,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "newton")) cat = CAT_NEWTON;
         else if (!strcmp(name, "newton_box")) cat = CAT_NEWTON_BOX;
         else if (!strcmp(name, "auglag")) cat = CAT_AUGLAG;
+        else if (!strcmp(name, "precond")) cat = CAT_PRECOND;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -4064,7 +4363,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (is_dynsolve_cat(r.cat) ? !(any_dynsolve || r.cat == cat) : any_dynsolve) continue;   // (nor are the solves)
             if (is_elim_cat(r.cat) && r.cat != cat) continue;
             if ((r.cat == CAT_REDUCED_PACK || r.cat == CAT_REDUCED_INPUT || r.cat == CAT_FEASIBLE || r.cat == CAT_NEWTON || r.cat == CAT_NEWTON_BOX ||
-                 r.cat == CAT_AUGLAG) && r.cat != cat) continue;
+                 r.cat == CAT_AUGLAG || r.cat == CAT_PRECOND) && r.cat != cat) continue;
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));

@@ -209,6 +209,7 @@ struct PinnedMailbox {
     int32_t red_flag;              // the reduced point's
     int32_t deferred_smax;         // the one-launch chain's squaring count of an enqueue-only call (smax_pending)
     double newton[2];              // the truncated-Newton step's (status, iterations) after every iteration
+    double precond[3];             // the preconditioned step's (status, iterations, pairs taken) after every iteration
 };
 
 struct Workspace { double* p = nullptr; size_t cap = 0; };   // grow-only device buffer, capacity in doubles (grow_workspace, dto_engine.cpp)
@@ -346,6 +347,13 @@ struct dto_handle {
     // y / w [n_vars], the partial results [12][chunks], the scalars [16] and the state bytes [n_vars]; d_newton_box_host: the
     // host-pointer form's mask, lo, hi, p, Zp and entry_state [n_vars] each, info [12] and trace [max_iter][6].  Grow-only like the above.
     dto::Workspace d_newton_box, d_newton_box_host;
+    // L-BFGS-preconditioned step (dto_preconditioned_newton_step[_dev], dto_newton_precondition[_dev], dto_newton_pairs_*;
+    // dto_precond_plan.h, dto_precond.hip).  newton_pairs: the option of that name, the store's capacity m (0: off).  d_pairs: the
+    // store, two banks of 2 m vectors [n_vars] (allocated whole by the first push or harvest; setting the option clears it);
+    // pairs_bank the current bank, in which pairs_count pairs lie as a ring from slot pairs_head.  d_precond: the routine's workspace
+    // (precond_workspace_doubles); d_precond_host: the host-pointer forms' vectors.
+    int newton_pairs = 0, pairs_bank = 0, pairs_count = 0, pairs_head = 0;
+    dto::Workspace d_pairs, d_precond, d_precond_host;
     // augmented-Lagrangian terms (dto_auglag_*; dto_auglag_plan.h, dto_auglag.hip).  d_al: mu_eff, weight, g, the rows of the
     // single-column route and the host-pointer forms' mu and rho [n_cons] each, then info [8]; d_al_t: the planes t [W][n_vars] of the
     // Gauss-Newton term; d_al_host: the host-pointer forms' lam [N n_states].  d_al_eq: the equality flag of every non-dynamics row,

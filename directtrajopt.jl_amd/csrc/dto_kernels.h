@@ -595,6 +595,34 @@ void launch_newton_box_step(hipStream_t st, const KNewtonBox& A, int j);
 // j = 0 behind the start, j >= 1 behind the step: the convergence test, the restart or the beta step, status, counts, `info` on exit
 void launch_newton_box_dir(hipStream_t st, const KNewtonBox& A, int j, int max_iter);
 
+// L-BFGS-preconditioned truncated-Newton step (dto_precond.hip; the pair store, the preparation, the application, the loop and the
+// layouts of `part`, `state` and `pc`: dto_precond_plan.h).  B as for the box step, with `part` [PRECOND_SLOTS][nb], `state`
+// [PRECOND_STATE], info [16] and trace [max_iter][8].  S / Y: the current bank's vectors, a ring of m slots of n doubles with pair k in
+// slot (head + k) % m; HS / HY: the other bank (null without harvest).
+struct KPrecond {
+    KNewtonBox B;
+    double* z;                 // [n]
+    double *uv, *gram, *pc;    // [2 cnt][nb], [precond_gram_count(cnt)][nb], [PRECOND_PC]
+    const double *S, *Y;
+    double *HS, *HY;
+    int m, head, cnt, harvest;
+};
+// the entry states of dto_newton_precondition: free where the entry is independent and the mask leaves it, fixed elsewhere
+void launch_precond_states(hipStream_t st, const KReduced& R, const KNewtonBox& A);
+// the partial sums of the Gram entries over the free entries; then one workgroup: their stage 2, admission, gamma, R and M into pc
+void launch_precond_gram(hipStream_t st, const KPrecond& A);
+void launch_precond_prep(hipStream_t st, const KPrecond& A);
+// the partial sums of s~_k . r_F and y~_k . r_F for every pair
+void launch_precond_dots(hipStream_t st, const KPrecond& A, const double* r);
+// stage 2 of those, the triangular solves, z and the partial sums of r . z; j: the iteration the application stands behind (0: the start)
+void launch_precond_comb(hipStream_t st, const KPrecond& A, const double* r, double* z, int j);
+// iteration j >= 1: the box step's launch with rz in the decision, the harvest copy and the multi-dot pass on the new r
+void launch_precond_step(hipStream_t st, const KPrecond& A, int j);
+// j = 0 behind the start's application, j >= 1 behind that of iteration j: the convergence test, the fallback, d, the counts, `info`
+void launch_precond_dir(hipStream_t st, const KPrecond& A, int j, int max_iter);
+// dst = src, n doubles
+void launch_precond_copy(hipStream_t st, int64_t n, const double* src, double* dst);
+
 // Augmented-Lagrangian terms (dto_auglag.hip; the row rules, the order of the sums and the eight scalars: dto_auglag_plan.h).
 struct KAlRows {
     int64_t n_dyn, n_cons;

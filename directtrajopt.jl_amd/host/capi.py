@@ -154,6 +154,18 @@ SYMBOLS = {
     "dto_auglag_newton_step_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                              C.c_double, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    "dto_newton_pairs_push": (C.c_int, [H, c_double_p, c_double_p]),
+    "dto_newton_pairs_push_dev": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dto_newton_pairs_clear": (C.c_int, [H]),
+    "dto_newton_pairs_info": (C.c_int, [H, c_int32_p, c_int32_p]),
+    "dto_newton_precondition": (C.c_int, [H, c_double_p, C.c_int32, c_double_p, c_double_p]),
+    "dto_newton_precondition_dev": (C.c_int, [H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dto_preconditioned_newton_step": (C.c_int, [H, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                 C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, c_double_p, c_double_p,
+                                                 c_double_p, c_double_p, c_double_p]),
+    "dto_preconditioned_newton_step_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dto_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dto_comm_create": (C.c_int, [H, C.c_void_p, C.c_int32, C.c_int32]),
     "dto_comm_set_ranges": (C.c_int, [H, C.c_int32, C.c_int32, c_int64_p, c_int64_p]),

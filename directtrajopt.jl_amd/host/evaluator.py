@@ -838,6 +838,73 @@ class Evaluator:
             out += (zp,)
         return out
 
+    # ---- L-BFGS preconditioner of the truncated-Newton step (include/dto_engine.h, "Preconditioned truncated-Newton step")
+    def newton_pairs_push(self, s, y):
+        """Append one pair (s, y), (n_variables,) each and finite, to the pair store (``dto_newton_pairs_push``); the oldest pair drops
+        at capacity.  The capacity is the option ``newton_pairs`` (``set_option("newton_pairs", m)``, 0 .. 16, default 0 = off)."""
+        s, y = _in(s, self.n_variables, "s"), _in(y, self.n_variables, "y")
+        self._check(self._lib.dto_newton_pairs_push(self._h, _dp(s), _dp(y)))
+
+    def newton_pairs_clear(self):
+        """Empty the pair store (``dto_newton_pairs_clear``); the capacity stays."""
+        self._check(self._lib.dto_newton_pairs_clear(self._h))
+
+    def newton_pairs_info(self):
+        """(count, capacity) of the pair store (``dto_newton_pairs_info``)."""
+        a, b = C.c_int32(), C.c_int32()
+        self._check(self._lib.dto_newton_pairs_info(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def newton_precondition(self, r, free=None):
+        """z = P H P r with the store's pairs (``dto_newton_precondition``): the compact L-BFGS inverse restricted to the independent
+        entries that ``free`` (None: all) leaves, zero elsewhere.  r (n_variables,) or (n_cols, n_variables); z has r's shape, and
+        every row has the bits of the call with that row alone.  With an empty store, or no admitted pair, z = r on those entries."""
+        r = np.asarray(r, dtype=np.float64)
+        single = r.ndim == 1
+        r = self._columns(r[None, :] if single else r, self.n_variables, "r")
+        if free is not None:
+            free = _in(free, self.n_variables, "free")
+        z = np.full(r.shape, np.nan)
+        self._check(self._lib.dto_newton_precondition(self._h, None if free is None else _dp(free), r.shape[0], _dp(r), _dp(z)))
+        return z[0] if single else z
+
+    def preconditioned_newton_step(self, Z, sigma=1.0, mu=None, rho=None, lo=None, hi=None, free=None, radius=0.0, shift=0.0, rtol=1e-6,
+                                   atol=0.0, max_iter=50, harvest=False, trace=False, states=False, trajectory=False):
+        """``auglag_newton_step`` (``rho=None``: ``reduced_newton_step_box``) preconditioned with the L-BFGS inverse of the pair store
+        (``dto_preconditioned_newton_step``).  ``harvest=True`` keeps the CG pairs (d, A d) of this call -- the last ``newton_pairs`` of
+        them -- as the store of the next call.  Arguments and results as there; info also has ``admitted``, ``harvested``,
+        ``fallbacks`` and ``rz0``, raw has 16 entries and the trace 8 columns (the box step's, rz, preconditioner on / off).  With an
+        empty store the step is the unpreconditioned one bit for bit."""
+        Z = self._Z(Z)
+        mu, rho = self._mu_rho(mu, rho)
+        if free is not None:
+            free = _in(free, self.n_variables, "free")
+        if lo is not None:
+            lo = _in(lo, self.n_variables, "lo")
+        if hi is not None:
+            hi = _in(hi, self.n_variables, "hi")
+        max_iter = int(max_iter)
+        opt = lambda a: None if a is None else _dp(a)
+        p = np.full(self.n_variables, np.nan)
+        raw = np.full(16, np.nan)
+        tr = np.full((max(max_iter, 0), 8), np.nan) if trace else None
+        es = np.full(self.n_variables, np.nan) if states else None
+        zp = np.full(self.n_variables, np.nan) if trajectory else None
+        self._check(self._lib.dto_preconditioned_newton_step(self._h, _dp(Z), float(sigma), opt(mu), opt(rho), opt(free), opt(lo), opt(hi),
+                                                             float(radius), float(shift), float(rtol), float(atol), max_iter, int(bool(harvest)),
+                                                             _dp(p), _dp(raw), opt(tr), opt(es), opt(zp)))
+        info = dict(status=int(raw[0]), iterations=int(raw[1]), gnorm=raw[2], rnorm=raw[3], pnorm=raw[4], pg=raw[5], predicted=raw[6],
+                    curvature=raw[7], held=int(raw[8]), hit=int(raw[9]), restarts=int(raw[10]), n_free=int(raw[11]), admitted=int(raw[12]),
+                    harvested=int(raw[13]), fallbacks=int(raw[14]), rz0=raw[15], raw=raw)
+        out = (p, info)
+        if trace:
+            out += (tr[:info["iterations"]],)
+        if states:
+            out += (es,)
+        if trajectory:
+            out += (zp,)
+        return out
+
     def independent_entries(self):
         """C: the entries of Z that are no state of a knot 2 .. N (controls, timesteps, times, the states of knot 1, globals),
         ascending, 0-based -- the variables of the reduced problem."""
@@ -1013,6 +1080,23 @@ class Evaluator:
                                                          int(max_iter), dp or None, dinfo or None, dtrace or None, dstates or None,
                                                          dZp or None, stream))
 
+    def newton_pairs_push_dev(self, ds, dy, stream=0):
+        """``newton_pairs_push`` on device pointers, copied on ``stream`` (no finiteness check)."""
+        self._check(self._lib.dto_newton_pairs_push_dev(self._h, ds or None, dy or None, stream))
+
+    def newton_precondition_dev(self, dfree, n_cols, dr, dz, stream=0):
+        """``newton_precondition`` on device pointers: dr and dz (n_cols, n_variables), dfree (n_variables) or 0."""
+        self._check(self._lib.dto_newton_precondition_dev(self._h, dfree or None, int(n_cols), dr or None, dz or None, stream))
+
+    def preconditioned_newton_step_dev(self, dZ, sigma, dmu, drho, dfree, dlo, dhi, radius, shift, rtol, atol, max_iter, harvest, dp, dinfo,
+                                       dtrace=0, dstates=0, dZp=0, stream=0):
+        """``preconditioned_newton_step`` on device pointers, arguments as ``auglag_newton_step_dev`` with harvest behind max_iter;
+        dinfo 16 doubles, dtrace (max_iter, 8)."""
+        self._check(self._lib.dto_preconditioned_newton_step_dev(self._h, dZ or None, float(sigma), dmu or None, drho or None, dfree or None,
+                                                                 dlo or None, dhi or None, float(radius), float(shift), float(rtol),
+                                                                 float(atol), int(max_iter), int(bool(harvest)), dp or None, dinfo or None,
+                                                                 dtrace or None, dstates or None, dZp or None, stream))
+
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod
     def comm_unique_id():
@@ -1080,8 +1164,9 @@ class Evaluator:
         ``_dev`` forms take J v^ and J' w from the input blocks kept with ``dynamics_solve_all``'s point -- two small launches instead
         of a J w and a J' w per product; another summation order, so values agree with the default route to rounding, not in bits),
         ``reduced_block_width`` (0 = the engine's choice, or 1 .. 64: the most columns per chunk of ``eval_hessian_lagrangian_products``
-        / ``reduced_hessian_products`` and their ``_dev`` forms; for tests and measurements, the results do not depend on it);
-        include/dto_engine.h lists every option."""
+        / ``reduced_hessian_products`` and their ``_dev`` forms; for tests and measurements, the results do not depend on it),
+        ``newton_pairs`` (0 .. 16, default 0 = off: the capacity of the pair store of ``preconditioned_newton_step``; setting it
+        clears the store); include/dto_engine.h lists every option."""
         self._check(self._lib.dto_set_option(self._h, name.encode(), int(value)))
 
     # ---- measurement

@@ -778,6 +778,62 @@ int dto_auglag_newton_step_dev(dto_handle* h, const double* dZ, double sigma, co
                                const double* dlo, const double* dhi, double radius, double shift, double rtol, double atol, int32_t max_iter,
                                double* dp, double* dinfo, double* dtrace, double* dentry_state, double* dZp, void* stream);
 
+/* ---- Preconditioned truncated-Newton step: dto_auglag_newton_step (without rho: dto_projected_newton_step_box) with an L-BFGS
+ * preconditioner built from pairs (s, y) -- automatic preconditioning after Morales and Nocedal: the pairs (d_j, A d_j) that CG forms
+ * anyway define a limited-memory BFGS inverse, and the next solve is preconditioned with it.  The rules, once, in plain C++:
+ * csrc/dto_precond_plan.h (the kernels of csrc/dto_precond.hip, the host routine and a g++-built test compile that text); every
+ * operation is rounded on its own and every dot takes the truncated-Newton step's order, so a NumPy restatement has the same bits.
+ * Pair store.  dto_set_option("newton_pairs", m), m = 0 .. 16, sets the capacity; 0, the default, means off; setting it clears the
+ *   store.  Pairs are raw vectors in the Z layout, the newest last, in two banks of 2 m vectors each (2 * 2 m * n_vars doubles of
+ *   device memory, allocated by the first push or harvest).  dto_newton_pairs_push appends one pair and drops the oldest at capacity;
+ *   dto_newton_pairs_clear empties the store; dto_newton_pairs_info returns the count and the capacity (either may be NULL).
+ * Preparation, once per call, with F0 the entries that are free behind the start: the Gram entries SY_ij = sum over F0 of s_i y_j and
+ *   YY_ij (i <= j) and SS_ii; a pair is admitted, walking from the oldest, iff SY_ii, SS_ii, YY_ii are finite and
+ *   SY_ii > 2^-26 sqrt(SS_ii YY_ii); gamma = SY_kk / YY_kk of the newest admitted pair k (none admitted: the identity).
+ * Application z = P_F H P_F r, F the entries free now, the compact form of Byrd, Nocedal and Schnabel in one pass of independent dots:
+ *   u = S~' r_F, v = Y~' r_F;  a = R^-1 u;  c1 = R^-T ((D + gamma YY) a - gamma v), c2 = -a;
+ *   z_i = gamma r_i + sum_k c1_k s_k,i + gamma sum_k c2_k y_k,i on F and 0 elsewhere, R the upper triangle and D the diagonal of SY over the
+ *   admitted pairs.  A principal submatrix of a positive definite matrix: no Gram matrix is rebuilt when an entry hits a bound.
+ * dto_newton_precondition: z_c = P H P r_c for n_cols vectors [n_cols][n_vars] at the store as it stands, F0 = F = the independent
+ *   entries that free_mask (NULL: all) leaves.  Column c has the bits of the call with that column alone.
+ * dto_preconditioned_newton_step: the arguments of dto_auglag_newton_step, then `harvest` in front of the outputs.  rho == NULL: the
+ *   operator of dto_projected_newton_step_box; lo == hi == NULL: no bounds.  The loop is the box step's with these changes and no
+ *   others: z is formed from r behind the start and behind every update; rz = r . z over F takes rr's place in alpha = rz / kappa and
+ *   beta = rz' / rz; d = beta d - z, the start is d = -z and a restart d = -z on F.  The convergence test, the reach, tau, tau_box, the
+ *   clamps, the predicted decrease and info[0 .. 11] keep their Euclidean definitions, and the trust region stays the Euclidean ball:
+ *   ||p|| is no longer monotone under preconditioning, but a boundary step still decreases the model, since q is convex and decreasing
+ *   on [0, alpha] along d.  Fallback: where the loop goes on with rz' not finite or <= 0, the preconditioner is switched off for the
+ *   rest of the call, rz' = rr', d = -r on F, and one fallback is counted.
+ *   info [16]: the box step's 12, then the pairs admitted, the pairs taken by the harvest, the fallbacks, sqrt(rz0).
+ *   trace [max_iter][8]: the box step's six columns, rz' as formed, and 1 / 0: the preconditioner is on / off behind the iteration.
+ *   harvest != 0: iteration j offers (d, w) as the loop holds them, w = y + shift d on F0; the pair is taken iff kappa is finite
+ *   and > 0.  The other bank keeps the last min(m, taken) pairs, and when the call ends, whatever its exit, the banks swap if a pair was
+ *   taken.  The call never reads a pair it wrote.
+ *   Identity: with an empty store, or with no pair admitted, z = r and rz = rr bit for bit, and p, info[0 .. 11], the trace's six
+ *   columns, entry_state and Zp are dto_projected_newton_step_box's (with rho: dto_auglag_newton_step's) bit for bit.
+ * Costs.  Per call the box start, one Gram launch, one one-workgroup launch (stage 2, admission, R, M), and the first application (multi-dot
+ *   launch, combination launch).  Per iteration the product and four launches: the box step's curvature pass; the step, which also
+ *   copies a harvested pair and runs the multi-dot pass on the r it has just updated; the combination (every workgroup finishes the 2 m
+ *   dots and runs the two triangular solves itself, then writes z); the direction.  An application reads each stored vector twice.
+ *   Profile name "precond" (every launch of these calls that is no product).
+ * Refused with text, the handle stays usable and nothing is written: what dto_auglag_newton_step refuses (the penalty rules with rho
+ *   only); a push, or harvest != 0, while the capacity is 0; newton_pairs outside 0 .. 16; in dto_newton_pairs_push a non-finite
+ *   entry, naming it; n_cols < 1; outputs that overlap inputs.  The _dev forms take device pointers and work on `stream`, errors
+ *   deferred as for every _dev call; the store is read and written in stream order, so pushes and steps belong on one stream. */
+int dto_newton_pairs_push(dto_handle* h, const double* s, const double* y);
+int dto_newton_pairs_push_dev(dto_handle* h, const double* ds, const double* dy, void* stream);
+int dto_newton_pairs_clear(dto_handle* h);
+int dto_newton_pairs_info(dto_handle* h, int32_t* count, int32_t* capacity);
+int dto_newton_precondition(dto_handle* h, const double* free_mask, int32_t n_cols, const double* r, double* z);
+int dto_newton_precondition_dev(dto_handle* h, const double* dfree_mask, int32_t n_cols, const double* dr, double* dz, void* stream);
+int dto_preconditioned_newton_step(dto_handle* h, const double* Z, double sigma, const double* mu, const double* rho, const double* free_mask,
+                                   const double* lo, const double* hi, double radius, double shift, double rtol, double atol, int32_t max_iter,
+                                   int32_t harvest, double* p, double* info, double* trace, double* entry_state, double* Zp);
+int dto_preconditioned_newton_step_dev(dto_handle* h, const double* dZ, double sigma, const double* dmu, const double* drho, const double* dfree_mask,
+                                       const double* dlo, const double* dhi, double radius, double shift, double rtol, double atol,
+                                       int32_t max_iter, int32_t harvest, double* dp, double* dinfo, double* dtrace, double* dentry_state,
+                                       double* dZp, void* stream);
+
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
  * communicator (SURVEY.md §8b "Ownership").  No callback needs a collective: every rank's Jacobian / Hessian / gradient
@@ -898,6 +954,8 @@ int dto_bind_output_dev(dto_handle* h, int32_t vector, double* dptr);
  *   "reduced_block_width" (default 0 = the engine's choice, 64): 1 .. 64 caps the columns per chunk of dto_eval_hessian_products /
  *   dto_projected_hessian_products and their _dev forms ("Block products" above); other values are refused.  For tests, which then
  *   exercise the chunk loop on small blocks, and for measurements.  The results do not depend on it, bit for bit.
+ *   "newton_pairs" (default 0 = no preconditioner): 0 .. 16, the capacity of the pair store of dto_preconditioned_newton_step
+ *   ("Preconditioned truncated-Newton step" above); other values are refused.  Setting it clears the store.
  *   "debug_bad_launch": TUNING builds only (libdto_engine_t.so) -- 1 gives the next callbacks' kernels an invalid launch
  *   configuration, which must come back as a non-zero return code with text (test of the error convention); the product
  *   library refuses the name. */
@@ -957,6 +1015,9 @@ int dto_profile_reset(dto_handle* h);
  * under "newton").
  * "auglag" (the dto_auglag_* calls: the row pass, the Gauss-Newton term's launches, the scaling and the addition; third output: BYTES as
  * executed; it feeds no other name, "all" included; with rho == NULL no launch counts here).
+ * "precond" (dto_preconditioned_newton_step, dto_newton_precondition, dto_newton_pairs_push_dev: every launch of theirs that is no
+ * product -- the Gram pass, the preparation, the multi-dot and combination passes, the step and the direction, and the box step's start
+ * and curvature pass where they run inside; third output: BYTES as executed; it feeds no other name, "all" included).
  * The block products count under "hess_product", "reduced_pack" and "reduced_input" too, one launch per chunk where a single product
  * has one, with bytes as executed: matrix bytes once per tile or chunk, vector bytes per column.
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the

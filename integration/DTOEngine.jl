@@ -1184,6 +1184,95 @@ function auglag_newton_step_dev!(ev::GPUEvaluator, dp::Ptr{Float64}, dinfo::Ptr{
                                                     stream::Ptr{Cvoid})::Cint)
 end
 
+# ---- L-BFGS preconditioner of the truncated-Newton step (include/dto_engine.h, "Preconditioned truncated-Newton step") ---------
+# set_option!(ev, "newton_pairs", m), m = 0 .. 16 (0, the default: off), sets the capacity of the pair store and clears it.
+function newton_pairs_push!(ev::GPUEvaluator, s::AbstractVector{Float64}, y::AbstractVector{Float64})
+    (length(s) == ev.n_variables && length(y) == ev.n_variables) ||
+        error("newton_pairs_push!: s and y have $(length(s)) and $(length(y)) entries, n_variables = $(ev.n_variables)")
+    sv, yv = Vector{Float64}(s), Vector{Float64}(y)
+    check(ev, @ccall lib.dto_newton_pairs_push(ev.handle::Ptr{Cvoid}, sv::Ptr{Float64}, yv::Ptr{Float64})::Cint)
+end
+
+function newton_pairs_push_dev!(ev::GPUEvaluator, ds::Ptr{Float64}, dy::Ptr{Float64}, stream::Ptr{Cvoid})
+    check(ev, @ccall lib.dto_newton_pairs_push_dev(ev.handle::Ptr{Cvoid}, ds::Ptr{Float64}, dy::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
+newton_pairs_clear!(ev::GPUEvaluator) = check(ev, @ccall lib.dto_newton_pairs_clear(ev.handle::Ptr{Cvoid})::Cint)
+
+# (count, capacity)
+function newton_pairs_info(ev::GPUEvaluator)
+    count, cap = Ref{Int32}(0), Ref{Int32}(0)
+    check(ev, @ccall lib.dto_newton_pairs_info(ev.handle::Ptr{Cvoid}, count::Ptr{Int32}, cap::Ptr{Int32})::Cint)
+    return Int(count[]), Int(cap[])
+end
+
+# z = P H P r for the columns of R (n_variables x n_cols) with the store's pairs; free: the optional mask
+function newton_precondition(ev::GPUEvaluator, R::AbstractMatrix{Float64}; free::Union{Nothing,AbstractVector{Float64}} = nothing)
+    size(R, 1) == ev.n_variables || error("newton_precondition: R has $(size(R, 1)) rows, n_variables = $(ev.n_variables)")
+    (free === nothing || length(free) == ev.n_variables) || error("newton_precondition: free has $(length(free)) entries, n_variables = $(ev.n_variables)")
+    Rm = Matrix{Float64}(R)
+    fv = free === nothing ? Float64[] : Vector{Float64}(free)
+    Zm = fill(NaN, size(Rm))
+    nc = Int32(size(Rm, 2))
+    GC.@preserve Rm fv Zm begin
+        fp = auglag_ptr(free, fv)
+        check(ev, @ccall lib.dto_newton_precondition(ev.handle::Ptr{Cvoid}, fp::Ptr{Float64}, nc::Int32, Rm::Ptr{Float64}, Zm::Ptr{Float64})::Cint)
+    end
+    return Zm
+end
+newton_precondition(ev::GPUEvaluator, r::AbstractVector{Float64}; free = nothing) =
+    vec(newton_precondition(ev, reshape(Vector{Float64}(r), :, 1); free = free))
+
+function newton_precondition_dev!(ev::GPUEvaluator, dz::Ptr{Float64}, dr::Ptr{Float64}, n_cols::Integer, dfree::Ptr{Float64}, stream::Ptr{Cvoid})
+    nc = Int32(n_cols)
+    check(ev, @ccall lib.dto_newton_precondition_dev(ev.handle::Ptr{Cvoid}, dfree::Ptr{Float64}, nc::Int32, dr::Ptr{Float64}, dz::Ptr{Float64},
+                                                     stream::Ptr{Cvoid})::Cint)
+end
+
+# auglag_newton_step (ρ = nothing: newton_step_box) preconditioned with the store's pairs: (p, info [16], trace [8 x iterations], states,
+# Zp); harvest = true keeps this call's CG pairs as the next call's store
+function preconditioned_newton_step(ev::GPUEvaluator, Z::AbstractVector{Float64}; σ::Float64 = 1.0,
+                                    μ::Union{Nothing,AbstractVector{Float64}} = nothing, ρ::Union{Nothing,AbstractVector{Float64}} = nothing,
+                                    lo::Union{Nothing,AbstractVector{Float64}} = nothing, hi::Union{Nothing,AbstractVector{Float64}} = nothing,
+                                    free::Union{Nothing,AbstractVector{Float64}} = nothing, radius::Float64 = 0.0, shift::Float64 = 0.0,
+                                    rtol::Float64 = 1e-6, atol::Float64 = 0.0, max_iter::Integer = 50, harvest::Bool = false)
+    reduced_check_lengths(ev, "preconditioned_newton_step", Z, μ, free)
+    auglag_check_lengths(ev, "preconditioned_newton_step", Z, μ, ρ)
+    (lo === nothing || length(lo) == ev.n_variables) || error("preconditioned_newton_step: lo has $(length(lo)) entries, n_variables = $(ev.n_variables)")
+    (hi === nothing || length(hi) == ev.n_variables) || error("preconditioned_newton_step: hi has $(length(hi)) entries, n_variables = $(ev.n_variables)")
+    max_iter >= 1 || error("preconditioned_newton_step: max_iter = $max_iter, at least 1 iteration is required")
+    Zv = Vector{Float64}(Z)
+    μv = μ === nothing ? Float64[] : Vector{Float64}(μ)
+    ρv = ρ === nothing ? Float64[] : Vector{Float64}(ρ)
+    fv = free === nothing ? Float64[] : Vector{Float64}(free)
+    lov = lo === nothing ? Float64[] : Vector{Float64}(lo)
+    hiv = hi === nothing ? Float64[] : Vector{Float64}(hi)
+    p, info, trace = fill(NaN, ev.n_variables), fill(NaN, 16), fill(NaN, 8, Int(max_iter))
+    states, Zp = fill(NaN, ev.n_variables), fill(NaN, ev.n_variables)
+    mi, hv = Int32(max_iter), Int32(harvest)
+    GC.@preserve Zv μv ρv fv lov hiv p info trace states Zp begin
+        μp, ρp, fp, lop, hip = auglag_ptr(μ, μv), auglag_ptr(ρ, ρv), auglag_ptr(free, fv), auglag_ptr(lo, lov), auglag_ptr(hi, hiv)
+        check(ev, @ccall lib.dto_preconditioned_newton_step(ev.handle::Ptr{Cvoid}, Zv::Ptr{Float64}, σ::Float64, μp::Ptr{Float64}, ρp::Ptr{Float64},
+                                                            fp::Ptr{Float64}, lop::Ptr{Float64}, hip::Ptr{Float64}, radius::Float64,
+                                                            shift::Float64, rtol::Float64, atol::Float64, mi::Int32, hv::Int32,
+                                                            p::Ptr{Float64}, info::Ptr{Float64}, trace::Ptr{Float64}, states::Ptr{Float64},
+                                                            Zp::Ptr{Float64})::Cint)
+    end
+    return p, info, trace[:, 1:Int(info[2])], states, Zp
+end
+
+function preconditioned_newton_step_dev!(ev::GPUEvaluator, dp::Ptr{Float64}, dinfo::Ptr{Float64}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64},
+                                         dρ::Ptr{Float64}, dfree::Ptr{Float64}, dlo::Ptr{Float64}, dhi::Ptr{Float64}, radius::Float64,
+                                         shift::Float64, rtol::Float64, atol::Float64, max_iter::Integer, harvest::Bool, dtrace::Ptr{Float64},
+                                         dstates::Ptr{Float64}, dZp::Ptr{Float64}, stream::Ptr{Cvoid})
+    mi, hv = Int32(max_iter), Int32(harvest)
+    check(ev, @ccall lib.dto_preconditioned_newton_step_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dρ::Ptr{Float64},
+                                                            dfree::Ptr{Float64}, dlo::Ptr{Float64}, dhi::Ptr{Float64}, radius::Float64,
+                                                            shift::Float64, rtol::Float64, atol::Float64, mi::Int32, hv::Int32,
+                                                            dp::Ptr{Float64}, dinfo::Ptr{Float64}, dtrace::Ptr{Float64}, dstates::Ptr{Float64},
+                                                            dZp::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+end
+
 # row bounds handed to the solver (src/solvers/solve.jl:30-65)
 function constraint_bounds(ev::GPUEvaluator)
     lo = Vector{Float64}(undef, ev.n_constraints)

@@ -41,11 +41,21 @@ iterations (rtol = 0, shift from the power iterations with the augmented operato
 of one call (device milliseconds, launches, bytes, and all three per iteration), the yardstick's "newton_box" profile, the active rows, and
     excess_ms = (auglag step - yardstick) - auglag device ms - (yardstick max - yardstick min)
 
+``--precond`` measures the L-BFGS-preconditioned step (Evaluator.preconditioned_newton_step_dev, option "newton_pairs" = 8) without
+bounds.  The YARDSTICK is the box step (reduced_newton_step_box_dev); rtol = 0, so every call runs exactly ``max_iter`` iterations.
+Beside it, calls alternating,
+    empty:      the new step with an empty store (the box step's iterations bit for bit: what the new loop's own launches cost)
+    pairs_8:    the new step with the 8 pairs a harvesting call left at the same point (the application's cost on top)
+each with the "precond" profile name of one call and the yardstick's "newton_box" profile.  Then ``to_rtol``: at rtol = 1e-6, for the
+tool's shift and for 0.55 of it, the iterations, the status and the median wall time of the box step, of the new step with an empty
+store, and of the new step with the 8 pairs harvested by a previous call at the same point and shift.
+
 One JSON line per shape.
 
     python tools/newton_time.py                       # 256 x 2000 and 64 x 1000
     python tools/newton_time.py --box                 # the bound-constrained step beside the existing one
     python tools/newton_time.py --auglag              # the augmented-Lagrangian step beside the bound-constrained one
+    python tools/newton_time.py --precond             # the preconditioned step beside the bound-constrained one
     python tools/newton_time.py --shapes 128x1000 --reps 9 --iters 10,30
 """
 import argparse
@@ -216,6 +226,102 @@ def measure_auglag(n, N, drives, scale, reps, iters, rho_value=10.0):
         ev.close()
 
 
+def measure_precond(n, N, drives, scale, reps, iters, m=8):
+    """the preconditioned step beside the box step (the yardstick), no bounds: an empty store, then 8 harvested pairs"""
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    prob = dto_amd.host.synthetic.multi_ket_problem(n, 1, drives, N, seed=42, u_bound=4.0, scale=scale or None)
+    ev = dto_amd.Evaluator(prob)
+    ev.set_option("reduced_input_store", 1)
+    ev.set_option("newton_pairs", m)
+    out = {"mode": "precond", "n": n, "knots": N, "drives": drives, "scale": scale, "reps": reps, "sigma": SIGMA, "newton_pairs": m,
+           "route": "reduced_input_store"}
+    try:
+        Zh = np.ascontiguousarray(prob.trajectory.vec(), dtype=np.float64)
+        Z = torch.from_numpy(Zh).to(dev)
+        gen = torch.Generator(device=dev); gen.manual_seed(7)
+        mu = torch.randn(ev.n_constraints, dtype=torch.float64, device=dev, generator=gen)
+        f64 = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
+        nv = ev.n_variables
+        y, p, info, pp, info_p = f64(nv), f64(nv), f64(12), f64(nv), f64(16)
+        mask = torch.zeros(nv, dtype=torch.float64, device=dev)
+        mask[torch.from_numpy(ev.independent_entries()).to(dev)] = 1.0
+        out["n_variables"], out["chunks"] = nv, -(-nv // 256)
+        v = torch.randn(nv, dtype=torch.float64, device=dev, generator=gen) * mask
+        top = 0.0
+        for _ in range(8):
+            v = v / torch.linalg.norm(v)
+            ev.reduced_hessian_product_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), v.data_ptr(), y.data_ptr(), st)
+            top = max(top, abs(float(torch.dot(v, y))))
+            v = y.clone()
+        shift = 2.0 * top
+        out["shift"] = shift
+
+        def profile(name, fn, max_iter):
+            ev.profile_enable(True); ev.profile_reset(); fn(); torch.cuda.synchronize()
+            ms, launches, nbytes = ev.profile_get(name)
+            ev.profile_enable(False)
+            return {"ms": round(ms, 4), "launches": launches, "bytes": nbytes, "ms_per_iteration": round(ms / max_iter, 5),
+                    "launches_per_iteration": launches / max_iter, "bytes_per_iteration": nbytes / max_iter}
+
+        def box(sh, rtol, max_iter):
+            return lambda: ev.reduced_newton_step_box_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), 0, 0, 0, 0.0, sh, rtol, 0.0, max_iter, p.data_ptr(),
+                                                          info.data_ptr(), 0, 0, 0, st)
+
+        def pre(sh, rtol, max_iter, harvest=False):
+            return lambda: ev.preconditioned_newton_step_dev(Z.data_ptr(), SIGMA, mu.data_ptr(), 0, 0, 0, 0, 0.0, sh, rtol, 0.0, max_iter, harvest,
+                                                             pp.data_ptr(), info_p.data_ptr(), 0, 0, 0, st)
+
+        def harvest(sh):
+            ev.newton_pairs_clear()
+            pre(sh, 0.0, m, harvest=True)()
+            torch.cuda.synchronize()
+            return ev.newton_pairs_info()[0]
+
+        for max_iter in iters:
+            res = {}
+            for key in ("empty", "pairs_8"):
+                ev.newton_pairs_clear()
+                if key == "pairs_8":
+                    res["pairs_in_store"] = harvest(shift)
+                fn = pre(shift, 0.0, max_iter)
+                pair = alternating(box(shift, 0.0, max_iter), fn, reps)
+                fn(); torch.cuda.synchronize()
+                raw = info_p.cpu().numpy()
+                pair.update(status=int(raw[0]), iterations=int(raw[1]), admitted=int(raw[12]), fallbacks=int(raw[14]),
+                            rnorm_over_gnorm=float(raw[3] / raw[2]))
+                pair["difference_ms_per_iteration"] = round(pair["difference_ms"] / max_iter, 5)
+                if key == "empty":
+                    box(shift, 0.0, max_iter)(); torch.cuda.synchronize()
+                    pair["same_bits_as_yardstick"] = bool(torch.equal(pp, p))
+                pair["precond_profile"] = profile("precond", fn, max_iter)
+                pair["yardstick_newton_box_profile"] = profile("newton_box", box(shift, 0.0, max_iter), max_iter)
+                res[key] = pair
+            out[f"max_iter_{max_iter}"] = res
+        to_rtol = {}
+        for factor in (1.0, 0.55):
+            sh, cap = factor * shift, 200
+
+            def timed(fn, raw_of):
+                for _ in range(2):
+                    event_ms(fn)
+                ms = statistics.median(event_ms(fn) for _ in range(reps))
+                raw = raw_of.cpu().numpy()
+                return {"ms": round(ms, 4), "status": int(raw[0]), "iterations": int(raw[1]), "rnorm_over_gnorm": float(raw[3] / raw[2])}
+
+            row = {"shift": sh, "box": timed(box(sh, 1e-6, cap), info)}
+            ev.newton_pairs_clear()
+            row["empty"] = timed(pre(sh, 1e-6, cap), info_p)
+            row["pairs_in_store"] = harvest(sh)
+            row["pairs_8"] = timed(pre(sh, 1e-6, cap), info_p)
+            row["pairs_8"]["admitted"] = int(info_p.cpu().numpy()[12])
+            to_rtol[f"shift_x{factor}"] = row
+        out["to_rtol_1e-6"] = to_rtol
+        return out
+    finally:
+        ev.close()
+
+
 def measure(n, N, drives, scale, reps, iters):
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -307,8 +413,9 @@ def main():
                     "headline benchmark; 0: 1 / sqrt(n), norms of order one)")
     ap.add_argument("--box", action="store_true", help="measure the bound-constrained step beside the existing step")
     ap.add_argument("--auglag", action="store_true", help="measure the augmented-Lagrangian step beside the bound-constrained step")
+    ap.add_argument("--precond", action="store_true", help="measure the L-BFGS-preconditioned step beside the bound-constrained step")
     a = ap.parse_args()
-    run = measure_auglag if a.auglag else measure_box if a.box else measure
+    run = measure_precond if a.precond else measure_auglag if a.auglag else measure_box if a.box else measure
     for s in a.shapes.split(","):
         n, N = (int(x) for x in s.lower().split("x"))
         print(json.dumps(run(n, N, a.drives, a.scale, a.reps, [int(i) for i in a.iters.split(",")])), flush=True)
