@@ -7,7 +7,7 @@ CSRC  := directtrajopt.jl_amd/csrc
 LIB   := directtrajopt.jl_amd/libdto_engine$(if $(TUNING),_t,).so
 O     := $(if $(TUNING),t.o,o)
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $(if $(TUNING),-DDTO_TUNING,)
-OBJS  := $(addprefix $(CSRC)/,dto_kernels.$(O) dto_small.$(O) dto_sweep_fused.$(O) dto_sweep_gs.$(O) dto_chain64.$(O) dto_tdb.$(O) dto_tdb_mfma.$(O) dto_tdb_kron.$(O) dto_kron.$(O) dto_quadform.$(O) dto_share.$(O) dto_rollout.$(O) dto_dynsolve.$(O) dto_elim.$(O) dto_reduced.$(O) dto_feasible.$(O) dto_newton.$(O) dto_newton_box.$(O) dto_precond.$(O) dto_auglag.$(O) dto_hess_product.$(O) dto_hostxfer.$(O) dto_comm.$(O) dto_create.$(O) dto_engine.$(O))
+OBJS  := $(addprefix $(CSRC)/,dto_kernels.$(O) dto_small.$(O) dto_sweep_fused.$(O) dto_sweep_gs.$(O) dto_chain64.$(O) dto_tdb.$(O) dto_tdb_mfma.$(O) dto_tdb_kron.$(O) dto_kron.$(O) dto_quadform.$(O) dto_share.$(O) dto_rollout.$(O) dto_dynsolve.$(O) dto_elim.$(O) dto_reduced.$(O) dto_feasible.$(O) dto_newton.$(O) dto_newton_box.$(O) dto_precond.$(O) dto_minimize.$(O) dto_auglag.$(O) dto_hess_product.$(O) dto_hostxfer.$(O) dto_comm.$(O) dto_create.$(O) dto_engine.$(O))
 
 all: $(LIB)
 

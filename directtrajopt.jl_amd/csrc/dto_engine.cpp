@@ -6,6 +6,7 @@
 #include "dto_handle.h"
 #include "dto_auglag_plan.h"
 #include "dto_newton_box_plan.h"
+#include "dto_minimize_plan.h"
 #include "dto_precond_plan.h"
 #include "dto_newton_plan.h"
 #include "dto_rollout_plan.h"
@@ -77,7 +78,7 @@ struct ProfScope {
 // sweep -- sixteen terms of 2 b^2 per column and (on average two) sources over the mode's (m + 2) column groups -- so it is part of
 // the third output of "all"
 enum { CAT_BGEMM = 0, CAT_SWEEP = 1, CAT_OTHER = 2, CAT_BGEMM_HORNER = 3, CAT_BGEMM_SQUARE = 4, CAT_SWEEP_ADJOINT = 5,
-       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25, CAT_FEASIBLE = 26, CAT_NEWTON = 27, CAT_NEWTON_BOX = 28, CAT_AUGLAG = 29, CAT_PRECOND = 30 };
+       CAT_ZERO = 6, CAT_BUILD_A = 7, CAT_ASSEMBLY = 8, CAT_BASIS_MULTI = 9, CAT_CHAIN64 = 10, CAT_HESS_PRODUCT = 11, CAT_SHARE = 12, CAT_TDB_MFMA = 13, CAT_JAC_PRODUCT = 14, CAT_TDB_KRON = 15, CAT_TDB_PRODUCT = 16, CAT_ROLLOUT = 17, CAT_ROLLOUT_TREE = 18, CAT_ROLLOUT_DESCENT = 19, CAT_DYNSOLVE_TREE = 20, CAT_DYNSOLVE_SCAN = 21, CAT_DYNSOLVE_COUPLE = 22, CAT_DYNSOLVE_DERIV = 23, CAT_REDUCED_PACK = 24, CAT_REDUCED_INPUT = 25, CAT_FEASIBLE = 26, CAT_NEWTON = 27, CAT_NEWTON_BOX = 28, CAT_AUGLAG = 29, CAT_PRECOND = 30, CAT_MINIMIZE = 31 };
 // CAT_ROLLOUT .. CAT_ROLLOUT_DESCENT ("rollout" = its parts "rollout_gather" + "rollout_tree" + "rollout_descent"): the gather, the
 // tree's products and the descent (with the start and the copy into the caller's layout) of dto_rollout[_dev], flops as executed with
 // padding; the tree's products run launch_bgemm_plain and count HERE, not under "bgemm_plain"; they feed no other name, "all" included
@@ -107,6 +108,8 @@ inline bool is_elim_cat(int cat) { return cat == CAT_DYNSOLVE_COUPLE || cat == C
 // CAT_PRECOND ("precond"): every launch of dto_preconditioned_newton_step, dto_newton_precondition and dto_newton_pairs_push_dev that is
 // no product -- the kernels of dto_precond.hip and the box step's start and curvature pass where the preconditioned step runs them;
 // BYTES as executed; it feeds no other name, "all" included.
+// CAT_MINIMIZE ("minimize"): the two kernels of dto_minimize.hip, one launch per trial and one per outer iteration of
+// dto_projected_minimize and its _dev form; BYTES, a trial's as if it is accepted; it feeds no other name, "all" included.
 // The block products (dto_eval_hessian_products, dto_projected_hessian_products) count under the same names -- "hess_product",
 // "reduced_pack", "reduced_input" -- one launch per chunk each, bytes as executed: the matrices once per tile or chunk, the vectors per column.
 // the form a generator sweep took (SWEEP_GS .. SWEEP_STEP, dto_sweep_plan.h): one count per run_sweep call, not per launch
@@ -4052,6 +4055,244 @@ int dto_newton_pairs_info(dto_handle* h, int32_t* count, int32_t* capacity) {
     return 0;
 }
 
+// ---- reduced-space minimize (include/dto_engine.h, "Reduced-space minimize"; dto_minimize.hip, dto_minimize_plan.h): minimize_solve's
+// loop with the step, the merit and the row pass above as its three callables, all unchanged, and one small launch behind every trial
+// and every outer iteration.
+
+// what the device routine takes: device pointers, Z / mu / rho in and out
+struct MinimizeArgs {
+    double *Z, *mu, *rho;
+    const double *mask, *lo, *hi;
+    MinimizeOptions opt;
+    int outer, trials, harvest;
+    double *info, *history, *outer_history, *entry_state;
+};
+
+// d_minimize's parts
+struct MinWork { double *p, *Zp, *Zt, *sinfo, *bank, *rinfo0, *rinfo, *phi_t, *mail; };
+
+static MinWork minimize_workspaces(dto_handle* h) {
+    const size_t n = (size_t)h->n_vars;
+    double* q = grow_workspace(h, h->d_minimize, 3 * n + MINIMIZE_STEP_INFO + 2 * MINIMIZE_STATE + 2 * AL_INFO + 4 + MINIMIZE_MAIL);
+    MinWork M{};
+    M.p = q; M.Zp = q + n; M.Zt = q + 2 * n; M.sinfo = q + 3 * n;
+    M.bank = M.sinfo + MINIMIZE_STEP_INFO; M.rinfo0 = M.bank + 2 * MINIMIZE_STATE; M.rinfo = M.rinfo0 + AL_INFO;
+    M.phi_t = M.rinfo + AL_INFO; M.mail = M.phi_t + 4;
+    return M;
+}
+
+// The device routine both entry-point families run: everything on `st`, every pointer a device pointer.
+static void minimize_run(dto_handle* h, const ElimPlan& ep, const FeasiblePlan& fp, double sigma, const MinimizeArgs& a, hipStream_t st) {
+    const bool pre = h->newton_pairs > 0, has_rho = a.rho != nullptr;
+    const bool store_route = h->reduced_input_store && h->K >= 1;
+    const double* opt = a.opt.v;
+    // every workspace before anything is enqueued
+    const MinWork M = minimize_workspaces(h);
+    const FeasWork W = feasible_workspaces(h, fp, true);
+    block_workspaces(h, ep, 1, store_route);
+    if (pre) precond_kernel_args(h, a.harvest != 0);
+    else grow_workspace(h, h->d_newton_box, (size_t)newton_box_workspace_doubles(h->n_vars));
+    AlWork al{};
+    if (has_rho) al = auglag_workspaces(h, 1);
+    const double* mu = h->n_cons > 0 ? a.mu : nullptr;
+    const int outer = has_rho ? a.outer : 1;
+
+    auto merit = [&](const double* Zin, double* Zout, double* dphi) {   // dto_auglag_merit_dev's launches
+        if (!has_rho) {
+            feasible_merit(h, fp, W, Zin, sigma, mu, dphi, Zout, nullptr, st);
+            return;
+        }
+        feasible_trajectory(h, fp, Zin, Zout, st);
+        do_objective(h, Zout, W.f, st);
+        do_constraint(h, Zout, W.g, st);
+        auglag_row_pass(h, W.g, mu, a.rho, nullptr, nullptr, al.info, sigma, W.f, dphi, st);
+    };
+    auto step = [&](double delta) {   // dto_preconditioned_newton_step_dev's launches, or dto_auglag_newton_step_dev's
+        const NewtonBoxArgs b{a.mask, a.lo, a.hi, delta, opt[MIN_OPT_SHIFT], opt[MIN_OPT_RTOL], opt[MIN_OPT_ATOL], (int)opt[MIN_OPT_MAX_ITER],
+                              M.p, M.sinfo, nullptr, a.entry_state, M.Zp};
+        const double* m = mu;
+        if (has_rho) {
+            auglag_rows_at(h, al, a.Z, mu, a.rho, nullptr, st);
+            m = al.mu_eff;
+        }
+        if (pre) precond_step(h, ep, a.Z, sigma, m, b, a.harvest, st, has_rho ? &al : nullptr);
+        else newton_box_step(h, ep, a.Z, sigma, m, b, st, has_rho ? &al : nullptr);
+    };
+    auto mail = [&] {   // the one readback behind a launch of dto_minimize.hip
+        HIP_CHECK(hipMemcpyAsync(h->mailbox->minimize, M.mail, MINIMIZE_MAIL * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return h->mailbox->minimize;
+    };
+
+    KMinimize K{};
+    K.n = h->n_vars; K.n_dyn = h->n_dyn; K.n_cons = h->n_cons;
+    K.Z = a.Z; K.Zt = M.Zt; K.sinfo = M.sinfo; K.phi_t = M.phi_t; K.rinfo = M.rinfo; K.rinfo0 = M.rinfo0;
+    K.mu = a.mu; K.rho = a.rho; K.mu_eff = al.mu_eff; K.mail = M.mail; K.info = a.info; K.opt = a.opt;
+    int q = 0;   // launches of dto_minimize.hip so far: bank q % 2 is current
+    auto banks = [&] {
+        K.bank_in = M.bank + MINIMIZE_STATE * (q % 2);
+        K.bank_out = M.bank + MINIMIZE_STATE * ((q + 1) % 2);
+    };
+    const double scalars = 8.0 * (2.0 * MINIMIZE_STATE + MINIMIZE_INFO + MINIMIZE_HISTORY + MINIMIZE_MAIL + 5.0);
+    HIP_CHECK(hipMemsetAsync(M.bank, 0, 2 * MINIMIZE_STATE * sizeof(double), st));
+    if (has_rho) auglag_rows_at(h, al, a.Z, mu, a.rho, M.rinfo0, st);   // the first max viol
+    int64_t trial = 0;
+    for (int o = 0; o < outer; ++o) {
+        merit(a.Z, a.Z, M.bank + MINIMIZE_STATE * (q % 2) + MNS_PHI);   // Z becomes its feasible trajectory
+        double delta = opt[MIN_OPT_RADIUS0];
+        int stop = MIN_STOP_NONE;
+        for (int t = 0; t < a.trials && stop == MIN_STOP_NONE; ++t, ++trial) {
+            step(delta);
+            // the gradient test stands in front of the merit, so the host reads the step's ||g|| (the step has just waited for its own
+            // status: the stream is idle)
+            HIP_CHECK(hipMemcpyAsync(h->mailbox->minimize_step, M.sinfo, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            const bool gradient = h->mailbox->minimize_step[2] <= opt[MIN_OPT_GTOL];
+            if (!gradient) merit(M.Zp, M.Zt, M.phi_t);
+            banks();
+            K.row = a.history ? a.history + MINIMIZE_HISTORY * trial : nullptr;
+            K.F = MinimizeTrialFlags{q == 0, t == 0, t == a.trials - 1, gradient, has_rho, pre ? 16 : 12};
+            {   // bytes as if the trial is accepted: Zt read and Z written, and the scalars
+                ProfScope ps(h, st, CAT_MINIMIZE, (gradient ? 0.0 : 16.0 * (double)h->n_vars) + scalars);
+                launch_minimize_trial(st, K);
+            }
+            ++q;
+            const double* m = mail();
+            delta = m[MNM_DELTA];
+            stop = (int)m[MNM_STOP];
+        }
+        if (stop == MIN_STOP_NOT_FINITE || !has_rho) break;
+        auglag_rows_at(h, al, a.Z, mu, a.rho, M.rinfo, st);
+        banks();
+        K.row = a.outer_history ? a.outer_history + MINIMIZE_OUTER_HISTORY * o : nullptr;
+        K.first_outer = o == 0; K.last_outer = o == outer - 1;
+        {
+            ProfScope ps(h, st, CAT_MINIMIZE, 32.0 * (double)(h->n_cons - h->n_dyn) + scalars + 8.0 * 2.0 * AL_INFO);
+            launch_minimize_outer(st, K);
+        }
+        ++q;
+        if (mail()[MNM_STOP] != 0.0) break;
+    }
+}
+
+static std::string minimize_refusal(const dto_handle* h, const std::string& who, const double* Z, const double* mu, const double* rho,
+                                    const double* rho_host, const double* mask, const double* lo, const double* hi, const double* options,
+                                    int32_t outer, int32_t trials, int32_t harvest, const double* info, const double* history,
+                                    const double* outer_history, const double* entry_state, MinimizeOptions* out) {
+    static const char* names[MINIMIZE_OPTIONS] = {"radius0", "eta_accept", "eta_shrink", "eta_grow", "shrink_div", "grow_mul", "radius_max", "radius_min",
+                                                  "gtol", "ctol", "viol_div", "rho_mul", "shift", "rtol", "atol", "max_iter"};
+    if (!Z || !info) return who + ": Z and info are required (NULL given)";
+    if (outer < 1) return who + ": outer = " + std::to_string(outer) + ", at least 1 outer iteration is required";
+    if (trials < 1) return who + ": trials = " + std::to_string(trials) + ", at least 1 trial is required";
+    if (!rho && outer != 1) return who + ": outer = " + std::to_string(outer) + " without rho: without penalties there is one outer iteration";
+    if (rho && !mu) return who + ": rho is given and mu is NULL: the multipliers are an output of the outer loop";
+    MinimizeOptions O = minimize_default_options();
+    if (options)
+        for (int i = 0; i < MINIMIZE_OPTIONS; ++i) O.v[i] = options[i];
+    const double* v = O.v;
+    for (int i = 0; i < MINIMIZE_OPTIONS; ++i)
+        if (!(v[i] >= 0.0)) return who + ": option " + names[i] + " = " + std::to_string(v[i]) + " is negative or a NaN";
+    if (!(v[MIN_OPT_RADIUS0] > 0.0) || !std::isfinite(v[MIN_OPT_RADIUS0])) return who + ": option radius0 must be finite and > 0";
+    if (!(v[MIN_OPT_ETA_ACCEPT] <= v[MIN_OPT_ETA_SHRINK] && v[MIN_OPT_ETA_SHRINK] < v[MIN_OPT_ETA_GROW]))
+        return who + ": the options must satisfy 0 <= eta_accept <= eta_shrink < eta_grow";
+    if (!(v[MIN_OPT_SHRINK_DIV] > 1.0)) return who + ": option shrink_div must be > 1";
+    if (!(v[MIN_OPT_GROW_MUL] >= 1.0)) return who + ": option grow_mul must be >= 1";
+    if (!(v[MIN_OPT_MAX_ITER] <= 2147483647.0) || v[MIN_OPT_MAX_ITER] != std::floor(v[MIN_OPT_MAX_ITER]))
+        return who + ": option max_iter must be a whole number";
+    std::string bad = newton_refusal(who, Z, v[MIN_OPT_RADIUS0], v[MIN_OPT_SHIFT], v[MIN_OPT_RTOL], v[MIN_OPT_ATOL], (int32_t)v[MIN_OPT_MAX_ITER], Z, info);
+    if (!bad.empty()) return bad;
+    const size_t nv = (size_t)h->n_vars, nc = (size_t)h->n_cons, nh = MINIMIZE_HISTORY * (size_t)outer * (size_t)trials;
+    if (rho) {
+        bad = auglag_refusal(h, who, rho_host, {}, {});
+        if (!bad.empty()) return bad;
+    }
+    bad = precond_refusal(h, who, harvest);
+    if (!bad.empty()) return bad;
+    const AlSpan outs[] = {{"Z", Z, nv}, {"mu", rho ? mu : nullptr, nc}, {"rho", rho, nc}, {"info", info, MINIMIZE_INFO}, {"history", history, nh},
+                           {"outer_history", outer_history, MINIMIZE_OUTER_HISTORY * (size_t)outer}, {"entry_state", entry_state, nv}};
+    const AlSpan ins[] = {{"mu", rho ? nullptr : mu, nc}, {"free_mask", mask, nv}, {"lo", lo, nv}, {"hi", hi, nv}};
+    for (size_t i = 0; i < sizeof(outs) / sizeof(outs[0]); ++i) {
+        for (const AlSpan& in : ins)
+            if (spans_overlap(outs[i].p, outs[i].n, in.p, in.n)) return who + ": " + outs[i].name + " overlaps " + in.name;
+        for (size_t j = i + 1; j < sizeof(outs) / sizeof(outs[0]); ++j)
+            if (spans_overlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n)) return who + ": " + outs[i].name + " overlaps " + outs[j].name;
+    }
+    *out = O;
+    return "";
+}
+
+int dto_projected_minimize_dev(dto_handle* h, double* dZ, double sigma, double* dmu, double* drho, const double* dfree_mask, const double* dlo,
+                             const double* dhi, const double* options, int32_t outer, int32_t trials, int32_t harvest, double* dinfo,
+                             double* dhistory, double* douter_history, double* dentry_state, void* stream) {
+    const std::string who = "dto_projected_minimize_dev";
+    if (!h) return fail(nullptr, "null handle");
+    MinimizeOptions O{};
+    const std::string bad = minimize_refusal(h, who, dZ, dmu, drho, nullptr, dfree_mask, dlo, dhi, options, outer, trials, harvest, dinfo, dhistory,
+                                             douter_history, dentry_state, &O);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, true);
+        const FeasiblePlan& fp = feasible_args(h, who, true);
+        reduced_workspaces(h, ep);
+        const MinimizeArgs a{dZ, dmu, drho, dfree_mask, dlo, dhi, O, outer, trials, harvest, dinfo, dhistory, douter_history, dentry_state};
+        minimize_run(h, ep, fp, sigma, a, (hipStream_t)stream);
+    }, G_ASYNC, (hipStream_t)stream);
+}
+
+int dto_projected_minimize(dto_handle* h, double* Z, double sigma, double* mu, double* rho, const double* free_mask, const double* lo,
+                         const double* hi, const double* options, int32_t outer, int32_t trials, int32_t harvest, double* info, double* history,
+                         double* outer_history, double* entry_state) {
+    const std::string who = "dto_projected_minimize";
+    if (!h) return fail(nullptr, "null handle");
+    MinimizeOptions O{};
+    const std::string bad = minimize_refusal(h, who, Z, mu, rho, rho, free_mask, lo, hi, options, outer, trials, harvest, info, history,
+                                             outer_history, entry_state, &O);
+    if (!bad.empty()) return fail(h, bad);
+    return guarded(h, [&] {
+        const ElimPlan& ep = reduced_args(h, who, true);
+        const FeasiblePlan& fp = feasible_args(h, who, true);
+        reduced_workspaces(h, ep);
+        const size_t n = (size_t)h->n_vars, nc = (size_t)std::max<int64_t>(h->n_cons, 1), bytes = sizeof(double) * n;
+        const size_t nh = MINIMIZE_HISTORY * (size_t)outer * (size_t)trials, no = MINIMIZE_OUTER_HISTORY * (size_t)outer;
+        // every workspace before the uploads are enqueued
+        minimize_workspaces(h);
+        feasible_workspaces(h, fp, true);
+        block_workspaces(h, ep, 1, h->reduced_input_store && h->K >= 1);
+        if (h->newton_pairs > 0) precond_kernel_args(h, harvest != 0);
+        else grow_workspace(h, h->d_newton_box, (size_t)newton_box_workspace_doubles(h->n_vars));
+        if (rho) auglag_workspaces(h, 1);
+        double* q = grow_workspace(h, h->d_minimize_host, 5 * n + 2 * nc + MINIMIZE_INFO + nh + no);
+        double *dZ = q, *dmask = q + n, *dlo = q + 2 * n, *dhi = q + 3 * n, *des = q + 4 * n, *dmu = q + 5 * n, *drho = dmu + nc;
+        double *dinfo = drho + nc, *dhist = dinfo + MINIMIZE_INFO, *dohist = dhist + nh;
+        hipStream_t st = h->stream;
+        const bool has_mu = mu && h->n_cons > 0, has_rho = rho != nullptr;
+        HIP_CHECK(hipMemcpyAsync(dZ, Z, bytes, hipMemcpyHostToDevice, st));
+        if (has_mu) HIP_CHECK(hipMemcpyAsync(dmu, mu, sizeof(double) * nc, hipMemcpyHostToDevice, st));
+        if (has_rho && h->n_cons > 0) HIP_CHECK(hipMemcpyAsync(drho, rho, sizeof(double) * nc, hipMemcpyHostToDevice, st));
+        if (free_mask) HIP_CHECK(hipMemcpyAsync(dmask, free_mask, bytes, hipMemcpyHostToDevice, st));
+        if (lo) HIP_CHECK(hipMemcpyAsync(dlo, lo, bytes, hipMemcpyHostToDevice, st));
+        if (hi) HIP_CHECK(hipMemcpyAsync(dhi, hi, bytes, hipMemcpyHostToDevice, st));
+        // the rows of the histories the loop does not reach keep the caller's values
+        if (history) HIP_CHECK(hipMemcpyAsync(dhist, history, sizeof(double) * nh, hipMemcpyHostToDevice, st));
+        if (outer_history) HIP_CHECK(hipMemcpyAsync(dohist, outer_history, sizeof(double) * no, hipMemcpyHostToDevice, st));
+        if (entry_state) HIP_CHECK(hipMemcpyAsync(des, entry_state, bytes, hipMemcpyHostToDevice, st));
+        const MinimizeArgs a{dZ, has_mu ? dmu : nullptr, has_rho ? drho : nullptr, free_mask ? dmask : nullptr, lo ? dlo : nullptr, hi ? dhi : nullptr,
+                             O, outer, trials, harvest, dinfo, history ? dhist : nullptr, outer_history ? dohist : nullptr,
+                             entry_state ? des : nullptr};
+        minimize_run(h, ep, fp, sigma, a, st);
+        HIP_CHECK(hipMemcpyAsync(Z, dZ, bytes, hipMemcpyDeviceToHost, st));
+        if (has_rho && h->n_cons > 0) {
+            HIP_CHECK(hipMemcpyAsync(mu, dmu, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(rho, drho, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
+        }
+        HIP_CHECK(hipMemcpyAsync(info, dinfo, sizeof(double) * MINIMIZE_INFO, hipMemcpyDeviceToHost, st));
+        if (history) HIP_CHECK(hipMemcpyAsync(history, dhist, sizeof(double) * nh, hipMemcpyDeviceToHost, st));
+        if (outer_history) HIP_CHECK(hipMemcpyAsync(outer_history, dohist, sizeof(double) * no, hipMemcpyDeviceToHost, st));
+        if (entry_state) HIP_CHECK(hipMemcpyAsync(entry_state, des, bytes, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }, G_BLOCKING);
+}
+
 // ---- multi-GPU: ranges, gather plans, collectives (dto_comm.h)
 int dto_comm_unique_id(void* id128) {
     if (!id128) return fail(nullptr, "dto_comm_unique_id: null argument");
@@ -4333,6 +4574,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
         else if (!strcmp(name, "newton_box")) cat = CAT_NEWTON_BOX;
         else if (!strcmp(name, "auglag")) cat = CAT_AUGLAG;
         else if (!strcmp(name, "precond")) cat = CAT_PRECOND;
+        else if (!strcmp(name, "minimize")) cat = CAT_MINIMIZE;
         else if (!strcmp(name, "hess_product_setup")) {
             // host time of the products' index build (once per handle), no launches; third output: device bytes of the private
             // slab and the index
@@ -4363,7 +4605,7 @@ int dto_profile_get(dto_handle* h, const char* name, double* ms, int64_t* launch
             if (is_dynsolve_cat(r.cat) ? !(any_dynsolve || r.cat == cat) : any_dynsolve) continue;   // (nor are the solves)
             if (is_elim_cat(r.cat) && r.cat != cat) continue;
             if ((r.cat == CAT_REDUCED_PACK || r.cat == CAT_REDUCED_INPUT || r.cat == CAT_FEASIBLE || r.cat == CAT_NEWTON || r.cat == CAT_NEWTON_BOX ||
-                 r.cat == CAT_AUGLAG || r.cat == CAT_PRECOND) && r.cat != cat) continue;
+                 r.cat == CAT_AUGLAG || r.cat == CAT_PRECOND || r.cat == CAT_MINIMIZE) && r.cat != cat) continue;
             HIP_CHECK(hipEventSynchronize(r.b));
             float t = 0;
             HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));

@@ -210,6 +210,8 @@ struct PinnedMailbox {
     int32_t deferred_smax;         // the one-launch chain's squaring count of an enqueue-only call (smax_pending)
     double newton[2];              // the truncated-Newton step's (status, iterations) after every iteration
     double precond[3];             // the preconditioned step's (status, iterations, pairs taken) after every iteration
+    double minimize[4];            // the minimize call's (accepted / grew, delta for the next step, stop, phi) after every trial and outer iteration
+    double minimize_step[3];       // and the step's (status, iterations, ||g||) in front of a trial's merit: the gradient test
 };
 
 struct Workspace { double* p = nullptr; size_t cap = 0; };   // grow-only device buffer, capacity in doubles (grow_workspace, dto_engine.cpp)
@@ -354,6 +356,11 @@ struct dto_handle {
     // (precond_workspace_doubles); d_precond_host: the host-pointer forms' vectors.
     int newton_pairs = 0, pairs_bank = 0, pairs_count = 0, pairs_head = 0;
     dto::Workspace d_pairs, d_precond, d_precond_host;
+    // reduced-space minimize (dto_projected_minimize[_dev]; dto_minimize_plan.h, dto_minimize.hip).  d_minimize: p, Zp, Zt [n_vars] each,
+    // the step's info [16], the two banks of scalars [16] each, the two row passes' scalars [8] each, phi_t and the mailbox [4];
+    // d_minimize_host: the host-pointer form's Z, mask, lo, hi, entry_state [n_vars] each, mu, rho [n_cons] each, info [16] and the
+    // two histories.  Grow-only like the above.
+    dto::Workspace d_minimize, d_minimize_host;
     // augmented-Lagrangian terms (dto_auglag_*; dto_auglag_plan.h, dto_auglag.hip).  d_al: mu_eff, weight, g, the rows of the
     // single-column route and the host-pointer forms' mu and rho [n_cons] each, then info [8]; d_al_t: the planes t [W][n_vars] of the
     // Gauss-Newton term; d_al_host: the host-pointer forms' lam [N n_states].  d_al_eq: the equality flag of every non-dynamics row,

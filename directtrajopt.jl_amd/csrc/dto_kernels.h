@@ -6,6 +6,7 @@
 
 #include <cstdlib>
 
+#include "dto_minimize_plan.h" // options, flags and scalars of the reduced-space minimize call (KMinimize)
 #include "dto_reduced_plan.h"  // index plan of the reduced-space operators (KReduced)
 #include "dto_rollout_plan.h"  // index plan of the rollout's tree (KRollout's padding and level count)
 #include "dto_slab_layout.h"  // where every Jacobian and Hessian entry sits in its value slab
@@ -643,6 +644,26 @@ void launch_al_gn(hipStream_t st, const KProb& P, const KCon& C, int w, int64_t 
 void launch_al_scale(hipStream_t st, int64_t n, const double* weight, double* c);
 // q = q + t, n entries
 void launch_al_add(hipStream_t st, int64_t n, const double* t, double* q);
+
+// Reduced-space minimize (dto_minimize.hip; the rules, the scalars' layout, the history rows and the mailbox: dto_minimize_plan.h).
+// One record serves both launches; a launch reads bank_in and writes bank_out, the other bank.
+struct KMinimize {
+    int64_t n, n_dyn, n_cons;
+    double* Z;                        // [n]: the trial launch copies Zt into it where the trial is accepted
+    const double* Zt;
+    const double* bank_in;            // [MINIMIZE_STATE]
+    double* bank_out;
+    const double *sinfo, *phi_t;      // the trial: the step's info, the trial point's merit value (one double)
+    const double *rinfo, *rinfo0;     // the outer iteration: the row pass's scalars behind the inner loop, and the first pass's
+    double *mu, *rho;                 // [n_cons], the outer iteration: mu <- mu_eff and the new rho on the non-dynamics rows
+    const double* mu_eff;
+    double *row, *mail, *info;        // the history row (or null), the mailbox [4], info [16]
+    MinimizeOptions opt;
+    MinimizeTrialFlags F;
+    int first_outer, last_outer;
+};
+void launch_minimize_trial(hipStream_t st, const KMinimize& A);
+void launch_minimize_outer(hipStream_t st, const KMinimize& A);
 
 void launch_fill(hipStream_t st, double* p, int64_t n, double v);
 void launch_zero_runs(hipStream_t st, const int64_t* start, const int64_t* len, int64_t n_runs, double* dst);

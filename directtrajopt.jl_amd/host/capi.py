@@ -70,6 +70,11 @@ SOLVE_FORWARD, SOLVE_ADJOINT = 0, 1
 NEWTON_CONVERGED, NEWTON_BOUNDARY, NEWTON_NEG_CURVATURE, NEWTON_MAX_ITER, NEWTON_NOT_FINITE = 0, 1, 2, 3, 4
 # entry states of the bound-constrained step (DTO_BOX_* in include/dto_engine.h)
 BOX_FIXED, BOX_FREE, BOX_HELD_LOWER, BOX_HELD_UPPER, BOX_HIT_LOWER, BOX_HIT_UPPER = 0, 1, 2, 3, 4, 5
+# dto_projected_minimize: the exit status in info[0], the option names in index order (DTO_MIN_OPT_*) and their defaults
+MINIMIZE_CONVERGED, MINIMIZE_MAX_OUTER, MINIMIZE_MAX_TRIALS, MINIMIZE_RADIUS, MINIMIZE_NOT_FINITE = 0, 1, 2, 3, 4
+MINIMIZE_OPTIONS = ("radius0", "eta_accept", "eta_shrink", "eta_grow", "shrink_div", "grow_mul", "radius_max", "radius_min", "gtol", "ctol",
+                    "viol_div", "rho_mul", "shift", "rtol", "atol", "max_iter")
+MINIMIZE_DEFAULTS = (1.0, 0.1, 0.25, 0.75, 4.0, 2.0, float("inf"), 0.0, 0.0, 0.0, 4.0, 10.0, 0.0, 1e-6, 0.0, 50.0)
 
 H = C.c_void_p
 
@@ -166,6 +171,10 @@ SYMBOLS = {
     "dto_preconditioned_newton_step_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dto_projected_minimize": (C.c_int, [H, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                       C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "dto_projected_minimize_dev": (C.c_int, [H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dto_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dto_comm_create": (C.c_int, [H, C.c_void_p, C.c_int32, C.c_int32]),
     "dto_comm_set_ranges": (C.c_int, [H, C.c_int32, C.c_int32, c_int64_p, c_int64_p]),

@@ -905,6 +905,63 @@ class Evaluator:
             out += (zp,)
         return out
 
+    # ---- reduced-space minimize (include/dto_engine.h, "Reduced-space minimize")
+    @staticmethod
+    def _minimize_options(options):
+        unknown = sorted(set(options) - set(capi.MINIMIZE_OPTIONS))
+        if unknown:
+            raise TypeError(f"reduced_minimize: unknown option(s) {unknown}; the options are {list(capi.MINIMIZE_OPTIONS)}")
+        return np.array([float(options.get(k, d)) for k, d in zip(capi.MINIMIZE_OPTIONS, capi.MINIMIZE_DEFAULTS)], dtype=np.float64)
+
+    @staticmethod
+    def _minimize_info(raw):
+        return dict(status=int(raw[0]), outer=int(raw[1]), trials=int(raw[2]), accepted=int(raw[3]), phi_first=raw[4], phi=raw[5], delta=raw[6],
+                    gnorm=raw[7], max_viol_first=raw[8], max_viol=raw[9], grew=int(raw[10]), iterations=int(raw[11]), harvested=int(raw[12]),
+                    fallbacks=int(raw[13]), raw=raw)
+
+    def reduced_minimize(self, Z, sigma=1.0, mu=None, rho=None, lo=None, hi=None, free=None, outer=1, trials=10, harvest=False, history=False,
+                         states=False, **options):
+        """The trust-region loop around the step and the merit -- and with ``rho`` the outer multiplier / penalty loop around it -- as
+        one device-resident call (``dto_projected_minimize``): the README's loops with the rules of csrc/dto_minimize_plan.h.  The step is
+        ``preconditioned_newton_step`` where the option ``newton_pairs`` is above 0, else ``auglag_newton_step``; the merit is
+        ``auglag_merit``, the row pass ``auglag_rows``.  The inputs are copied.  ``options``: ``radius0``, ``eta_accept``,
+        ``eta_shrink``, ``eta_grow``, ``shrink_div``, ``grow_mul``, ``radius_max``, ``radius_min``, ``gtol``, ``ctol``, ``viol_div``,
+        ``rho_mul`` and the step's ``shift``, ``rtol``, ``atol``, ``max_iter`` (defaults: ``capi.MINIMIZE_DEFAULTS``).
+        Returns (Z, info[, mu, rho][, history, outer_history][, states]): mu and rho where ``rho`` is given; info a dict with
+        ``status`` (``capi.MINIMIZE_*``), ``outer``, ``trials``, ``accepted``, ``phi_first``, ``phi``, ``delta``, ``gnorm``,
+        ``max_viol_first``, ``max_viol``, ``grew``, ``iterations`` (the steps' CG iterations, summed), ``harvested``, ``fallbacks`` and
+        ``raw``; history (trials run, 8): ratio, accepted, delta, phi_t, predicted, the step's status, iterations, ||g||;
+        outer_history (outer iterations run, 4): max viol, grew, active rows, P; states: the last step's entry states."""
+        Z = np.array(self._Z(Z), dtype=np.float64)
+        mu, rho = self._mu_rho(mu, rho)
+        mu = None if mu is None else np.array(mu, dtype=np.float64)
+        rho = None if rho is None else np.array(rho, dtype=np.float64)
+        if free is not None:
+            free = _in(free, self.n_variables, "free")
+        if lo is not None:
+            lo = _in(lo, self.n_variables, "lo")
+        if hi is not None:
+            hi = _in(hi, self.n_variables, "hi")
+        outer, trials = int(outer), int(trials)
+        opts = self._minimize_options(options)
+        opt = lambda a: None if a is None else _dp(a)
+        raw = np.full(16, np.nan)
+        hist = np.full((max(outer, 0) * max(trials, 0), 8), np.nan) if history else None
+        ohist = np.full((max(outer, 0), 4), np.nan) if history else None
+        es = np.full(self.n_variables, np.nan) if states else None
+        self._check(self._lib.dto_projected_minimize(self._h, _dp(Z), float(sigma), opt(mu), opt(rho), opt(free), opt(lo), opt(hi), _dp(opts), outer,
+                                                   trials, int(bool(harvest)), _dp(raw), opt(hist), opt(ohist), opt(es)))
+        info = self._minimize_info(raw)
+        out = (Z, info)
+        if rho is not None:
+            out += (mu, rho)
+        if history:
+            passes = 0 if rho is None else info["outer"] - (info["status"] == capi.MINIMIZE_NOT_FINITE)   # NOT_FINITE: no row pass behind it
+            out += (hist[:info["trials"]], ohist[:passes])
+        if states:
+            out += (es,)
+        return out
+
     def independent_entries(self):
         """C: the entries of Z that are no state of a knot 2 .. N (controls, timesteps, times, the states of knot 1, globals),
         ascending, 0-based -- the variables of the reduced problem."""
@@ -1096,6 +1153,16 @@ class Evaluator:
                                                                  dlo or None, dhi or None, float(radius), float(shift), float(rtol),
                                                                  float(atol), int(max_iter), int(bool(harvest)), dp or None, dinfo or None,
                                                                  dtrace or None, dstates or None, dZp or None, stream))
+
+    def reduced_minimize_dev(self, dZ, sigma, dmu, drho, dfree, dlo, dhi, outer, trials, harvest, dinfo, dhistory=0, douter_history=0, dstates=0,
+                             stream=0, **options):
+        """``reduced_minimize`` on device pointers: dZ, dmu and drho are updated in place on ``stream`` (dmu may be 0 only where drho
+        is); dinfo 16 doubles, dhistory (outer * trials, 8), douter_history (outer, 4), dstates (n_variables) or 0.  The call waits on
+        ``stream`` for its own mailbox after every trial; ``options`` as ``reduced_minimize`` (they are read on the host)."""
+        opts = self._minimize_options(options)
+        self._check(self._lib.dto_projected_minimize_dev(self._h, dZ or None, float(sigma), dmu or None, drho or None, dfree or None, dlo or None,
+                                                       dhi or None, opts.ctypes.data, int(outer), int(trials), int(bool(harvest)), dinfo or None,
+                                                       dhistory or None, douter_history or None, dstates or None, stream))
 
     # ---- multi-GPU: the engine's own collectives (RCCL over xGMI behind the C ABI; include/dto_engine.h, "Multi-GPU")
     @staticmethod

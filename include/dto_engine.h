@@ -834,6 +834,78 @@ int dto_preconditioned_newton_step_dev(dto_handle* h, const double* dZ, double s
                                        int32_t max_iter, int32_t harvest, double* dp, double* dinfo, double* dtrace, double* dentry_state,
                                        double* dZp, void* stream);
 
+/* ---- Reduced-space minimize: the trust-region loop around the step and the merit above, and with penalties the outer multiplier /
+ * penalty loop around that, as ONE call that stays on the device.  The rules, once, in plain C++: csrc/dto_minimize_plan.h (the kernels
+ * of csrc/dto_minimize.hip, the host routine and a g++-built test compile that text); every operation is rounded on its own, so a NumPy
+ * restatement around the public step, merit and row pass has the same bits.  The call composes the existing routines unchanged:
+ *   step    dto_preconditioned_newton_step where the capacity "newton_pairs" is above 0, else dto_auglag_newton_step (rho == NULL:
+ *           dto_projected_newton_step_box), with radius = delta and the options' shift, rtol, atol, max_iter;
+ *   merit   dto_auglag_merit (rho == NULL: dto_feasible_merit);      rows    dto_auglag_rows.
+ * A trial:  (info, Zp) = step(Z, delta).  info[2] = ||g|| <= gtol ends the inner loop with GRADIENT before any merit is evaluated; the
+ *   step is discarded and the trial logged as rejected.  Otherwise (phi_t, Zt) = merit(Zp) and, minimize_trial_decide,
+ *     ratio = (phi - phi_t) / predicted;   accepted = ratio > eta_accept: Z = Zt, phi = phi_t;
+ *     ratio < eta_shrink: delta / shrink_div;  else ratio > eta_grow and the step's status != DTO_NEWTON_CONVERGED:
+ *     min(delta * grow_mul, radius_max);  else delta.
+ *   The step's status DTO_NEWTON_NOT_FINITE, or a ratio that is not finite (predicted == 0 among these), ends the call with NOT_FINITE:
+ *   the trial is rejected and delta stays.  A new delta below radius_min ends the inner loop with RADIUS, the last trial with MAX_TRIALS.
+ * An outer iteration (rho != NULL; without rho there is exactly one, with no row pass and no outer decision):  phi, Z <- merit(Z), so Z
+ *   becomes its feasible trajectory; delta = radius0; up to `trials` trials; then, unless the call ended NOT_FINITE, the row pass at Z
+ *   gives mu_eff and max viol, mu <- mu_eff on the non-dynamics rows, and minimize_outer_decide:
+ *     grew = !(new_viol <= viol / viol_div)  (a NaN grows the penalty): rho_r <- rho_r * rho_mul on the rows with rho_r != 0;
+ *   viol = new_viol.  The first viol is the row pass's at the caller's Z.  Dynamics rows of mu and rho are never written.
+ * Exit status, info[0]:  DTO_MINIMIZE_CONVERGED  the inner loop ended with GRADIENT and, with rho, max viol <= ctol;
+ *   DTO_MINIMIZE_MAX_OUTER  `outer` ran out;  DTO_MINIMIZE_NOT_FINITE;  and without rho only DTO_MINIMIZE_MAX_TRIALS, DTO_MINIMIZE_RADIUS.
+ *   With gtol = ctol = radius_min = 0, the defaults, the loop runs outer x trials trials (unless a gradient norm is exactly 0).
+ * options [16] (NULL: the defaults), indices DTO_MIN_OPT_*:  radius0 (1), eta_accept (0.1), eta_shrink (0.25), eta_grow (0.75),
+ *   shrink_div (4), grow_mul (2), radius_max (+inf), radius_min (0), gtol (0), ctol (0), viol_div (4), rho_mul (10), and the step's
+ *   shift (0), rtol (1e-6), atol (0), max_iter (50).  The defaults make the loops of the README, bit for bit.
+ * info [16]:  status, outer iterations, trials, accepted trials, phi first, phi last, the last delta, the last step's ||g||, max viol
+ *   first, max viol last, penalty increases, the sum of the steps' CG iterations, pairs harvested, fallbacks, 0, 0.
+ * history [outer * trials][8] (or NULL), one row per trial run, consecutive:  ratio, accepted, the delta used, phi_t, predicted, the
+ *   step's status, iterations and ||g||  (a GRADIENT trial: ratio 0, phi_t = phi).  outer_history [outer][4] (or NULL):  max viol, grew,
+ *   active rows, P.  Rows the loop does not reach keep the caller's values.  entry_state [n_vars] (or NULL): the last step's.
+ * Z, mu and rho are in / out (mu may be NULL only where rho is; without rho mu is an input).  harvest as in the preconditioned step.
+ * Costs.  Two kernels of dto_minimize.hip, profile name "minimize": one launch behind every trial (every workgroup takes the decision
+ *   itself and copies its slice of Zt into Z where the trial is accepted; workgroup 0 writes the scalars, the history row and a
+ *   32-byte mailbox), one behind every outer iteration (mu, rho, the scalars).  The scalars live in two banks, so no launch reads a
+ *   scalar it writes.  The host reads the mailbox (accepted, delta, stop, phi) once per trial -- it needs delta as the next step's radius
+ *   -- and the step's 24 bytes (status, iterations, ||g||) in front of the merit for the gradient test; no vector crosses the bus
+ *   between the upload and the download of the host-pointer form.  A rejected trial leaves Z's contents alone, so the next step finds
+ *   its kept points and rebuilds nothing.
+ * Refused with text, with nothing enqueued: what the composed calls refuse (sharded handles among these); outer < 1 or trials < 1;
+ *   rho == NULL with outer != 1; rho != NULL with mu == NULL; radius0 <= 0 or not finite; a negative or NaN option; not
+ *   0 <= eta_accept <= eta_shrink < eta_grow; shrink_div <= 1 or grow_mul < 1; a max_iter that is no whole number; harvest with
+ *   capacity 0; outputs that overlap inputs or each other.  The _dev form takes device pointers, updates dZ, dmu and drho in place on
+ *   `stream` and waits for its mailbox on it; `options` is a host pointer in both forms; errors are deferred as for every _dev call. */
+#define DTO_MINIMIZE_CONVERGED 0
+#define DTO_MINIMIZE_MAX_OUTER 1
+#define DTO_MINIMIZE_MAX_TRIALS 2
+#define DTO_MINIMIZE_RADIUS 3
+#define DTO_MINIMIZE_NOT_FINITE 4
+#define DTO_MIN_OPT_RADIUS0 0
+#define DTO_MIN_OPT_ETA_ACCEPT 1
+#define DTO_MIN_OPT_ETA_SHRINK 2
+#define DTO_MIN_OPT_ETA_GROW 3
+#define DTO_MIN_OPT_SHRINK_DIV 4
+#define DTO_MIN_OPT_GROW_MUL 5
+#define DTO_MIN_OPT_RADIUS_MAX 6
+#define DTO_MIN_OPT_RADIUS_MIN 7
+#define DTO_MIN_OPT_GTOL 8
+#define DTO_MIN_OPT_CTOL 9
+#define DTO_MIN_OPT_VIOL_DIV 10
+#define DTO_MIN_OPT_RHO_MUL 11
+#define DTO_MIN_OPT_SHIFT 12
+#define DTO_MIN_OPT_RTOL 13
+#define DTO_MIN_OPT_ATOL 14
+#define DTO_MIN_OPT_MAX_ITER 15
+#define DTO_MIN_OPTIONS 16
+int dto_projected_minimize(dto_handle* h, double* Z, double sigma, double* mu, double* rho, const double* free_mask, const double* lo,
+                         const double* hi, const double* options, int32_t outer, int32_t trials, int32_t harvest, double* info, double* history,
+                         double* outer_history, double* entry_state);
+int dto_projected_minimize_dev(dto_handle* h, double* dZ, double sigma, double* dmu, double* drho, const double* dfree_mask, const double* dlo,
+                             const double* dhi, const double* options, int32_t outer, int32_t trials, int32_t harvest, double* dinfo,
+                             double* dhistory, double* douter_history, double* dentry_state, void* stream);
+
 /* ---- Multi-GPU: knot ranges sharded over the GPUs of one node, one process (or thread with its own device) per GPU
  * (BASELINE configs[3] "knot range sharded across 8 x MI355X (RCCL allgather)").  The engine owns the RCCL
  * communicator (SURVEY.md §8b "Ownership").  No callback needs a collective: every rank's Jacobian / Hessian / gradient
@@ -1018,6 +1090,9 @@ int dto_profile_reset(dto_handle* h);
  * "precond" (dto_preconditioned_newton_step, dto_newton_precondition, dto_newton_pairs_push_dev: every launch of theirs that is no
  * product -- the Gram pass, the preparation, the multi-dot and combination passes, the step and the direction, and the box step's start
  * and curvature pass where they run inside; third output: BYTES as executed; it feeds no other name, "all" included).
+ * "minimize" (dto_projected_minimize and its _dev form: the two kernels of dto_minimize.hip, one launch per trial and one per outer
+ * iteration; third output: BYTES, a trial's as if it is accepted; it feeds no other name, "all" included; the step, the merit and the
+ * row pass inside count under their own names).
  * The block products count under "hess_product", "reduced_pack" and "reduced_input" too, one launch per chunk where a single product
  * has one, with bytes as executed: matrix bytes once per tile or chunk, vector bytes per column.
  * Returns accumulated device milliseconds, launches and algorithmic FLOPs of those launches -- for the four assembly names and "share" the

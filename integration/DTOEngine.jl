@@ -1273,6 +1273,70 @@ function preconditioned_newton_step_dev!(ev::GPUEvaluator, dp::Ptr{Float64}, din
                                                             dZp::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
 end
 
+# ---- reduced-space minimize (include/dto_engine.h, "Reduced-space minimize") ------------------------------------------------
+const DTO_MINIMIZE_CONVERGED = Int32(0)    # reduced_minimize!: status in info[1]
+const DTO_MINIMIZE_MAX_OUTER = Int32(1)
+const DTO_MINIMIZE_MAX_TRIALS = Int32(2)
+const DTO_MINIMIZE_RADIUS = Int32(3)
+const DTO_MINIMIZE_NOT_FINITE = Int32(4)
+const DTO_MIN_OPTIONS = Int32(16)
+# the options in index order (DTO_MIN_OPT_*, 0-based in the header) and their defaults
+const MINIMIZE_OPTION_NAMES = (:radius0, :eta_accept, :eta_shrink, :eta_grow, :shrink_div, :grow_mul, :radius_max, :radius_min, :gtol, :ctol,
+                               :viol_div, :rho_mul, :shift, :rtol, :atol, :max_iter)
+const MINIMIZE_OPTION_DEFAULTS = (1.0, 0.1, 0.25, 0.75, 4.0, 2.0, Inf, 0.0, 0.0, 0.0, 4.0, 10.0, 0.0, 1e-6, 0.0, 50.0)
+
+function minimize_options(options)
+    for k in keys(options)
+        k in MINIMIZE_OPTION_NAMES || error("reduced_minimize!: unknown option $k; the options are $(MINIMIZE_OPTION_NAMES)")
+    end
+    return Float64[Float64(get(options, k, d)) for (k, d) in zip(MINIMIZE_OPTION_NAMES, MINIMIZE_OPTION_DEFAULTS)]
+end
+
+# The trust-region loop around the step and the merit -- with ρ the outer multiplier / penalty loop around it -- as one device-resident
+# call.  Z (and with ρ: μ, ρ) are updated IN PLACE; returns (info [16], history [8 x trials run], outer_history [4 x outer], states).
+function reduced_minimize!(ev::GPUEvaluator, Z::Vector{Float64}; σ::Float64 = 1.0, μ::Union{Nothing,Vector{Float64}} = nothing,
+                           ρ::Union{Nothing,Vector{Float64}} = nothing, lo::Union{Nothing,AbstractVector{Float64}} = nothing,
+                           hi::Union{Nothing,AbstractVector{Float64}} = nothing, free::Union{Nothing,AbstractVector{Float64}} = nothing,
+                           outer::Integer = 1, trials::Integer = 10, harvest::Bool = false, options...)
+    reduced_check_lengths(ev, "reduced_minimize!", Z, μ, free)
+    auglag_check_lengths(ev, "reduced_minimize!", Z, μ, ρ)
+    (lo === nothing || length(lo) == ev.n_variables) || error("reduced_minimize!: lo has $(length(lo)) entries, n_variables = $(ev.n_variables)")
+    (hi === nothing || length(hi) == ev.n_variables) || error("reduced_minimize!: hi has $(length(hi)) entries, n_variables = $(ev.n_variables)")
+    (outer >= 1 && trials >= 1) || error("reduced_minimize!: outer = $outer, trials = $trials, at least 1 of each is required")
+    opts = minimize_options(options)
+    μv = μ === nothing ? Float64[] : μ
+    ρv = ρ === nothing ? Float64[] : ρ
+    fv = free === nothing ? Float64[] : Vector{Float64}(free)
+    lov = lo === nothing ? Float64[] : Vector{Float64}(lo)
+    hiv = hi === nothing ? Float64[] : Vector{Float64}(hi)
+    info, history, outer_history = fill(NaN, 16), fill(NaN, 8, Int(outer) * Int(trials)), fill(NaN, 4, Int(outer))
+    states = fill(NaN, ev.n_variables)
+    no, nt, hv = Int32(outer), Int32(trials), Int32(harvest)
+    GC.@preserve Z μv ρv fv lov hiv opts info history outer_history states begin
+        μp, ρp, fp, lop, hip = auglag_ptr(μ, μv), auglag_ptr(ρ, ρv), auglag_ptr(free, fv), auglag_ptr(lo, lov), auglag_ptr(hi, hiv)
+        check(ev, @ccall lib.dto_projected_minimize(ev.handle::Ptr{Cvoid}, Z::Ptr{Float64}, σ::Float64, μp::Ptr{Float64}, ρp::Ptr{Float64},
+                                                  fp::Ptr{Float64}, lop::Ptr{Float64}, hip::Ptr{Float64}, opts::Ptr{Float64}, no::Int32,
+                                                  nt::Int32, hv::Int32, info::Ptr{Float64}, history::Ptr{Float64},
+                                                  outer_history::Ptr{Float64}, states::Ptr{Float64})::Cint)
+    end
+    passes = ρ === nothing ? 0 : Int(info[2]) - (Int(info[1]) == DTO_MINIMIZE_NOT_FINITE ? 1 : 0)
+    return info, history[:, 1:Int(info[3])], outer_history[:, 1:passes], states
+end
+
+# device pointers, updated in place on `stream`; opts: the sixteen options on the HOST (as minimize_options builds them)
+function reduced_minimize_dev!(ev::GPUEvaluator, dZ::Ptr{Float64}, dinfo::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dρ::Ptr{Float64},
+                               dfree::Ptr{Float64}, dlo::Ptr{Float64}, dhi::Ptr{Float64}, opts::Vector{Float64}, outer::Integer, trials::Integer,
+                               harvest::Bool, dhistory::Ptr{Float64}, douter_history::Ptr{Float64}, dstates::Ptr{Float64}, stream::Ptr{Cvoid})
+    length(opts) == 16 || error("reduced_minimize_dev!: opts has $(length(opts)) entries, 16 are required (minimize_options)")
+    no, nt, hv = Int32(outer), Int32(trials), Int32(harvest)
+    GC.@preserve opts begin
+        check(ev, @ccall lib.dto_projected_minimize_dev(ev.handle::Ptr{Cvoid}, dZ::Ptr{Float64}, σ::Float64, dμ::Ptr{Float64}, dρ::Ptr{Float64},
+                                                      dfree::Ptr{Float64}, dlo::Ptr{Float64}, dhi::Ptr{Float64}, opts::Ptr{Float64}, no::Int32,
+                                                      nt::Int32, hv::Int32, dinfo::Ptr{Float64}, dhistory::Ptr{Float64},
+                                                      douter_history::Ptr{Float64}, dstates::Ptr{Float64}, stream::Ptr{Cvoid})::Cint)
+    end
+end
+
 # row bounds handed to the solver (src/solvers/solve.jl:30-65)
 function constraint_bounds(ev::GPUEvaluator)
     lo = Vector{Float64}(undef, ev.n_constraints)

@@ -41,6 +41,13 @@ iterations (rtol = 0, shift from the power iterations with the augmented operato
 of one call (device milliseconds, launches, bytes, and all three per iteration), the yardstick's "newton_box" profile, the active rows, and
     excess_ms = (auglag step - yardstick) - auglag device ms - (yardstick max - yardstick min)
 
+``--minimize`` measures the reduced-space minimize call (Evaluator.reduced_minimize_dev, ten trials, no bounds, no penalties, the
+tool's shift, rtol = 1e-6, max_iter = the largest of ``--iters``) beside the same loop written in Python over the existing _dev entry
+points -- the step, the merit, torch ``.item()`` reads of the step's info and of phi, the decisions on the host: what a user wrote before
+the call existed.  Calls alternate, medians of ``--reps`` with the yardstick's min .. max; ms per trial for both, the "minimize" profile
+name's device time and bytes per trial, and whether the call's time is at most the yardstick's plus that device time plus the yardstick's
+spread.  Then, with "newton_pairs" = 8, ``harvest=True`` against capacity 0 on the same run: total CG iterations and ms over the trials.
+
 ``--precond`` measures the L-BFGS-preconditioned step (Evaluator.preconditioned_newton_step_dev, option "newton_pairs" = 8) without
 bounds.  The YARDSTICK is the box step (reduced_newton_step_box_dev); rtol = 0, so every call runs exactly ``max_iter`` iterations.
 Beside it, calls alternating,
@@ -56,6 +63,7 @@ One JSON line per shape.
     python tools/newton_time.py --box                 # the bound-constrained step beside the existing one
     python tools/newton_time.py --auglag              # the augmented-Lagrangian step beside the bound-constrained one
     python tools/newton_time.py --precond             # the preconditioned step beside the bound-constrained one
+    python tools/newton_time.py --minimize            # the one-call trust-region loop beside the loop over the _dev entry points
     python tools/newton_time.py --shapes 128x1000 --reps 9 --iters 10,30
 """
 import argparse
@@ -322,6 +330,104 @@ def measure_precond(n, N, drives, scale, reps, iters, m=8):
         ev.close()
 
 
+def measure_minimize(n, N, drives, scale, reps, iters, m=8, trials=10):
+    """the one-call trust-region loop (Evaluator.reduced_minimize_dev) beside the same loop written in Python over the _dev entry points
+    with torch .item() reads (the yardstick), no bounds, no penalties; then harvested pairs against capacity 0 on the same run"""
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    prob = dto_amd.host.synthetic.multi_ket_problem(n, 1, drives, N, seed=42, u_bound=4.0, scale=scale or None)
+    ev = dto_amd.Evaluator(prob)
+    ev.set_option("reduced_input_store", 1)
+    out = {"mode": "minimize", "n": n, "knots": N, "drives": drives, "scale": scale, "reps": reps, "sigma": SIGMA, "trials": trials,
+           "route": "reduced_input_store"}
+    try:
+        Zh = np.ascontiguousarray(prob.trajectory.vec(), dtype=np.float64)
+        Z0 = torch.from_numpy(Zh).to(dev)
+        gen = torch.Generator(device=dev); gen.manual_seed(7)
+        mu = torch.randn(ev.n_constraints, dtype=torch.float64, device=dev, generator=gen)
+        f64 = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
+        nv = ev.n_variables
+        y, p, Zc, Zp, Zt, info, minfo, dphi, dphit = f64(nv), f64(nv), f64(nv), f64(nv), f64(nv), f64(16), f64(16), f64(1), f64(1)
+        mask = torch.zeros(nv, dtype=torch.float64, device=dev)
+        mask[torch.from_numpy(ev.independent_entries()).to(dev)] = 1.0
+        out["n_variables"], out["chunks"] = nv, -(-nv // 256)
+        v = torch.randn(nv, dtype=torch.float64, device=dev, generator=gen) * mask
+        top = 0.0
+        for _ in range(8):
+            v = v / torch.linalg.norm(v)
+            ev.reduced_hessian_product_dev(Z0.data_ptr(), SIGMA, mu.data_ptr(), v.data_ptr(), y.data_ptr(), st)
+            top = max(top, abs(float(torch.dot(v, y))))
+            v = y.clone()
+        shift = 2.0 * top
+        out["shift"] = shift
+        max_iter = max(iters)
+        out["max_iter"] = max_iter
+        log = {}
+
+        def hand(harvest=False):
+            """the loop a user writes today: the engine's step and merit on device pointers, the decisions on the host"""
+            pairs = ev.newton_pairs_info()[1] > 0
+            Zc.copy_(Z0)
+            ev.feasible_merit_dev(Zc.data_ptr(), SIGMA, mu.data_ptr(), dphi.data_ptr(), Zc.data_ptr(), 0, st)
+            phi, delta, cg, acc = dphi.item(), 1.0, 0, 0
+            for _ in range(trials):
+                if pairs:
+                    ev.preconditioned_newton_step_dev(Zc.data_ptr(), SIGMA, mu.data_ptr(), 0, 0, 0, 0, delta, shift, 1e-6, 0.0, max_iter, harvest,
+                                                      p.data_ptr(), info.data_ptr(), 0, 0, Zp.data_ptr(), st)
+                else:
+                    ev.reduced_newton_step_box_dev(Zc.data_ptr(), SIGMA, mu.data_ptr(), 0, 0, 0, delta, shift, 1e-6, 0.0, max_iter, p.data_ptr(),
+                                                   info.data_ptr(), 0, 0, Zp.data_ptr(), st)
+                status, its, predicted = info[0].item(), info[1].item(), info[6].item()
+                ev.feasible_merit_dev(Zp.data_ptr(), SIGMA, mu.data_ptr(), dphit.data_ptr(), Zt.data_ptr(), 0, st)
+                phi_t = dphit.item()
+                ratio = (phi - phi_t) / predicted
+                cg += int(its)
+                if ratio > 0.1:
+                    Zc.copy_(Zt)
+                    phi, acc = phi_t, acc + 1
+                if ratio < 0.25:
+                    delta /= 4
+                elif ratio > 0.75 and status != dto_amd.capi.NEWTON_CONVERGED:
+                    delta *= 2
+            log["hand"] = dict(phi=phi, iterations=cg, accepted=acc)
+
+        def call(harvest=False):
+            Zc.copy_(Z0)
+            ev.reduced_minimize_dev(Zc.data_ptr(), SIGMA, mu.data_ptr(), 0, 0, 0, 0, 1, trials, harvest, minfo.data_ptr(), stream=st, shift=shift,
+                                    max_iter=max_iter)
+
+        pair = alternating(hand, call, reps)
+        hand(); call(); torch.cuda.synchronize()
+        raw = minfo.cpu().numpy()
+        pair.update(status=int(raw[0]), trials_run=int(raw[2]), accepted=int(raw[3]), iterations=int(raw[11]), phi_first=float(raw[4]), phi=float(raw[5]),
+                    yardstick=log["hand"], same_phi_as_yardstick=bool(raw[5] == log["hand"]["phi"]))
+        k = max(int(raw[2]), 1)
+        ev.profile_enable(True); ev.profile_reset(); call(); torch.cuda.synchronize()
+        ms, launches, nbytes = ev.profile_get("minimize")
+        ev.profile_enable(False)
+        pair["minimize_profile"] = {"ms": round(ms, 4), "launches": launches, "bytes": nbytes, "ms_per_trial": round(ms / k, 5), "bytes_per_trial": nbytes / k}
+        pair["yardstick_ms_per_trial"], pair["call_ms_per_trial"] = round(pair["yardstick_ms"] / trials, 4), round(pair["step_ms"] / k, 4)
+        spread = pair["yardstick_max_ms"] - pair["yardstick_min_ms"]
+        pair["claim_call_le_yardstick_plus_minimize_plus_spread"] = bool(pair["step_ms"] <= pair["yardstick_ms"] + ms + spread)
+        out["loop"] = pair
+        # harvested pairs against capacity 0 on the same run: total CG iterations and wall time of the one call
+        res = {}
+        for key, cap, harvest in (("capacity_0", 0, False), (f"pairs_{m}_harvest", m, True)):
+            ev.set_option("newton_pairs", cap)
+            fn = lambda: (ev.newton_pairs_clear(), call(harvest))
+            for _ in range(2):
+                event_ms(fn)
+            t = [event_ms(fn) for _ in range(reps)]
+            raw = minfo.cpu().numpy()
+            res[key] = {"ms": round(statistics.median(t), 4), "min_ms": round(min(t), 4), "max_ms": round(max(t), 4), "iterations": int(raw[11]),
+                        "accepted": int(raw[3]), "harvested": int(raw[12]), "fallbacks": int(raw[13]), "phi": float(raw[5]), "status": int(raw[0])}
+        ev.set_option("newton_pairs", 0)
+        out["harvest_over_trials"] = res
+        return out
+    finally:
+        ev.close()
+
+
 def measure(n, N, drives, scale, reps, iters):
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -414,8 +520,9 @@ def main():
     ap.add_argument("--box", action="store_true", help="measure the bound-constrained step beside the existing step")
     ap.add_argument("--auglag", action="store_true", help="measure the augmented-Lagrangian step beside the bound-constrained step")
     ap.add_argument("--precond", action="store_true", help="measure the L-BFGS-preconditioned step beside the bound-constrained step")
+    ap.add_argument("--minimize", action="store_true", help="measure the one-call trust-region loop beside the loop over the _dev entry points")
     a = ap.parse_args()
-    run = measure_precond if a.precond else measure_auglag if a.auglag else measure_box if a.box else measure
+    run = measure_minimize if a.minimize else measure_precond if a.precond else measure_auglag if a.auglag else measure_box if a.box else measure
     for s in a.shapes.split(","):
         n, N = (int(x) for x in s.lower().split("x"))
         print(json.dumps(run(n, N, a.drives, a.scale, a.reps, [int(i) for i in a.iters.split(",")])), flush=True)
